@@ -12,8 +12,13 @@ The real file is not available offline, so the input is the synthetic stand-in o
 One STEP = the reference's whole ingest of that file through its launch surface: `kernel` (reset) + republishing the
 36 ring slots + two `kernel_construct` launches (20 + 16 batches, main_progressive_octree.cpp:364-428 /
 progressive_octree_voxels.cu:883).  value = points inserted per second over exactly K such steps (max over ranks).
-The raster half of the metric is measured right after, on the octree of the last step: K frames of `kernel_render` at
-1920x1080 (HQS, the reference's default, and plain) and reported under "raster".
+The raster half of the metric is measured right after (with --full), on the octree of the last step: K frames of `kernel_render`
+at 1920x1080 (HQS, the reference's default, and plain) and reported under "raster".
+
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs DIR) and prints the line.  Everything else
+(the raster half, the other host legs, per-kernel and roofline passes, the loader row, the coalesced mode, the CPU baselines and the
+reference B0, quoted profiles, the collective checks of N>1) runs with --full only.
+--dump-outputs DIR writes what the last timed step built, as float64 .npy files (dump_outputs below).
 
 N>1 (weak scaling, BASELINE config 4's shape): ONE global cube over a terrain of N tiles of 36 M points each.  Every rank generates its
 tile ON THE DEVICE (simlod_generate_terrain), the ranks histogram the points over the 512 level-3 cells of the global cube, the cells
@@ -48,6 +53,9 @@ def parse():
     ap.add_argument("--raster-presets", default="bird,close", help="camera presets of the raster half (tools/profile.sh collects counters for the bird preset alone)")
     ap.add_argument("--stream", action="store_true", help="N=1 too: device-generated points streamed through the 50-slot ring with the reference's back-pressure (config 4's per-rank path)")
     ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: raster, other host legs, per-kernel / roofline passes, loader row, "
+                                                        "coalesced mode, CPU baselines, quoted profiles, collective checks (off: a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step built (octree + Stats) to DIR/<name>.npy, float64")
     ap.add_argument("--cpu-points", type=int, default=36_000_000, help="bounded sample for the CPU baseline (the port finishes all 36 M in a few seconds)")
     ap.add_argument("--b0-points", type=int, default=36_000_000, help="how much of the same terrain B0 — the reference's own sources as host code — is given (it stops after 25 s)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -86,6 +94,38 @@ def collect_profile(L):
     cnt = ctypes.c_int(0)
     L.simlod_profile_collect(ctypes.byref(buf), 64, ctypes.byref(cnt))
     return {buf[i].name.decode(): (int(buf[i].launches), float(buf[i].total_ms)) for i in range(cnt.value)}
+
+
+# --dump-outputs: what the timed path hands its caller — the octree kernel_construct built and its Stats.  Node slots and the samples
+# inside a node's chunk lists are ordered by the device's scheduling, so the octree is written as the canonical, order-independent
+# description the parity tests compare (oracle.dump_image: one row per node, sorted by (level, X, Y, Z); the contents of its grid and
+# its point and voxel lists as hashes).  64-bit fields are split into high and low 32-bit halves so that float64 holds them exactly.
+DUMP_NODE_FIELDS = ("level", "X", "Y", "Z", "isLeaf", "childMask", "counter", "numPoints", "numVoxels", "numVoxelsStored", "countIteration",
+                    "hasGrid", "gridPopcount", "gridHash", "pointsSum", "pointsXor", "voxelPosSum", "voxelPosXor", "pointChunks", "voxelChunks")
+DUMP_STATS_FIELDS = ("numNodes", "numInner", "numLeaves", "numNonemptyLeaves", "numPoints", "numVoxels", "allocatedBytes_persistent",
+                     "numChunksPoints", "numChunksVoxels", "batchletIndex", "numPointsProcessed", "numAllocatedChunks", "chunkPoolSize",
+                     "memCapacityReached")      # (the fields that are deterministic for a fixed batch sequence: tests/util.py)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dev, out_dir, suffix=""):
+    import oracle
+    os.makedirs(out_dir, exist_ok=True)
+    st = dev.read_stats()
+    np.save(os.path.join(out_dir, f"stats{suffix}.npy"), np.array([float(int(st[f])) for f in DUMP_STATS_FIELDS], dtype=np.float64))
+    nodes, pers, n, nodes_base, pers_base = dev.download_image()
+    oracle.rebase_image(nodes, n, pers, nodes_base, pers_base)
+    d = oracle.dump_image(nodes, n)
+    del nodes, pers
+    cols = []
+    for f in DUMP_NODE_FIELDS:
+        v = d[f].astype(np.uint64)
+        cols += [(v >> np.uint64(32)).astype(np.float64), (v & np.uint64(0xffffffff)).astype(np.float64)] if d.dtype[f].itemsize == 8 else [v.astype(np.float64)]
+    table = np.stack(cols, axis=1)
+    rows = DUMP_MAX_BYTES // table[0].nbytes
+    if len(table) > rows:                      # (263 157 nodes at most: 50 MB; a fixed, seeded sample only beyond the budget)
+        table = table[np.sort(np.random.RandomState(0).choice(len(table), rows, replace=False))]
+    np.save(os.path.join(out_dir, f"octree_nodes{suffix}.npy"), table)
 
 
 def relaunch_through_torchrun(args):
@@ -231,12 +271,14 @@ def main():
     assert int(stats["numPointsProcessed"]) == my_points and int(stats["numPoints"]) == my_points, "ingest lost points"
     assert int(stats["dbg"]) == 0, f"device error bits {int(stats['dbg']):#x}"
     value = world * n_points / (ms_per_step * 1e-3) / 1e6
+    if args.dump_outputs:
+        dump_outputs(dev, args.dump_outputs, f"_rank{rank}" if world > 1 else "")
     # The headline is what the UNCHANGED reference host gets: the library sizes its launches by the upload-counter writes it is told about (shim/cuda.h
     # forwards the uploader's cuMemsetD32Async, main_progressive_octree.cpp:1047-1050; the Python mirror's publish() does the same) and by what its
     # earlier launches reported.  Beside it: the same steps with the host ALSO saying how many batches are pending in front of every launch
     # (simlod_context_hint_pending_batches) — the two must agree — and with a host that tells nothing at all (the library's prediction alone).
     without_hint = None
-    if source is None and rank == 0 and not use_dist and not args.no_cpu_baseline:      # (not in the profiling passes: their per-launch figures count three ingests)
+    if args.full and source is None and rank == 0 and not use_dist and not args.no_cpu_baseline:      # (not in the profiling passes: their per-launch figures count three ingests)
         def timed():
             ingest_step()
             torch.cuda.synchronize()
@@ -256,7 +298,7 @@ def main():
         without_hint = {"with_host_hint": with_hint, "host_tells_nothing": blind,
                         "what": "headline: launches sized by the upload-counter writes the shim forwards; with_host_hint: + simlod_context_hint_pending_batches per launch; host_tells_nothing: neither (prediction from the launches' own reports)"}
     collective = None
-    if use_dist:
+    if args.full and use_dist:
         # what the process group really was: every rank adds 1 (ranks_seen must be the world size) and its point count (the octrees of all
         # ranks together hold every generated point)
         seen = torch.tensor([1, int(stats["numPoints"])], dtype=torch.int64, device=dev.device)
@@ -280,9 +322,9 @@ def main():
     # Kept measurements (profiles/): quoted ONLY when they were taken on the kernel sources of this tree — the fingerprint the profiling tools
     # record must equal the one computed here; otherwise the fields stay null and `profiles_note` says why.
     from simlod_amd.fingerprint import kept_profiles
-    pdir, tfile, profiles_note, sha_now = kept_profiles(args.profiles)
+    pdir, tfile, profiles_note, sha_now = kept_profiles(args.profiles) if args.full else (None, None, None, None)
     rtraffic = json.load(open(tfile)) if tfile else {}
-    presets = args.raster_presets.split(",")
+    presets = args.raster_presets.split(",") if args.full else []
     for name, hqs, Tcam in [m for m in (("hqs", 1, T), ("plain", 0, T), ("hqs_close", 1, T_close), ("plain_close", 0, T_close)) if ("close" if "close" in m[0] else "bird") in presets]:
         uc = dev.uniforms(W, H, Tcam, box, hqs=bool(hqs))
 
@@ -349,7 +391,7 @@ def main():
     # measurement aid in the control block at byte 0 of the momentary buffer: construct.hip Ctl.expandNs[7] (stored points moved by splits) at byte 208
     CTL_COUNTERS = slice(208, 216)
     CTL_GROUPS = slice(184, 192)           # Ctl.expandNs[4]: groups of batches ingested (every per-group kernel had that many launches with work)
-    if rank == 0 and not args.no_profile:
+    if args.full and rank == 0 and not args.no_profile:
         L.simlod_profile_enable(2)
         dev.momentary[CTL_GROUPS].zero_()
         ingest_step()
@@ -403,7 +445,7 @@ def main():
 
     # ---- loader row: LAS format-2 records (26 B) -> Points (16 B) on the device, one 1 M-point batch per launch ----
     loader = None
-    if rank == 0 and not args.no_profile:
+    if args.full and rank == 0 and not args.no_profile:
         from simlod_amd import lasio
         rs = np.random.RandomState(5)
         rec = lasio.las_records(rs.randint(0, 6_000_000, size=(batch, 3)).astype(np.int32), rs.randint(0, 65536, size=(batch, 3)).astype(np.uint16), 2)
@@ -453,7 +495,7 @@ def main():
 
     # ---- CPU baseline: the oracle's serial C restatement on a bounded sample of the same workload ------------------
     cpu = None
-    if rank == 0 and world == 1 and not use_dist and not args.no_cpu_baseline:   # (the torchrun path generates its points on the device)
+    if args.full and rank == 0 and world == 1 and not use_dist and not args.no_cpu_baseline:   # (the torchrun path generates its points on the device)
         import subprocess
         import tempfile
         # the serial restatement rebuilt -march=native ON this box, into a scratch file (the library that ships stays portable)
@@ -533,7 +575,7 @@ def main():
 
     # ---- the opt-in coalesced ingest mode on the same resident input (reported beside the headline, never as `value`) ---------------------
     coalesced = None
-    if rank == 0 and world == 1 and not args.coalesce and not args.no_profile:
+    if args.full and rank == 0 and world == 1 and not args.coalesce and not args.no_profile:
         try:
             mb = max(args.momentary_mb, 700)
             dev2 = DeviceOctree(f"cuda:{local}", persistent_bytes=8 << 30, momentary_bytes=mb * 1_000_000, max_pixels=W * H, coalesce=True)
@@ -577,7 +619,7 @@ def main():
             "value": value, "unit": "M points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32+u32 (fp32 quantise/project, fp64 pixel coordinate, integer octree/atomics)", "data": "synthetic",
-            "ingest_mode": "coalesced" if args.coalesce else "exact",
+            "ingest_mode": "coalesced" if args.coalesce else "exact", "full": args.full,
             "host_hint": "simlod_context_hint_pending_batches per launch" if dev.hint_pending else None,
             "ingest_other_hosts": without_hint,
             "config": {"workload": (f"BASELINE config 4 shape: tiled terrain, {n_points} device-generated 16 B points per GPU streamed through the 50-slot ring ({n_batches} x 1M batches), "
@@ -586,7 +628,7 @@ def main():
                        "points_per_gpu": n_points, "record_order": args.order if not use_dist else "device-generated tiles, swath order",
                        "parallelism": f"one global cube, level-3 cells dealt to {world} rank(s) by point count"},
             "csrc_sha16": sha_now, "profiles_note": profiles_note,
-            "roofline": roofline, "roofline_chain": chain, "cpu_baseline": cpu, "raster": raster, "coalesced_ingest": coalesced, "loader": loader,
+            "roofline": roofline, "roofline_chain": chain, "cpu_baseline": cpu, "raster": raster if args.full else None, "coalesced_ingest": coalesced, "loader": loader,
             "collective": collective, "partition": partition, "config3": config3, "kernels": kernels,
             "octree": {k: int(stats[k]) for k in ("numNodes", "numInner", "numLeaves", "numVoxels", "allocatedBytes_persistent")},
         }

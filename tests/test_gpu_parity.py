@@ -1567,7 +1567,7 @@ def test_bench_runs_under_torch_distributed_run_and_prints_one_json_line(built_l
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                           "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-                          "--points", "4000000", "--frames", "2", "--no-profile", "--persistent-gb", "8"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+                          "--points", "4000000", "--frames", "2", "--no-profile", "--persistent-gb", "8", "--full"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines

@@ -1,6 +1,7 @@
 """Loader row, CPU side: the numpy restatement of the reference's LAS parse loop and the host-side header /
 .simlod readers, pinned to fixtures minted from the reference itself (tests/golden/make_golden_las.py: loadLasNative built in
-place, tools/las2simlod.mjs run with node), and — where oracle/_ref/libref_las.so is present — to the reference live."""
+place, tools/las2simlod.mjs run with node), and to the reference loader's record of four more files (tests/golden/oracle_pin.npz)."""
+import hashlib
 import os
 import tempfile
 
@@ -73,22 +74,37 @@ def test_writer_roundtrip_las14_point_count(tmp_path):
     assert (h.versionMinor, h.numPoints, h.bytesPerPoint, h.headerSize, h.offsetToPointData) == (4, 5, 36, 375, 375)
 
 
-@pytest.mark.skipif(not oracle.have_ref_las(), reason="oracle/_ref/libref_las.so not built (needs /root/reference at build time)")
-def test_port_equals_reference_live(tmp_path):
+def record_live(kind, tmpdir):
+    """Four LAS files written here, read back by the reference's loader (kind="ref": oracle/_ref/libref_las.so, loadHeader +
+    loadLasNative) or by the numpy parse + the oracle's decode (kind="port"); -> header numbers and SHA-256 digests of the decoded bits.
+    tests/golden/make_golden_pin.py stores the reference's record in tests/golden/oracle_pin.npz (keys "las_live__...")."""
     rs = np.random.RandomState(77)
+    rec = {}
     for fmt, ver in [(2, (1, 2)), (3, (1, 2)), (7, (1, 4)), (1, (1, 1))]:
         n = 20_000
         xyz = rs.randint(-2 ** 31, 2 ** 31 - 1, size=(n, 3), dtype=np.int64).astype(np.int32)
         rgb = rs.randint(0, 65536, size=(n, 3)).astype(np.uint16)
-        p = str(tmp_path / f"l{fmt}.las")
+        p = os.path.join(tmpdir, f"l{fmt}.las")
         lasio.write_las(p, lasio.las_records(xyz, rgb, fmt, seed=fmt), fmt, (1e-3, 1e-2, 1e-7), (5e5, -4e6, 1e3), (1e5, -5e6, 0), (9e5, 0, 5e3), version=ver)
         h = lasio.load_header(p)
-        rh = oracle.ref_las_header(p)
-        assert rh["numPoints"] == h.numPoints and rh["offsetToPointData"] == h.offsetToPointData
         tr = tuple(-m for m in h.min)
-        ref = oracle.ref_las_load(p, 123, 15_000, tr)
-        port = oracle.decode_las_port(lasio.read_records(p, h, 123, 15_000), h.bytesPerPoint, h.format, h.scale, lasio.decode_offset(h, tr))
+        if kind == "ref":
+            rh = oracle.ref_las_header(p)
+            head, pts = (rh["numPoints"], rh["offsetToPointData"]), oracle.ref_las_load(p, 123, 15_000, tr)
+        else:
+            head = (h.numPoints, h.offsetToPointData)
+            pts = oracle.decode_las_port(lasio.read_records(p, h, 123, 15_000), h.bytesPerPoint, h.format, h.scale, lasio.decode_offset(h, tr))
+        rec[f"f{fmt}_header"] = np.array(head, dtype=np.int64)
         for k in "xyz":
-            assert np.array_equal(ref[k].view(np.uint32), port[k].view(np.uint32))
+            rec[f"f{fmt}_{k}"] = np.frombuffer(hashlib.sha256(pts[k].view(np.uint32).tobytes()).digest(), dtype=np.uint8)
         if fmt in lasio.RGB_OFFSET:
-            assert np.array_equal(ref["color"] & 0xffffff, port["color"] & 0xffffff)
+            rec[f"f{fmt}_rgb"] = np.frombuffer(hashlib.sha256((pts["color"] & 0xffffff).tobytes()).digest(), dtype=np.uint8)
+    return rec
+
+
+def test_port_equals_reference_live(tmp_path):
+    from test_oracle_pin import golden
+    want, got = golden("las_live"), record_live("port", str(tmp_path))
+    assert sorted(want) == sorted(got)
+    for k in want:
+        assert np.array_equal(want[k], got[k]), k

@@ -1,7 +1,12 @@
 """Pins the C restatement (oracle/simlod_oracle.c) against the reference ITSELF: oracle/_ref = the reference's own
 reset.cu / progressive_octree_voxels.cu / render.cu compiled in place as single-thread host code (oracle/Makefile).
 A serial run has one legal outcome, so the two must agree on every byte that is not an address: node records, chunk
-contents at identical allocator offsets, occupancy grids, Stats, pre-EDL framebuffers."""
+contents at identical allocator offsets, occupancy grids, Stats, pre-EDL framebuffers.
+
+Every scenario is one `record_*` function, run on a back-end: tests/golden/make_golden_pin.py runs them on the reference
+(kind="ref") into tests/golden/oracle_pin.npz; the tests run them on the restatement and compare with that fixture, so
+they need neither the reference nor oracle/_ref.  Framebuffers are kept as SHA-256 digests."""
+import hashlib
 import os
 
 import numpy as np
@@ -11,10 +16,19 @@ import oracle
 from cases import CASES, batches_of, case, uniforms_for
 from util import STATS_BUILD_FIELDS, STATS_RENDER_FIELDS, assert_dumps_equal, assert_stats_equal
 
-pytestmark = pytest.mark.skipif(not (oracle.have_ref() or os.path.isdir("/root/reference")),
-                                reason="oracle/_ref not built and /root/reference absent")
-
 NODE_VALUE_FIELDS = ["counter", "numPoints", "level", "X", "Y", "Z", "countIteration", "name", "numVoxels", "numVoxelsStored"]
+GOLDEN_PIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_pin.npz")
+EDGE_VARIANTS = ["odd_size_hqs", "odd_size_plain_boxes", "tiny_frame", "inside_the_cloud_hqs", "inside_the_cloud_plain", "fine_lod_hqs", "boxes_only"]
+
+
+def _digest(fb):
+    return np.frombuffer(hashlib.sha256(fb.tobytes()).digest(), dtype=np.uint8)
+
+
+def golden(scenario):
+    """The reference's record of one scenario (keys "<scenario>__<what>" in tests/golden/oracle_pin.npz)."""
+    g = np.load(GOLDEN_PIN)
+    return {k.split("__", 1)[1]: g[k] for k in g.files if k.split("__", 1)[0] == scenario}
 
 
 def _run(kind, name):
@@ -29,60 +43,72 @@ def _run(kind, name):
     return o, box, T
 
 
-@pytest.mark.parametrize("name", CASES)
-def test_restatement_equals_reference_build(built_libs, name):
-    ref, box, T = _run("ref", name)
-    port, _, _ = _run("port", name)
-    assert port.last_error() == 0
-    assert_stats_equal(port.stats[0], ref.stats[0], STATS_BUILD_FIELDS, name)
-    n = int(ref.stats["numNodes"][0])
+def record_build(kind, name):
+    o, box, T = _run(kind, name)
+    n = int(o.stats["numNodes"][0])
+    rec = {"stats": o.stats.copy(), "dump": o.dump()}                # the dump: every stored point, voxel position and grid bit
     for f in NODE_VALUE_FIELDS:
-        assert np.array_equal(ref.nodes[f][:n], port.nodes[f][:n]), f"Node.{f}"
+        rec[f"node_{f}"] = o.nodes[f][:n].copy()
     # same allocation order -> same offsets inside the persistent buffer for grids and chunk lists
     for f in ("grid", "points", "voxelChunks"):
-        ra = np.where(ref.nodes[f][:n] != 0, ref.nodes[f][:n] - np.uint64(ref.persistent.ctypes.data), 0)
-        pa = np.where(port.nodes[f][:n] != 0, port.nodes[f][:n] - np.uint64(port.persistent.ctypes.data), 0)
-        assert np.array_equal(ra, pa), f"Node.{f} offsets"
-    ca = np.where(ref.nodes["children"][:n] != 0, ref.nodes["children"][:n] - np.uint64(ref.nodes.ctypes.data), 0)
-    cb = np.where(port.nodes["children"][:n] != 0, port.nodes["children"][:n] - np.uint64(port.nodes.ctypes.data), 0)
-    assert np.array_equal(ca, cb), "children indices"
-    assert_dumps_equal(port.dump(), ref.dump(), name)       # includes every stored point, voxel position and grid bit
+        rec[f"offset_{f}"] = np.where(o.nodes[f][:n] != 0, o.nodes[f][:n] - np.uint64(o.persistent.ctypes.data), 0)
+    rec["children"] = np.where(o.nodes["children"][:n] != 0, o.nodes["children"][:n] - np.uint64(o.nodes.ctypes.data), 0)
     for hqs in (False, True):
-        u = uniforms_for(box, T, hqs=hqs)
-        fa, _ = ref.render(u)
-        fb, _ = port.render(u)
-        assert np.array_equal(fa, fb), f"{name}: pre-EDL framebuffer differs (hqs={hqs})"
-        assert_stats_equal(port.stats[0], ref.stats[0], STATS_RENDER_FIELDS, name)
-        va, vb = ref.visible, port.visible
-        assert len(va) == len(vb) and np.array_equal(va["name"], vb["name"]), "visible-node list order"
+        fb, _ = o.render(uniforms_for(box, T, hqs=hqs))
+        rec[f"fb_{int(hqs)}"], rec[f"render_stats_{int(hqs)}"], rec[f"visible_{int(hqs)}"] = _digest(fb), o.stats.copy(), o.visible["name"].copy()
+    return o, rec
 
 
-def test_point_size_and_color_modes_match_reference(built_libs):
-    ref, box, T = _run("ref", "uniform_3x40k")
-    port, _, _ = _run("port", "uniform_3x40k")
-    for kw in (dict(point_size=2), dict(point_size=3)):
-        u = uniforms_for(box, T, **kw)
-        assert np.array_equal(ref.render(u)[0], port.render(u)[0]), kw
+@pytest.mark.parametrize("name", CASES)
+def test_restatement_equals_reference_build(built_libs, name):
+    port, got = record_build("port", name)
+    want = golden(f"build_{name}")
+    assert port.last_error() == 0
+    assert_stats_equal(got["stats"][0], want["stats"][0], STATS_BUILD_FIELDS, name)
+    for f in NODE_VALUE_FIELDS:
+        assert np.array_equal(want[f"node_{f}"], got[f"node_{f}"]), f"Node.{f}"
+    for f in ("grid", "points", "voxelChunks"):
+        assert np.array_equal(want[f"offset_{f}"], got[f"offset_{f}"]), f"Node.{f} offsets"
+    assert np.array_equal(want["children"], got["children"]), "children indices"
+    assert_dumps_equal(got["dump"], want["dump"], name)
+    for hqs in (0, 1):
+        assert np.array_equal(want[f"fb_{hqs}"], got[f"fb_{hqs}"]), f"{name}: pre-EDL framebuffer differs (hqs={hqs})"
+        assert_stats_equal(got[f"render_stats_{hqs}"][0], want[f"render_stats_{hqs}"][0], STATS_RENDER_FIELDS, name)
+        va, vb = want[f"visible_{hqs}"], got[f"visible_{hqs}"]
+        assert len(va) == len(vb) and np.array_equal(va, vb), "visible-node list order"
+
+
+def record_modes(kind):
+    """Frames of uniform_3x40k in the point-size, debug-line and colour modes, in this order; -> (frames, digests)."""
+    o, box, T = _run(kind, "uniform_3x40k")
+    frames = []
+    for ps in (2, 3):
+        frames.append((("point_size", ps), o.render(uniforms_for(box, T, point_size=ps))[0]))
     for hqs in (0, 1):                      # debug lines: node boxes + frustum, rasterization.cuh:90-183
         u = uniforms_for(box, T, hqs=bool(hqs))
         u["showBoundingBox"] = 1
-        fa, fb = ref.render(u)[0], port.render(u)[0]
-        assert np.array_equal(fa, fb) and int(((fa & np.uint64(0xffffffff)) == np.uint64(0xff00)).sum()) > 500
+        frames.append((("showBoundingBox", hqs), o.render(u)[0]))
     for field in ("colorByNode", "colorByLOD"):
         u = uniforms_for(box, T)
         u[field] = 1
         for hqs in (0, 1):
             u["useHighQualityShading"] = hqs
-            assert np.array_equal(ref.render(u)[0], port.render(u)[0]), (field, hqs)
+            frames.append(((field, hqs), o.render(u)[0]))
+    return frames, {"fb": np.stack([_digest(fb) for _, fb in frames])}
 
 
-def test_hazard_regimes_match_reference(built_libs):
-    """Where the reference is lossy the restatement must be lossy in the same way (the HIP path documents where it is not):
-    20 split rounds down to level 20 with 70 000 identical points (the reference does not count after its 20th split, allocates no
-    chunks for the level-20 leaf, increments its numPoints and drops the points, voxels.cu:394-412, 599-604 — the restatement
-    reports that as NULL_CHUNK), and points exactly on the box faces (coordinate == boxMax quantises to 2^20, wraps into the low
-    child, voxels.cu:148-179)."""
-    from simlod_amd import abi, camera, synthetic
+def test_point_size_and_color_modes_match_reference(built_libs):
+    frames, got = record_modes("port")
+    want = golden("modes")["fb"]
+    assert len(want) == len(frames)
+    for (what, fb), a, b in zip(frames, want, got["fb"]):
+        assert np.array_equal(a, b), what
+        if what[0] == "showBoundingBox":
+            assert int(((fb & np.uint64(0xffffffff)) == np.uint64(0xff00)).sum()) > 500
+
+
+def record_hazards(kind):
+    from simlod_amd import camera, synthetic
     rs = np.random.RandomState(4)
     base, box = synthetic.uniform_cube(20_000, seed=9)
     same = np.repeat(base[:1], 70_000)
@@ -93,25 +119,31 @@ def test_hazard_regimes_match_reference(built_libs):
     pts = np.concatenate([base[:10_000], same, corners, base[10_000:]])
     T = camera.lookat_transform((1.8, -1.2, 1.4), (0.5, 0.5, 0.3), 256, 256)
     u = uniforms_for(box, T)
-    runs = {}
-    for kind in ("ref", "port"):
-        o = oracle.HostOctree(kind, persistent_bytes=1 << 30, ring_slots=4)
-        o.reset(u)
-        o.add_points(u, pts, 50_000)
-        runs[kind] = o
-    ref, port = runs["ref"], runs["port"]
+    o = oracle.HostOctree(kind, persistent_bytes=1 << 30, ring_slots=4)
+    o.reset(u)
+    o.add_points(u, pts, 50_000)
+    rec = {"stats": o.stats.copy(), "dump": o.dump()}
+    rec["fb"] = _digest(o.render(u)[0])
+    return o, rec
+
+
+def test_hazard_regimes_match_reference(built_libs):
+    """Where the reference is lossy the restatement must be lossy in the same way (the HIP path documents where it is not):
+    20 split rounds down to level 20 with 70 000 identical points (the reference does not count after its 20th split, allocates no
+    chunks for the level-20 leaf, increments its numPoints and drops the points, voxels.cu:394-412, 599-604 — the restatement
+    reports that as NULL_CHUNK), and points exactly on the box faces (coordinate == boxMax quantises to 2^20, wraps into the low
+    child, voxels.cu:148-179)."""
+    from simlod_amd import abi
+    port, got = record_hazards("port")
+    want = golden("hazards")
     assert port.last_error() == 5                                   # ORACLE_ERR_NULL_CHUNK
-    assert_stats_equal(port.stats[0], ref.stats[0], STATS_BUILD_FIELDS, "hazards")
-    assert int(ref.stats["numNodes"][0]) == 1 + 8 * 20 and int(ref.nodes["level"][:161].max()) == abi.MAX_DEPTH
-    assert_dumps_equal(port.dump(), ref.dump(), "hazards")
-    assert np.array_equal(ref.render(u)[0], port.render(u)[0])
+    assert_stats_equal(got["stats"][0], want["stats"][0], STATS_BUILD_FIELDS, "hazards")
+    assert int(want["stats"]["numNodes"][0]) == 1 + 8 * 20 and int(want["dump"]["level"].max()) == abi.MAX_DEPTH
+    assert_dumps_equal(got["dump"], want["dump"], "hazards")
+    assert np.array_equal(want["fb"], got["fb"])
 
 
-@pytest.mark.parametrize("variant", ["odd_size_hqs", "odd_size_plain_boxes", "tiny_frame", "inside_the_cloud_hqs", "inside_the_cloud_plain",
-                                     "fine_lod_hqs", "boxes_only"])
-def test_render_edge_cases_match_reference(built_libs, variant):
-    """The render edge cases of the GPU suite (tests/test_gpu_parity.py: frame sizes off the 16-pixel grid, camera inside the cloud,
-    fine LOD threshold, lines without points), restatement against the reference's own render.cu on a reference-built octree."""
+def record_edge_case(kind, variant):
     from simlod_amd import abi, camera, synthetic
     Wd, Hd = (250, 131) if "odd_size" in variant else (40, 23) if variant == "tiny_frame" else (384, 256)
     pts, box = synthetic.uniform_cube(300_000, seed=77)
@@ -127,16 +159,23 @@ def test_render_edge_cases_match_reference(built_libs, variant):
         u["minNodeSize"] = 8.0
     if variant == "tiny_frame":
         u["minNodeSize"] = 2.0
-    frames = {}
-    for kind in ("ref", "port"):
-        o = oracle.HostOctree(kind, persistent_bytes=1 << 30, ring_slots=4)
-        o.reset(u)
-        o.add_points(u, pts, 100_000)
-        frames[kind] = (o.render(u)[0], o.stats[0].copy(), o.visible["name"].copy())
-    assert np.array_equal(frames["ref"][0], frames["port"][0]), variant
-    assert_stats_equal(frames["port"][1], frames["ref"][1], STATS_RENDER_FIELDS, variant)
-    assert np.array_equal(frames["ref"][2], frames["port"][2])
-    assert int((frames["ref"][0] != abi.CLEAR_PIXEL).sum()) > 50
+    o = oracle.HostOctree(kind, persistent_bytes=1 << 30, ring_slots=4)
+    o.reset(u)
+    o.add_points(u, pts, 100_000)
+    fb = o.render(u)[0]
+    return fb, {"fb": _digest(fb), "stats": o.stats.copy(), "visible": o.visible["name"].copy(), "nonbg": np.array([int((fb != abi.CLEAR_PIXEL).sum())])}
+
+
+@pytest.mark.parametrize("variant", EDGE_VARIANTS)
+def test_render_edge_cases_match_reference(built_libs, variant):
+    """The render edge cases of the GPU suite (tests/test_gpu_parity.py: frame sizes off the 16-pixel grid, camera inside the cloud,
+    fine LOD threshold, lines without points), restatement against the reference's own render.cu on a reference-built octree."""
+    _, got = record_edge_case("port", variant)
+    want = golden(f"edge_{variant}")
+    assert np.array_equal(want["fb"], got["fb"]), variant
+    assert_stats_equal(got["stats"][0], want["stats"][0], STATS_RENDER_FIELDS, variant)
+    assert np.array_equal(want["visible"], got["visible"])
+    assert int(want["nonbg"][0]) > 50
 
 
 def test_edl_restatement_matches_the_reference_edl_block():

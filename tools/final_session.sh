@@ -30,6 +30,6 @@ timeout 200 python tools/las_bench.py 2>&1 | grep -v amdgpu > $F/las_decode.txt
 timeout 200 python tools/batch_shape.py 2>&1 | grep -v amdgpu > $F/batch_shape.txt
 python tools/fold_profiles.py $TAG > $F/fold.txt 2>&1
 mkdir -p profiles/$TAG; cp gpurun_out/final_$TAG/config3_350m* profiles/$TAG/ 2>/dev/null
-timeout 900 python bench.py --profiles $TAG > $F/bench_final.json 2> $F/bench_final.err
-timeout 300 python bench.py --stream --steps 2 --warmup 1 --no-cpu-baseline --no-profile --profiles $TAG > $F/bench_stream_500m_1gpu.json 2> $F/bench_stream.err
+timeout 900 python bench.py --full --profiles $TAG > $F/bench_final.json 2> $F/bench_final.err
+timeout 300 python bench.py --full --stream --steps 2 --warmup 1 --no-cpu-baseline --no-profile --profiles $TAG > $F/bench_stream_500m_1gpu.json 2> $F/bench_stream.err
 tail -c 600 $F/bench_final.json; ls $F

@@ -9,7 +9,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 2 --warmup 1 --frames 4 --no-cpu-baseline --no-profile --raster-presets bird $*"
+CMD="python $REPO/bench.py --full --steps 2 --warmup 1 --frames 4 --no-cpu-baseline --no-profile --raster-presets bird $*"
 cd /tmp
 rocprofv3 -L > $OUT/counters_available.txt 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $CMD > $OUT/trace_bench.json 2> $OUT/trace.err
@@ -26,7 +26,7 @@ pass pmc_lds SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS
 pass pmc_atomic TCC_EA0_ATOMIC_sum TCC_ATOMIC_sum
 pass pmc_atomic2 TCC_EA0_ATOMIC_LEVEL_sum TCC_EA0_RDREQ_sum
 # the close-up camera preset (most samples of the near leaves leave their tiles): the byte passes of the raster kernels alone
-CMDC="python $REPO/bench.py --steps 1 --warmup 0 --frames 4 --no-cpu-baseline --no-profile --raster-presets close"
+CMDC="python $REPO/bench.py --full --steps 1 --warmup 0 --frames 4 --no-cpu-baseline --no-profile --raster-presets close"
 passc() { local name=$1; shift; timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -- $CMDC > /dev/null 2> $OUT/$name.err || echo "pass $name failed" >> $OUT/failed.txt; }
 passc pmc_fetch_close FETCH_SIZE
 passc pmc_write_close WRITE_SIZE

@@ -6,7 +6,7 @@ for V in "$@"; do
   ENVS=""; FLAGS=""
   for W in $V; do case $W in --*) FLAGS="$FLAGS $W";; [0-9]*) FLAGS="$FLAGS $W";; *) ENVS="$ENVS $W";; esac; done
   echo "== $V" >> $OUT
-  env $ENVS timeout 300 python bench.py --steps 3 --warmup 1 --frames 2 --no-cpu-baseline $FLAGS 2>> $OUT.err | python -c "
+  env $ENVS timeout 300 python bench.py --full --steps 3 --warmup 1 --frames 2 --no-cpu-baseline $FLAGS 2>> $OUT.err | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('value %.0f M pts/s  ms_per_step %.3f' % (d['value'], d['ms_per_step']))
