@@ -258,6 +258,76 @@ int simlod_generate_terrain(SimlodPoint* out, uint64_t numPoints, uint64_t first
 int simlod_generate_terrain_scan(SimlodPoint* out, uint64_t numPoints, uint64_t firstIndex, uint64_t pointsPerTile, uint32_t seed,
                                  uint32_t tilesX, const float tileExtent[3], float swathWidth, void* stream);
 
+/* ---- octree export / import (no counterpart in the reference) --------------------------------------------------------------
+ * A pointer-free, self-describing form of the octree, for saving it, handing a LOD cut to other code, and rendering it in another process.
+ *
+ * The table lists nodes breadth-first from the root (entry 0): within a level in their parents' order, children in octant order
+ * (k = x << 2 | y << 1 | z).  It does not depend on where the builder put each node, so two builds of one input give one table.  The
+ * samples of a node follow its chunk list (chunk 0 first); sample order inside the list and voxel colours are as scheduling-dependent as
+ * the image itself.  A node's samples are its points if it is a leaf of the SOURCE octree, else its voxels: the lists kernel_render draws. */
+typedef struct SimlodExportNode {
+	uint32_t level, X, Y, Z;      /* as Node                                                                                     */
+	uint32_t parent;              /* table index; 0xffffffff for the root                                                        */
+	uint32_t firstChild;          /* table index of the first LISTED child (listed children are consecutive, in octant order); 0xffffffff: none */
+	uint8_t  childMask;           /* bit k: the child in octant k is listed                                                      */
+	uint8_t  flags;               /* SIMLOD_EXPORT_FLAG_*                                                                        */
+	uint16_t reserved;            /* 0                                                                                           */
+	uint32_t numSamples;          /* samples of this node in the sample array (0 if not selected)                                */
+	uint64_t firstSample;         /* exclusive scan of numSamples in table order                                                 */
+} SimlodExportNode;
+typedef struct SimlodExportCounts {   /* written by the device */
+	uint32_t numNodes;            /* table entries written                                                                       */
+	uint32_t error;               /* SIMLOD_EXPORT_ERR_* bits; nonzero: the table / samples are incomplete                      */
+	uint64_t numSamples;          /* samples written                                                                             */
+} SimlodExportCounts;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodExportNode) == 40, "ExportNode");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodExportNode, parent) == 16, "ExportNode.parent");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodExportNode, firstChild) == 20, "ExportNode.firstChild");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodExportNode, childMask) == 24, "ExportNode.childMask");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodExportNode, flags) == 25, "ExportNode.flags");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodExportNode, reserved) == 26, "ExportNode.reserved");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodExportNode, numSamples) == 28, "ExportNode.numSamples");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodExportNode, firstSample) == 32, "ExportNode.firstSample");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodExportCounts) == 16, "ExportCounts");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodExportCounts, numSamples) == 8, "ExportCounts.numSamples");
+
+#define SIMLOD_EXPORT_NONE         0xffffffffu
+#define SIMLOD_EXPORT_FLAG_LEAF    0x01u   /* a leaf of the source octree: its samples are points, else voxels */
+#define SIMLOD_EXPORT_FLAG_SELECTED 0x02u  /* the node's samples are in the sample array */
+/* `select` */
+#define SIMLOD_EXPORT_ALL          0u      /* every listed node */
+#define SIMLOD_EXPORT_CUT          1u      /* the leaves of the truncated table: source leaves with level <= maxLevel and inner nodes at maxLevel */
+#define SIMLOD_EXPORT_VISIBLE      2u      /* the nodes the last kernel_render on this node array drew (render.cu:905-935, from Node.visible / isLarge) */
+/* SimlodExportCounts.error bits */
+#define SIMLOD_EXPORT_ERR_CAPACITY   0x1u  /* tableCapacity or sampleCapacity too small: nothing was written beyond either */
+#define SIMLOD_EXPORT_ERR_NODE_COUNT 0x2u  /* the nodes reached from the root are not Stats.numNodes (or a child pointer leaves the node array) */
+#define SIMLOD_EXPORT_ERR_SHORT_LIST 0x4u  /* a chunk list ends before its count */
+/* Stats.dbg bit of simlod_import_octree: the table failed validation; nothing was written but this bit */
+#define SIMLOD_ERR_IMPORT 0x400u
+
+/* Bytes of the `scratch` buffer export and import need for tables of up to nodeCapacity entries and up to sampleCapacity samples. */
+uint64_t simlod_export_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleCapacity);
+
+/* Writes the table (nodes with level <= maxLevel; 20 or more: every node) and the selected samples of the octree in `nodes` / Stats.
+ * Stats.numNodes and Stats.numPoints + Stats.numVoxels bound every selection: size `table` and `samples` from them.  The real counts go to
+ * `counts` (device).  SIMLOD_EXPORT_VISIBLE without a kernel_render on `nodes` since its last reset, construct or import: hipErrorInvalidValue,
+ * nothing enqueued.  While the builder's chunk table for `nodes` is valid the first chunks of each list come from it; the rest by `next`. */
+int simlod_export_octree(const SimlodNode* nodes, const SimlodStats* stats, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                         SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodExportCounts* counts,
+                         void* stream);
+
+/* Writes a renderable octree from a table (e.g. a loaded file): fresh chunks from byte 16 of `persistent` (the allocator header at byte 0
+ * made consistent), Node records (children from firstChild / childMask, level, X/Y/Z, name, counts, list heads, grid = NULL; a table node
+ * without listed children becomes a leaf and its samples its points) and the Stats counts (numNodes, numInner, numLeaves, numNonemptyLeaves,
+ * numPoints, numVoxels, numChunksPoints, numChunksVoxels, allocatedBytes_persistent; the other fields 0).  numNodes above the context's node
+ * capacity, or 0: hipErrorInvalidValue, nothing enqueued.  A validation kernel runs first (levels and coordinates against the parent,
+ * breadth-first order, child and sample ranges, the scan, the persistent bytes the chunks need against persistentCapacity): if anything
+ * fails it sets SIMLOD_ERR_IMPORT in Stats.dbg and nothing else is written.  The builder's chunk table for `nodes` is dropped, as
+ * simlod_octree_image_replaced does.  An imported octree is for rendering: until kernel_reset runs on `nodes`, kernel_construct and the colour
+ * filter return hipErrorInvalidValue for it and enqueue nothing. */
+int simlod_import_octree(const SimlodExportNode* table, uint32_t numNodes, const SimlodPoint* samples, uint64_t numSamples, void* scratch,
+                         uint64_t scratchBytes, uint8_t* persistent, uint64_t persistentCapacity, SimlodNode* nodes, SimlodStats* stats, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

@@ -106,3 +106,21 @@ def make_uniforms(width, height, transform, box_size, *, transform_update_bound=
     u["enableEDL"] = 1
     u["edlStrength"] = 0.8
     return u
+
+
+# ---- octree export / import (include/simlod_hip.h, "octree export / import") ---------------------------------------------------------
+EXPORT_ALL, EXPORT_CUT, EXPORT_VISIBLE = 0, 1, 2
+EXPORT_SELECT = {"all": EXPORT_ALL, "cut": EXPORT_CUT, "visible": EXPORT_VISIBLE}
+EXPORT_NONE = 0xFFFFFFFF
+EXPORT_FLAG_LEAF, EXPORT_FLAG_SELECTED = 0x1, 0x2
+EXPORT_ERR_CAPACITY, EXPORT_ERR_NODE_COUNT, EXPORT_ERR_SHORT_LIST = 0x1, 0x2, 0x4
+SIMLOD_ERR_IMPORT = 0x400
+
+export_node_dtype = np.dtype({
+    "names": ["level", "X", "Y", "Z", "parent", "firstChild", "childMask", "flags", "reserved", "numSamples", "firstSample"],
+    "formats": ["<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "u1", "u1", "<u2", "<u4", "<u8"],
+    "offsets": [0, 4, 8, 12, 16, 20, 24, 25, 26, 28, 32],
+    "itemsize": 40,
+})
+export_counts_dtype = np.dtype({"names": ["numNodes", "error", "numSamples"], "formats": ["<u4", "<u4", "<u8"], "offsets": [0, 4, 8], "itemsize": 16})
+assert export_node_dtype.itemsize == 40 and export_counts_dtype.itemsize == 16

@@ -1,0 +1,464 @@
+// export.hip — octree export / import (include/simlod_hip.h, "octree export / import"; no counterpart in the reference).
+//
+// Export: four launches on the caller's stream.
+//   k_x_hier   ONE workgroup: the breadth-first walk, level by level (at most 21 levels, none past maxLevel).  Per level one lane per node:
+//              the node's child mask from its non-null children, a workgroup exclusive scan of the popcounts gives the children's table
+//              indices, the lane writes its table entry (everything but firstSample) and its children's source indices.  Config 2 has
+//              4 425 nodes: five rounds of 1 024 lanes in all; no grid-wide barrier.
+//   k_x_scan   ONE workgroup: exclusive scans of numSamples (-> firstSample) and of the chunks per node (-> the node's first copy item);
+//              the capacity check of the samples; SimlodExportCounts.
+//   k_x_dir    one lane per table entry: the node's chunk addresses — the first <= 50 from the builder's chunk table while that is valid
+//              (the stamp check r_visible does, render.hip), the rest (or all) by `next` — as copy items {source, destination, count}.
+//   k_copy     the hot path: one workgroup per chunk at a time (grid-stride), 16-byte loads and stores, four per lane in flight.
+// Import: k_i_validate (ONE workgroup: every check, the scans, the Stats counts) -> k_i_nodes (one lane per node: Node record, the chunk
+// headers of its list, its copy items) -> k_copy (the same kernel, samples -> chunks) -> k_i_finish (allocator header, Stats).
+// Everything in between lives in the caller's scratch buffer (export_min_bytes), never in kernel_construct's momentary buffer: the builder's
+// recycle stack and the chunk table export reads are there.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "simlod_device.hpp"
+#include "simlod_hip.h"
+#include "simlod_internal.hpp"
+
+namespace simlod {
+namespace {
+
+constexpr uint32_t WG_TPB = 1024;                                                  // the single-workgroup passes
+constexpr uint32_t WG_WAVES = WG_TPB / SIMLOD_WAVE;
+constexpr uint32_t LANE_TPB = 256;                                                 // one lane per node / the copy
+constexpr uint64_t CHUNK_STRIDE = SIMLOD_ALLOC_ROUND(sizeof(SimlodChunk));         // 16 032: what AllocatorGlobal::alloc advances per chunk
+constexpr uint64_t CHUNK_BASE = 16;                                                // first allocation behind the allocator header
+constexpr uint32_t NONE = SIMLOD_EXPORT_NONE;
+
+struct CopyItem { uint64_t src, dst; uint32_t count, pad0; uint64_t pad1; };       // 32 B; count == 0: nothing
+static_assert(sizeof(CopyItem) == 32, "CopyItem");
+
+// scratch: header | map u32[cap] (export: table index -> node index) | par u32[cap] (export: parent table index) | first u32[cap + 1]
+// (first copy item of each table entry) | items CopyItem[itemCap]
+struct Header {
+	uint32_t error, numListed, ok, pad;
+	uint64_t numItems;
+	uint64_t totalChunks;
+	uint32_t counts[8];                  // import: inner, leaves, nonempty leaves, points, voxels, point chunks, voxel chunks
+};
+static_assert(sizeof(Header) <= 256, "Header");
+__host__ __device__ inline uint64_t align256(uint64_t v) { return (v + 255u) & ~255ull; }
+struct Layout {
+	uint64_t map = 0, par = 0, first = 0, items = 0, itemCap = 0, bytes = 0;
+	Layout() = default;
+	__host__ __device__ Layout(uint32_t cap, uint64_t sampleCap) {
+		map = 256; par = map + align256(4ull * cap); first = par + align256(4ull * cap); items = first + align256(4ull * cap + 4u);
+		itemCap = sampleCap / SIMLOD_POINTS_PER_CHUNK + cap + 1u;     // sum over nodes of ceil(n_i / 1000) <= N / 1000 + nodes
+		bytes = items + itemCap * sizeof(CopyItem);
+	}
+};
+
+// exclusive scan over the workgroup (WG_TPB lanes); every lane gets the total.  `lds`: WG_WAVES words, reused by the next call after a barrier.
+template <typename T>
+__device__ __forceinline__ T block_scan(T v, T& total, T* lds) {
+	const int lane = lane_id(), w = (int)(threadIdx.x / SIMLOD_WAVE);
+	T x = v;
+#pragma unroll
+	for (int o = 1; o < SIMLOD_WAVE; o <<= 1) {
+		const T y = __shfl_up(x, (unsigned)o, SIMLOD_WAVE);
+		if (lane >= o) x += y;
+	}
+	if (lane == SIMLOD_WAVE - 1) lds[w] = x;
+	__syncthreads();
+	T before = 0, all = 0;
+	for (int k = 0; k < (int)WG_WAVES; k++) { const T s = lds[k]; before += k < w ? s : (T)0; all += s; }
+	__syncthreads();
+	total = all;
+	return before + x - v;
+}
+
+__device__ __forceinline__ uint32_t ceil_chunks(uint64_t n) { return (uint32_t)((n + SIMLOD_POINTS_PER_CHUNK - 1u) / SIMLOD_POINTS_PER_CHUNK); }
+
+struct ExportArgs {
+	const SimlodNode*  nodes;
+	const SimlodStats* stats;
+	uint32_t           maxLevel, select, cap;
+	uint8_t*           scratch;
+	SimlodExportNode*  table;
+	SimlodPoint*       samples;
+	uint64_t           sampleCap;
+	SimlodExportCounts* counts;
+	Layout             lay;
+	// the builder's chunk table of `nodes` (LeafTableRef), or table == nullptr
+	const uint8_t*     lt;
+	const uint8_t*     ltPers;
+	const uint32_t*    ltMagic;
+	const uint32_t*    ltBatch;
+	const uint64_t*    ltNodes;
+	const uint64_t*    ltSig;
+	uint32_t           ltMagicValue, ltSlots, ltRows;
+};
+
+__global__ __launch_bounds__(WG_TPB) void k_x_hier(ExportArgs a) {
+	__shared__ uint32_t sh_scan[WG_WAVES];
+	__shared__ uint32_t sh_err, sh_trunc;
+	Header* hdr = reinterpret_cast<Header*>(a.scratch);
+	uint32_t* map = reinterpret_cast<uint32_t*>(a.scratch + a.lay.map);
+	uint32_t* par = reinterpret_cast<uint32_t*>(a.scratch + a.lay.par);
+	const uint32_t numNodes = a.stats->numNodes;
+	const uint32_t maxLevel = min(a.maxLevel, (uint32_t)SIMLOD_MAX_DEPTH);
+	if (threadIdx.x == 0) {
+		sh_err = numNodes == 0u ? SIMLOD_EXPORT_ERR_NODE_COUNT : a.cap == 0u ? SIMLOD_EXPORT_ERR_CAPACITY : 0u;
+		sh_trunc = 0u;
+		if (sh_err == 0u) { map[0] = 0u; par[0] = NONE; }
+	}
+	__syncthreads();
+	uint32_t lo = 0u, hi = sh_err == 0u ? 1u : 0u;
+	for (uint32_t L = 0; L <= maxLevel && lo < hi; L++) {
+		uint32_t next = hi;
+		for (uint32_t base = lo; base < hi; base += WG_TPB) {
+			const uint32_t t = base + threadIdx.x;
+			const bool act = t < hi;
+			const uint32_t src = act ? map[t] : 0u;
+			const SimlodNode* n = a.nodes + src;
+			uint32_t child[8], mask = 0u;
+			bool srcLeaf = true;
+			if (act) {
+#pragma unroll
+				for (int k = 0; k < 8; k++) {
+					const SimlodNode* c = n->children[k];
+					child[k] = 0u;
+					if (c == nullptr) continue;
+					srcLeaf = false;
+					const uint64_t idx = (uint64_t)(c - a.nodes);
+					if (c < a.nodes || idx >= numNodes) { atomicOr(&sh_err, SIMLOD_EXPORT_ERR_NODE_COUNT); continue; }
+					child[k] = (uint32_t)idx;
+					if (L < maxLevel) mask |= 1u << k;
+				}
+				if (!srcLeaf && L >= maxLevel) atomicOr(&sh_trunc, 1u);
+			}
+			uint32_t total;
+			const uint32_t off = block_scan<uint32_t>((uint32_t)__popc(mask), total, sh_scan);
+			const uint32_t fc = next + off;
+			if (act) {
+				uint32_t r = 0;
+				for (int k = 0; k < 8; k++) {
+					if (!(mask & (1u << k))) continue;
+					if (fc + r < a.cap) { map[fc + r] = child[k]; par[fc + r] = t; }
+					else atomicOr(&sh_err, SIMLOD_EXPORT_ERR_CAPACITY);
+					r++;
+				}
+				const uint32_t parent = par[t];
+				bool sel = true;
+				if (a.select == SIMLOD_EXPORT_CUT) sel = srcLeaf || L == maxLevel;
+				else if (a.select == SIMLOD_EXPORT_VISIBLE) {
+					// render.cu:905-935 as r_visible decides it (render.hip visible_nodes): drawn = visible && (large ? leaf : parent large)
+					const bool parentLarge = parent != NONE && a.nodes[map[parent]].isLarge != 0;
+					sel = n->visible != 0 && (n->isLarge != 0 ? srcLeaf : parentLarge);
+				}
+				SimlodExportNode e;
+				e.level = n->level; e.X = n->X; e.Y = n->Y; e.Z = n->Z;
+				e.parent = parent;
+				e.firstChild = mask != 0u ? fc : NONE;
+				e.childMask = (uint8_t)mask;
+				e.flags = (uint8_t)((srcLeaf ? SIMLOD_EXPORT_FLAG_LEAF : 0u) | (sel ? SIMLOD_EXPORT_FLAG_SELECTED : 0u));
+				e.reserved = 0;
+				e.numSamples = sel ? (srcLeaf ? n->numPoints : n->numVoxels) : 0u;
+				e.firstSample = 0;
+				a.table[t] = e;
+			}
+			next += total;
+		}
+		__syncthreads();                         // (the children's map entries, written by other lanes, are read next level)
+		lo = hi;
+		hi = min(next, a.cap);
+		if (sh_err & SIMLOD_EXPORT_ERR_CAPACITY) break;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		uint32_t err = sh_err;
+		const uint32_t listed = (err & SIMLOD_EXPORT_ERR_CAPACITY) ? lo : hi;        // entries written
+		// every node is reached exactly once from the root: all of them when nothing was cut off, no more than all of them otherwise
+		if (sh_trunc == 0u ? listed != numNodes : listed > numNodes) err |= SIMLOD_EXPORT_ERR_NODE_COUNT;
+		hdr->error = err;
+		hdr->numListed = listed;
+	}
+}
+
+__global__ __launch_bounds__(WG_TPB) void k_x_scan(ExportArgs a) {
+	__shared__ uint64_t sh_scan[WG_WAVES];
+	Header* hdr = reinterpret_cast<Header*>(a.scratch);
+	uint32_t* first = reinterpret_cast<uint32_t*>(a.scratch + a.lay.first);
+	const uint32_t n = hdr->numListed;
+	uint64_t samples = 0, items = 0;
+	for (uint32_t base = 0; base < n; base += WG_TPB) {
+		const uint32_t t = base + threadIdx.x;
+		const uint64_t ns = t < n ? a.table[t].numSamples : 0u;
+		uint64_t totS, totI;
+		const uint64_t offS = block_scan<uint64_t>(ns, totS, sh_scan);
+		const uint64_t offI = block_scan<uint64_t>(ceil_chunks(ns), totI, sh_scan);
+		if (t < n) { a.table[t].firstSample = samples + offS; first[t] = (uint32_t)(items + offI); }
+		samples += totS; items += totI;
+	}
+	if (threadIdx.x == 0) {
+		uint32_t err = hdr->error;
+		if (samples > a.sampleCap || items > a.lay.itemCap) err |= SIMLOD_EXPORT_ERR_CAPACITY;
+		first[n] = (uint32_t)items;
+		hdr->numItems = (err & SIMLOD_EXPORT_ERR_CAPACITY) ? 0u : items;       // a sample array that is too small gets nothing
+		SimlodExportCounts c;
+		c.numNodes = n; c.error = err; c.numSamples = samples;
+		*a.counts = c;
+	}
+}
+
+__global__ __launch_bounds__(LANE_TPB) void k_x_dir(ExportArgs a) {
+	const Header* hdr = reinterpret_cast<const Header*>(a.scratch);
+	const uint32_t* map = reinterpret_cast<const uint32_t*>(a.scratch + a.lay.map);
+	const uint32_t* first = reinterpret_cast<const uint32_t*>(a.scratch + a.lay.first);
+	CopyItem* items = reinterpret_cast<CopyItem*>(a.scratch + a.lay.items);
+	const uint32_t t = blockIdx.x * LANE_TPB + threadIdx.x;
+	if (t >= hdr->numListed || hdr->numItems == 0u) return;
+	const SimlodExportNode& e = a.table[t];
+	const uint32_t ns = e.numSamples;
+	if (ns == 0u) return;
+	const uint32_t src = map[t];
+	const SimlodNode* n = a.nodes + src;
+	const SimlodChunk* c = (e.flags & SIMLOD_EXPORT_FLAG_LEAF) ? n->points : n->voxelChunks;
+	// the builder's table describes this octree as it is now (render.hip visible_nodes: the same four stamp words) and its row starts at the list's head
+	bool rows = false;
+	if (a.lt != nullptr && src < a.ltRows) {
+		rows = *a.ltMagic == a.ltMagicValue && *a.ltBatch == a.stats->batchletIndex && *a.ltNodes == (uint64_t)a.nodes && *a.ltSig == table_signature(a.stats);
+		rows = rows && leaf_row_get(a.lt, a.ltPers, src, 0u) == c;
+	}
+	const uint32_t nch = ceil_chunks(ns), f = first[t];
+	const uint64_t dst0 = reinterpret_cast<uint64_t>(a.samples + e.firstSample);
+	uint32_t k = 0;
+	for (; k < nch; k++) {
+		if (k > 0u) c = rows && k < a.ltSlots ? leaf_row_get(a.lt, a.ltPers, src, k) : c->next;
+		if (c == nullptr) { atomicOr(&a.counts->error, SIMLOD_EXPORT_ERR_SHORT_LIST); break; }
+		CopyItem it;
+		it.src = reinterpret_cast<uint64_t>(c->points);
+		it.dst = dst0 + (uint64_t)k * SIMLOD_POINTS_PER_CHUNK * sizeof(SimlodPoint);
+		it.count = min(ns - k * SIMLOD_POINTS_PER_CHUNK, SIMLOD_POINTS_PER_CHUNK);
+		it.pad0 = 0; it.pad1 = 0;
+		items[f + k] = it;
+	}
+	for (; k < nch; k++) items[f + k] = CopyItem{0, 0, 0, 0, 0};
+}
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+// the hot path: one chunk (<= 1 000 samples of 16 bytes) per workgroup and turn, four 16-byte loads per lane in flight before the stores
+__global__ __launch_bounds__(LANE_TPB) void k_copy(const uint8_t* scratch, uint64_t itemsOff) {
+	const Header* hdr = reinterpret_cast<const Header*>(scratch);
+	const CopyItem* items = reinterpret_cast<const CopyItem*>(scratch + itemsOff);
+	const uint64_t numItems = hdr->numItems;
+	for (uint64_t i = blockIdx.x; i < numItems; i += gridDim.x) {
+		const CopyItem it = items[i];
+		const u32x4* s = reinterpret_cast<const u32x4*>(it.src);
+		u32x4* d = reinterpret_cast<u32x4*>(it.dst);
+		const uint32_t cnt = it.count;
+		u32x4 v[4];
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			const uint32_t k = threadIdx.x + (uint32_t)j * LANE_TPB;
+			if (k < cnt) v[j] = __builtin_nontemporal_load(s + k);
+		}
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			const uint32_t k = threadIdx.x + (uint32_t)j * LANE_TPB;
+			if (k < cnt) __builtin_nontemporal_store(v[j], d + k);
+		}
+	}
+}
+static_assert(4u * LANE_TPB >= SIMLOD_POINTS_PER_CHUNK, "k_copy: one chunk per workgroup and turn");
+
+// ---- import -------------------------------------------------------------------------------------------------------------------------
+struct ImportArgs {
+	const SimlodExportNode* table;
+	uint32_t                n;
+	const SimlodPoint*      samples;
+	uint64_t                numSamples;
+	uint8_t*                scratch;
+	Layout                  lay;
+	uint8_t*                pers;
+	uint64_t                persCap;
+	SimlodNode*             nodes;
+	SimlodStats*            stats;
+};
+
+__device__ __forceinline__ uint32_t octant_of(const SimlodExportNode& e) { return ((e.X & 1u) << 2) | ((e.Y & 1u) << 1) | (e.Z & 1u); }
+
+__global__ __launch_bounds__(WG_TPB) void k_i_validate(ImportArgs a) {
+	__shared__ uint64_t sh_scan[WG_WAVES];
+	__shared__ uint32_t sh_bad;
+	__shared__ uint32_t sh_cnt[7];
+	Header* hdr = reinterpret_cast<Header*>(a.scratch);
+	uint32_t* first = reinterpret_cast<uint32_t*>(a.scratch + a.lay.first);
+	if (threadIdx.x < 7) sh_cnt[threadIdx.x] = 0u;
+	if (threadIdx.x == 0) sh_bad = 0u;
+	__syncthreads();
+	uint64_t samples = 0, chunks = 0, children = 1;                   // (the root is nobody's child)
+	for (uint32_t base = 0; base < a.n; base += WG_TPB) {
+		const uint32_t t = base + threadIdx.x;
+		const bool act = t < a.n;
+		SimlodExportNode e{};
+		bool bad = false;
+		if (act) {
+			e = a.table[t];
+			bad |= e.level > (uint32_t)SIMLOD_MAX_DEPTH || e.reserved != 0 || (e.flags & ~(SIMLOD_EXPORT_FLAG_LEAF | SIMLOD_EXPORT_FLAG_SELECTED)) != 0;
+			if (t == 0u) bad |= e.parent != NONE || e.level != 0u || e.X != 0u || e.Y != 0u || e.Z != 0u;
+			else if (e.parent >= t) bad = true;
+			else {
+				// level and coordinates follow from the parent, and the parent lists this entry where its octant says
+				const SimlodExportNode p = a.table[e.parent];
+				const uint32_t k = octant_of(e);
+				bad |= e.level != p.level + 1u || (e.X >> 1) != p.X || (e.Y >> 1) != p.Y || (e.Z >> 1) != p.Z;
+				bad |= !(p.childMask & (1u << k)) || p.firstChild == NONE || t != p.firstChild + (uint32_t)__popc(p.childMask & ((1u << k) - 1u));
+			}
+			if (e.childMask == 0u) bad |= e.firstChild != NONE;
+			else bad |= e.firstChild == NONE || e.firstChild <= t || (uint64_t)e.firstChild + (uint32_t)__popc(e.childMask) > a.n || e.level >= (uint32_t)SIMLOD_MAX_DEPTH;
+		}
+		const uint64_t kids = (uint64_t)__popc(e.childMask), ns = act ? e.numSamples : 0u, nch = act ? ceil_chunks(ns) : 0u;
+		uint64_t totK, totS, totC;
+		const uint64_t offK = block_scan<uint64_t>(kids, totK, sh_scan);
+		const uint64_t offS = block_scan<uint64_t>(ns, totS, sh_scan);
+		const uint64_t offC = block_scan<uint64_t>(nch, totC, sh_scan);
+		if (act) {
+			// breadth-first order: an entry's children come right after the children of the entries before it
+			if (e.childMask != 0u) bad |= (uint64_t)e.firstChild != children + offK;
+			bad |= e.firstSample != samples + offS;
+			if (samples + offS + ns <= a.numSamples && chunks + offC < a.lay.itemCap) first[t] = (uint32_t)(chunks + offC);
+			const bool leaf = e.childMask == 0u;
+			const uint32_t c[7] = {leaf ? 0u : 1u, leaf ? 1u : 0u, leaf && ns > 0u ? 1u : 0u, leaf ? (uint32_t)ns : 0u, leaf ? 0u : (uint32_t)ns,
+			                       leaf ? (uint32_t)nch : 0u, leaf ? 0u : (uint32_t)nch};
+			for (int q = 0; q < 7; q++) if (c[q] != 0u) atomicAdd(&sh_cnt[q], c[q]);
+		}
+		if (bad) atomicOr(&sh_bad, 1u);
+		children += totK; samples += totS; chunks += totC;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		bool bad = sh_bad != 0u || a.n == 0u || children != a.n || samples != a.numSamples || chunks > a.lay.itemCap;
+		bad |= CHUNK_BASE + chunks * CHUNK_STRIDE > a.persCap;
+		hdr->ok = bad ? 0u : 1u;
+		hdr->numItems = bad ? 0u : chunks;
+		hdr->totalChunks = chunks;
+		for (int q = 0; q < 7; q++) hdr->counts[q] = sh_cnt[q];
+		if (bad) a.stats->dbg |= SIMLOD_ERR_IMPORT;
+		else first[a.n] = (uint32_t)chunks;
+	}
+}
+
+__global__ __launch_bounds__(LANE_TPB) void k_i_nodes(ImportArgs a) {
+	const Header* hdr = reinterpret_cast<const Header*>(a.scratch);
+	const uint32_t t = blockIdx.x * LANE_TPB + threadIdx.x;
+	if (t >= a.n || hdr->ok == 0u) return;
+	const uint32_t* first = reinterpret_cast<const uint32_t*>(a.scratch + a.lay.first);
+	CopyItem* items = reinterpret_cast<CopyItem*>(a.scratch + a.lay.items);
+	const SimlodExportNode e = a.table[t];
+	const bool leaf = e.childMask == 0u;
+	const uint32_t ns = e.numSamples, nch = ceil_chunks(ns), f = first[t];
+	SimlodChunk* head = ns != 0u ? reinterpret_cast<SimlodChunk*>(a.pers + CHUNK_BASE + (uint64_t)f * CHUNK_STRIDE) : nullptr;
+	SimlodNode nd;
+	uint32_t r = 0;
+	for (int k = 0; k < 8; k++) nd.children[k] = (e.childMask & (1u << k)) ? a.nodes + e.firstChild + r++ : nullptr;
+	nd.counter = leaf ? ns : 0u;
+	nd.numPoints = leaf ? ns : 0u;
+	nd.level = e.level; nd.X = e.X; nd.Y = e.Y; nd.Z = e.Z;
+	nd.countIteration = 0u; nd.countFlag = 0u;
+	// 'r' and one digit per level below the root, the octant the path takes there (construct_expand.inc: the builder's names)
+	for (int k = 0; k < 20; k++) nd.name[k] = 0;
+	nd.name[0] = 'r';
+	for (uint32_t l = 1; l <= e.level && l < 20u; l++) {
+		const uint32_t s = e.level - l;
+		nd.name[l] = (uint8_t)('0' + ((((e.X >> s) & 1u) << 2) | (((e.Y >> s) & 1u) << 1) | ((e.Z >> s) & 1u)));
+	}
+	nd.visible = 0; nd.isFiltered = 0; nd.isLeaf = 0; nd.isLarge = 0;
+	nd.grid = nullptr;
+	nd.points = leaf ? head : nullptr;
+	nd.voxelChunks = leaf ? nullptr : head;
+	nd.numVoxels = leaf ? 0u : ns;
+	nd.numVoxelsStored = nd.numVoxels;
+	a.nodes[t] = nd;
+	// the list: consecutive chunks, `next` as the builder leaves it (the last one NULL), the head's size / padding_0 the tail's address
+	// (construct_begin.inc tail_of), the other chunks' 0
+	const uint64_t src0 = reinterpret_cast<uint64_t>(a.samples + e.firstSample);
+	for (uint32_t k = 0; k < nch; k++) {
+		SimlodChunk* c = reinterpret_cast<SimlodChunk*>(a.pers + CHUNK_BASE + (uint64_t)(f + k) * CHUNK_STRIDE);
+		c->next = k + 1u < nch ? reinterpret_cast<SimlodChunk*>(reinterpret_cast<uint8_t*>(c) + CHUNK_STRIDE) : nullptr;
+		*reinterpret_cast<uint64_t*>(&c->size) = k == 0u ? reinterpret_cast<uint64_t>(a.pers + CHUNK_BASE + (uint64_t)(f + nch - 1u) * CHUNK_STRIDE) : 0ull;
+		CopyItem it;
+		it.src = src0 + (uint64_t)k * SIMLOD_POINTS_PER_CHUNK * sizeof(SimlodPoint);
+		it.dst = reinterpret_cast<uint64_t>(c->points);
+		it.count = min(ns - k * SIMLOD_POINTS_PER_CHUNK, SIMLOD_POINTS_PER_CHUNK);
+		it.pad0 = 0; it.pad1 = 0;
+		items[f + k] = it;
+	}
+}
+
+__global__ void k_i_finish(ImportArgs a) {
+	const Header* hdr = reinterpret_cast<const Header*>(a.scratch);
+	if (hdr->ok == 0u) return;
+	SimlodAllocatorGlobal* alloc = reinterpret_cast<SimlodAllocatorGlobal*>(a.pers);
+	alloc->buffer = a.pers;
+	alloc->offset = CHUNK_BASE + hdr->totalChunks * CHUNK_STRIDE;
+	SimlodStats s{};
+	s.numNodes = a.n;
+	s.numInner = hdr->counts[0]; s.numLeaves = hdr->counts[1]; s.numNonemptyLeaves = hdr->counts[2];
+	s.numPoints = hdr->counts[3]; s.numVoxels = hdr->counts[4];
+	s.numChunksPoints = hdr->counts[5]; s.numChunksVoxels = hdr->counts[6];
+	s.allocatedBytes_persistent = alloc->offset;
+	*a.stats = s;
+}
+
+uint32_t copy_grid(uint64_t itemCap) {
+	const uint64_t g = (uint64_t)device_info().numCUs * 8u;                 // 8 workgroups of 256 lanes per CU
+	return (uint32_t)(itemCap < g ? (itemCap == 0u ? 1u : itemCap) : g);
+}
+
+}  // namespace
+
+uint64_t export_min_bytes(uint32_t nodeCapacity, uint64_t sampleCapacity) { return Layout(nodeCapacity, sampleCapacity).bytes; }
+
+int launch_export(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                  SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodExportCounts* counts, hipStream_t stream) {
+	if (nodes == nullptr || stats == nullptr || scratch == nullptr || table == nullptr || counts == nullptr || (samples == nullptr && sampleCapacity != 0u))
+		return (int)hipErrorInvalidValue;
+	if (select > SIMLOD_EXPORT_VISIBLE || scratchBytes < export_min_bytes(tableCapacity, sampleCapacity)) return (int)hipErrorInvalidValue;
+	if (select == SIMLOD_EXPORT_VISIBLE && !array_state(ctx, nodes).rendered) return (int)hipErrorInvalidValue;
+	ExportArgs a{};
+	a.nodes = nodes; a.stats = stats; a.maxLevel = maxLevel; a.select = select; a.cap = tableCapacity;
+	a.scratch = reinterpret_cast<uint8_t*>(scratch); a.table = table; a.samples = samples; a.sampleCap = sampleCapacity; a.counts = counts;
+	a.lay = Layout(tableCapacity, sampleCapacity);
+	LeafTableRef lt;
+	if (find_leaf_table(ctx, nodes, lt) && lt.slots <= LEAF_ROW_SLOTS) {
+		a.lt = lt.table; a.ltPers = lt.pers; a.ltMagic = lt.magic; a.ltBatch = lt.batch; a.ltNodes = lt.tableNodes; a.ltSig = lt.sig;
+		a.ltMagicValue = lt.magicValue; a.ltSlots = lt.slots; a.ltRows = lt.rows;
+	}
+	SIMLOD_LAUNCH(k_x_hier, dim3(1), dim3(WG_TPB), stream, a);
+	SIMLOD_LAUNCH(k_x_scan, dim3(1), dim3(WG_TPB), stream, a);
+	if (tableCapacity != 0u) SIMLOD_LAUNCH(k_x_dir, dim3((tableCapacity + LANE_TPB - 1u) / LANE_TPB), dim3(LANE_TPB), stream, a);
+	SIMLOD_LAUNCH(k_copy, dim3(copy_grid(a.lay.itemCap)), dim3(LANE_TPB), stream, (const uint8_t*)a.scratch, a.lay.items);
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+int launch_import(Context& ctx, const SimlodExportNode* table, uint32_t numNodes, const SimlodPoint* samples, uint64_t numSamples, void* scratch,
+                  uint64_t scratchBytes, uint8_t* pers, uint64_t persCapacity, SimlodNode* nodes, SimlodStats* stats, hipStream_t stream) {
+	if (table == nullptr || scratch == nullptr || pers == nullptr || nodes == nullptr || stats == nullptr || (samples == nullptr && numSamples != 0u))
+		return (int)hipErrorInvalidValue;
+	if (numNodes == 0u || numNodes > ctx.nodeCapacity.load() || scratchBytes < export_min_bytes(numNodes, numSamples)) return (int)hipErrorInvalidValue;
+	ImportArgs a{};
+	a.table = table; a.n = numNodes; a.samples = samples; a.numSamples = numSamples; a.scratch = reinterpret_cast<uint8_t*>(scratch);
+	a.lay = Layout(numNodes, numSamples); a.pers = pers; a.persCap = persCapacity; a.nodes = nodes; a.stats = stats;
+	SIMLOD_LAUNCH(k_i_validate, dim3(1), dim3(WG_TPB), stream, a);
+	SIMLOD_LAUNCH(k_i_nodes, dim3((numNodes + LANE_TPB - 1u) / LANE_TPB), dim3(LANE_TPB), stream, a);
+	SIMLOD_LAUNCH(k_copy, dim3(copy_grid(a.lay.itemCap)), dim3(LANE_TPB), stream, (const uint8_t*)a.scratch, a.lay.items);
+	SIMLOD_LAUNCH(k_i_finish, dim3(1), dim3(1), stream, a);
+	if (profile_enabled()) profile_close(stream);
+	const int rc = (int)hipGetLastError();
+	if (rc != 0) return rc;
+	// the builder's side tables and its chunk table describe the octree that was there (simlod_octree_image_replaced)
+	forget_leaf_table(ctx, nodes);
+	ctx.sideTablesStale.store(true);
+	array_event(ctx, nodes, ARRAY_IMPORTED);
+	return 0;
+}
+
+}  // namespace simlod

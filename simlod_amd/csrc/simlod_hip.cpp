@@ -157,6 +157,31 @@ bool find_leaf_table(Context& ctx, const void* nodes, LeafTableRef& ref) {
 	return false;
 }
 
+// ---- per node array: rendered since the last reset / construct / import, holds an imported octree (simlod_internal.hpp ArrayState) ------
+void array_event(Context& ctx, const void* nodes, ArrayEvent e) {
+	std::lock_guard<std::mutex> hold(ctx.arraysLock);
+	ArrayState* st = nullptr;
+	for (ArrayState& s : ctx.arrays) if (s.nodes == nodes) st = &s;
+	if (st == nullptr) {
+		if (e == ARRAY_RESET || e == ARRAY_CONSTRUCT) return;       // (nothing to forget)
+		if (ctx.arrays.size() >= 64) ctx.arrays.erase(ctx.arrays.begin());
+		ctx.arrays.push_back(ArrayState{nodes, false, false});
+		st = &ctx.arrays.back();
+	}
+	switch (e) {
+	case ARRAY_RESET: st->rendered = false; st->imported = false; break;
+	case ARRAY_CONSTRUCT: st->rendered = false; break;
+	case ARRAY_RENDERED: st->rendered = true; break;
+	case ARRAY_IMPORTED: st->rendered = false; st->imported = true; break;
+	}
+}
+
+ArrayState array_state(Context& ctx, const void* nodes) {
+	std::lock_guard<std::mutex> hold(ctx.arraysLock);
+	for (const ArrayState& s : ctx.arrays) if (s.nodes == nodes) return s;
+	return ArrayState{nodes, false, false};
+}
+
 // ---- launch sizing: how many batches a kernel_construct launch can find (simlod_internal.hpp launch_plan) ---------------------------------
 // The reference's kernel loops over whatever has been uploaded when it starts (voxels.cu:870-885); here every group of batches is a handful of kernel
 // launches the HOST enqueues before it can read that number (the upload counter lives on the device).  Kernels of a group without a batch leave at
@@ -472,7 +497,9 @@ int simlod_launch_reset(const SimlodUniforms* uniforms, uint8_t* buffer_octree, 
                         void* cudaprint, uint32_t* numBatchesUploaded, uint32_t* batchSizes, void* stream) {
 	(void)cudaprint;   // CudaPrint's device side is a no-op (modules/CudaPrint/CudaPrint.cuh:49-51): accepted, unused
 	if (!uniforms || !buffer_octree || !nodes || !stats || !numBatchesUploaded || !batchSizes) return (int)hipErrorInvalidValue;
-	return launch_reset(context_of(nodes), uniforms, buffer_octree, nodes, stats, numBatchesUploaded, batchSizes, (hipStream_t)stream);
+	Context& ctx = context_of(nodes);
+	array_event(ctx, nodes, ARRAY_RESET);
+	return launch_reset(ctx, uniforms, buffer_octree, nodes, stats, numBatchesUploaded, batchSizes, (hipStream_t)stream);
 }
 
 int simlod_launch_construct(const SimlodUniforms* uniforms, SimlodPoint* points, uint32_t* buffer, uint8_t* buffer_persistent,
@@ -481,7 +508,10 @@ int simlod_launch_construct(const SimlodUniforms* uniforms, SimlodPoint* points,
 	(void)cudaprint;
 	if (!uniforms || !points || !buffer || !buffer_persistent || !nodes || !stats || !frameStartTimestamp ||
 	    !numBatchesUploaded_volatile || !batchSizes) return (int)hipErrorInvalidValue;
-	return build::launch_construct(context_of(nodes), uniforms, points, buffer, buffer_persistent, nodes, stats, frameStartTimestamp, numBatchesUploaded_volatile, batchSizes, (hipStream_t)stream);
+	Context& ctx = context_of(nodes);
+	if (array_state(ctx, nodes).imported) return (int)hipErrorInvalidValue;      // an imported octree has no grids and no builder state
+	array_event(ctx, nodes, ARRAY_CONSTRUCT);
+	return build::launch_construct(ctx, uniforms, points, buffer, buffer_persistent, nodes, stats, frameStartTimestamp, numBatchesUploaded_volatile, batchSizes, (hipStream_t)stream);
 }
 
 int simlod_decode_las(const void* records, uint64_t numPoints, uint32_t bytesPerPoint, uint32_t format, const double scale[3],
@@ -491,7 +521,21 @@ int simlod_decode_las(const void* records, uint64_t numPoints, uint32_t bytesPer
 
 int simlod_launch_colorfilter(const SimlodUniforms* uniforms, uint32_t* buffer, SimlodNode* nodes, uint32_t* numNodes, SimlodStats* stats, void* stream) {
 	if (!uniforms || !buffer || !nodes || (!numNodes && !stats)) return (int)hipErrorInvalidValue;
-	return launch_colorfilter(context_of(nodes), uniforms, buffer, nodes, numNodes, stats, (hipStream_t)stream);
+	Context& ctx = context_of(nodes);
+	if (array_state(ctx, nodes).imported) return (int)hipErrorInvalidValue;
+	return launch_colorfilter(ctx, uniforms, buffer, nodes, numNodes, stats, (hipStream_t)stream);
+}
+
+uint64_t simlod_export_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleCapacity) { return export_min_bytes(nodeCapacity, sampleCapacity); }
+
+int simlod_export_octree(const SimlodNode* nodes, const SimlodStats* stats, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                         SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodExportCounts* counts, void* stream) {
+	return launch_export(context_of(nodes), nodes, stats, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples, sampleCapacity, counts, (hipStream_t)stream);
+}
+
+int simlod_import_octree(const SimlodExportNode* table, uint32_t numNodes, const SimlodPoint* samples, uint64_t numSamples, void* scratch,
+                         uint64_t scratchBytes, uint8_t* persistent, uint64_t persistentCapacity, SimlodNode* nodes, SimlodStats* stats, void* stream) {
+	return launch_import(context_of(nodes), table, numNodes, samples, numSamples, scratch, scratchBytes, persistent, persistentCapacity, nodes, stats, (hipStream_t)stream);
 }
 
 uint64_t simlod_colorfilter_buffer_min_bytes(void) { return colorfilter_min_bytes(default_context().nodeCapacity.load()); }
@@ -510,14 +554,20 @@ int simlod_launch_render(uint32_t* buffer, const SimlodUniforms* uniforms, Simlo
                          SimlodStats* stats, uint64_t* frameStartTimestamp, void* cudaprint, void* stream) {
 	(void)cudaprint;
 	if (!uniforms || !buffer || !nodes || !stats || !frameStartTimestamp) return (int)hipErrorInvalidValue;
-	return launch_render(context_of(nodes), buffer, uniforms, nodes, colorbuffer, stats, frameStartTimestamp, (hipStream_t)stream, RENDER_ALL);
+	Context& ctx = context_of(nodes);
+	const int rc = launch_render(ctx, buffer, uniforms, nodes, colorbuffer, stats, frameStartTimestamp, (hipStream_t)stream, RENDER_ALL);
+	if (rc == 0) array_event(ctx, nodes, ARRAY_RENDERED);           // (SIMLOD_EXPORT_VISIBLE: the visible / isLarge bytes are this frame's)
+	return rc;
 }
 
 int simlod_launch_render_part(uint32_t part, uint32_t* buffer, const SimlodUniforms* uniforms, SimlodNode* nodes, uint32_t* colorbuffer,
                               SimlodStats* stats, uint64_t* frameStartTimestamp, void* cudaprint, void* stream) {
 	(void)cudaprint;
 	if (!uniforms || !buffer || !nodes || !stats || !frameStartTimestamp || part > 3) return (int)hipErrorInvalidValue;
-	return launch_render(context_of(nodes), buffer, uniforms, nodes, colorbuffer, stats, frameStartTimestamp, (hipStream_t)stream, 1u << part);
+	Context& ctx = context_of(nodes);
+	const int rc = launch_render(ctx, buffer, uniforms, nodes, colorbuffer, stats, frameStartTimestamp, (hipStream_t)stream, 1u << part);
+	if (rc == 0 && part == 0) array_event(ctx, nodes, ARRAY_RENDERED);
+	return rc;
 }
 
 // ---- a frame composed across ranks in one call (include/simlod_hip.h) -------------------------------------------------------------------
@@ -534,6 +584,7 @@ int simlod_render_frame_composed(uint32_t* buffer, const SimlodUniforms* u, Siml
 	auto red = [&](uint32_t plane, uint64_t offset, uint64_t count, uint32_t elemBytes, uint32_t op) { return reduce ? reduce(user, plane, base + offset, count, elemBytes, op, stream) : 0; };
 	const bool hqs = u->useHighQualityShading != 0, boxes = u->showBoundingBox != 0;
 	int rc = part(0);
+	if (rc == 0) array_event(ctx, nodes, ARRAY_RENDERED);
 	if (rc == 0 && hqs) rc = red(SIMLOD_PLANE_DEPTH, render_depth_plane_offset(W, H), px, 4, SIMLOD_REDUCE_MIN);
 	if (rc == 0 && hqs) rc = part(1);
 	if (rc == 0 && hqs) rc = red(SIMLOD_PLANE_SUMS, render_sum_planes_offset(W, H), px * 4, 4, SIMLOD_REDUCE_SUM);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "simlod_abi.h"
+#include "simlod_hip.h"
 
 namespace simlod {
 
@@ -78,6 +79,12 @@ struct FrameFeedback { const void* buffer; volatile uint32_t* seen; bool bins; u
 struct SideStream;                                           // construct.hip: the second stream of kernel_construct and its events
 void destroy_side_stream(SideStream* s);
 
+// What the host knows of a node array beyond the builder's tables (export.hip): a kernel_render ran on it since its last reset, construct or
+// import (SIMLOD_EXPORT_VISIBLE reads the visible / isLarge bytes that frame wrote) | it holds an imported octree (no grids, no builder state:
+// kernel_construct and the colour filter refuse it until the next reset).  Keyed by node array, not by context: two arrays may share one.
+struct ArrayState { const void* nodes; bool rendered, imported; };
+enum ArrayEvent : int { ARRAY_RESET, ARRAY_CONSTRUCT, ARRAY_RENDERED, ARRAY_IMPORTED };
+
 struct Context {
 	std::atomic<uint32_t> nodeCapacity{263157u};             // 40 000 000 B / 152 B, main_progressive_octree.cpp:552
 	std::atomic<uint32_t> ingestMode{0u};                    // 0 = exact (one batch at a time, the reference's granularity), 1 = coalesced
@@ -94,6 +101,8 @@ struct Context {
 	std::vector<LaunchHistory> history;
 	std::mutex framesLock;
 	std::vector<FrameFeedback> frames;
+	std::mutex arraysLock;
+	std::vector<struct ArrayState> arrays;                    // per node array: what export / import need to know of it (array_event)
 	hipEvent_t gateEvent[64] = {};                            // per device ordinal: the end of this context's latest k_expand, when it runs without a second stream (expand_gate)
 	Context();
 	~Context();
@@ -105,6 +114,8 @@ struct Context {
 // the frame's other parts.  nullptr (no page-locked memory): every frame sorts.
 uint32_t* frame_feedback(Context& ctx, const void* buffer, uint32_t parts, bool& possible, bool& bins, uint64_t& bufferBytes);   // parts: RENDER_* of this launch; bufferBytes: what the allocation behind `buffer` holds from `buffer` on
 void frame_feedback_no_bins(Context& ctx, const void* buffer);
+void array_event(Context& ctx, const void* nodes, ArrayEvent e);
+ArrayState array_state(Context& ctx, const void* nodes);      // {nodes, false, false} for an array nothing was recorded for
 Context& context_of(const void* nodes);                      // the context `nodes` is attached to, else the default one
 uint32_t live_contexts();                                    // contexts that exist right now (the default one included once it has been used)
 
@@ -169,6 +180,11 @@ int launch_decode_las(const void* records, uint64_t numPoints, uint32_t bytesPer
                       const double* offset, SimlodPoint* out, hipStream_t stream);
 int launch_colorfilter(Context& ctx, const SimlodUniforms* u, uint32_t* buffer, SimlodNode* nodes, const uint32_t* numNodes, SimlodStats* stats, hipStream_t stream);
 uint64_t colorfilter_min_bytes(uint32_t nodeCapacity);
+int launch_export(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                  SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodExportCounts* counts, hipStream_t stream);
+int launch_import(Context& ctx, const SimlodExportNode* table, uint32_t numNodes, const SimlodPoint* samples, uint64_t numSamples, void* scratch,
+                  uint64_t scratchBytes, uint8_t* pers, uint64_t persCapacity, SimlodNode* nodes, SimlodStats* stats, hipStream_t stream);
+uint64_t export_min_bytes(uint32_t nodeCapacity, uint64_t sampleCapacity);
 int launch_generate_terrain(SimlodPoint* out, uint64_t numPoints, uint64_t firstIndex, uint64_t pointsPerTile, uint32_t seed, uint32_t tilesX,
                             const float tileExtent[3], float swathWidth, hipStream_t stream);
 enum : uint32_t { RENDER_FIRST = 1u, RENDER_COLOR = 2u, RENDER_RESOLVE = 4u, RENDER_OUTPUT = 8u, RENDER_ALL = 15u };

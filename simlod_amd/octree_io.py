@@ -1,0 +1,181 @@
+"""A built octree in a pointer-free form: the export table and sample array of simlod_export_octree (include/simlod_hip.h, "octree
+export / import"), its host-side validation, and a file format for it.
+
+File format (little-endian throughout):
+
+    offset  bytes  field
+         0      8  magic b"SIMLODX\\0"
+         8      4  version (1)
+        12      4  select (0 all, 1 cut, 2 visible)
+        16      4  max_level (20: every level)
+        20      4  header bytes (64)
+        24      8  numNodes
+        32      8  numSamples
+        40     12  box_min, 3 x float32
+        52     12  box_max, 3 x float32
+        64          numNodes x 40-byte SimlodExportNode (abi.export_node_dtype)
+                    numSamples x 16-byte SimlodPoint (abi.point_dtype)
+
+`load` checks the header, the file size and the table (`validate`) before anything reaches a device.
+"""
+import numpy as np
+import torch
+
+from . import abi
+
+MAGIC = b"SIMLODX\0"
+VERSION = 1
+HEADER_BYTES = 64
+header_dtype = np.dtype({
+    "names": ["magic", "version", "select", "max_level", "header_bytes", "numNodes", "numSamples", "box_min", "box_max"],
+    "formats": ["S8", "<u4", "<u4", "<u4", "<u4", "<u8", "<u8", ("<f4", 3), ("<f4", 3)],
+    "offsets": [0, 8, 12, 16, 20, 24, 32, 40, 52],
+    "itemsize": HEADER_BYTES,
+})
+
+_POPCOUNT = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint32)
+
+
+def _as_bytes_tensor(a):
+    if isinstance(a, torch.Tensor):
+        return a.reshape(-1).view(torch.uint8)
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1))
+
+
+class OctreeExport:
+    """The table (numNodes x abi.export_node_dtype) and the samples (numSamples x abi.point_dtype) as uint8 tensors on the host or on a device,
+    with what is needed to render them again: the box of the uniforms they were built with, and which part of the octree they hold."""
+
+    def __init__(self, table, samples, box_min, box_max, max_level=20, select=abi.EXPORT_ALL):
+        self.table_tensor = _as_bytes_tensor(table)
+        self.samples_tensor = _as_bytes_tensor(samples)
+        if self.table_tensor.numel() % abi.export_node_dtype.itemsize or self.samples_tensor.numel() % abi.point_dtype.itemsize:
+            raise ValueError("table / samples are not whole records")
+        self.box_min = tuple(float(v) for v in np.asarray(box_min, dtype=np.float32).reshape(3))
+        self.box_max = tuple(float(v) for v in np.asarray(box_max, dtype=np.float32).reshape(3))
+        self.max_level = int(max_level)
+        self.select = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
+        self._nodes = self._samples = None
+
+    @property
+    def num_nodes(self):
+        return self.table_tensor.numel() // abi.export_node_dtype.itemsize
+
+    @property
+    def num_samples(self):
+        return self.samples_tensor.numel() // abi.point_dtype.itemsize
+
+    @property
+    def device(self):
+        return self.table_tensor.device
+
+    @property
+    def nodes(self):
+        """The table as a numpy array of abi.export_node_dtype (copied to the host once)."""
+        if self._nodes is None:
+            self._nodes = self.table_tensor.cpu().numpy().view(abi.export_node_dtype)
+        return self._nodes
+
+    @property
+    def samples(self):
+        """The samples as a numpy array of abi.point_dtype (copied to the host once)."""
+        if self._samples is None:
+            self._samples = self.samples_tensor.cpu().numpy().view(abi.point_dtype)
+        return self._samples
+
+    def to(self, device):
+        return OctreeExport(self.table_tensor.to(device), self.samples_tensor.to(device), self.box_min, self.box_max, self.max_level, self.select)
+
+    def validate(self):
+        """The host-side mirror of the checks simlod_import_octree runs on the device; raises ValueError naming the first that fails."""
+        validate_table(self.nodes, self.num_samples)
+        return self
+
+    def save(self, path):
+        h = np.zeros(1, dtype=header_dtype)
+        h["magic"], h["version"], h["select"], h["max_level"], h["header_bytes"] = MAGIC, VERSION, self.select, self.max_level, HEADER_BYTES
+        h["numNodes"], h["numSamples"] = self.num_nodes, self.num_samples
+        h["box_min"], h["box_max"] = self.box_min, self.box_max
+        with open(path, "wb") as f:
+            f.write(h.tobytes())
+            f.write(self.table_tensor.cpu().numpy().tobytes())
+            f.write(self.samples_tensor.cpu().numpy().tobytes())
+
+    @classmethod
+    def load(cls, path):
+        """Read a file written by save(); the table is validated before the export is returned (host tensors)."""
+        raw = np.fromfile(path, dtype=np.uint8)
+        if raw.size < HEADER_BYTES:
+            raise ValueError(f"{path}: truncated header")
+        h = raw[:HEADER_BYTES].view(header_dtype)[0]
+        if bytes(h["magic"]).ljust(8, b"\0") != MAGIC:
+            raise ValueError(f"{path}: not an octree export (magic)")
+        if int(h["version"]) != VERSION or int(h["header_bytes"]) != HEADER_BYTES:
+            raise ValueError(f"{path}: unsupported version {int(h['version'])}")
+        if int(h["select"]) > abi.EXPORT_VISIBLE:
+            raise ValueError(f"{path}: unknown selection {int(h['select'])}")
+        n, m = int(h["numNodes"]), int(h["numSamples"])
+        tb, sb = n * abi.export_node_dtype.itemsize, m * abi.point_dtype.itemsize
+        if raw.size != HEADER_BYTES + tb + sb:
+            raise ValueError(f"{path}: {raw.size} bytes, the header announces {HEADER_BYTES + tb + sb}")
+        ex = cls(raw[HEADER_BYTES: HEADER_BYTES + tb].copy(), raw[HEADER_BYTES + tb:].copy(), h["box_min"], h["box_max"], int(h["max_level"]), int(h["select"]))
+        return ex.validate()
+
+
+def validate_table(t, num_samples):
+    """Checks of a table against itself (and the sample count): see OctreeExport.validate."""
+    t = np.asarray(t).view(abi.export_node_dtype)
+    n = len(t)
+    if n == 0:
+        raise ValueError("empty table: no root")
+    if n > 0xFFFFFFFE:
+        raise ValueError("too many nodes")
+    level = t["level"].astype(np.int64)
+    if (level > abi.MAX_DEPTH).any():
+        raise ValueError("level above 20")
+    if (t["reserved"] != 0).any() or (t["flags"] & ~np.uint8(abi.EXPORT_FLAG_LEAF | abi.EXPORT_FLAG_SELECTED)).any():
+        raise ValueError("reserved bits set")
+    r = t[0]
+    if int(r["parent"]) != abi.EXPORT_NONE or int(r["level"]) != 0 or int(r["X"]) | int(r["Y"]) | int(r["Z"]):
+        raise ValueError("entry 0 is not the root")
+    idx = np.arange(n, dtype=np.int64)
+    mask = t["childMask"].astype(np.int64)
+    kids = _POPCOUNT[mask].astype(np.int64)
+    fc = t["firstChild"].astype(np.int64)
+    has = mask != 0
+    if (fc[~has] != abi.EXPORT_NONE).any():
+        raise ValueError("firstChild set without children")
+    if has.any():
+        if (fc[has] <= idx[has]).any() or (fc[has] + kids[has] > n).any():
+            raise ValueError("child index out of range")
+        if (level[has] >= abi.MAX_DEPTH).any():
+            raise ValueError("children below level 20")
+        expect = 1 + np.concatenate([[0], np.cumsum(kids)[:-1]])
+        if (fc[has] != expect[has]).any():
+            raise ValueError("children not in breadth-first order")
+    if 1 + int(kids.sum()) != n:
+        raise ValueError("entries that are nobody's child")
+    if n > 1:
+        c = idx[1:]
+        p = t["parent"][1:].astype(np.int64)
+        if (p >= c).any():
+            raise ValueError("parent index out of range")
+        pt = t[p]
+        if (level[1:] != pt["level"].astype(np.int64) + 1).any():
+            raise ValueError("level does not match the parent's")
+        for a in ("X", "Y", "Z"):
+            if ((t[a][1:] >> 1) != pt[a]).any():
+                raise ValueError(f"coordinate {a} does not match the parent's")
+        k = ((t["X"][1:] & 1) << 2 | (t["Y"][1:] & 1) << 1 | (t["Z"][1:] & 1)).astype(np.int64)
+        pm = pt["childMask"].astype(np.int64)
+        if ((pm >> k) & 1 == 0).any():
+            raise ValueError("the parent does not list this octant")
+        rank = _POPCOUNT[pm & ((1 << k) - 1)].astype(np.int64)
+        if (pt["firstChild"].astype(np.int64) + rank != c).any():
+            raise ValueError("the parent lists another entry in this octant")
+    ns = t["numSamples"].astype(np.uint64)
+    scan = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.uint64)
+    if (t["firstSample"] != scan).any():
+        raise ValueError("firstSample is not the scan of numSamples")
+    if int(ns.sum()) != int(num_samples):
+        raise ValueError(f"the table holds {int(ns.sum())} samples, the sample array {int(num_samples)}")

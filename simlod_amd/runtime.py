@@ -82,6 +82,10 @@ def lib():
         L.simlod_colorfilter_buffer_min_bytes.restype = u64
         L.simlod_generate_terrain.argtypes = [vp, u64, u64, u64, u32, u32, ctypes.POINTER(ctypes.c_float), vp]
         L.simlod_generate_terrain_scan.argtypes = [vp, u64, u64, u64, u32, u32, ctypes.POINTER(ctypes.c_float), ctypes.c_float, vp]
+        L.simlod_export_buffer_min_bytes.restype = u64
+        L.simlod_export_buffer_min_bytes.argtypes = [u32, u64]
+        L.simlod_export_octree.argtypes = [vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
+        L.simlod_import_octree.argtypes = [vp, u32, vp, u64, vp, u64, vp, u64, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -97,6 +101,7 @@ EXPORTED_SYMBOLS = [
     "simlod_octree_image_replaced", "simlod_render_frame_composed", "simlod_render_frame_rccl", "simlod_context_set_trunk_mask", "simlod_rccl_version",
     "simlod_context_hint_pending_batches", "simlod_upload_counter_written",
     "simlod_profile_enable", "simlod_profile_collect", "simlod_generate_terrain", "simlod_generate_terrain_scan", "simlod_launch_colorfilter", "simlod_colorfilter_buffer_min_bytes",
+    "simlod_export_buffer_min_bytes", "simlod_export_octree", "simlod_import_octree",
 ]
 
 
@@ -544,6 +549,52 @@ class DeviceOctree:
         self.momentary[:4096].zero_()          # control block: the builder's side tables describe the previous octree
         _check(self.L.simlod_octree_image_replaced(self.nodes.data_ptr()), "simlod_octree_image_replaced")
         self.processed_host = int(st["batchletIndex"][0])
+
+    # -- export / import (include/simlod_hip.h, "octree export / import"; simlod_amd/octree_io.py) ----------------------------------------
+    def _export_scratch(self, need):
+        t = self.__dict__.get("_xscratch")
+        if t is None or t.numel() < need:
+            t = self._xscratch = torch.empty(max(int(need), 1 << 20), dtype=torch.uint8, device=self.device)
+        return t
+
+    def export_octree(self, uniforms, max_level=None, select="all"):
+        """The octree as an octree_io.OctreeExport on this device: nodes with level <= max_level (None: all) and the samples of the nodes
+        `select` names ("all", "cut": the leaves of the truncated table, "visible": what the last render drew).  Reads Stats once to size
+        the outputs; raises SimlodError when the device reports an error."""
+        from .octree_io import OctreeExport
+        sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
+        ml = abi.MAX_DEPTH if max_level is None else max(0, min(int(max_level), abi.MAX_DEPTH))
+        st = self.read_stats()
+        nn, ns = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+        need = int(self.L.simlod_export_buffer_min_bytes(nn, ns))
+        scratch = self._export_scratch(need)
+        table = torch.empty(max(nn, 1) * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        samples = torch.empty(max(ns, 1) * abi.point_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        counts = torch.zeros(abi.export_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        _check(self.L.simlod_export_octree(self._p(self.nodes), self._p(self.stats), ml, sel, self._p(scratch), ctypes.c_uint64(scratch.numel()),
+                                           self._p(table), nn, self._p(samples), ctypes.c_uint64(ns), self._p(counts), self._stream()), "simlod_export_octree")
+        c = counts.cpu().numpy().view(abi.export_counts_dtype)[0]
+        if int(c["error"]) != 0:
+            raise SimlodError(f"simlod_export_octree reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples)")
+        u = np.asarray(uniforms).reshape(-1)[0]
+        return OctreeExport(table[: int(c["numNodes"]) * abi.export_node_dtype.itemsize], samples[: int(c["numSamples"]) * abi.point_dtype.itemsize],
+                            u["boxMin"], u["boxMax"], ml, sel)
+
+    def import_octree(self, export, check=True):
+        """Replace this object's octree by `export` (an octree_io.OctreeExport on the host or on a device): simlod_import_octree validates the
+        table on the device and writes a renderable octree into the node array and the persistent buffer.  check: read Stats back and raise
+        SimlodError when the table failed validation (SIMLOD_ERR_IMPORT).  Until the next reset, construct() and colorfilter() refuse it."""
+        table = export.table_tensor.to(self.device)
+        samples = export.samples_tensor.to(self.device)
+        n, m = export.num_nodes, export.num_samples
+        need = int(self.L.simlod_export_buffer_min_bytes(n, m))
+        scratch = self._export_scratch(need)
+        _check(self.L.simlod_import_octree(self._p(table), n, self._p(samples), ctypes.c_uint64(m), self._p(scratch), ctypes.c_uint64(scratch.numel()),
+                                           self._p(self.persistent), ctypes.c_uint64(self.persistent_bytes), self._p(self.nodes), self._p(self.stats),
+                                           self._stream()), "simlod_import_octree")
+        self.uploaded_host = self.processed_host = 0
+        if check and int(self.read_stats()["dbg"]) & abi.SIMLOD_ERR_IMPORT:
+            raise SimlodError("simlod_import_octree: the table failed validation on the device (SIMLOD_ERR_IMPORT)")
 
     def download_image(self):
         """(nodes, persistent, numNodes, device base addresses) — the octree image as host arrays, pointers untouched."""

@@ -1,0 +1,103 @@
+"""Octree export / import on the config-2 stand-in (bench.py's workload: 36 M-point terrain in 1 M batches, exact mode): export ALL, export
+CUT@20, import, and a plain device-to-device copy of the same sample bytes as the ceiling — each timed `--reps` times after a warm-up with
+device events around the bare C call.  Prints one JSON line.  Per-kernel split: run it under `rocprofv3 --kernel-trace --stats -- python ...`."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from simlod_amd import abi, camera, synthetic  # noqa: E402
+from simlod_amd.runtime import DeviceOctree  # noqa: E402
+
+PEAK_GBS = 8000.0
+
+
+def timed(fn, reps, warmup=2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for a, b in ev:
+        a.record(); fn(); b.record()
+    torch.cuda.synchronize()
+    ms = np.array([a.elapsed_time(b) for a, b in ev])
+    return float(np.median(ms)), float(ms.min())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, default=36_000_000)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--persistent-gb", type=int, default=16)
+    args = ap.parse_args()
+    n_points, batch = args.points, abi.MAX_BATCH_SIZE
+    pts, box = synthetic.terrain(n_points, seed=7)
+    dev = DeviceOctree("cuda:0", persistent_bytes=args.persistent_gb << 30, max_pixels=1920 * 1080)
+    nb = (n_points + batch - 1) // batch
+    ring = dev.ring.view(torch.uint8)
+    for i in range(nb):
+        c = pts[i * batch:(i + 1) * batch]
+        ring[i * batch * 16: i * batch * 16 + len(c) * 16].copy_(torch.from_numpy(c.view(np.uint8).reshape(-1)))
+    T = camera.lookat_transform((1.8 * box[0], -1.2 * box[1], 1.4 * max(box)), (0.5 * box[0], 0.5 * box[1], 0.3 * box[2]), 1920, 1080)
+    u = dev.uniforms(1920, 1080, T, box)
+    dev.reset(u)
+    dev.batch_sizes[:nb] = torch.tensor([min(batch, n_points - i * batch) for i in range(nb)], dtype=torch.int32, device=dev.device)
+    dev.publish(nb)
+    dev.uploaded_host = nb
+    dev.drain(u)
+    st = dev.read_stats()
+    nn, ns = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    L = dev.L
+    need = int(L.simlod_export_buffer_min_bytes(nn, ns))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    table = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    samples = torch.empty(ns * 16, dtype=torch.uint8, device=dev.device)
+    counts = torch.zeros(16, dtype=torch.uint8, device=dev.device)
+    p = dev._p
+    stream = dev._stream()
+
+    def export(ml, sel):
+        rc = L.simlod_export_octree(p(dev.nodes), p(dev.stats), ml, sel, p(scratch), ctypes.c_uint64(need), p(table), nn, p(samples), ctypes.c_uint64(ns), p(counts), stream)
+        assert rc == 0
+
+    out = {"points": n_points, "numNodes": nn, "numSamples": ns, "reps": args.reps}
+    ms_all = timed(lambda: export(20, abi.EXPORT_ALL), args.reps)
+    c = counts.cpu().numpy().view(abi.export_counts_dtype)[0]
+    assert int(c["error"]) == 0 and int(c["numSamples"]) == ns and int(c["numNodes"]) == nn
+    ms_cut = timed(lambda: export(20, abi.EXPORT_CUT), args.reps)
+    n_cut = int(counts.cpu().numpy().view(abi.export_counts_dtype)[0]["numSamples"])
+    export(20, abi.EXPORT_ALL)
+    torch.cuda.synchronize()
+    dst = DeviceOctree("cuda:0", persistent_bytes=ns // 1000 * 16100 + nn * 16100 + (64 << 20), max_pixels=64 * 64)
+    nbytes = ns * 16
+
+    def imp():
+        rc = L.simlod_import_octree(p(table), nn, p(samples), ctypes.c_uint64(ns), p(scratch), ctypes.c_uint64(need), p(dst.persistent),
+                                    ctypes.c_uint64(dst.persistent_bytes), p(dst.nodes), p(dst.stats), stream)
+        assert rc == 0
+    ms_imp = timed(imp, args.reps)
+    assert int(dst.read_stats()["dbg"]) == 0 and int(dst.read_stats()["numNodes"]) == nn
+    copy_dst = torch.empty_like(samples)
+    ms_copy = timed(lambda: copy_dst.copy_(samples), args.reps)
+    copy_gbs = 2 * nbytes / (ms_copy[0] * 1e6)
+
+    def row(ms, nsamp):
+        b = 2 * nsamp * 16 + nn * 40
+        gbs = b / (ms[0] * 1e6)
+        return {"ms": round(ms[0], 4), "ms_min": round(ms[1], 4), "algorithmic_bytes": b, "GBs": round(gbs, 1),
+                "frac_of_peak": round(gbs / PEAK_GBS, 4), "frac_of_copy": round(gbs / copy_gbs, 4)}
+    out["export_all"] = row(ms_all, ns)
+    out["export_cut20"] = row(ms_cut, n_cut)
+    out["import"] = row(ms_imp, ns)
+    out["d2d_copy"] = {"ms": round(ms_copy[0], 4), "bytes": 2 * nbytes, "GBs": round(copy_gbs, 1), "frac_of_peak": round(copy_gbs / PEAK_GBS, 4)}
+    out["target"] = "export ALL >= 50 % of the copy rate"
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
