@@ -101,7 +101,10 @@ int simlod_set_node_capacity(uint32_t numNodes);
  * — every Node and Stats field after every batch is the reference's.  1 = COALESCED: all pending batches of a launch (<= 20, as many
  * as the momentary buffer holds) are ingested as one batch.  Topology, per-node sample multisets, occupancy bitsets, voxel positions
  * and counts do not depend on the granularity; the allocator / chunk-pool accounting (Stats.allocatedBytes_persistent,
- * numAllocatedChunks, chunkPoolSize) does: fewer intermediate chunks are ever allocated.  Default context. */
+ * numAllocatedChunks, chunkPoolSize) does: fewer intermediate chunks are ever allocated.  Default context.
+ * Voxel colours: the reference colours a voxel from a point of the first batch that hit its cell.  EXACT mode voxelizes a launch's batches in
+ * groups (SIMLOD_EXACT_GROUP, default 5): a voxel's colour comes from a point of the GROUP that holds that batch (or from a stored point an
+ * earlier batch brought); SIMLOD_EXACT_GROUP=1 gives the reference's outcome set.  COALESCED mode: from the launch that holds that batch. */
 int simlod_set_ingest_mode(uint32_t mode);
 
 /* Optional host hint: no more than `maxBatches` (1..20, default 20) ring batches are pending when kernel_construct is launched, so

@@ -73,6 +73,7 @@ def port_lib():
         lib.oracle_check_invariants.restype = ctypes.c_int
         lib.oracle_check_invariants.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 5
         lib.oracle_dump.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+        lib.oracle_voxel_cells.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_uint32] * 4 + [ctypes.c_void_p] * 2
         lib.oracle_gather.restype = ctypes.c_uint32
         lib.oracle_gather.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
         lib.ref_call_construct.argtypes = [ctypes.c_void_p] * 11
@@ -266,6 +267,17 @@ def gather_samples(head_ptr, count):
     out = np.zeros(count, dtype=abi.point_dtype)
     got = port_lib().oracle_gather(ctypes.c_void_p(int(head_ptr)), count, _ptr(out))
     return out[:got]
+
+
+def voxel_cells(uniforms, points, level, X, Y, Z):
+    """(cells uint32[n], centres float32[n, 3]): where sample_voxel puts each point in the 128^3 grid of node (level, X, Y, Z) —
+    pX + 128 pY + 128^2 pZ, or 0xffffffff for a point outside that node — and the voxel position it gives that cell (oracle_voxel_cells)."""
+    u = np.ascontiguousarray(uniforms).reshape(1)
+    pts = np.ascontiguousarray(points, dtype=abi.point_dtype)
+    cells = np.zeros(len(pts), dtype=np.uint32)
+    centres = np.zeros((len(pts), 3), dtype=np.float32)
+    port_lib().oracle_voxel_cells(_ptr(u), _ptr(pts), len(pts), int(level), int(X), int(Y), int(Z), _ptr(cells), _ptr(centres))
+    return cells, centres
 
 
 def rebase_image_to(nodes, num_nodes, persistent, old_nodes_base, old_persistent_base, new_nodes_base, new_persistent_base):

@@ -291,6 +291,18 @@ static void do_splitting(BuildEnv* e) {
 	for (uint32_t s = 0; s < c->numSpilling; s++) memset(c->spilling[s]->grid->values, 0, sizeof(SimlodOccupancyGrid));
 }
 
+/* the position of the voxel of cell (pX, pY, pZ) of a node, voxels.cu:103-114 */
+static void voxel_centre(float size, float minx, float miny, float minz, uint32_t level, uint32_t X, uint32_t Y, uint32_t Z,
+                         uint32_t pX, uint32_t pY, uint32_t pZ, SimlodPoint* v) {
+	float nodeSize = size / ldexpf(1.0f, (int)level);   /* pow(2.0f, level) is exact */
+	float nminx = ((float)X + 0.0f) * nodeSize + minx;
+	float nminy = ((float)Y + 0.0f) * nodeSize + miny;
+	float nminz = ((float)Z + 0.0f) * nodeSize + minz;
+	v->x = nminx + nodeSize * ((float)pX + 0.5f) / (float)SIMLOD_GRID_SIZE;
+	v->y = nminy + nodeSize * ((float)pY + 0.5f) / (float)SIMLOD_GRID_SIZE;
+	v->z = nminz + nodeSize * ((float)pZ + 0.5f) / (float)SIMLOD_GRID_SIZE;
+}
+
 /* sampleVoxel, voxels.cu:50-121 */
 static void sample_voxel(BuildEnv* e, SimlodNode* node, uint32_t pXf, uint32_t pYf, uint32_t pZf, const SimlodPoint* p) {
 	if (!node->grid) return;
@@ -303,19 +315,42 @@ static void sample_voxel(BuildEnv* e, SimlodNode* node, uint32_t pXf, uint32_t p
 	if (node->grid->values[word] & mask) return;
 	node->grid->values[word] |= mask;
 	node->numVoxels += 1;
-	float nodeSize = e->size / ldexpf(1.0f, (int)node->level);   /* pow(2.0f, level) is exact */
-	float nminx = ((float)node->X + 0.0f) * nodeSize + e->minx;
-	float nminy = ((float)node->Y + 0.0f) * nodeSize + e->miny;
-	float nminz = ((float)node->Z + 0.0f) * nodeSize + e->minz;
 	SimlodPoint v;
-	v.x = nminx + nodeSize * ((float)pX + 0.5f) / (float)SIMLOD_GRID_SIZE;
-	v.y = nminy + nodeSize * ((float)pY + 0.5f) / (float)SIMLOD_GRID_SIZE;
-	v.z = nminz + nodeSize * ((float)pZ + 0.5f) / (float)SIMLOD_GRID_SIZE;
+	voxel_centre(e->size, e->minx, e->miny, e->minz, node->level, node->X, node->Y, node->Z, pX, pY, pZ, &v);
 	v.color = p->color;
 	if (e->c->numBacklog >= VOXEL_BACKLOG_CAPACITY) { e->c->lastError = ORACLE_ERR_BACKLOG; return; }
 	e->c->backlogVoxels[e->c->numBacklog] = v;
 	e->c->backlogTargets[e->c->numBacklog] = node;
 	e->c->numBacklog++;
+}
+
+/* TEST AID (not part of the reference): where sample_path puts each of `n` points in the grid of node (level, X, Y, Z).  cells[i] =
+ * pX + 128 pY + 128^2 pZ with sample_voxel's quantization, or 0xffffffff when the point does not lie in that node (descend's 2^20
+ * quantization; below level 20, the 2^28 one); centres[3i..3i+2] = the position sample_voxel gives a voxel of that cell.  A voxel's
+ * colour names the point that made it: this recovers the voxel's cell at every level, also where fp32 no longer resolves neighbouring
+ * cells' positions. */
+void oracle_voxel_cells(const SimlodUniforms* u, const SimlodPoint* pts, uint32_t n, uint32_t level, uint32_t X, uint32_t Y, uint32_t Z,
+                        uint32_t* cells, float* centres) {
+	const float size = octree_size(u), fGrid = 1048576.0f, fFull = 268435456.0f;
+	const uint32_t shift = level <= 21u ? 21u - level : 0u;
+	for (uint32_t i = 0; i < n; i++) {
+		const SimlodPoint* p = &pts[i];
+		uint32_t pXf = quantize(fFull, p->x, u->boxMin.x, size), pYf = quantize(fFull, p->y, u->boxMin.y, size), pZf = quantize(fFull, p->z, u->boxMin.z, size);
+		int inside;
+		if (level <= (uint32_t)SIMLOD_MAX_DEPTH) {
+			const uint32_t s = (uint32_t)SIMLOD_MAX_DEPTH - level;
+			inside = level == 0u || ((quantize(fGrid, p->x, u->boxMin.x, size) >> s) == X && (quantize(fGrid, p->y, u->boxMin.y, size) >> s) == Y &&
+			                         (quantize(fGrid, p->z, u->boxMin.z, size) >> s) == Z);
+		} else {
+			const uint32_t s = level < 28u ? 28u - level : 0u;
+			inside = (pXf >> s) == X && (pYf >> s) == Y && (pZf >> s) == Z;
+		}
+		const uint32_t cX = (pXf >> shift) % SIMLOD_GRID_SIZE, cY = (pYf >> shift) % SIMLOD_GRID_SIZE, cZ = (pZf >> shift) % SIMLOD_GRID_SIZE;
+		cells[i] = inside ? cX + cY * SIMLOD_GRID_SIZE + cZ * SIMLOD_GRID_SIZE * SIMLOD_GRID_SIZE : 0xffffffffu;
+		SimlodPoint v;
+		voxel_centre(size, u->boxMin.x, u->boxMin.y, u->boxMin.z, level, X, Y, Z, cX, cY, cZ, &v);
+		centres[3 * i] = v.x; centres[3 * i + 1] = v.y; centres[3 * i + 2] = v.z;
+	}
 }
 
 /* voxelSampling::traverse, voxels.cu:426-470 — sampleVoxel on EVERY node of the root-to-leaf path */

@@ -51,6 +51,9 @@ namespace build {
 #include "construct_voxelize.inc"   // voxel chunks on demand, k_voxelize, voxelize_small, voxroot_pieces, end_of_batch
 #include "construct_insert.inc"     // k_voxdone, k_rootpre, k_insert, k_stats, k_finish
 
+// (simlod_amd/runtime.py DeviceOctree.group_size / groups_ingested and bench.py read these words of the control block)
+static_assert(offsetof(Ctl, groupMax) == 44 && offsetof(Ctl, expandNs) + 4 * sizeof(uint64_t) == 184, "Ctl.groupMax at byte 44, Ctl.expandNs[4] at byte 184");
+
 // ---- host side ----------------------------------------------------------------------------------------------------------
 static inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 

@@ -446,6 +446,24 @@ class DeviceOctree:
         self.processed_host = int(self.stats[76:80].cpu().numpy().view(np.uint32)[0])
         return self.processed_host
 
+    # kernel_construct's control block at byte 0 of the momentary buffer (csrc/construct_state.inc, struct Ctl; construct.hip asserts the offsets)
+    CTL_GROUP_MAX = 44          # Ctl.groupMax (uint32): batches per group the latest launch aimed at (1: one group of kernels per batch)
+    CTL_GROUPS = 184            # Ctl.expandNs[4] (uint64): groups of batches ingested since the word was last zeroed (bench.py reads it too)
+
+    def groups_ingested(self, zero=False):
+        """How many groups of batches kernel_construct has ingested since the counter was last zeroed (waits for the stream); zero=True: zero it
+        (in stream order, e.g. right behind a reset — a reset does not)."""
+        w = self.momentary[self.CTL_GROUPS: self.CTL_GROUPS + 8]
+        if zero:
+            w.zero_()
+            return 0
+        return int(w.cpu().numpy().view(np.uint64)[0])
+
+    def group_size(self):
+        """Batches per group the latest kernel_construct launch aimed at (exact mode: SIMLOD_EXACT_GROUP as the momentary buffer's layout and
+        the memory guard allow it)."""
+        return int(self.momentary[self.CTL_GROUP_MAX: self.CTL_GROUP_MAX + 4].cpu().numpy().view(np.uint32)[0])
+
     def drain(self, uniforms, max_launches=1000):
         """Launch kernel_construct until every uploaded batch is ingested.  One launch takes at most 20 batches and stops
         early once it has run for 10 ms (progressive_octree_voxels.cu:883, :939-949) — the reference host simply launches

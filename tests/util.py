@@ -74,6 +74,153 @@ def voxel_colors_are_member(nodes, n, points, box_size, max_level=20):
     return checked
 
 
+# ---- which batch coloured a voxel (a voxel's colour is the colour of a point of the FIRST batch that hit its cell) ----------------
+# A tagged input names its points by their colours; construction never reads a colour, so a tagged run builds the same octree (only the
+# pointsSum / pointsXor hashes follow the colours), and every voxel's colour names the one input point that won its cell.
+
+# (node = level + key X << 40 | Y << 20 | Z; cell = pX + 128 pY + 128^2 pZ of the node's grid; x, y, z = the voxel position's fp32 bits)
+voxel_row_dtype = np.dtype([("level", "<u4"), ("key", "<u8"), ("cell", "<u4"), ("x", "<u4"), ("y", "<u4"), ("z", "<u4"), ("batch", "<u4")])
+_ROW_ORDER = ["level", "key", "cell", "x", "y", "z", "batch"]
+
+
+def tag_colors(points):
+    """A copy of `points` whose colour is the global point index: each colour names exactly one input point."""
+    t = np.array(points, dtype=abi.point_dtype, copy=True)
+    t["color"] = np.arange(len(t), dtype=np.uint32)
+    return t
+
+
+def batch_of_points(batches):
+    """Global point index -> index of the batch it came in (empty batches count)."""
+    return np.repeat(np.arange(len(batches), dtype=np.uint32), [len(b) for b in batches])
+
+
+def _voxel_rows(uniforms, nodes, n, tagged):
+    """One row per stored voxel of a HOST-addressed image: (node key, cell of the winner point in the node's grid, voxel position bits,
+    winner point index in `batch`).  Raises AssertionError where a winner does not lie in its voxel's node or cell."""
+    out = []
+    for i in np.nonzero(nodes["numVoxelsStored"][:n])[0]:
+        nd = nodes[i]
+        nv, lvl, X, Y, Z = int(nd["numVoxelsStored"]), int(nd["level"]), int(nd["X"]), int(nd["Y"]), int(nd["Z"])
+        where = f"node level={lvl} XYZ=({X},{Y},{Z})"
+        vox = oracle.gather_samples(int(nd["voxelChunks"]), nv)
+        assert len(vox) == nv, f"{where}: voxel list holds {len(vox)} of its {nv} voxels"
+        win = vox["color"].astype(np.int64)
+        if (win >= len(tagged)).any():
+            raise AssertionError(f"{where}: {int((win >= len(tagged)).sum())} voxel colours name no input point")
+        cells, centres = oracle.voxel_cells(uniforms, tagged[win], lvl, X, Y, Z)
+        outside = cells == 0xFFFFFFFF
+        if outside.any():
+            k = int(np.argmax(outside))
+            raise AssertionError(f"{where}: {int(outside.sum())} voxels won by a point outside the voxel's node (first: voxel {k}, point {int(win[k])})")
+        pos = np.stack([vox["x"], vox["y"], vox["z"]], axis=1)
+        off = (pos.view(np.uint32) != centres.view(np.uint32)).any(axis=1)
+        if off.any():
+            k = int(np.argmax(off))
+            raise AssertionError(f"{where}: {int(off.sum())} voxels won by a point outside the voxel's cell (first: voxel {k} at {tuple(pos[k])}, "
+                                 f"point {int(win[k])} makes {tuple(centres[k])})")
+        r = np.zeros(nv, dtype=voxel_row_dtype)
+        r["level"] = lvl
+        r["key"] = (X << 40) | (Y << 20) | Z
+        r["cell"] = cells
+        r["x"], r["y"], r["z"] = pos.view(np.uint32).T
+        r["batch"] = win                   # (the winner, for now)
+        out.append(r)
+    return np.concatenate(out) if out else np.zeros(0, dtype=voxel_row_dtype)
+
+
+def _sorted_rows(rows):
+    return rows[np.lexsort([rows[f] for f in reversed(_ROW_ORDER)])]
+
+
+def replay_first_hits(uniforms, batches, persistent_bytes=None):
+    """Run `batches` (tagged) through the port oracle ONE at a time.  The oracle appends a node's voxels in batch order
+    (simlod_oracle.c insertVoxels: slot = numVoxelsStored++), so slot i of a node was made by the first batch after which its numVoxelsStored
+    exceeds i.  Returns (the HostOctree as the last batch it took left it, the first-hit table: voxel_row_dtype rows sorted by
+    (node, cell, position bits, batch) — every (node, position) group's `batch` column is the sorted list of its first-hit batches b*).
+    A cell can hold several voxels: the root's grid is cleared when the root splits.  A batch the memory guard refuses ends the replay."""
+    u = np.ascontiguousarray(uniforms).reshape(1)
+    tagged = np.concatenate(batches) if len(batches) else np.zeros(0, dtype=abi.point_dtype)
+    assert np.array_equal(tagged["color"], np.arange(len(tagged), dtype=np.uint32)), "replay_first_hits wants tag_colors() points"
+    cap = int(u["persistentBufferCapacity"][0])
+    ref = oracle.HostOctree("port", persistent_bytes=persistent_bytes or min(cap, 4 << 30), ring_slots=abi.BATCH_STREAM_SIZE)
+    ref.reset(u)
+    prev = np.zeros(0, dtype=np.int64)
+    ev_node, ev_old, ev_new, ev_batch = [], [], [], []
+    for b, pts in enumerate(batches):
+        ref.upload(pts)
+        ref.construct(u)                   # (nothing else is pending: the launch takes this batch, or the memory guard refuses it)
+        assert ref.last_error() == 0, f"oracle error {ref.last_error()} in batch {b}"
+        if int(ref.stats["batchletIndex"][0]) != b + 1:
+            break
+        cur = ref.nodes["numVoxelsStored"][: int(ref.stats["numNodes"][0])].astype(np.int64)
+        old = np.zeros_like(cur)
+        old[: len(prev)] = prev
+        ch = np.nonzero(cur != old)[0]
+        ev_node.append(ch); ev_old.append(old[ch]); ev_new.append(cur[ch]); ev_batch.append(np.full(len(ch), b))
+        prev = cur
+    nn = int(ref.stats["numNodes"][0])
+    rows = _voxel_rows(u, ref.nodes, nn, tagged)
+    if len(rows):
+        node, old, new, bat = (np.concatenate(v) for v in (ev_node, ev_old, ev_new, ev_batch))
+        cnt = new - old
+        assert (cnt > 0).all(), "numVoxelsStored shrank"
+        # b* per (node, slot), in the order _voxel_rows lists the voxels: nodes by index, slots ascending (a node's events come in batch order)
+        order = np.argsort(node, kind="stable")
+        bstar = np.repeat(bat[order], cnt[order])
+        assert len(bstar) == len(rows)
+        rows["batch"] = bstar
+    return ref, _sorted_rows(rows)
+
+
+def first_hit_batches(uniforms, batches):
+    """The first-hit table of replay_first_hits (see there)."""
+    return replay_first_hits(uniforms, batches)[1]
+
+
+def assert_voxel_winners(nodes, n, tagged, batch_of_point, first_hit, bound, uniforms):
+    """Batch-aware colour check of a HOST-addressed image built from `tagged` points (tag_colors).  Every voxel's winner must lie in the
+    voxel's node and cell (oracle_voxel_cells: the oracle's own quantization, every level); grouped by (node, cell, position) and sorted on
+    both sides, the voxels must pair up one to one with the first-hit table's, and the batch of each winner must be <= bound(b*) of its
+    partner (bound: numpy array of b* -> array of the latest batch allowed; `lambda b: b` is the reference's rule).  Returns the number of
+    voxels checked."""
+    rows = _voxel_rows(uniforms, nodes, n, tagged)
+    rows["batch"] = batch_of_point[rows["batch"].astype(np.int64)]
+    rows = _sorted_rows(rows)
+    same = len(rows) == len(first_hit)
+    if same:
+        diff = np.zeros(len(rows), bool)
+        for f in _ROW_ORDER[:-1]:
+            diff |= rows[f] != first_hit[f]
+        same = not diff.any()
+    if not same:
+        ca, cb = {}, {}
+        for c, t in ((ca, rows), (cb, first_hit)):
+            for k in t[_ROW_ORDER[:3]].tolist():
+                c[k] = c.get(k, 0) + 1
+        bad = sorted(k for k in set(ca) | set(cb) if ca.get(k) != cb.get(k))
+        k = bad[0] if bad else (0, 0, 0)
+        raise AssertionError(f"voxel counts per (node, cell) differ from the oracle's at {len(bad)} cells ({len(rows)} voxels, oracle {len(first_hit)}); "
+                             f"first: level {k[0]} XYZ key {k[1]:#x} cell {k[2]}: {ca.get(k, 0)} != {cb.get(k, 0)}")
+    allowed = np.asarray(bound(first_hit["batch"].astype(np.int64)))
+    late = rows["batch"].astype(np.int64) > allowed
+    if late.any():
+        i = int(np.argmax(late))
+        raise AssertionError(f"{int(late.sum())} of {len(rows)} voxels are coloured from a later batch than the bound allows; first: level "
+                             f"{int(rows['level'][i])} XYZ key {int(rows['key'][i]):#x} cell {int(rows['cell'][i])}: batch {int(rows['batch'][i])}, first hit {int(first_hit['batch'][i])}, "
+                             f"allowed <= {int(allowed[i])}")
+    return len(rows)
+
+
+def late_voxels(nodes, n, tagged, batch_of_point, first_hit, uniforms):
+    """How many voxels are coloured from a later batch than the first that hit their cell (the pairing of assert_voxel_winners)."""
+    rows = _voxel_rows(uniforms, nodes, n, tagged)
+    rows["batch"] = batch_of_point[rows["batch"].astype(np.int64)]
+    rows = _sorted_rows(rows)
+    assert len(rows) == len(first_hit)
+    return int((rows["batch"] > first_hit["batch"]).sum()), len(rows)
+
+
 def points_multiset_hash(pts):
     """(sum, xor) order-independent hash of a set of 16-byte points — the same mixer as oracle_dump's pointsSum / pointsXor."""
     w = pts.view(np.uint32).reshape(-1, 4).astype(np.uint64)
