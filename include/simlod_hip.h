@@ -331,6 +331,27 @@ int simlod_export_octree(const SimlodNode* nodes, const SimlodStats* stats, uint
 int simlod_import_octree(const SimlodExportNode* table, uint32_t numNodes, const SimlodPoint* samples, uint64_t numSamples, void* scratch,
                          uint64_t scratchBytes, uint8_t* persistent, uint64_t persistentCapacity, SimlodNode* nodes, SimlodStats* stats, void* stream);
 
+/* Stats.dbg bit of simlod_import_octree_buildable: a rebuilt occupancy grid disagrees with the table (a non-root inner node's popcount is
+ * not its numSamples, or the root's exceeds its numSamples) — the uniforms' box is not the one the octree was built with.  FATAL: sticky
+ * until kernel_reset; kernel_construct launches do nothing while it is set.  The octree still renders. */
+#define SIMLOD_ERR_IMPORT_GRID 0x800u
+
+/* The "buildable" import: everything simlod_import_octree writes, plus what kernel_construct needs to go on ingesting into the octree —
+ * the occupancy grid of every inner node and of the root, rebuilt from the samples (the grid of a node is the set of its level's cells of
+ * every point below it: the leaves' samples), and a builder state as after a reset (batchletIndex, numPointsProcessed 0; the recycle stack
+ * empty: numAllocatedChunks = chunkPoolSize = the point chunks in use).  `uniforms` give the box (boxMin / boxMax, which must be the box the octree was
+ * built with), persistentBufferCapacity and frameCounter.  The upload counter and batchSizes are zeroed in stream order, as kernel_reset
+ * does, and the next kernel_construct launch is sized as after a reset.
+ * Only full exports qualify: besides simlod_import_octree's checks the validation kernel requires every entry SELECTED, FLAG_LEAF set
+ * exactly when childMask == 0, childMask 0 or 0xff, and the chunks, the grids (SIMLOD_ALLOC_ROUND(sizeof(SimlodOccupancyGrid)) each) and,
+ * for a root that is still a leaf, room for its voxel list (one chunk per 1 000 of its points) within persistentBufferCapacity; a failure
+ * sets SIMLOD_ERR_IMPORT and writes nothing else.  A root that is still a leaf gets its voxels back (the export carries its points only):
+ * one per occupied cell of its grid, in ascending cell order, at the cell centre, coloured by the cell's lowest-index point.
+ * The scratch bound is simlod_export_buffer_min_bytes(numNodes, numSamples). */
+int simlod_import_octree_buildable(const SimlodUniforms* uniforms, const SimlodExportNode* table, uint32_t numNodes, const SimlodPoint* samples,
+                                   uint64_t numSamples, void* scratch, uint64_t scratchBytes, uint8_t* persistent, SimlodNode* nodes,
+                                   SimlodStats* stats, uint32_t* numBatchesUploaded, uint32_t* batchSizes, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

@@ -115,6 +115,7 @@ EXPORT_NONE = 0xFFFFFFFF
 EXPORT_FLAG_LEAF, EXPORT_FLAG_SELECTED = 0x1, 0x2
 EXPORT_ERR_CAPACITY, EXPORT_ERR_NODE_COUNT, EXPORT_ERR_SHORT_LIST = 0x1, 0x2, 0x4
 SIMLOD_ERR_IMPORT = 0x400
+SIMLOD_ERR_IMPORT_GRID = 0x800          # simlod_import_octree_buildable: a rebuilt grid disagrees with the table (wrong box); sticky until a reset
 
 export_node_dtype = np.dtype({
     "names": ["level", "X", "Y", "Z", "parent", "firstChild", "childMask", "flags", "reserved", "numSamples", "firstSample"],

@@ -106,7 +106,8 @@ __global__ __launch_bounds__(TPB) void k_begin(BuildArgs a, uint32_t momentaryTo
 	Ctl* ctl = ctl_of(a);
 	const bool stale = momentaryTooSmall != 0u || (debugFlags & 4u) != 0u || stamp_is_stale(a, ctl);      // (debugFlags bit 2: the host knows the image was replaced — simlod_octree_image_replaced, a reset)
 	if (threadIdx.x == 0 && blockIdx.x == 0) {
-		const uint32_t fatal = a.stats->dbg & (SIMLOD_ERR_BARRIER_TIMEOUT | SIMLOD_ERR_DIRECTORY_FULL);   // sticky until the host resets the octree
+		// sticky until the host resets the octree (the import bits: a buildable import whose table or grids failed its checks)
+		const uint32_t fatal = a.stats->dbg & (SIMLOD_ERR_BARRIER_TIMEOUT | SIMLOD_ERR_DIRECTORY_FULL | SIMLOD_ERR_IMPORT | SIMLOD_ERR_IMPORT_GRID);
 		ctl->errors = momentaryTooSmall ? SIMLOD_ERR_MOMENTARY_TOO_SMALL : 0u;
 		ctl->stop = (momentaryTooSmall || fatal) ? 1u : 0u;
 		ctl->abortBatch = 0;

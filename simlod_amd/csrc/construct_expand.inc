@@ -860,16 +860,7 @@ __global__ __launch_bounds__(TPB) void k_hist2(BuildArgs a, uint32_t ordinal) {
 // cell-centre position of a voxel, voxels.cu:103-114, operation by operation (no contraction): cell (cx, cy, cz) of the 128^3 grid of the
 // level-`level` node with coordinates (nX, nY, nZ)
 __device__ __forceinline__ float4 voxel_at(const BuildArgs& a, int level, uint32_t nX, uint32_t nY, uint32_t nZ, uint32_t cx, uint32_t cy, uint32_t cz, float colorBits) {
-	const float nodeSize = a.size / exp2_int((uint32_t)level);
-	const float nminx = ((float)nX + 0.0f) * nodeSize + a.minx;
-	const float nminy = ((float)nY + 0.0f) * nodeSize + a.miny;
-	const float nminz = ((float)nZ + 0.0f) * nodeSize + a.minz;
-	float4 v;
-	v.x = nminx + (nodeSize * ((float)cx + 0.5f)) / 128.0f;
-	v.y = nminy + (nodeSize * ((float)cy + 0.5f)) / 128.0f;
-	v.z = nminz + (nodeSize * ((float)cz + 0.5f)) / 128.0f;
-	v.w = colorBits;                       // colour of the claiming point
-	return v;
+	return voxel_centre(a.size, a.minx, a.miny, a.minz, level, nX, nY, nZ, cx, cy, cz, colorBits);      // (simlod_device.hpp; the import rebuilds root voxels with it)
 }
 // ... of the cell a sample with 28-bit coordinates (pX, pY, pZ) falls into
 __device__ __forceinline__ float4 voxel_of(const BuildArgs& a, int level, uint32_t pX, uint32_t pY, uint32_t pZ, float colorBits) {

@@ -166,8 +166,6 @@ __device__ __forceinline__ int table_find(const BlockTable& t, uint32_t key) {
 
 
 static constexpr uint32_t TPB = 256;
-static constexpr float F_GRID = 1048576.0f;      // 2^MAX_DEPTH, progressive_octree_voxels.cu:139
-static constexpr float F_FULL = 268435456.0f;    // MAX_DEPTH_GRIDSIZE, structures.cuh:26
 
 struct NodeDir {          // per node, valid for the batch whose tag it carries: where the leaf's chunks stand in the batch's chunk directory
 	uint32_t ptBase, ptFirst, ptTag, pad0;

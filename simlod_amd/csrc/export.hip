@@ -12,10 +12,15 @@
 //   k_copy     the hot path: one workgroup per chunk at a time (grid-stride), 16-byte loads and stores, four per lane in flight.
 // Import: k_i_validate (ONE workgroup: every check, the scans, the Stats counts) -> k_i_nodes (one lane per node: Node record, the chunk
 // headers of its list, its copy items) -> k_copy (the same kernel, samples -> chunks) -> k_i_finish (allocator header, Stats).
+// The buildable import (simlod_import_octree_buildable): the same four kernels — the validation with the buildability checks, the Node records
+// with grid pointers — and, between k_copy and k_i_finish, the occupancy grids rebuilt from the samples: k_i_gleaf, k_i_gdown per level,
+// k_i_groot (below); k_i_finish then also writes the builder's counters as k_reset does.
 // Everything in between lives in the caller's scratch buffer (export_min_bytes), never in kernel_construct's momentary buffer: the builder's
 // recycle stack and the chunk table export reads are there.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <algorithm>
 
 #include "simlod_device.hpp"
 #include "simlod_hip.h"
@@ -29,6 +34,7 @@ constexpr uint32_t WG_WAVES = WG_TPB / SIMLOD_WAVE;
 constexpr uint32_t LANE_TPB = 256;                                                 // one lane per node / the copy
 constexpr uint64_t CHUNK_STRIDE = SIMLOD_ALLOC_ROUND(sizeof(SimlodChunk));         // 16 032: what AllocatorGlobal::alloc advances per chunk
 constexpr uint64_t CHUNK_BASE = 16;                                                // first allocation behind the allocator header
+constexpr uint64_t GRID_STRIDE = SIMLOD_ALLOC_ROUND(sizeof(SimlodOccupancyGrid));  // 262 160: what the builder's grid allocations advance
 constexpr uint32_t NONE = SIMLOD_EXPORT_NONE;
 
 struct CopyItem { uint64_t src, dst; uint32_t count, pad0; uint64_t pad1; };       // 32 B; count == 0: nothing
@@ -41,6 +47,12 @@ struct Header {
 	uint64_t numItems;
 	uint64_t totalChunks;
 	uint32_t counts[8];                  // import: inner, leaves, nonempty leaves, points, voxels, point chunks, voxel chunks
+	// buildable import: the table entries of each level below 20 ([lvFirst, lvEnd): breadth-first order keeps a level together; level 20 has
+	// no inner nodes), the grids (one per inner node and the root, in table order, from gridBase on), a grid that disagrees with the table,
+	// the voxels rebuilt for a root that is a leaf
+	uint32_t lvFirst[SIMLOD_MAX_DEPTH], lvEnd[SIMLOD_MAX_DEPTH];
+	uint32_t numGrids, gridBad, rootVoxels, pad1;
+	uint64_t gridBase, rootVoxBase;
 };
 static_assert(sizeof(Header) <= 256, "Header");
 __host__ __device__ inline uint64_t align256(uint64_t v) { return (v + 255u) & ~255ull; }
@@ -280,6 +292,13 @@ struct ImportArgs {
 	uint64_t                persCap;
 	SimlodNode*             nodes;
 	SimlodStats*            stats;
+	// the buildable import (launch_import_buildable): the box as the builder derives it (construct.hip), and what k_reset also writes
+	uint32_t                buildable;
+	float                   minx, miny, minz, size;
+	uint32_t*               numBatchesUploaded;
+	uint32_t*               batchSizes;
+	uint32_t*               feedback;
+	uint32_t                feedbackSeq, frameCounter;
 };
 
 __device__ __forceinline__ uint32_t octant_of(const SimlodExportNode& e) { return ((e.X & 1u) << 2) | ((e.Y & 1u) << 1) | (e.Z & 1u); }
@@ -288,12 +307,15 @@ __global__ __launch_bounds__(WG_TPB) void k_i_validate(ImportArgs a) {
 	__shared__ uint64_t sh_scan[WG_WAVES];
 	__shared__ uint32_t sh_bad;
 	__shared__ uint32_t sh_cnt[7];
+	__shared__ uint32_t sh_lvFirst[SIMLOD_MAX_DEPTH], sh_lvEnd[SIMLOD_MAX_DEPTH];
 	Header* hdr = reinterpret_cast<Header*>(a.scratch);
 	uint32_t* first = reinterpret_cast<uint32_t*>(a.scratch + a.lay.first);
+	uint32_t* gridOf = reinterpret_cast<uint32_t*>(a.scratch + a.lay.map);     // buildable: table index -> grid ordinal (NONE: a leaf below the root)
 	if (threadIdx.x < 7) sh_cnt[threadIdx.x] = 0u;
+	if (threadIdx.x < (uint32_t)SIMLOD_MAX_DEPTH) { sh_lvFirst[threadIdx.x] = NONE; sh_lvEnd[threadIdx.x] = 0u; }
 	if (threadIdx.x == 0) sh_bad = 0u;
 	__syncthreads();
-	uint64_t samples = 0, chunks = 0, children = 1;                   // (the root is nobody's child)
+	uint64_t samples = 0, chunks = 0, children = 1, grids = 0;        // (the root is nobody's child)
 	for (uint32_t base = 0; base < a.n; base += WG_TPB) {
 		const uint32_t t = base + threadIdx.x;
 		const bool act = t < a.n;
@@ -313,12 +335,21 @@ __global__ __launch_bounds__(WG_TPB) void k_i_validate(ImportArgs a) {
 			}
 			if (e.childMask == 0u) bad |= e.firstChild != NONE;
 			else bad |= e.firstChild == NONE || e.firstChild <= t || (uint64_t)e.firstChild + (uint32_t)__popc(e.childMask) > a.n || e.level >= (uint32_t)SIMLOD_MAX_DEPTH;
+			if (a.buildable) {
+				// a full export of an octree the builder made: every sample present, the leaf flag as the children say, eight children or none
+				bad |= (e.flags & SIMLOD_EXPORT_FLAG_SELECTED) == 0u || ((e.flags & SIMLOD_EXPORT_FLAG_LEAF) != 0u) != (e.childMask == 0u);
+				bad |= e.childMask != 0u && e.childMask != 0xffu;
+				if (e.level < (uint32_t)SIMLOD_MAX_DEPTH) { atomicMin(&sh_lvFirst[e.level], t); atomicMax(&sh_lvEnd[e.level], t + 1u); }
+			}
 		}
 		const uint64_t kids = (uint64_t)__popc(e.childMask), ns = act ? e.numSamples : 0u, nch = act ? ceil_chunks(ns) : 0u;
-		uint64_t totK, totS, totC;
+		const bool hasGrid = act && a.buildable != 0u && (t == 0u || e.childMask != 0u);
+		uint64_t totK, totS, totC, totG;
 		const uint64_t offK = block_scan<uint64_t>(kids, totK, sh_scan);
 		const uint64_t offS = block_scan<uint64_t>(ns, totS, sh_scan);
 		const uint64_t offC = block_scan<uint64_t>(nch, totC, sh_scan);
+		const uint64_t offG = block_scan<uint64_t>(hasGrid ? 1u : 0u, totG, sh_scan);
+		if (act && a.buildable) gridOf[t] = hasGrid ? (uint32_t)(grids + offG) : NONE;
 		if (act) {
 			// breadth-first order: an entry's children come right after the children of the entries before it
 			if (e.childMask != 0u) bad |= (uint64_t)e.firstChild != children + offK;
@@ -330,15 +361,25 @@ __global__ __launch_bounds__(WG_TPB) void k_i_validate(ImportArgs a) {
 			for (int q = 0; q < 7; q++) if (c[q] != 0u) atomicAdd(&sh_cnt[q], c[q]);
 		}
 		if (bad) atomicOr(&sh_bad, 1u);
-		children += totK; samples += totS; chunks += totC;
+		children += totK; samples += totS; chunks += totC; grids += totG;
 	}
 	__syncthreads();
 	if (threadIdx.x == 0) {
 		bool bad = sh_bad != 0u || a.n == 0u || children != a.n || samples != a.numSamples || chunks > a.lay.itemCap;
-		bad |= CHUNK_BASE + chunks * CHUNK_STRIDE > a.persCap;
+		// persistent layout: the chunks, then (buildable) the grids, then the voxel list of a root that is still a leaf (<= one voxel per point)
+		uint64_t end = CHUNK_BASE + chunks * CHUNK_STRIDE;
+		hdr->gridBase = end;
+		if (a.buildable) {
+			end += grids * GRID_STRIDE;
+			hdr->rootVoxBase = end;
+			if (a.n != 0u && a.table[0].childMask == 0u) end += (uint64_t)ceil_chunks(a.table[0].numSamples) * CHUNK_STRIDE;
+		}
+		bad |= end > a.persCap;
 		hdr->ok = bad ? 0u : 1u;
 		hdr->numItems = bad ? 0u : chunks;
 		hdr->totalChunks = chunks;
+		hdr->numGrids = (uint32_t)grids; hdr->gridBad = 0u; hdr->rootVoxels = 0u;
+		for (int l = 0; l < SIMLOD_MAX_DEPTH; l++) { hdr->lvFirst[l] = sh_lvFirst[l]; hdr->lvEnd[l] = sh_lvEnd[l]; }
 		for (int q = 0; q < 7; q++) hdr->counts[q] = sh_cnt[q];
 		if (bad) a.stats->dbg |= SIMLOD_ERR_IMPORT;
 		else first[a.n] = (uint32_t)chunks;
@@ -371,6 +412,10 @@ __global__ __launch_bounds__(LANE_TPB) void k_i_nodes(ImportArgs a) {
 	}
 	nd.visible = 0; nd.isFiltered = 0; nd.isLeaf = 0; nd.isLarge = 0;
 	nd.grid = nullptr;
+	if (a.buildable) {
+		const uint32_t g = reinterpret_cast<const uint32_t*>(a.scratch + a.lay.map)[t];
+		if (g != NONE) nd.grid = reinterpret_cast<SimlodOccupancyGrid*>(a.pers + hdr->gridBase + (uint64_t)g * GRID_STRIDE);
+	}
 	nd.points = leaf ? head : nullptr;
 	nd.voxelChunks = leaf ? nullptr : head;
 	nd.numVoxels = leaf ? 0u : ns;
@@ -394,17 +439,254 @@ __global__ __launch_bounds__(LANE_TPB) void k_i_nodes(ImportArgs a) {
 
 __global__ void k_i_finish(ImportArgs a) {
 	const Header* hdr = reinterpret_cast<const Header*>(a.scratch);
+	// buildable: what the next kernel_construct launch is sized by (simlod_hip.cpp launch_plan), as k_reset reports it — nothing ingested, nothing uploaded
+	if (a.buildable && a.feedback != nullptr) {
+		a.feedback[0] = 0u; a.feedback[1] = 0u; a.feedback[2] = 1u;
+		__hip_atomic_store(a.feedback + 3, a.feedbackSeq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+	}
 	if (hdr->ok == 0u) return;
+	const uint32_t rootVoxChunks = ceil_chunks(hdr->rootVoxels);
 	SimlodAllocatorGlobal* alloc = reinterpret_cast<SimlodAllocatorGlobal*>(a.pers);
 	alloc->buffer = a.pers;
-	alloc->offset = CHUNK_BASE + hdr->totalChunks * CHUNK_STRIDE;
+	alloc->offset = a.buildable ? hdr->rootVoxBase + (uint64_t)rootVoxChunks * CHUNK_STRIDE : CHUNK_BASE + hdr->totalChunks * CHUNK_STRIDE;
 	SimlodStats s{};
 	s.numNodes = a.n;
 	s.numInner = hdr->counts[0]; s.numLeaves = hdr->counts[1]; s.numNonemptyLeaves = hdr->counts[2];
+	// (the voxels of a root that is still a leaf are not counted: the builder's Stats count the lists of inner nodes only)
 	s.numPoints = hdr->counts[3]; s.numVoxels = hdr->counts[4];
 	s.numChunksPoints = hdr->counts[5]; s.numChunksVoxels = hdr->counts[6];
 	s.allocatedBytes_persistent = alloc->offset;
+	if (a.buildable) {
+		// the builder's counters start as after a reset (batchletIndex, numPointsProcessed: 0), with an empty recycle stack: numAllocatedChunks is the
+		// stack pointer a split returns its leaf's chunks below (voxels.cu:346-357), so it counts the point chunks in use, and chunkPoolSize (its
+		// high-water mark) equals it — 0 would send the first split's chunks below the stack's bottom (SIMLOD_ERR_CHUNK_QUEUE_OVERFLOW)
+		s.numAllocatedChunks = hdr->counts[5]; s.chunkPoolSize = hdr->counts[5];
+		s.frameID = a.frameCounter;
+		s.dbg = hdr->gridBad != 0u ? SIMLOD_ERR_IMPORT_GRID : 0u;
+		*a.numBatchesUploaded = 0u;
+		for (uint32_t k = 0; k < SIMLOD_BATCH_STREAM_SIZE; k++) a.batchSizes[k] = 0u;
+	}
 	*a.stats = s;
+}
+
+// ---- the buildable import's occupancy grids ------------------------------------------------------------------------------------------
+// The grid of a node is the set of its level's cells of every point below it (every point samples every node on its path that has a grid,
+// voxels.cu:449-469; a node that splits re-samples all its points, :362-381; the root's grid is cleared and re-sampled at its split).  A child
+// covers one 64^3 octant of its parent's 128^3 grid (8 192 words): the node grid is the fp32 quotient of quantize(F_FULL) scaled by an exact
+// power of two, so the bit below which a point files at level L + 1 is the top bit of its cell at level L — the max face included (2^28 on an
+// axis: cell 0, node coordinate 0).  So every word of a parent's grid is written by exactly one of its eight children, with plain stores:
+//   k_i_gleaf   a leaf's octant from its points, built in LDS (one workgroup per table entry; inner entries leave at once)
+//   k_i_gdown   per level, deepest first: an inner node's finished grid, 2x2x2 cells -> one, into its octant of the parent's grid; its popcount
+//               against its voxel count on the way (one workgroup per node)
+//   k_i_groot   the root: the popcount check of an inner root; a root that is still a leaf gets its grid and its voxel list from its points
+constexpr uint32_t G_TPB = 256;
+constexpr uint32_t OCT_WORDS = SIMLOD_GRID_NUM_WORDS / 8u;                        // 8 192 words: one octant of a grid, two words per row of 64 cells
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint32_t* grid_of(const ImportArgs& a, const Header* hdr, uint32_t t) {
+	const uint32_t g = reinterpret_cast<const uint32_t*>(a.scratch + a.lay.map)[t];
+	return reinterpret_cast<uint32_t*>(a.pers + hdr->gridBase + (uint64_t)g * GRID_STRIDE);
+}
+// word w of an octant (w = xw | ly << 1 | lz << 7) -> its word in the grid whose octant (ox, oy, oz) it is (cell = x + 128 y + 128^2 z)
+__device__ __forceinline__ uint32_t octant_word(uint32_t w, uint32_t ox, uint32_t oy, uint32_t oz) {
+	return ox * 2u + (w & 1u) + 4u * (oy * 64u + ((w >> 1) & 63u)) + 512u * (oz * 64u + (w >> 7));
+}
+// bit i (< 16) = bit 2i | bit 2i + 1 of v: 32 cells of a row -> the 16 cells of the level above
+__device__ __forceinline__ uint32_t squeeze(uint32_t v) {
+	v = (v | (v >> 1)) & 0x55555555u;
+	v = (v | (v >> 1)) & 0x33333333u;
+	v = (v | (v >> 2)) & 0x0f0f0f0fu;
+	v = (v | (v >> 4)) & 0x00ff00ffu;
+	return (v | (v >> 8)) & 0x0000ffffu;
+}
+
+__global__ __launch_bounds__(G_TPB) void k_i_gleaf(ImportArgs a) {
+	__shared__ uint32_t oct[OCT_WORDS];
+	const Header* hdr = reinterpret_cast<const Header*>(a.scratch);
+	const uint32_t t = blockIdx.x;
+	if (hdr->ok == 0u || t == 0u || t >= a.n) return;
+	const SimlodExportNode e = a.table[t];
+	if (e.childMask != 0u) return;
+	for (uint32_t w = threadIdx.x; w < OCT_WORDS; w += G_TPB) oct[w] = 0u;
+	__syncthreads();
+	// the cell in the PARENT's grid (level e.level - 1): grid_cell() of construct_voxelize.inc, the builder's quantisation (k_voxelize)
+	const uint32_t shf = (uint32_t)(SIMLOD_MAX_DEPTH + 2) - e.level;
+	const uint32_t ox = e.X & 1u, oy = e.Y & 1u, oz = e.Z & 1u;
+	const float4* pts = reinterpret_cast<const float4*>(a.samples + e.firstSample);
+	const uint32_t n = e.numSamples;
+	for (uint32_t i0 = 0; i0 < n; i0 += 4u * G_TPB) {
+		float4 p[4];
+#pragma unroll
+		for (uint32_t j = 0; j < 4u; j++) {
+			const uint32_t i = i0 + j * G_TPB + threadIdx.x;
+			p[j] = i < n ? pts[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		}
+#pragma unroll
+		for (uint32_t j = 0; j < 4u; j++) {
+			if (i0 + j * G_TPB + threadIdx.x >= n) continue;
+			const uint32_t cx = (quantize(F_FULL, p[j].x, a.minx, a.size) >> shf) & 127u;
+			const uint32_t cy = (quantize(F_FULL, p[j].y, a.miny, a.size) >> shf) & 127u;
+			const uint32_t cz = (quantize(F_FULL, p[j].z, a.minz, a.size) >> shf) & 127u;
+			// (a cell outside the leaf's octant is not the builder's either: dropped, and the parent's popcount check reports the octree)
+			if ((cx >> 6) != ox || (cy >> 6) != oy || (cz >> 6) != oz) continue;
+			const uint32_t lx = cx & 63u;
+			atomicOr(&oct[(lx >> 5) | ((cy & 63u) << 1) | ((cz & 63u) << 7)], 1u << (lx & 31u));
+		}
+	}
+	__syncthreads();
+	uint32_t* parent = grid_of(a, hdr, e.parent);
+	for (uint32_t k = threadIdx.x; k < OCT_WORDS / 2u; k += G_TPB) {
+		u32x2 v;
+		v.x = oct[2u * k]; v.y = oct[2u * k + 1u];
+		*reinterpret_cast<u32x2*>(parent + octant_word(2u * k, ox, oy, oz)) = v;
+	}
+}
+
+__global__ __launch_bounds__(G_TPB) void k_i_gdown(ImportArgs a, uint32_t level) {
+	__shared__ uint32_t sh_pop;
+	Header* hdr = reinterpret_cast<Header*>(a.scratch);
+	if (hdr->ok == 0u) return;
+	const uint32_t lo = hdr->lvFirst[level], hi = min(hdr->lvEnd[level], a.n);
+	for (uint32_t t = lo + blockIdx.x; t < hi; t += gridDim.x) {
+		const SimlodExportNode e = a.table[t];
+		if (e.childMask == 0u) continue;                                   // (the same for the whole workgroup)
+		const uint32_t* child = grid_of(a, hdr, t);
+		uint32_t* parent = grid_of(a, hdr, e.parent);
+		const uint32_t ox = e.X & 1u, oy = e.Y & 1u, oz = e.Z & 1u;
+		if (threadIdx.x == 0) sh_pop = 0u;
+		__syncthreads();
+		uint32_t pop = 0;
+		// output word w: cells xw * 32 .. + 31 of row (ly, lz) of the octant <- child words 2 xw, 2 xw + 1 of rows (2 ly + {0, 1}, 2 lz + {0, 1});
+		// four outputs per lane and turn, their 16 loads in flight together
+		for (uint32_t w0 = 0; w0 < OCT_WORDS; w0 += 4u * G_TPB) {
+			u32x2 r[4][4];
+#pragma unroll
+			for (uint32_t j = 0; j < 4u; j++) {
+				const uint32_t w = w0 + j * G_TPB + threadIdx.x, xw = w & 1u, ly = (w >> 1) & 63u, lz = w >> 7;
+#pragma unroll
+				for (uint32_t q = 0; q < 4u; q++)
+					r[j][q] = *reinterpret_cast<const u32x2*>(child + 2u * xw + 4u * (2u * ly + (q & 1u)) + 512u * (2u * lz + (q >> 1)));
+			}
+#pragma unroll
+			for (uint32_t j = 0; j < 4u; j++) {
+				const uint32_t w = w0 + j * G_TPB + threadIdx.x;
+				const uint32_t lo32 = r[j][0].x | r[j][1].x | r[j][2].x | r[j][3].x, hi32 = r[j][0].y | r[j][1].y | r[j][2].y | r[j][3].y;
+#pragma unroll
+				for (uint32_t q = 0; q < 4u; q++) pop += (uint32_t)__popc(r[j][q].x) + (uint32_t)__popc(r[j][q].y);
+				parent[octant_word(w, ox, oy, oz)] = squeeze(lo32) | (squeeze(hi32) << 16);
+			}
+		}
+		atomicAdd(&sh_pop, pop);
+		__syncthreads();
+		// a non-root inner node: one voxel per occupied cell (oracle_check_invariants rule 12)
+		if (threadIdx.x == 0 && sh_pop != e.numSamples) atomicOr(&hdr->gridBad, 1u);
+		__syncthreads();
+	}
+}
+static_assert(OCT_WORDS % (4u * G_TPB) == 0u, "k_i_gdown: whole turns");
+
+// The root.  Inner: its grid is complete (k_i_gdown of level 1); it may hold duplicate voxels (its grid was cleared when it split), so its
+// popcount is at most its voxel count.  A leaf: its grid in 16 slabs of 8 z-layers (4 096 words) built in LDS from its points, and its voxel
+// list, which the export does not carry: one voxel per occupied cell in ascending cell order (slot = cells before it), at the cell centre
+// (voxel_centre, the builder's formula), coloured by the cell's lowest-index point (atomicMin of the point index into the slot's colour word,
+// then the index replaced by that point's colour).  One workgroup: a root that is a leaf holds a few ten thousand points.
+constexpr uint32_t R_TPB = WG_TPB, SLAB_WORDS = 4096u, SLABS = SIMLOD_GRID_NUM_WORDS / SLAB_WORDS;
+static_assert(SLAB_WORDS == 4u * R_TPB, "k_i_groot: four words per lane and slab");
+
+__device__ __forceinline__ SimlodPoint* root_voxel(const ImportArgs& a, const Header* hdr, uint32_t rank) {
+	SimlodChunk* c = reinterpret_cast<SimlodChunk*>(a.pers + hdr->rootVoxBase + (uint64_t)(rank / SIMLOD_POINTS_PER_CHUNK) * CHUNK_STRIDE);
+	return &c->points[rank % SIMLOD_POINTS_PER_CHUNK];
+}
+
+__global__ __launch_bounds__(R_TPB) void k_i_groot(ImportArgs a) {
+	__shared__ uint32_t occ[SLAB_WORDS], pre[SLAB_WORDS];
+	__shared__ uint32_t sh_scan[WG_WAVES];
+	__shared__ uint32_t sh_pop;
+	Header* hdr = reinterpret_cast<Header*>(a.scratch);
+	if (hdr->ok == 0u) return;
+	const SimlodExportNode r = a.table[0];
+	uint32_t* grid = grid_of(a, hdr, 0u);
+	if (r.childMask != 0u) {
+		if (threadIdx.x == 0) sh_pop = 0u;
+		__syncthreads();
+		uint32_t pop = 0;
+		const uint4* g4 = reinterpret_cast<const uint4*>(grid);
+		for (uint32_t w = threadIdx.x; w < SIMLOD_GRID_NUM_WORDS / 4u; w += R_TPB) {
+			const uint4 v = g4[w];
+			pop += (uint32_t)(__popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w));
+		}
+		atomicAdd(&sh_pop, pop);
+		__syncthreads();
+		if (threadIdx.x == 0 && sh_pop > r.numSamples) atomicOr(&hdr->gridBad, 1u);
+		return;
+	}
+	const uint32_t n = r.numSamples;
+	const float4* pts = reinterpret_cast<const float4*>(a.samples + r.firstSample);
+	const uint32_t* colors = reinterpret_cast<const uint32_t*>(pts) + 3;             // SimlodPoint.color: the fourth word
+	uint32_t base = 0;                                                                 // voxels of the slabs before
+	for (uint32_t s = 0; s < SLABS; s++) {
+		for (uint32_t w = threadIdx.x; w < SLAB_WORDS; w += R_TPB) occ[w] = 0u;
+		__syncthreads();
+		for (uint32_t i = threadIdx.x; i < n; i += R_TPB) {
+			const float4 p = pts[i];
+			const uint32_t cell = ((quantize(F_FULL, p.x, a.minx, a.size) >> 21) & 127u) + ((quantize(F_FULL, p.y, a.miny, a.size) >> 21) & 127u) * 128u +
+			                      ((quantize(F_FULL, p.z, a.minz, a.size) >> 21) & 127u) * 16384u;
+			if ((cell >> 5) / SLAB_WORDS == s) atomicOr(&occ[(cell >> 5) % SLAB_WORDS], 1u << (cell & 31u));
+		}
+		__syncthreads();
+		const uint32_t w0 = 4u * threadIdx.x;
+		const uint4 mine = make_uint4(occ[w0], occ[w0 + 1u], occ[w0 + 2u], occ[w0 + 3u]);
+		reinterpret_cast<uint4*>(grid)[(s * SLAB_WORDS + w0) / 4u] = mine;
+		const uint32_t c0 = (uint32_t)__popc(mine.x), c1 = (uint32_t)__popc(mine.y), c2 = (uint32_t)__popc(mine.z), c3 = (uint32_t)__popc(mine.w);
+		uint32_t total;
+		const uint32_t off = base + block_scan<uint32_t>(c0 + c1 + c2 + c3, total, sh_scan);
+		pre[w0] = off; pre[w0 + 1u] = off + c0; pre[w0 + 2u] = off + c0 + c1; pre[w0 + 3u] = off + c0 + c1 + c2;
+		// the slab's voxels at their cell centres, colour word = "no point yet"
+		const uint32_t words[4] = {mine.x, mine.y, mine.z, mine.w};
+		for (uint32_t k = 0; k < 4u; k++) {
+			uint32_t bits = words[k], rank = pre[w0 + k];
+			while (bits != 0u) {
+				const uint32_t b = (uint32_t)__ffs((int)bits) - 1u;
+				bits &= bits - 1u;
+				const uint32_t cell = (s * SLAB_WORDS + w0 + k) * 32u + b;
+				const float4 v = voxel_centre(a.size, a.minx, a.miny, a.minz, 0, 0u, 0u, 0u, cell & 127u, (cell >> 7) & 127u, cell >> 14, 0.0f);
+				SimlodPoint* o = root_voxel(a, hdr, rank++);
+				o->x = v.x; o->y = v.y; o->z = v.z; o->color = 0xffffffffu;
+			}
+		}
+		__threadfence();
+		__syncthreads();
+		for (uint32_t i = threadIdx.x; i < n; i += R_TPB) {
+			const float4 p = pts[i];
+			const uint32_t cell = ((quantize(F_FULL, p.x, a.minx, a.size) >> 21) & 127u) + ((quantize(F_FULL, p.y, a.miny, a.size) >> 21) & 127u) * 128u +
+			                      ((quantize(F_FULL, p.z, a.minz, a.size) >> 21) & 127u) * 16384u;
+			if ((cell >> 5) / SLAB_WORDS != s) continue;
+			const uint32_t w = (cell >> 5) % SLAB_WORDS, below = occ[w] & ((1u << (cell & 31u)) - 1u);
+			atomicMin(&root_voxel(a, hdr, pre[w] + (uint32_t)__popc(below))->color, i);
+		}
+		__threadfence();
+		__syncthreads();
+		for (uint32_t k = base + threadIdx.x; k < base + total; k += R_TPB) {
+			SimlodPoint* o = root_voxel(a, hdr, k);
+			const uint32_t idx = __hip_atomic_load(&o->color, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			o->color = idx < n ? colors[4u * (uint64_t)idx] : 0u;          // (every occupied cell has a point: idx < n)
+		}
+		base += total;
+		__syncthreads();                          // (occ and pre are the next slab's)
+	}
+	// the list: consecutive chunks, `next` as the builder leaves it, the head's spare word the tail's address (k_i_nodes)
+	const uint32_t nch = ceil_chunks(base);
+	for (uint32_t k = threadIdx.x; k < nch; k += R_TPB) {
+		SimlodChunk* c = reinterpret_cast<SimlodChunk*>(a.pers + hdr->rootVoxBase + (uint64_t)k * CHUNK_STRIDE);
+		c->next = k + 1u < nch ? reinterpret_cast<SimlodChunk*>(reinterpret_cast<uint8_t*>(c) + CHUNK_STRIDE) : nullptr;
+		*reinterpret_cast<uint64_t*>(&c->size) = k == 0u ? reinterpret_cast<uint64_t>(a.pers + hdr->rootVoxBase + (uint64_t)(nch - 1u) * CHUNK_STRIDE) : 0ull;
+	}
+	if (threadIdx.x == 0) {
+		SimlodNode* root = a.nodes;
+		root->numVoxels = base; root->numVoxelsStored = base;
+		root->voxelChunks = base != 0u ? reinterpret_cast<SimlodChunk*>(a.pers + hdr->rootVoxBase) : nullptr;
+		hdr->rootVoxels = base;
+	}
 }
 
 uint32_t copy_grid(uint64_t itemCap) {
@@ -458,6 +740,44 @@ int launch_import(Context& ctx, const SimlodExportNode* table, uint32_t numNodes
 	forget_leaf_table(ctx, nodes);
 	ctx.sideTablesStale.store(true);
 	array_event(ctx, nodes, ARRAY_IMPORTED);
+	return 0;
+}
+
+int launch_import_buildable(Context& ctx, const SimlodUniforms* u, const SimlodExportNode* table, uint32_t numNodes, const SimlodPoint* samples,
+                            uint64_t numSamples, void* scratch, uint64_t scratchBytes, uint8_t* pers, SimlodNode* nodes, SimlodStats* stats,
+                            uint32_t* numBatchesUploaded, uint32_t* batchSizes, hipStream_t stream) {
+	if (u == nullptr || table == nullptr || scratch == nullptr || pers == nullptr || nodes == nullptr || stats == nullptr || numBatchesUploaded == nullptr ||
+	    batchSizes == nullptr || (samples == nullptr && numSamples != 0u))
+		return (int)hipErrorInvalidValue;
+	if (numNodes == 0u || numNodes > ctx.nodeCapacity.load() || scratchBytes < export_min_bytes(numNodes, numSamples)) return (int)hipErrorInvalidValue;
+	ImportArgs a{};
+	a.table = table; a.n = numNodes; a.samples = samples; a.numSamples = numSamples; a.scratch = reinterpret_cast<uint8_t*>(scratch);
+	a.lay = Layout(numNodes, numSamples); a.pers = pers; a.persCap = u->persistentBufferCapacity; a.nodes = nodes; a.stats = stats;
+	a.buildable = 1u;
+	// the box as kernel_construct derives it (construct.hip launch_construct, voxels.cu:860-863)
+	const float bx = u->boxMax.x - u->boxMin.x, by = u->boxMax.y - u->boxMin.y, bz = u->boxMax.z - u->boxMin.z;
+	a.size = fmaxf(fmaxf(bx, by), bz);
+	a.minx = u->boxMin.x; a.miny = u->boxMin.y; a.minz = u->boxMin.z;
+	a.numBatchesUploaded = numBatchesUploaded; a.batchSizes = batchSizes; a.frameCounter = (uint32_t)u->frameCounter;
+	// what launch_reset forgets of this node array's launches and upload counter (the counter is zeroed by k_i_finish, in stream order)
+	forget_launch_history(ctx, stats, numBatchesUploaded, &a.feedback, &a.feedbackSeq);
+	SIMLOD_LAUNCH(k_i_validate, dim3(1), dim3(WG_TPB), stream, a);
+	SIMLOD_LAUNCH(k_i_nodes, dim3((numNodes + LANE_TPB - 1u) / LANE_TPB), dim3(LANE_TPB), stream, a);
+	SIMLOD_LAUNCH(k_copy, dim3(copy_grid(a.lay.itemCap)), dim3(LANE_TPB), stream, (const uint8_t*)a.scratch, a.lay.items);
+	SIMLOD_LAUNCH(k_i_gleaf, dim3(numNodes), dim3(G_TPB), stream, a);
+	// inner nodes lie at levels 0 .. numInner - 1 at most (and below 20): one launch per level that can have any, deepest first
+	const uint32_t numInner = (numNodes - 1u) / 8u;
+	const uint32_t deepest = std::min<uint32_t>((uint32_t)SIMLOD_MAX_DEPTH - 1u, numInner > 0u ? numInner - 1u : 0u);
+	const uint32_t wgs = std::min<uint32_t>(numNodes, device_info().numCUs * 4u);
+	for (uint32_t level = deepest; level >= 1u; level--) SIMLOD_LAUNCH(k_i_gdown, dim3(wgs), dim3(G_TPB), stream, a, level);
+	SIMLOD_LAUNCH(k_i_groot, dim3(1), dim3(R_TPB), stream, a);
+	SIMLOD_LAUNCH(k_i_finish, dim3(1), dim3(1), stream, a);
+	if (profile_enabled()) profile_close(stream);
+	const int rc = (int)hipGetLastError();
+	if (rc != 0) return rc;
+	forget_leaf_table(ctx, nodes);
+	ctx.sideTablesStale.store(true);
+	array_event(ctx, nodes, ARRAY_IMPORTED_BUILDABLE);
 	return 0;
 }
 

@@ -34,12 +34,32 @@ __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi
 // exact 2^level as fp32 (the reference's pow(2.0f, float(level)))
 __device__ __forceinline__ float exp2_int(uint32_t level) { return __uint_as_float((127u + level) << 23); }
 
+// the two scales quantize() is used with: the node grid and the full-depth sample coordinates (the same fp32 quotient times an exact power of two)
+static constexpr float F_GRID = 1048576.0f;      // 2^MAX_DEPTH, progressive_octree_voxels.cu:139
+static constexpr float F_FULL = 268435456.0f;    // MAX_DEPTH_GRIDSIZE, structures.cuh:26
+
 // fp32 -> u32 quantisation of one coordinate, progressive_octree_voxels.cu:148-155: scale * (p - min) / size,
 // evaluated left to right in fp32, truncated (v_cvt_u32_f32 saturates: NaN/negative -> 0).
 __device__ __forceinline__ uint32_t quantize(float scale, float p, float mn, float size) {
 	float v = scale * (p - mn);
 	v = v / size;
 	return (uint32_t)v;
+}
+
+// cell-centre position of a voxel, voxels.cu:103-114, operation by operation (no contraction): cell (cx, cy, cz) of the 128^3 grid of the
+// level-`level` node with coordinates (nX, nY, nZ) in the box (min, size)
+__device__ __forceinline__ float4 voxel_centre(float size, float minx, float miny, float minz, int level, uint32_t nX, uint32_t nY, uint32_t nZ,
+                                               uint32_t cx, uint32_t cy, uint32_t cz, float colorBits) {
+	const float nodeSize = size / exp2_int((uint32_t)level);
+	const float nminx = ((float)nX + 0.0f) * nodeSize + minx;
+	const float nminy = ((float)nY + 0.0f) * nodeSize + miny;
+	const float nminz = ((float)nZ + 0.0f) * nodeSize + minz;
+	float4 v;
+	v.x = nminx + (nodeSize * ((float)cx + 0.5f)) / 128.0f;
+	v.y = nminy + (nodeSize * ((float)cy + 0.5f)) / 128.0f;
+	v.z = nminz + (nodeSize * ((float)cz + 0.5f)) / 128.0f;
+	v.w = colorBits;                       // colour of the claiming point
+	return v;
 }
 
 __device__ __forceinline__ int child_index(uint32_t X, uint32_t Y, uint32_t Z, int level) {

@@ -173,6 +173,7 @@ void array_event(Context& ctx, const void* nodes, ArrayEvent e) {
 	case ARRAY_CONSTRUCT: st->rendered = false; break;
 	case ARRAY_RENDERED: st->rendered = true; break;
 	case ARRAY_IMPORTED: st->rendered = false; st->imported = true; break;
+	case ARRAY_IMPORTED_BUILDABLE: st->rendered = false; st->imported = false; break;
 	}
 }
 
@@ -536,6 +537,14 @@ int simlod_export_octree(const SimlodNode* nodes, const SimlodStats* stats, uint
 int simlod_import_octree(const SimlodExportNode* table, uint32_t numNodes, const SimlodPoint* samples, uint64_t numSamples, void* scratch,
                          uint64_t scratchBytes, uint8_t* persistent, uint64_t persistentCapacity, SimlodNode* nodes, SimlodStats* stats, void* stream) {
 	return launch_import(context_of(nodes), table, numNodes, samples, numSamples, scratch, scratchBytes, persistent, persistentCapacity, nodes, stats, (hipStream_t)stream);
+}
+
+int simlod_import_octree_buildable(const SimlodUniforms* uniforms, const SimlodExportNode* table, uint32_t numNodes, const SimlodPoint* samples,
+                                   uint64_t numSamples, void* scratch, uint64_t scratchBytes, uint8_t* persistent, SimlodNode* nodes,
+                                   SimlodStats* stats, uint32_t* numBatchesUploaded, uint32_t* batchSizes, void* stream) {
+	if (!uniforms || !numBatchesUploaded || !batchSizes) return (int)hipErrorInvalidValue;
+	return launch_import_buildable(context_of(nodes), uniforms, table, numNodes, samples, numSamples, scratch, scratchBytes, persistent, nodes, stats,
+	                               numBatchesUploaded, batchSizes, (hipStream_t)stream);
 }
 
 uint64_t simlod_colorfilter_buffer_min_bytes(void) { return colorfilter_min_bytes(default_context().nodeCapacity.load()); }

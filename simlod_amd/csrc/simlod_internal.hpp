@@ -83,7 +83,7 @@ void destroy_side_stream(SideStream* s);
 // import (SIMLOD_EXPORT_VISIBLE reads the visible / isLarge bytes that frame wrote) | it holds an imported octree (no grids, no builder state:
 // kernel_construct and the colour filter refuse it until the next reset).  Keyed by node array, not by context: two arrays may share one.
 struct ArrayState { const void* nodes; bool rendered, imported; };
-enum ArrayEvent : int { ARRAY_RESET, ARRAY_CONSTRUCT, ARRAY_RENDERED, ARRAY_IMPORTED };
+enum ArrayEvent : int { ARRAY_RESET, ARRAY_CONSTRUCT, ARRAY_RENDERED, ARRAY_IMPORTED, ARRAY_IMPORTED_BUILDABLE };   // (buildable: grids and builder state, as after a reset)
 
 struct Context {
 	std::atomic<uint32_t> nodeCapacity{263157u};             // 40 000 000 B / 152 B, main_progressive_octree.cpp:552
@@ -184,6 +184,9 @@ int launch_export(Context& ctx, const SimlodNode* nodes, const SimlodStats* stat
                   SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodExportCounts* counts, hipStream_t stream);
 int launch_import(Context& ctx, const SimlodExportNode* table, uint32_t numNodes, const SimlodPoint* samples, uint64_t numSamples, void* scratch,
                   uint64_t scratchBytes, uint8_t* pers, uint64_t persCapacity, SimlodNode* nodes, SimlodStats* stats, hipStream_t stream);
+int launch_import_buildable(Context& ctx, const SimlodUniforms* u, const SimlodExportNode* table, uint32_t numNodes, const SimlodPoint* samples,
+                            uint64_t numSamples, void* scratch, uint64_t scratchBytes, uint8_t* pers, SimlodNode* nodes, SimlodStats* stats,
+                            uint32_t* numBatchesUploaded, uint32_t* batchSizes, hipStream_t stream);
 uint64_t export_min_bytes(uint32_t nodeCapacity, uint64_t sampleCapacity);
 int launch_generate_terrain(SimlodPoint* out, uint64_t numPoints, uint64_t firstIndex, uint64_t pointsPerTile, uint32_t seed, uint32_t tilesX,
                             const float tileExtent[3], float swathWidth, hipStream_t stream);

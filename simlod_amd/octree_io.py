@@ -86,10 +86,26 @@ class OctreeExport:
     def to(self, device):
         return OctreeExport(self.table_tensor.to(device), self.samples_tensor.to(device), self.box_min, self.box_max, self.max_level, self.select)
 
-    def validate(self):
-        """The host-side mirror of the checks simlod_import_octree runs on the device; raises ValueError naming the first that fails."""
-        validate_table(self.nodes, self.num_samples)
+    def validate(self, buildable=False):
+        """The host-side mirror of the checks simlod_import_octree runs on the device; raises ValueError naming the first that fails.
+        buildable=True: also those of simlod_import_octree_buildable — a full export (select "all", max_level 20) of an octree the builder made
+        (validate_table(buildable=True))."""
+        if buildable:
+            if self.select != abi.EXPORT_ALL:
+                raise ValueError(f"not a full export (select {self.select}): a resumable octree needs every node's samples")
+            if self.max_level < abi.MAX_DEPTH:
+                raise ValueError(f"a truncated export (max_level {self.max_level}): a resumable octree needs every level")
+        validate_table(self.nodes, self.num_samples, buildable)
         return self
+
+    @property
+    def is_buildable(self):
+        """Whether import_octree(buildable=True) accepts this export (validate(buildable=True) passes)."""
+        try:
+            self.validate(buildable=True)
+        except ValueError:
+            return False
+        return True
 
     def save(self, path):
         h = np.zeros(1, dtype=header_dtype)
@@ -122,12 +138,20 @@ class OctreeExport:
         return ex.validate()
 
 
-def validate_table(t, num_samples):
-    """Checks of a table against itself (and the sample count): see OctreeExport.validate."""
+def validate_table(t, num_samples, buildable=False):
+    """Checks of a table against itself (and the sample count): see OctreeExport.validate.  buildable: the device checks of
+    simlod_import_octree_buildable too — every entry selected, the leaf flag set exactly on the entries without children, eight children or none."""
     t = np.asarray(t).view(abi.export_node_dtype)
     n = len(t)
     if n == 0:
         raise ValueError("empty table: no root")
+    if buildable:
+        if ((t["flags"] & abi.EXPORT_FLAG_SELECTED) == 0).any():
+            raise ValueError("an entry is not selected: its samples are missing")
+        if (((t["flags"] & abi.EXPORT_FLAG_LEAF) != 0) != (t["childMask"] == 0)).any():
+            raise ValueError("the leaf flag does not match the children (a truncated export)")
+        if ((t["childMask"] != 0) & (t["childMask"] != 0xFF)).any():
+            raise ValueError("a node with neither eight children nor none")
     if n > 0xFFFFFFFE:
         raise ValueError("too many nodes")
     level = t["level"].astype(np.int64)

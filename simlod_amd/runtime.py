@@ -86,6 +86,7 @@ def lib():
         L.simlod_export_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_export_octree.argtypes = [vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
         L.simlod_import_octree.argtypes = [vp, u32, vp, u64, vp, u64, vp, u64, vp, vp, vp]
+        L.simlod_import_octree_buildable.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -101,7 +102,7 @@ EXPORTED_SYMBOLS = [
     "simlod_octree_image_replaced", "simlod_render_frame_composed", "simlod_render_frame_rccl", "simlod_context_set_trunk_mask", "simlod_rccl_version",
     "simlod_context_hint_pending_batches", "simlod_upload_counter_written",
     "simlod_profile_enable", "simlod_profile_collect", "simlod_generate_terrain", "simlod_generate_terrain_scan", "simlod_launch_colorfilter", "simlod_colorfilter_buffer_min_bytes",
-    "simlod_export_buffer_min_bytes", "simlod_export_octree", "simlod_import_octree",
+    "simlod_export_buffer_min_bytes", "simlod_export_octree", "simlod_import_octree", "simlod_import_octree_buildable",
 ]
 
 
@@ -598,21 +599,49 @@ class DeviceOctree:
         return OctreeExport(table[: int(c["numNodes"]) * abi.export_node_dtype.itemsize], samples[: int(c["numSamples"]) * abi.point_dtype.itemsize],
                             u["boxMin"], u["boxMax"], ml, sel)
 
-    def import_octree(self, export, check=True):
+    def import_octree(self, export, check=True, *, buildable=False, uniforms=None):
         """Replace this object's octree by `export` (an octree_io.OctreeExport on the host or on a device): simlod_import_octree validates the
         table on the device and writes a renderable octree into the node array and the persistent buffer.  check: read Stats back and raise
-        SimlodError when the table failed validation (SIMLOD_ERR_IMPORT).  Until the next reset, construct() and colorfilter() refuse it."""
+        SimlodError when the table failed validation (SIMLOD_ERR_IMPORT).  Until the next reset, construct() and colorfilter() refuse it.
+
+        buildable=True: simlod_import_octree_buildable — the occupancy grids and a builder state as after a reset too, so that construct()
+        goes on ingesting into the octree.  `uniforms` (required) give the box, which must be the export's, and the persistent capacity; the
+        export must be a full one (select "all", max_level 20: OctreeExport.validate(buildable=True)).  Both are checked here, before anything
+        is enqueued (SimlodError).  check=True also raises on SIMLOD_ERR_IMPORT_GRID (a grid disagrees with the table: the wrong box)."""
+        if buildable:
+            if uniforms is None:
+                raise SimlodError("import_octree(buildable=True) needs the uniforms the octree goes on being built with")
+            u0 = np.asarray(uniforms).reshape(-1)[0]
+            if tuple(np.asarray(u0["boxMin"], np.float32).tolist()) != export.box_min or tuple(np.asarray(u0["boxMax"], np.float32).tolist()) != export.box_max:
+                raise SimlodError(f"import_octree(buildable=True): the uniforms' box {tuple(u0['boxMin'])}..{tuple(u0['boxMax'])} is not the export's "
+                                  f"{export.box_min}..{export.box_max}")
+            try:
+                export.validate(buildable=True)
+            except ValueError as e:
+                raise SimlodError(f"import_octree(buildable=True): {e}") from None
         table = export.table_tensor.to(self.device)
         samples = export.samples_tensor.to(self.device)
         n, m = export.num_nodes, export.num_samples
         need = int(self.L.simlod_export_buffer_min_bytes(n, m))
         scratch = self._export_scratch(need)
-        _check(self.L.simlod_import_octree(self._p(table), n, self._p(samples), ctypes.c_uint64(m), self._p(scratch), ctypes.c_uint64(scratch.numel()),
-                                           self._p(self.persistent), ctypes.c_uint64(self.persistent_bytes), self._p(self.nodes), self._p(self.stats),
-                                           self._stream()), "simlod_import_octree")
+        if buildable:
+            u, up = self._u(uniforms)
+            _check(self.L.simlod_import_octree_buildable(up, self._p(table), n, self._p(samples), ctypes.c_uint64(m), self._p(scratch),
+                                                         ctypes.c_uint64(scratch.numel()), self._p(self.persistent), self._p(self.nodes), self._p(self.stats),
+                                                         self._p(self.num_uploaded), self._p(self.batch_sizes), self._stream()), "simlod_import_octree_buildable")
+            what, bits = "simlod_import_octree_buildable", abi.SIMLOD_ERR_IMPORT | abi.SIMLOD_ERR_IMPORT_GRID
+        else:
+            _check(self.L.simlod_import_octree(self._p(table), n, self._p(samples), ctypes.c_uint64(m), self._p(scratch), ctypes.c_uint64(scratch.numel()),
+                                               self._p(self.persistent), ctypes.c_uint64(self.persistent_bytes), self._p(self.nodes), self._p(self.stats),
+                                               self._stream()), "simlod_import_octree")
+            what, bits = "simlod_import_octree", abi.SIMLOD_ERR_IMPORT
         self.uploaded_host = self.processed_host = 0
-        if check and int(self.read_stats()["dbg"]) & abi.SIMLOD_ERR_IMPORT:
-            raise SimlodError("simlod_import_octree: the table failed validation on the device (SIMLOD_ERR_IMPORT)")
+        if check:
+            dbg = int(self.read_stats()["dbg"]) & bits
+            if dbg & abi.SIMLOD_ERR_IMPORT:
+                raise SimlodError(f"{what}: the table failed validation on the device (SIMLOD_ERR_IMPORT)")
+            if dbg & abi.SIMLOD_ERR_IMPORT_GRID:
+                raise SimlodError(f"{what}: a rebuilt occupancy grid disagrees with the table — not the box the octree was built with (SIMLOD_ERR_IMPORT_GRID)")
 
     def download_image(self):
         """(nodes, persistent, numNodes, device base addresses) — the octree image as host arrays, pointers untouched."""
