@@ -352,6 +352,65 @@ int simlod_import_octree_buildable(const SimlodUniforms* uniforms, const SimlodE
                                    uint64_t numSamples, void* scratch, uint64_t scratchBytes, uint8_t* persistent, SimlodNode* nodes,
                                    SimlodStats* stats, uint32_t* numBatchesUploaded, uint32_t* batchSizes, void* stream);
 
+/* ---- region queries: the samples inside a convex region at a chosen level of detail ---------------------------------------------------
+ * simlod_query_region writes what simlod_export_octree writes — a breadth-first table and a sample array — restricted to the intersection of
+ * up to 16 half-spaces.  The result is an ordinary table: it validates, saves, and imports render-only (a crop).  The source is only read.
+ *
+ * The box is the builder's: min = uniforms.boxMin, size = the largest extent (fmaxf of the fp32 differences boxMax - boxMin).  All geometry is
+ * fp64 computed from the fp32 inputs without fused multiply-add, every sum in the order written here.
+ *  1. Listed nodes.  Entry 0 is the root.  A node below it is listed iff its parent is listed, its level is <= maxLevel and it is not OUTSIDE.
+ *     With s = size / 2^level, e = size * 2^-20, lo_a = (min_a + A * s) - e and hi_a = (min_a + (A + 1) * s) + e for the node's coordinate A on
+ *     axis a, a node is outside iff D_max = ((nx*fx + ny*fy) + nz*fz) + d < 0 for some plane, f_a = n_a >= 0 ? hi_a : lo_a (the corner farthest
+ *     along the normal).  The inflation by e (one level-20 cell) covers the fp32 rounding of the builder's quantisation, which can file a point
+ *     up to about size * 2^-22 beyond the exact face of its node.  childMask / firstChild / parent describe the listed nodes only.
+ *  2. Selected nodes among the listed: SIMLOD_EXPORT_ALL every one, SIMLOD_EXPORT_CUT the source leaves and the nodes at maxLevel.  FLAG_LEAF
+ *     keeps its meaning (a leaf of the source octree).  A root that is outside is listed and contributes no samples.
+ *  3. A selected node that is not outside contributes those of its samples with ((nx*x + ny*y) + nz*z) + d >= 0 for every plane (a NaN fails),
+ *     in chunk-list order with the failing ones removed.  numSamples / firstSample are the counts after filtering and their scan.
+ *  4. Such a node is COPIED without a per-sample test iff D_min >= 0 for every plane (the nearest corner of the same inflated cube:
+ *     f_a = n_a >= 0 ? lo_a : hi_a); else it is FILTERED.  For finite samples in the half-open box min <= p < min + size neither the culling nor
+ *     the shortcut changes the result.  OUTSIDE THE CONTRACT: samples outside that box, on its max faces, or with non-finite coordinates.  The
+ *     builder does not keep them in the node whose cube holds them (a point with x == min + size is stored under nodes with X = 0); such a sample
+ *     is returned iff the node it is stored in is copied, or is filtered and the sample passes the test.
+ *  5. samples == NULL: count only — the table and the counts are complete and nothing else is written (sampleCapacity is ignored).  Otherwise
+ *     a tableCapacity or sampleCapacity that is too small sets SIMLOD_EXPORT_ERR_CAPACITY and nothing is written beyond either.  Stats.numNodes
+ *     and Stats.numPoints + Stats.numVoxels bound every result.
+ *  6. With zero planes the result equals simlod_export_octree(maxLevel, select) byte for byte and every node with samples is copied. */
+#define SIMLOD_REGION_MAX_PLANES 16u
+typedef struct SimlodRegion {          /* host memory, read before the call returns */
+	uint32_t numPlanes;                /* 0..16; 0: the whole space */
+	uint32_t reserved[3];              /* 0 */
+	float    planes[SIMLOD_REGION_MAX_PLANES][4];   /* (nx, ny, nz, d): a point is inside iff nx*x + ny*y + nz*z + d >= 0 for every plane */
+} SimlodRegion;
+typedef struct SimlodQueryCounts {     /* written by the device */
+	uint32_t numNodes;                 /* table entries written                                                                  */
+	uint32_t error;                    /* SIMLOD_EXPORT_ERR_* bits                                                               */
+	uint64_t numSamples;               /* samples that passed (= written, unless count-only or a capacity error)                 */
+	uint64_t numCandidates;            /* samples of the selected, listed nodes that are not outside, before the test            */
+	uint32_t numFilteredNodes;         /* such nodes (with at least one sample) whose samples were tested one by one             */
+	uint32_t numCopiedNodes;           /* such nodes (with at least one sample) that were copied without a test                  */
+} SimlodQueryCounts;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodRegion) == 272, "Region");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRegion, planes) == 16, "Region.planes");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodQueryCounts) == 32, "QueryCounts");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodQueryCounts, numSamples) == 8, "QueryCounts.numSamples");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodQueryCounts, numCandidates) == 16, "QueryCounts.numCandidates");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodQueryCounts, numFilteredNodes) == 24, "QueryCounts.numFilteredNodes");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodQueryCounts, numCopiedNodes) == 28, "QueryCounts.numCopiedNodes");
+
+/* Bytes of the `scratch` buffer a query needs for a table of up to nodeCapacity entries whose selected nodes hold up to sampleBound samples
+ * BEFORE the test (Stats.numPoints + Stats.numVoxels always suffices): one 32-byte item per 1 000-sample chunk.  A buffer that holds the
+ * table's part but too few items makes the query report SIMLOD_EXPORT_ERR_CAPACITY. */
+uint64_t simlod_query_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+
+/* The region query (rules above).  Asynchronous on `stream`; everything in between lives in `scratch`.  hipErrorInvalidValue with nothing
+ * enqueued: a null pointer other than `samples`, numPlanes > 16, a non-finite coefficient, nonzero `reserved`, `select` other than
+ * SIMLOD_EXPORT_ALL / SIMLOD_EXPORT_CUT, scratchBytes below simlod_query_buffer_min_bytes(tableCapacity, 0).  While the builder's chunk table
+ * for `nodes` is valid the first chunks of each list come from it, the rest by `next` (as simlod_export_octree). */
+int simlod_query_region(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                        uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
+                        SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

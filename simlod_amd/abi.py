@@ -111,6 +111,7 @@ def make_uniforms(width, height, transform, box_size, *, transform_update_bound=
 # ---- octree export / import (include/simlod_hip.h, "octree export / import") ---------------------------------------------------------
 EXPORT_ALL, EXPORT_CUT, EXPORT_VISIBLE = 0, 1, 2
 EXPORT_SELECT = {"all": EXPORT_ALL, "cut": EXPORT_CUT, "visible": EXPORT_VISIBLE}
+EXPORT_REGION = 3                       # the `select` an OctreeExport carries that came from a region query (never passed to the device)
 EXPORT_NONE = 0xFFFFFFFF
 EXPORT_FLAG_LEAF, EXPORT_FLAG_SELECTED = 0x1, 0x2
 EXPORT_ERR_CAPACITY, EXPORT_ERR_NODE_COUNT, EXPORT_ERR_SHORT_LIST = 0x1, 0x2, 0x4
@@ -125,3 +126,11 @@ export_node_dtype = np.dtype({
 })
 export_counts_dtype = np.dtype({"names": ["numNodes", "error", "numSamples"], "formats": ["<u4", "<u4", "<u8"], "offsets": [0, 4, 8], "itemsize": 16})
 assert export_node_dtype.itemsize == 40 and export_counts_dtype.itemsize == 16
+
+# ---- region queries (include/simlod_hip.h, "region queries") ----------------------------------------------------------------------------
+REGION_MAX_PLANES = 16
+region_dtype = np.dtype({"names": ["numPlanes", "reserved", "planes"], "formats": ["<u4", ("<u4", 3), ("<f4", (REGION_MAX_PLANES, 4))],
+                         "offsets": [0, 4, 16], "itemsize": 272})
+query_counts_dtype = np.dtype({"names": ["numNodes", "error", "numSamples", "numCandidates", "numFilteredNodes", "numCopiedNodes"],
+                               "formats": ["<u4", "<u4", "<u8", "<u8", "<u4", "<u4"], "offsets": [0, 4, 8, 16, 24, 28], "itemsize": 32})
+assert region_dtype.itemsize == 272 and query_counts_dtype.itemsize == 32

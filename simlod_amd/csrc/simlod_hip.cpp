@@ -547,6 +547,15 @@ int simlod_import_octree_buildable(const SimlodUniforms* uniforms, const SimlodE
 	                               numBatchesUploaded, batchSizes, (hipStream_t)stream);
 }
 
+uint64_t simlod_query_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return query_min_bytes(nodeCapacity, sampleBound); }
+
+int simlod_query_region(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region, uint32_t maxLevel,
+                        uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
+                        uint64_t sampleCapacity, SimlodQueryCounts* counts, void* stream) {
+	return launch_query(context_of(nodes), nodes, stats, uniforms, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples,
+	                    sampleCapacity, counts, (hipStream_t)stream);
+}
+
 uint64_t simlod_colorfilter_buffer_min_bytes(void) { return colorfilter_min_bytes(default_context().nodeCapacity.load()); }
 
 int simlod_generate_terrain(SimlodPoint* out, uint64_t numPoints, uint64_t firstIndex, uint64_t pointsPerTile, uint32_t seed, uint32_t tilesX,

@@ -188,6 +188,10 @@ int launch_import_buildable(Context& ctx, const SimlodUniforms* u, const SimlodE
                             uint64_t numSamples, void* scratch, uint64_t scratchBytes, uint8_t* pers, SimlodNode* nodes, SimlodStats* stats,
                             uint32_t* numBatchesUploaded, uint32_t* batchSizes, hipStream_t stream);
 uint64_t export_min_bytes(uint32_t nodeCapacity, uint64_t sampleCapacity);
+int launch_query(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region, uint32_t maxLevel,
+                 uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
+                 uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream);
+uint64_t query_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
 int launch_generate_terrain(SimlodPoint* out, uint64_t numPoints, uint64_t firstIndex, uint64_t pointsPerTile, uint32_t seed, uint32_t tilesX,
                             const float tileExtent[3], float swathWidth, hipStream_t stream);
 enum : uint32_t { RENDER_FIRST = 1u, RENDER_COLOR = 2u, RENDER_RESOLVE = 4u, RENDER_OUTPUT = 8u, RENDER_ALL = 15u };

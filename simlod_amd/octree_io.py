@@ -6,7 +6,7 @@ File format (little-endian throughout):
     offset  bytes  field
          0      8  magic b"SIMLODX\\0"
          8      4  version (1)
-        12      4  select (0 all, 1 cut, 2 visible)
+        12      4  select (0 all, 1 cut, 2 visible, 3 a region query: a crop)
         16      4  max_level (20: every level)
         20      4  header bytes (64)
         24      8  numNodes
@@ -17,6 +17,9 @@ File format (little-endian throughout):
                     numSamples x 16-byte SimlodPoint (abi.point_dtype)
 
 `load` checks the header, the file size and the table (`validate`) before anything reaches a device.
+
+Region queries (include/simlod_hip.h, "region queries"): `Region` holds the half-spaces, and `OctreeExport.crop` is the host mirror of
+simlod_query_region — every rule restated in numpy float64, which reproduces the device's fp64 arithmetic bit for bit.
 """
 import numpy as np
 import torch
@@ -107,6 +110,79 @@ class OctreeExport:
             return False
         return True
 
+    def crop(self, region, max_level=None, select="all", return_counts=False):
+        """The host mirror of simlod_query_region: what the device returns for `region` on the octree this FULL export (select "all", max level
+        20; anything else ValueError) was taken from, as an OctreeExport on the host — and, return_counts, the SimlodQueryCounts record too."""
+        if self.select != abi.EXPORT_ALL or self.max_level < abi.MAX_DEPTH:
+            raise ValueError(f"crop needs a full export (select all, max level 20), not select {self.select} / max level {self.max_level}")
+        sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
+        if sel not in (abi.EXPORT_ALL, abi.EXPORT_CUT):
+            raise ValueError("a region query selects 'all' or 'cut'")
+        ml = abi.MAX_DEPTH if max_level is None else max(0, min(int(max_level), abi.MAX_DEPTH))
+        src, smp = self.nodes, self.samples
+        pl = np.asarray(region.planes, dtype=np.float32).astype(np.float64)
+        mn, size = _box_of(self.box_min, self.box_max)
+        outside, inside = classify_nodes(pl, src, self.box_min, self.box_max)
+        # the breadth-first walk over the listed nodes
+        order, parent, masks, firsts = [0], [abi.EXPORT_NONE], [], []
+        t = 0
+        while t < len(order):
+            nd = src[order[t]]
+            mask, first = 0, abi.EXPORT_NONE
+            if int(nd["level"]) < ml and nd["childMask"]:
+                c = int(nd["firstChild"])
+                for k in range(8):
+                    if not (int(nd["childMask"]) >> k) & 1:
+                        continue
+                    if not outside[c]:
+                        if first == abi.EXPORT_NONE:
+                            first = len(order)
+                        mask |= 1 << k
+                        order.append(c)
+                        parent.append(t)
+                    c += 1
+            masks.append(mask)
+            firsts.append(first)
+            t += 1
+        order = np.asarray(order, dtype=np.int64)
+        out = src[order].copy()
+        out["parent"], out["firstChild"], out["childMask"] = parent, firsts, masks
+        leaf = (out["flags"] & abi.EXPORT_FLAG_LEAF) != 0
+        chosen = np.ones(len(out), bool) if sel == abi.EXPORT_ALL else leaf | (out["level"] == ml)
+        out["flags"] = np.where(leaf, abi.EXPORT_FLAG_LEAF, 0) | np.where(chosen, abi.EXPORT_FLAG_SELECTED, 0)
+        cand = np.where(chosen & ~outside[order], src["numSamples"][order], 0).astype(np.int64)
+        # rule 3 on every sample at once; rule 4's promise on the samples of the contract (finite, in the half-open box)
+        x, y, z = (smp[a].astype(np.float64) for a in ("x", "y", "z"))
+        ok = np.ones(len(smp), bool)
+        with np.errstate(invalid="ignore"):
+            for nx, ny, nz, d in pl:
+                ok &= ((nx * x + ny * y) + nz * z) + d >= 0
+            inbox = (x >= mn[0]) & (x < mn[0] + size) & (y >= mn[1]) & (y < mn[1] + size) & (z >= mn[2]) & (z < mn[2] + size)
+        parts, ns_out = [], np.zeros(len(out), np.int64)
+        n_filtered = n_copied = 0
+        for t in np.nonzero(cand)[0]:
+            i = order[t]
+            a = int(src["firstSample"][i])
+            seg = slice(a, a + int(cand[t]))
+            if inside[i]:
+                assert (ok[seg] | ~inbox[seg]).all(), f"node {i} is copied and holds a sample of the box that fails the test"
+                parts.append(smp[seg])
+                n_copied += 1
+            else:
+                parts.append(smp[seg][ok[seg]])
+                n_filtered += 1
+            ns_out[t] = len(parts[-1])
+        out["numSamples"] = ns_out
+        out["firstSample"] = np.concatenate([[0], np.cumsum(ns_out)[:-1]]).astype(np.uint64)
+        samples = np.concatenate(parts) if parts else np.zeros(0, dtype=abi.point_dtype)
+        ex = OctreeExport(out, samples, self.box_min, self.box_max, ml, abi.EXPORT_REGION)
+        if not return_counts:
+            return ex
+        c = np.zeros((), dtype=abi.query_counts_dtype)
+        c["numNodes"], c["numSamples"], c["numCandidates"] = len(out), len(samples), int(cand.sum())
+        c["numFilteredNodes"], c["numCopiedNodes"] = n_filtered, n_copied
+        return ex, c
+
     def save(self, path):
         h = np.zeros(1, dtype=header_dtype)
         h["magic"], h["version"], h["select"], h["max_level"], h["header_bytes"] = MAGIC, VERSION, self.select, self.max_level, HEADER_BYTES
@@ -128,7 +204,7 @@ class OctreeExport:
             raise ValueError(f"{path}: not an octree export (magic)")
         if int(h["version"]) != VERSION or int(h["header_bytes"]) != HEADER_BYTES:
             raise ValueError(f"{path}: unsupported version {int(h['version'])}")
-        if int(h["select"]) > abi.EXPORT_VISIBLE:
+        if int(h["select"]) > abi.EXPORT_REGION:
             raise ValueError(f"{path}: unknown selection {int(h['select'])}")
         n, m = int(h["numNodes"]), int(h["numSamples"])
         tb, sb = n * abi.export_node_dtype.itemsize, m * abi.point_dtype.itemsize
@@ -136,6 +212,71 @@ class OctreeExport:
             raise ValueError(f"{path}: {raw.size} bytes, the header announces {HEADER_BYTES + tb + sb}")
         ex = cls(raw[HEADER_BYTES: HEADER_BYTES + tb].copy(), raw[HEADER_BYTES + tb:].copy(), h["box_min"], h["box_max"], int(h["max_level"]), int(h["select"]))
         return ex.validate()
+
+
+def _box_of(box_min, box_max):
+    """(min as float64, size): the box as construct.hip derives it — the largest of the fp32 differences boxMax - boxMin."""
+    mn32, mx32 = np.asarray(box_min, np.float32), np.asarray(box_max, np.float32)
+    return mn32.astype(np.float64), np.float64((mx32 - mn32).max())
+
+
+def classify_nodes(planes, nodes, box_min, box_max):
+    """Rules 1 and 4 of the region query for every entry of a table: (outside, inside) as boolean arrays — the inflated cube of the node
+    against every plane (N x 4, float64 values of the float32 coefficients).  Neither: the node is filtered sample by sample."""
+    mn, size = _box_of(box_min, box_max)
+    s = np.ldexp(size, -nodes["level"].astype(np.int64))[:, None]
+    e = np.ldexp(size, -abi.MAX_DEPTH)
+    A = np.stack([nodes["X"], nodes["Y"], nodes["Z"]], axis=1).astype(np.float64)
+    lo, hi = (mn + A * s) - e, (mn + (A + 1.0) * s) + e
+    outside, inside = np.zeros(len(nodes), bool), np.ones(len(nodes), bool)
+    for nx, ny, nz, d in np.asarray(planes, dtype=np.float64).reshape(-1, 4):
+        fx, fy, fz = (hi if nx >= 0 else lo)[:, 0], (hi if ny >= 0 else lo)[:, 1], (hi if nz >= 0 else lo)[:, 2]
+        gx, gy, gz = (lo if nx >= 0 else hi)[:, 0], (lo if ny >= 0 else hi)[:, 1], (lo if nz >= 0 else hi)[:, 2]
+        outside |= ((nx * fx + ny * fy) + nz * fz) + d < 0
+        inside &= ((nx * gx + ny * gy) + nz * gz) + d >= 0
+    return outside, inside
+
+
+class Region:
+    """A convex region: up to 16 half-spaces (nx, ny, nz, d) as float32; a point is inside iff nx*x + ny*y + nz*z + d >= 0 for every one.
+    No planes: the whole space."""
+
+    def __init__(self, planes=()):
+        p = np.asarray(planes, dtype=np.float64).reshape(-1, 4)
+        if len(p) > abi.REGION_MAX_PLANES:
+            raise ValueError(f"{len(p)} planes: a region has at most {abi.REGION_MAX_PLANES}")
+        with np.errstate(over="ignore"):
+            self.planes = p.astype(np.float32)
+        if not np.isfinite(self.planes).all():
+            raise ValueError("a plane coefficient is not finite (as float32)")
+
+    @classmethod
+    def from_planes(cls, planes):
+        return cls(planes)
+
+    @classmethod
+    def from_box(cls, lo, hi):
+        """The axis-aligned box lo <= p <= hi: per axis the planes (+e, -lo) and (-e, +hi)."""
+        lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+        p = np.zeros((6, 4))
+        for a in range(3):
+            p[2 * a, a], p[2 * a, 3] = 1.0, -lo[a]
+            p[2 * a + 1, a], p[2 * a + 1, 3] = -1.0, hi[a]
+        return cls(p)
+
+    @classmethod
+    def from_frustum(cls, transform):
+        """The view frustum's four side planes and w >= 0 of a world-view-projection matrix as the uniforms store it (row-major: clip = M (p, 1)):
+        w + x, w - x, w + y, w - y, w."""
+        m = np.asarray(transform, dtype=np.float64).reshape(4, 4)
+        return cls(np.stack([m[3] + m[0], m[3] - m[0], m[3] + m[1], m[3] - m[1], m[3]]))
+
+    def record(self):
+        """The SimlodRegion the C ABI takes (abi.region_dtype, one record)."""
+        r = np.zeros(1, dtype=abi.region_dtype)
+        r["numPlanes"] = len(self.planes)
+        r["planes"][0, : len(self.planes)] = self.planes
+        return r
 
 
 def validate_table(t, num_samples, buildable=False):

@@ -87,6 +87,9 @@ def lib():
         L.simlod_export_octree.argtypes = [vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
         L.simlod_import_octree.argtypes = [vp, u32, vp, u64, vp, u64, vp, u64, vp, vp, vp]
         L.simlod_import_octree_buildable.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp]
+        L.simlod_query_buffer_min_bytes.restype = u64
+        L.simlod_query_buffer_min_bytes.argtypes = [u32, u64]
+        L.simlod_query_region.argtypes = [vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
         _lib = L
     return _lib
 
@@ -103,6 +106,7 @@ EXPORTED_SYMBOLS = [
     "simlod_context_hint_pending_batches", "simlod_upload_counter_written",
     "simlod_profile_enable", "simlod_profile_collect", "simlod_generate_terrain", "simlod_generate_terrain_scan", "simlod_launch_colorfilter", "simlod_colorfilter_buffer_min_bytes",
     "simlod_export_buffer_min_bytes", "simlod_export_octree", "simlod_import_octree", "simlod_import_octree_buildable",
+    "simlod_query_buffer_min_bytes", "simlod_query_region",
 ]
 
 
@@ -598,6 +602,51 @@ class DeviceOctree:
         u = np.asarray(uniforms).reshape(-1)[0]
         return OctreeExport(table[: int(c["numNodes"]) * abi.export_node_dtype.itemsize], samples[: int(c["numSamples"]) * abi.point_dtype.itemsize],
                             u["boxMin"], u["boxMax"], ml, sel)
+
+    # -- region queries (include/simlod_hip.h, "region queries") ---------------------------------------------------------------------------
+    def _query(self, uniforms, region, ml, sel, table, samples, sample_capacity, bound):
+        """One simlod_query_region call -> the SimlodQueryCounts record (host).  samples None: count only."""
+        u, up = self._u(uniforms)
+        r = region.record()
+        nn = table.numel() // abi.export_node_dtype.itemsize
+        scratch = self._export_scratch(int(self.L.simlod_query_buffer_min_bytes(nn, bound)))
+        counts = torch.zeros(abi.query_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        _check(self.L.simlod_query_region(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data), ml, sel, self._p(scratch),
+                                          ctypes.c_uint64(scratch.numel()), self._p(table), nn, None if samples is None else self._p(samples),
+                                          ctypes.c_uint64(sample_capacity), self._p(counts), self._stream()), "simlod_query_region")
+        c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
+        if int(c["error"]) != 0:
+            raise SimlodError(f"simlod_query_region reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples)")
+        return c
+
+    def _query_setup(self, max_level, select):
+        sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
+        ml = abi.MAX_DEPTH if max_level is None else max(0, min(int(max_level), abi.MAX_DEPTH))
+        st = self.read_stats()
+        nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+        table = torch.empty(max(nn, 1) * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        return sel, ml, table, bound
+
+    def count_region(self, uniforms, region, max_level=None, select="cut"):
+        """How much of the octree lies in `region` (an octree_io.Region) at `max_level`: the SimlodQueryCounts record of a count-only
+        simlod_query_region call (numNodes, numSamples, numCandidates, numFilteredNodes, numCopiedNodes).  No sample is written."""
+        sel, ml, table, bound = self._query_setup(max_level, select)
+        return self._query(uniforms, region, ml, sel, table, None, 0, bound)
+
+    def query_region(self, uniforms, region, max_level=None, select="cut", return_counts=False):
+        """The samples inside `region` as an octree_io.OctreeExport on this device (select abi.EXPORT_REGION): the pruned table and, in chunk-list
+        order, the samples of the selected nodes ("cut": source leaves and the nodes at max_level; "all": every listed node) that pass the
+        region's test.  A count-only call first, then the outputs sized exactly.  Raises SimlodError when the device reports an error."""
+        from .octree_io import OctreeExport
+        sel, ml, table, bound = self._query_setup(max_level, select)
+        c = self._query(uniforms, region, ml, sel, table, None, 0, bound)
+        nn, ns = int(c["numNodes"]), int(c["numSamples"])
+        table = torch.empty(nn * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        samples = torch.empty(max(ns, 1) * abi.point_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        c = self._query(uniforms, region, ml, sel, table, samples, ns, bound)
+        u = np.asarray(uniforms).reshape(-1)[0]
+        ex = OctreeExport(table, samples[: int(c["numSamples"]) * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_REGION)
+        return (ex, c) if return_counts else ex
 
     def import_octree(self, export, check=True, *, buildable=False, uniforms=None):
         """Replace this object's octree by `export` (an octree_io.OctreeExport on the host or on a device): simlod_import_octree validates the

@@ -1,7 +1,10 @@
 """Octree export / import on the config-2 stand-in (bench.py's workload: 36 M-point terrain in 1 M batches, exact mode): export ALL, export
 CUT@20, import, the buildable import (--buildable: simlod_import_octree_buildable, which also rebuilds the occupancy grids), and a plain
 device-to-device copy of the same sample bytes as the ceiling — each timed `--reps` times after a warm-up with device events around the bare C
-call.  Prints one JSON line.  Per-kernel split: run it under `rocprofv3 --kernel-trace --stats -- python ...`."""
+call.  Prints one JSON line.  Per-kernel split: run it under `rocprofv3 --kernel-trace --stats -- python ...`.
+--region: instead, simlod_query_region CUT@20 on the same octree — the whole box (zero planes) beside simlod_export_octree CUT@20, the two
+alternating rep by rep; half the terrain (one oblique plane through the box centre); a city block (a box of 1 % of the area), with its
+count-only call — and the device-to-device copy, all in this one run."""
 import argparse
 import ctypes
 import json
@@ -30,12 +33,109 @@ def timed(fn, reps, warmup=2):
     return float(np.median(ms)), float(ms.min())
 
 
+def timed_alternating(fns, reps, warmup=2):
+    """The median / minimum ms of each of `fns`, run in turns (a, b, a, b, ...) so that a drift of the machine hits all alike."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)] for _ in fns]
+    for r in range(reps):
+        for k, fn in enumerate(fns):
+            a, b = ev[k][r]
+            a.record(); fn(); b.record()
+    torch.cuda.synchronize()
+    out = []
+    for k in range(len(fns)):
+        ms = np.array([a.elapsed_time(b) for a, b in ev[k]])
+        out.append((float(np.median(ms)), float(ms.min())))
+    return out
+
+
+def region_bench(dev, u, box, st, reps):
+    from simlod_amd import fingerprint
+    from simlod_amd.octree_io import Region, classify_nodes
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    need = max(int(L.simlod_query_buffer_min_bytes(nn, bound)), int(L.simlod_export_buffer_min_bytes(nn, bound)))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    table = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    samples = torch.empty(bound * 16, dtype=torch.uint8, device=dev.device)
+    counts = torch.zeros(32, dtype=torch.uint8, device=dev.device)
+    uu, up = dev._u(u)
+    b = np.asarray(box, dtype=np.float64)
+    n = np.array([0.6, 0.8, 0.1])
+    regions = {"whole_box": Region(), "half_terrain": Region.from_planes([[*n, -float(n @ (b / 2))]]),
+               "city_block": Region.from_box((0.45 * b[0], 0.45 * b[1], -1.0), (0.55 * b[0], 0.55 * b[1], b[2] + 1.0))}
+    records = {k: r.record() for k, r in regions.items()}
+
+    def query(kind, count_only=False):
+        rc = L.simlod_query_region(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(records[kind].ctypes.data), 20, abi.EXPORT_CUT, p(scratch),
+                                   ctypes.c_uint64(need), p(table), nn, None if count_only else p(samples), ctypes.c_uint64(bound), p(counts), stream)
+        assert rc == 0
+
+    def export_cut():
+        rc = L.simlod_export_octree(p(dev.nodes), p(dev.stats), 20, abi.EXPORT_CUT, p(scratch), ctypes.c_uint64(need), p(table), nn, p(samples),
+                                    ctypes.c_uint64(bound), p(counts), stream)
+        assert rc == 0
+
+    copy_dst = torch.empty(int(st["numPoints"]) * 16, dtype=torch.uint8, device=dev.device)
+    copy_src = samples[: copy_dst.numel()]
+    # the two calls alternate, so each runs behind the other's sample copy; the plain copy is timed on its own, as in the export bench (behind
+    # a 1.1 GB copy through the caches the single-workgroup walk of whichever call comes next finds its nodes in HBM: 40 us more)
+    t_query, t_cut = timed_alternating([lambda: query("whole_box"), export_cut], reps)
+    t_copy = timed(lambda: copy_dst.copy_(copy_src), reps)
+    copy_gbs = 2 * copy_dst.numel() / (t_copy[0] * 1e6)
+    out = {"points": int(st["numPoints"]), "numNodes": nn, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(),
+           "d2d_copy": {"ms": round(t_copy[0], 4), "bytes": 2 * copy_dst.numel(), "GBs": round(copy_gbs, 1)},
+           "export_cut20": {"ms": round(t_cut[0], 4), "ms_min": round(t_cut[1], 4)}}
+
+    def row(kind, ms):
+        query(kind)
+        torch.cuda.synchronize()
+        c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
+        assert int(c["error"]) == 0
+        t = table[: int(c["numNodes"]) * 40].cpu().numpy().view(abi.export_node_dtype)
+        # the share of the candidates that lie in filtered nodes: the result's table holds the counts AFTER the test, so ask a zero-plane
+        # query for the counts before it and classify its entries on the host
+        outside, inside = classify_nodes(regions[kind].planes, t, u["boxMin"], u["boxMax"])
+        query("whole_box", count_only=True)
+        torch.cuda.synchronize()
+        full = table.cpu().numpy().view(abi.export_node_dtype)
+        key = lambda a: (a["level"].astype(np.uint64) << np.uint64(60)) | (a["X"].astype(np.uint64) << np.uint64(40)) | (a["Y"].astype(np.uint64) << np.uint64(20)) | a["Z"].astype(np.uint64)
+        before = dict(zip(key(full).tolist(), full["numSamples"].tolist()))
+        sel = (t["flags"] & abi.EXPORT_FLAG_SELECTED) != 0
+        cand = np.array([before[k] for k in key(t).tolist()], dtype=np.int64) * (sel & ~outside)
+        assert int(cand.sum()) == int(c["numCandidates"])
+        f = float(cand[~inside].sum()) / max(int(c["numCandidates"]), 1)
+        nbytes = int(c["numCandidates"]) * 16 + int(c["numSamples"]) * 16 + int(c["numNodes"]) * 40
+        gbs = nbytes / (ms[0] * 1e6)
+        return {"ms": round(ms[0], 4), "ms_min": round(ms[1], 4), "nodes_listed": int(c["numNodes"]), "nodes_copied": int(c["numCopiedNodes"]),
+                "nodes_filtered": int(c["numFilteredNodes"]), "numCandidates": int(c["numCandidates"]), "numSamples": int(c["numSamples"]),
+                "f_candidates_in_filtered_nodes": round(f, 4), "algorithmic_bytes": nbytes, "GBs": round(gbs, 1), "frac_of_copy": round(gbs / copy_gbs, 4)}
+
+    out["whole_box"] = row("whole_box", t_query)
+    out["whole_box"]["over_export_cut20"] = round(t_query[0] / t_cut[0], 4)
+    out["whole_box"]["bound"] = "t_query <= 1.10 * t_cut of the same run"
+    out["whole_box"]["bound_held"] = bool(t_query[0] <= 1.10 * t_cut[0])
+    t_half, t_half_count = timed_alternating([lambda: query("half_terrain"), lambda: query("half_terrain", True)], reps)
+    out["half_terrain"] = row("half_terrain", t_half)
+    out["half_terrain"]["count_only_ms"] = round(t_half_count[0], 4)
+    out["half_terrain"]["target"] = ">= 50 % of the copy rate"
+    out["half_terrain"]["target_held"] = bool(out["half_terrain"]["frac_of_copy"] >= 0.5)
+    t_block, t_block_count = timed_alternating([lambda: query("city_block"), lambda: query("city_block", True)], reps)
+    out["city_block"] = row("city_block", t_block)
+    out["city_block"]["count_only_ms"] = round(t_block_count[0], 4)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=36_000_000)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--persistent-gb", type=int, default=16)
     ap.add_argument("--buildable", action="store_true", help="also time simlod_import_octree_buildable (grid rebuild included)")
+    ap.add_argument("--region", action="store_true", help="time simlod_query_region (whole box, half the terrain, a city block) instead")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
     pts, box = synthetic.terrain(n_points, seed=7)
@@ -54,6 +154,8 @@ def main():
     dev.drain(u)
     st = dev.read_stats()
     nn, ns = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    if args.region:
+        return region_bench(dev, u, box, st, args.reps)
     L = dev.L
     need = int(L.simlod_export_buffer_min_bytes(nn, ns))
     scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
