@@ -326,7 +326,7 @@ static void sample_voxel(BuildEnv* e, SimlodNode* node, uint32_t pXf, uint32_t p
 
 /* TEST AID (not part of the reference): where sample_path puts each of `n` points in the grid of node (level, X, Y, Z).  cells[i] =
  * pX + 128 pY + 128^2 pZ with sample_voxel's quantization, or 0xffffffff when the point does not lie in that node (descend's 2^20
- * quantization; below level 20, the 2^28 one); centres[3i..3i+2] = the position sample_voxel gives a voxel of that cell.  A voxel's
+ * quantization, wrapped at the max face as descend wraps it; below level 20, the 2^28 one); centres[3i..3i+2] = the position sample_voxel gives a voxel of that cell.  A voxel's
  * colour names the point that made it: this recovers the voxel's cell at every level, also where fp32 no longer resolves neighbouring
  * cells' positions. */
 void oracle_voxel_cells(const SimlodUniforms* u, const SimlodPoint* pts, uint32_t n, uint32_t level, uint32_t X, uint32_t Y, uint32_t Z,
@@ -339,8 +339,10 @@ void oracle_voxel_cells(const SimlodUniforms* u, const SimlodPoint* pts, uint32_
 		int inside;
 		if (level <= (uint32_t)SIMLOD_MAX_DEPTH) {
 			const uint32_t s = (uint32_t)SIMLOD_MAX_DEPTH - level;
-			inside = level == 0u || ((quantize(fGrid, p->x, u->boxMin.x, size) >> s) == X && (quantize(fGrid, p->y, u->boxMin.y, size) >> s) == Y &&
-			                         (quantize(fGrid, p->z, u->boxMin.z, size) >> s) == Z);
+			/* (descend reads bits 19..0 only, child_index: a coordinate on the max face quantises to 2^20 and goes down the low children) */
+			const uint32_t m = 0xfffffu;
+			inside = level == 0u || (((quantize(fGrid, p->x, u->boxMin.x, size) & m) >> s) == X && ((quantize(fGrid, p->y, u->boxMin.y, size) & m) >> s) == Y &&
+			                         ((quantize(fGrid, p->z, u->boxMin.z, size) & m) >> s) == Z);
 		} else {
 			const uint32_t s = level < 28u ? 28u - level : 0u;
 			inside = (pXf >> s) == X && (pYf >> s) == Y && (pZf >> s) == Z;

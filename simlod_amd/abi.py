@@ -71,11 +71,13 @@ def alloc_round(size: int) -> int:
 def make_uniforms(width, height, transform, box_size, *, transform_update_bound=None,
                   persistent_capacity=0, momentary_capacity=0, frame_counter=0, point_size=1,
                   min_node_size=64.0, hqs=False, show_points=True, color_by_node=False, color_by_lod=False,
-                  show_bounding_box=False, fovy_deg=60.0):
+                  show_bounding_box=False, fovy_deg=60.0, box_min=(0.0, 0.0, 0.0)):
     """Fill a Uniforms record the way getUniforms() does (main_progressive_octree.cpp:283-331).
 
     `transform` is the ROW-MAJOR 4x4 world-view-projection matrix (rows[i] = row i, i.e. what the host
-    obtains after glm::transpose).  boxMin is always 0 and boxMax the bounding-box size (:312-313).
+    obtains after glm::transpose).  The reference host always sends boxMin = 0 and boxMax = the bounding-box size (:312-313);
+    `box_min` places the box elsewhere: boxMin = float32(box_min), boxMax = float32(boxMin + float32(box_size)), the sum formed in
+    fp32 as a host that keeps fp32 coordinates would form it (so boxMax - boxMin need not give box_size back).
     """
     u = np.zeros((), dtype=uniforms_dtype)
     t = np.asarray(transform, dtype=np.float32).reshape(4, 4)
@@ -93,8 +95,9 @@ def make_uniforms(width, height, transform, box_size, *, transform_update_bound=
     u["persistentBufferCapacity"] = persistent_capacity
     u["momentaryBufferCapacity"] = momentary_capacity
     u["frameCounter"] = frame_counter
-    u["boxMin"] = (0.0, 0.0, 0.0)
-    u["boxMax"] = tuple(float(v) for v in box_size)
+    mn = np.asarray(box_min, dtype=np.float32).reshape(3)
+    u["boxMin"] = mn
+    u["boxMax"] = mn + np.asarray(box_size, dtype=np.float32).reshape(3)
     u["showBoundingBox"] = show_bounding_box
     u["showPoints"] = show_points
     u["colorByNode"], u["colorByLOD"] = color_by_node, color_by_lod

@@ -26,6 +26,10 @@ out.update({f"modes__{k}": v for k, v in pin.record_modes("ref")[1].items()})
 out.update({f"hazards__{k}": v for k, v in pin.record_hazards("ref")[1].items()})
 for variant in pin.EDGE_VARIANTS:
     out.update({f"edge_{variant}__{k}": v for k, v in pin.record_edge_case("ref", variant)[1].items()})
+for name, offset in pin.OFFSET_BOXES:
+    out.update({f"offset_{offset}_{name}__{k}": v for k, v in pin.record_offset_box("ref", name, offset)[1].items()})
+for name, live in pin.FROZEN_CASES:
+    out.update({f"frozen_{name}_{live}__{k}": v for k, v in pin.record_frozen_camera("ref", name, live).items()})
 with tempfile.TemporaryDirectory() as tmp:
     out.update({f"las_live__{k}": v for k, v in test_las.record_live("ref", tmp).items()})
 np.savez_compressed(pin.GOLDEN_PIN, **out)

@@ -12,23 +12,24 @@ NORMAL = (0.6, 0.8, 0.1)
 REGION_NAMES = ["oblique", "slab", "box", "none", "miss"]
 
 
-def region(kind, box):
-    """The test regions, placed relative to the box (boxMin = 0): an oblique half-space through the centre, a slab around it, an x/y box of
-    30-70 % x 20-90 % of the extents, no plane at all, a half-space that misses the box."""
+def region(kind, box, box_min=(0, 0, 0)):
+    """The test regions, placed relative to the box [box_min, box_min + box]: an oblique half-space through the centre, a slab around it,
+    an x/y box of 30-70 % x 20-90 % of the extents, no plane at all, a half-space that misses the box."""
     box = np.asarray(box, dtype=np.float64)
+    mn = np.asarray(box_min, dtype=np.float64)
     n = np.asarray(NORMAL)
-    c = float(n @ (box / 2))
+    c = float(n @ (mn + box / 2))
     if kind == "oblique":
         return Region.from_planes([[*n, -c]])
     if kind == "slab":
         h = 0.2 * float(box.max())
         return Region.from_planes([[*n, -c + h], [*(-n), c + h]])
     if kind == "box":
-        return Region.from_box((0.3 * box[0], 0.2 * box[1], -1.0), (0.7 * box[0], 0.9 * box[1], box[2] + 1.0))
+        return Region.from_box((mn[0] + 0.3 * box[0], mn[1] + 0.2 * box[1], mn[2] - 1.0), (mn[0] + 0.7 * box[0], mn[1] + 0.9 * box[1], mn[2] + box[2] + 1.0))
     if kind == "none":
         return Region()
     if kind == "miss":
-        return Region.from_planes([[1.0, 0.0, 0.0, -3.0 * float(box.max())]])
+        return Region.from_planes([[1.0, 0.0, 0.0, -(float(mn[0]) + 3.0 * float(box.max()))]])
     raise KeyError(kind)
 
 
@@ -52,14 +53,17 @@ def assert_same_multiset(got, want, what=""):
     assert np.array_equal(sorted_samples(got), sorted_samples(want)), f"{what}: the samples differ as multisets"
 
 
-def host_octree(name=None, pts=None, box=None, batch=None):
-    """An octree built by the oracle's port from a case of tests/cases.py (or from `pts`) -> (full export as OctreeExport, points, box, HostOctree)."""
+def host_octree(name=None, pts=None, box=None, batch=None, box_min=(0, 0, 0)):
+    """An octree built by the oracle's port from a case of tests/cases.py (or from `pts`) -> (full export as OctreeExport, points, box, HostOctree).
+    With `box_min` the case's points are moved by it (cases.shifted) and the box starts there."""
     if name is not None:
         pts, box, batch, T = cases.case(name)
+        if tuple(box_min) != (0, 0, 0):
+            pts, box_min, box, batch = cases.shifted(name, box_min)
         batches = cases.batches_of(name, pts, batch)
     else:
         batches = [pts[i:i + batch] for i in range(0, len(pts), batch)]
-    u = cases.uniforms_for(box, np.eye(4, dtype=np.float32))
+    u = cases.uniforms_for(box, np.eye(4, dtype=np.float32), box_min=box_min)
     ho = oracle.HostOctree("port", persistent_bytes=1 << 30, ring_slots=8)
     ho.reset(u)
     for b in batches:
@@ -67,4 +71,4 @@ def host_octree(name=None, pts=None, box=None, batch=None):
             ho.add_points(u, b, len(b))
     assert int(ho.stats["dbg"][0]) == 0
     t, s = export_host(ho.nodes, int(ho.stats["numNodes"][0]))
-    return OctreeExport(t, s, (0, 0, 0), box), pts, box, ho
+    return OctreeExport(t, s, u["boxMin"], u["boxMax"]), pts, box, ho

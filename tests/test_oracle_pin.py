@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle
+import cases
 from cases import CASES, batches_of, case, uniforms_for
 from util import STATS_BUILD_FIELDS, STATS_RENDER_FIELDS, assert_dumps_equal, assert_stats_equal
 
@@ -31,20 +32,46 @@ def golden(scenario):
     return {k.split("__", 1)[1]: g[k] for k in g.files if k.split("__", 1)[0] == scenario}
 
 
-def _run(kind, name):
+OFFSET_BOXES = [(name, off) for name in CASES for off in ("dyadic", "inexact")] + [("terrain_4x100k", "georef")]
+FROZEN_CASES = [(name, live) for name in ("uniform_3x40k", "terrain_4x100k") for live in cases.LIVE_CAMERAS if not (live == "grazing" and name != "terrain_4x100k")]
+
+
+def _run(kind, name, offset=None):
+    """Build a case on a back-end; with `offset` (a name of cases.offset_of) the points, the box and the camera are moved by it."""
     pts, box, batch, T = case(name)
+    if offset is not None:
+        off = cases.offset_of(offset, box)
+        pts, box_min, box, batch = cases.shifted(name, off)
+        u = uniforms_for(box, cases.shifted_cam(box, off), box_min=box_min)
+        return _build(kind, name, pts, batch, u), u
     u = uniforms_for(box, T)
+    return _build(kind, name, pts, batch, u), box, T
+
+
+def _build(kind, name, pts, batch, u):
     o = oracle.HostOctree(kind, persistent_bytes=1 << 30, ring_slots=8)
     o.reset(u)
     for b in batches_of(name, pts, batch):
         o.upload(b)
     while int(o.stats["batchletIndex"][0]) < int(o.num_uploaded[0]):
         o.construct(u)
-    return o, box, T
+    return o
 
 
-def record_build(kind, name):
-    o, box, T = _run(kind, name)
+def _with(u, **fields):
+    v = np.array(u, copy=True)
+    for k, val in fields.items():
+        v[k] = val
+    return v
+
+
+def record_build(kind, name, offset=None):
+    if offset is None:
+        o, box, T = _run(kind, name)
+        frame_uniforms = lambda hqs: uniforms_for(box, T, hqs=hqs)
+    else:
+        o, u0 = _run(kind, name, offset)
+        frame_uniforms = lambda hqs: _with(u0, useHighQualityShading=int(hqs))
     n = int(o.stats["numNodes"][0])
     rec = {"stats": o.stats.copy(), "dump": o.dump()}                # the dump: every stored point, voxel position and grid bit
     for f in NODE_VALUE_FIELDS:
@@ -54,15 +81,42 @@ def record_build(kind, name):
         rec[f"offset_{f}"] = np.where(o.nodes[f][:n] != 0, o.nodes[f][:n] - np.uint64(o.persistent.ctypes.data), 0)
     rec["children"] = np.where(o.nodes["children"][:n] != 0, o.nodes["children"][:n] - np.uint64(o.nodes.ctypes.data), 0)
     for hqs in (False, True):
-        fb, _ = o.render(uniforms_for(box, T, hqs=hqs))
+        fb, _ = o.render(frame_uniforms(hqs))
         rec[f"fb_{int(hqs)}"], rec[f"render_stats_{int(hqs)}"], rec[f"visible_{int(hqs)}"] = _digest(fb), o.stats.copy(), o.visible["name"].copy()
+        if offset is not None and not hqs:
+            from simlod_amd import abi
+            rec["nonbg"] = np.array([int((fb != abi.CLEAR_PIXEL).sum())])
     return o, rec
+
+
+def record_offset_box(kind, name, offset):
+    """record_build with the case's points, box and camera moved by a named offset (cases.offset_of): boxMin != 0."""
+    return record_build(kind, name, offset)
 
 
 @pytest.mark.parametrize("name", CASES)
 def test_restatement_equals_reference_build(built_libs, name):
-    port, got = record_build("port", name)
-    want = golden(f"build_{name}")
+    _check_build(name, *record_build("port", name), golden(f"build_{name}"))
+
+
+@pytest.mark.parametrize("name,offset", OFFSET_BOXES)
+def test_restatement_equals_reference_build_in_a_box_off_the_origin(built_libs, name, offset):
+    """The build and the two frames with boxMin != 0 (the reference's kernels honour it; its host never sends it).  Guards: the fixture's
+    frame draws something, and the same points in the box [0, boxMax] give another octree — so a `min` that is dropped somewhere shows."""
+    port, got = record_offset_box("port", name, offset)
+    want = golden(f"offset_{offset}_{name}")
+    _check_build(f"{name}/{offset}", port, got, want)
+    assert int(want["nonbg"][0])  > 200                   # (the hotspot is one level-3 cell: some 350 pixels)
+    assert np.array_equal(want["nonbg"], got["nonbg"])
+    _, u = _run("port", name, offset)
+    if offset == "inexact":
+        assert cases.size_differs(u), "the inexact offset must make (boxMin + size) - boxMin differ from size"
+    pts = cases.shifted(name, cases.offset_of(offset, case(name)[1]))[0]
+    ignoring = _build("port", name, pts, case(name)[2], cases.origin_box_uniforms(u)).dump()
+    assert len(ignoring) != len(got["dump"]) or any(not np.array_equal(ignoring[f], got["dump"][f]) for f in ("key", "numPoints", "gridHash", "voxelPosSum"))
+
+
+def _check_build(name, port, got, want):
     assert port.last_error() == 0
     assert_stats_equal(got["stats"][0], want["stats"][0], STATS_BUILD_FIELDS, name)
     for f in NODE_VALUE_FIELDS:
@@ -76,6 +130,59 @@ def test_restatement_equals_reference_build(built_libs, name):
         assert_stats_equal(got[f"render_stats_{hqs}"][0], want[f"render_stats_{hqs}"][0], STATS_RENDER_FIELDS, name)
         va, vb = want[f"visible_{hqs}"], got[f"visible_{hqs}"]
         assert len(va) == len(vb) and np.array_equal(va, vb), "visible-node list order"
+
+
+_FROZEN_BUILT = {}
+
+
+def record_frozen_camera(kind, name, live):
+    """Frames of a case whose nodes are chosen by one camera (transform_updateBound: frustum test, `large`, render.cu:792-861, 1025-1053) and
+    drawn by another (transform), plain / HQS x node boxes off / on.  minNodeSize is 64 on the terrain, where the two cameras then cut its 33
+    nodes at different depths, and 16 on uniform_3x40k, whose 9 nodes leave nothing to cut: there the cameras differ in the frustum test
+    only.  Also, for the tests' guards: the non-background pixels of the frame, in how many pixels it differs from the (live, live) and the
+    (frozen, frozen) frame, and numVisibleNodes of (live, live)."""
+    if (kind, name) not in _FROZEN_BUILT:
+        _FROZEN_BUILT.clear()
+        _FROZEN_BUILT[(kind, name)] = _run(kind, name)
+    from simlod_amd import abi
+    o, box, _ = _FROZEN_BUILT[(kind, name)]
+    Tl, Tf = cases.frozen_pair(live, box, cases.W, cases.H)
+    rec = {}
+    for hqs in (0, 1):
+        for boxes in (0, 1):
+            mk = lambda t, tu: abi.make_uniforms(cases.W, cases.H, t, box, transform_update_bound=tu, persistent_capacity=1 << 30, momentary_capacity=300_000_000,
+                                                 hqs=bool(hqs), min_node_size=64.0 if "terrain" in name else 16.0, show_bounding_box=bool(boxes))
+            fb = o.render(mk(Tl, Tf))[0]
+            st, vis = o.stats.copy(), o.visible["name"].copy()
+            fb_ll = o.render(mk(Tl, Tl))[0]
+            n_ll = int(o.stats["numVisibleNodes"][0])
+            fb_ff = o.render(mk(Tf, Tf))[0]
+            k = f"{hqs}{boxes}"
+            rec[f"fb_{k}"], rec[f"stats_{k}"], rec[f"visible_{k}"] = _digest(fb), st, vis
+            rec[f"guard_{k}"] = np.array([int((fb != abi.CLEAR_PIXEL).sum()), int((fb != fb_ll).sum()), int((fb != fb_ff).sum()), n_ll])
+    return rec
+
+
+@pytest.mark.parametrize("name,live", FROZEN_CASES)
+def test_frozen_visibility_camera_matches_reference(built_libs, name, live):
+    """transform_updateBound != transform: the restatement against the reference's own render.cu.  Guards, from the fixture alone: the frame
+    differs from the frame of (frozen, frozen) and — on the terrain — of (live, live); `away` draws nothing but still lists the frozen
+    camera's nodes, where (live, live) lists none; on uniform_3x40k (every node drawn by either camera) the cameras with another frustum
+    list another number of nodes than (live, live) does."""
+    got, want = record_frozen_camera("port", name, live), golden(f"frozen_{name}_{live}")
+    for k in ("00", "01", "10", "11"):
+        assert np.array_equal(want[f"fb_{k}"], got[f"fb_{k}"]), f"{name}/{live}: pre-EDL framebuffer differs (hqs, boxes = {k})"
+        assert_stats_equal(got[f"stats_{k}"][0], want[f"stats_{k}"][0], STATS_RENDER_FIELDS, f"{name}/{live}/{k}")
+        assert np.array_equal(want[f"visible_{k}"], got[f"visible_{k}"]), "visible-node list order"
+        assert np.array_equal(want[f"guard_{k}"], got[f"guard_{k}"])
+        nonbg, d_live, d_frozen, n_live = (int(v) for v in want[f"guard_{k}"])
+        assert d_frozen > 0
+        if live == "away":                                              # (its debug lines lie behind the live camera; (live, live) sees its own frustum)
+            assert (nonbg == 0 or k[1] == "1") and n_live == 0 and int(want[f"stats_{k}"]["numVisibleNodes"][0]) > 0
+        elif "terrain" in name or k[1] == "1":                          # (with the lines on, the frozen frustum itself is on screen)
+            assert d_live > 0 and nonbg > 500, (nonbg, d_live)
+        else:
+            assert nonbg > 500 and (live not in ("inside",) or n_live != int(want[f"stats_{k}"]["numVisibleNodes"][0]))
 
 
 def record_modes(kind):

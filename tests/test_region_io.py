@@ -79,9 +79,19 @@ def test_region_from_frustum():
     assert np.array_equal(got[far], want[far]) and 0 < want[far].sum() < far.sum()
 
 
-@pytest.fixture(scope="module", params=cases.CASES)
+# (case, offset of its box: None = at the origin, as the reference host places it)
+BUILT = [(n, None) for n in cases.CASES] + [("uniform_3x40k", "inexact"), ("terrain_4x100k", "georef"), ("hotspot_150k", "dyadic")]
+
+
+@pytest.fixture(scope="module", params=BUILT, ids=lambda p: p[0] if p[1] is None else f"{p[0]}@{p[1]}")
 def built(request):
-    return (request.param,) + rr.host_octree(request.param)
+    """-> (name, full export, points, (box size, box min), HostOctree)"""
+    name, offset = request.param
+    box_min = (0, 0, 0) if offset is None else cases.offset_of(offset, cases.case(name)[1])
+    ex, pts, box, ho = rr.host_octree(name, box_min=box_min)
+    if offset is not None:
+        assert ex.box_min == tuple(float(np.float32(v)) for v in box_min) and (pts["x"] >= np.float32(box_min[0])).all()
+    return name, ex, pts, (box, box_min), ho
 
 
 def test_crop_without_planes_is_the_export(built):
@@ -100,10 +110,12 @@ def test_crop_without_planes_is_the_export(built):
 @pytest.mark.parametrize("kind", ["oblique", "slab", "box"])
 def test_crop_is_the_brute_force_filter(built, kind):
     name, ex, pts, box, ho = built
-    r = rr.region(kind, box)
+    r = rr.region(kind, *box)
     c, cnt = ex.crop(r, 20, "cut", return_counts=True)
     c.validate()
-    rr.assert_same_multiset(c.samples, pts[rr.brute_mask(r, pts)], f"{name} {kind}")
+    inside = rr.brute_mask(r, pts)
+    assert 0 < inside.sum() and (inside.sum() < len(pts) or "hotspot" in name), "the region must cut the cloud (the hotspot's one cell lies inside some)"
+    rr.assert_same_multiset(c.samples, pts[inside], f"{name} {kind}")
     assert int(cnt["numSamples"]) == c.num_samples <= int(cnt["numCandidates"]) and int(cnt["numNodes"]) == c.num_nodes
     # per node: the source node's samples under the mask, in order
     src = {(int(e["level"]), int(e["X"]), int(e["Y"]), int(e["Z"])): e for e in ex.nodes}
@@ -124,7 +136,7 @@ def test_crop_is_the_brute_force_filter(built, kind):
 
 def test_crop_that_misses_the_box(built):
     name, ex, pts, box, ho = built
-    c, cnt = ex.crop(rr.region("miss", box), 20, "cut", return_counts=True)
+    c, cnt = ex.crop(rr.region("miss", *box), 20, "cut", return_counts=True)
     c.validate()
     assert c.num_nodes == 1 and c.num_samples == 0 and int(c.nodes["childMask"][0]) == 0 and int(c.nodes["firstChild"][0]) == abi.EXPORT_NONE
     assert [int(cnt[f]) for f in cnt.dtype.names] == [1, 0, 0, 0, 0, 0]
@@ -197,11 +209,11 @@ PINNED_MAX_FACE_POINTS_IN_UPPER_HALF = 0      # (they are stored under X = 0 nod
 
 def test_crop_file_roundtrip_and_refusals(built, tmp_path):
     name, ex, pts, box, ho = built
-    c = ex.crop(rr.region("oblique", box), 20, "cut")
+    c = ex.crop(rr.region("oblique", *box), 20, "cut")
     p = tmp_path / "crop.simlodx"
     c.save(p)
     ld = OctreeExport.load(p)
-    assert ld.select == abi.EXPORT_REGION and ld.max_level == 20
+    assert ld.select == abi.EXPORT_REGION and ld.max_level == 20 and ld.box_min == ex.box_min and ld.box_max == ex.box_max
     assert ld.nodes.tobytes() == c.nodes.tobytes() and ld.samples.tobytes() == c.samples.tobytes()
     with pytest.raises(ValueError, match="not a full export"):
         c.validate(buildable=True)
@@ -212,9 +224,9 @@ def test_crop_file_roundtrip_and_refusals(built, tmp_path):
     n = int(ho.stats["numNodes"][0])
     t, s = export_host(ho.nodes, n, 20, abi.EXPORT_CUT)
     with pytest.raises(ValueError, match="full export"):
-        OctreeExport(t, s, (0, 0, 0), box, 20, "cut").crop(Region())
+        OctreeExport(t, s, ex.box_min, ex.box_max, 20, "cut").crop(Region())
     t, s = export_host(ho.nodes, n, 1, abi.EXPORT_ALL)
     with pytest.raises(ValueError, match="full export"):
-        OctreeExport(t, s, (0, 0, 0), box, 1, "all").crop(Region())
+        OctreeExport(t, s, ex.box_min, ex.box_max, 1, "all").crop(Region())
     with pytest.raises(ValueError):
         ex.crop(Region(), select="visible")

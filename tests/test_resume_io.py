@@ -11,9 +11,9 @@ from simlod_amd import abi, synthetic
 from simlod_amd.octree_io import OctreeExport
 
 
-def _oracle(pts, box, batches):
+def _oracle(pts, box, batches, box_min=(0.0, 0.0, 0.0)):
     T = cases._cam(box)
-    u = cases.uniforms_for(box, T)
+    u = cases.uniforms_for(box, T, box_min=box_min)
     ref = oracle.HostOctree("port", persistent_bytes=1 << 30, ring_slots=abi.BATCH_STREAM_SIZE)
     ref.reset(u)
     for b in batches:
@@ -49,12 +49,21 @@ def _input(name):
     return pts, box, cases.batches_of(name, pts, batch)
 
 
-NAMES = cases.CASES + ["terrain_2m", "hotspot_600k", "max_face", "ragged_tiny_root_leaf"]
+# "<input>@<offset>": the input moved into a box off the origin (cases.offset_of)
+NAMES = cases.CASES + ["terrain_2m", "hotspot_600k", "max_face", "ragged_tiny_root_leaf", "terrain_4x100k@georef", "uniform_3x40k@inexact", "max_face@dyadic",
+                       "ragged_tiny_root_leaf@inexact"]
 
 
 def _built(name):
+    name, _, offset = name.partition("@")
     pts, box, batches = _input(name)
-    ref, u = _oracle(pts, box, batches)
+    box_min = (0.0, 0.0, 0.0)
+    if offset:
+        off = cases.offset_of(offset, box)
+        cuts = np.cumsum([0] + [len(b) for b in batches])
+        pts = np.concatenate([cases.shift_points(pts[: cuts[-1]], off), pts[cuts[-1]:]])
+        batches, box_min = [pts[a:b] for a, b in zip(cuts[:-1], cuts[1:])], tuple(float(np.float32(v)) for v in off)
+    ref, u = _oracle(pts, box, batches, box_min)
     nn = int(ref.stats["numNodes"][0])
     t, s = export_host(ref.nodes, nn)
     return ref, u, nn, t, s, pts
@@ -77,8 +86,13 @@ def test_rebuilt_grids_equal_the_oracles(name):
             bad = np.nonzero(got != want)[0]
             raise AssertionError(f"{name}: node level={int(nd['level'])} XYZ=({int(nd['X'])},{int(nd['Y'])},{int(nd['Z'])}): {len(bad)} grid words differ, "
                                  f"first word {int(bad[0])}: {int(got[bad[0]]):#x} != {int(want[bad[0]]):#x}")
-    if name == "max_face":
+    if name.startswith("max_face"):
         assert (pts["x"] == pts["x"].max()).sum() >= 500          # (the input really has points on the max face)
+        assert pts["x"].max() == np.asarray(u["boxMax"], np.float32).reshape(3)[0]
+    if "@" in name:
+        # the case can tell "honours boxMin" from "ignores it": rebuilt in the box [0, boxMax] the grids are others
+        other = rebuild_grids(t, s, cases.origin_box_uniforms(u))
+        assert any(not np.array_equal(other.get(k), g) for k, g in grids.items())
     if t[0]["childMask"] == 0:
         # a root that is still a leaf: its voxels are rebuilt with the oracle root's cells and bit-equal positions
         cells, vox = root_leaf_voxels(t, s, u)
@@ -153,10 +167,22 @@ def test_validate_buildable_rejects(what):
 
 
 def test_buildable_survives_save_load(tmp_path):
-    ex = _full_export()
+    _save_load(_full_export(), tmp_path)
+
+
+def test_buildable_survives_save_load_in_a_box_off_the_origin(tmp_path):
+    ref, u, nn, t, s, pts = _built("uniform_3x40k@inexact")
+    u0 = np.asarray(u).reshape(-1)[0]
+    ex = OctreeExport(t, s, u0["boxMin"], u0["boxMax"], 20, "all")
+    assert ex.box_min == tuple(float(np.float32(v)) for v in cases.INEXACT_UNIT)
+    _save_load(ex, tmp_path)
+
+
+def _save_load(ex, tmp_path):
     ex.save(tmp_path / "full.simlodx")
     ld = OctreeExport.load(tmp_path / "full.simlodx")
     assert ld.is_buildable and ld.nodes.tobytes() == ex.nodes.tobytes() and ld.samples.tobytes() == ex.samples.tobytes()
+    assert ld.box_min == ex.box_min and ld.box_max == ex.box_max
     cut = _with(ex, select="cut")
     cut.save(tmp_path / "cut.simlodx")
     assert not OctreeExport.load(tmp_path / "cut.simlodx").is_buildable

@@ -233,3 +233,40 @@ def points_multiset_hash(pts):
         b = (w[:, 2] << np.uint64(32)) | w[:, 3]
         h = mix(a ^ mix(b + np.uint64(0x9e3779b97f4a7c15)))
         return np.uint64(h.sum()), np.bitwise_xor.reduce(mix(h + np.uint64(1)))
+
+
+def oracle_frame(nodes, nn, u):
+    """The oracle's rasteriser on a HOST-addressed image -> (pre-EDL framebuffer uint64[H*W], EDL'd RGBA8 uint32[H*W], Stats record, visible-node records)."""
+    import ctypes
+    Wd, Hd = int(u["width"]), int(u["height"])
+    fb = np.zeros(Wd * Hd, dtype=np.uint64)
+    col = np.zeros(Wd * Hd, dtype=np.uint32)
+    vis = np.zeros(abi.MAX_VISIBLE_NODES, dtype=abi.node_dtype)
+    stats = np.zeros(1, dtype=abi.stats_dtype)
+    stats["numNodes"] = nn
+    uu = np.ascontiguousarray(u).reshape(1)
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)
+    oracle.port_lib().oracle_render(None, p(uu), p(nodes), p(stats), p(fb), p(col), p(vis), 1)
+    return fb, col, stats[0], vis[: int(stats["numVisibleNodes"][0])].copy()
+
+
+def node_keys(rec):
+    """level << 60 | X << 40 | Y << 20 | Z of Node (or export table) records."""
+    return ((rec["level"].astype(np.uint64) << np.uint64(60)) | (rec["X"].astype(np.uint64) << np.uint64(40)) | (rec["Y"].astype(np.uint64) << np.uint64(20)) |
+            rec["Z"].astype(np.uint64))
+
+
+def assert_frame_equals_oracle(dev, nodes, nn, u, what, floor):
+    """The frame the device just drew from `u` against the oracle's on the same image: render Stats equal, pre-EDL framebuffer bit-identical,
+    more than `floor` pixels drawn, RGBA8 within 1 per channel (log2 / exp from different libms).  -> (device fb, colour, oracle Stats, visible records)."""
+    Wd, Hd = int(u["width"]), int(u["height"])
+    fb_dev, col_dev, ds = dev.framebuffer(Wd, Hd), dev.color(Wd, Hd), dev.read_stats()
+    assert int(ds["dbg"]) == 0, f"{what}: device error bits {int(ds['dbg']):#x}"
+    fb, col, st, vis = oracle_frame(nodes, nn, u)
+    assert_stats_equal(ds, st, STATS_RENDER_FIELDS, what)
+    diff = np.nonzero(fb_dev != fb)[0]
+    assert len(diff) == 0, f"{what}: {len(diff)} pixels differ, first {diff[:5]}: dev {fb_dev[diff[:5]]} oracle {fb[diff[:5]]}"
+    if floor is not None:
+        assert int((fb != abi.CLEAR_PIXEL).sum()) > floor, f"{what}: the case must draw something"
+    assert int(np.abs(col_dev.view(np.uint8).astype(np.int16) - col.view(np.uint8).astype(np.int16)).max()) <= 1, f"{what}: RGBA8 differs by more than 1"
+    return fb_dev, col_dev, st, vis
