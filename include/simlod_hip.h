@@ -411,6 +411,94 @@ int simlod_query_region(const SimlodNode* nodes, const SimlodStats* stats, const
                         uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
                         SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, void* stream);
 
+/* ---- ray queries: the first sample in a cone along each ray of a batch ----------------------------------------------------------------------
+ * simlod_query_rays answers "what does this ray hit" for up to 2^20 rays at once: per ray the sample with the smallest parameter t that lies
+ * within radius + spread * t of the ray, among the samples of the nodes simlod_export_octree(maxLevel, select) selects.  The source is only read.
+ *
+ * The box is the builder's, as for region queries (min = uniforms.boxMin, size = the largest fp32 extent).  All geometry is fp64 computed from the
+ * fp32 inputs without fused multiply-add, every sum in the order written here; divisions are IEEE divisions.  s, e, lo_a, hi_a of a node are
+ * those of region-query rule 1 (the cube inflated by one level-20 cell).
+ *  0. The table.  The nodes considered are exactly the entries of simlod_export_octree(maxLevel, select) on the same octree, select ALL, CUT or
+ *     VISIBLE (VISIBLE is refused as the export refuses it when no frame ran).  SimlodRayHit.node is an index into THAT table and `ordinal` an
+ *     index into that node's sample range: export.samples[export.nodes[node].firstSample + ordinal] is the hit's sample.  With table != NULL the
+ *     call also writes that table, byte for byte the export's (it is never pruned per ray); tableCapacity bounds the walk either way.
+ *  1. Valid rays.  A ray is valid iff every float is finite, dir != 0, 0 <= tMin <= tMax, radius >= 0, spread >= 0 and reserved == 0.  An
+ *     invalid ray misses, is counted in numInvalid and forms no pair (checked on the device: rays may come from a kernel).
+ *  2. The sample test.  With p = sample - origin (per component), dd = (dx*dx + dy*dy) + dz*dz, t = ((dx*px + dy*py) + dz*pz) / dd,
+ *     q_a = p_a - t*d_a, s2 = (qx*qx + qy*qy) + qz*qz and rr = radius + spread*t the sample passes iff t >= tMin && t <= tMax && s2 <= rr*rr
+ *     (a NaN fails).
+ *  3. Pairs.  A valid ray and a selected table entry with numSamples > 0 form a PAIR iff the entry and all its listed ancestors pass the slab
+ *     test: R = radius + spread*tMax; per axis a, L = lo_a - R and H = hi_a + R; if d_a == 0 the axis fails iff o_a < L || o_a > H and otherwise
+ *     contributes nothing; else t1 = (L - o_a)/d_a, t2 = (H - o_a)/d_a, n_a = fmin(t1, t2), f_a = fmax(t1, t2); the node passes iff no axis fails
+ *     and max(tMin, n_x, n_y, n_z) <= min(tMax, f_x, f_y, f_z) over the contributing axes.  numPairs is the number of pairs, numCandidates the
+ *     sum of numSamples over the pairs; both are defined by this rule alone, whatever work the kernels skip.
+ *  4. The hit of a valid ray is, among the samples of its pairs that pass rule 2, the one with the smallest t; equal t: the smallest node,
+ *     then the smallest ordinal.  No passing sample: a miss (t = +infinity, node = ordinal = 0xffffffff, a zero sample).  The result is a pure
+ *     function of the octree image and the rays.  For finite samples in the half-open box the culling of rule 3 never changes it: a passing
+ *     sample lies within R of the ray's point at its t, which therefore lies in the node's cube widened by R, and in every ancestor's (what e
+ *     leaves over the builder's quantisation slack, about size * 2^-21, is many orders above the fp64 rounding of the slab test, about
+ *     size * 2^-50).  OUTSIDE THE CONTRACT, as in region-query rule 4: samples outside that box or on its max faces; such a sample is a
+ *     candidate iff the node it is stored in forms a pair.
+ *  5. hits == NULL: count only — the counts (and the table, if asked for) are complete, nothing else is written, and
+ *     simlod_rays_buffer_min_bytes(cap, bound, numRays, 0, 0) of scratch suffices (numHits then comes from a ray-major pass that stops at a
+ *     ray's first passing sample: it reads a chunk once per ray that reaches it, so a host that wants the hits anyway asks for them).
+ *     With hits, scratch sized from the counts of a count-only call always suffices; a buffer that holds the walk but not the pairs sets
+ *     SIMLOD_EXPORT_ERR_CAPACITY and then NO hit record is written; a walk error (ERR_NODE_COUNT, ERR_SHORT_LIST, the table capacity) likewise. */
+typedef struct SimlodRay {             /* DEVICE memory */
+	float    origin[3]; float tMin;    /* world coordinates (the uniforms' box)                                 */
+	float    dir[3];    float tMax;    /* any non-zero direction; t is in units of |dir|                        */
+	float    radius;    float spread;  /* cone radius at parameter t: radius + spread * t                       */
+	uint32_t reserved[2];              /* 0                                                                     */
+} SimlodRay;
+typedef struct SimlodRayHit {          /* DEVICE memory, one per ray, in ray order */
+	double      t;                     /* parameter of the hit; miss: +infinity                                 */
+	uint32_t    node;                  /* table index of the node that holds it; miss: 0xffffffff               */
+	uint32_t    ordinal;               /* index among that node's samples in chunk-list order; miss: 0xffffffff */
+	SimlodPoint sample;                /* the 16 bytes of the sample; miss: zeros                               */
+} SimlodRayHit;
+typedef struct SimlodRayCounts {       /* written by the device */
+	uint32_t numNodes;                 /* table entries                                                         */
+	uint32_t error;                    /* SIMLOD_EXPORT_ERR_* bits                                              */
+	uint32_t numHits;                  /* rays with a hit                                                        */
+	uint32_t numInvalid;               /* rays that fail rule 1                                                 */
+	uint64_t numPairs;                 /* rule 3                                                                */
+	uint64_t numCandidates;            /* rule 3                                                                */
+} SimlodRayCounts;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodRay) == 48, "Ray");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRay, tMin) == 12, "Ray.tMin");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRay, dir) == 16, "Ray.dir");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRay, tMax) == 28, "Ray.tMax");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRay, radius) == 32, "Ray.radius");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRay, spread) == 36, "Ray.spread");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRay, reserved) == 40, "Ray.reserved");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodRayHit) == 32, "RayHit");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRayHit, node) == 8, "RayHit.node");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRayHit, ordinal) == 12, "RayHit.ordinal");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRayHit, sample) == 16, "RayHit.sample");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodRayCounts) == 32, "RayCounts");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRayCounts, numHits) == 8, "RayCounts.numHits");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRayCounts, numInvalid) == 12, "RayCounts.numInvalid");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRayCounts, numPairs) == 16, "RayCounts.numPairs");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodRayCounts, numCandidates) == 24, "RayCounts.numCandidates");
+#define SIMLOD_RAYS_MAX (1u << 20)
+
+/* Bytes of the `scratch` buffer a ray query needs: a table of up to nodeCapacity entries whose selected nodes hold up to sampleBound samples
+ * (Stats.numPoints + Stats.numVoxels always suffices), numRays rays, and — for a call with hits — the numPairs and numCandidates a count-only
+ * call reported (0, 0: enough for a count-only call).  The sum of a part that depends on nodeCapacity and numRays only, 32 bytes per chunk
+ * item for sampleBound / 1000 + nodeCapacity + 1 items, 32 bytes per pair (its record and one partial result) and 16 bytes per further thousand
+ * candidates.  What a call with hits really needs is the same sum with the chunks the table's selected nodes have (ceil(numSamples / 1000)
+ * each) in the place of that item bound: one byte less sets SIMLOD_EXPORT_ERR_CAPACITY. */
+uint64_t simlod_rays_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates);
+
+/* The ray query (rules above).  Asynchronous on `stream`; everything in between lives in `scratch`.  hipErrorInvalidValue with nothing
+ * enqueued: a null pointer other than `table` / `hits`, numRays == 0 or > SIMLOD_RAYS_MAX, `select` other than ALL / CUT / VISIBLE (VISIBLE
+ * without a frame), scratchBytes below simlod_rays_buffer_min_bytes(tableCapacity, 0, numRays, 0, 0).  A scratch buffer too small for the
+ * chunk items or the pairs sets SIMLOD_EXPORT_ERR_CAPACITY on the device.  While the builder's chunk table for `nodes` is valid the first
+ * chunks of each list come from it, the rest by `next` (as simlod_export_octree). */
+int simlod_query_rays(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRay* rays, uint32_t numRays,
+                      uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
+                      SimlodRayHit* hits, SimlodRayCounts* counts, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

@@ -137,3 +137,12 @@ region_dtype = np.dtype({"names": ["numPlanes", "reserved", "planes"], "formats"
 query_counts_dtype = np.dtype({"names": ["numNodes", "error", "numSamples", "numCandidates", "numFilteredNodes", "numCopiedNodes"],
                                "formats": ["<u4", "<u4", "<u8", "<u8", "<u4", "<u4"], "offsets": [0, 4, 8, 16, 24, 28], "itemsize": 32})
 assert region_dtype.itemsize == 272 and query_counts_dtype.itemsize == 32
+
+# ---- ray queries (include/simlod_hip.h, "ray queries") -----------------------------------------------------------------------------------
+RAYS_MAX = 1 << 20
+ray_dtype = np.dtype({"names": ["origin", "tMin", "dir", "tMax", "radius", "spread", "reserved"],
+                      "formats": [("<f4", 3), "<f4", ("<f4", 3), "<f4", "<f4", "<f4", ("<u4", 2)], "offsets": [0, 12, 16, 28, 32, 36, 40], "itemsize": 48})
+ray_hit_dtype = np.dtype({"names": ["t", "node", "ordinal", "sample"], "formats": ["<f8", "<u4", "<u4", point_dtype], "offsets": [0, 8, 12, 16], "itemsize": 32})
+ray_counts_dtype = np.dtype({"names": ["numNodes", "error", "numHits", "numInvalid", "numPairs", "numCandidates"],
+                             "formats": ["<u4", "<u4", "<u4", "<u4", "<u8", "<u8"], "offsets": [0, 4, 8, 12, 16, 24], "itemsize": 32})
+assert ray_dtype.itemsize == 48 and ray_hit_dtype.itemsize == 32 and ray_counts_dtype.itemsize == 32

@@ -556,6 +556,18 @@ int simlod_query_region(const SimlodNode* nodes, const SimlodStats* stats, const
 	                    sampleCapacity, counts, (hipStream_t)stream);
 }
 
+uint64_t simlod_rays_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates) {
+	return rays_min_bytes(nodeCapacity, sampleBound, numRays, numPairs, numCandidates);
+}
+
+int simlod_query_rays(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRay* rays, uint32_t numRays,
+                      uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
+                      SimlodRayHit* hits, SimlodRayCounts* counts, void* stream) {
+	if (nodes == nullptr) return (int)hipErrorInvalidValue;
+	return launch_rays(context_of(nodes), nodes, stats, uniforms, rays, numRays, maxLevel, select, scratch, scratchBytes, table, tableCapacity, hits,
+	                   counts, (hipStream_t)stream);
+}
+
 uint64_t simlod_colorfilter_buffer_min_bytes(void) { return colorfilter_min_bytes(default_context().nodeCapacity.load()); }
 
 int simlod_generate_terrain(SimlodPoint* out, uint64_t numPoints, uint64_t firstIndex, uint64_t pointsPerTile, uint32_t seed, uint32_t tilesX,

@@ -192,6 +192,10 @@ int launch_query(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats
                  uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
                  uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream);
 uint64_t query_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+int launch_rays(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRay* rays, uint32_t numRays,
+                uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
+                SimlodRayHit* hits, SimlodRayCounts* counts, hipStream_t stream);
+uint64_t rays_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates);
 int launch_generate_terrain(SimlodPoint* out, uint64_t numPoints, uint64_t firstIndex, uint64_t pointsPerTile, uint32_t seed, uint32_t tilesX,
                             const float tileExtent[3], float swathWidth, hipStream_t stream);
 enum : uint32_t { RENDER_FIRST = 1u, RENDER_COLOR = 2u, RENDER_RESOLVE = 4u, RENDER_OUTPUT = 8u, RENDER_ALL = 15u };

@@ -20,6 +20,9 @@ File format (little-endian throughout):
 
 Region queries (include/simlod_hip.h, "region queries"): `Region` holds the half-spaces, and `OctreeExport.crop` is the host mirror of
 simlod_query_region — every rule restated in numpy float64, which reproduces the device's fp64 arithmetic bit for bit.
+
+Ray queries (include/simlod_hip.h, "ray queries"): `Rays` holds a batch of SimlodRay records, `OctreeExport.cast` (on a full export) and
+`OctreeExport.cast_selected` (on any export) are the host mirror of simlod_query_rays, in the same float64 operation order.
 """
 import numpy as np
 import torch
@@ -183,6 +186,128 @@ class OctreeExport:
         c["numFilteredNodes"], c["numCopiedNodes"] = n_filtered, n_copied
         return ex, c
 
+    # -- ray queries (include/simlod_hip.h, "ray queries") -----------------------------------------------------------------------------------
+    def truncated(self, max_level=None, select="cut"):
+        """What simlod_export_octree(max_level, select) writes for the octree this FULL export was taken from ("all" or "cut"): breadth-first
+        order keeps the levels together, so the table is a prefix of this one with the entries at max_level cut off from their children."""
+        if self.select != abi.EXPORT_ALL or self.max_level < abi.MAX_DEPTH:
+            raise ValueError(f"needs a full export (select all, max level 20), not select {self.select} / max level {self.max_level}")
+        sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
+        if sel not in (abi.EXPORT_ALL, abi.EXPORT_CUT):
+            raise ValueError("only 'all' and 'cut' follow from a full export")
+        ml = abi.MAX_DEPTH if max_level is None else max(0, min(int(max_level), abi.MAX_DEPTH))
+        src, smp = self.nodes, self.samples
+        k = int((src["level"] <= ml).sum())
+        out = src[:k].copy()
+        assert (out["level"] <= ml).all(), "the table is not in breadth-first order"
+        cut = out["level"] == ml
+        out["childMask"][cut], out["firstChild"][cut] = 0, abi.EXPORT_NONE
+        leaf = (out["flags"] & abi.EXPORT_FLAG_LEAF) != 0
+        chosen = np.ones(k, bool) if sel == abi.EXPORT_ALL else leaf | cut
+        out["flags"] = np.where(leaf, abi.EXPORT_FLAG_LEAF, 0) | np.where(chosen, abi.EXPORT_FLAG_SELECTED, 0)
+        ns = src["numSamples"][:k].astype(np.int64)
+        out["numSamples"] = np.where(chosen, ns, 0)
+        out["firstSample"] = np.concatenate([[0], np.cumsum(out["numSamples"].astype(np.int64))[:-1]]).astype(np.uint64)
+        samples = smp[: int(ns.sum())][np.repeat(chosen, ns)]
+        return OctreeExport(out, samples, self.box_min, self.box_max, ml, sel)
+
+    def cast(self, rays, max_level=None, select="cut", return_counts=False, return_passing=False):
+        """The host mirror of simlod_query_rays on the octree this FULL export was taken from: the hits (abi.ray_hit_dtype, one per ray) whose
+        `node` / `ordinal` index the table and sample ranges of export_octree(max_level, select) — and, return_counts, the SimlodRayCounts
+        record; return_passing, the number of samples of its pairs that pass the test, per ray."""
+        return self.truncated(max_level, select).cast_selected(rays, return_counts, return_passing)
+
+    def _ray_pairs(self, rec):
+        """Rules 1 and 3 for SimlodRay records against this table: (valid per ray, [(table index, the rays paired with it)] in table order)."""
+        tb = self.nodes
+        o, d = rec["origin"].astype(np.float64), rec["dir"].astype(np.float64)
+        tmin, tmax, rad, spr = (rec[f].astype(np.float64) for f in ("tMin", "tMax", "radius", "spread"))
+        with np.errstate(invalid="ignore", over="ignore"):
+            valid = np.isfinite(o).all(1) & np.isfinite(d).all(1) & np.isfinite(tmin) & np.isfinite(tmax) & np.isfinite(rad) & np.isfinite(spr)
+            valid &= (d != 0).any(1) & (tmin >= 0) & (tmin <= tmax) & (rad >= 0) & (spr >= 0) & (rec["reserved"] == 0).all(1)
+            R = rad + spr * tmax
+        mn, size = _box_of(self.box_min, self.box_max)
+        e = np.ldexp(size, -abi.MAX_DEPTH)
+        reach = {0: np.nonzero(valid)[0]}
+        pairs = []
+        for t in range(len(tb)):
+            idx = reach.pop(t, None)
+            if idx is None or len(idx) == 0:
+                continue
+            nd = tb[t]
+            s = np.ldexp(size, -int(nd["level"]))
+            A = np.array([nd["X"], nd["Y"], nd["Z"]], dtype=np.float64)
+            lo, hi = (mn + A * s) - e, (mn + (A + 1.0) * s) + e
+            idx = idx[_slab(lo, hi, o[idx], d[idx], tmin[idx], tmax[idx], R[idx])]
+            if len(idx) == 0:
+                continue
+            c = int(nd["firstChild"])
+            for k in range(8):
+                if (int(nd["childMask"]) >> k) & 1:
+                    reach[c] = idx
+                    c += 1
+            if int(nd["numSamples"]) != 0 and int(nd["flags"]) & abi.EXPORT_FLAG_SELECTED:
+                pairs.append((t, idx))
+        return valid, pairs
+
+    def rays_per_node(self, rays):
+        """How many rays form a pair with each table entry (rule 3 alone: no sample is tested)."""
+        rec = rays.record() if isinstance(rays, Rays) else np.ascontiguousarray(rays).view(abi.ray_dtype).reshape(-1)
+        out = np.zeros(self.num_nodes, np.int64)
+        for t, idx in self._ray_pairs(rec)[1]:
+            out[t] = len(idx)
+        return out
+
+    def cast_selected(self, rays, return_counts=False, return_passing=False):
+        """The mirror on an export whose selection is already made (any `select`, "visible" included): the nodes considered are this table's."""
+        rec = rays.record() if isinstance(rays, Rays) else np.ascontiguousarray(rays).view(abi.ray_dtype).reshape(-1)
+        tb, smp = self.nodes, self.samples
+        n = len(rec)
+        hits = np.zeros(n, dtype=abi.ray_hit_dtype)
+        hits["t"], hits["node"], hits["ordinal"] = np.inf, abi.EXPORT_NONE, abi.EXPORT_NONE
+        passing = np.zeros(n, np.int64)
+        o, d = rec["origin"].astype(np.float64), rec["dir"].astype(np.float64)
+        tmin, tmax, rad, spr = (rec[f].astype(np.float64) for f in ("tMin", "tMax", "radius", "spread"))
+        with np.errstate(invalid="ignore", over="ignore"):
+            dd = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        x, y, z = (smp[a].astype(np.float64) for a in ("x", "y", "z"))
+        valid, pairs = self._ray_pairs(rec)
+        num_pairs = num_cand = 0
+        for t, idx in pairs:
+            ns, a = int(tb["numSamples"][t]), int(tb["firstSample"][t])
+            num_pairs += len(idx)
+            num_cand += len(idx) * ns
+            sx, sy, sz = x[a:a + ns], y[a:a + ns], z[a:a + ns]
+            step = max(1, (1 << 21) // ns)
+            for b in range(0, len(idx), step):
+                i = idx[b:b + step]
+                col = lambda v: v[i][:, None]
+                dx, dy, dz = col(d[:, 0]), col(d[:, 1]), col(d[:, 2])
+                with np.errstate(invalid="ignore", over="ignore"):
+                    px, py, pz = sx[None, :] - col(o[:, 0]), sy[None, :] - col(o[:, 1]), sz[None, :] - col(o[:, 2])
+                    tt = ((dx * px + dy * py) + dz * pz) / col(dd)
+                    qx, qy, qz = px - tt * dx, py - tt * dy, pz - tt * dz
+                    s2 = (qx * qx + qy * qy) + qz * qz
+                    rr = col(rad) + col(spr) * tt
+                    ok = (tt >= col(tmin)) & (tt <= col(tmax)) & (s2 <= rr * rr)
+                passing[i] += ok.sum(1)
+                tm = np.where(ok, tt, np.inf)
+                j = tm.argmin(1)                                   # (the first of equal minima: the smallest ordinal)
+                tb_ = tm[np.arange(len(i)), j]
+                upd = tb_ < hits["t"][i]                           # (nodes in ascending order: an equal t keeps the smaller node)
+                iu, ju = i[upd], j[upd]
+                hits["t"][iu], hits["node"][iu], hits["ordinal"][iu] = tb_[upd], t, ju
+                hits["sample"][iu] = smp[a + ju]
+        out = [hits]
+        if return_counts:
+            c = np.zeros((), dtype=abi.ray_counts_dtype)
+            c["numNodes"], c["numHits"], c["numInvalid"] = len(tb), int((hits["node"] != abi.EXPORT_NONE).sum()), int((~valid).sum())
+            c["numPairs"], c["numCandidates"] = num_pairs, num_cand
+            out.append(c)
+        if return_passing:
+            out.append(passing)
+        return out[0] if len(out) == 1 else tuple(out)
+
     def save(self, path):
         h = np.zeros(1, dtype=header_dtype)
         h["magic"], h["version"], h["select"], h["max_level"], h["header_bytes"] = MAGIC, VERSION, self.select, self.max_level, HEADER_BYTES
@@ -277,6 +402,72 @@ class Region:
         r["numPlanes"] = len(self.planes)
         r["planes"][0, : len(self.planes)] = self.planes
         return r
+
+
+def _slab(lo, hi, o, d, tmin, tmax, R):
+    """Rule 3 of the ray query for one node's inflated cube [lo, hi] against rays (rows of o, d; tmin, tmax, R per ray) -> a boolean per ray."""
+    ok = np.ones(len(o), bool)
+    near, far = tmin.copy(), tmax.copy()
+    for a in range(3):
+        L, H = lo[a] - R, hi[a] + R
+        zero = d[:, a] == 0
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            t1, t2 = (L - o[:, a]) / d[:, a], (H - o[:, a]) / d[:, a]
+        ok &= ~(zero & ((o[:, a] < L) | (o[:, a] > H)))
+        near = np.where(zero, near, np.fmax(near, np.fmin(t1, t2)))
+        far = np.where(zero, far, np.fmin(far, np.fmax(t1, t2)))
+    return ok & (near <= far)
+
+
+class Rays:
+    """A batch of SimlodRay records (abi.ray_dtype): origin, direction (any non-zero length; t is in units of it), [t_min, t_max], and the cone
+    radius + spread * t.  Scalars broadcast over the batch.  Nothing is validated here: an invalid ray is legal input and misses."""
+
+    def __init__(self, origin, direction, t_min=0.0, t_max=1.0, radius=0.0, spread=0.0):
+        o = np.asarray(origin, dtype=np.float64).reshape(-1, 3)
+        r = np.zeros(len(o), dtype=abi.ray_dtype)
+        with np.errstate(over="ignore", invalid="ignore"):
+            r["origin"], r["dir"] = o, np.broadcast_to(np.asarray(direction, dtype=np.float64), o.shape)
+            r["tMin"], r["tMax"], r["radius"], r["spread"] = t_min, t_max, radius, spread
+        self.rays = r
+
+    def __len__(self):
+        return len(self.rays)
+
+    @classmethod
+    def from_records(cls, records):
+        self = cls.__new__(cls)
+        self.rays = np.array(np.ascontiguousarray(records).view(abi.ray_dtype).reshape(-1), copy=True)
+        return self
+
+    @classmethod
+    def vertical(cls, xy, z_top, radius, z_bottom=0.0):
+        """Rays straight down from (x, y, z_top) to z_bottom, of constant radius: the height under each position is z_top - hit.t."""
+        xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+        o = np.concatenate([xy, np.full((len(xy), 1), float(z_top))], axis=1)
+        return cls(o, (0.0, 0.0, -1.0), 0.0, float(z_top) - float(z_bottom), radius, 0.0)
+
+    @classmethod
+    def from_pixels(cls, transform, width, height, pixels, pixel_radius=0.5, t_max=None):
+        """Cones through pixel centres of the camera `transform` (row-major world-view-projection as the uniforms store it; pixel (i, j) covers
+        ndc [2i/width - 1, 2(i+1)/width - 1] as the rasteriser maps it).  The origin is the pixel's point on the near plane, the direction has
+        unit length, and radius / spread are pixel_radius times the pixel's footprint there and its growth per unit t.  t_max: None -> the far plane."""
+        m = np.linalg.inv(np.asarray(transform, dtype=np.float64).reshape(4, 4))
+        px = np.asarray(pixels, dtype=np.float64).reshape(-1, 2)
+
+        def unproject(i, j, zc):
+            c = np.stack([2.0 * i / width - 1.0, 2.0 * j / height - 1.0, np.full(len(i), zc), np.ones(len(i))], axis=1) @ m.T
+            return c[:, :3] / c[:, 3:4]
+
+        i, j = px[:, 0] + 0.5, px[:, 1] + 0.5
+        n0, f0, n1, f1 = unproject(i, j, -1.0), unproject(i, j, 1.0), unproject(i + 1.0, j, -1.0), unproject(i + 1.0, j, 1.0)
+        length = np.linalg.norm(f0 - n0, axis=1)
+        wn, wf = np.linalg.norm(n1 - n0, axis=1), np.linalg.norm(f1 - f0, axis=1)
+        return cls(n0, (f0 - n0) / length[:, None], 0.0, length if t_max is None else t_max, pixel_radius * wn, pixel_radius * (wf - wn) / length)
+
+    def record(self):
+        """The SimlodRay records the C ABI takes (abi.ray_dtype, one per ray)."""
+        return self.rays
 
 
 def validate_table(t, num_samples, buildable=False):

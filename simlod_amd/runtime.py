@@ -90,6 +90,9 @@ def lib():
         L.simlod_query_buffer_min_bytes.restype = u64
         L.simlod_query_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_query_region.argtypes = [vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
+        L.simlod_rays_buffer_min_bytes.restype = u64
+        L.simlod_rays_buffer_min_bytes.argtypes = [u32, u64, u32, u64, u64]
+        L.simlod_query_rays.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, u64, vp, u32, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -106,7 +109,7 @@ EXPORTED_SYMBOLS = [
     "simlod_context_hint_pending_batches", "simlod_upload_counter_written",
     "simlod_profile_enable", "simlod_profile_collect", "simlod_generate_terrain", "simlod_generate_terrain_scan", "simlod_launch_colorfilter", "simlod_colorfilter_buffer_min_bytes",
     "simlod_export_buffer_min_bytes", "simlod_export_octree", "simlod_import_octree", "simlod_import_octree_buildable",
-    "simlod_query_buffer_min_bytes", "simlod_query_region",
+    "simlod_query_buffer_min_bytes", "simlod_query_region", "simlod_rays_buffer_min_bytes", "simlod_query_rays",
 ]
 
 
@@ -647,6 +650,52 @@ class DeviceOctree:
         u = np.asarray(uniforms).reshape(-1)[0]
         ex = OctreeExport(table, samples[: int(c["numSamples"]) * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_REGION)
         return (ex, c) if return_counts else ex
+
+    # -- ray queries (include/simlod_hip.h, "ray queries") ---------------------------------------------------------------------------------
+    def _rays(self, uniforms, rays, max_level, select, hits, pairs=0, candidates=0):
+        """One simlod_query_rays call -> the SimlodRayCounts record (host).  hits None: count only.  `rays`: an octree_io.Rays or a uint8
+        device tensor of SimlodRay records."""
+        u, up = self._u(uniforms)
+        sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
+        ml = abi.MAX_DEPTH if max_level is None else max(0, min(int(max_level), abi.MAX_DEPTH))
+        st = self.read_stats()
+        nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+        n = rays.numel() // abi.ray_dtype.itemsize
+        scratch = self._export_scratch(int(self.L.simlod_rays_buffer_min_bytes(nn, bound, n, pairs, candidates)))
+        counts = torch.zeros(abi.ray_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        _check(self.L.simlod_query_rays(self._p(self.nodes), self._p(self.stats), up, self._p(rays), n, ml, sel, self._p(scratch),
+                                        ctypes.c_uint64(scratch.numel()), None, nn, None if hits is None else self._p(hits), self._p(counts),
+                                        self._stream()), "simlod_query_rays")
+        c = counts.cpu().numpy().view(abi.ray_counts_dtype)[0]
+        if int(c["error"]) != 0:
+            raise SimlodError(f"simlod_query_rays reported error bits {int(c['error']):#x} ({int(c['numNodes'])} nodes, {int(c['numPairs'])} pairs)")
+        return c
+
+    def _rays_tensor(self, rays):
+        if isinstance(rays, torch.Tensor):
+            t = rays.reshape(-1).view(torch.uint8)
+            if t.device != self.device or t.numel() == 0 or t.numel() % abi.ray_dtype.itemsize:
+                raise SimlodError("rays: a non-empty tensor of whole SimlodRay records on this octree's device")
+            return t
+        rec = np.ascontiguousarray(rays.record())
+        if len(rec) == 0:
+            raise SimlodError("rays: an empty batch")
+        return torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(self.device)
+
+    def count_rays(self, uniforms, rays, max_level=None, select="cut"):
+        """The SimlodRayCounts record of a count-only simlod_query_rays call (numNodes, numHits, numInvalid, numPairs, numCandidates)."""
+        return self._rays(uniforms, self._rays_tensor(rays), max_level, select, None)
+
+    def cast_rays(self, uniforms, rays, max_level=None, select="cut", return_counts=False):
+        """The first sample in the cone along each ray (an octree_io.Rays, or a device tensor of SimlodRay records): a count-only call, scratch
+        sized from its counts, then the hits — a numpy record array (abi.ray_hit_dtype) for host rays, a uint8 device tensor of the same
+        records for device rays.  `node` / `ordinal` refer to export_octree(max_level, select).  A miss has t = inf and node = EXPORT_NONE."""
+        t = self._rays_tensor(rays)
+        c = self._rays(uniforms, t, max_level, select, None)
+        hits = torch.empty(t.numel() // abi.ray_dtype.itemsize * abi.ray_hit_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        c = self._rays(uniforms, t, max_level, select, hits, int(c["numPairs"]), int(c["numCandidates"]))
+        out = hits if isinstance(rays, torch.Tensor) else hits.cpu().numpy().view(abi.ray_hit_dtype)
+        return (out, c) if return_counts else out
 
     def import_octree(self, export, check=True, *, buildable=False, uniforms=None):
         """Replace this object's octree by `export` (an octree_io.OctreeExport on the host or on a device): simlod_import_octree validates the

@@ -4,7 +4,10 @@ device-to-device copy of the same sample bytes as the ceiling — each timed `--
 call.  Prints one JSON line.  Per-kernel split: run it under `rocprofv3 --kernel-trace --stats -- python ...`.
 --region: instead, simlod_query_region CUT@20 on the same octree — the whole box (zero planes) beside simlod_export_octree CUT@20, the two
 alternating rep by rep; half the terrain (one oblique plane through the box centre); a city block (a box of 1 % of the area), with its
-count-only call — and the device-to-device copy, all in this one run."""
+count-only call — and the device-to-device copy, all in this one run.
+--rays: instead, simlod_query_rays CUT@20 on the same octree — one pixel cone through the frame's centre beside the count-only region
+query of a thin box around the same ray, the two alternating rep by rep; 4 096 vertical rays of radius 0.5 with their pairs, candidates
+and the distinct chunk bytes of the paired nodes — and the device-to-device copy, all in this one run."""
 import argparse
 import ctypes
 import json
@@ -129,6 +132,88 @@ def region_bench(dev, u, box, st, reps):
     print(json.dumps(out))
 
 
+def rays_bench(dev, u, box, st, reps, T, width, height):
+    from simlod_amd import fingerprint
+    from simlod_amd.octree_io import OctreeExport, Rays, Region
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    uu, up = dev._u(u)
+    table = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    counts = torch.zeros(32, dtype=torch.uint8, device=dev.device)
+    b = np.asarray(box, dtype=np.float64)
+    cone = Rays.from_pixels(T, width, height, [[width // 2, height // 2]], pixel_radius=0.5, t_max=3.0 * float(b.max()))
+    rs = np.random.RandomState(42)
+    vertical = Rays.vertical(rs.rand(4096, 2) * b[:2], b[2] + 10.0, 0.5, -10.0)
+    # a thin box around the cone: four planes along the ray at its widest radius, two across it at t = 0 and tMax
+    r0 = cone.record()[0]
+    o, d, tmax = r0["origin"].astype(np.float64), r0["dir"].astype(np.float64), float(r0["tMax"])
+    wide = float(r0["radius"]) + float(r0["spread"]) * tmax
+    a1 = np.cross(d, [0.0, 0.0, 1.0]); a1 /= np.linalg.norm(a1)
+    a2 = np.cross(d, a1)
+    planes = [[*n, -float(n @ o) + w] for n, w in ((a1, wide), (-a1, wide), (a2, wide), (-a2, wide), (d, 0.0), (-d, tmax))]
+    region = Region.from_planes(planes).record()
+    q_need = int(L.simlod_query_buffer_min_bytes(nn, bound))
+    q_scratch = torch.empty(q_need, dtype=torch.uint8, device=dev.device)
+    q_counts = torch.zeros(32, dtype=torch.uint8, device=dev.device)
+
+    def region_count():
+        rc = L.simlod_query_region(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(region.ctypes.data), 20, abi.EXPORT_CUT, p(q_scratch),
+                                   ctypes.c_uint64(q_need), p(table), nn, None, ctypes.c_uint64(0), p(q_counts), stream)
+        assert rc == 0
+
+    def setup(rays):
+        d_rays = torch.from_numpy(rays.record().view(np.uint8).reshape(-1)).to(dev.device)
+        n = len(rays)
+        c = dev.count_rays(u, rays)
+        need = int(L.simlod_rays_buffer_min_bytes(nn, bound, n, int(c["numPairs"]), int(c["numCandidates"])))
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+        hits = torch.empty(n * 32, dtype=torch.uint8, device=dev.device)
+
+        def call(count_only=False):
+            rc = L.simlod_query_rays(p(dev.nodes), p(dev.stats), up, p(d_rays), n, 20, abi.EXPORT_CUT, p(scratch), ctypes.c_uint64(need), None, nn,
+                                     None if count_only else p(hits), p(counts), stream)
+            assert rc == 0
+        return call, c, need
+
+    cut = dev.export_octree(u, select="cut")
+    n_points = int(st["numPoints"])
+    copy_dst = torch.empty(n_points * 16, dtype=torch.uint8, device=dev.device)
+    copy_src = cut.samples_tensor[: copy_dst.numel()]
+    t_copy = timed(lambda: copy_dst.copy_(copy_src), reps)
+    copy_gbs = 2 * copy_dst.numel() / (t_copy[0] * 1e6)
+    out = {"points": n_points, "numNodes": nn, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(),
+           "d2d_copy": {"ms": round(t_copy[0], 4), "bytes": 2 * copy_dst.numel(), "GBs": round(copy_gbs, 1)}}
+
+    def counts_of(call):
+        call()
+        torch.cuda.synchronize()
+        c = counts.cpu().numpy().view(abi.ray_counts_dtype)[0]
+        assert int(c["error"]) == 0
+        return {f: int(c[f]) for f in abi.ray_counts_dtype.names}
+
+    call1, c1, need1 = setup(cone)
+    t_cone, t_cone_count, t_region = timed_alternating([call1, lambda: call1(True), region_count], reps)
+    torch.cuda.synchronize()
+    qc = q_counts.cpu().numpy().view(abi.query_counts_dtype)[0]
+    out["pixel_cone"] = {"ms": round(t_cone[0], 4), "ms_min": round(t_cone[1], 4), "count_only_ms": round(t_cone_count[0], 4), **counts_of(call1),
+                         "region_count_only_ms": round(t_region[0], 4), "region_numCandidates": int(qc["numCandidates"]),
+                         "over_region_count_only": round(t_cone[0] / t_region[0], 4), "target": "<= 1.5 x the count-only region query of the same run",
+                         "target_held": bool(t_cone[0] <= 1.5 * t_region[0])}
+    call4, c4, need4 = setup(vertical)
+    t_vert, t_vert_count = timed_alternating([call4, lambda: call4(True)], reps)
+    per_node = cut.rays_per_node(vertical)
+    chunk_bytes = int(cut.nodes["numSamples"][per_node > 0].astype(np.int64).sum()) * 16
+    ideal = chunk_bytes + len(vertical) * 32
+    gbs = ideal / (t_vert[0] * 1e6)
+    cv = counts_of(call4)
+    gflops = cv["numCandidates"] * 25 / (t_vert[0] * 1e6)
+    out["vertical_4096"] = {"ms": round(t_vert[0], 4), "ms_min": round(t_vert[1], 4), "count_only_ms": round(t_vert_count[0], 4), **cv,
+                            "paired_nodes": int((per_node > 0).sum()), "distinct_chunk_bytes": chunk_bytes, "ideal_bytes": ideal, "scratch_bytes": need4,
+                            "GBs": round(gbs, 1), "frac_of_copy": round(gbs / copy_gbs, 4), "fp64_GFLOPs_at_25_per_candidate": round(gflops, 1),
+                            "target": ">= 50 % of the copy rate on the ideal bytes", "target_held": bool(gbs / copy_gbs >= 0.5)}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=36_000_000)
@@ -136,6 +221,7 @@ def main():
     ap.add_argument("--persistent-gb", type=int, default=16)
     ap.add_argument("--buildable", action="store_true", help="also time simlod_import_octree_buildable (grid rebuild included)")
     ap.add_argument("--region", action="store_true", help="time simlod_query_region (whole box, half the terrain, a city block) instead")
+    ap.add_argument("--rays", action="store_true", help="time simlod_query_rays (one pixel cone, 4 096 vertical rays) instead")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
     pts, box = synthetic.terrain(n_points, seed=7)
@@ -156,6 +242,8 @@ def main():
     nn, ns = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
     if args.region:
         return region_bench(dev, u, box, st, args.reps)
+    if args.rays:
+        return rays_bench(dev, u, box, st, args.reps, T, 1920, 1080)
     L = dev.L
     need = int(L.simlod_export_buffer_min_bytes(nn, ns))
     scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
