@@ -114,7 +114,8 @@ static constexpr int RSV_SLOT_SHIFT = 52;
 __device__ __forceinline__ uint32_t slots_in_use(const BatchCtl* bc) {
 	return (uint32_t)(__hip_atomic_load(&bc->reserve, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> RSV_SLOT_SHIFT);
 }
-__device__ __forceinline__ bool reserve(const BuildArgs& a, Ctl* ctl, BatchCtl* bc, uint32_t slots, uint32_t nodes, uint32_t spill, uint32_t& slotBase, uint32_t& nodeBase, uint32_t& spillBase) {
+// -> 0, or the error bit of what did not fit (nothing is raised: reserve() below does that; a caller that asks for several things at once decides itself)
+__device__ __forceinline__ uint32_t reserve_try(const BuildArgs& a, BatchCtl* bc, uint32_t slots, uint32_t nodes, uint32_t spill, uint32_t& slotBase, uint32_t& nodeBase, uint32_t& spillBase) {
 	// ONE add on the packed word hands out the three ranges; a caller that finds any of them beyond its capacity takes its add back and fails.  While such
 	// a failed add stands, every other caller sees that field beyond its capacity too and fails as well (conservatively: the leaf stays as it is and is
 	// queued again later) — so a caller that SUCCEEDS never got its ranges on top of amounts that are taken back afterwards.  The fields have room for
@@ -125,10 +126,14 @@ __device__ __forceinline__ bool reserve(const BuildArgs& a, Ctl* ctl, BatchCtl* 
 	const unsigned long long old = atomicAdd(&bc->reserve, inc);
 	slotBase = (uint32_t)(old >> RSV_SLOT_SHIFT); nodeBase = (uint32_t)(old >> 32) & 0xfffffu; spillBase = (uint32_t)old;
 	const bool okSlots = slotBase + slots <= SLOT_CAP, okNodes = nodeBase + nodes <= a.nodeCapacity, okSpill = (unsigned long long)spillBase + spill <= a.spilledCap;
-	if (okSlots && okNodes && okSpill) { atomicAdd(&a.stats->numNodes, nodes); return true; }       // voxels.cu:317
+	if (okSlots && okNodes && okSpill) { atomicAdd(&a.stats->numNodes, nodes); return 0u; }       // voxels.cu:317
 	atomicAdd(&bc->reserve, 0ull - inc);
-	raise(ctl, !okSlots ? SIMLOD_ERR_SPILLING_OVERFLOW : !okNodes ? SIMLOD_ERR_NODES_EXHAUSTED : SIMLOD_ERR_SPILLED_OVERFLOW);      // more leaves cross the limit at once than a batch has slots for | node array full | spill space
-	return false;
+	return !okSlots ? SIMLOD_ERR_SPILLING_OVERFLOW : !okNodes ? SIMLOD_ERR_NODES_EXHAUSTED : SIMLOD_ERR_SPILLED_OVERFLOW;      // more leaves cross the limit at once than a batch has slots for | node array full | spill space
+}
+__device__ __forceinline__ bool reserve(const BuildArgs& a, Ctl* ctl, BatchCtl* bc, uint32_t slots, uint32_t nodes, uint32_t spill, uint32_t& slotBase, uint32_t& nodeBase, uint32_t& spillBase) {
+	const uint32_t err = reserve_try(a, bc, slots, nodes, spill, slotBase, nodeBase, spillBase);
+	if (err != 0u) raise(ctl, err);
+	return err == 0u;
 }
 
 // the occupancy grid of a node that splits in this batch: allocated if the node has none (voxels.cu:363-365), cleared in any case
@@ -142,13 +147,14 @@ __device__ __forceinline__ void note_clear(const BuildArgs& a, const BatchCtl* b
 		for (uint32_t i = 0; i < SIMLOD_GRID_NUM_WORDS / 4; i++) w[i] = make_uint4(0, 0, 0, 0);
 	}
 }
-__device__ __forceinline__ SimlodOccupancyGrid* grid_for_split(const BuildArgs& a, BatchCtl* bc) {
-	uint8_t* mem = persistent_alloc(a.pers, sizeof(SimlodOccupancyGrid), 1);          // (two independent atomics with a return value: one round trip)
-	const uint32_t c = atomicAdd(&bc->numClear, 1u);
-	SimlodOccupancyGrid* g = reinterpret_cast<SimlodOccupancyGrid*>(mem);
-	note_clear(a, bc, c, g);
-	return g;
+// the grids of `count` such nodes at once (k_expand: a slot's splitting children and grandchildren and its next-round nodes): ONE allocation (the counted form: the allocator's offset advances as by `count` single ones) and ONE add on the list's length;
+// grid k of them is grid_of_many(mem, k), and its list entry clearBase + k (note_clear)
+__device__ __forceinline__ uint8_t* grids_for_splits(const BuildArgs& a, BatchCtl* bc, uint32_t count, uint32_t& clearBase) {
+	uint8_t* mem = persistent_alloc(a.pers, sizeof(SimlodOccupancyGrid), count);          // (two independent atomics with a return value: one round trip)
+	clearBase = atomicAdd(&bc->numClear, count);
+	return mem;
 }
+__device__ __forceinline__ SimlodOccupancyGrid* grid_of_many(uint8_t* mem, uint32_t k) { return reinterpret_cast<SimlodOccupancyGrid*>(mem + (uint64_t)k * SIMLOD_ALLOC_ROUND(sizeof(SimlodOccupancyGrid))); }
 
 // Queue leaf `nodeIdx` for splitting: ONE WAVE (k_queue).  Everything the split needs is reserved here, before anything is modified: a slot (and
 // with it a histogram), eight node slots and the spill space for the stored points together, the occupancy grid.  Then the leaf's

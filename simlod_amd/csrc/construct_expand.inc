@@ -18,17 +18,21 @@ __device__ __forceinline__ VoxItem* vox_items(const BuildArgs& a, const BatchCtl
 // ---- chunks for the leaves with new samples ----------------------------------------------------------------------------
 // The point chunks of the leaves with new samples and their share of k_voxelize's work list (voxels.cu:485-538), for ALLOC_LEAVES entries
 // of the batch's list: ONE WORKGROUP.
-//   phase 1, wave 0, one leaf per lane: how many chunks, directory entries and work items each leaf needs; the reservations of the wave's
+//   phase 1, the first `waves` waves, one leaf per lane: how many chunks, directory entries and work items each leaf needs; the reservations of the wave's
 //     leaves — directory entries, chunks off the recycle stack (voxels.cu:505-516), work items, memory for the chunks the stack cannot
 //     serve — are summed over the wave and made with ONE atomic each (the words they advance are shared by every leaf of the batch, and
 //     device-scope atomics on one word retire at ~88 M/s here);
 //   phase 2, all waves, one NEW CHUNK per lane: fetch it (stack or fresh memory), link it, enter it in the chunk directory and the leaf
 //     chunk table.  A leaf the batch has filled from nothing needs 50 chunks; taken one after the other by the leaf's lane that was 50
 //     dependent round trips (the whole of round 2's allocation kernel: 13 us), taken side by side it is two.
+// The number of waves that take leaves is a RUN-TIME argument of a call (64 leaves per wave): the lists of touched leaves and the ordinary slot (8.7 fresh
+// leaves on average) take one wave — its four wave-wide sums and four atomics are the whole of phase 1 —, a slot whose cascade made more than 64 fresh
+// leaves takes a wave per 64 of them in ONE turn (a group of several batches hands a root's or a flooded leaf's cascade over at once: up to 584 nodes; with
+// one wave that was nine turns of ~5 us each, one behind the other).  ALLOC_WAVES_N is the most a call can ask for: enough for every node a slot can create.
 #ifndef ALLOC_WAVES_N
-#define ALLOC_WAVES_N 1      /* (8: a wave per 64 leaves — measured: no gain, k_expand's build phase is not bound by this loop; and a fault in plain exact mode with the trunk mask that was not understood) */
+#define ALLOC_WAVES_N 10
 #endif
-static constexpr uint32_t ALLOC_WAVES = ALLOC_WAVES_N, ALLOC_LEAVES = 64 * ALLOC_WAVES;      // leaves per call: a wave per 64 (a group of several batches hands a cascade's 584 nodes over at once: one wave took nine turns, 45 us of k_expand's 61 per slot)
+static constexpr uint32_t ALLOC_WAVES = ALLOC_WAVES_N, ALLOC_LEAVES = 64 * ALLOC_WAVES;      // waves, leaves of a call at most
 struct AllocRec {
 	uint32_t node, existing, additional, fromPool;
 	uint32_t dirNew, prefix;                                // directory entry of the leaf's first new chunk | new chunks of the lanes below
@@ -41,14 +45,14 @@ struct FreshLeaf { uint32_t node, samples, level, X, Y, Z; };      // a leaf a c
 // Entry k is taken when firstEntry + lane < numEntries.  `touched` (global memory): the leaves k_count found new samples for — what
 // each held when the batch began comes from stored_at_start().  `fresh` (LDS): {node, samples} of the empty leaves a cascade has
 // just made (nothing about them has to be read back).  One of the two lists is given.
-// (rec: ALLOC_LEAVES records in LDS — k_expand lends the words of its hash table)
-__device__ void alloc_points(const BuildArgs& a, Ctl* ctl, BatchCtl* bc, AllocShared& sh, AllocRec* rec, const uint32_t* touched, const FreshLeaf* fresh, uint32_t firstEntry, uint32_t numEntries) {
+// (rec: 64 * waves records in LDS — k_expand lends the words of its hash table; waves <= ALLOC_WAVES, the same for every thread of the workgroup)
+__device__ void alloc_points(const BuildArgs& a, Ctl* ctl, BatchCtl* bc, AllocShared& sh, AllocRec* rec, const uint32_t* touched, const FreshLeaf* fresh, uint32_t firstEntry, uint32_t numEntries, uint32_t waves) {
 	const bool fresh_leaves = fresh != nullptr;
 	NodeDir* nodeDir = at<NodeDir>(a, a.offNodeDir);
 	SimlodChunk** chunkDir = chunk_dir(a, bc);
 	SimlodChunk** chunkQueue = at<SimlodChunk*>(a, a.offQueue);
 	uint8_t* const leafChunks = a.mom + a.offLeafChunks;
-	if (threadIdx.x < 64u * ALLOC_WAVES) {
+	if (threadIdx.x < 64u * waves) {
 		const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
 		firstEntry += wv * 64u;                                         // (this wave's 64 entries)
 		// (Node.numPoints is not looked at: the back half of the batch before may still be advancing it)
@@ -144,10 +148,10 @@ __device__ void alloc_points(const BuildArgs& a, Ctl* ctl, BatchCtl* bc, AllocSh
 	__syncthreads();
 	// phase 2: new chunk q of the workgroup = chunk k of the leaf whose prefix covers q
 	uint32_t total = 0;
-	for (uint32_t w = 0; w < ALLOC_WAVES; w++) total += sh.waveTotal[w];
+	for (uint32_t w = 0; w < waves; w++) total += sh.waveTotal[w];
 	for (uint32_t q0 = threadIdx.x; q0 < total; q0 += blockDim.x) {
 		uint32_t q = q0, wv = 0;                                         // the wave whose leaves new chunk q0 belongs to, and its number among that wave's
-		while (wv + 1u < ALLOC_WAVES && q >= sh.waveTotal[wv]) { q -= sh.waveTotal[wv]; wv++; }
+		while (wv + 1u < waves && q >= sh.waveTotal[wv]) { q -= sh.waveTotal[wv]; wv++; }
 		uint32_t lo = wv * 64u, hi = lo + 64u;                           // the last leaf with prefix <= q (leaves without new chunks share their successor's prefix)
 		while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (rec[mid].prefix <= q) lo = mid; else hi = mid; }
 		const AllocRec r = rec[lo];
@@ -317,6 +321,10 @@ struct ExpandShared {
 	uint8_t nameL[20];
 	SimlodOccupancyGrid* gridL;
 	uint32_t numFresh, numFill;
+	uint32_t part[ETPB / 64u];                     // block_exclusive's word per wave
+	uint32_t nextGranted, nextSlot, nextChild, clearBase;      // the slots of the next round this slot's nodes got: how many, the first, its children; the grids' first entry of the clear list
+	uint8_t* gridMem;                              // ... and the grids themselves (the splitting children and grandchildren first, then the nodes with a slot)
+	uint32_t fillStart[LOCAL_NODES];               // first cell of fill[j] among all the cells to fill
 	// new leaves at level <= 3 whose cells of the top table the whole workgroup fills: {node | level << 19, X, Y, Z}.  The ROOT's cascade can make all of its
 	// 8 + 64 + 512 nodes such leaves (rounds 3-6 had 72 entries here: a terrain's first batch lists ~120, the entries beyond the array landed in whatever
 	// followed it — alloc_points' records while those stood there, harmlessly; the grids' pointers once they did not: a wild pointer in a path entry, a fault
@@ -355,34 +363,51 @@ __device__ __forceinline__ void hist_add(const BuildArgs& a, ExpandShared& sh, u
 	}
 	hist_flush(a, key, cnt, acct);          // no room in the table: straight to the histogram (this workgroup's copy)
 }
+// sum of `v` over the threads of the workgroup below this one, and over all of them (every thread calls: two barriers; part: a word per wave in LDS)
+__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* part, uint32_t& total) {
+	uint32_t waveTotal;
+	const uint32_t ex = wave_exclusive(v, waveTotal), wv = threadIdx.x >> 6;
+	__syncthreads();
+	if ((threadIdx.x & 63u) == 0u) part[wv] = waveTotal;
+	__syncthreads();
+	uint32_t before = 0;
+	total = 0;
+	for (uint32_t w = 0; w < ETPB / 64u; w++) { const uint32_t c = part[w]; if (w < wv) before += c; total += c; }
+	return before + ex;
+}
 // local node number t of a slot -> depth below the slot's node (1..3) and the octants chosen on the way
 __device__ __forceinline__ uint32_t local_depth(uint32_t t) { return t < 8u ? 1u : t < 72u ? 2u : 3u; }
 
 #ifndef EXPAND_U
-#define EXPAND_U 4      /* samples of a thread in flight in the in-kernel histogram pass of rounds >= 1.  Round 6, exact groups, ms per 36 M (same box): 4: 2.594, 8: 2.637, 16: 2.80 — the kernel lives
-                         at its 128-VGPR cap (1024 threads) and spills 116 / 212 / 504 bytes per lane with 4 / 8 / 16 */
+#define EXPAND_U 4      /* samples of a thread in flight in the in-kernel histogram pass of rounds >= 1 (only the instantiation that has such a pass: k_expand<false>).  Round 6, exact groups, ms per
+                         36 M (same box): 4: 2.594, 8: 2.637, 16: 2.80.  Registers of k_expand<false> at the 128-VGPR cap of 1024 threads: 4: 119 VGPRs, 8: 128, both without scratch memory; 16: 128 and
+                         292 bytes per lane.  (Round 6 blamed this pass for 104 bytes per lane with 4: those were values of the build phase hoisted out of its slot loop — see `t` there — and
+                         the round-0 instantiation, which has no pass, carried them too) */
 #endif
 // Rounds [firstRound, lastRound) of the cascade.  A launch that takes its batches one by one runs all rounds in ONE instance (0, MAX), the later rounds' histogram passes inside the
 // kernel behind grid barriers.  A launch that takes GROUPS runs round 0 in one instance (0, 1), the histogram pass of round 1 — a group's first cascades meet fresh territory with
 // four batches' worth of samples: four of nine groups of the terrain need it — as a kernel of its own over the whole chip (k_hist2), and round 1 and whatever follows in a second
 // instance (1, MAX): the two grid barriers and the 128-workgroup pass of the one-instance form cost ~100 us per second round, a kernel boundary costs nothing on one queue
 // (DESIGN §2) and an instance that finds nothing to do ~4 us.
+// ROUND0: the instance (0, 1) of a launch that takes groups, as an instantiation of its own — it never runs a histogram pass, never meets a grid barrier and never waits
+// for the other slots' decisions, and carries no code for any of them (the arguments firstRound / lastRound are ignored: 0 and 1).
+template <bool ROUND0>
 __global__ __launch_bounds__(ETPB) void k_expand(BuildArgs a, uint32_t ordinal, uint32_t firstRound, uint32_t lastRound) {
+	if (ROUND0) { firstRound = 0u; lastRound = 1u; }
 	Ctl* ctl = ctl_of(a);
 	BatchCtl* bc = batch_of(ctl, ordinal);
 	if (bc == nullptr || ctl->abortBatch) return;
 	if (firstRound != 0u && slots_in_use(bc) <= min(bc->slotsRound0, SLOT_CAP)) return;      // (round 0 queued nothing for a round 1)
 	__shared__ ExpandShared sh;
-	static_assert(sizeof(AllocRec) * ALLOC_LEAVES <= sizeof(uint32_t) * 2u * HT_CAP, "alloc_points' records in the hash table's words");
 	if (firstRound == 0u) {
 		// The chunks of the leaves that k_count found new samples for and that do not split (voxels.cu:485-538 allocatePointChunks; the nodes of
 		// a cascade get theirs below, from the workgroup that builds them): 64 leaves per list, list #k to the k-th workgroup FROM THE END —
 		// the first workgroups are the ones that build the cascades — beside the cascade and off k_insert's path.
 		const uint32_t numTouched = min(bc->numTouched, a.nodeCapacity);
-		const uint32_t allocBlocks = (numTouched + ALLOC_LEAVES - 1) / ALLOC_LEAVES;
+		const uint32_t allocBlocks = (numTouched + 63u) / 64u;
 		for (uint32_t blk = gridDim.x - 1u - blockIdx.x; blk < allocBlocks; blk += gridDim.x) {
 			__syncthreads();
-			alloc_points(a, ctl, bc, sh.alloc, sh.allocRec, at<const uint32_t>(a, a.offTouched), nullptr, blk * ALLOC_LEAVES, numTouched);
+			alloc_points(a, ctl, bc, sh.alloc, sh.allocRec, at<const uint32_t>(a, a.offTouched), nullptr, blk * 64u, numTouched, 1u);
 		}
 		__syncthreads();
 	}
@@ -414,7 +439,7 @@ __global__ __launch_bounds__(ETPB) void k_expand(BuildArgs a, uint32_t ordinal, 
 	for (uint32_t round = firstRound; round < min(lastRound, (uint32_t)SIMLOD_MAX_EXPAND_ROUNDS) && sb < se; ++round) {
 		uint64_t t0 = timer ? wall_ns() : 0, t1;
 		// -- H: histograms (this instance's first round: k_hist / k_hist2 have built them) --------------------------------------------------
-		const bool histHere = round > firstRound;
+		const bool histHere = !ROUND0 && round > firstRound;
 		if (histHere) {
 			for (uint32_t i = threadIdx.x; i < HT_CAP; i += ETPB) { sh.keys[i] = TBL_EMPTY; sh.vals[i] = 0u; }
 			__syncthreads();
@@ -472,7 +497,14 @@ __global__ __launch_bounds__(ETPB) void k_expand(BuildArgs a, uint32_t ordinal, 
 		// -- D: decide and build ---------------------------------------------------------------------------------------------
 		Phase pd(ctl, blockIdx.x == 0);      // (measure builds: slots 32..39 of Ctl.phaseNs — where workgroup 0's D phase goes; tools/probe.py)
 		for (uint32_t s = sb + blockIdx.x; s < se; s += gridDim.x) {
-			const uint32_t t = threadIdx.x;
+			uint32_t t = threadIdx.x;
+			// (opaque to the optimiser: what a thread derives from its number alone — its local node's octants, masks' bits, addresses — is the same for every slot
+			// of the loop, and hoisted in front of the loop it stayed live across the whole body: 18 values per lane went to scratch memory at the loop's head and
+			// came back where they were used, 104 bytes per lane.  Computed per slot they cost a few ALU operations and the kernel needs no scratch memory: 102 VGPRs
+			// in the round-0 instantiation, 119 in the other)
+			asm volatile("" : "+v"(t));
+			uint64_t before[6] = {0, 0, 0, 0, 0, 0};      // (measure builds: the phase sums as this slot found them)
+			if (pd.on) for (uint32_t k = 0; k < 6u; k++) before[k] = ctl->phaseNs[32u + k];
 			const uint32_t myBin = t < HIST_BINS ? hist_sum(hist, (uint64_t)s * HIST_BINS + t) : 0u;      // (needs the slot's number only: in flight beside its record)
 			const SlotRec rec = slots[s];
 			if (rec.node == NONE) { if (t == 0u) atomicAdd(&bc->decided, 1u); continue; }      // nothing could be reserved for this leaf (and it queues nothing)
@@ -636,30 +668,58 @@ __global__ __launch_bounds__(ETPB) void k_expand(BuildArgs a, uint32_t ordinal, 
 				__syncthreads();
 			}
 			pd.mark(33);      // exact groups: when every node split, chunks taken and returned per batch
-			if (t < LOCAL_NODES && exists(t)) {
-				const uint32_t level = l + local_depth(t);
-				if (splits(t)) sh.grid[t] = grid_for_split(a, bc);
-				else if (countOf(t) > SIMLOD_MAX_POINTS_PER_NODE && level < (uint32_t)SIMLOD_MAX_DEPTH && local_depth(t) == 3u) {
-					// still too full after three levels: a slot of its own for the next round (its eight children reserved now, no stored points)
-					uint32_t slot = 0, childBase = 0, dummy;
-					if (reserve(a, ctl, bc, 1u, 8u, 0u, slot, childBase, dummy)) {
-						for (uint32_t sd = 0; sd < (slot < HIST_SHARDED ? HIST_SHARDS : 1u); sd++) {
-							uint4* h = reinterpret_cast<uint4*>(hist + hist_word(slot << 9, sd));
-							for (uint32_t i = 0; i < HIST_BINS / 4; i++) h[i] = make_uint4(0, 0, 0, 0);
-						}
-						uint32_t born = NONE, cThen = 0;
-						if (acct) {      // (an exact group: the slot's histograms per batch; the batch in which this node splits — when its children are created)
-							uint4* hb = reinterpret_cast<uint4*>(at<uint32_t>(a, a.offHistB) + (uint64_t)slot * HIST_BINS * GBS);
-							for (uint32_t i = 0; i < HIST_BINS / 4u * GBS; i++) hb[i] = make_uint4(0, 0, 0, 0);
-							born = split_time(t, sh.splitAt[8u + ((t - 72u) >> 3)], false, cThen);
-						}
-						slots[slot] = SlotRec{indexOf(t), level, childBase, 0u, 0u, born, 0u, 0u};
-						sh.listed[t] = MAP_LISTED | (level << 16) | slot;
-					}
+			// ---- the slots of the next round and every grid this slot needs, in ONE go ----
+			// A great-grandchild that is still too full after three levels gets a slot of its own for the next round (its eight children reserved now, no stored
+			// points).  The root's cascade, or a flood into a fresh leaf, lists dozens of them: they are COUNTED (a prefix sum over the workgroup, local-node
+			// order), thread 0 reserves slots and children for all of them with one add on the reservation word — when that fails: as many as still fit, the
+			// first in local-node order, the others stay too full (deferred) —, and allocates the grids of the children and grandchildren that split here
+			// and of the nodes that got a slot (like a queued leaf's, before its children exist) with one counted allocation and one add on the clear list's
+			// length.  Then the WHOLE WORKGROUP zeroes the new slots' histograms (consecutive slots: consecutive words in every copy), a uint4 per thread and step.
+			// (Rounds 2-6: a returning atomic per listed node, and that one lane zeroed its slot's 4 copies + per-batch rows, 16 KB, word by word.)
+			const bool wants = t >= 72u && t < LOCAL_NODES && exists(t) && countOf(t) > SIMLOD_MAX_POINTS_PER_NODE && l + 3u < (uint32_t)SIMLOD_MAX_DEPTH;
+			uint32_t numWant;
+			const uint32_t wantRank = block_exclusive(wants ? 1u : 0u, sh.part, numWant);
+			const uint32_t n1 = (uint32_t)__popc(mask1), numSplit = n1 + (uint32_t)__popcll(mask2);
+			if (t == 0u) {
+				uint32_t granted = numWant, slot0 = 0, child0 = 0, dummy;
+				if (numWant != 0u && reserve_try(a, bc, numWant, 8u * numWant, 0u, slot0, child0, dummy) != 0u) {
+					const unsigned long long w = __hip_atomic_load(&bc->reserve, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+					const uint32_t slotsUsed = (uint32_t)(w >> RSV_SLOT_SHIFT), nodesUsed = (uint32_t)(w >> 32) & 0xfffffu;
+					const uint32_t fitSlots = SLOT_CAP > slotsUsed ? SLOT_CAP - slotsUsed : 0u, fitNodes = a.nodeCapacity > nodesUsed ? (a.nodeCapacity - nodesUsed) / 8u : 0u;
+					granted = min(numWant, min(fitSlots, fitNodes));
+					if (granted != 0u && reserve_try(a, bc, granted, 8u * granted, 0u, slot0, child0, dummy) != 0u) granted = 0u;
+					if (granted < numWant) raise(ctl, fitSlots <= fitNodes ? SIMLOD_ERR_SPILLING_OVERFLOW : SIMLOD_ERR_NODES_EXHAUSTED);      // (what the first node left out ran into)
 				}
+				uint32_t clearBase = 0;
+				uint8_t* mem = numSplit + granted != 0u ? grids_for_splits(a, bc, numSplit + granted, clearBase) : nullptr;
+				sh.nextGranted = granted; sh.nextSlot = slot0; sh.nextChild = child0; sh.gridMem = mem; sh.clearBase = clearBase;
 			}
 			__syncthreads();
-			// this slot's reservations for the next round are made (the workgroup's threads have their answers): say so — see "is there a next round" below
+			const uint32_t numNext = sh.nextGranted, slot0 = sh.nextSlot;
+			if (t < 72u && splits(t)) {
+				const uint32_t k = t < 8u ? (uint32_t)__popc(mask1 & ((1u << t) - 1u)) : n1 + (uint32_t)__popcll(mask2 & ((1ull << (t - 8u)) - 1ull));
+				SimlodOccupancyGrid* g = grid_of_many(sh.gridMem, k);
+				note_clear(a, bc, sh.clearBase + k, g);
+				sh.grid[t] = g;
+			} else if (wants && wantRank < numNext) {
+				const uint32_t slot = slot0 + wantRank, level = l + 3u;
+				note_clear(a, bc, sh.clearBase + numSplit + wantRank, grid_of_many(sh.gridMem, numSplit + wantRank));
+				uint32_t born = NONE, cThen = 0;
+				if (acct) born = split_time(t, sh.splitAt[8u + ((t - 72u) >> 3)], false, cThen);      // (an exact group: the batch in which this node splits — when its children are created)
+				slots[slot] = SlotRec{indexOf(t), level, sh.nextChild + 8u * wantRank, 0u, 0u, born, 0u, 0u};
+				sh.listed[t] = MAP_LISTED | (level << 16) | slot;
+			}
+			if (numNext != 0u) {
+				auto zero = [&](uint32_t* words, uint32_t count) {      // (every range starts at a slot's first bin: 2 KB aligned)
+					uint4* w = reinterpret_cast<uint4*>(words);
+					for (uint32_t i = t; i < count / 4u; i += ETPB) w[i] = make_uint4(0, 0, 0, 0);
+				};
+				zero(hist + (uint64_t)slot0 * HIST_BINS, numNext * HIST_BINS);
+				if (slot0 < HIST_SHARDED) for (uint32_t sd = 1; sd < HIST_SHARDS; sd++) zero(hist + hist_word(slot0 << 9, sd), (min(slot0 + numNext, HIST_SHARDED) - slot0) * HIST_BINS);
+				if (acct) zero(at<uint32_t>(a, a.offHistB) + (uint64_t)slot0 * HIST_BINS * GBS, numNext * HIST_BINS * GBS);      // (an exact group: the slots' histograms per batch)
+			}
+			__syncthreads();
+			// this slot's reservations for the next round are made (the workgroup's threads have their answers, the new slots' histograms are zero): say so — see "is there a next round" below
 			if (t == 0u) atomicAdd(&bc->decided, 1u);
 			pd.mark(34);      // grids, slots of the next round
 			if (t < LOCAL_NODES && exists(t)) {
@@ -700,9 +760,7 @@ __global__ __launch_bounds__(ETPB) void k_expand(BuildArgs a, uint32_t ordinal, 
 				c.visible = 0; c.isFiltered = 0; c.isLeaf = 1; c.isLarge = 0;
 				c.grid = split ? sh.grid[t] : nullptr; c.points = nullptr; c.voxelChunks = nullptr;
 				c.numVoxels = 0; c.numVoxelsStored = 0;
-				if (nextRound) {                                                   // (its grid: like a queued leaf's, before its children exist)
-					c.grid = grid_for_split(a, bc);
-				}
+				if (nextRound) c.grid = grid_of_many(sh.gridMem, numSplit + wantRank);                                 // (its grid: like a queued leaf's, before its children exist)
 				// parent, and the ancestor path: parent first, ..., then L, then L's own ancestors
 				const uint32_t parentLocal = depth == 1u ? NONE : depth == 2u ? (t - 8u) >> 3 : 8u + ((t - 72u) >> 3);
 				const uint32_t parentIdx = depth == 1u ? L : indexOf(parentLocal);
@@ -754,28 +812,52 @@ __global__ __launch_bounds__(ETPB) void k_expand(BuildArgs a, uint32_t ordinal, 
 				if (sh.accD[t] != 0u) atomicAdd(&bc->acctD[t], sh.accD[t]);
 				if (sh.accF[t] != 0u) atomicAdd(&bc->acctF[t], sh.accF[t]);
 			}
-			for (uint32_t j = 0; j < sh.numFill; j++) {                          // the top table's cells under the big new leaves, all threads
-				const uint4 f = sh.fill[j];
-				const uint32_t flevel = (f.x >> 19) & 31u, k = TOP_LEVEL - flevel, side = 1u << k;
+			if (sh.numFill != 0u) {
+				// the top table's cells under the big new leaves: ALL entries' cells as one index space over the workgroup (an entry has 64, 512 or 4096 cells: a wave's
+				// 64 cells lie in one entry, which it finds by bisection in the entries' prefix sums).  A root's cascade lists dozens of entries; one after the other,
+				// each was a loop of its own with most of the workgroup idle.
+				const uint32_t nf = sh.numFill;
+				uint32_t cells;
+				const uint32_t start = block_exclusive(t < nf ? 1u << (3u * (TOP_LEVEL - ((sh.fill[t].x >> 19) & 31u))) : 0u, sh.part, cells);
+				if (t < nf) sh.fillStart[t] = start;
+				__syncthreads();
 				uint32_t* top = at<uint32_t>(a, a.offTop);
-				for (uint32_t i = t; i < (1u << (3u * k)); i += ETPB) {
-					const uint32_t dx = i >> (2u * k), dy = (i >> k) & (side - 1u), dz = i & (side - 1u);
+				for (uint32_t i = t; i < cells; i += ETPB) {
+					uint32_t lo = 0, hi = nf;                                          // the last entry that starts at or before cell i
+					while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (sh.fillStart[mid] <= i) lo = mid; else hi = mid; }
+					const uint4 f = sh.fill[lo];
+					const uint32_t k = TOP_LEVEL - ((f.x >> 19) & 31u), side = 1u << k, c = i - sh.fillStart[lo];
+					const uint32_t dx = c >> (2u * k), dy = (c >> k) & (side - 1u), dz = c & (side - 1u);
 					top[(((f.y << k) + dx) << (2u * TOP_LEVEL)) | (((f.z << k) + dy) << TOP_LEVEL) | ((f.w << k) + dz)] = f.x;
 				}
 			}
 			pd.mark(36);      // top table
-			for (uint32_t first = 0; first < sh.numFresh; first += ALLOC_LEAVES) {
-				alloc_points(a, ctl, bc, sh.alloc, sh.allocRec, nullptr, sh.fresh, first, sh.numFresh);
-				__syncthreads();
+			{
+				const uint32_t waves = min((sh.numFresh + 63u) / 64u, ALLOC_WAVES);      // (one wave for the ordinary slot; a big cascade: all its leaves in one turn)
+				for (uint32_t first = 0; first < sh.numFresh; first += 64u * waves) {
+					alloc_points(a, ctl, bc, sh.alloc, sh.allocRec, nullptr, sh.fresh, first, sh.numFresh, waves);
+					__syncthreads();
+				}
 			}
 			pd.mark(37);      // the fresh leaves' chunks
-			if (pd.on) { ctl->phaseNs[38] += sh.numFresh; ctl->phaseNs[39] += 1; }
+			if (pd.on) {
+				ctl->phaseNs[38] += sh.numFresh; ctl->phaseNs[39] += 1;
+				// the SLOWEST slot this workgroup has built since the host cleared the clocks: its six phases (40..45), fresh leaves | top-table entries << 16 |
+				// next-round slots << 32 (46), their sum (47) — the mean above hides the few slots of a root's cascade or a flood into a fresh leaf
+				uint64_t sum = 0;
+				for (uint32_t k = 0; k < 6u; k++) sum += ctl->phaseNs[32u + k] - before[k];
+				if (sum > ctl->phaseNs[47]) {
+					for (uint32_t k = 0; k < 6u; k++) ctl->phaseNs[40u + k] = ctl->phaseNs[32u + k] - before[k];
+					ctl->phaseNs[46] = (uint64_t)sh.numFresh | ((uint64_t)sh.numFill << 16) | ((uint64_t)numNext << 32);
+					ctl->phaseNs[47] = sum;
+				}
+			}
 		}
 		// -- is there a next round?  Only a great-grandchild that is still over the limit makes one, and such a node has reserved its slot by now: once every slot of
 		//    this round is past its reservations (a counter; the workgroups without a slot wait here for the ones that have one — they are resident together, as for the
 		//    barrier below, and a slot's workgroup passes that point ~12 us into its build phase), the reservation word says.  (Rounds 2-6: every workgroup read every
 		//    histogram of the round up front to predict it — 10-14 us per round in front of the build phase.)
-		if (round + 1u >= lastRound) break;      // (the next round belongs to another instance: the kernel's end is the meeting point, the reservation word tells that instance)
+		if (ROUND0 || round + 1u >= lastRound) break;      // (the next round belongs to another instance: the kernel's end is the meeting point, the reservation word tells that instance)
 		__syncthreads();
 		if (threadIdx.x == 0) {
 			uint32_t good = 1;

@@ -77,12 +77,16 @@ for var in args.variants:
     if len(vt):
         print(f"    k_voxelize of the last launch, us from the first workgroup in: last piece done {np.mean(vt[:, 1] - vt[:, 0]) / 1e3:5.1f} (max {np.max(vt[:, 1] - vt[:, 0]) / 1e3:5.1f}), "
               f"last wave out {np.mean(vt[:, 2] - vt[:, 0]) / 1e3:5.1f} (max {np.max(vt[:, 2] - vt[:, 0]) / 1e3:5.1f}); batches {len(vt)}")
-    ph = dev.momentary[696:696 + 48 * 8].cpu().numpy().view(np.uint64).astype(np.float64)
+    ph = dev.momentary[696:696 + 48 * 8].cpu().numpy().view(np.uint64).astype(np.float64)      # (every value far below 2^53)
     f = lambda lo, n, cnt: " ".join(f"{ph[lo + i] / 1e3 / max(ph[cnt], 1):5.1f}" for i in range(n))
     print(f"    us per call, one workgroup: k_count [main loop, flush, queue_split] {f(0, 3, 3)} | k_hist [loop, flush] {f(4, 2, 6)} | k_insert wg0 [alloc, clear, count, reserve, wait, store] {f(8, 6, 14)}"
           f" | k_insert last wg {f(16, 6, 22)} | k_voxelize wg0 per piece [item+path+chunks, cubes+samples, level 1, levels 2+, write-back, reserve+chunks, store] {f(24, 7, 31)}", flush=True)
     if ph[39] > 0:
         print(f"    k_expand wg0 per slot us [hist+decide+reserve, acct timing, grids+next slots, nodes+paths+map, top table, fresh leaves' chunks] {f(32, 6, 39)}; fresh leaves per slot {ph[38] / ph[39]:5.1f}; slots (wg0) {int(ph[39])}", flush=True)
+    if ph[47] > 0:      # the slowest slot that workgroup built (Ctl.phaseNs[40..47], measure builds)
+        w = int(ph[46])
+        print(f"    k_expand wg0 SLOWEST slot us [same six phases] {' '.join(f'{ph[40 + i] / 1e3:5.1f}' for i in range(6))} = {ph[47] / 1e3:5.1f}; fresh leaves {w & 0xffff}, top-table entries {(w >> 16) & 0xffff}, "
+              f"next-round slots {w >> 32}", flush=True)
     for k, v in saved.items():
         if v is None:
             os.environ.pop(k, None)
