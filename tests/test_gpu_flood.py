@@ -22,16 +22,21 @@ from cases import H, W
 
 DENSE_CELLS, DENSE_POINTS = 72, 55_000
 SPARSE_CELLS, SPARSE_POINTS = 100, 300
+CONCENTRATED_POINTS = 52_000
 BATCH = 1_000_000
 G = 4
 ALL_TRUNK_NODES = ((1 << 64) - 1, (1 << 9) - 1)      # simlod_context_set_trunk_mask: bit 0 the root, 1 + c the level-1 nodes, 9 + c the level-2 nodes
 _CASE = {}
 
 
-def flood_case(seed=23):
-    """-> (points, box, batches, level-3 cells (x, y, z) that are dense, ... that are sparse)"""
-    if "case" in _CASE:
-        return _CASE["case"]
+def flood_case(dense=DENSE_CELLS, sparse=SPARSE_CELLS, concentrated=0, seed=23):
+    """-> (points, box, batches, level-3 cells (x, y, z) that are dense, ... that are sparse).  `dense` / `sparse`: how many of each, spread evenly over the 36
+    level-2 cells (at least one dense cell in each: every sparse cell's parent splits).  `concentrated`: in that many of the first dense cells CONCENTRATED_POINTS
+    of the cell's points lie in its level-6 subcell (3, 3, 3), at the same fractional offsets — the cell's cascade goes three levels further down."""
+    key = (dense, sparse, concentrated, seed)
+    if key in _CASE:
+        return _CASE[key]
+    ndense, nsparse_all = dense, sparse
     rs = np.random.RandomState(seed)
     l2 = [(x, y, z) for x in range(4) for y in range(4) for z in range(4) if not (x >= 2 and y >= 2 and z >= 2)]      # (the level-2 cells outside octant (1, 1, 1))
     assert len(l2) == 56
@@ -39,17 +44,24 @@ def flood_case(seed=23):
     dense, sparse = [], []
     for i, (x, y, z) in enumerate(l2):
         kids = rs.permutation(8)
-        nsparse = 3 if i < 28 else 2
-        for k in kids[:2]:
+        nd = ndense // 36 + (1 if i < ndense % 36 else 0)                  # (the default: 2)
+        nsparse = nsparse_all // 36 + (1 if i < nsparse_all % 36 else 0)      # (the default: 3 if i < 28 else 2)
+        assert nd >= 1 and nd + nsparse <= 8
+        for k in kids[:nd]:
             dense.append((2 * x + (k >> 2 & 1), 2 * y + (k >> 1 & 1), 2 * z + (k & 1)))
-        for k in kids[2:2 + nsparse]:
+        for k in kids[nd:nd + nsparse]:
             sparse.append((2 * x + (k >> 2 & 1), 2 * y + (k >> 1 & 1), 2 * z + (k & 1)))
-    assert len(dense) == DENSE_CELLS and len(sparse) == SPARSE_CELLS and len(set(dense + sparse)) == DENSE_CELLS + SPARSE_CELLS
+    assert len(dense) == ndense and len(sparse) == nsparse_all and len(set(dense + sparse)) == ndense + nsparse_all
     cells = np.concatenate([np.repeat(np.asarray(dense, dtype=np.float32), DENSE_POINTS, axis=0), np.repeat(np.asarray(sparse, dtype=np.float32), SPARSE_POINTS, axis=0)])
     n = len(cells)
-    assert n == 3_990_000
+    assert n == ndense * DENSE_POINTS + nsparse_all * SPARSE_POINTS and (G - 1) * BATCH < n <= G * BATCH
+    assert key != (DENSE_CELLS, SPARSE_CELLS, 0, 23) or n == 3_990_000
     v = (rs.random_sample((n, 3)) * 0.998 + 0.001).astype(np.float32)      # (strictly inside its cell: no sample on a cell's face)
     p = (cells + v) * np.float32(0.125)
+    assert concentrated <= ndense
+    for d in range(concentrated):                     # (the dense cells' points come first, cell by cell)
+        s = slice(d * DENSE_POINTS, d * DENSE_POINTS + CONCENTRATED_POINTS)
+        p[s] = (cells[s] + (np.float32(3.0) + v[s]) * np.float32(0.125)) * np.float32(0.125)
     c = np.floor(v * np.float32(255.0)).astype(np.uint32)
     pts = np.empty(n, dtype=abi.point_dtype)
     pts["x"], pts["y"], pts["z"] = p[:, 0], p[:, 1], p[:, 2]
@@ -57,8 +69,8 @@ def flood_case(seed=23):
     pts = pts[rs.permutation(n)]                      # every batch of the group holds a quarter of every cell
     batches = [pts[i:i + BATCH] for i in range(0, n, BATCH)]
     assert len(batches) == G
-    _CASE["case"] = (pts, np.array([1, 1, 1], dtype=np.float32), batches, dense, sparse)
-    return _CASE["case"]
+    _CASE[key] = (pts, np.array([1, 1, 1], dtype=np.float32), batches, dense, sparse)
+    return _CASE[key]
 
 
 def _oracle(u, batches, mask):
