@@ -87,7 +87,7 @@ bool layout_construct(BuildArgs& a, uint64_t capacity, bool coalesce, uint32_t g
 	a.offNodeDir = off;  off += align_up((uint64_t)a.nodeCapacity * sizeof(NodeDir), 256);
 	a.offChunkDir = off; off += align_up(2ull * a.dirCap * 8, 256);            // (two copies, by batch parity)
 	a.offLeafChunks = off; off += (uint64_t)a.nodeCapacity * LEAF_ROW_BYTES;
-	a.offPaths = off; off += align_up((uint64_t)a.nodeCapacity * PATH_WORDS * 8, 256);
+	a.offPaths = off; off += align_up((uint64_t)a.nodeCapacity * PATH_ROW * 8, 256);      // (compact rows: 96 bytes per node instead of 168 — what lets groups of five into the reference host's 300 MB)
 	a.offTop = off;   off += align_up((uint64_t)TOP_CELLS * 4, 256);
 	a.offKid = off;   off += align_up((uint64_t)a.nodeCapacity * 4, 256);
 	a.voxItemCap = min(a.nodeCapacity + 2u * VOX_BIG_ITEMS, 1u << 20);         // VOX_BIG_ITEMS pieces + small items: a leaf has one more than its new samples / 128, and 65 536 x 128 = 8 M samples

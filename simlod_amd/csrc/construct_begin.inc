@@ -86,19 +86,20 @@ __device__ void rebuild_side_tables(const BuildArgs& a, bool irregular) {      /
 				v = v->next;
 			}
 		}
-		// the ancestors, parent first, zero-terminated
-		unsigned long long* rec = at<unsigned long long>(a, a.offPaths) + i * PATH_WORDS;
+		// the ancestors, parent first: the first PATH_ROW of them, zero-terminated when there are fewer (the others stand in the rows of the node's
+		// PATH_ROW-th ancestor and of that one's, which their own threads write: path_far)
+		unsigned long long* rec = at<unsigned long long>(a, a.offPaths) + i * PATH_ROW;
 		const uint32_t L = min(n->level, PATH_WORDS - 1u), s = (uint32_t)SIMLOD_MAX_DEPTH - L;
 		const uint32_t X = n->X << s, Y = n->Y << s, Z = n->Z << s;        // (child_index() takes coordinates at full depth)
 		uint32_t cur = 0, l = 0;
 		for (; l < L; l++) {
 			const SimlodNode* anc = a.nodes + cur;
-			rec[L - 1u - l] = path_pack(a.pers, cur, anc->level, anc->grid);
+			if (L - 1u - l < PATH_ROW) rec[L - 1u - l] = path_pack(a.pers, cur, anc->level, anc->grid);
 			const SimlodNode* c = anc->children[child_index(X, Y, Z, (int)l)];
 			if (c == nullptr) break;                                         // (an image whose node is not where its coordinates say: entries below stay as they are, the list ends)
 			cur = (uint32_t)(c - a.nodes);
 		}
-		rec[L] = 0;
+		if (L < PATH_ROW) rec[L] = 0;
 	}
 }
 

@@ -519,7 +519,11 @@ __global__ __launch_bounds__(ETPB) void k_expand(BuildArgs a, uint32_t ordinal, 
 			}
 			if (t < HIST_BINS) sh.bins[t] = binTotal;
 			if (t < SIMLOD_MAX_BATCHES_PER_LAUNCH) { sh.accD[t] = 0; sh.accF[t] = 0; }
-			if (t < PATH_WORDS) sh.pathL[t] = t + 1 < PATH_WORDS ? paths[(uint64_t)L * PATH_WORDS + t] : 0ull;
+			if (t < PATH_WORDS) {      // the slot node's WHOLE path: its row, and for a node below level PATH_ROW the entries its row continues in (path_far)
+				unsigned long long e = t < PATH_ROW ? paths[(uint64_t)L * PATH_ROW + t] : 0ull;
+				if (t >= PATH_ROW && t < l) e = path_far(paths, L, t, a.nodeCapacity);
+				sh.pathL[t] = e;
+			}
 			// the slot node's coordinates, name and grid: one round trip here, beside its path, instead of one in every phase that wants them
 			if (t == 64u) { const SimlodNode* nl = a.nodes + L; sh.LX = nl->X; sh.LY = nl->Y; sh.LZ = nl->Z; sh.gridL = nl->grid; }
 			if (t >= 96u && t < 116u) sh.nameL[t - 96u] = a.nodes[L].name[t - 96u];
@@ -765,13 +769,14 @@ __global__ __launch_bounds__(ETPB) void k_expand(BuildArgs a, uint32_t ordinal, 
 				const uint32_t parentLocal = depth == 1u ? NONE : depth == 2u ? (t - 8u) >> 3 : 8u + ((t - 72u) >> 3);
 				const uint32_t parentIdx = depth == 1u ? L : indexOf(parentLocal);
 				parentOf[idx] = parentIdx;
-				unsigned long long* mine = paths + (uint64_t)idx * PATH_WORDS;
+				// (its row: the first PATH_ROW of them, zero-terminated when there are fewer — the others are found through the row of the last one: path_far)
+				unsigned long long* mine = paths + (uint64_t)idx * PATH_ROW;
 				uint32_t w = 0;
 				if (depth >= 3u) { const uint32_t g = 8u + ((t - 72u) >> 3); mine[w++] = path_pack(a.pers, indexOf(g), l + 2u, sh.grid[g]); }
 				if (depth >= 2u) { const uint32_t ch = depth == 2u ? (t - 8u) >> 3 : (t - 72u) >> 6; mine[w++] = path_pack(a.pers, indexOf(ch), l + 1u, sh.grid[ch]); }
 				mine[w++] = path_pack(a.pers, L, l, sh.gridL);
-				for (uint32_t k = 0; w < PATH_WORDS; k++) {
-					const unsigned long long e = w + 1 < PATH_WORDS ? sh.pathL[k] : 0ull;
+				for (uint32_t k = 0; w < PATH_ROW; k++) {
+					const unsigned long long e = sh.pathL[k];       // (pathL[20] is zero: k < PATH_ROW <= 20)
 					mine[w++] = e;
 					if (e == 0ull) break;
 				}

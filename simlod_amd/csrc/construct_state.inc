@@ -179,12 +179,22 @@ static constexpr uint32_t LEAF_SLOTS = LEAF_ROW_SLOTS;      // (rows are packed:
 static constexpr uint32_t TABLE_MAGIC = 0x51ab1e05u;
 static_assert(LEAF_SLOTS <= 64, "queue_split hands a leaf's chunks out one per lane");
 
-// Ancestor paths: PATH_WORDS 64-bit entries per node, entry k = the k-th ancestor (parent first), zero-terminated.
+// Ancestor paths: a row of PATH_DIRECT 64-bit entries per node, entry k = the k-th ancestor (parent first), zero-terminated when the node has
+// fewer than PATH_DIRECT ancestors.
 // An entry packs everything `sample` and `insert` need to know about that ancestor — its occupancy grid (offset into the
 // persistent buffer), level and node index — so a sample reads its whole root path with independent loads instead of chasing
 // parent -> node -> grid pointers level by level.
-// Rebuilt for every node at the start of a launch (k_paths), extended for the eight children at a split (k_expand).
-static constexpr uint32_t PATH_WORDS = SIMLOD_MAX_DEPTH + 1;
+// A node deeper than PATH_DIRECT levels continues in the row of its PATH_DIRECT-th ancestor (the node its row's last entry names), whose row
+// holds that ancestor's ancestors, and so on: entry k >= PATH_DIRECT of a node is entry k - PATH_DIRECT of that ancestor (path_far) — one more
+// dependent load per PATH_DIRECT levels, paid only by leaves below level PATH_DIRECT.  (Rounds 1-7: a row held all 20 possible ancestors,
+// 168 bytes per node; the terrain's leaves lie at levels 5-7, a hotspot's around 10 — more than half of every row was never read.)
+// Rebuilt for every node when the side tables are stale (rebuild_side_tables), extended for the eight children at a split (k_expand).
+#ifndef PATH_DIRECT
+#define PATH_DIRECT 12      /* `make variant DEFS=-DPATH_DIRECT=...` */
+#endif
+static constexpr uint32_t PATH_WORDS = SIMLOD_MAX_DEPTH + 1;      // a whole path in LDS: up to 20 ancestors and the terminator
+static constexpr uint32_t PATH_ROW = PATH_DIRECT;                 // entries of a node's row in the table
+static_assert(PATH_ROW >= 3u && PATH_ROW <= (uint32_t)SIMLOD_MAX_DEPTH, "k_expand writes up to three entries of a new node's row before it copies the slot node's path");
 static constexpr unsigned long long PATH_VALID = 1ull << 63;
 
 __device__ __forceinline__ unsigned long long path_pack(const uint8_t* pers, uint32_t nodeIdx, uint32_t level, const SimlodOccupancyGrid* grid) {
@@ -195,6 +205,16 @@ __device__ __forceinline__ uint32_t path_node(unsigned long long e) { return (ui
 __device__ __forceinline__ uint32_t path_level(unsigned long long e) { return (uint32_t)(e >> 36) & 31u; }
 __device__ __forceinline__ SimlodOccupancyGrid* path_grid(uint8_t* pers, unsigned long long e) {
 	return reinterpret_cast<SimlodOccupancyGrid*>(pers + ((e & 0xfffffffffull) << 4));
+}
+// entry k >= PATH_ROW of `node`'s path, for a node that has more than k ancestors (so every row on the way is full): through the continuation rows.
+// (A last entry that names no node of this table — an image whose node is not where its level says — ends the path.)
+__device__ inline unsigned long long path_far(const unsigned long long* paths, uint32_t node, uint32_t k, uint32_t nodeCapacity) {
+	while (k >= PATH_ROW) {
+		const unsigned long long last = paths[(uint64_t)node * PATH_ROW + (PATH_ROW - 1u)];
+		node = path_node(last); k -= PATH_ROW;
+		if (last == 0ull || node >= nodeCapacity) return 0ull;
+	}
+	return paths[(uint64_t)node * PATH_ROW + k];
 }
 
 // Top table: for every cell of the 32^3 grid of level 5, the deepest node at level <= 5 that contains it, as node | level << 19 — where k_count's
@@ -364,7 +384,8 @@ struct Samples {
 	}
 };
 
-// what the stamp remembers of the momentary buffer's layout: side tables of another node capacity / buffer size / group size are not these
+// what the stamp remembers of the momentary buffer's layout: side tables of another node capacity / buffer size / group size / path row format are not these
+// (rows of PATH_ROW entries with continuation: a stamp left by a build with whole-path rows, which had no such term, or with another row length does not match)
 __host__ __device__ inline uint64_t layout_signature(const BuildArgs& a) {
-	return a.scratchBytes ^ ((uint64_t)a.nodeCapacity << 40) ^ ((uint64_t)a.groupMax << 59) ^ (a.offSpilled * 0x9E3779B97F4A7C15ull);
+	return a.scratchBytes ^ ((uint64_t)a.nodeCapacity << 40) ^ ((uint64_t)a.groupMax << 59) ^ (a.offSpilled * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)PATH_ROW * 0xC2B2AE3D27D4EB4Full);
 }

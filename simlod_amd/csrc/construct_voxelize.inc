@@ -212,7 +212,12 @@ __device__ __forceinline__ void voxelize_small(const BuildArgs& a, Ctl* ctl, Bat
 			// the leaf's path, one entry per lane (entry d - 1 = ancestor d; a root that is still a leaf samples itself, voxels.cu:449-463)
 			mine[u] = 0ull;
 			if (leafIdx == 0u) { SimlodOccupancyGrid* g = a.nodes[0].grid; if (lane == 0u && g != nullptr) mine[u] = path_pack(a.pers, 0u, 0u, g); }
-			else if (lane < PATH_WORDS - 1) mine[u] = (at<const unsigned long long>(a, a.offPaths) + (uint64_t)leafIdx * PATH_WORDS)[lane];
+			else {
+				const unsigned long long* paths = at<const unsigned long long>(a, a.offPaths);
+				if (lane < PATH_ROW) mine[u] = paths[(uint64_t)leafIdx * PATH_ROW + lane];
+				// (a leaf below level PATH_ROW: the entries its row continues in — the item says so, the same for the whole wave)
+				if ((it[u].leaf >> 24) > PATH_ROW && lane >= PATH_ROW && lane < (it[u].leaf >> 24)) mine[u] = path_far(paths, leafIdx, lane, a.nodeCapacity);
+			}
 		}
 #pragma unroll
 		for (uint32_t u = 0; u < U; u++) {
@@ -328,12 +333,14 @@ __global__ __launch_bounds__(VTPB) void k_voxelize(BuildArgs a, uint32_t ordinal
 		it.leaf &= 0xffffffu;
 		if (it.leaf == 0u) continue;                              // (the root as a leaf: voxroot_pieces)
 		const uint32_t LX = a.nodes[it.leaf].X, LY = a.nodes[it.leaf].Y, LZ = a.nodes[it.leaf].Z;      // (in flight beside the leaf's path)
-		const unsigned long long* rec = at<const unsigned long long>(a, a.offPaths) + (uint64_t)it.leaf * PATH_WORDS;
+		const unsigned long long* rec = at<const unsigned long long>(a, a.offPaths) + (uint64_t)it.leaf * PATH_ROW;
 		__syncthreads();                                       // the previous item's LDS state is no longer read
 		if (threadIdx.x < PATH_WORDS) {
 			// ancestor d (1 = parent) is anc[d - 1].  (A root that is still a leaf samples ITSELF, voxels.cu:449-463 — the whole octree holds fewer
-			// than 50 000 points —: voxroot_pieces, skipped here.)
-			const unsigned long long e = threadIdx.x < PATH_WORDS - 1 ? rec[threadIdx.x] : 0ull;
+			// than 50 000 points —: voxroot_pieces, skipped here.)  A leaf below level PATH_ROW finds the ancestors beyond its row through path_far:
+			// the item knows the level, so every other leaf takes no branch that depends on a load.
+			unsigned long long e = threadIdx.x < PATH_ROW ? rec[threadIdx.x] : 0ull;
+			if (leafLevel > PATH_ROW && threadIdx.x >= PATH_ROW && threadIdx.x < leafLevel) e = path_far(at<const unsigned long long>(a, a.offPaths), it.leaf, threadIdx.x, a.nodeCapacity);
 			sh.anc[threadIdx.x] = e; sh.cnt[threadIdx.x] = 0; sh.hiOcc[threadIdx.x] = 0; sh.hiFresh[threadIdx.x] = 0; sh.rank[threadIdx.x] = 0;
 			if (threadIdx.x < 8u) sh.listCount[threadIdx.x] = 0;
 		}
