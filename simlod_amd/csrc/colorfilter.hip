@@ -163,9 +163,7 @@ int launch_colorfilter(Context& ctx, const SimlodUniforms* u, uint32_t* buffer, 
 	FilterArgs a{};
 	a.mom = reinterpret_cast<uint8_t*>(buffer); a.nodes = nodes; a.stats = stats; a.numNodesPtr = numNodes;
 	a.nodeCapacity = ctx.nodeCapacity.load();
-	const float bx = u->boxMax.x - u->boxMin.x, by = u->boxMax.y - u->boxMin.y, bz = u->boxMax.z - u->boxMin.z;
-	a.cubeSize = fmaxf(fmaxf(bx, by), bz);
-	a.minx = u->boxMin.x; a.miny = u->boxMin.y; a.minz = u->boxMin.z;
+	octree_box(u, a.cubeSize, a.minx, a.miny, a.minz);
 	a.octreeSizeX = (a.minx + a.cubeSize) - a.minx; a.octreeSizeY = (a.miny + a.cubeSize) - a.miny; a.octreeSizeZ = (a.minz + a.cubeSize) - a.minz;
 	a.offHeights = 4096;
 	a.offGrids = (a.offHeights + a.nodeCapacity + 255) / 256 * 256;

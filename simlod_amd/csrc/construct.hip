@@ -165,9 +165,7 @@ int launch_construct(Context& ctx, const SimlodUniforms* u, SimlodPoint* points,
 	BuildArgs a{};
 	a.ring = points; a.mom = reinterpret_cast<uint8_t*>(buffer); a.pers = pers; a.nodes = nodes; a.stats = stats;
 	a.frameStart = frameStart; a.numBatchesUploaded = numBatchesUploaded; a.batchSizes = batchSizes;
-	const float bx = u->boxMax.x - u->boxMin.x, by = u->boxMax.y - u->boxMin.y, bz = u->boxMax.z - u->boxMin.z;
-	a.size = fmaxf(fmaxf(bx, by), bz);                                         // voxels.cu:860-863
-	a.minx = u->boxMin.x; a.miny = u->boxMin.y; a.minz = u->boxMin.z;
+	octree_box(u, a.size, a.minx, a.miny, a.minz);                             // voxels.cu:860-863
 	a.persCapacity = u->persistentBufferCapacity;
 	a.frameCounter = u->frameCounter;
 	a.nodeCapacity = ctx.nodeCapacity.load();

@@ -1586,9 +1586,7 @@ int launch_render(Context& ctx, uint32_t* buffer, const SimlodUniforms* u, Simlo
 	a.W = (int)u->width; a.H = (int)u->height;
 	if (a.W <= 0 || a.H <= 0) return (int)hipErrorInvalidValue;
 	a.numPixels = (uint32_t)a.W * (uint32_t)a.H;
-	const float bx = u->boxMax.x - u->boxMin.x, by = u->boxMax.y - u->boxMin.y, bz = u->boxMax.z - u->boxMin.z;
-	a.cubeSize = fmaxf(fmaxf(bx, by), bz);                               // render.cu:1135-1137
-	a.minx = u->boxMin.x; a.miny = u->boxMin.y; a.minz = u->boxMin.z;
+	octree_box(u, a.cubeSize, a.minx, a.miny, a.minz);                   // render.cu:1135-1137
 	a.minNodeSize = u->minNodeSize;
 	a.pointSize = u->pointSize;
 	a.nodeCapacity = ctx.nodeCapacity.load();

@@ -56,6 +56,13 @@ struct LeafTableRef {
 __host__ __device__ inline uint64_t table_signature(const SimlodStats* s) {
 	return ((uint64_t)s->numNodes | (uint64_t)s->numPoints << 32) ^ (s->allocatedBytes_persistent * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)s->numVoxels << 20);
 }
+// The octree's cube as every launcher derives it from the uniforms (voxels.cu:860-863, render.cu:1135-1137): the box's longest edge, from its
+// minimum corner.
+inline void octree_box(const SimlodUniforms* u, float& size, float& minx, float& miny, float& minz) {
+	const float bx = u->boxMax.x - u->boxMin.x, by = u->boxMax.y - u->boxMin.y, bz = u->boxMax.z - u->boxMin.z;
+	size = fmaxf(fmaxf(bx, by), bz);
+	minx = u->boxMin.x; miny = u->boxMin.y; minz = u->boxMin.z;
+}
 // ---- per-octree state (include/simlod_hip.h, simlod_context_*) -----------------------------------------------------------------------------
 // Everything the library keeps between launches belongs to a context: the ingest mode, the node capacity, the host's batch limit, the
 // tuning knobs (read from the environment ONCE, when the context is made; simlod_context_set_knob overrides one), the second stream and
@@ -79,7 +86,7 @@ struct FrameFeedback { const void* buffer; volatile uint32_t* seen; bool bins; u
 struct SideStream;                                           // construct.hip: the second stream of kernel_construct and its events
 void destroy_side_stream(SideStream* s);
 
-// What the host knows of a node array beyond the builder's tables (export.hip): a kernel_render ran on it since its last reset, construct or
+// What the host knows of a node array beyond the builder's tables (export.hip, the launchers): a kernel_render ran on it since its last reset, construct or
 // import (SIMLOD_EXPORT_VISIBLE reads the visible / isLarge bytes that frame wrote) | it holds an imported octree (no grids, no builder state:
 // kernel_construct and the colour filter refuse it until the next reset).  Keyed by node array, not by context: two arrays may share one.
 struct ArrayState { const void* nodes; bool rendered, imported; };

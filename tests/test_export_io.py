@@ -39,6 +39,31 @@ def test_export_symbols_exported(built_libs):
     assert L.simlod_export_buffer_min_bytes(100, 1_000_000) >= a + 1000 * 32 and L.simlod_export_buffer_min_bytes(200, 0) > a
 
 
+def test_scratch_bounds_are_exactly_the_layouts(built_libs):
+    """The three scratch bounds are a contract with callers: each is pinned to the layout it states, region by region (csrc/export_common.inc
+    Layout, export_region.inc QueryLayout, export_rays.inc RayLayout): a 256-byte header (two for the rays), every array rounded up to 256
+    bytes, then 32 bytes per chunk item, per pair, and 16 per further thousand candidates."""
+    from simlod_amd import runtime
+    L = runtime.lib()
+
+    def a(v):
+        return (v + 255) & ~255
+
+    def items(cap, bound):
+        return (bound // 1000 + cap + 1) * 32
+
+    for cap in (0, 1, 64, 100, 4425):
+        q, f = a(4 * cap), a(4 * cap + 4)
+        for bound in (0, 999, 1000, 36_000_000):
+            assert L.simlod_export_buffer_min_bytes(cap, bound) == 256 + 2 * q + f + items(cap, bound), (cap, bound)
+            assert L.simlod_query_buffer_min_bytes(cap, bound) == 256 + 3 * q + f + items(cap, bound), (cap, bound)
+            for rays in (1, 64, 4096):
+                for pairs, cand in ((0, 0), (3, 68_019)):
+                    want = (512 + 5 * q + f + a(40 * cap) + a(8 * cap + 8) + a(4 * rays) + a(8 * rays + 8) + items(cap, bound)
+                            + 32 * pairs + 16 * (cand // 1000))
+                    assert L.simlod_rays_buffer_min_bytes(cap, bound, rays, pairs, cand) == want, (cap, bound, rays, pairs, cand)
+
+
 def _table(spec):
     """A breadth-first table from {octant: subtree} dicts (the root is `spec`); every node gets (level + 1) * 3 samples."""
     rows, queue = [], [(spec, abi.EXPORT_NONE, 0, 0, 0, 0)]

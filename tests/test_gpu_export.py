@@ -92,6 +92,26 @@ def test_export_all_matches_host(built_libs, name):
     assert len(s) == int(st["numPoints"]) + int(st["numVoxels"]) and len(t) == int(st["numNodes"])
 
 
+def test_lists_longer_than_a_chunk_table_row(built_libs):
+    """The voxel lists of a dense cube's upper nodes hold more than 50 chunks, a row of the builder's chunk table: k_x_dir takes what the row
+    gives and follows `next` behind it, and the result is the host walk's, as it is with the table dropped."""
+    pts, box = synthetic.uniform_cube(600_000, seed=9)
+    dev = _device()
+    u = dev.uniforms(W, H, cases._cam(box), box)
+    dev.reset(u)
+    for i in range(0, len(pts), 200_000):
+        if dev.uploaded_host - dev.processed() >= dev.ring_slots:
+            dev.drain(u)
+        dev.upload(pts[i:i + 200_000])
+    dev.drain(u)
+    assert int(dev.read_stats()["dbg"]) == 0
+    t, s = _host_export(dev)
+    assert int(t["numSamples"].max()) > 50 * abi.POINTS_PER_CHUNK
+    _assert_export(dev.export_octree(u), t, s, "dense cube (chunk table)")
+    dev.L.simlod_octree_image_replaced(dev._p(dev.nodes))
+    _assert_export(dev.export_octree(u), t, s, "dense cube (walk)")
+
+
 def test_export_cut_levels(built_libs):
     dev, u, pts = _build("hotspot_150k")
     deepest = int(_host_export(dev)[0]["level"].max())

@@ -279,8 +279,8 @@ def test_pair_counts(octrees):
 
 
 def test_sample_test_kernel_uses_no_scratch():
-    """`make resource-usage` on export.hip: the ray kernels keep everything in registers and LDS (a spill in the hot loop of k_r_test would
-    halve it)."""
+    """`make resource-usage` on export.hip (the ray kernels are its export_rays.inc): they keep everything in registers and LDS (a spill in
+    the hot loop of k_r_test would halve it)."""
     import shutil
     import subprocess
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
