@@ -69,7 +69,7 @@ int simlod_context_set_ingest_mode(SimlodContext* ctx, uint32_t mode);
 int simlod_context_set_construct_batch_limit(SimlodContext* ctx, uint32_t maxBatches);
 /* "That many ring batches are pending right now" (uploaded and not ingested, not counting what launches already enqueued will take): for the NEXT
  * kernel_construct launch of the context only — it enqueues kernels for that many batches (0: none, an idle frame), whatever the library would have
- * guessed.  Optional: hosts whose upload-counter writes reach simlod_upload_counter_written (shim/cuda.h does that for the reference's) need not call it. */
+ * guessed.  The hint is consumed by the context's next launch, whichever octree that launch is for.  Optional: hosts whose upload-counter writes reach simlod_upload_counter_written (shim/cuda.h does that for the reference's) need not call it. */
 int simlod_context_hint_pending_batches(SimlodContext* ctx, uint32_t pending);
 /* The host has enqueued a write of `value` to the 4-byte upload counter at `numBatchesUploaded` (main_progressive_octree.cpp:1047-1050:
  * cuMemsetD32Async(cptr_numBatchesUploaded, batchStreamUploadIndex + 1, 1, stream_upload)).  kernel_construct reads the counter on the device when it

@@ -189,13 +189,13 @@ int launch_construct(Context& ctx, const SimlodUniforms* u, SimlodPoint* points,
 	const DeviceInfo& dev = device_info();
 
 	note_upload_counter(numBatchesUploaded, 0u, false, true);
-	const LaunchPlan plan = launch_plan(ctx, stats, numBatchesUploaded);
+	const LaunchPlan plan = launch_plan(ctx, nodes, numBatchesUploaded);
 	const uint32_t limit = plan.batches;
 	// batches per group this launch aims at: the layout's, or — exact mode, when the latest launch reported that groups of several batches are out of the
 	// question for now (LaunchPlan::mayGroup) — one, with one group of kernels per batch
 	const uint32_t take = a.acct != 0u && !plan.mayGroup ? 1u : a.groupMax;
 	// (one workgroup does the launch's bookkeeping; all of them restore the side tables when the stamp is stale: the first launch of an octree, as a rule)
-	SIMLOD_LAUNCH(k_begin, dim3(fits ? dev.numCUs * 2 : 1u), dim3(TPB), stream, a, fits ? 0u : 1u, limit, ((uint32_t)ctx.tune(KNOB_DEBUG_FORCE_BARRIER_TIMEOUT, 0) & 1u) | (ctx.tune(KNOB_DEBUG_VOXELIZE_CLOCK, 0) != 0 ? 2u : 0u) | (ctx.sideTablesStale.exchange(false) ? 4u : 0u) | (ctx.tune(KNOB_DEBUG_IRREGULAR_CHILDREN, 0) != 0 ? 8u : 0u) | (((uint32_t)ctx.tune(KNOB_DEBUG_PHASE_WG, 0) & 0xffffu) << 8),
+	SIMLOD_LAUNCH(k_begin, dim3(fits ? dev.numCUs * 2 : 1u), dim3(TPB), stream, a, fits ? 0u : 1u, limit, ((uint32_t)ctx.tune(KNOB_DEBUG_FORCE_BARRIER_TIMEOUT, 0) & 1u) | (ctx.tune(KNOB_DEBUG_VOXELIZE_CLOCK, 0) != 0 ? 2u : 0u) | (plan.sideTablesStale ? 4u : 0u) | (ctx.tune(KNOB_DEBUG_IRREGULAR_CHILDREN, 0) != 0 ? 8u : 0u) | (((uint32_t)ctx.tune(KNOB_DEBUG_PHASE_WG, 0) & 0xffffu) << 8),
 	              (uint32_t)std::max(0, ctx.tune(KNOB_DEBUG_BUDGET_US, 0)), take);
 	if (fits) {
 		const uint32_t gridPoints = dev.numCUs * (uint32_t)ctx.tune(KNOB_GRID_MULT, 8);
@@ -244,30 +244,18 @@ int launch_construct(Context& ctx, const SimlodUniforms* u, SimlodPoint* points,
 			SIMLOD_LAUNCH(k_hist, dim3(gridPoints), dim3(TPB), stream, a, b);
 			// (with two streams the kernels the other stream waits for carry their event as the launch's stop event: it is signalled by the
 			// kernel's own completion, where hipEventRecord puts a marker of its own behind the kernel — 3.93 -> 3.85 ms per ingest)
-			if (side != nullptr) {
-				if (!single) {      // groups: round 0, the next round's histogram pass over the whole chip, then round 1 and whatever follows (k_expand's comment)
-					SIMLOD_LAUNCH(k_expand<true>, dim3(expandWgs), dim3(ETPB), stream, a, b, 0u, 1u);
-					SIMLOD_LAUNCH(k_hist2, dim3(gridPoints), dim3(TPB), stream, a, b);
-				}
-				const bool gated = expand_gate_enter(ctx, stream);
-				SIMLOD_LAUNCH_STOP(k_expand<false>, dim3(expandWgs), dim3(ETPB), stream, side->expanded[b], a, b, single ? 0u : 1u, (uint32_t)SIMLOD_MAX_EXPAND_ROUNDS);
-				expand_gate_leave(ctx, stream, side->expanded[b], gated);
-				{ const hipError_t e = hipStreamWaitEvent(back, side->expanded[b], 0); if (e != hipSuccess) return fail(e); }
-				if (!single && a.acct != 0u) SIMLOD_LAUNCH(k_rootpre, dim3(1), dim3(1024), back, a, b);
-				if (single) SIMLOD_LAUNCH_STOP(k_insert<true>, dim3(gridPoints), dim3(TPB), back, side->inserted[b], a, b);   // grid clears, points, end-of-batch bookkeeping, the previous group's voxel lists
-				else SIMLOD_LAUNCH_STOP(k_insert<false>, dim3(gridPoints), dim3(TPB), back, side->inserted[b], a, b);
-			} else {
-				if (!single) {
-					SIMLOD_LAUNCH(k_expand<true>, dim3(expandWgs), dim3(ETPB), stream, a, b, 0u, 1u);
-					SIMLOD_LAUNCH(k_hist2, dim3(gridPoints), dim3(TPB), stream, a, b);
-				}
-				const bool gated = expand_gate_enter(ctx, stream);
-				SIMLOD_LAUNCH(k_expand<false>, dim3(expandWgs), dim3(ETPB), stream, a, b, single ? 0u : 1u, (uint32_t)SIMLOD_MAX_EXPAND_ROUNDS);
-				expand_gate_leave(ctx, stream, nullptr, gated);
-				if (!single && a.acct != 0u) SIMLOD_LAUNCH(k_rootpre, dim3(1), dim3(1024), back, a, b);
-				if (single) SIMLOD_LAUNCH(k_insert<true>, dim3(gridPoints), dim3(TPB), back, a, b);
-				else SIMLOD_LAUNCH(k_insert<false>, dim3(gridPoints), dim3(TPB), back, a, b);
+			if (!single) {      // groups: round 0, the next round's histogram pass over the whole chip, then round 1 and whatever follows (k_expand's comment)
+				SIMLOD_LAUNCH(k_expand<true>, dim3(expandWgs), dim3(ETPB), stream, a, b, 0u, 1u);
+				SIMLOD_LAUNCH(k_hist2, dim3(gridPoints), dim3(TPB), stream, a, b);
 			}
+			const hipEvent_t expanded = side != nullptr ? side->expanded[b] : nullptr, inserted = side != nullptr ? side->inserted[b] : nullptr;
+			const bool gated = expand_gate_enter(ctx, stream);
+			SIMLOD_LAUNCH_STOP(k_expand<false>, dim3(expandWgs), dim3(ETPB), stream, expanded, a, b, single ? 0u : 1u, (uint32_t)SIMLOD_MAX_EXPAND_ROUNDS);
+			expand_gate_leave(ctx, stream, expanded, gated);
+			if (side != nullptr) { const hipError_t e = hipStreamWaitEvent(back, expanded, 0); if (e != hipSuccess) return fail(e); }
+			if (!single && a.acct != 0u) SIMLOD_LAUNCH(k_rootpre, dim3(1), dim3(1024), back, a, b);
+			if (single) SIMLOD_LAUNCH_STOP(k_insert<true>, dim3(gridPoints), dim3(TPB), back, inserted, a, b);   // grid clears, points, end-of-batch bookkeeping, the previous group's voxel lists
+			else SIMLOD_LAUNCH_STOP(k_insert<false>, dim3(gridPoints), dim3(TPB), back, inserted, a, b);
 			if (profile_dominant()) {      // bench.py's roofline: the dominant kernel timed in the headline configuration, by the launch's own start / stop events
 				hipEvent_t e0, e1;
 				profile_kernel_events("k_voxelize", &e0, &e1);

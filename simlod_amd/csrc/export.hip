@@ -177,7 +177,7 @@ int run_import(Context& ctx, const SimlodUniforms* u, const SimlodExportNode* ta
 		octree_box(u, a.size, a.minx, a.miny, a.minz);                          // voxels.cu:860-863
 		a.numBatchesUploaded = numBatchesUploaded; a.batchSizes = batchSizes; a.frameCounter = (uint32_t)u->frameCounter;
 		// what launch_reset forgets of this node array's launches and upload counter (the counter is zeroed by k_i_finish, in stream order)
-		forget_launch_history(ctx, stats, numBatchesUploaded, &a.feedback, &a.feedbackSeq);
+		forget_launch_history(ctx, nodes, numBatchesUploaded, &a.feedback, &a.feedbackSeq);
 	}
 	SIMLOD_LAUNCH(k_i_validate, dim3(1), dim3(WG_TPB), stream, a);
 	SIMLOD_LAUNCH(k_i_nodes, dim3((numNodes + LANE_TPB - 1u) / LANE_TPB), dim3(LANE_TPB), stream, a);
@@ -196,8 +196,7 @@ int run_import(Context& ctx, const SimlodUniforms* u, const SimlodExportNode* ta
 	const int rc = (int)hipGetLastError();
 	if (rc != 0) return rc;
 	// the builder's side tables and its chunk table describe the octree that was there (simlod_octree_image_replaced)
-	forget_leaf_table(ctx, nodes);
-	ctx.sideTablesStale.store(true);
+	octree_image_replaced(ctx, nodes);
 	array_event(ctx, nodes, u != nullptr ? ARRAY_IMPORTED_BUILDABLE : ARRAY_IMPORTED);
 	return 0;
 }

@@ -1551,10 +1551,9 @@ uint64_t render_buffer_bytes(uint32_t width, uint32_t height) {
 
 int launch_reset(Context& ctx, const SimlodUniforms* u, uint8_t* pers, SimlodNode* nodes, SimlodStats* stats, uint32_t* numBatchesUploaded,
                  uint32_t* batchSizes, hipStream_t stream) {
-	forget_leaf_table(ctx, nodes);
-	ctx.sideTablesStale.store(true);
+	octree_image_replaced(ctx, nodes);
 	uint32_t* words = nullptr; uint32_t seq = 0;
-	forget_launch_history(ctx, stats, numBatchesUploaded, &words, &seq);
+	forget_launch_history(ctx, nodes, numBatchesUploaded, &words, &seq);
 	SIMLOD_LAUNCH(k_reset, dim3(64), dim3(TPB), stream, pers, nodes, stats, numBatchesUploaded, batchSizes, (uint32_t)u->frameCounter, words, seq);
 	return (int)hipGetLastError();
 }
@@ -1568,6 +1567,7 @@ static void render_plane_offsets(uint64_t numPixels, uint64_t& offWork, uint64_t
 	if (offDir != nullptr) *offDir = offOverflow + numPixels * 16;
 }
 
+uint64_t render_framebuffer_offset() { return R_OFF_FB; }
 uint64_t render_depth_plane_offset(uint32_t width, uint32_t height) {
 	uint64_t w, i, d, c, o; render_plane_offsets((uint64_t)width * height, w, i, d, c, o); return d;
 }

@@ -76,7 +76,7 @@ Context::~Context() {
 	for (SideStream*& s : side) { if (s != nullptr) destroy_side_stream(s); s = nullptr; }
 	// the page-locked feedback words: a copy enqueued by the context's last launches (on the CALLER's streams) may still be on its way
 	(void)hipDeviceSynchronize();
-	for (LaunchHistory& h : history) (void)hipHostFree(const_cast<uint32_t*>(h.seen));
+	for (OctreeState& o : octrees) (void)hipHostFree(const_cast<uint32_t*>(o.history.seen));
 	for (FrameFeedback& f : frames) (void)hipHostFree(const_cast<uint32_t*>(f.seen));
 	for (hipEvent_t& e : gateEvent) if (e != nullptr) { (void)hipEventDestroy(e); e = nullptr; }
 	(void)hipGetLastError();
@@ -122,80 +122,38 @@ const DeviceInfo& device_info() {
 
 uint64_t render_buffer_bytes(uint32_t width, uint32_t height);
 
-// ---- builder -> rasteriser: where each octree's leaf chunk table lives (simlod_internal.hpp LeafTableRef) --------
-void note_leaf_table(Context& ctx, const LeafTableRef& ref) {
-	std::lock_guard<std::mutex> hold(ctx.tablesLock);
-	std::vector<LeafTableRef>& g_leafTables = ctx.tables;
-	for (LeafTableRef& r : g_leafTables)
-		if (r.nodes == ref.nodes) { r = ref; return; }
-	if (g_leafTables.size() >= 64) g_leafTables.erase(g_leafTables.begin());
-	g_leafTables.push_back(ref);
+// ---- one record per node array (octree_state.hpp): the accessors the launchers use, each under the context's one lock --------------------------------
+static volatile uint32_t* host_words() {
+	void* pinned = nullptr;
+	if (hipHostMalloc(&pinned, 64, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+	return static_cast<volatile uint32_t*>(pinned);
 }
-
-void forget_leaf_table(Context& ctx, const void* nodes) {
-	std::lock_guard<std::mutex> hold(ctx.tablesLock);
-	std::vector<LeafTableRef>& g_leafTables = ctx.tables;
-	for (size_t i = 0; i < g_leafTables.size(); i++)
-		if (g_leafTables[i].nodes == nodes) { g_leafTables.erase(g_leafTables.begin() + (long)i); return; }
-}
-
+namespace {
+struct Locked {      // the record of `nodes` under the context's lock; create: made if there is none (else o may be nullptr)
+	std::lock_guard<std::mutex> hold; OctreeState* o;
+	Locked(Context& ctx, const void* nodes, bool create) : hold(ctx.octreesLock), o(create ? &octree_of(ctx.octrees, nodes, host_words) : find_octree(ctx.octrees, nodes)) {}
+	OctreeState* operator->() const { return o; }
+};
+}  // namespace
+void note_leaf_table(Context& ctx, const LeafTableRef& ref) { Locked o(ctx, ref.nodes, true); o->table = ref; o->haveTable = true; }
+void forget_leaf_table(Context& ctx, const void* nodes) { Locked o(ctx, nodes, false); if (o.o != nullptr) o->haveTable = false; }
+void octree_image_replaced(Context& ctx, const void* nodes) { Locked o(ctx, nodes, false); if (o.o != nullptr) o->image_replaced(); }   // (an array without a record: its record will start that way)
 bool find_leaf_table(Context& ctx, const void* nodes, LeafTableRef& ref) {
-	std::lock_guard<std::mutex> hold(ctx.tablesLock);
-	std::vector<LeafTableRef>& g_leafTables = ctx.tables;
-	for (size_t i = 0; i < g_leafTables.size(); i++) {
-		if (g_leafTables[i].nodes != nodes) continue;
-		// the host may have freed the construct buffer since: the kernel must not touch an address that is no longer mapped
-		hipPointerAttribute_t attr;
-		if (hipPointerGetAttributes(&attr, g_leafTables[i].block) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-			(void)hipGetLastError();
-			g_leafTables.erase(g_leafTables.begin() + (long)i);
-			return false;
-		}
-		ref = g_leafTables[i];
-		return true;
-	}
-	return false;
+	Locked o(ctx, nodes, false);
+	if (o.o == nullptr || !o->haveTable) return false;
+	// the host may have freed the construct buffer since: the kernel must not touch an address that is no longer mapped
+	hipPointerAttribute_t attr;
+	if (hipPointerGetAttributes(&attr, o->table.block) != hipSuccess || attr.type != hipMemoryTypeDevice) { (void)hipGetLastError(); o->haveTable = false; return false; }
+	ref = o->table;
+	return true;
 }
-
-// ---- per node array: rendered since the last reset / construct / import, holds an imported octree (simlod_internal.hpp ArrayState) ------
 void array_event(Context& ctx, const void* nodes, ArrayEvent e) {
-	std::lock_guard<std::mutex> hold(ctx.arraysLock);
-	ArrayState* st = nullptr;
-	for (ArrayState& s : ctx.arrays) if (s.nodes == nodes) st = &s;
-	if (st == nullptr) {
-		if (e == ARRAY_RESET || e == ARRAY_CONSTRUCT) return;       // (nothing to forget)
-		if (ctx.arrays.size() >= 64) ctx.arrays.erase(ctx.arrays.begin());
-		ctx.arrays.push_back(ArrayState{nodes, false, false});
-		st = &ctx.arrays.back();
-	}
-	switch (e) {
-	case ARRAY_RESET: st->rendered = false; st->imported = false; break;
-	case ARRAY_CONSTRUCT: st->rendered = false; break;
-	case ARRAY_RENDERED: st->rendered = true; break;
-	case ARRAY_IMPORTED: st->rendered = false; st->imported = true; break;
-	case ARRAY_IMPORTED_BUILDABLE: st->rendered = false; st->imported = false; break;
-	}
+	Locked o(ctx, nodes, e != ARRAY_RESET && e != ARRAY_CONSTRUCT);                 // (those two: nothing to forget of an array without a record)
+	if (o.o != nullptr) o->on(e);
 }
+ArrayState array_state(Context& ctx, const void* nodes) { Locked o(ctx, nodes, false); return o.o != nullptr ? ArrayState{o->rendered, o->imported} : ArrayState{false, false}; }
 
-ArrayState array_state(Context& ctx, const void* nodes) {
-	std::lock_guard<std::mutex> hold(ctx.arraysLock);
-	for (const ArrayState& s : ctx.arrays) if (s.nodes == nodes) return s;
-	return ArrayState{nodes, false, false};
-}
-
-// ---- launch sizing: how many batches a kernel_construct launch can find (simlod_internal.hpp launch_plan) ---------------------------------
-// The reference's kernel loops over whatever has been uploaded when it starts (voxels.cu:870-885); here every group of batches is a handful of kernel
-// launches the HOST enqueues before it can read that number (the upload counter lives on the device).  Kernels of a group without a batch leave at
-// once, but its event hops stand in line behind the real work (~45 us per empty group).  What the host can know:
-//   * the upload counter itself: the reference's uploader publishes it with cuMemsetD32Async(cptr_numBatchesUploaded, n, 1, stream_upload)
-//     (main_progressive_octree.cpp:1047-1050) — shim/cuda.h passes every such write on (simlod_upload_counter_written), the Python mirror does the same;
-//   * Stats.batchletIndex as the latest launch whose end the host has seen left it (k_finish stores it, the upload counter, whether the octree is
-//     fit for exact groups, and the launch's sequence number into page-locked memory: no synchronisation), and how many batches the launches
-//     enqueued since then were sized for.
-// pending = uploaded - index - (what those launches will take).  A host that does not say (no shim, no hint): the counter the latest report saw + the
-// uploader's pace, and never less than one group — a host that uploads, launches once and waits must not wait for ever.
-static constexpr uint32_t NOTHING_SEEN = 0xffffffffu;
-
+// ---- launch sizing (octree_state.hpp size_launch): the upload counters the host has told about, and the part of launch_plan that needs the process ----
 namespace {
 struct UploadCounter { const void* ptr; uint32_t value; bool known; };      // known: the host has said what it wrote there (a reset: zero)
 std::mutex g_countersLock;
@@ -216,89 +174,26 @@ void note_upload_counter(const void* counter, uint32_t value, bool written, bool
 	g_counters.push_back(UploadCounter{counter, value, written});
 }
 
-static LaunchHistory* history_of(Context& ctx, const void* stats, bool create) {
-	std::vector<LaunchHistory>& g_history = ctx.history;
-	for (LaunchHistory& h : g_history) if (h.stats == stats) return &h;
-	if (!create) return nullptr;
-	volatile uint32_t* seen = nullptr;
-	if (g_history.size() >= 64) {
-		// the oldest entry makes room — its page-locked words are handed on, never freed: a copy enqueued by an earlier launch may still
-		// be on its way into them (what arrives late is at worst a stale hint for the new owner: one launch with too many or too few groups)
-		seen = g_history.front().seen;
-		g_history.erase(g_history.begin());
-	} else {
-		void* pinned = nullptr;
-		if (hipHostMalloc(&pinned, 64, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-		seen = static_cast<volatile uint32_t*>(pinned);
-	}
-	seen[0] = NOTHING_SEEN; seen[1] = NOTHING_SEEN; seen[2] = 1u; seen[3] = 0u;
-	LaunchHistory h{};
-	h.stats = stats; h.seen = seen;
-	g_history.push_back(h);
-	return &g_history.back();
-}
-
-LaunchPlan launch_plan(Context& ctx, const SimlodStats* stats, const void* uploadCounter) {
-	LaunchPlan plan{SIMLOD_MAX_BATCHES_PER_LAUNCH, true, nullptr, 0u};
+LaunchPlan launch_plan(Context& ctx, const void* nodes, const void* uploadCounter) {
 	const uint32_t limit = std::min<uint32_t>(ctx.batchLimit.load(), SIMLOD_MAX_BATCHES_PER_LAUNCH);
 	const int hinted = ctx.hintPending.exchange(-1);                      // simlod_context_hint_pending_batches: for THIS launch
-	std::lock_guard<std::mutex> hold(ctx.historyLock);
-	LaunchHistory* h = ctx.tune(KNOB_ADAPTIVE_GROUPS, 1) != 0 ? history_of(ctx, stats, true) : nullptr;
-	if (h == nullptr) { plan.batches = hinted >= 0 ? std::min<uint32_t>((uint32_t)hinted, limit) : limit; return plan; }
-	const uint32_t seq = ++h->seq;
-	plan.feedback = const_cast<uint32_t*>(h->seen); plan.seq = seq;
-	const uint32_t index = h->seen[0], uploadedSeen = h->seen[1], reportSeq = h->seen[3];
-	// a launch of this octree, or its reset, has ended and said so.  (A report from BEFORE the latest reset — a launch that was still running when the host
-	// enqueued the reset writes its words after forget_launch_history cleared them — describes an octree that is gone: ignored; k_reset's own report follows it)
-	const bool reported = index != NOTHING_SEEN && uploadedSeen != NOTHING_SEEN && (int32_t)(reportSeq - h->resetSeq) >= 0;
-	plan.mayGroup = !reported || h->seen[2] != 0u;
-	// what the launches enqueued behind the reporting one (or behind the reset, while nothing has reported) were sized for
-	const uint32_t since = reported ? reportSeq : h->resetSeq;
-	uint32_t inflight = 0;
-	if (seq - since > 32u) inflight = NOTHING_SEEN;
-	else for (uint32_t q = since + 1u; q != seq; q++) inflight += h->enq[q % 32u];
-	const bool knowsStart = reported || h->resetKnown;                                  // index is known: the report's, or zero (a reset is in the stream ahead of this launch)
-	const uint32_t indexNow = reported ? index : 0u;
-	uint32_t want, uploadedHost = 0;
-	if (hinted >= 0) want = (uint32_t)hinted;
-	else if (knowsStart && inflight != NOTHING_SEEN && host_uploaded(uploadCounter, uploadedHost) && !(reported && uploadedSeen > uploadedHost)) {
-		// (... unless a launch has SEEN more on the device than the host has told: a host that does not pass its counter writes on — the only value this
-		// library knows is the zero of its own reset.  Such a host gets the prediction below)
-		const uint32_t pending = uploadedHost > indexNow ? uploadedHost - indexNow : 0u;
-		want = pending > inflight ? pending - inflight : 0u;
-		// (a launch may take less than it was sized for — the memory guard, the time budget —: while the launches in flight have not reported, they
-		// cannot be counted on to have taken everything, and this one enqueues one group: a frame loop must not stand still with batches pending)
-		if (want == 0u && pending != 0u) want = 1u;
-		// ... and nothing at all is enqueued only on the word of a host that has been HEARD since the reset or whose launches have reported: "zero uploaded"
-		// right after a reset is also what a host that tells nothing looks like (it uploads, launches once and waits)
-		if (want == 0u && !reported) want = 1u;
-	} else if (!reported) want = SIMLOD_MAX_BATCHES_PER_LAUNCH;                          // nothing is known: everything
-	else {
-		// the host says nothing: what the latest report saw pending + what was uploaded between the last two reports (the uploader's pace per launch)
-		const uint32_t pending = uploadedSeen > index ? uploadedSeen - index : 0u;
-		if (!h->havePrev) h->arrivals = SIMLOD_MAX_BATCHES_PER_LAUNCH;                  // (one report says nothing about the pace)
-		else if (index != h->prevIndex || uploadedSeen != h->prevUploaded)
-			h->arrivals = uploadedSeen >= h->prevUploaded && index >= h->prevIndex ? uploadedSeen - h->prevUploaded : SIMLOD_MAX_BATCHES_PER_LAUNCH;   // (counters that went back: reset by other means)
-		else if (pending == 0u) h->arrivals = 0u;                                       // the same numbers again and nothing pending: the loader is idle or done
-		h->prevIndex = index; h->prevUploaded = uploadedSeen; h->havePrev = true;
-		want = std::max<uint32_t>(1u, pending + h->arrivals);                           // (never nothing: such a host may upload, launch once and wait)
+	uint32_t uploadedHost = 0;
+	const bool hostKnown = host_uploaded(uploadCounter, uploadedHost);
+	Locked o(ctx, nodes, true);
+	LaunchPlan plan{hinted >= 0 ? std::min<uint32_t>((uint32_t)hinted, limit) : limit, true, nullptr, 0u, false};      // (launches that are not sized)
+	if (ctx.tune(KNOB_ADAPTIVE_GROUPS, 1) != 0 && o->history.seen != nullptr) {
+		const uint32_t seen[4] = {o->history.seen[0], o->history.seen[1], o->history.seen[2], o->history.seen[3]};
+		plan = size_launch(&o->history, seen, hinted, limit, hostKnown, uploadedHost);
 	}
-	plan.batches = std::min<uint32_t>(want, limit);
-	h->enq[seq % 32u] = plan.batches;
+	plan.sideTablesStale = o->take_stale();
 	return plan;
 }
 
-void forget_launch_history(Context& ctx, const SimlodStats* stats, const void* uploadCounter, uint32_t** words, uint32_t* seq) {
-	if (uploadCounter != nullptr) note_upload_counter(uploadCounter, 0u, true, true);        // reset.cu:84: the reset zeroes the upload counter
-	std::lock_guard<std::mutex> hold(ctx.historyLock);
-	LaunchHistory* h = history_of(ctx, stats, words != nullptr);
-	if (words != nullptr) { *words = nullptr; *seq = 0u; }
-	if (h == nullptr) return;
-	h->seen[0] = NOTHING_SEEN; h->seen[1] = NOTHING_SEEN; h->seen[2] = 1u;
-	h->havePrev = false;
-	h->resetSeq = ++h->seq; h->resetKnown = words != nullptr;
-	h->enq[h->seq % 32u] = 0u;
-	if (words != nullptr) { *words = const_cast<uint32_t*>(h->seen); *seq = h->seq; }  // (k_reset reports in stream order: index 0, uploaded 0)
+void forget_launch_history(Context& ctx, const void* nodes, const void* uploadCounter, uint32_t** words, uint32_t* seq) {
+	note_upload_counter(uploadCounter, 0u, true, true);        // reset.cu:84: the reset zeroes the upload counter
+	Locked o(ctx, nodes, true);
+	*words = const_cast<uint32_t*>(o->history.seen);           // (k_reset reports in stream order: index 0, uploaded 0)
+	*seq = *words != nullptr ? forget_history(&o->history) : 0u;
 }
 
 // ---- frame feedback: did the render buffer's previous frame have nodes that sort into the screen bins (render.hip r_overflow) ----------
@@ -319,17 +214,15 @@ uint32_t* frame_feedback(Context& ctx, const void* buffer, uint32_t parts, bool&
 	FrameFeedback* f = nullptr;
 	for (FrameFeedback& g : ctx.frames) if (g.buffer == buffer) f = &g;
 	if (f == nullptr) {
-		volatile uint32_t* seen = nullptr;
+		volatile uint32_t* handedOn = nullptr;
 		if (ctx.frames.size() >= 64) {                       // the oldest entry without a frame in progress makes room; its word is handed on (a late store into it: a stale hint)
 			size_t victim = 0;
 			for (size_t i = 0; i < ctx.frames.size(); i++) if (!ctx.frames[i].open) { victim = i; break; }
-			seen = ctx.frames[victim].seen;
+			handedOn = ctx.frames[victim].seen;
 			ctx.frames.erase(ctx.frames.begin() + (long)victim);
-		} else {
-			void* pinned = nullptr;
-			if (hipHostMalloc(&pinned, 64, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); bufferBytes = bytes_behind(buffer); bins = possible; return nullptr; }
-			seen = static_cast<volatile uint32_t*>(pinned);
 		}
+		volatile uint32_t* seen = words_for_newcomer(handedOn, host_words);
+		if (seen == nullptr) { bufferBytes = bytes_behind(buffer); bins = possible; return nullptr; }
 		seen[0] = 1u;                                        // a buffer's first frame sorts
 		ctx.frames.push_back(FrameFeedback{buffer, seen, false, 0, false, false});
 		f = &ctx.frames.back();
@@ -474,9 +367,7 @@ int simlod_context_reload_env(SimlodContext* c) { ctx_or_default(c).reload_env()
 
 int simlod_set_node_capacity(uint32_t numNodes) { return simlod_context_set_node_capacity(nullptr, numNodes); }
 
-uint64_t simlod_render_framebuffer_offset(void) {
-	return (uint64_t)SIMLOD_MAX_VISIBLE_NODES * sizeof(SimlodNode) + 7 * 16 + 32 + 16000000ull;
-}
+uint64_t simlod_render_framebuffer_offset(void) { return render_framebuffer_offset(); }
 
 uint64_t simlod_render_buffer_bytes(uint32_t width, uint32_t height) { return render_buffer_bytes(width, height); }
 
@@ -487,12 +378,7 @@ int simlod_set_ingest_mode(uint32_t mode) { return simlod_context_set_ingest_mod
 
 int simlod_set_construct_batch_limit(uint32_t maxBatches) { return simlod_context_set_construct_batch_limit(nullptr, maxBatches); }
 
-int simlod_octree_image_replaced(const SimlodNode* nodes) {
-	Context& ctx = context_of(nodes);
-	forget_leaf_table(ctx, nodes);
-	ctx.sideTablesStale.store(true);
-	return 0;
-}
+int simlod_octree_image_replaced(const SimlodNode* nodes) { octree_image_replaced(context_of(nodes), nodes); return 0; }
 
 int simlod_launch_reset(const SimlodUniforms* uniforms, uint8_t* buffer_octree, SimlodNode* nodes, SimlodStats* stats,
                         void* cudaprint, uint32_t* numBatchesUploaded, uint32_t* batchSizes, void* stream) {

@@ -13,6 +13,7 @@
 
 #include "simlod_abi.h"
 #include "simlod_hip.h"
+#include "octree_state.hpp"      // LeafTableRef, LaunchHistory, ArrayEvent, OctreeState and its registry, size_launch: the part that needs no HIP
 
 namespace simlod {
 
@@ -40,18 +41,6 @@ __host__ __device__ inline void leaf_row_set(uint8_t* table, const uint8_t* pers
 	reinterpret_cast<uint32_t*>(r)[k] = (uint32_t)v;
 	r[LEAF_ROW_SLOTS * 4u + k] = (uint8_t)(v >> 32);
 }
-struct LeafTableRef {
-	const void*               nodes;
-	const void*               block;       // start of the buffer the table lives in (the construct kernel's momentary buffer)
-	const uint8_t*            table;       // rows of LEAF_ROW_BYTES (leaf_row_get)
-	const uint8_t*            pers;        // the persistent buffer the rows' offsets refer to
-	const uint32_t*           magic;
-	const uint32_t*           batch;
-	const uint64_t*           tableNodes;
-	const uint64_t*           sig;         // table_signature() of the Stats the table was stamped for
-	uint32_t                  magicValue, slots;
-	uint32_t                  rows;        // rows the table has (the node capacity of the launch that registered it)
-};
 // what the stamp remembers of the Stats block: an octree image that reached the buffers some other way (a host upload) differs here
 __host__ __device__ inline uint64_t table_signature(const SimlodStats* s) {
 	return ((uint64_t)s->numNodes | (uint64_t)s->numPoints << 32) ^ (s->allocatedBytes_persistent * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)s->numVoxels << 20);
@@ -66,7 +55,7 @@ inline void octree_box(const SimlodUniforms* u, float& size, float& minx, float&
 // ---- per-octree state (include/simlod_hip.h, simlod_context_*) -----------------------------------------------------------------------------
 // Everything the library keeps between launches belongs to a context: the ingest mode, the node capacity, the host's batch limit, the
 // tuning knobs (read from the environment ONCE, when the context is made; simlod_context_set_knob overrides one), the second stream and
-// its events, the registry of leaf chunk tables, the launch feedback.  The reference's launch signatures carry no handle, so a launch
+// its events, one record per node array (octree_state.hpp OctreeState).  The reference's launch signatures carry no handle, so a launch
 // finds its context through the node array it is given (simlod_context_attach); node arrays nobody attached share the default context.
 enum Knob : int {
 	KNOB_OVERLAP_TAIL, KNOB_EXPAND_WGS, KNOB_GRID_MULT, KNOB_COUNT_TPB, KNOB_VOXELIZE_WGS, KNOB_ADAPTIVE_GROUPS,
@@ -76,40 +65,25 @@ enum Knob : int {
 static constexpr int KNOB_UNSET = INT_MIN;
 extern const char* const KNOB_NAMES[KNOB_COUNT_];            // "SIMLOD_OVERLAP_TAIL", ...
 
-struct LaunchHistory {      // seen (page-locked, written by the launches' last kernels and by k_reset): [0] batchletIndex, [1] the upload counter, [2] fit for exact groups, [3] sequence number of the launch that wrote them
-	const void* stats; volatile uint32_t* seen; uint32_t prevIndex, prevUploaded, arrivals; bool havePrev;
-	uint32_t seq, resetSeq; bool resetKnown;      // launches (and resets) of this octree so far | the latest reset's number | ... and it ran through this library (index 0 from there on)
-	uint32_t enq[32];                             // batches launch #seq was sized for
-};
-struct LaunchPlan { uint32_t batches; bool mayGroup; uint32_t* feedback; uint32_t seq; };   // batches this launch can find (0: none — an idle frame) | exact groups allowed | where its last kernel reports, and as which launch
 struct FrameFeedback { const void* buffer; volatile uint32_t* seen; bool bins; uint64_t bytes; bool possible, open; };                       // render.hip launch_render: seen[0] = nodes of the buffer's latest frame that sort (or would)
 struct SideStream;                                           // construct.hip: the second stream of kernel_construct and its events
 void destroy_side_stream(SideStream* s);
 
-// What the host knows of a node array beyond the builder's tables (export.hip, the launchers): a kernel_render ran on it since its last reset, construct or
-// import (SIMLOD_EXPORT_VISIBLE reads the visible / isLarge bytes that frame wrote) | it holds an imported octree (no grids, no builder state:
-// kernel_construct and the colour filter refuse it until the next reset).  Keyed by node array, not by context: two arrays may share one.
-struct ArrayState { const void* nodes; bool rendered, imported; };
-enum ArrayEvent : int { ARRAY_RESET, ARRAY_CONSTRUCT, ARRAY_RENDERED, ARRAY_IMPORTED, ARRAY_IMPORTED_BUILDABLE };   // (buildable: grids and builder state, as after a reset)
+struct ArrayState { bool rendered, imported; };               // OctreeState's pair, as array_state hands it out
 
 struct Context {
 	std::atomic<uint32_t> nodeCapacity{263157u};             // 40 000 000 B / 152 B, main_progressive_octree.cpp:552
 	std::atomic<uint32_t> ingestMode{0u};                    // 0 = exact (one batch at a time, the reference's granularity), 1 = coalesced
 	std::atomic<uint32_t> batchLimit{SIMLOD_MAX_BATCHES_PER_LAUNCH};   // simlod_context_set_construct_batch_limit: a launch never takes more than this many batches (<= 20)
-	std::atomic<bool>     sideTablesStale{false};                       // simlod_octree_image_replaced / a reset: the next kernel_construct rebuilds its side tables whatever the stamp in the buffer says (an uploaded image with the same counters as the one it replaces: ADVICE r5)
 	std::atomic<int>      hintPending{-1};                              // simlod_context_hint_pending_batches: that many batches are pending NOW — for the next launch, then forgotten
 	std::atomic<uint64_t> trunkLo{0u}, trunkHi{0u};          // simlod_context_set_trunk_mask: upper nodes (levels 0-2) that split whatever they hold; zero: the reference's rule alone
 	int knob[KNOB_COUNT_];
 	std::mutex sideLock;
 	SideStream* side[64] = {};                               // per device ordinal, made by the first launch that wants it
-	std::mutex tablesLock;
-	std::vector<LeafTableRef> tables;
-	std::mutex historyLock;
-	std::vector<LaunchHistory> history;
+	std::mutex octreesLock;
+	std::vector<OctreeState> octrees;                        // per node array: its leaf chunk table, rendered / imported, stale side tables, launch feedback (octree_state.hpp)
 	std::mutex framesLock;
 	std::vector<FrameFeedback> frames;
-	std::mutex arraysLock;
-	std::vector<struct ArrayState> arrays;                    // per node array: what export / import need to know of it (array_event)
 	hipEvent_t gateEvent[64] = {};                            // per device ordinal: the end of this context's latest k_expand, when it runs without a second stream (expand_gate)
 	Context();
 	~Context();
@@ -122,7 +96,7 @@ struct Context {
 uint32_t* frame_feedback(Context& ctx, const void* buffer, uint32_t parts, bool& possible, bool& bins, uint64_t& bufferBytes);   // parts: RENDER_* of this launch; bufferBytes: what the allocation behind `buffer` holds from `buffer` on
 void frame_feedback_no_bins(Context& ctx, const void* buffer);
 void array_event(Context& ctx, const void* nodes, ArrayEvent e);
-ArrayState array_state(Context& ctx, const void* nodes);      // {nodes, false, false} for an array nothing was recorded for
+ArrayState array_state(Context& ctx, const void* nodes);      // {false, false} for an array nothing was recorded for
 Context& context_of(const void* nodes);                      // the context `nodes` is attached to, else the default one
 uint32_t live_contexts();                                    // contexts that exist right now (the default one included once it has been used)
 
@@ -143,12 +117,13 @@ uint64_t construct_min_bytes(uint32_t nodeCapacity);
 }  // namespace build
 
 void note_leaf_table(Context& ctx, const LeafTableRef& ref);                 // kernel_construct: after a launch whose layout fits
-void forget_leaf_table(Context& ctx, const void* nodes);                     // reset
+void forget_leaf_table(Context& ctx, const void* nodes);                     // a launch whose layout does not fit
+void octree_image_replaced(Context& ctx, const void* nodes);                 // reset, import, simlod_octree_image_replaced: no chunk table, and the next kernel_construct rebuilds its side tables (LaunchPlan::sideTablesStale)
 bool find_leaf_table(Context& ctx, const void* nodes, LeafTableRef& ref);    // false also when the table's buffer is no longer a live device allocation
 
 // How many batches a kernel_construct launch should enqueue kernels for (simlod_hip.cpp: launch sizing).
-LaunchPlan launch_plan(Context& ctx, const SimlodStats* stats, const void* uploadCounter);
-void forget_launch_history(Context& ctx, const SimlodStats* stats, const void* uploadCounter = nullptr, uint32_t** words = nullptr, uint32_t* seq = nullptr);   // reset (words: where k_reset reports, as launch *seq)
+LaunchPlan launch_plan(Context& ctx, const void* nodes, const void* uploadCounter);
+void forget_launch_history(Context& ctx, const void* nodes, const void* uploadCounter, uint32_t** words, uint32_t* seq);   // reset (words: where k_reset reports, as launch *seq)
 void note_upload_counter(const void* counter, uint32_t value, bool written, bool create);     // written: the host has enqueued a write of `value` to the upload counter at `counter`; else: `counter` is named as one
 
 struct DeviceInfo {
@@ -172,9 +147,10 @@ void profile_kernel_events(const char* kernelName, hipEvent_t* start, hipEvent_t
 		hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);          \
 		if (::simlod::debug_sync()) ::simlod::debug_synced(#kernel);              \
 	} while (0)
-// a launch whose completion signals `stopEvent` (hipExtLaunchKernelGGL): for kernels another stream waits for
+// a launch whose completion signals `stopEvent` (hipExtLaunchKernelGGL): for kernels another stream waits for, when there is one — stopEvent == nullptr is SIMLOD_LAUNCH, profile mark included
 #define SIMLOD_LAUNCH_STOP(kernel, grid, block, stream, stopEvent, ...)                       \
 	do {                                                                                      \
+		if ((stopEvent) == nullptr) { SIMLOD_LAUNCH(kernel, grid, block, stream, __VA_ARGS__); break; } \
 		hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, nullptr, stopEvent, 0, __VA_ARGS__); \
 		if (::simlod::debug_sync()) ::simlod::debug_synced(#kernel);                          \
 	} while (0)
@@ -208,6 +184,7 @@ int launch_generate_terrain(SimlodPoint* out, uint64_t numPoints, uint64_t first
 enum : uint32_t { RENDER_FIRST = 1u, RENDER_COLOR = 2u, RENDER_RESOLVE = 4u, RENDER_OUTPUT = 8u, RENDER_ALL = 15u };
 int launch_render(Context& ctx, uint32_t* buffer, const SimlodUniforms* u, SimlodNode* nodes, uint32_t* colorbuffer, SimlodStats* stats,
                   uint64_t* frameStart, hipStream_t stream, uint32_t parts);
+uint64_t render_framebuffer_offset();
 uint64_t render_depth_plane_offset(uint32_t width, uint32_t height);
 uint64_t render_sum_planes_offset(uint32_t width, uint32_t height);
 
