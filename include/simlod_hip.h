@@ -125,7 +125,7 @@ int simlod_octree_image_replaced(const SimlodNode* nodes);
  * and, last, the screen bins (a 48 MB pool of 16-byte entries + per-bin tables) that frames with very large nodes sort their samples into.
  * 1920 x 1080: 193.5 MB — inside the 200 000 000 bytes the reference host allocates whatever its window's size (main_progressive_octree.cpp:555).
  * Larger frames need more for the full layout (1920 x 1200: 202 MB, 2560 x 1440: 255 MB); a buffer that is smaller is still fine as long as it
- * holds everything in front of the bin pool (2560 x 1440: 199.2 MB): kernel_render asks the runtime how large the ALLOCATION behind `buffer` is
+ * holds everything in front of the bin pool (2560 x 1440: 206.8 MB): kernel_render asks the runtime how large the ALLOCATION behind `buffer` is
  * (hipMemGetAddressRange) and sizes the pool by what is left — with less than 1 MB left it draws without bins (same frame, the samples of
  * screen-filling nodes take device-scope atomics).  A host that carves `buffer` out of a larger allocation of its own must therefore give it
  * simlod_render_buffer_bytes(width, height): what lies behind `buffer` inside that allocation is taken for the pool. */
@@ -176,6 +176,22 @@ int simlod_launch_render_part(uint32_t part, uint32_t* buffer, const SimlodUnifo
                               void* stream);
 uint64_t simlod_render_depth_plane_offset(uint32_t width, uint32_t height);
 uint64_t simlod_render_sum_planes_offset(uint32_t width, uint32_t height);
+/* The whole layout of kernel_render's `buffer` for a width x height frame (simlod_amd/csrc/render_layout.hpp states it; this is its image for
+ * hosts and tools): byte offsets of every region in buffer order, `bytes` = simlod_render_buffer_bytes(width, height), and the few sizes a reader
+ * of the regions needs.  `framebuffer`, `depth` and `sums` are what the three offset queries above return.  The frame's counters are 32-bit words
+ * `counterStride` bytes apart from `counters` on; `work` holds 32-bit words (their indices: the W_* enum of render_layout.hpp, abi.py WORK_WORDS);
+ * `items` holds `itemClasses` arrays of `maxDrawItems` records of `drawItemBytes`; `binSegs` lists per bin 256 segments of `binSegBytes`, `binStats`
+ * one such record per bin, `binPool` 16-byte entries up to the buffer's tail.  binTiles == 0: a frame too large for the bins; `probe`: the clock
+ * words of a -DVAR_PROBE build, inside the vertex array.  hipErrorInvalidValue for out == NULL or a zero width or height. */
+typedef struct SimlodFrameLayout {
+	uint64_t visible, counters, lines, vertices, probe, framebuffer;
+	uint64_t work, items, depth, colour, sums, dir;
+	uint64_t binSegs, binSegCount, binStats, binPool;
+	uint64_t bytes, binTiles, binTilesX;
+	uint64_t counterStride, drawItemBytes, binSegBytes, maxDrawItems, itemClasses;
+} SimlodFrameLayout;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodFrameLayout) == 192, "SimlodFrameLayout: 24 x uint64");
+int simlod_render_frame_layout(uint32_t width, uint32_t height, SimlodFrameLayout* out);
 
 /* The four parts and the reductions between them in ONE call, for hosts that are not Python (simlod_amd/distributed.py render_frame is the
  * same sequence over torch.distributed).  `reduce` is called on the launch stream's timeline, between the parts, with the plane to reduce

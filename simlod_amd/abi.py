@@ -146,3 +146,16 @@ ray_hit_dtype = np.dtype({"names": ["t", "node", "ordinal", "sample"], "formats"
 ray_counts_dtype = np.dtype({"names": ["numNodes", "error", "numHits", "numInvalid", "numPairs", "numCandidates"],
                              "formats": ["<u4", "<u4", "<u4", "<u4", "<u8", "<u8"], "offsets": [0, 4, 8, 12, 16, 24], "itemsize": 32})
 assert ray_dtype.itemsize == 48 and ray_hit_dtype.itemsize == 32 and ray_counts_dtype.itemsize == 32
+
+# ---- kernel_render's buffer (include/simlod_hip.h simlod_render_frame_layout; simlod_amd/csrc/render_layout.hpp states the layout) -------
+frame_layout_dtype = np.dtype([(n, "<u8") for n in (
+    "visible", "counters", "lines", "vertices", "probe", "framebuffer", "work", "items", "depth", "colour", "sums", "dir",
+    "binSegs", "binSegCount", "binStats", "binPool", "bytes", "binTiles", "binTilesX",
+    "counterStride", "drawItemBytes", "binSegBytes", "maxDrawItems", "itemClasses")])
+assert frame_layout_dtype.itemsize == 192
+# the frame's counters (enum C_*) and the 32-bit words of its work area (enum W_*), by the enums' names
+COUNTERS = {"C_VISIBLE": 0, "C_POINTS": 1, "C_VOXELS": 2, "C_INNER": 3, "C_LEAVES": 4, "C_TABLE_LISTS": 5, "C_OUTSIDE_TILES": 6, "C_COUNT": 7}
+WORK_WORDS = {"W_CURSOR0": 0, "W_DIR_ENTRIES": 4, "W_ITEMS0": 8, "W_POOL_TAKEN": 12, "W_BINNED": 13, "W_SORTING_NODES": 14, "W_COUNT": 15, "W_READY": 15}
+# a draw item (render_common.inc DrawItem), as the raster tools read it
+draw_item_dtype = np.dtype([("chunks", "<u8"), ("samples", "<u4"), ("visibleIdx", "<u4"), ("tileX", "<i4"), ("tileY", "<i4"), ("tileW", "<u2"), ("tileH", "<u2"), ("took", "<u4")])
+assert draw_item_dtype.itemsize == 32

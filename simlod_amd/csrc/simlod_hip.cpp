@@ -14,6 +14,7 @@
 
 #include "simlod_hip.h"
 #include "simlod_internal.hpp"
+#include "render_layout.hpp"
 
 namespace simlod {
 
@@ -119,8 +120,6 @@ const DeviceInfo& device_info() {
 	}
 	return cache[dev];
 }
-
-uint64_t render_buffer_bytes(uint32_t width, uint32_t height);
 
 // ---- one record per node array (octree_state.hpp): the accessors the launchers use, each under the context's one lock --------------------------------
 static volatile uint32_t* host_words() {
@@ -367,9 +366,19 @@ int simlod_context_reload_env(SimlodContext* c) { ctx_or_default(c).reload_env()
 
 int simlod_set_node_capacity(uint32_t numNodes) { return simlod_context_set_node_capacity(nullptr, numNodes); }
 
-uint64_t simlod_render_framebuffer_offset(void) { return render_framebuffer_offset(); }
-
-uint64_t simlod_render_buffer_bytes(uint32_t width, uint32_t height) { return render_buffer_bytes(width, height); }
+// the layout of kernel_render's buffer: render_layout.hpp
+uint64_t simlod_render_framebuffer_offset(void) { return FrameLayout::framebuffer; }
+uint64_t simlod_render_buffer_bytes(uint32_t width, uint32_t height) { return FrameLayout(width, height).bytes; }
+uint64_t simlod_render_depth_plane_offset(uint32_t width, uint32_t height) { return FrameLayout(width, height).depth; }
+uint64_t simlod_render_sum_planes_offset(uint32_t width, uint32_t height) { return FrameLayout(width, height).sums; }
+int simlod_render_frame_layout(uint32_t width, uint32_t height, SimlodFrameLayout* out) {
+	if (out == nullptr || width == 0u || height == 0u) return (int)hipErrorInvalidValue;
+	const FrameLayout l(width, height);
+	*out = SimlodFrameLayout{l.visible, l.counters, l.lines, l.vertices, l.probe, l.framebuffer, l.work, l.items, l.depth, l.colour, l.sums, l.dir,
+	                         l.binSegs, l.binSegCount, l.binStats, l.binPool, l.bytes, l.binTiles, l.binTilesX,
+	                         COUNTER_STRIDE, DRAW_ITEM_BYTES, BIN_SEG_BYTES, MAX_DRAW_ITEMS, (uint64_t)ITEM_CLASSES};
+	return 0;
+}
 
 uint64_t simlod_construct_buffer_min_bytes(void) { return build::construct_min_bytes(default_context().nodeCapacity.load()); }
 uint64_t simlod_context_construct_buffer_min_bytes(SimlodContext* c) { return build::construct_min_bytes(ctx_or_default(c).nodeCapacity.load()); }
@@ -495,17 +504,18 @@ int simlod_render_frame_composed(uint32_t* buffer, const SimlodUniforms* u, Siml
 	hipStream_t st = (hipStream_t)stream;
 	const uint32_t W = (uint32_t)u->width, H = (uint32_t)u->height;
 	const uint64_t px = (uint64_t)W * H;
+	const FrameLayout lay(W, H);
 	uint8_t* base = reinterpret_cast<uint8_t*>(buffer);
 	auto part = [&](uint32_t k) { return launch_render(ctx, buffer, u, nodes, colorbuffer, stats, frameStartTimestamp, st, 1u << k); };
 	auto red = [&](uint32_t plane, uint64_t offset, uint64_t count, uint32_t elemBytes, uint32_t op) { return reduce ? reduce(user, plane, base + offset, count, elemBytes, op, stream) : 0; };
 	const bool hqs = u->useHighQualityShading != 0, boxes = u->showBoundingBox != 0;
 	int rc = part(0);
 	if (rc == 0) array_event(ctx, nodes, ARRAY_RENDERED);
-	if (rc == 0 && hqs) rc = red(SIMLOD_PLANE_DEPTH, render_depth_plane_offset(W, H), px, 4, SIMLOD_REDUCE_MIN);
+	if (rc == 0 && hqs) rc = red(SIMLOD_PLANE_DEPTH, lay.depth, px, 4, SIMLOD_REDUCE_MIN);
 	if (rc == 0 && hqs) rc = part(1);
-	if (rc == 0 && hqs) rc = red(SIMLOD_PLANE_SUMS, render_sum_planes_offset(W, H), px * 4, 4, SIMLOD_REDUCE_SUM);
+	if (rc == 0 && hqs) rc = red(SIMLOD_PLANE_SUMS, lay.sums, px * 4, 4, SIMLOD_REDUCE_SUM);
 	if (rc == 0 && hqs) rc = part(2);
-	if (rc == 0 && (!hqs || boxes)) rc = red(SIMLOD_PLANE_FRAMEBUFFER, simlod_render_framebuffer_offset(), px, 8, SIMLOD_REDUCE_MIN);
+	if (rc == 0 && (!hqs || boxes)) rc = red(SIMLOD_PLANE_FRAMEBUFFER, lay.framebuffer, px, 8, SIMLOD_REDUCE_MIN);
 	if (rc == 0) rc = part(3);
 	return rc;
 }
@@ -557,9 +567,6 @@ int simlod_render_frame_rccl(uint32_t* buffer, const SimlodUniforms* u, SimlodNo
 	if (!rccl()->supported) return (int)hipErrorNotSupported;           // no RCCL in the process, or one whose enum ABI this entry was not written for
 	return simlod_render_frame_composed(buffer, u, nodes, colorbuffer, stats, frameStartTimestamp, cudaprint, stream, reduce_over_rccl, ncclComm);
 }
-
-uint64_t simlod_render_depth_plane_offset(uint32_t width, uint32_t height) { return render_depth_plane_offset(width, height); }
-uint64_t simlod_render_sum_planes_offset(uint32_t width, uint32_t height) { return render_sum_planes_offset(width, height); }
 
 static bool ends_with(const std::string& s, const char* suffix) {
 	const size_t n = std::strlen(suffix);

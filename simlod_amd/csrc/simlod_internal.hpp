@@ -184,8 +184,5 @@ int launch_generate_terrain(SimlodPoint* out, uint64_t numPoints, uint64_t first
 enum : uint32_t { RENDER_FIRST = 1u, RENDER_COLOR = 2u, RENDER_RESOLVE = 4u, RENDER_OUTPUT = 8u, RENDER_ALL = 15u };
 int launch_render(Context& ctx, uint32_t* buffer, const SimlodUniforms* u, SimlodNode* nodes, uint32_t* colorbuffer, SimlodStats* stats,
                   uint64_t* frameStart, hipStream_t stream, uint32_t parts);
-uint64_t render_framebuffer_offset();
-uint64_t render_depth_plane_offset(uint32_t width, uint32_t height);
-uint64_t render_sum_planes_offset(uint32_t width, uint32_t height);
 
 }  // namespace simlod

@@ -68,6 +68,7 @@ def lib():
         L.simlod_render_depth_plane_offset.argtypes = [u32, u32]
         L.simlod_render_sum_planes_offset.restype = u64
         L.simlod_render_sum_planes_offset.argtypes = [u32, u32]
+        L.simlod_render_frame_layout.argtypes = [u32, u32, vp]
         L.simlod_program_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_char_p), ctypes.c_int]
         L.simlod_program_destroy.argtypes = [vp]
@@ -102,7 +103,7 @@ EXPORTED_SYMBOLS = [
     "simlod_construct_buffer_min_bytes", "simlod_launch_reset", "simlod_launch_construct", "simlod_launch_render",
     "simlod_program_create", "simlod_program_destroy", "simlod_program_kernel", "simlod_function_max_active_blocks",
     "simlod_launch_cooperative", "simlod_build_info", "simlod_decode_las", "simlod_launch_render_part",
-    "simlod_render_depth_plane_offset", "simlod_render_sum_planes_offset", "simlod_set_ingest_mode", "simlod_set_construct_batch_limit",
+    "simlod_render_depth_plane_offset", "simlod_render_sum_planes_offset", "simlod_render_frame_layout", "simlod_set_ingest_mode", "simlod_set_construct_batch_limit",
     "simlod_context_create", "simlod_context_destroy", "simlod_context_attach", "simlod_context_set_node_capacity", "simlod_context_set_ingest_mode",
     "simlod_context_set_construct_batch_limit", "simlod_context_set_knob", "simlod_context_reload_env", "simlod_context_construct_buffer_min_bytes",
     "simlod_octree_image_replaced", "simlod_render_frame_composed", "simlod_render_frame_rccl", "simlod_context_set_trunk_mask", "simlod_rccl_version",
@@ -146,6 +147,7 @@ class DeviceOctree:
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self.max_nodes = max_nodes
+        self._layouts = {}                 # frame_layout's records by (W, H)
         # this octree's own context (include/simlod_hip.h): node capacity, ingest granularity — exact = the reference's batch-by-batch
         # bookkeeping; coalesced = all pending batches of a launch as one (same octree content, different allocator / chunk-pool
         # counters) —, batch limit, tuning knobs (from the environment as it is NOW), second stream; launches find it by the node array
@@ -333,7 +335,8 @@ class DeviceOctree:
                                               self._p(self.nodes), self._p(self.stats), self._p(self.frame_start), None,
                                               self._p(self.num_uploaded), self._p(self.batch_sizes), self._stream()), "kernel_construct")
 
-    def render(self, uniforms):
+    def _launch_frame(self, uniforms, launch, what):
+        """One kernel_render-shaped call: the two buffers grown to what the uniforms' W x H frame needs, then launch(the eight arguments).  -> (W, H), which the readers below take as the last frame's size"""
         u, up = self._u(uniforms)
         W, H = int(u["width"][0]), int(u["height"][0])
         need = int(self.L.simlod_render_buffer_bytes(W, H))
@@ -341,9 +344,12 @@ class DeviceOctree:
             self.render_buffer = torch.empty(need, dtype=torch.uint8, device=self.device)
         if self.colorbuffer.numel() < W * H:
             self.colorbuffer = torch.zeros(W * H, dtype=torch.int32, device=self.device)
-        _check(self.L.simlod_launch_render(self._p(self.render_buffer), up, self._p(self.nodes), self._p(self.colorbuffer),
-                                           self._p(self.stats), self._p(self.frame_start), None, self._stream()), "kernel_render")
-        return W, H
+        _check(launch(self._p(self.render_buffer), up, self._p(self.nodes), self._p(self.colorbuffer), self._p(self.stats), self._p(self.frame_start), None, self._stream()), what)
+        self._frame_size = W, H
+        return self._frame_size
+
+    def render(self, uniforms):
+        return self._launch_frame(uniforms, self.L.simlod_launch_render, "kernel_render")
 
     def select_frame(self, k):
         """Switch between render buffers (distributed.render_frames_pipelined keeps two frames in flight: while the planes of one are being
@@ -358,16 +364,7 @@ class DeviceOctree:
 
     # -- a frame in parts, for composition across GPUs (simlod_launch_render_part; driven by distributed.render_frame) ----------
     def render_part(self, uniforms, part):
-        u, up = self._u(uniforms)
-        W, H = int(u["width"][0]), int(u["height"][0])
-        need = int(self.L.simlod_render_buffer_bytes(W, H))
-        if self.render_buffer.numel() < need:
-            self.render_buffer = torch.empty(need, dtype=torch.uint8, device=self.device)
-        if self.colorbuffer.numel() < W * H:
-            self.colorbuffer = torch.zeros(W * H, dtype=torch.int32, device=self.device)
-        _check(self.L.simlod_launch_render_part(ctypes.c_uint32(part), self._p(self.render_buffer), up, self._p(self.nodes), self._p(self.colorbuffer),
-                                                self._p(self.stats), self._p(self.frame_start), None, self._stream()), "kernel_render part")
-        self._frame_size = (W, H)
+        self._launch_frame(uniforms, lambda *args: self.L.simlod_launch_render_part(ctypes.c_uint32(part), *args), "kernel_render part")
 
     REDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p)
 
@@ -375,38 +372,47 @@ class DeviceOctree:
         """One frame through simlod_render_frame_composed / simlod_render_frame_rccl (include/simlod_hip.h): the four parts of kernel_render with
         a reduction of the named plane over all ranks in between — `reduce(plane, data_ptr, count, elem_bytes, op, stream) -> int`, or an
         ncclComm_t as an integer address."""
-        u, up = self._u(uniforms)
-        W, H = int(u["width"][0]), int(u["height"][0])
-        need = int(self.L.simlod_render_buffer_bytes(W, H))
-        if self.render_buffer.numel() < need:
-            self.render_buffer = torch.empty(need, dtype=torch.uint8, device=self.device)
-        if self.colorbuffer.numel() < W * H:
-            self.colorbuffer = torch.zeros(W * H, dtype=torch.int32, device=self.device)
-        args = [self._p(self.render_buffer), up, self._p(self.nodes), self._p(self.colorbuffer), self._p(self.stats), self._p(self.frame_start), None, self._stream()]
         if rccl_comm is not None:
-            _check(self.L.simlod_render_frame_rccl(*args, ctypes.c_void_p(rccl_comm)), "simlod_render_frame_rccl")
+            self._launch_frame(uniforms, lambda *args: self.L.simlod_render_frame_rccl(*args, ctypes.c_void_p(rccl_comm)), "simlod_render_frame_rccl")
         else:
             cb = self.REDUCE_FN(lambda user, plane, data, count, eb, op, stream: int(reduce(plane, data, count, eb, op, stream))) if reduce is not None else None
-            _check(self.L.simlod_render_frame_composed(*args, ctypes.cast(cb, ctypes.c_void_p) if cb is not None else None, None), "simlod_render_frame_composed")
-        self._frame_size = (W, H)
+            self._launch_frame(uniforms, lambda *args: self.L.simlod_render_frame_composed(*args, ctypes.cast(cb, ctypes.c_void_p) if cb is not None else None, None), "simlod_render_frame_composed")
+
+    def frame_layout(self, W, H):
+        """Where everything lies in the render buffer for a W x H frame: the abi.frame_layout_dtype record of simlod_render_frame_layout."""
+        if (W, H) not in self._layouts:
+            rec = np.zeros(1, dtype=abi.frame_layout_dtype)
+            _check(self.L.simlod_render_frame_layout(W, H, ctypes.c_void_p(rec.ctypes.data)), "simlod_render_frame_layout")
+            self._layouts[(W, H)] = {n: int(rec[n][0]) for n in abi.frame_layout_dtype.names}
+        return self._layouts[(W, H)]
+
+    def _plane(self, name, elem_bytes, dtype):
+        W, H = self._frame_size
+        off = self.frame_layout(W, H)[name]
+        return self.render_buffer[off: off + W * H * elem_bytes].view(dtype)
+
+    def _counter(self, name):
+        """Counter `name` (abi.COUNTERS) of the last frame as a one-element device view."""
+        lay = self.frame_layout(*self._frame_size)
+        off = lay["counters"] + abi.COUNTERS[name] * lay["counterStride"]
+        return self.render_buffer[off: off + 4].view(torch.int32)
+
+    def _work_word(self, name, W, H):
+        """Work word `name` (abi.WORK_WORDS) of the last W x H frame as a one-element device view."""
+        off = self.frame_layout(W, H)["work"] + abi.WORK_WORDS[name] * 4
+        return self.render_buffer[off: off + 4].view(torch.int32)
 
     def depth_plane(self):
         """The HQS depth plane as an int32 view (positive float bits: integer MIN == float MIN)."""
-        W, H = self._frame_size
-        off = int(self.L.simlod_render_depth_plane_offset(W, H))
-        return self.render_buffer[off: off + W * H * 4].view(torch.int32)
+        return self._plane("depth", 4, torch.int32)
 
     def sum_planes(self):
         """{R, G, B, count} per pixel as an int32 view."""
-        W, H = self._frame_size
-        off = int(self.L.simlod_render_sum_planes_offset(W, H))
-        return self.render_buffer[off: off + W * H * 16].view(torch.int32)
+        return self._plane("sums", 16, torch.int32)
 
     def framebuffer_words(self):
         """depth|colour words as an int64 view (the sign bit is never set)."""
-        W, H = self._frame_size
-        off = int(self.L.simlod_render_framebuffer_offset())
-        return self.render_buffer[off: off + W * H * 8].view(torch.int64)
+        return self._plane("framebuffer", 8, torch.int64)
 
     def visible_records(self):
         """(bytes of the visible-node array, number of visible nodes of the last frame as a device tensor — no host sync)."""
@@ -416,33 +422,35 @@ class DeviceOctree:
     def visible_records_early(self):
         """As visible_records, but the count comes from the frame's own counter (valid once part 0 of the frame has run, clamped by the
         consumer): the all-gather of the visible nodes can be issued right behind part 0 and overlap the rest of the frame."""
-        off = abi.MAX_VISIBLE_NODES * abi.node_dtype.itemsize
-        return self.render_buffer, self.render_buffer[off: off + 4].view(torch.int32)
+        return self.render_buffer, self._counter("C_VISIBLE")
 
     def lists_read_through_table(self):
-        """How many chunk lists the last frame's r_visible read through the builder's chunk table instead of chasing `next`
-        (render.hip: counter 5 of the frame counters behind the visible-node array)."""
-        off = abi.MAX_VISIBLE_NODES * abi.node_dtype.itemsize + 5 * 16
-        return int(self.render_buffer[off: off + 4].view(torch.int32).item())
+        """How many chunk lists the last frame's r_visible read through the builder's chunk table instead of chasing `next`."""
+        return int(self._counter("C_TABLE_LISTS").item())
 
     def samples_outside_tiles(self):
         """How many samples the last frame's first draw pass sent down the global-atomic path — outside their draw item's LDS tile, or drawn
-        without one (render.hip: counter 6 of the frame counters behind the visible-node array)."""
-        off = abi.MAX_VISIBLE_NODES * abi.node_dtype.itemsize + 6 * 16
-        return int(self.render_buffer[off: off + 4].view(torch.int32).item())
+        without one."""
+        return int(self._counter("C_OUTSIDE_TILES").item())
 
     def samples_binned(self, width, height):
-        """How many samples the last frame's first draw pass sorted into the screen bins (render.hip r_overflow: word 13 of the frame's work
-        area, behind the framebuffer plane)."""
-        off = int(self.L.simlod_render_framebuffer_offset()) + (width * height * 8 + 15) // 16 * 16 + 13 * 4
-        return int(self.render_buffer[off: off + 4].view(torch.int32).item())
+        """How many samples the last frame's first draw pass sorted into the screen bins (r_overflow rasterises them)."""
+        return int(self._work_word("W_BINNED", width, height).item())
+
+    def draw_items(self, W, H):
+        """The draw items of the last W x H frame, all size classes, as a host array of abi.draw_item_dtype (tools/raster_items.py, raster_big.py)."""
+        lay = self.frame_layout(W, H)
+        work = self.render_buffer[lay["work"]: lay["work"] + abi.WORK_WORDS["W_COUNT"] * 4].cpu().numpy().view(np.uint32)
+        size, cap = lay["drawItemBytes"], lay["maxDrawItems"]
+        return np.concatenate([self.render_buffer[lay["items"] + cl * cap * size: lay["items"] + (cl * cap + min(int(work[abi.WORK_WORDS["W_ITEMS0"] + cl]), cap)) * size]
+                               .cpu().numpy().view(abi.draw_item_dtype) for cl in range(lay["itemClasses"])])
 
     # -- readback ------------------------------------------------------------------------------------------------
     def read_stats(self):
         return self.stats.cpu().numpy().view(abi.stats_dtype)[0].copy()
 
     def framebuffer(self, W, H):
-        off = int(self.L.simlod_render_framebuffer_offset())
+        off = self.frame_layout(W, H)["framebuffer"]
         return self.render_buffer[off: off + W * H * 8].cpu().numpy().view(np.uint64).copy()
 
     def color(self, W, H):

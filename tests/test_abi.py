@@ -36,6 +36,24 @@ def test_layout_queries(built_libs):
     assert L.simlod_render_framebuffer_offset() == 100_000 * 152 + 7 * 16 + 32 + 16_000_000
     assert L.simlod_render_buffer_bytes(1920, 1080) <= 200_000_000          # fits the host's cptr_renderbuffer (main.cpp:555)
     assert L.simlod_construct_buffer_min_bytes() <= 300_000_000             # fits the host's 300 MB cptr_buffer (main.cpp:554)
+    # the whole layout in one record (simlod_render_frame_layout): it agrees with the three older queries and the buffer size at every size
+    # tests/host/render_layout_check.cpp looks at, and its regions follow one another
+    order = ["visible", "counters", "lines", "vertices", "framebuffer", "work", "items", "depth", "colour", "sums", "dir", "binSegs", "binSegCount", "binStats", "binPool", "bytes"]
+    for W, H in [(1, 1), (3, 3), (128, 96), (129, 97), (1920, 1080), (1921, 1081), (2560, 1440), (3840, 2160), (4096, 2160)]:
+        rec = np.zeros(1, dtype=abi.frame_layout_dtype)
+        assert L.simlod_render_frame_layout(W, H, ctypes.c_void_p(rec.ctypes.data)) == 0
+        lay = {n: int(rec[n][0]) for n in abi.frame_layout_dtype.names}
+        assert lay["framebuffer"] == L.simlod_render_framebuffer_offset() and lay["bytes"] == L.simlod_render_buffer_bytes(W, H), (W, H)
+        assert lay["depth"] == L.simlod_render_depth_plane_offset(W, H) and lay["sums"] == L.simlod_render_sum_planes_offset(W, H), (W, H)
+        assert [lay[n] for n in order] == sorted(lay[n] for n in order) and lay["vertices"] <= lay["probe"] < lay["framebuffer"], (W, H)
+        assert (lay["counterStride"], lay["drawItemBytes"], lay["binSegBytes"]) == (16, abi.draw_item_dtype.itemsize, 8)
+        assert lay["lines"] == lay["counters"] + abi.COUNTERS["C_COUNT"] * lay["counterStride"] and lay["items"] - lay["work"] >= 4 * (abi.WORK_WORDS["W_READY"] + 1)
+        assert lay["depth"] == lay["items"] + lay["itemClasses"] * lay["maxDrawItems"] * lay["drawItemBytes"]
+        assert lay["binTiles"] == (((W >> 5) + 1) * ((H >> 5) + 1) if (W, H) != (4096, 2160) else 0) and lay["binTilesX"] == (W >> 5) + 1
+    rec = np.zeros(1, dtype=abi.frame_layout_dtype)
+    assert L.simlod_render_frame_layout(64, 64, None) != 0
+    assert L.simlod_render_frame_layout(0, 64, ctypes.c_void_p(rec.ctypes.data)) != 0 and L.simlod_render_frame_layout(64, 0, ctypes.c_void_p(rec.ctypes.data)) != 0
+    assert not rec.view(np.uint8).any()
 
 
 def test_program_surface_mirrors_cuda_modular_program(built_libs):
@@ -68,6 +86,20 @@ def test_numpy_mirrors_match_the_header():
             continue
         assert dt.fields[field][1] == int(off), (struct, field)
     assert abi.alloc_round(262144) == 262160 and abi.alloc_round(16016) == 16032
+    # SimlodFrameLayout (include/simlod_hip.h): the same fields in the same order, all uint64, and the size the header asserts
+    hip = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "simlod_hip.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct SimlodFrameLayout \{(.*?)\} SimlodFrameLayout;", hip, flags=re.S).group(1)
+    assert set(re.findall(r"\b(\w+_t)\b", body)) == {"uint64_t"}
+    assert tuple(re.findall(r"\b(?!uint64_t\b)(\w+)\s*[,;]", body)) == abi.frame_layout_dtype.names
+    assert all(abi.frame_layout_dtype.fields[n] == (np.dtype("<u8"), 8 * k) for k, n in enumerate(abi.frame_layout_dtype.names))
+    assert int(re.search(r"sizeof\(SimlodFrameLayout\) == (\d+)", hip).group(1)) == abi.frame_layout_dtype.itemsize
+    # the counter and work-word indices: the enums of simlod_amd/csrc/render_layout.hpp, name by name
+    layout = open(os.path.join(ROOT, "simlod_amd", "csrc", "render_layout.hpp")).read()
+    enums = " ".join(re.findall(r"^enum \{(.*?)\};", re.sub(r"//[^\n]*", "", layout), flags=re.S | re.M))
+    values = {}
+    for name, value in re.findall(r"\b([CW]_[A-Z0-9_]+) = (\w+)", enums):
+        values[name] = int(value) if value.isdigit() else values[value]
+    assert {k: v for k, v in values.items() if k.startswith("C_")} == abi.COUNTERS and {k: v for k, v in values.items() if k.startswith("W_")} == abi.WORK_WORDS
 
 
 def test_runtime_refuses_to_run_without_gpu(built_libs):

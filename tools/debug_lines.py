@@ -26,12 +26,13 @@ ld = np.nonzero(fd != f0)[0]; lo = np.nonzero(fo != f0)[0]
 print("line pixels dev", len(ld), "oracle", len(lo), "only dev", len(np.setdiff1d(ld, lo)), "only oracle", len(np.setdiff1d(lo, ld)))
 
 import torch, oracle
-off_lines = 100000*152 + 7*16
+lay = dev.frame_layout(Wd, Hd)
+off_lines = lay["lines"]
 cnt = int(dev.render_buffer[off_lines:off_lines+4].cpu().numpy().view(np.uint32)[0])
 # re-render with lines to refill vertices (last render was without)
 u["showBoundingBox"] = 1; dev.render(u); torch.cuda.synchronize()
 cnt = int(dev.render_buffer[off_lines:off_lines+4].cpu().numpy().view(np.uint32)[0])
-verts = dev.render_buffer[off_lines+32: off_lines+32+cnt*16].cpu().numpy().copy()
+verts = dev.render_buffer[lay["vertices"]: lay["vertices"]+cnt*16].cpu().numpy().copy()
 fb2 = f0.copy()
 uu = np.ascontiguousarray(u).reshape(1)
 oracle.port_lib().oracle_rasterize_lines(ctypes.c_void_p(uu.ctypes.data), ctypes.c_void_p(verts.ctypes.data), cnt, ctypes.c_void_p(fb2.ctypes.data))

@@ -49,15 +49,12 @@ for name, Tc in (("bird", T), ("close", T_close)):
         print(f"{name:5s} {'hqs  ' if hqs else 'plain'} {e0.elapsed_time(e1) / 20:7.4f} ms/frame  visible {int(s['numVisiblePoints']) + int(s['numVisibleVoxels'])} samples in {int(s['numVisibleNodes'])} nodes | us per kernel (one stream, events): {ks}", flush=True)
 
 # per draw item of the bird HQS frame's COLOUR pass (DrawItem::took: a library built with -DSIMLOD_MEASURE=1, SIMLOD_HIP_LIB=...; zeros otherwise)
-item_dtype = np.dtype([("chunks", "<u8"), ("samples", "<u4"), ("visibleIdx", "<u4"), ("tileX", "<i4"), ("tileY", "<i4"), ("tileW", "<u2"), ("tileH", "<u2"), ("took", "<u4")])
 for name, Tc in (("bird", T), ("close", T_close)):
     uc = dev.uniforms(W, H, Tc, box, hqs=True)
     for _ in range(2):
         dev.render(uc)
     torch.cuda.synchronize()
-    off_work = int(dev.L.simlod_render_framebuffer_offset()) + (W * H * 8 + 15) // 16 * 16
-    work = dev.render_buffer[off_work: off_work + 64].cpu().numpy().view(np.uint32)
-    it = np.concatenate([dev.render_buffer[off_work + 256 + cl * 150000 * 32: off_work + 256 + (cl * 150000 + int(work[8 + cl])) * 32].cpu().numpy().view(item_dtype) for cl in range(4)])
+    it = dev.draw_items(W, H)
     us = it["took"] / 100.0
     if us.sum() == 0:
         break

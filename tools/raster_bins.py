@@ -20,12 +20,10 @@ dev.add_points(u0, pts)
 for _ in range(3):
     dev.render(u0)
 torch.cuda.synchronize()
-px = W * H
-a16 = lambda v: (v + 15) // 16 * 16
-tx, ty = (W >> 5) + 1, (H >> 5) + 1
-tiles = tx * ty
-off = int(dev.L.simlod_render_framebuffer_offset()) + a16(px * 8) + 256 + 150000 * 4 * 32 + a16(px * 4) + a16(px * 8) + px * 16 + 2_000_000 * 8 + 3_000_000 * 16 + tiles * 256 * 8 + a16(tiles * 4)
-st = dev.render_buffer[off: off + tiles * 8].cpu().numpy().view(np.uint32).reshape(tiles, 2)
+lay = dev.frame_layout(W, H)
+tx, tiles = lay["binTilesX"], lay["binTiles"]
+ty = tiles // tx
+st = dev.render_buffer[lay["binStats"]: lay["binStats"] + tiles * lay["binSegBytes"]].cpu().numpy().view(np.uint32).reshape(tiles, 2)
 entries, segs, took = st[:, 0].astype(np.int64), st[:, 1] >> 20, (st[:, 1] & 0xfffff) / 100.0
 print(f"{tiles} bins ({tx} x {ty}); with entries: {(entries > 0).sum()}; entries {entries.sum()}; binned {dev.samples_binned(W, H)}; outside {dev.samples_outside_tiles()}")
 order = np.argsort(-took)[:12]

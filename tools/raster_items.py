@@ -18,21 +18,12 @@ dev = DeviceOctree("cuda:0", persistent_bytes=8 << 30, max_pixels=W * H)
 u0 = dev.uniforms(W, H, T, box, hqs=False)
 dev.reset(u0)
 dev.add_points(u0, pts)
-item_dtype = np.dtype([("chunks", "<u8"), ("samples", "<u4"), ("visibleIdx", "<u4"), ("tileX", "<i4"), ("tileY", "<i4"), ("tileW", "<u2"), ("tileH", "<u2"), ("took", "<u4")])
 for name, Tc in [q for q in (("bird", T), ("close", T_close)) if q[0] in os.environ.get("PRESETS", "bird,close").split(",")]:
     u = dev.uniforms(W, H, Tc, box, hqs=False)
     for _ in range(3):
         dev.render(u)
     torch.cuda.synchronize()
-    off_work = int(dev.L.simlod_render_framebuffer_offset()) + (W * H * 8 + 15) // 16 * 16
-    work = dev.render_buffer[off_work: off_work + 64].cpu().numpy().view(np.uint32)
-    cap = 150000
-    items = []
-    for cl in range(4):
-        n = int(work[8 + cl])
-        a = dev.render_buffer[off_work + 256 + cl * cap * 32: off_work + 256 + (cl * cap + n) * 32].cpu().numpy().view(item_dtype)
-        items.append(a)
-    it = np.concatenate(items)
+    it = dev.draw_items(W, H)
     us = it["took"] / 100.0
     print(f"== {name}: {len(it)} items, {int(it['samples'].sum())} samples; sum of item times {us.sum():.0f} us = {us.sum() / 256:.1f} us per workgroup of 256; longest item {us.max():.1f} us")
     kinds = {"sorting": it["tileX"] == -2, "no tile": it["tileX"] == -1, "tile 128x128": (it["tileX"] >= 0) & (it["tileW"].astype(int) * it["tileH"] >= 128 * 128), "smaller tile": (it["tileX"] >= 0) & (it["tileW"].astype(int) * it["tileH"] < 128 * 128)}

@@ -6,7 +6,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-from simlod_amd import camera, synthetic, abi
+from simlod_amd import camera, synthetic
 from simlod_amd.runtime import DeviceOctree
 
 pts, box = synthetic.terrain(36_000_000, seed=7)
@@ -16,7 +16,7 @@ dev = DeviceOctree("cuda:0", persistent_bytes=8 << 30, max_pixels=W * H)
 u0 = dev.uniforms(W, H, T, box, hqs=False)
 dev.reset(u0)
 dev.add_points(u0, pts)
-off = abi.MAX_VISIBLE_NODES * abi.node_dtype.itemsize + 7 * 16 + 32 + 8_000_000
+off = dev.frame_layout(W, H)["probe"]
 names = ["first start", "numNodes loaded (last)", "node fields + geometry (last)", "reservations returned (last)", "items stored (last)", "visible_nodes done (last)",
          "kernel end (last)", "kernel end (first)", "frame-ready seen (last)", "box on screen (last)", "before reservations (last)", "had to wait for frame-ready (last)"]
 for hqs in (False, True):
