@@ -515,6 +515,99 @@ int simlod_query_rays(const SimlodNode* nodes, const SimlodStats* stats, const S
                       uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
                       SimlodRayHit* hits, SimlodRayCounts* counts, void* stream);
 
+/* ---- neighbour queries: the k nearest samples within a radius of each position of a batch ------------------------------------------------------
+ * simlod_query_neighbours answers "which samples lie around this position" for up to 2^20 positions at once: per query the k <= 16 samples
+ * nearest to `center` among those within `radius` of it, among the samples of the nodes simlod_export_octree(maxLevel, select) selects, and how
+ * many samples lie within the radius at all.  The source is only read.
+ *
+ * The box is the builder's, as for region queries (min = uniforms.boxMin, size = the largest fp32 extent).  All geometry is fp64 computed from the
+ * fp32 inputs without fused multiply-add, every sum in the order written here.  s, e, lo_a, hi_a of a node are those of region-query rule 1 (the
+ * cube inflated by one level-20 cell).  c_a is the centre, r the radius, rr = r*r.
+ *  0. The table.  Exactly as ray-query rule 0: the nodes considered are the entries of simlod_export_octree(maxLevel, select) on the same octree,
+ *     select ALL, CUT or VISIBLE (VISIBLE is refused as the export refuses it when no frame ran).  SimlodNeighbour.node is an index into THAT
+ *     table and `ordinal` an index into that node's sample range: export.samples[export.nodes[node].firstSample + ordinal] is the neighbour's
+ *     sample.  With table != NULL the call also writes that table, byte for byte the export's; tableCapacity bounds the walk either way.
+ *  1. Valid queries.  A query is valid iff its four floats are finite and radius >= 0 (radius 0 is valid).  An invalid query forms no pair, is
+ *     counted in numInvalid, and gets k miss records and within = 0 (checked on the device: queries may come from a kernel).
+ *  2. The sample test.  With p_a = s_a - c_a per component of the sample s, d2 = (px*px + py*py) + pz*pz; the sample passes iff d2 <= rr (a NaN
+ *     fails).
+ *  3. Pairs.  A valid query and a selected table entry with numSamples > 0 form a PAIR iff the entry and all its listed ancestors pass the
+ *     sphere-cube test: ex_a = max(lo_a - c_a, 0, c_a - hi_a), g2 = (ex_x*ex_x + ex_y*ex_y) + ex_z*ex_z; the node passes iff g2 <= rr.  numPairs
+ *     is the number of pairs, numCandidates the sum of numSamples over the pairs; both are defined by this rule alone, whatever work the kernels
+ *     skip.  For finite samples in the half-open box the culling never changes a result: such a sample lies in its node's exact cube and in
+ *     every ancestor's up to the builder's quantisation slack (about size * 2^-22), so per axis |p_a| exceeds ex_a by at least what e leaves
+ *     over that slack (about size * 2^-21, many orders above the fp64 rounding of the differences, about size * 2^-52) wherever ex_a > 0, and
+ *     |p_a| >= 0 = ex_a elsewhere; squares of non-negative numbers and sums taken in the same order are monotone under IEEE rounding, so
+ *     g2 <= d2, and d2 <= rr implies g2 <= rr for the node and each of its ancestors.  OUTSIDE THE CONTRACT, as in region-query rule 4 and for
+ *     rays: samples outside that box, on its max faces or with non-finite coordinates; such a sample is a candidate iff the node it is stored
+ *     in forms a pair.
+ *  4. The result.  neighbours[q*k .. q*k + k) holds the first k of query q's passing samples (those of its pairs that pass rule 2) in the total
+ *     order (d2, node, ordinal), ascending; the places behind them hold the miss record (d2 = +infinity, node = ordinal = 0xffffffff, a zero
+ *     sample).  within[q] is the number of passing samples among the query's pairs, however large.  numFound is the sum over the queries of
+ *     min(k, within), numWithin the sum of within.  Everything returned is the prefix of one total order or a sum: a pure function of the
+ *     octree image and the queries.  A query centred on a sample finds that sample at d2 = 0: callers who want the OTHER points ask for k + 1.
+ *  5. neighbours == NULL: count only, and then `within` must be NULL too — the counts (and the table, if asked for) are complete except that
+ *     numFound = numWithin = 0; no sample is tested, nothing else is written, and simlod_neighbours_buffer_min_bytes(cap, bound, n, k, 0, 0) of
+ *     scratch suffices.  With results, scratch sized from the numPairs and numCandidates of a count-only call always suffices; a buffer that
+ *     holds the walk but not the pairs sets SIMLOD_EXPORT_ERR_CAPACITY and then NO neighbour or within record is written; a walk error
+ *     (ERR_NODE_COUNT, ERR_SHORT_LIST, the table capacity) likewise. */
+typedef struct SimlodSphere {          /* DEVICE memory */
+	float    center[3];                /* world coordinates (the uniforms' box)                                 */
+	float    radius;                   /* >= 0                                                                  */
+} SimlodSphere;
+typedef struct SimlodNeighbour {       /* DEVICE memory, k per query, in query order (SimlodRayHit's shape) */
+	double      d2;                    /* squared distance (rule 2); miss: +infinity                            */
+	uint32_t    node;                  /* table index of the node that holds it; miss: 0xffffffff               */
+	uint32_t    ordinal;               /* index among that node's samples in chunk-list order; miss: 0xffffffff */
+	SimlodPoint sample;                /* the 16 bytes of the sample; miss: zeros                               */
+} SimlodNeighbour;
+typedef struct SimlodNeighbourCounts { /* written by the device */
+	uint32_t numNodes;                 /* table entries                                                         */
+	uint32_t error;                    /* SIMLOD_EXPORT_ERR_* bits                                              */
+	uint32_t numInvalid;               /* queries that fail rule 1                                              */
+	uint32_t k;                        /* the call's k                                                          */
+	uint64_t numPairs;                 /* rule 3                                                                */
+	uint64_t numCandidates;            /* rule 3                                                                */
+	uint64_t numFound;                 /* neighbour records that are not the miss record (rule 4)               */
+	uint64_t numWithin;                /* the sum of within (rule 4)                                            */
+} SimlodNeighbourCounts;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodSphere) == 16, "Sphere");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSphere, radius) == 12, "Sphere.radius");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodNeighbour) == 32, "Neighbour");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodNeighbour, node) == 8, "Neighbour.node");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodNeighbour, ordinal) == 12, "Neighbour.ordinal");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodNeighbour, sample) == 16, "Neighbour.sample");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodNeighbourCounts) == 48, "NeighbourCounts");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodNeighbourCounts, numInvalid) == 8, "NeighbourCounts.numInvalid");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodNeighbourCounts, k) == 12, "NeighbourCounts.k");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodNeighbourCounts, numPairs) == 16, "NeighbourCounts.numPairs");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodNeighbourCounts, numCandidates) == 24, "NeighbourCounts.numCandidates");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodNeighbourCounts, numFound) == 32, "NeighbourCounts.numFound");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodNeighbourCounts, numWithin) == 40, "NeighbourCounts.numWithin");
+#define SIMLOD_NEIGHBOURS_MAX (1u << 20)
+#define SIMLOD_NEIGHBOURS_MAX_K 16u
+
+/* Bytes of the `scratch` buffer a neighbour query needs: a table of up to nodeCapacity entries whose selected nodes hold up to sampleBound
+ * samples (Stats.numPoints + Stats.numVoxels always suffices), numQueries queries, and — for a call with results — the numPairs and
+ * numCandidates a count-only call reported (0, 0: enough for a count-only call).  The sum of a part that depends on nodeCapacity and numQueries
+ * only (the ray query's for as many rays), 32 bytes per chunk item for sampleBound / 1000 + nodeCapacity + 1 items, 16 + 16 * (k + 1) bytes per
+ * pair (its record and one partial result: k entries and a count) and 16 * (k + 1) bytes per further thousand candidates.  What a call with
+ * results really needs is the same sum with the chunks the table's selected nodes have (ceil(numSamples / 1000) each) in the place of that
+ * item bound: one byte less sets SIMLOD_EXPORT_ERR_CAPACITY. */
+uint64_t simlod_neighbours_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numQueries, uint32_t k, uint64_t numPairs,
+                                            uint64_t numCandidates);
+
+/* The neighbour query (rules above).  Asynchronous on `stream`; everything in between lives in `scratch`.  hipErrorInvalidValue with nothing
+ * enqueued and nothing touched: a null pointer other than `table` / `neighbours` / `within`, within != NULL while neighbours == NULL,
+ * numQueries == 0 or > SIMLOD_NEIGHBOURS_MAX, k == 0 or > SIMLOD_NEIGHBOURS_MAX_K, `select` other than ALL / CUT / VISIBLE (VISIBLE without a
+ * frame), scratchBytes below simlod_neighbours_buffer_min_bytes(tableCapacity, 0, numQueries, k, 0, 0).  `within` may be NULL in a call with
+ * neighbours.  A scratch buffer too small for the chunk items or the pairs sets SIMLOD_EXPORT_ERR_CAPACITY on the device.  While the builder's
+ * chunk table for `nodes` is valid the first chunks of each list come from it, the rest by `next` (as simlod_export_octree). */
+int simlod_query_neighbours(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodSphere* queries,
+                            uint32_t numQueries, uint32_t k, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                            SimlodExportNode* table, uint32_t tableCapacity, SimlodNeighbour* neighbours, uint32_t* within,
+                            SimlodNeighbourCounts* counts, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

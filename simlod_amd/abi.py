@@ -147,6 +147,15 @@ ray_counts_dtype = np.dtype({"names": ["numNodes", "error", "numHits", "numInval
                              "formats": ["<u4", "<u4", "<u4", "<u4", "<u8", "<u8"], "offsets": [0, 4, 8, 12, 16, 24], "itemsize": 32})
 assert ray_dtype.itemsize == 48 and ray_hit_dtype.itemsize == 32 and ray_counts_dtype.itemsize == 32
 
+# ---- neighbour queries (include/simlod_hip.h, "neighbour queries") -----------------------------------------------------------------------
+NEIGHBOURS_MAX = 1 << 20
+NEIGHBOURS_MAX_K = 16
+sphere_dtype = np.dtype({"names": ["center", "radius"], "formats": [("<f4", 3), "<f4"], "offsets": [0, 12], "itemsize": 16})
+neighbour_dtype = np.dtype({"names": ["d2", "node", "ordinal", "sample"], "formats": ["<f8", "<u4", "<u4", point_dtype], "offsets": [0, 8, 12, 16], "itemsize": 32})
+neighbour_counts_dtype = np.dtype({"names": ["numNodes", "error", "numInvalid", "k", "numPairs", "numCandidates", "numFound", "numWithin"],
+                                   "formats": ["<u4", "<u4", "<u4", "<u4", "<u8", "<u8", "<u8", "<u8"], "offsets": [0, 4, 8, 12, 16, 24, 32, 40], "itemsize": 48})
+assert sphere_dtype.itemsize == 16 and neighbour_dtype.itemsize == 32 and neighbour_counts_dtype.itemsize == 48
+
 # ---- kernel_render's buffer (include/simlod_hip.h simlod_render_frame_layout; simlod_amd/csrc/render_layout.hpp states the layout) -------
 frame_layout_dtype = np.dtype([(n, "<u8") for n in (
     "visible", "counters", "lines", "vertices", "probe", "framebuffer", "work", "items", "depth", "colour", "sums", "dir",

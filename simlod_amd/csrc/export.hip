@@ -17,6 +17,8 @@
 // k_i_groot (export_grids.inc); k_i_finish then also writes the builder's counters as k_reset does.
 // Region query (simlod_query_region): k_q_hier -> k_q_dir -> k_q_count -> k_q_scan -> k_q_write, described in export_region.inc.
 // Ray query (simlod_query_rays): k_r_hier -> k_q_dir -> k_r_pairs<count> -> k_r_scan -> k_r_pairs<fill> -> k_r_test -> k_r_reduce, in export_rays.inc.
+// Neighbour query (simlod_query_neighbours): k_r_hier -> k_q_dir -> k_n_pairs<count> -> k_n_scan -> k_n_pairs<fill> -> k_n_test -> k_n_reduce, in
+// export_neighbours.inc (the descent, the layout and the pair records are the ray query's).
 // Everything in between lives in the caller's scratch buffer (export_min_bytes), never in kernel_construct's momentary buffer: the builder's
 // recycle stack and the chunk table export reads are there.
 // One translation unit: the device code lies in export_*.inc, the host side — the scratch bounds and the launchers — here.
@@ -38,6 +40,7 @@ namespace {
 #include "export_table.inc"    // hier_walk, k_x_hier, k_x_scan, k_x_dir
 #include "export_region.inc"   // QueryGeom, classify, QItem, QueryLayout, QueryArgs, k_q_hier, k_q_dir, k_q_count, k_q_scan, k_q_write
 #include "export_rays.inc"     // the ray records, RayLayout, RayArgs, k_r_hier, k_r_pairs, k_r_scan, k_r_test, k_r_reduce
+#include "export_neighbours.inc"  // NbArgs, sphere_load, sphere_cube, k_n_pairs, k_n_scan, k_n_test, k_n_reduce
 #include "export_import.inc"   // ImportArgs, link_chunk_list, k_i_validate, k_i_nodes, k_i_finish
 #include "export_grids.inc"    // the buildable import's grids: k_i_gleaf, k_i_gdown, k_i_groot
 
@@ -154,6 +157,50 @@ int launch_rays(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats,
 		SIMLOD_LAUNCH(k_r_pairs<1>, dim3(rayGrid), dim3(LANE_TPB), stream, r);
 		SIMLOD_LAUNCH(k_r_test, dim3(copy_grid(a.lay.itemCap)), dim3(LANE_TPB), stream, r);
 		SIMLOD_LAUNCH(k_r_reduce, dim3(rayGrid), dim3(LANE_TPB), stream, r);
+	}
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+uint64_t neighbours_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numQueries, uint32_t k, uint64_t numPairs, uint64_t numCandidates) {
+	return RayLayout(nodeCapacity, numQueries).x.items + (sampleBound / SIMLOD_POINTS_PER_CHUNK + nodeCapacity + 1u) * sizeof(QItem) +
+	       numPairs * (sizeof(RayPair) + nb_part_bytes(k)) + (numCandidates / SIMLOD_POINTS_PER_CHUNK) * nb_part_bytes(k);
+}
+
+int launch_neighbours(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodSphere* queries,
+                      uint32_t numQueries, uint32_t k, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
+                      uint32_t tableCapacity, SimlodNeighbour* neighbours, uint32_t* within, SimlodNeighbourCounts* counts, hipStream_t stream) {
+	if (nodes == nullptr || stats == nullptr || u == nullptr || queries == nullptr || scratch == nullptr || counts == nullptr) return (int)hipErrorInvalidValue;
+	if (within != nullptr && neighbours == nullptr) return (int)hipErrorInvalidValue;
+	if (numQueries == 0u || numQueries > SIMLOD_NEIGHBOURS_MAX || k == 0u || k > SIMLOD_NEIGHBOURS_MAX_K || select > SIMLOD_EXPORT_VISIBLE) return (int)hipErrorInvalidValue;
+	if (scratchBytes < neighbours_min_bytes(tableCapacity, 0u, numQueries, k, 0u, 0u)) return (int)hipErrorInvalidValue;
+	if (select == SIMLOD_EXPORT_VISIBLE && !array_state(ctx, nodes).rendered) return (int)hipErrorInvalidValue;
+	const RayLayout rl(tableCapacity, numQueries);
+	NbArgs n{};
+	RayArgs& r = n.r;
+	ExportArgs& a = r.x;
+	a.nodes = nodes; a.stats = stats; a.maxLevel = maxLevel; a.select = select; a.cap = tableCapacity;
+	a.scratch = reinterpret_cast<uint8_t*>(scratch);
+	a.table = table != nullptr ? table : reinterpret_cast<SimlodExportNode*>(a.scratch + rl.tab);
+	a.lay = rl.x; a.lay.take_rest(scratchBytes);
+	float size, minx, miny, minz;
+	octree_box(u, size, minx, miny, minz);                                      // voxels.cu:860-863
+	r.size = (double)size; r.min[0] = (double)minx; r.min[1] = (double)miny; r.min[2] = (double)minz;
+	r.numRays = numQueries; r.scratchBytes = scratchBytes; r.at = rl.at;
+	n.queries = queries; n.neighbours = neighbours; n.within = within; n.counts = counts; n.k = k;
+	bind_leaf_table(ctx, nodes, a);
+	QueryArgs q{};                                                              // k_q_dir's view of the same buffers
+	q.x = a; q.cls = rl.at.cls;
+	const uint32_t qGrid = (numQueries + RAY_WAVES - 1u) / RAY_WAVES;
+	SIMLOD_LAUNCH(k_r_hier, dim3(1), dim3(WG_TPB), stream, r);
+	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                          // k_q_dir: one wave per table entry
+	if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
+	SIMLOD_LAUNCH(k_n_pairs<0>, dim3(qGrid), dim3(LANE_TPB), stream, n);
+	SIMLOD_LAUNCH(k_n_scan, dim3(1), dim3(WG_TPB), stream, n);
+	if (neighbours != nullptr) {
+		SIMLOD_LAUNCH(k_n_pairs<1>, dim3(qGrid), dim3(LANE_TPB), stream, n);
+		SIMLOD_LAUNCH(k_n_test, dim3(copy_grid(a.lay.itemCap)), dim3(LANE_TPB), stream, n);
+		SIMLOD_LAUNCH(k_n_reduce, dim3(qGrid), dim3(LANE_TPB), stream, n);
 	}
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();

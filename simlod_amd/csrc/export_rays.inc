@@ -1,5 +1,5 @@
 // export_rays.inc — part of export.hip: ray queries.  The ray records, RayLayout, RayArgs, k_r_hier, RayD, ray_load, slab, sample_t, hit_less,
-// wave_hit_min, k_r_pairs, k_r_scan, k_r_test, k_r_reduce.
+// wave_hit_min, wave_descend, k_r_pairs, k_r_scan, k_r_test, k_r_reduce.
 // ---- ray query ------------------------------------------------------------------------------------------------------------------------
 // simlod_query_rays (simlod_hip.h, "ray queries"): seven launches on the caller's stream, four for a count-only call.
 //   k_r_hier    ONE workgroup: k_x_hier's walk (the table is the export's, into the caller's array or into scratch), then k_x_scan's scans:
@@ -143,6 +143,57 @@ __device__ __forceinline__ Hit wave_hit_min(double bt, uint32_t bn, uint32_t bo)
 	return Hit{bt, bn, bo};
 }
 
+// One WAVE descends the table depth first with a bucket of pending nodes per level (fc / mk: this wave's buckets in LDS): a turn takes up to
+// eight nodes of the deepest level that has any and probes their 64 children, one lane each, so a bucket never holds more than 64.
+// probe(entry): does the node pass (rule 3 of the ray query, rule 3 of the neighbour query); on_pairs(isPair per lane, table index, samples)
+// once per turn for the selected entries with samples among those that passed.  Shared by k_r_pairs and k_n_pairs.
+template <class Probe, class OnPairs>
+__device__ __forceinline__ void wave_descend(const ExportArgs& x, uint32_t numListed, uint32_t (&fc)[RAY_LEVELS][SIMLOD_WAVE], uint8_t (&mk)[RAY_LEVELS][SIMLOD_WAVE],
+                                             uint32_t lane, Probe probe, OnPairs on_pairs) {
+	const uint64_t below = (1ull << lane) - 1ull;
+	uint32_t myCnt = 0;                                                            // lane L: the nodes pending at level L
+	int cur = -1;                                                                  // the deepest level that may have any
+	{
+		const SimlodExportNode e = x.table[0];
+		if (probe(e)) {
+			if (e.childMask != 0u) {
+				if (lane == 0u) { fc[0][0] = e.firstChild; mk[0][0] = e.childMask; myCnt = 1u; }
+				cur = 0;
+			}
+			on_pairs(lane == 0u && e.numSamples != 0u && (e.flags & SIMLOD_EXPORT_FLAG_SELECTED) != 0u, 0u, e.numSamples);
+		}
+	}
+	while (cur >= 0) {
+		const uint32_t c = __shfl(myCnt, cur, SIMLOD_WAVE);
+		if (c == 0u) { cur--; continue; }
+		const uint32_t take = min(c, 8u), base = c - take;
+		if ((int)lane == cur) myCnt = base;
+		__builtin_amdgcn_wave_barrier();                                           // (the buckets go from lane to lane through LDS, inside one wave)
+		const uint32_t e = lane >> 3, k = lane & 7u;
+		bool has = false;
+		uint32_t ci = 0;
+		if (e < take) {
+			const uint32_t f = fc[cur][base + e], m = mk[cur][base + e];
+			ci = f + (uint32_t)__popc(m & ((1u << k) - 1u));
+			has = ((m >> k) & 1u) != 0u && ci < numListed;
+		}
+		SimlodExportNode ce{};
+		bool pass = false;
+		if (has) { ce = x.table[ci]; pass = probe(ce); }
+		const bool push = pass && ce.childMask != 0u && cur + 1 < (int)RAY_LEVELS;
+		const uint64_t pb = __ballot(push);
+		__builtin_amdgcn_wave_barrier();
+		if (pb != 0ull) {
+			// (level cur + 1 was empty: cur is the deepest level with anything pending, so a bucket holds at most these 64)
+			if (push) { const uint32_t pos = (uint32_t)__popcll(pb & below); fc[cur + 1][pos] = ce.firstChild; mk[cur + 1][pos] = ce.childMask; }
+			if ((int)lane == cur + 1) myCnt = (uint32_t)__popcll(pb);
+			cur++;
+		}
+		__builtin_amdgcn_wave_barrier();
+		on_pairs(pass && ce.numSamples != 0u && (ce.flags & SIMLOD_EXPORT_FLAG_SELECTED) != 0u, ci, ce.numSamples);
+	}
+}
+
 template <int FILL>
 __global__ __launch_bounds__(LANE_TPB) void k_r_pairs(RayArgs a) {
 	__shared__ uint32_t sh_fc[RAY_WAVES][RAY_LEVELS][SIMLOD_WAVE];                 // pending nodes per level: their firstChild ...
@@ -168,7 +219,6 @@ __global__ __launch_bounds__(LANE_TPB) void k_r_pairs(RayArgs a) {
 		return;
 	}
 	const bool countHits = !FILL && a.hits == nullptr;
-	const uint64_t below = (1ull << lane) - 1ull;
 	uint32_t nPairs = 0, nParts = 0;                                               // this lane's share (count)
 	uint64_t nCand = 0;
 	bool found = false;
@@ -210,47 +260,7 @@ __global__ __launch_bounds__(LANE_TPB) void k_r_pairs(RayArgs a) {
 		}
 	};
 
-	uint32_t myCnt = 0;                                                            // lane L: the nodes pending at level L
-	int cur = -1;                                                                  // the deepest level that may have any
-	{
-		const SimlodExportNode e = x.table[0];
-		if (slab(r, a, e.level, e.X, e.Y, e.Z)) {
-			if (e.childMask != 0u) {
-				if (lane == 0u) { sh_fc[w][0][0] = e.firstChild; sh_mk[w][0][0] = e.childMask; myCnt = 1u; }
-				cur = 0;
-			}
-			on_pairs(lane == 0u && e.numSamples != 0u && (e.flags & SIMLOD_EXPORT_FLAG_SELECTED) != 0u, 0u, e.numSamples);
-		}
-	}
-	while (cur >= 0) {
-		const uint32_t c = __shfl(myCnt, cur, SIMLOD_WAVE);
-		if (c == 0u) { cur--; continue; }
-		const uint32_t take = min(c, 8u), base = c - take;
-		if ((int)lane == cur) myCnt = base;
-		__builtin_amdgcn_wave_barrier();                                           // (the buckets go from lane to lane through LDS, inside one wave)
-		const uint32_t e = lane >> 3, k = lane & 7u;
-		bool has = false;
-		uint32_t ci = 0;
-		if (e < take) {
-			const uint32_t fc = sh_fc[w][cur][base + e], mk = sh_mk[w][cur][base + e];
-			ci = fc + (uint32_t)__popc(mk & ((1u << k) - 1u));
-			has = ((mk >> k) & 1u) != 0u && ci < numListed;
-		}
-		SimlodExportNode ce{};
-		bool pass = false;
-		if (has) { ce = x.table[ci]; pass = slab(r, a, ce.level, ce.X, ce.Y, ce.Z); }
-		const bool push = pass && ce.childMask != 0u && cur + 1 < (int)RAY_LEVELS;
-		const uint64_t pb = __ballot(push);
-		__builtin_amdgcn_wave_barrier();
-		if (pb != 0ull) {
-			// (level cur + 1 was empty: cur is the deepest level with anything pending, so a bucket holds at most these 64)
-			if (push) { const uint32_t pos = (uint32_t)__popcll(pb & below); sh_fc[w][cur + 1][pos] = ce.firstChild; sh_mk[w][cur + 1][pos] = ce.childMask; }
-			if ((int)lane == cur + 1) myCnt = (uint32_t)__popcll(pb);
-			cur++;
-		}
-		__builtin_amdgcn_wave_barrier();
-		on_pairs(pass && ce.numSamples != 0u && (ce.flags & SIMLOD_EXPORT_FLAG_SELECTED) != 0u, ci, ce.numSamples);
-	}
+	wave_descend(x, numListed, sh_fc[w], sh_mk[w], lane, [&](const SimlodExportNode& e) { return slab(r, a, e.level, e.X, e.Y, e.Z); }, on_pairs);
 	if (FILL) return;
 #pragma unroll
 	for (int o = SIMLOD_WAVE / 2; o > 0; o >>= 1) {

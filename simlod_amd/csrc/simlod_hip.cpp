@@ -463,6 +463,20 @@ int simlod_query_rays(const SimlodNode* nodes, const SimlodStats* stats, const S
 	                   counts, (hipStream_t)stream);
 }
 
+uint64_t simlod_neighbours_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numQueries, uint32_t k, uint64_t numPairs,
+                                            uint64_t numCandidates) {
+	return neighbours_min_bytes(nodeCapacity, sampleBound, numQueries, k, numPairs, numCandidates);
+}
+
+int simlod_query_neighbours(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodSphere* queries,
+                            uint32_t numQueries, uint32_t k, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                            SimlodExportNode* table, uint32_t tableCapacity, SimlodNeighbour* neighbours, uint32_t* within,
+                            SimlodNeighbourCounts* counts, void* stream) {
+	if (nodes == nullptr) return (int)hipErrorInvalidValue;
+	return launch_neighbours(context_of(nodes), nodes, stats, uniforms, queries, numQueries, k, maxLevel, select, scratch, scratchBytes, table,
+	                         tableCapacity, neighbours, within, counts, (hipStream_t)stream);
+}
+
 uint64_t simlod_colorfilter_buffer_min_bytes(void) { return colorfilter_min_bytes(default_context().nodeCapacity.load()); }
 
 int simlod_generate_terrain(SimlodPoint* out, uint64_t numPoints, uint64_t firstIndex, uint64_t pointsPerTile, uint32_t seed, uint32_t tilesX,

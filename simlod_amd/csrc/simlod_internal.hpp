@@ -179,6 +179,10 @@ int launch_rays(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats,
                 uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
                 SimlodRayHit* hits, SimlodRayCounts* counts, hipStream_t stream);
 uint64_t rays_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates);
+int launch_neighbours(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodSphere* queries,
+                      uint32_t numQueries, uint32_t k, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
+                      uint32_t tableCapacity, SimlodNeighbour* neighbours, uint32_t* within, SimlodNeighbourCounts* counts, hipStream_t stream);
+uint64_t neighbours_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numQueries, uint32_t k, uint64_t numPairs, uint64_t numCandidates);
 int launch_generate_terrain(SimlodPoint* out, uint64_t numPoints, uint64_t firstIndex, uint64_t pointsPerTile, uint32_t seed, uint32_t tilesX,
                             const float tileExtent[3], float swathWidth, hipStream_t stream);
 enum : uint32_t { RENDER_FIRST = 1u, RENDER_COLOR = 2u, RENDER_RESOLVE = 4u, RENDER_OUTPUT = 8u, RENDER_ALL = 15u };

@@ -23,6 +23,9 @@ simlod_query_region — every rule restated in numpy float64, which reproduces t
 
 Ray queries (include/simlod_hip.h, "ray queries"): `Rays` holds a batch of SimlodRay records, `OctreeExport.cast` (on a full export) and
 `OctreeExport.cast_selected` (on any export) are the host mirror of simlod_query_rays, in the same float64 operation order.
+
+Neighbour queries (include/simlod_hip.h, "neighbour queries"): `Spheres` holds a batch of SimlodSphere records, `OctreeExport.neighbours` (on a
+full export) and `OctreeExport.neighbours_selected` (on any export) are the host mirror of simlod_query_neighbours, built the same way.
 """
 import numpy as np
 import torch
@@ -219,13 +222,19 @@ class OctreeExport:
 
     def _ray_pairs(self, rec):
         """Rules 1 and 3 for SimlodRay records against this table: (valid per ray, [(table index, the rays paired with it)] in table order)."""
-        tb = self.nodes
         o, d = rec["origin"].astype(np.float64), rec["dir"].astype(np.float64)
         tmin, tmax, rad, spr = (rec[f].astype(np.float64) for f in ("tMin", "tMax", "radius", "spread"))
         with np.errstate(invalid="ignore", over="ignore"):
             valid = np.isfinite(o).all(1) & np.isfinite(d).all(1) & np.isfinite(tmin) & np.isfinite(tmax) & np.isfinite(rad) & np.isfinite(spr)
             valid &= (d != 0).any(1) & (tmin >= 0) & (tmin <= tmax) & (rad >= 0) & (spr >= 0) & (rec["reserved"] == 0).all(1)
             R = rad + spr * tmax
+        return valid, self._descend(valid, lambda lo, hi, idx: _slab(lo, hi, o[idx], d[idx], tmin[idx], tmax[idx], R[idx]))
+
+    def _descend(self, valid, probe):
+        """The table descent the ray and the neighbour mirror share: probe(lo, hi, idx) says which of the probes `idx` pass the node's inflated
+        cube [lo, hi]; a probe reaches a node iff it passed every listed ancestor.  -> [(table index, the probes paired with it)] in table
+        order, for the selected entries with samples."""
+        tb = self.nodes
         mn, size = _box_of(self.box_min, self.box_max)
         e = np.ldexp(size, -abi.MAX_DEPTH)
         reach = {0: np.nonzero(valid)[0]}
@@ -238,7 +247,7 @@ class OctreeExport:
             s = np.ldexp(size, -int(nd["level"]))
             A = np.array([nd["X"], nd["Y"], nd["Z"]], dtype=np.float64)
             lo, hi = (mn + A * s) - e, (mn + (A + 1.0) * s) + e
-            idx = idx[_slab(lo, hi, o[idx], d[idx], tmin[idx], tmax[idx], R[idx])]
+            idx = idx[probe(lo, hi, idx)]
             if len(idx) == 0:
                 continue
             c = int(nd["firstChild"])
@@ -248,7 +257,7 @@ class OctreeExport:
                     c += 1
             if int(nd["numSamples"]) != 0 and int(nd["flags"]) & abi.EXPORT_FLAG_SELECTED:
                 pairs.append((t, idx))
-        return valid, pairs
+        return pairs
 
     def rays_per_node(self, rays):
         """How many rays form a pair with each table entry (rule 3 alone: no sample is tested)."""
@@ -307,6 +316,85 @@ class OctreeExport:
         if return_passing:
             out.append(passing)
         return out[0] if len(out) == 1 else tuple(out)
+
+    # -- neighbour queries (include/simlod_hip.h, "neighbour queries") -----------------------------------------------------------------------
+    def neighbours(self, spheres, k, max_level=None, select="cut", return_counts=False):
+        """The host mirror of simlod_query_neighbours on the octree this FULL export was taken from: (the neighbours as an (n, k) array of
+        abi.neighbour_dtype whose `node` / `ordinal` index the table and sample ranges of export_octree(max_level, select), `within` per
+        query) — and, return_counts, the SimlodNeighbourCounts record."""
+        return self.truncated(max_level, select).neighbours_selected(spheres, k, return_counts)
+
+    def _sphere_pairs(self, rec):
+        """Rules 1 and 3 for SimlodSphere records against this table: (valid per query, [(table index, the queries paired with it)] in table order)."""
+        c, r = rec["center"].astype(np.float64), rec["radius"].astype(np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            valid = np.isfinite(c).all(1) & np.isfinite(r) & (r >= 0)
+            rr = r * r
+
+        def probe(lo, hi, idx):
+            with np.errstate(invalid="ignore", over="ignore"):
+                ex = np.maximum(np.maximum(lo - c[idx], 0.0), c[idx] - hi)
+                return (ex[:, 0] * ex[:, 0] + ex[:, 1] * ex[:, 1]) + ex[:, 2] * ex[:, 2] <= rr[idx]
+        return valid, self._descend(valid, probe)
+
+    def spheres_per_node(self, spheres):
+        """How many queries form a pair with each table entry (rule 3 alone: no sample is tested)."""
+        out = np.zeros(self.num_nodes, np.int64)
+        for t, idx in self._sphere_pairs(_sphere_records(spheres))[1]:
+            out[t] = len(idx)
+        return out
+
+    def neighbours_selected(self, spheres, k, return_counts=False):
+        """The mirror on an export whose selection is already made (any `select`, "visible" included): the nodes considered are this table's."""
+        k = int(k)
+        if not 1 <= k <= abi.NEIGHBOURS_MAX_K:
+            raise ValueError(f"k = {k}: 1 .. {abi.NEIGHBOURS_MAX_K}")
+        rec = _sphere_records(spheres)
+        tb, smp = self.nodes, self.samples
+        n = len(rec)
+        best = np.zeros((n, k), dtype=abi.neighbour_dtype)
+        best["d2"], best["node"], best["ordinal"] = np.inf, abi.EXPORT_NONE, abi.EXPORT_NONE
+        within = np.zeros(n, np.int64)
+        c, r = rec["center"].astype(np.float64), rec["radius"].astype(np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            rr = r * r
+        x, y, z = (smp[a].astype(np.float64) for a in ("x", "y", "z"))
+        valid, pairs = self._sphere_pairs(rec)
+        num_pairs = num_cand = 0
+        for t, idx in pairs:                                       # (nodes in ascending order)
+            ns, a = int(tb["numSamples"][t]), int(tb["firstSample"][t])
+            num_pairs += len(idx)
+            num_cand += len(idx) * ns
+            sx, sy, sz = x[a:a + ns], y[a:a + ns], z[a:a + ns]
+            step = max(1, (1 << 21) // ns)
+            for b in range(0, len(idx), step):
+                i = idx[b:b + step]
+                with np.errstate(invalid="ignore", over="ignore"):
+                    px, py, pz = sx[None, :] - c[i, 0][:, None], sy[None, :] - c[i, 1][:, None], sz[None, :] - c[i, 2][:, None]
+                    d2 = (px * px + py * py) + pz * pz
+                    ok = d2 <= rr[i][:, None]
+                within[i] += ok.sum(1)
+                cols = np.nonzero(ok.any(0))[0]                    # (ascending ordinals: the stable sort below keeps the smaller one first)
+                if len(cols) == 0:
+                    continue
+                sub = np.where(ok[:, cols], d2[:, cols], np.inf)
+                order = np.argsort(sub, axis=1, kind="stable")[:, :k]
+                new = np.zeros((len(i), order.shape[1]), dtype=abi.neighbour_dtype)
+                new["d2"] = np.take_along_axis(sub, order, 1)
+                hit = np.isfinite(new["d2"])
+                new["node"], new["ordinal"] = np.where(hit, t, abi.EXPORT_NONE), np.where(hit, cols[order], abi.EXPORT_NONE)
+                new["sample"][hit] = smp[a + cols[order]][hit]
+                # what was found so far comes from smaller nodes: a stable sort by d2 keeps the total order (d2, node, ordinal)
+                both = np.concatenate([best[i], new], axis=1)
+                keep = np.argsort(both["d2"], axis=1, kind="stable")[:, :k]
+                best[i] = np.take_along_axis(both, keep, 1)
+        if not return_counts:
+            return best, within
+        cn = np.zeros((), dtype=abi.neighbour_counts_dtype)
+        cn["numNodes"], cn["numInvalid"], cn["k"] = len(tb), int((~valid).sum()), k
+        cn["numPairs"], cn["numCandidates"] = num_pairs, num_cand
+        cn["numFound"], cn["numWithin"] = int(np.minimum(within, k).sum()), int(within.sum())
+        return best, within, cn
 
     def save(self, path):
         h = np.zeros(1, dtype=header_dtype)
@@ -468,6 +556,41 @@ class Rays:
     def record(self):
         """The SimlodRay records the C ABI takes (abi.ray_dtype, one per ray)."""
         return self.rays
+
+
+def _sphere_records(spheres):
+    return spheres.record() if isinstance(spheres, Spheres) else np.ascontiguousarray(spheres).view(abi.sphere_dtype).reshape(-1)
+
+
+class Spheres:
+    """A batch of SimlodSphere records (abi.sphere_dtype): a centre and a radius per query; a scalar radius broadcasts over the batch.  Nothing
+    is validated here: an invalid query is legal input and finds nothing."""
+
+    def __init__(self, centers, radius):
+        c = np.asarray(centers, dtype=np.float64).reshape(-1, 3)
+        s = np.zeros(len(c), dtype=abi.sphere_dtype)
+        with np.errstate(over="ignore", invalid="ignore"):
+            s["center"], s["radius"] = c, radius
+        self.spheres = s
+
+    def __len__(self):
+        return len(self.spheres)
+
+    @classmethod
+    def from_records(cls, records):
+        self = cls.__new__(cls)
+        self.spheres = np.array(np.ascontiguousarray(records).view(abi.sphere_dtype).reshape(-1), copy=True)
+        return self
+
+    @classmethod
+    def from_points(cls, points, radius):
+        """Queries centred on the x, y, z of point records (abi.point_dtype)."""
+        p = np.asarray(points)
+        return cls(np.stack([p["x"], p["y"], p["z"]], axis=1), radius)
+
+    def record(self):
+        """The SimlodSphere records the C ABI takes (abi.sphere_dtype, one per query)."""
+        return self.spheres
 
 
 def validate_table(t, num_samples, buildable=False):

@@ -94,6 +94,9 @@ def lib():
         L.simlod_rays_buffer_min_bytes.restype = u64
         L.simlod_rays_buffer_min_bytes.argtypes = [u32, u64, u32, u64, u64]
         L.simlod_query_rays.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, u64, vp, u32, vp, vp, vp]
+        L.simlod_neighbours_buffer_min_bytes.restype = u64
+        L.simlod_neighbours_buffer_min_bytes.argtypes = [u32, u64, u32, u32, u64, u64]
+        L.simlod_query_neighbours.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, vp, u64, vp, u32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -111,6 +114,7 @@ EXPORTED_SYMBOLS = [
     "simlod_profile_enable", "simlod_profile_collect", "simlod_generate_terrain", "simlod_generate_terrain_scan", "simlod_launch_colorfilter", "simlod_colorfilter_buffer_min_bytes",
     "simlod_export_buffer_min_bytes", "simlod_export_octree", "simlod_import_octree", "simlod_import_octree_buildable",
     "simlod_query_buffer_min_bytes", "simlod_query_region", "simlod_rays_buffer_min_bytes", "simlod_query_rays",
+    "simlod_neighbours_buffer_min_bytes", "simlod_query_neighbours",
 ]
 
 
@@ -704,6 +708,90 @@ class DeviceOctree:
         c = self._rays(uniforms, t, max_level, select, hits, int(c["numPairs"]), int(c["numCandidates"]))
         out = hits if isinstance(rays, torch.Tensor) else hits.cpu().numpy().view(abi.ray_hit_dtype)
         return (out, c) if return_counts else out
+
+    # -- neighbour queries (include/simlod_hip.h, "neighbour queries") ---------------------------------------------------------------------
+    def _neighbours(self, uniforms, queries, k, max_level, select, out, within, pairs=0, candidates=0):
+        """One simlod_query_neighbours call -> the SimlodNeighbourCounts record (host).  out None: count only.  `queries`: a uint8 device
+        tensor of SimlodSphere records."""
+        u, up = self._u(uniforms)
+        sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
+        ml = abi.MAX_DEPTH if max_level is None else max(0, min(int(max_level), abi.MAX_DEPTH))
+        st = self.read_stats()
+        nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+        n = queries.numel() // abi.sphere_dtype.itemsize
+        scratch = self._export_scratch(int(self.L.simlod_neighbours_buffer_min_bytes(nn, bound, n, k, pairs, candidates)))
+        counts = torch.zeros(abi.neighbour_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        _check(self.L.simlod_query_neighbours(self._p(self.nodes), self._p(self.stats), up, self._p(queries), n, k, ml, sel, self._p(scratch),
+                                              ctypes.c_uint64(scratch.numel()), None, nn, None if out is None else self._p(out),
+                                              None if within is None else self._p(within), self._p(counts), self._stream()), "simlod_query_neighbours")
+        c = counts.cpu().numpy().view(abi.neighbour_counts_dtype)[0]
+        if int(c["error"]) != 0:
+            raise SimlodError(f"simlod_query_neighbours reported error bits {int(c['error']):#x} ({int(c['numNodes'])} nodes, {int(c['numPairs'])} pairs)")
+        return c
+
+    def _spheres_tensor(self, spheres, k):
+        if not 1 <= int(k) <= abi.NEIGHBOURS_MAX_K:
+            raise SimlodError(f"k = {k}: 1 .. {abi.NEIGHBOURS_MAX_K}")
+        if isinstance(spheres, torch.Tensor):
+            t = spheres.reshape(-1).view(torch.uint8)
+            if t.device != self.device or t.numel() == 0 or t.numel() % abi.sphere_dtype.itemsize:
+                raise SimlodError("spheres: a non-empty tensor of whole SimlodSphere records on this octree's device")
+            return t
+        rec = np.ascontiguousarray(spheres.record())
+        if len(rec) == 0:
+            raise SimlodError("spheres: an empty batch")
+        return torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(self.device)
+
+    def count_neighbours(self, uniforms, spheres, k, max_level=None, select="cut"):
+        """The SimlodNeighbourCounts record of a count-only simlod_query_neighbours call (numNodes, numInvalid, numPairs, numCandidates;
+        numFound and numWithin are 0: no sample is tested)."""
+        return self._neighbours(uniforms, self._spheres_tensor(spheres, k), int(k), max_level, select, None, None)
+
+    def find_neighbours(self, uniforms, spheres, k, max_level=None, select="cut", return_counts=False):
+        """The k nearest samples within the radius of each query (an octree_io.Spheres, or a device tensor of SimlodSphere records): a
+        count-only call, scratch sized from its counts, then the results -> (neighbours, within).  Host queries: an (n, k) numpy record array
+        (abi.neighbour_dtype) and an int array; device queries: a uint8 device tensor of the same records and a device tensor of n int32
+        counts.  `node` / `ordinal` refer to export_octree(max_level, select).  The places behind min(k, within) hold d2 = inf and
+        node = EXPORT_NONE."""
+        k = int(k)
+        t = self._spheres_tensor(spheres, k)
+        n = t.numel() // abi.sphere_dtype.itemsize
+        c = self._neighbours(uniforms, t, k, max_level, select, None, None)
+        out = torch.empty(n * k * abi.neighbour_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        within = torch.empty(n, dtype=torch.int32, device=self.device)
+        c = self._neighbours(uniforms, t, k, max_level, select, out, within, int(c["numPairs"]), int(c["numCandidates"]))
+        if not isinstance(spheres, torch.Tensor):
+            out, within = out.cpu().numpy().view(abi.neighbour_dtype).reshape(n, k), within.cpu().numpy().view(np.uint32).astype(np.int64)
+        return (out, within, c) if return_counts else (out, within)
+
+    def k_nearest(self, uniforms, points, k, radius0, max_level=None, select="cut"):
+        """The k nearest samples of each position without a radius of the caller's: `points` are abi.point_dtype records or an (n, 3) array on
+        the host.  Queries every position at radius0, then only the positions with within < k again at twice the radius, until every position
+        has k or the radius exceeds the box diagonal -> (neighbours, within) as find_neighbours returns them for host queries.  A position
+        with within >= k has its exact k nearest; one with fewer (the octree holds fewer than k samples within the last radius) has them all.
+        Every doubling is a find_neighbours call of its own: two C calls and a device round trip for the counts and the results, so choose
+        radius0 near the expected distance of the k-th neighbour."""
+        from .octree_io import Spheres
+        p = np.asarray(points)
+        centers = np.stack([p["x"], p["y"], p["z"]], axis=1) if p.dtype.names else p.reshape(-1, 3)
+        centers = centers.astype(np.float32)
+        n, k = len(centers), int(k)
+        u = np.asarray(uniforms).reshape(-1)[0]
+        diag = float(np.sqrt(3.0) * (np.asarray(u["boxMax"], np.float32) - np.asarray(u["boxMin"], np.float32)).max())
+        out = np.zeros((n, k), dtype=abi.neighbour_dtype)
+        out["d2"], out["node"], out["ordinal"] = np.inf, abi.EXPORT_NONE, abi.EXPORT_NONE
+        within = np.zeros(n, np.int64)
+        todo, r = np.arange(n), np.float32(radius0)
+        if not (np.isfinite(r) and r > 0):
+            raise SimlodError("k_nearest: radius0 must be positive and finite")
+        while len(todo):
+            nb, w = self.find_neighbours(uniforms, Spheres(centers[todo], r), k, max_level, select)
+            out[todo], within[todo] = nb, w
+            todo = todo[w < k]
+            if float(r) > diag:
+                break
+            r = np.float32(2.0) * r
+        return out, within
 
     def import_octree(self, export, check=True, *, buildable=False, uniforms=None):
         """Replace this object's octree by `export` (an octree_io.OctreeExport on the host or on a device): simlod_import_octree validates the

@@ -7,7 +7,10 @@ alternating rep by rep; half the terrain (one oblique plane through the box cent
 count-only call — and the device-to-device copy, all in this one run.
 --rays: instead, simlod_query_rays CUT@20 on the same octree — one pixel cone through the frame's centre beside the count-only region
 query of a thin box around the same ray, the two alternating rep by rep; 4 096 vertical rays of radius 0.5 with their pairs, candidates
-and the distinct chunk bytes of the paired nodes — and the device-to-device copy, all in this one run."""
+and the distinct chunk bytes of the paired nodes — and the device-to-device copy, all in this one run.
+--neighbours: instead, simlod_query_neighbours CUT@20 on the same octree — 4 096 queries at random input points, at a radius for which the
+host mirror's median `within` (on the first 256 of them) is about 30, with k = 1, 8 and 16 and the count-only call alone — and, for scale, the
+--rays case of 4 096 vertical rays and the device-to-device copy, all in this one run."""
 import argparse
 import ctypes
 import json
@@ -214,6 +217,75 @@ def rays_bench(dev, u, box, st, reps, T, width, height):
     print(json.dumps(out))
 
 
+def neighbours_bench(dev, u, box, st, reps, pts):
+    from simlod_amd import fingerprint
+    from simlod_amd.octree_io import Rays, Spheres
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    uu, up = dev._u(u)
+    b = np.asarray(box, dtype=np.float64)
+    n_q, n_mirror, target = 4096, 256, 30
+    centers = pts[np.sort(np.random.RandomState(42).choice(len(pts), n_q, replace=False))]
+    cut = dev.export_octree(u, select="cut").to("cpu")
+    # the radius: from the surface density first, then corrected once by the mirror's median on the first queries
+    radius = float(np.sqrt(target * b[0] * b[1] / (np.pi * len(pts))))
+    for _ in range(2):
+        within = cut.neighbours_selected(Spheres.from_points(centers[:n_mirror], radius), 1)[1]
+        radius *= float(np.sqrt(target / max(float(np.median(within)), 1.0)))
+    q = Spheres.from_points(centers, radius)
+    mirror_within = cut.neighbours_selected(Spheres.from_records(q.record()[:n_mirror]), 1)[1]
+    d_q = torch.from_numpy(q.record().view(np.uint8).reshape(-1)).to(dev.device)
+    counts = torch.zeros(abi.neighbour_counts_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+    c0 = dev.count_neighbours(u, q, 16)
+    need = int(L.simlod_neighbours_buffer_min_bytes(nn, bound, n_q, 16, int(c0["numPairs"]), int(c0["numCandidates"])))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    out_t = torch.empty(n_q * 16 * abi.neighbour_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+    within_t = torch.empty(n_q, dtype=torch.int32, device=dev.device)
+
+    def call(k, count_only=False):
+        rc = L.simlod_query_neighbours(p(dev.nodes), p(dev.stats), up, p(d_q), n_q, k, 20, abi.EXPORT_CUT, p(scratch), ctypes.c_uint64(need), None, nn,
+                                       None if count_only else p(out_t), None if count_only else p(within_t), p(counts), stream)
+        assert rc == 0
+
+    n_points = int(st["numPoints"])
+    copy_dst = torch.empty(n_points * 16, dtype=torch.uint8, device=dev.device)
+    copy_src = cut.samples_tensor.to(dev.device)[: copy_dst.numel()]
+    t_copy = timed(lambda: copy_dst.copy_(copy_src), reps)
+    copy_gbs = 2 * copy_dst.numel() / (t_copy[0] * 1e6)
+    out = {"points": n_points, "numNodes": nn, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(), "queries": n_q, "radius": radius,
+           "mirror_median_within": float(np.median(mirror_within)), "scratch_bytes": need,
+           "d2d_copy": {"ms": round(t_copy[0], 4), "bytes": 2 * copy_dst.numel(), "GBs": round(copy_gbs, 1)}}
+    ts = timed_alternating([lambda: call(1), lambda: call(8), lambda: call(16), lambda: call(16, True)], reps)
+    per_node = cut.spheres_per_node(q)
+    chunk_bytes = int(cut.nodes["numSamples"][per_node > 0].astype(np.int64).sum()) * 16
+    for k, t in zip((1, 8, 16), ts):
+        call(k)
+        torch.cuda.synchronize()
+        c = counts.cpu().numpy().view(abi.neighbour_counts_dtype)[0]
+        assert int(c["error"]) == 0 and np.array_equal(within_t[:n_mirror].cpu().numpy().astype(np.int64), mirror_within)
+        ideal = chunk_bytes + n_q * (k * 32 + 4)
+        out[f"k{k}"] = {"ms": round(t[0], 4), "ms_min": round(t[1], 4), **{f: int(c[f]) for f in abi.neighbour_counts_dtype.names},
+                        "ideal_bytes": ideal, "GBs": round(ideal / (t[0] * 1e6), 1), "frac_of_copy": round(ideal / (t[0] * 1e6) / copy_gbs, 4)}
+    out["count_only"] = {"ms": round(ts[3][0], 4), "ms_min": round(ts[3][1], 4)}
+    out["paired_nodes"], out["distinct_chunk_bytes"] = int((per_node > 0).sum()), chunk_bytes
+    # for scale: the ray query's 4 096 vertical rays of radius 0.5 (export_bench --rays)
+    vertical = Rays.vertical(np.random.RandomState(42).rand(4096, 2) * b[:2], b[2] + 10.0, 0.5, -10.0)
+    d_rays = torch.from_numpy(vertical.record().view(np.uint8).reshape(-1)).to(dev.device)
+    cr = dev.count_rays(u, vertical)
+    r_need = int(L.simlod_rays_buffer_min_bytes(nn, bound, 4096, int(cr["numPairs"]), int(cr["numCandidates"])))
+    r_scratch = torch.empty(r_need, dtype=torch.uint8, device=dev.device)
+    hits = torch.empty(4096 * 32, dtype=torch.uint8, device=dev.device)
+    r_counts = torch.zeros(32, dtype=torch.uint8, device=dev.device)
+
+    def rays():
+        rc = L.simlod_query_rays(p(dev.nodes), p(dev.stats), up, p(d_rays), 4096, 20, abi.EXPORT_CUT, p(r_scratch), ctypes.c_uint64(r_need), None, nn,
+                                 p(hits), p(r_counts), stream)
+        assert rc == 0
+    t_rays = timed(rays, reps)
+    out["rays_vertical_4096"] = {"ms": round(t_rays[0], 4), "ms_min": round(t_rays[1], 4), "numPairs": int(cr["numPairs"]), "numCandidates": int(cr["numCandidates"])}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=36_000_000)
@@ -222,6 +294,7 @@ def main():
     ap.add_argument("--buildable", action="store_true", help="also time simlod_import_octree_buildable (grid rebuild included)")
     ap.add_argument("--region", action="store_true", help="time simlod_query_region (whole box, half the terrain, a city block) instead")
     ap.add_argument("--rays", action="store_true", help="time simlod_query_rays (one pixel cone, 4 096 vertical rays) instead")
+    ap.add_argument("--neighbours", action="store_true", help="time simlod_query_neighbours (4 096 queries, k = 1, 8, 16, count-only) instead")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
     pts, box = synthetic.terrain(n_points, seed=7)
@@ -244,6 +317,8 @@ def main():
         return region_bench(dev, u, box, st, args.reps)
     if args.rays:
         return rays_bench(dev, u, box, st, args.reps, T, 1920, 1080)
+    if args.neighbours:
+        return neighbours_bench(dev, u, box, st, args.reps, pts)
     L = dev.L
     need = int(L.simlod_export_buffer_min_bytes(nn, ns))
     scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
