@@ -16,9 +16,9 @@
 // with grid pointers — and, between k_copy and k_i_finish, the occupancy grids rebuilt from the samples: k_i_gleaf, k_i_gdown per level,
 // k_i_groot (export_grids.inc); k_i_finish then also writes the builder's counters as k_reset does.
 // Region query (simlod_query_region): k_q_hier -> k_q_dir -> k_q_count -> k_q_scan -> k_q_write, described in export_region.inc.
-// Ray query (simlod_query_rays): k_r_hier -> k_q_dir -> k_r_pairs<count> -> k_r_scan -> k_r_pairs<fill> -> k_r_test -> k_r_reduce, in export_rays.inc.
-// Neighbour query (simlod_query_neighbours): k_r_hier -> k_q_dir -> k_n_pairs<count> -> k_n_scan -> k_n_pairs<fill> -> k_n_test -> k_n_reduce, in
-// export_neighbours.inc (the descent, the layout and the pair records are the ray query's).
+// Pair queries: k_p_hier -> k_q_dir -> k_p_pairs<Q, count> -> k_p_scan<Q> -> k_p_pairs<Q, fill> -> Q's test kernel -> Q's reduce kernel; the pipeline
+// is written once over a query trait Q, in export_pairs.inc.  Ray query (simlod_query_rays): RayQuery, k_r_test, k_r_reduce, in export_rays.inc.
+// Neighbour query (simlod_query_neighbours): NbQuery, k_n_test, k_n_reduce, in export_neighbours.inc.
 // Everything in between lives in the caller's scratch buffer (export_min_bytes), never in kernel_construct's momentary buffer: the builder's
 // recycle stack and the chunk table export reads are there.
 // One translation unit: the device code lies in export_*.inc, the host side — the scratch bounds and the launchers — here.
@@ -39,8 +39,9 @@ namespace {
 #include "export_common.inc"   // constants, Header, Layout, block_scan, ExportArgs, leaf_rows_valid, scan_table, load_chunk4, copy_chunk, k_copy
 #include "export_table.inc"    // hier_walk, k_x_hier, k_x_scan, k_x_dir
 #include "export_region.inc"   // QueryGeom, classify, QItem, QueryLayout, QueryArgs, k_q_hier, k_q_dir, k_q_count, k_q_scan, k_q_write
-#include "export_rays.inc"     // the ray records, RayLayout, RayArgs, k_r_hier, k_r_pairs, k_r_scan, k_r_test, k_r_reduce
-#include "export_neighbours.inc"  // NbArgs, sphere_load, sphere_cube, k_n_pairs, k_n_scan, k_n_test, k_n_reduce
+#include "export_pairs.inc"    // the pair records, PairLayout, PairArgs, k_p_hier, wave_descend, k_p_pairs, k_p_scan, TestView, test_chunk
+#include "export_rays.inc"     // RayArgs, ray_load, slab, sample_t, RayQuery, k_r_test, k_r_reduce
+#include "export_neighbours.inc"  // NbArgs, sphere_load, sphere_cube, sphere_d2, NbQuery, k_n_test, k_n_reduce
 #include "export_import.inc"   // ImportArgs, link_chunk_list, k_i_validate, k_i_nodes, k_i_finish
 #include "export_grids.inc"    // the buildable import's grids: k_i_gleaf, k_i_gdown, k_i_groot
 
@@ -121,89 +122,86 @@ int launch_query(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats
 	return (int)hipGetLastError();
 }
 
+namespace {
+
+// what a pair query (export_pairs.inc) needs for its layout, its chunk items and, behind them, its pairs and their partials of `partBytes` each
+uint64_t pairs_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numQueries, uint64_t partBytes, uint64_t numPairs, uint64_t numCandidates) {
+	const uint64_t pairsOff = PairLayout(nodeCapacity, numQueries).x.items + (sampleBound / SIMLOD_POINTS_PER_CHUNK + nodeCapacity + 1u) * sizeof(QItem);
+	return pair_need(pairsOff, numPairs, numCandidates, partBytes);
+}
+
+// The pair pipeline for query Q after its front end's own checks; `q` comes with Q's own fields set.  results(qGrid, itemGrid): the launches
+// of Q's test and reduce kernels.
+template <class Q, class Results>
+int launch_pairs(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, uint32_t numQueries, uint32_t maxLevel,
+                 uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, typename Q::Args& q,
+                 hipStream_t stream, Results results) {
+	if (nodes == nullptr || stats == nullptr || u == nullptr || scratch == nullptr || select > SIMLOD_EXPORT_VISIBLE) return (int)hipErrorInvalidValue;
+	if (scratchBytes < pairs_min_bytes(tableCapacity, 0u, numQueries, Q::part_bytes(q), 0u, 0u)) return (int)hipErrorInvalidValue;
+	if (select == SIMLOD_EXPORT_VISIBLE && !array_state(ctx, nodes).rendered) return (int)hipErrorInvalidValue;
+	const PairLayout pl(tableCapacity, numQueries);
+	PairArgs& p = q.p;
+	ExportArgs& a = p.x;
+	a.nodes = nodes; a.stats = stats; a.maxLevel = maxLevel; a.select = select; a.cap = tableCapacity;
+	a.scratch = reinterpret_cast<uint8_t*>(scratch);
+	a.table = table != nullptr ? table : reinterpret_cast<SimlodExportNode*>(a.scratch + pl.tab);
+	a.lay = pl.x; a.lay.take_rest(scratchBytes);
+	float size, minx, miny, minz;
+	octree_box(u, size, minx, miny, minz);                                      // voxels.cu:860-863
+	p.size = (double)size; p.min[0] = (double)minx; p.min[1] = (double)miny; p.min[2] = (double)minz;
+	p.numQueries = numQueries; p.scratchBytes = scratchBytes; p.at = pl.at;
+	bind_leaf_table(ctx, nodes, a);
+	QueryArgs d{};                                                              // k_q_dir's view of the same buffers
+	d.x = a; d.cls = pl.at.cls;
+	const uint32_t qGrid = (numQueries + PAIR_WAVES - 1u) / PAIR_WAVES;
+	SIMLOD_LAUNCH(k_p_hier, dim3(1), dim3(WG_TPB), stream, p);
+	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                          // k_q_dir: one wave per table entry
+	if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, d);
+	SIMLOD_LAUNCH((k_p_pairs<Q, 0>), dim3(qGrid), dim3(LANE_TPB), stream, q);
+	SIMLOD_LAUNCH(k_p_scan<Q>, dim3(1), dim3(WG_TPB), stream, q);
+	if (Q::wants_results(q)) {
+		SIMLOD_LAUNCH((k_p_pairs<Q, 1>), dim3(qGrid), dim3(LANE_TPB), stream, q);
+		results(qGrid, copy_grid(a.lay.itemCap));
+	}
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+}  // namespace
+
 uint64_t rays_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates) {
-	return RayLayout(nodeCapacity, numRays).x.items + (sampleBound / SIMLOD_POINTS_PER_CHUNK + nodeCapacity + 1u) * sizeof(QItem) +
-	       numPairs * (sizeof(RayPair) + sizeof(RayPart)) + (numCandidates / SIMLOD_POINTS_PER_CHUNK) * sizeof(RayPart);
+	return pairs_min_bytes(nodeCapacity, sampleBound, numRays, sizeof(RayPart), numPairs, numCandidates);
 }
 
 int launch_rays(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRay* rays, uint32_t numRays,
                 uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
                 SimlodRayHit* hits, SimlodRayCounts* counts, hipStream_t stream) {
-	if (nodes == nullptr || stats == nullptr || u == nullptr || rays == nullptr || scratch == nullptr || counts == nullptr) return (int)hipErrorInvalidValue;
-	if (numRays == 0u || numRays > SIMLOD_RAYS_MAX || select > SIMLOD_EXPORT_VISIBLE) return (int)hipErrorInvalidValue;
-	if (scratchBytes < rays_min_bytes(tableCapacity, 0u, numRays, 0u, 0u)) return (int)hipErrorInvalidValue;
-	if (select == SIMLOD_EXPORT_VISIBLE && !array_state(ctx, nodes).rendered) return (int)hipErrorInvalidValue;
-	const RayLayout rl(tableCapacity, numRays);
+	if (rays == nullptr || counts == nullptr || numRays == 0u || numRays > SIMLOD_RAYS_MAX) return (int)hipErrorInvalidValue;
 	RayArgs r{};
-	ExportArgs& a = r.x;
-	a.nodes = nodes; a.stats = stats; a.maxLevel = maxLevel; a.select = select; a.cap = tableCapacity;
-	a.scratch = reinterpret_cast<uint8_t*>(scratch);
-	a.table = table != nullptr ? table : reinterpret_cast<SimlodExportNode*>(a.scratch + rl.tab);
-	a.lay = rl.x; a.lay.take_rest(scratchBytes);
-	float size, minx, miny, minz;
-	octree_box(u, size, minx, miny, minz);                                      // voxels.cu:860-863
-	r.size = (double)size; r.min[0] = (double)minx; r.min[1] = (double)miny; r.min[2] = (double)minz;
-	r.rays = rays; r.numRays = numRays; r.hits = hits; r.counts = counts; r.scratchBytes = scratchBytes; r.at = rl.at;
-	bind_leaf_table(ctx, nodes, a);
-	QueryArgs q{};                                                              // k_q_dir's view of the same buffers
-	q.x = a; q.cls = rl.at.cls;
-	const uint32_t rayGrid = (numRays + RAY_WAVES - 1u) / RAY_WAVES;
-	SIMLOD_LAUNCH(k_r_hier, dim3(1), dim3(WG_TPB), stream, r);
-	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                          // k_q_dir: one wave per table entry
-	if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
-	SIMLOD_LAUNCH(k_r_pairs<0>, dim3(rayGrid), dim3(LANE_TPB), stream, r);
-	SIMLOD_LAUNCH(k_r_scan, dim3(1), dim3(WG_TPB), stream, r);
-	if (hits != nullptr) {
-		SIMLOD_LAUNCH(k_r_pairs<1>, dim3(rayGrid), dim3(LANE_TPB), stream, r);
-		SIMLOD_LAUNCH(k_r_test, dim3(copy_grid(a.lay.itemCap)), dim3(LANE_TPB), stream, r);
+	r.rays = rays; r.hits = hits; r.counts = counts;
+	return launch_pairs<RayQuery>(ctx, nodes, stats, u, numRays, maxLevel, select, scratch, scratchBytes, table, tableCapacity, r, stream,
+	                              [&](uint32_t rayGrid, uint32_t itemGrid) {
+		SIMLOD_LAUNCH(k_r_test, dim3(itemGrid), dim3(LANE_TPB), stream, r);
 		SIMLOD_LAUNCH(k_r_reduce, dim3(rayGrid), dim3(LANE_TPB), stream, r);
-	}
-	if (profile_enabled()) profile_close(stream);
-	return (int)hipGetLastError();
+	});
 }
 
 uint64_t neighbours_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numQueries, uint32_t k, uint64_t numPairs, uint64_t numCandidates) {
-	return RayLayout(nodeCapacity, numQueries).x.items + (sampleBound / SIMLOD_POINTS_PER_CHUNK + nodeCapacity + 1u) * sizeof(QItem) +
-	       numPairs * (sizeof(RayPair) + nb_part_bytes(k)) + (numCandidates / SIMLOD_POINTS_PER_CHUNK) * nb_part_bytes(k);
+	return pairs_min_bytes(nodeCapacity, sampleBound, numQueries, nb_part_bytes(k), numPairs, numCandidates);
 }
 
 int launch_neighbours(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodSphere* queries,
                       uint32_t numQueries, uint32_t k, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
                       uint32_t tableCapacity, SimlodNeighbour* neighbours, uint32_t* within, SimlodNeighbourCounts* counts, hipStream_t stream) {
-	if (nodes == nullptr || stats == nullptr || u == nullptr || queries == nullptr || scratch == nullptr || counts == nullptr) return (int)hipErrorInvalidValue;
-	if (within != nullptr && neighbours == nullptr) return (int)hipErrorInvalidValue;
-	if (numQueries == 0u || numQueries > SIMLOD_NEIGHBOURS_MAX || k == 0u || k > SIMLOD_NEIGHBOURS_MAX_K || select > SIMLOD_EXPORT_VISIBLE) return (int)hipErrorInvalidValue;
-	if (scratchBytes < neighbours_min_bytes(tableCapacity, 0u, numQueries, k, 0u, 0u)) return (int)hipErrorInvalidValue;
-	if (select == SIMLOD_EXPORT_VISIBLE && !array_state(ctx, nodes).rendered) return (int)hipErrorInvalidValue;
-	const RayLayout rl(tableCapacity, numQueries);
+	if (queries == nullptr || counts == nullptr || (within != nullptr && neighbours == nullptr)) return (int)hipErrorInvalidValue;
+	if (numQueries == 0u || numQueries > SIMLOD_NEIGHBOURS_MAX || k == 0u || k > SIMLOD_NEIGHBOURS_MAX_K) return (int)hipErrorInvalidValue;
 	NbArgs n{};
-	RayArgs& r = n.r;
-	ExportArgs& a = r.x;
-	a.nodes = nodes; a.stats = stats; a.maxLevel = maxLevel; a.select = select; a.cap = tableCapacity;
-	a.scratch = reinterpret_cast<uint8_t*>(scratch);
-	a.table = table != nullptr ? table : reinterpret_cast<SimlodExportNode*>(a.scratch + rl.tab);
-	a.lay = rl.x; a.lay.take_rest(scratchBytes);
-	float size, minx, miny, minz;
-	octree_box(u, size, minx, miny, minz);                                      // voxels.cu:860-863
-	r.size = (double)size; r.min[0] = (double)minx; r.min[1] = (double)miny; r.min[2] = (double)minz;
-	r.numRays = numQueries; r.scratchBytes = scratchBytes; r.at = rl.at;
 	n.queries = queries; n.neighbours = neighbours; n.within = within; n.counts = counts; n.k = k;
-	bind_leaf_table(ctx, nodes, a);
-	QueryArgs q{};                                                              // k_q_dir's view of the same buffers
-	q.x = a; q.cls = rl.at.cls;
-	const uint32_t qGrid = (numQueries + RAY_WAVES - 1u) / RAY_WAVES;
-	SIMLOD_LAUNCH(k_r_hier, dim3(1), dim3(WG_TPB), stream, r);
-	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                          // k_q_dir: one wave per table entry
-	if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
-	SIMLOD_LAUNCH(k_n_pairs<0>, dim3(qGrid), dim3(LANE_TPB), stream, n);
-	SIMLOD_LAUNCH(k_n_scan, dim3(1), dim3(WG_TPB), stream, n);
-	if (neighbours != nullptr) {
-		SIMLOD_LAUNCH(k_n_pairs<1>, dim3(qGrid), dim3(LANE_TPB), stream, n);
-		SIMLOD_LAUNCH(k_n_test, dim3(copy_grid(a.lay.itemCap)), dim3(LANE_TPB), stream, n);
+	return launch_pairs<NbQuery>(ctx, nodes, stats, u, numQueries, maxLevel, select, scratch, scratchBytes, table, tableCapacity, n, stream,
+	                             [&](uint32_t qGrid, uint32_t itemGrid) {
+		SIMLOD_LAUNCH(k_n_test, dim3(itemGrid), dim3(LANE_TPB), stream, n);
 		SIMLOD_LAUNCH(k_n_reduce, dim3(qGrid), dim3(LANE_TPB), stream, n);
-	}
-	if (profile_enabled()) profile_close(stream);
-	return (int)hipGetLastError();
+	});
 }
 
 namespace {

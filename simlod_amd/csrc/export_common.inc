@@ -88,7 +88,7 @@ struct ExportArgs {
 	uint32_t           ltMagicValue, ltSlots, ltRows;
 };
 
-// the class of a table entry against a query's region (cls[] in the scratch buffer; the ray query tags every entry as copied)
+// the class of a table entry against a query's region (cls[] in the scratch buffer; the pair queries tag every entry as copied)
 enum : uint32_t { Q_OUTSIDE = 0u, Q_FILTERED = 1u, Q_COPIED = 2u };
 
 // Does the builder's chunk table describe node `src` of this octree as it is now (render.hip visible_nodes: the same four stamp words), and
@@ -102,7 +102,7 @@ __device__ __forceinline__ bool leaf_rows_valid(const ExportArgs& a, uint32_t sr
 	return rows;
 }
 
-// The scans behind a walk (ONE workgroup; k_x_scan, k_r_hier): numSamples -> firstSample, the chunks per node -> first[] (the node's first
+// The scans behind a walk (ONE workgroup; k_x_scan, k_p_hier): numSamples -> firstSample, the chunks per node -> first[] (the node's first
 // item), first[n], the item capacity check.  per(t): what the kernel writes per entry on top.  `err` (lane 0 only): the header's error word
 // with the check applied.  (`a` by value: k_x_scan then reads its arguments where it did before the routine was shared, and keeps its registers.)
 struct TableScan { uint32_t n, err; uint64_t samples, items; };

@@ -259,17 +259,32 @@ class OctreeExport:
                 pairs.append((t, idx))
         return pairs
 
-    def rays_per_node(self, rays):
-        """How many rays form a pair with each table entry (rule 3 alone: no sample is tested)."""
-        rec = rays.record() if isinstance(rays, Rays) else np.ascontiguousarray(rays).view(abi.ray_dtype).reshape(-1)
+    def _per_node(self, pairs):
         out = np.zeros(self.num_nodes, np.int64)
-        for t, idx in self._ray_pairs(rec)[1]:
+        for t, idx in pairs:
             out[t] = len(idx)
         return out
 
+    def _pair_blocks(self, pairs, totals):
+        """The loop the ray and the neighbour mirror share, per pair list of _descend (nodes in ascending order): yields (table index, the
+        node's first sample, its sample slice, a block of at most 2^21 // numSamples of its probes); totals[0] += pairs, totals[1] +=
+        candidates on the way."""
+        tb = self.nodes
+        for t, idx in pairs:
+            ns, a = int(tb["numSamples"][t]), int(tb["firstSample"][t])
+            totals[0] += len(idx)
+            totals[1] += len(idx) * ns
+            step = max(1, (1 << 21) // ns)
+            for b in range(0, len(idx), step):
+                yield t, a, slice(a, a + ns), idx[b:b + step]
+
+    def rays_per_node(self, rays):
+        """How many rays form a pair with each table entry (rule 3 alone: no sample is tested)."""
+        return self._per_node(self._ray_pairs(_ray_records(rays))[1])
+
     def cast_selected(self, rays, return_counts=False, return_passing=False):
         """The mirror on an export whose selection is already made (any `select`, "visible" included): the nodes considered are this table's."""
-        rec = rays.record() if isinstance(rays, Rays) else np.ascontiguousarray(rays).view(abi.ray_dtype).reshape(-1)
+        rec = _ray_records(rays)
         tb, smp = self.nodes, self.samples
         n = len(rec)
         hits = np.zeros(n, dtype=abi.ray_hit_dtype)
@@ -281,37 +296,31 @@ class OctreeExport:
             dd = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
         x, y, z = (smp[a].astype(np.float64) for a in ("x", "y", "z"))
         valid, pairs = self._ray_pairs(rec)
-        num_pairs = num_cand = 0
-        for t, idx in pairs:
-            ns, a = int(tb["numSamples"][t]), int(tb["firstSample"][t])
-            num_pairs += len(idx)
-            num_cand += len(idx) * ns
-            sx, sy, sz = x[a:a + ns], y[a:a + ns], z[a:a + ns]
-            step = max(1, (1 << 21) // ns)
-            for b in range(0, len(idx), step):
-                i = idx[b:b + step]
-                col = lambda v: v[i][:, None]
-                dx, dy, dz = col(d[:, 0]), col(d[:, 1]), col(d[:, 2])
-                with np.errstate(invalid="ignore", over="ignore"):
-                    px, py, pz = sx[None, :] - col(o[:, 0]), sy[None, :] - col(o[:, 1]), sz[None, :] - col(o[:, 2])
-                    tt = ((dx * px + dy * py) + dz * pz) / col(dd)
-                    qx, qy, qz = px - tt * dx, py - tt * dy, pz - tt * dz
-                    s2 = (qx * qx + qy * qy) + qz * qz
-                    rr = col(rad) + col(spr) * tt
-                    ok = (tt >= col(tmin)) & (tt <= col(tmax)) & (s2 <= rr * rr)
-                passing[i] += ok.sum(1)
-                tm = np.where(ok, tt, np.inf)
-                j = tm.argmin(1)                                   # (the first of equal minima: the smallest ordinal)
-                tb_ = tm[np.arange(len(i)), j]
-                upd = tb_ < hits["t"][i]                           # (nodes in ascending order: an equal t keeps the smaller node)
-                iu, ju = i[upd], j[upd]
-                hits["t"][iu], hits["node"][iu], hits["ordinal"][iu] = tb_[upd], t, ju
-                hits["sample"][iu] = smp[a + ju]
+        totals = [0, 0]
+        for t, a, sl, i in self._pair_blocks(pairs, totals):
+            sx, sy, sz = x[sl], y[sl], z[sl]
+            col = lambda v: v[i][:, None]
+            dx, dy, dz = col(d[:, 0]), col(d[:, 1]), col(d[:, 2])
+            with np.errstate(invalid="ignore", over="ignore"):
+                px, py, pz = sx[None, :] - col(o[:, 0]), sy[None, :] - col(o[:, 1]), sz[None, :] - col(o[:, 2])
+                tt = ((dx * px + dy * py) + dz * pz) / col(dd)
+                qx, qy, qz = px - tt * dx, py - tt * dy, pz - tt * dz
+                s2 = (qx * qx + qy * qy) + qz * qz
+                rr = col(rad) + col(spr) * tt
+                ok = (tt >= col(tmin)) & (tt <= col(tmax)) & (s2 <= rr * rr)
+            passing[i] += ok.sum(1)
+            tm = np.where(ok, tt, np.inf)
+            j = tm.argmin(1)                                   # (the first of equal minima: the smallest ordinal)
+            tb_ = tm[np.arange(len(i)), j]
+            upd = tb_ < hits["t"][i]                           # (nodes in ascending order: an equal t keeps the smaller node)
+            iu, ju = i[upd], j[upd]
+            hits["t"][iu], hits["node"][iu], hits["ordinal"][iu] = tb_[upd], t, ju
+            hits["sample"][iu] = smp[a + ju]
         out = [hits]
         if return_counts:
             c = np.zeros((), dtype=abi.ray_counts_dtype)
             c["numNodes"], c["numHits"], c["numInvalid"] = len(tb), int((hits["node"] != abi.EXPORT_NONE).sum()), int((~valid).sum())
-            c["numPairs"], c["numCandidates"] = num_pairs, num_cand
+            c["numPairs"], c["numCandidates"] = totals
             out.append(c)
         if return_passing:
             out.append(passing)
@@ -339,10 +348,7 @@ class OctreeExport:
 
     def spheres_per_node(self, spheres):
         """How many queries form a pair with each table entry (rule 3 alone: no sample is tested)."""
-        out = np.zeros(self.num_nodes, np.int64)
-        for t, idx in self._sphere_pairs(_sphere_records(spheres))[1]:
-            out[t] = len(idx)
-        return out
+        return self._per_node(self._sphere_pairs(_sphere_records(spheres))[1])
 
     def neighbours_selected(self, spheres, k, return_counts=False):
         """The mirror on an export whose selection is already made (any `select`, "visible" included): the nodes considered are this table's."""
@@ -360,39 +366,33 @@ class OctreeExport:
             rr = r * r
         x, y, z = (smp[a].astype(np.float64) for a in ("x", "y", "z"))
         valid, pairs = self._sphere_pairs(rec)
-        num_pairs = num_cand = 0
-        for t, idx in pairs:                                       # (nodes in ascending order)
-            ns, a = int(tb["numSamples"][t]), int(tb["firstSample"][t])
-            num_pairs += len(idx)
-            num_cand += len(idx) * ns
-            sx, sy, sz = x[a:a + ns], y[a:a + ns], z[a:a + ns]
-            step = max(1, (1 << 21) // ns)
-            for b in range(0, len(idx), step):
-                i = idx[b:b + step]
-                with np.errstate(invalid="ignore", over="ignore"):
-                    px, py, pz = sx[None, :] - c[i, 0][:, None], sy[None, :] - c[i, 1][:, None], sz[None, :] - c[i, 2][:, None]
-                    d2 = (px * px + py * py) + pz * pz
-                    ok = d2 <= rr[i][:, None]
-                within[i] += ok.sum(1)
-                cols = np.nonzero(ok.any(0))[0]                    # (ascending ordinals: the stable sort below keeps the smaller one first)
-                if len(cols) == 0:
-                    continue
-                sub = np.where(ok[:, cols], d2[:, cols], np.inf)
-                order = np.argsort(sub, axis=1, kind="stable")[:, :k]
-                new = np.zeros((len(i), order.shape[1]), dtype=abi.neighbour_dtype)
-                new["d2"] = np.take_along_axis(sub, order, 1)
-                hit = np.isfinite(new["d2"])
-                new["node"], new["ordinal"] = np.where(hit, t, abi.EXPORT_NONE), np.where(hit, cols[order], abi.EXPORT_NONE)
-                new["sample"][hit] = smp[a + cols[order]][hit]
-                # what was found so far comes from smaller nodes: a stable sort by d2 keeps the total order (d2, node, ordinal)
-                both = np.concatenate([best[i], new], axis=1)
-                keep = np.argsort(both["d2"], axis=1, kind="stable")[:, :k]
-                best[i] = np.take_along_axis(both, keep, 1)
+        totals = [0, 0]
+        for t, a, sl, i in self._pair_blocks(pairs, totals):
+            sx, sy, sz = x[sl], y[sl], z[sl]
+            with np.errstate(invalid="ignore", over="ignore"):
+                px, py, pz = sx[None, :] - c[i, 0][:, None], sy[None, :] - c[i, 1][:, None], sz[None, :] - c[i, 2][:, None]
+                d2 = (px * px + py * py) + pz * pz
+                ok = d2 <= rr[i][:, None]
+            within[i] += ok.sum(1)
+            cols = np.nonzero(ok.any(0))[0]                    # (ascending ordinals: the stable sort below keeps the smaller one first)
+            if len(cols) == 0:
+                continue
+            sub = np.where(ok[:, cols], d2[:, cols], np.inf)
+            order = np.argsort(sub, axis=1, kind="stable")[:, :k]
+            new = np.zeros((len(i), order.shape[1]), dtype=abi.neighbour_dtype)
+            new["d2"] = np.take_along_axis(sub, order, 1)
+            hit = np.isfinite(new["d2"])
+            new["node"], new["ordinal"] = np.where(hit, t, abi.EXPORT_NONE), np.where(hit, cols[order], abi.EXPORT_NONE)
+            new["sample"][hit] = smp[a + cols[order]][hit]
+            # what was found so far comes from smaller nodes: a stable sort by d2 keeps the total order (d2, node, ordinal)
+            both = np.concatenate([best[i], new], axis=1)
+            keep = np.argsort(both["d2"], axis=1, kind="stable")[:, :k]
+            best[i] = np.take_along_axis(both, keep, 1)
         if not return_counts:
             return best, within
         cn = np.zeros((), dtype=abi.neighbour_counts_dtype)
         cn["numNodes"], cn["numInvalid"], cn["k"] = len(tb), int((~valid).sum()), k
-        cn["numPairs"], cn["numCandidates"] = num_pairs, num_cand
+        cn["numPairs"], cn["numCandidates"] = totals
         cn["numFound"], cn["numWithin"] = int(np.minimum(within, k).sum()), int(within.sum())
         return best, within, cn
 
@@ -556,6 +556,10 @@ class Rays:
     def record(self):
         """The SimlodRay records the C ABI takes (abi.ray_dtype, one per ray)."""
         return self.rays
+
+
+def _ray_records(rays):
+    return rays.record() if isinstance(rays, Rays) else np.ascontiguousarray(rays).view(abi.ray_dtype).reshape(-1)
 
 
 def _sphere_records(spheres):

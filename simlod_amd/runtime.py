@@ -638,23 +638,24 @@ class DeviceOctree:
         sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
         ml = abi.MAX_DEPTH if max_level is None else max(0, min(int(max_level), abi.MAX_DEPTH))
         st = self.read_stats()
-        nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
-        table = torch.empty(max(nn, 1) * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
-        return sel, ml, table, bound
+        return sel, ml, int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+
+    def _table(self, nn):
+        return torch.empty(max(nn, 1) * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
 
     def count_region(self, uniforms, region, max_level=None, select="cut"):
         """How much of the octree lies in `region` (an octree_io.Region) at `max_level`: the SimlodQueryCounts record of a count-only
         simlod_query_region call (numNodes, numSamples, numCandidates, numFilteredNodes, numCopiedNodes).  No sample is written."""
-        sel, ml, table, bound = self._query_setup(max_level, select)
-        return self._query(uniforms, region, ml, sel, table, None, 0, bound)
+        sel, ml, nn, bound = self._query_setup(max_level, select)
+        return self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound)
 
     def query_region(self, uniforms, region, max_level=None, select="cut", return_counts=False):
         """The samples inside `region` as an octree_io.OctreeExport on this device (select abi.EXPORT_REGION): the pruned table and, in chunk-list
         order, the samples of the selected nodes ("cut": source leaves and the nodes at max_level; "all": every listed node) that pass the
         region's test.  A count-only call first, then the outputs sized exactly.  Raises SimlodError when the device reports an error."""
         from .octree_io import OctreeExport
-        sel, ml, table, bound = self._query_setup(max_level, select)
-        c = self._query(uniforms, region, ml, sel, table, None, 0, bound)
+        sel, ml, nn, bound = self._query_setup(max_level, select)
+        c = self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound)
         nn, ns = int(c["numNodes"]), int(c["numSamples"])
         table = torch.empty(nn * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
         samples = torch.empty(max(ns, 1) * abi.point_dtype.itemsize, dtype=torch.uint8, device=self.device)
@@ -663,89 +664,78 @@ class DeviceOctree:
         ex = OctreeExport(table, samples[: int(c["numSamples"]) * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_REGION)
         return (ex, c) if return_counts else ex
 
-    # -- ray queries (include/simlod_hip.h, "ray queries") ---------------------------------------------------------------------------------
-    def _rays(self, uniforms, rays, max_level, select, hits, pairs=0, candidates=0):
-        """One simlod_query_rays call -> the SimlodRayCounts record (host).  hits None: count only.  `rays`: an octree_io.Rays or a uint8
-        device tensor of SimlodRay records."""
+    # -- pair queries: what the ray and the neighbour query share (csrc/export_pairs.inc) ------------------------------------------------------
+    # per C call simlod_query_<what>: the record's dtype, its name in messages, its C name, the counts record's dtype.  What _pair_query
+    # relies on (include/simlod_hip.h), with `ks` the query's own scalars and `outs` its result pointers, each in the header's order:
+    #   simlod_<what>_buffer_min_bytes(nodeCapacity, sampleBound, numRecords, *ks, numPairs, numCandidates)
+    #   simlod_query_<what>(nodes, stats, uniforms, records, numRecords, *ks, maxLevel, select, scratch, scratchBytes, table, tableCapacity,
+    #                       *outs, counts, stream)
+    #   rays: ks = (), outs = (hits,);  neighbours: ks = (k,), outs = (neighbours, within)
+    _PAIR_QUERIES = {"rays": (abi.ray_dtype, "rays", "SimlodRay", abi.ray_counts_dtype),
+                     "neighbours": (abi.sphere_dtype, "spheres", "SimlodSphere", abi.neighbour_counts_dtype)}
+
+    def _pair_query(self, what, uniforms, records, ks, max_level, select, outs, counts_of=None):
+        """One simlod_query_<what> call -> its counts record (host).  `records`: a uint8 device tensor of the query's records; ks: the arguments
+        behind the record count ((k,) for neighbours); outs: the result tensors, None each in a count-only call; counts_of: the counts of a
+        count-only call, from which a call with results sizes its scratch."""
+        rec_dtype, _, _, counts_dtype = self._PAIR_QUERIES[what]
         u, up = self._u(uniforms)
-        sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
-        ml = abi.MAX_DEPTH if max_level is None else max(0, min(int(max_level), abi.MAX_DEPTH))
-        st = self.read_stats()
-        nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
-        n = rays.numel() // abi.ray_dtype.itemsize
-        scratch = self._export_scratch(int(self.L.simlod_rays_buffer_min_bytes(nn, bound, n, pairs, candidates)))
-        counts = torch.zeros(abi.ray_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
-        _check(self.L.simlod_query_rays(self._p(self.nodes), self._p(self.stats), up, self._p(rays), n, ml, sel, self._p(scratch),
-                                        ctypes.c_uint64(scratch.numel()), None, nn, None if hits is None else self._p(hits), self._p(counts),
-                                        self._stream()), "simlod_query_rays")
-        c = counts.cpu().numpy().view(abi.ray_counts_dtype)[0]
+        sel, ml, nn, bound = self._query_setup(max_level, select)
+        n = records.numel() // rec_dtype.itemsize
+        pairs, candidates = (0, 0) if counts_of is None else (int(counts_of["numPairs"]), int(counts_of["numCandidates"]))
+        scratch = self._export_scratch(int(getattr(self.L, f"simlod_{what}_buffer_min_bytes")(nn, bound, n, *ks, pairs, candidates)))
+        counts = torch.zeros(counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        fn = f"simlod_query_{what}"
+        _check(getattr(self.L, fn)(self._p(self.nodes), self._p(self.stats), up, self._p(records), n, *ks, ml, sel, self._p(scratch),
+                                   ctypes.c_uint64(scratch.numel()), None, nn, *(None if o is None else self._p(o) for o in outs), self._p(counts),
+                                   self._stream()), fn)
+        c = counts.cpu().numpy().view(counts_dtype)[0]
         if int(c["error"]) != 0:
-            raise SimlodError(f"simlod_query_rays reported error bits {int(c['error']):#x} ({int(c['numNodes'])} nodes, {int(c['numPairs'])} pairs)")
+            raise SimlodError(f"{fn} reported error bits {int(c['error']):#x} ({int(c['numNodes'])} nodes, {int(c['numPairs'])} pairs)")
         return c
 
-    def _rays_tensor(self, rays):
-        if isinstance(rays, torch.Tensor):
-            t = rays.reshape(-1).view(torch.uint8)
-            if t.device != self.device or t.numel() == 0 or t.numel() % abi.ray_dtype.itemsize:
-                raise SimlodError("rays: a non-empty tensor of whole SimlodRay records on this octree's device")
+    def _records_tensor(self, what, records):
+        """The records of a simlod_query_<what> call (an octree_io.Rays / Spheres, or a device tensor of whole records) as a uint8 tensor on
+        this octree's device."""
+        dtype, name, struct, _ = self._PAIR_QUERIES[what]
+        if isinstance(records, torch.Tensor):
+            t = records.reshape(-1).view(torch.uint8)
+            if t.device != self.device or t.numel() == 0 or t.numel() % dtype.itemsize:
+                raise SimlodError(f"{name}: a non-empty tensor of whole {struct} records on this octree's device")
             return t
-        rec = np.ascontiguousarray(rays.record())
+        rec = np.ascontiguousarray(records.record())
         if len(rec) == 0:
-            raise SimlodError("rays: an empty batch")
+            raise SimlodError(f"{name}: an empty batch")
         return torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(self.device)
 
+    # -- ray queries (include/simlod_hip.h, "ray queries") ---------------------------------------------------------------------------------
     def count_rays(self, uniforms, rays, max_level=None, select="cut"):
         """The SimlodRayCounts record of a count-only simlod_query_rays call (numNodes, numHits, numInvalid, numPairs, numCandidates)."""
-        return self._rays(uniforms, self._rays_tensor(rays), max_level, select, None)
+        return self._pair_query("rays", uniforms, self._records_tensor("rays", rays), (), max_level, select, (None,))
 
     def cast_rays(self, uniforms, rays, max_level=None, select="cut", return_counts=False):
         """The first sample in the cone along each ray (an octree_io.Rays, or a device tensor of SimlodRay records): a count-only call, scratch
         sized from its counts, then the hits — a numpy record array (abi.ray_hit_dtype) for host rays, a uint8 device tensor of the same
         records for device rays.  `node` / `ordinal` refer to export_octree(max_level, select).  A miss has t = inf and node = EXPORT_NONE."""
-        t = self._rays_tensor(rays)
-        c = self._rays(uniforms, t, max_level, select, None)
+        t = self._records_tensor("rays", rays)
+        c = self._pair_query("rays", uniforms, t, (), max_level, select, (None,))
         hits = torch.empty(t.numel() // abi.ray_dtype.itemsize * abi.ray_hit_dtype.itemsize, dtype=torch.uint8, device=self.device)
-        c = self._rays(uniforms, t, max_level, select, hits, int(c["numPairs"]), int(c["numCandidates"]))
+        c = self._pair_query("rays", uniforms, t, (), max_level, select, (hits,), c)
         out = hits if isinstance(rays, torch.Tensor) else hits.cpu().numpy().view(abi.ray_hit_dtype)
         return (out, c) if return_counts else out
 
     # -- neighbour queries (include/simlod_hip.h, "neighbour queries") ---------------------------------------------------------------------
-    def _neighbours(self, uniforms, queries, k, max_level, select, out, within, pairs=0, candidates=0):
-        """One simlod_query_neighbours call -> the SimlodNeighbourCounts record (host).  out None: count only.  `queries`: a uint8 device
-        tensor of SimlodSphere records."""
-        u, up = self._u(uniforms)
-        sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
-        ml = abi.MAX_DEPTH if max_level is None else max(0, min(int(max_level), abi.MAX_DEPTH))
-        st = self.read_stats()
-        nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
-        n = queries.numel() // abi.sphere_dtype.itemsize
-        scratch = self._export_scratch(int(self.L.simlod_neighbours_buffer_min_bytes(nn, bound, n, k, pairs, candidates)))
-        counts = torch.zeros(abi.neighbour_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
-        _check(self.L.simlod_query_neighbours(self._p(self.nodes), self._p(self.stats), up, self._p(queries), n, k, ml, sel, self._p(scratch),
-                                              ctypes.c_uint64(scratch.numel()), None, nn, None if out is None else self._p(out),
-                                              None if within is None else self._p(within), self._p(counts), self._stream()), "simlod_query_neighbours")
-        c = counts.cpu().numpy().view(abi.neighbour_counts_dtype)[0]
-        if int(c["error"]) != 0:
-            raise SimlodError(f"simlod_query_neighbours reported error bits {int(c['error']):#x} ({int(c['numNodes'])} nodes, {int(c['numPairs'])} pairs)")
-        return c
-
-    def _spheres_tensor(self, spheres, k):
+    @staticmethod
+    def _k(k):
         if not 1 <= int(k) <= abi.NEIGHBOURS_MAX_K:
             raise SimlodError(f"k = {k}: 1 .. {abi.NEIGHBOURS_MAX_K}")
-        if isinstance(spheres, torch.Tensor):
-            t = spheres.reshape(-1).view(torch.uint8)
-            if t.device != self.device or t.numel() == 0 or t.numel() % abi.sphere_dtype.itemsize:
-                raise SimlodError("spheres: a non-empty tensor of whole SimlodSphere records on this octree's device")
-            return t
-        rec = np.ascontiguousarray(spheres.record())
-        if len(rec) == 0:
-            raise SimlodError("spheres: an empty batch")
-        return torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(self.device)
+        return int(k)
 
     def count_neighbours(self, uniforms, spheres, k, max_level=None, select="cut"):
         """The SimlodNeighbourCounts record of a count-only simlod_query_neighbours call (numNodes, numInvalid, numPairs, numCandidates;
         numFound and numWithin are 0: no sample is tested)."""
-        return self._neighbours(uniforms, self._spheres_tensor(spheres, k), int(k), max_level, select, None, None)
+        k = self._k(k)
+        return self._pair_query("neighbours", uniforms, self._records_tensor("neighbours", spheres), (k,), max_level, select, (None, None))
 
     def find_neighbours(self, uniforms, spheres, k, max_level=None, select="cut", return_counts=False):
         """The k nearest samples within the radius of each query (an octree_io.Spheres, or a device tensor of SimlodSphere records): a
@@ -753,13 +743,13 @@ class DeviceOctree:
         (abi.neighbour_dtype) and an int array; device queries: a uint8 device tensor of the same records and a device tensor of n int32
         counts.  `node` / `ordinal` refer to export_octree(max_level, select).  The places behind min(k, within) hold d2 = inf and
         node = EXPORT_NONE."""
-        k = int(k)
-        t = self._spheres_tensor(spheres, k)
+        k = self._k(k)
+        t = self._records_tensor("neighbours", spheres)
         n = t.numel() // abi.sphere_dtype.itemsize
-        c = self._neighbours(uniforms, t, k, max_level, select, None, None)
+        c = self._pair_query("neighbours", uniforms, t, (k,), max_level, select, (None, None))
         out = torch.empty(n * k * abi.neighbour_dtype.itemsize, dtype=torch.uint8, device=self.device)
         within = torch.empty(n, dtype=torch.int32, device=self.device)
-        c = self._neighbours(uniforms, t, k, max_level, select, out, within, int(c["numPairs"]), int(c["numCandidates"]))
+        c = self._pair_query("neighbours", uniforms, t, (k,), max_level, select, (out, within), c)
         if not isinstance(spheres, torch.Tensor):
             out, within = out.cpu().numpy().view(abi.neighbour_dtype).reshape(n, k), within.cpu().numpy().view(np.uint32).astype(np.int64)
         return (out, within, c) if return_counts else (out, within)

@@ -41,8 +41,8 @@ def test_export_symbols_exported(built_libs):
 
 def test_scratch_bounds_are_exactly_the_layouts(built_libs):
     """The three scratch bounds are a contract with callers: each is pinned to the layout it states, region by region (csrc/export_common.inc
-    Layout, export_region.inc QueryLayout, export_rays.inc RayLayout): a 256-byte header (two for the rays), every array rounded up to 256
-    bytes, then 32 bytes per chunk item, per pair, and 16 per further thousand candidates."""
+    Layout, export_region.inc QueryLayout, export_pairs.inc PairLayout): a 256-byte header (two for the pair queries), every array rounded
+    up to 256 bytes, then 32 bytes per chunk item, per pair, and 16 per further thousand candidates."""
     from simlod_amd import runtime
     L = runtime.lib()
 

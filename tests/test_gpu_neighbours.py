@@ -1,7 +1,7 @@
 """GPU tier: simlod_query_neighbours (include/simlod_hip.h, "neighbour queries") through the C ABI against the host mirror
 OctreeExport.neighbours on the device's own export, byte for byte, and against a brute force over the input points; exact ties, more
 queries on one node than a tile holds, count-only calls, capacities, refused arguments, degenerate queries, the limit of 2^20 queries,
-imported octrees and a box off the origin."""
+imported octrees and a box off the origin; the ray and the neighbour query in turn on one octree's cached scratch."""
 import ctypes
 
 import numpy as np
@@ -11,9 +11,10 @@ import torch
 import cases
 import neighbours_ref as nr
 import oracle
+import rays_ref as yr
 from simlod_amd import abi, synthetic
 from simlod_amd.octree_io import Spheres
-from util import STATS_BUILD_FIELDS, assert_dumps_equal, assert_stats_equal, host_image_of
+from util import STATS_BUILD_FIELDS, _build, _chunks, _device, _ingest, assert_dumps_equal, assert_stats_equal, host_image_of
 
 pytestmark = pytest.mark.gpu
 W, H = cases.W, cases.H
@@ -23,50 +24,12 @@ NONE = abi.EXPORT_NONE
 NB, CB = abi.neighbour_dtype.itemsize, abi.neighbour_counts_dtype.itemsize
 
 
-def _device(**kw):
-    from simlod_amd.runtime import DeviceOctree
-    kw.setdefault("persistent_bytes", 2 << 30)
-    kw.setdefault("max_pixels", 1920 * 1080)
-    dev = DeviceOctree("cuda:0", **kw)
-    # nothing may trust bytes it did not write (tests/test_gpu_parity.py _device)
-    dev.momentary.fill_(0xA5); dev.render_buffer.fill_(0xA5); dev.persistent.fill_(0xA5)
-    return dev
-
-
-def _ingest(dev, u, batches):
-    for b in batches:
-        if dev.uploaded_host - dev.processed() >= dev.ring_slots:
-            dev.drain(u)
-        dev.upload(b)
-    dev.drain(u)
-    assert int(dev.read_stats()["dbg"]) == 0
-
-
-def _build(name, offset=None):
-    dev = _device()
-    if offset is None:
-        pts, box, batch, T = cases.case(name)
-        u = dev.uniforms(W, H, T, box)
-    else:
-        pts, box_min, box, batch = cases.shifted(name, offset)
-        u = dev.uniforms(W, H, cases.shifted_cam(box, offset), box, box_min=box_min)
-    dev.reset(u)
-    _ingest(dev, u, cases.batches_of(name, pts, batch))
-    return dev, u, pts, box
-
-
 def _build_points(pts, box, batch):
     dev = _device()
     u = dev.uniforms(W, H, cases._cam(box), box)
     dev.reset(u)
     _ingest(dev, u, [pts[i:i + batch] for i in range(0, len(pts), batch)])
     return dev, u
-
-
-def _chunks(export):
-    """The chunk items of an export's table: ceil(numSamples / 1000) per node."""
-    ns = export.nodes["numSamples"].astype(np.int64)
-    return int(((ns + abi.POINTS_PER_CHUNK - 1) // abi.POINTS_PER_CHUNK).sum())
 
 
 class Raw:
@@ -436,3 +399,27 @@ def test_queries_leave_their_source_alone(built_libs):
     nodes, pers, n = host_image_of(dev)
     assert_dumps_equal(oracle.dump_image(nodes, n), ref.dump(), name)
     assert_stats_equal(dev.read_stats(), ref.stats[0], STATS_BUILD_FIELDS, name)
+
+
+def test_queries_alternate_on_one_scratch(built_libs):
+    """The ray and the neighbour query share the pair kernels, the scratch layout and, through DeviceOctree, one cached scratch tensor: calls
+    of both in turn (CUT @ 20) return what each returns alone, and no call sees what the one before left in the buffer."""
+    name = "uniform_3x40k"
+    dev, u, pts, box = _build(name)
+    full = dev.export_octree(u)
+    rays = yr.ray_sets(name, pts, box)["vertical r0.003"][0]
+    q, k = nr.wide(pts, box), 8
+    hits, rc = full.cast(rays, return_counts=True)
+    nb, within, nc = full.neighbours(q, k, return_counts=True)
+    assert int(rc["numHits"]) > 0 and int(rc["numPairs"]) > 0 and int(nc["numPairs"]) > 0 and int(nc["numWithin"]) > 0
+    first = dev.cast_rays(u, rays)
+    got, gw = dev.find_neighbours(u, q, k)
+    again = dev.cast_rays(u, rays)
+    crays = dev.count_rays(u, rays)
+    cnb = dev.count_neighbours(u, q, k)
+    assert first.tobytes() == hits.tobytes() and again.tobytes() == first.tobytes()
+    assert got.tobytes() == nb.tobytes() and np.array_equal(gw, within)
+    assert {f: int(crays[f]) for f in abi.ray_counts_dtype.names} == {f: int(rc[f]) for f in abi.ray_counts_dtype.names}
+    same = [f for f in COUNT_FIELDS if f not in ("numFound", "numWithin")]
+    assert {f: int(cnb[f]) for f in same} == {f: int(nc[f]) for f in same}
+    assert int(cnb["numFound"]) == 0 and int(cnb["numWithin"]) == 0

@@ -12,51 +12,13 @@ import oracle
 import rays_ref as yr
 from simlod_amd import abi, synthetic
 from simlod_amd.octree_io import Rays
-from util import STATS_BUILD_FIELDS, assert_dumps_equal, assert_stats_equal, host_image_of
+from util import STATS_BUILD_FIELDS, _build, _chunks, _device, _ingest, assert_dumps_equal, assert_stats_equal, host_image_of
 
 pytestmark = pytest.mark.gpu
 W, H = cases.W, cases.H
 MODES = [("cut", 20), ("all", 20), ("cut", 2)]
 COUNT_FIELDS = list(abi.ray_counts_dtype.names)
 NONE = abi.EXPORT_NONE
-
-
-def _device(**kw):
-    from simlod_amd.runtime import DeviceOctree
-    kw.setdefault("persistent_bytes", 2 << 30)
-    kw.setdefault("max_pixels", 1920 * 1080)
-    dev = DeviceOctree("cuda:0", **kw)
-    # nothing may trust bytes it did not write (tests/test_gpu_parity.py _device)
-    dev.momentary.fill_(0xA5); dev.render_buffer.fill_(0xA5); dev.persistent.fill_(0xA5)
-    return dev
-
-
-def _ingest(dev, u, batches):
-    for b in batches:
-        if dev.uploaded_host - dev.processed() >= dev.ring_slots:
-            dev.drain(u)
-        dev.upload(b)
-    dev.drain(u)
-    assert int(dev.read_stats()["dbg"]) == 0
-
-
-def _build(name, offset=None):
-    dev = _device()
-    if offset is None:
-        pts, box, batch, T = cases.case(name)
-        u = dev.uniforms(W, H, T, box)
-    else:
-        pts, box_min, box, batch = cases.shifted(name, offset)
-        u = dev.uniforms(W, H, cases.shifted_cam(box, offset), box, box_min=box_min)
-    dev.reset(u)
-    _ingest(dev, u, cases.batches_of(name, pts, batch))
-    return dev, u, pts, box
-
-
-def _chunks(export):
-    """The chunk items of an export's table: ceil(numSamples / 1000) per node."""
-    ns = export.nodes["numSamples"].astype(np.int64)
-    return int(((ns + abi.POINTS_PER_CHUNK - 1) // abi.POINTS_PER_CHUNK).sum())
 
 
 class Raw:

@@ -11,40 +11,12 @@ import oracle
 import region_ref as rr
 from simlod_amd import abi, synthetic
 from simlod_amd.octree_io import Region
-from util import STATS_BUILD_FIELDS, assert_dumps_equal, assert_stats_equal, host_image_of
+from util import STATS_BUILD_FIELDS, _build, _device, _ingest, assert_dumps_equal, assert_stats_equal, host_image_of
 
 pytestmark = pytest.mark.gpu
 W, H = cases.W, cases.H
 MODES = [("cut", 20), ("all", 20), ("cut", 2)]
 COUNT_FIELDS = list(abi.query_counts_dtype.names)
-
-
-def _device(**kw):
-    from simlod_amd.runtime import DeviceOctree
-    kw.setdefault("persistent_bytes", 2 << 30)
-    kw.setdefault("max_pixels", 1920 * 1080)
-    dev = DeviceOctree("cuda:0", **kw)
-    # nothing may trust bytes it did not write (tests/test_gpu_parity.py _device)
-    dev.momentary.fill_(0xA5); dev.render_buffer.fill_(0xA5); dev.persistent.fill_(0xA5)
-    return dev
-
-
-def _ingest(dev, u, batches):
-    for b in batches:
-        if dev.uploaded_host - dev.processed() >= dev.ring_slots:
-            dev.drain(u)
-        dev.upload(b)
-    dev.drain(u)
-    assert int(dev.read_stats()["dbg"]) == 0
-
-
-def _build(name):
-    pts, box, batch, T = cases.case(name)
-    dev = _device()
-    u = dev.uniforms(W, H, T, box)
-    dev.reset(u)
-    _ingest(dev, u, cases.batches_of(name, pts, batch))
-    return dev, u, pts, box
 
 
 class Raw:

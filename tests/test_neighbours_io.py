@@ -258,8 +258,9 @@ def test_pair_counts(octrees):
 
 
 def test_neighbour_kernels_use_no_scratch():
-    """`make resource-usage` on export.hip (the neighbour kernels are its export_neighbours.inc): everything stays in registers and LDS, and
-    sharing the descent left the ray kernels as they were — six of them, none with scratch."""
+    """`make resource-usage` on export.hip: the neighbour query's five kernels of its own (the pair pipeline of export_pairs.inc over NbQuery,
+    k_n_test and k_n_reduce of export_neighbours.inc) keep everything in registers and LDS, and sharing the pipeline left the ray query
+    as it was — six kernels, none with scratch."""
     import shutil
     import subprocess
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -268,8 +269,9 @@ def test_neighbour_kernels_use_no_scratch():
     out = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "simlod_amd", "csrc"), "resource-usage", "RU_SRCS=export.hip"], capture_output=True, text=True, check=True).stdout
     blocks = re.split(r"Function Name: ", out)[1:]
     scratch = {b.split()[0]: int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1)) for b in blocks}
-    nbk = {k: v for k, v in scratch.items() if "k_n_" in k}
-    assert len(nbk) == 5 and all(any(n in k for k in nbk) for n in ("k_n_pairs", "k_n_scan", "k_n_test", "k_n_reduce")), sorted(scratch)
+    nbk = {k: v for k, v in scratch.items() if ("k_p_" in k and "NbQuery" in k) or "k_n_" in k}
+    assert len(nbk) == 5 and sum("k_p_pairs" in k for k in nbk) == 2, sorted(scratch)
+    assert all(any(n in k for k in nbk) for n in ("k_p_pairs", "k_p_scan", "k_n_test", "k_n_reduce")), sorted(scratch)
     assert all(v == 0 for v in nbk.values()), nbk
-    rays = {k: v for k, v in scratch.items() if "k_r_" in k}
+    rays = {k: v for k, v in scratch.items() if "k_p_hier" in k or ("k_p_" in k and "RayQuery" in k) or "k_r_" in k}
     assert len(rays) == 6 and all(v == 0 for v in rays.values()), rays

@@ -279,8 +279,8 @@ def test_pair_counts(octrees):
 
 
 def test_sample_test_kernel_uses_no_scratch():
-    """`make resource-usage` on export.hip (the ray kernels are its export_rays.inc): they keep everything in registers and LDS (a spill in
-    the hot loop of k_r_test would halve it)."""
+    """`make resource-usage` on export.hip: the ray query's six kernels (the pair pipeline of export_pairs.inc over RayQuery, k_r_test and
+    k_r_reduce of export_rays.inc) keep everything in registers and LDS (a spill in the hot loop of k_r_test would halve it)."""
     import shutil
     import subprocess
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -289,6 +289,7 @@ def test_sample_test_kernel_uses_no_scratch():
     out = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "simlod_amd", "csrc"), "resource-usage", "RU_SRCS=export.hip"], capture_output=True, text=True, check=True).stdout
     blocks = re.split(r"Function Name: ", out)[1:]
     scratch = {b.split()[0]: int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1)) for b in blocks}
-    rays = {k: v for k, v in scratch.items() if "k_r_" in k}
-    assert len(rays) == 6 and any("k_r_test" in k for k in rays), sorted(scratch)
+    rays = {k: v for k, v in scratch.items() if "k_p_hier" in k or ("k_p_" in k and "RayQuery" in k) or "k_r_" in k}
+    assert len(rays) == 6 and sum("k_p_pairs" in k for k in rays) == 2, sorted(scratch)
+    assert all(any(n in k for k in rays) for n in ("k_p_hier", "k_p_pairs", "k_p_scan", "k_r_test", "k_r_reduce")), sorted(scratch)
     assert all(v == 0 for v in rays.values()), rays

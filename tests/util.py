@@ -1,6 +1,7 @@
 """Comparison helpers shared by the parity tests (H6-aware: see SURVEY.md §2.5)."""
 import numpy as np
 
+import cases
 import oracle
 from simlod_amd import abi
 
@@ -270,3 +271,42 @@ def assert_frame_equals_oracle(dev, nodes, nn, u, what, floor):
         assert int((fb != abi.CLEAR_PIXEL).sum()) > floor, f"{what}: the case must draw something"
     assert int(np.abs(col_dev.view(np.uint8).astype(np.int16) - col.view(np.uint8).astype(np.int16)).max()) <= 1, f"{what}: RGBA8 differs by more than 1"
     return fb_dev, col_dev, st, vis
+
+
+# -- what the GPU query tests (region, rays, neighbours) build their octrees with ------------------------------------------------------
+def _device(**kw):
+    from simlod_amd.runtime import DeviceOctree
+    kw.setdefault("persistent_bytes", 2 << 30)
+    kw.setdefault("max_pixels", 1920 * 1080)
+    dev = DeviceOctree("cuda:0", **kw)
+    # nothing may trust bytes it did not write (tests/test_gpu_parity.py _device)
+    dev.momentary.fill_(0xA5); dev.render_buffer.fill_(0xA5); dev.persistent.fill_(0xA5)
+    return dev
+
+
+def _ingest(dev, u, batches):
+    for b in batches:
+        if dev.uploaded_host - dev.processed() >= dev.ring_slots:
+            dev.drain(u)
+        dev.upload(b)
+    dev.drain(u)
+    assert int(dev.read_stats()["dbg"]) == 0
+
+
+def _build(name, offset=None):
+    dev = _device()
+    if offset is None:
+        pts, box, batch, T = cases.case(name)
+        u = dev.uniforms(cases.W, cases.H, T, box)
+    else:
+        pts, box_min, box, batch = cases.shifted(name, offset)
+        u = dev.uniforms(cases.W, cases.H, cases.shifted_cam(box, offset), box, box_min=box_min)
+    dev.reset(u)
+    _ingest(dev, u, cases.batches_of(name, pts, batch))
+    return dev, u, pts, box
+
+
+def _chunks(export):
+    """The chunk items of an export's table: ceil(numSamples / 1000) per node."""
+    ns = export.nodes["numSamples"].astype(np.int64)
+    return int(((ns + abi.POINTS_PER_CHUNK - 1) // abi.POINTS_PER_CHUNK).sum())
