@@ -67,3 +67,10 @@ def keys_of(table):
     """(level, X, Y, Z) of each entry as one integer per entry, the key oracle.dump_image sorts by."""
     t = table.view(abi.export_node_dtype)
     return (t["level"].astype(np.uint64) << np.uint64(60)) | (t["X"].astype(np.uint64) << np.uint64(40)) | (t["Y"].astype(np.uint64) << np.uint64(20)) | t["Z"].astype(np.uint64)
+
+
+def entry_index(table):
+    """{(level, X, Y, Z): table index}.  (keys_of keeps four bits of the level: from level 16 on it wraps, which sorting a dump survives and a
+    lookup by a Python integer does not.)"""
+    t = table.view(abi.export_node_dtype)
+    return {(int(l), int(x), int(y), int(z)): i for i, (l, x, y, z) in enumerate(zip(t["level"], t["X"], t["Y"], t["Z"]))}

@@ -53,14 +53,18 @@ def assert_same_multiset(got, want, what=""):
     assert np.array_equal(sorted_samples(got), sorted_samples(want)), f"{what}: the samples differ as multisets"
 
 
-def host_octree(name=None, pts=None, box=None, batch=None, box_min=(0, 0, 0)):
-    """An octree built by the oracle's port from a case of tests/cases.py (or from `pts`) -> (full export as OctreeExport, points, box, HostOctree).
-    With `box_min` the case's points are moved by it (cases.shifted) and the box starts there."""
+def host_octree(name=None, pts=None, box=None, batch=None, box_min=(0, 0, 0), batches=None, export=True):
+    """An octree built by the oracle's port from a case of tests/cases.py (or from `pts`, or from `batches` of unequal sizes)
+    -> (full export as OctreeExport, points, box, HostOctree).
+    With `box_min` the case's points are moved by it (cases.shifted) and the box starts there.  export=False: no export (None in its place),
+    for an image export_host cannot walk as it stands."""
     if name is not None:
         pts, box, batch, T = cases.case(name)
         if tuple(box_min) != (0, 0, 0):
             pts, box_min, box, batch = cases.shifted(name, box_min)
         batches = cases.batches_of(name, pts, batch)
+    elif batches is not None:
+        pts = np.concatenate(batches)
     else:
         batches = [pts[i:i + batch] for i in range(0, len(pts), batch)]
     u = cases.uniforms_for(box, np.eye(4, dtype=np.float32), box_min=box_min)
@@ -70,5 +74,7 @@ def host_octree(name=None, pts=None, box=None, batch=None, box_min=(0, 0, 0)):
         if len(b):
             ho.add_points(u, b, len(b))
     assert int(ho.stats["dbg"][0]) == 0
+    if not export:
+        return None, pts, box, ho
     t, s = export_host(ho.nodes, int(ho.stats["numNodes"][0]))
     return OctreeExport(t, s, u["boxMin"], u["boxMax"]), pts, box, ho

@@ -27,28 +27,42 @@ SIZES = (60_000, 400_000, 100_000, 2_000)      # A, B, C, D
 LIMIT = 50_000                                 # a leaf splits when it holds more (voxels.cu:209-217)
 VOX_SMALL = 512                                # construct_expand.inc: a leaf with fewer new samples goes the wave-per-leaf way
 CELL_LEVELS = [11, 9]
+OFF_ORIGIN_MARGIN = 1.0 / 64.0                 # of a cell of level cell_level + 2, off the origin: far more than the fp32 rounding of a coordinate there
 _CASES, _REFS = {}, {}
 
 
-def deep_case(cell_level):
-    """-> (box, [A, B, C, D], per batch the 64 counts of the cells of level cell_level + 2, index x << 4 | y << 2 | z)"""
-    if cell_level not in _CASES:
+def deep_case(cell_level, scale=1.0, cell=None):
+    """-> (box, [A, B, C, D], per batch the 64 counts of the cells of level cell_level + 2, index x << 4 | y << 2 | z)
+    `scale` (a power of two) is the size of the box; `cell` the cell of level cell_level the points go into, (0, 0, 0) by default.  Off the
+    origin a coordinate is formed in fp64 and rounded to fp32, so the margin that keeps a point strictly inside its cell is wider there."""
+    key = (cell_level, float(scale), None if cell is None else tuple(int(c) for c in cell))
+    if key not in _CASES:
         rs = np.random.RandomState(100 + cell_level)
-        scale = np.float32(2.0 ** -(cell_level + 2))
+        assert np.frexp(float(scale))[0] == 0.5, "the box size is a power of two"
+        size = np.float32(float(scale) * 2.0 ** -(cell_level + 2))                 # of a cell of level cell_level + 2
         batches, counts = [], []
         for n in SIZES:
-            cell = rs.randint(0, 4, size=(n, 3))
-            v = (rs.random_sample((n, 3)) * 0.998 + 0.001).astype(np.float32)      # strictly inside the cell: no sample on a face
-            p = (cell.astype(np.float32) + v) * scale                              # (a power of two: exact)
-            assert np.array_equal(np.floor(p / scale).astype(np.int64), cell)
+            sub = rs.randint(0, 4, size=(n, 3))
+            r = rs.random_sample((n, 3))
+            if cell is None:
+                v = (r * 0.998 + 0.001).astype(np.float32)                         # strictly inside the cell: no sample on a face
+                p = (sub.astype(np.float32) + v) * size                            # (a power of two: exact)
+                want = sub
+            else:
+                assert all(0 <= int(c) < 1 << cell_level for c in cell)
+                v = r * (1.0 - 2.0 * OFF_ORIGIN_MARGIN) + OFF_ORIGIN_MARGIN
+                want = sub + 4 * np.asarray(cell, dtype=np.int64)
+                p = ((want.astype(np.float64) + v) * np.float64(size)).astype(np.float32)
+                v = v.astype(np.float32)
+            assert np.array_equal(np.floor(p.astype(np.float64) / np.float64(size)).astype(np.int64), want)
             c = np.floor(v * np.float32(255.0)).astype(np.uint32)
             pts = np.empty(n, dtype=abi.point_dtype)
             pts["x"], pts["y"], pts["z"] = p[:, 0], p[:, 1], p[:, 2]
             pts["color"] = c[:, 0] | (c[:, 1] << 8) | (c[:, 2] << 16) | np.uint32(255 << 24)
             batches.append(pts)
-            counts.append(np.bincount(cell[:, 0] << 4 | cell[:, 1] << 2 | cell[:, 2], minlength=64))
-        _CASES[cell_level] = (np.array([1, 1, 1], dtype=np.float32), batches, counts)
-    return _CASES[cell_level]
+            counts.append(np.bincount(sub[:, 0] << 4 | sub[:, 1] << 2 | sub[:, 2], minlength=64))
+        _CASES[key] = (np.array([scale, scale, scale], dtype=np.float32), batches, counts)
+    return _CASES[key]
 
 
 def _upper(counts64):

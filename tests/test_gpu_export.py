@@ -148,14 +148,14 @@ def test_export_visible(built_libs, hqs):
     _assert_export(ex, t, s, "visible")
 
 
-def _frames_equal(src, dst, u, what):
+def _frames_equal(src, dst, u, what, floor=1000):
     nodes, pers, nn = host_image_of(src)
     for name, v in _variants(u):
         src.render(v)
         fb_s, col_s = src.framebuffer(W, H), src.color(W, H)
         dst.render(v)
         fb_d, col_d = dst.framebuffer(W, H), dst.color(W, H)
-        assert int((fb_s != abi.CLEAR_PIXEL).sum()) > 1000, (what, name)
+        assert int((fb_s != abi.CLEAR_PIXEL).sum()) > floor, (what, name)
         assert np.array_equal(fb_d, fb_s), f"{what} {name}: {int((fb_d != fb_s).sum())} pixels differ from the source frame"
         assert np.array_equal(col_d, col_s), f"{what} {name}: colour plane differs from the source frame"
         fb_o, col_o = _oracle_render(nodes, nn, v)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import oracle
-from export_ref import keys_of
+from export_ref import entry_index
 from resume_ref import rebuild_grids, root_leaf_voxels
 from simlod_amd import abi, camera, synthetic
 from test_gpu_export import _device, _frames_equal
@@ -88,19 +88,20 @@ def _import(dst, ld, u):
     return uu
 
 
-def _check_import(src, dst, ex, u, what):
-    """Right after the buildable import: the source's dump (grids included), resume_ref's grids byte for byte, the same export, the same frames."""
+def _check_import(src, dst, ex, u, what, floor=1000):
+    """Right after the buildable import: the source's dump (grids included), resume_ref's grids byte for byte, the same export, the same frames
+    (more than `floor` pixels drawn)."""
     nodes_s, pers_s, ns = host_image_of(src)
     nodes_d, pers_d, nd = host_image_of(dst)
     _assert_fields(oracle.dump_image(nodes_d, nd), oracle.dump_image(nodes_s, ns), RESUME_FIELDS, f"{what} (import vs source)")
     oracle.check_invariants(nodes_d, nd)
     grids = rebuild_grids(ex.nodes, ex.samples, u)
-    where = {int(k): i for i, k in enumerate(keys_of(ex.nodes))}
+    where = entry_index(ex.nodes)
     have = np.nonzero(nodes_d["grid"][:nd] != 0)[0]
     assert len(have) == len(grids)
     for i in have:
         n = nodes_d[i]
-        key = (int(n["level"]) << 60) | (int(n["X"]) << 40) | (int(n["Y"]) << 20) | int(n["Z"])
+        key = (int(n["level"]), int(n["X"]), int(n["Y"]), int(n["Z"]))
         off = int(n["grid"]) - pers_d.ctypes.data
         assert np.array_equal(pers_d[off: off + abi.GRID_BYTES].view(np.uint32), grids[where[key]]), f"{what}: grid of node {i} differs from resume_ref's"
     if ex.nodes[0]["childMask"] == 0:
@@ -115,7 +116,7 @@ def _check_import(src, dst, ex, u, what):
     re = dst.export_octree(u)
     assert re.nodes.tobytes() == ex.nodes.tobytes() and re.samples.tobytes() == ex.samples.tobytes(), f"{what}: the re-export differs"
     if ex.nodes[0]["childMask"] != 0:
-        _frames_equal(src, dst, u, what)
+        _frames_equal(src, dst, u, what, floor)
     else:
         # a root that is still a leaf draws its voxels too, and the source coloured those by whichever point got there first (scheduling
         # dependent): positions, hence depths, are bit-equal
@@ -127,6 +128,12 @@ def _check_import(src, dst, ex, u, what):
 
 def _resume(name, tmp_path, dst=None, check_import=True, **kw):
     pts, box, batches, cut = _input(name)
+    return _resume_batches(name, box, batches, cut, tmp_path, dst=dst, check_import=check_import, pts=pts, **kw)
+
+
+def _resume_batches(name, box, batches, cut, tmp_path, dst=None, check_import=True, pts=None, feed=_feed, **kw):
+    """Build batches[:cut], export through a file, import buildable into `dst` (a fresh device by default), feed batches[cut:] with `feed`, and
+    compare with the oracle's continuous build of all batches.  -> (dst, its uniforms, the export)"""
     T = cases._cam(box)
     src = _device()
     u = src.uniforms(W, H, T, box)
@@ -139,7 +146,7 @@ def _resume(name, tmp_path, dst=None, check_import=True, **kw):
     if check_import:
         _check_import(src, dst, ex, uu, name)
     del src
-    _feed(dst, uu, batches[cut:])
+    feed(dst, uu, batches[cut:])
     ref = _continuous(uu, batches)
     nodes, pers, n = host_image_of(dst)
     _assert_fields(oracle.dump_image(nodes, n), ref.dump(), RESUME_FIELDS, f"{name} (resume vs continuous)")
@@ -148,7 +155,7 @@ def _resume(name, tmp_path, dst=None, check_import=True, **kw):
     _assert_stats(st, ref.stats[0], name)
     assert int(st["dbg"]) == 0 and int(st["batchletIndex"]) == len(batches) - cut
     assert int(st["numPointsProcessed"]) == sum(len(b) for b in batches[cut:])
-    if len(pts) <= 100_000:
+    if pts is not None and len(pts) <= 100_000:
         assert voxel_colors_are_member(nodes, n, pts, box) > 0
     return dst, uu, ex
 
