@@ -427,6 +427,56 @@ int simlod_query_region(const SimlodNode* nodes, const SimlodStats* stats, const
                         uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
                         SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, void* stream);
 
+/* ---- footprint queries: the samples inside an extruded polygon at a chosen level of detail ------------------------------------------------
+ * simlod_query_footprint is simlod_query_region plus a footprint: a polygon of up to 256 vertices in a plane the points are mapped into by an
+ * affine map, extruded along the map's null direction (a parcel, a building outline, a lasso drawn in an orthographic view).  The polygon need
+ * not be convex.  Everything the region section says stays in force: the box, the inflated cube lo_a / hi_a of rule 1, the listing and
+ * selection rules, rule 5's count-only calls and capacities, SimlodQueryCounts, SIMLOD_EXPORT_REGION, the chunk-table / `next` sources.  The
+ * footprint composes with the region's half-spaces (polygon, height band and frustum in one call), and the result is an ordinary table.
+ * NOT COVERED: perspective lassos (u = x_clip / w); an affine map covers plan-view outlines and any orthographic view.
+ *
+ * All new geometry is fp64 computed from the fp32 inputs without fused multiply-add, every sum in the order written here; there is no division.
+ *  F1. Sample rule.  u = ((ux*x + uy*y) + uz*z) + u0 and v likewise from axisU / axisV.  For each edge i from a = P[i] to b = P[(i+1) mod n]:
+ *      du = b_u - a_u, dv = b_v - a_v, c = du*(v - a_v) - dv*(u - a_u); the edge is crossed iff (a_v > v) != (b_v > v) and (c > 0) == (dv > 0).
+ *      The sample passes the footprint iff the number of crossed edges is odd (the even-odd rule: self-intersecting polygons are defined; a
+ *      polygon of zero area passes nothing off its own line; a NaN coordinate passes nothing).  A sample exactly on an edge's line (c == 0)
+ *      crosses that edge iff it runs towards smaller v: a rectangle (lo, lo), (lo, hi), (hi, hi), (hi, lo) passes lo <= u <= hi, lo <= v < hi.
+ *      A sample passes the query iff it passes F1 and region rule 3.
+ *  F2. Projected rectangle of a node.  U_lo = ((ux*fx + uy*fy) + uz*fz) + u0 with f_a = u_a >= 0 ? lo_a : hi_a; U_hi from the opposite corner;
+ *      V_lo, V_hi likewise (the corner selection of region rules 1 and 4).  fp64 rounding is monotone, so the computed (u, v) of every sample
+ *      inside the inflated cube lies in the rectangle, in floating point and not only in exact arithmetic.
+ *  F3. Far edges.  Edge i is FAR from a node iff max(a_v, b_v) < V_lo, or min(a_v, b_v) > V_hi, or c(U_lo,V_lo), c(U_lo,V_hi), c(U_hi,V_lo),
+ *      c(U_hi,V_hi) are all > 0 or all < 0 (c is monotone in u and in v: the sign then holds for every sample of the node).  Any other edge
+ *      is NEAR.
+ *  F4. Node class by the footprint.  A node with a NEAR edge is FILTERED.  A node without one takes rule F1's verdict at (U_lo, V_lo): COPIED
+ *      if that point passes, else OUTSIDE.  The final class: OUTSIDE if outside by the planes or by the footprint, COPIED iff copied by both,
+ *      else FILTERED.  Each node is classified on its own; outside nodes are not listed, copied nodes contribute every sample without a test.
+ *  F5. For finite samples in the half-open box F3 / F4 change nothing against F1 applied to every sample — provided no corner value lies within
+ *      fp64 rounding of zero with the wrong exact sign (an edge's line grazing a node's corner).  The host mirror asserts this per query.
+ *  F6. footprint == NULL gives exactly simlod_query_region, byte for byte.  `region` is required and may have zero planes.
+ *  F7. hipErrorInvalidValue with nothing enqueued: everything simlod_query_region refuses, numVertices outside 3..256, a non-finite vertex or
+ *      axis coefficient, nonzero `reserved`, scratchBytes below simlod_footprint_buffer_min_bytes(tableCapacity, 0). */
+#define SIMLOD_FOOTPRINT_MAX_VERTICES 256u
+typedef struct SimlodFootprint {       /* host memory, read before the call returns */
+	uint32_t numVertices;              /* 3..256; the polygon closes from the last vertex to the first */
+	uint32_t reserved[3];              /* 0 */
+	float    axisU[4], axisV[4];       /* u = ((ux*x + uy*y) + uz*z) + u0, v likewise: an affine map of the point into the polygon's plane */
+	float    vertices[SIMLOD_FOOTPRINT_MAX_VERTICES][2];   /* (u, v) */
+} SimlodFootprint;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodFootprint) == 2096, "Footprint");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodFootprint, axisU) == 16, "Footprint.axisU");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodFootprint, axisV) == 32, "Footprint.axisV");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodFootprint, vertices) == 48, "Footprint.vertices");
+
+/* simlod_query_buffer_min_bytes plus a fixed block for the polygon widened to fp64 (8 KB). */
+uint64_t simlod_footprint_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+
+/* The footprint query (rules above; arguments as simlod_query_region's).  Asynchronous on `stream` once `footprint` has been read. */
+int simlod_query_footprint(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                           const SimlodFootprint* footprint, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                           SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity,
+                           SimlodQueryCounts* counts, void* stream);
+
 /* ---- ray queries: the first sample in a cone along each ray of a batch ----------------------------------------------------------------------
  * simlod_query_rays answers "what does this ray hit" for up to 2^20 rays at once: per ray the sample with the smallest parameter t that lies
  * within radius + spread * t of the ray, among the samples of the nodes simlod_export_octree(maxLevel, select) selects.  The source is only read.

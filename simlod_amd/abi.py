@@ -138,6 +138,13 @@ query_counts_dtype = np.dtype({"names": ["numNodes", "error", "numSamples", "num
                                "formats": ["<u4", "<u4", "<u8", "<u8", "<u4", "<u4"], "offsets": [0, 4, 8, 16, 24, 28], "itemsize": 32})
 assert region_dtype.itemsize == 272 and query_counts_dtype.itemsize == 32
 
+# ---- footprint queries (include/simlod_hip.h, "footprint queries") ----------------------------------------------------------------------
+FOOTPRINT_MAX_VERTICES = 256
+footprint_dtype = np.dtype({"names": ["numVertices", "reserved", "axisU", "axisV", "vertices"],
+                            "formats": ["<u4", ("<u4", 3), ("<f4", 4), ("<f4", 4), ("<f4", (FOOTPRINT_MAX_VERTICES, 2))],
+                            "offsets": [0, 4, 16, 32, 48], "itemsize": 2096})
+assert footprint_dtype.itemsize == 2096
+
 # ---- ray queries (include/simlod_hip.h, "ray queries") -----------------------------------------------------------------------------------
 RAYS_MAX = 1 << 20
 ray_dtype = np.dtype({"names": ["origin", "tMin", "dir", "tMax", "radius", "spread", "reserved"],

@@ -16,6 +16,8 @@
 // with grid pointers — and, between k_copy and k_i_finish, the occupancy grids rebuilt from the samples: k_i_gleaf, k_i_gdown per level,
 // k_i_groot (export_grids.inc); k_i_finish then also writes the builder's counters as k_reset does.
 // Region query (simlod_query_region): k_q_hier -> k_q_dir -> k_q_count -> k_q_scan -> k_q_write, described in export_region.inc.
+// Footprint query (simlod_query_footprint): k_f_hier -> k_q_dir -> k_f_count -> k_q_scan -> k_f_write, the region query's sequence with an extruded
+// polygon on top of the planes, in export_footprint.inc.
 // Pair queries: k_p_hier -> k_q_dir -> k_p_pairs<Q, count> -> k_p_scan<Q> -> k_p_pairs<Q, fill> -> Q's test kernel -> Q's reduce kernel; the pipeline
 // is written once over a query trait Q, in export_pairs.inc.  Ray query (simlod_query_rays): RayQuery, k_r_test, k_r_reduce, in export_rays.inc.
 // Neighbour query (simlod_query_neighbours): NbQuery, k_n_test, k_n_reduce, in export_neighbours.inc.
@@ -39,6 +41,7 @@ namespace {
 #include "export_common.inc"   // constants, Header, Layout, block_scan, ExportArgs, leaf_rows_valid, scan_table, load_chunk4, copy_chunk, k_copy
 #include "export_table.inc"    // hier_walk, k_x_hier, k_x_scan, k_x_dir
 #include "export_region.inc"   // QueryGeom, classify, QItem, QueryLayout, QueryArgs, k_q_hier, k_q_dir, k_q_count, k_q_scan, k_q_write
+#include "export_footprint.inc"  // FootEdge, FootGeom, FootArgs, stage_edges, Footprint, classify_footprint, k_f_hier, k_f_count, k_f_write
 #include "export_pairs.inc"    // the pair records, PairLayout, PairArgs, k_p_hier, wave_descend, k_p_pairs, k_p_scan, TestView, test_chunk
 #include "export_rays.inc"     // RayArgs, ray_load, slab, sample_t, RayQuery, k_r_test, k_r_reduce
 #include "export_neighbours.inc"  // NbArgs, sphere_load, sphere_cube, sphere_d2, NbQuery, k_n_test, k_n_reduce
@@ -85,15 +88,18 @@ uint64_t query_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) {
 	return QueryLayout(nodeCapacity).x.items + (sampleBound / SIMLOD_POINTS_PER_CHUNK + nodeCapacity + 1u) * sizeof(QItem);
 }
 
-int launch_query(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region, uint32_t maxLevel,
-                 uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
-                 uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
+namespace {
+
+// What the region and the footprint query share in front of their launches: the checks of simlod_query_region and the kernels' arguments.
+// `frontBytes` of the scratch buffer are kept free in front of the items (the footprint's polygon; 0: the region query's layout).
+int prepare_query(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region, uint32_t maxLevel,
+                  uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
+                  uint64_t sampleCapacity, SimlodQueryCounts* counts, uint64_t frontBytes, QueryArgs& q) {
 	if (nodes == nullptr || stats == nullptr || u == nullptr || region == nullptr || scratch == nullptr || table == nullptr || counts == nullptr)
 		return (int)hipErrorInvalidValue;
 	if (region->numPlanes > SIMLOD_REGION_MAX_PLANES || region->reserved[0] != 0u || region->reserved[1] != 0u || region->reserved[2] != 0u)
 		return (int)hipErrorInvalidValue;
-	if ((select != SIMLOD_EXPORT_ALL && select != SIMLOD_EXPORT_CUT) || scratchBytes < query_min_bytes(tableCapacity, 0u)) return (int)hipErrorInvalidValue;
-	QueryArgs q{};
+	if ((select != SIMLOD_EXPORT_ALL && select != SIMLOD_EXPORT_CUT) || scratchBytes < query_min_bytes(tableCapacity, 0u) + frontBytes) return (int)hipErrorInvalidValue;
 	for (uint32_t p = 0; p < region->numPlanes; p++)
 		for (int k = 0; k < 4; k++) {
 			if (!std::isfinite(region->planes[p][k])) return (int)hipErrorInvalidValue;
@@ -107,17 +113,69 @@ int launch_query(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats
 	a.nodes = nodes; a.stats = stats; a.maxLevel = maxLevel; a.select = select; a.cap = tableCapacity;
 	a.scratch = reinterpret_cast<uint8_t*>(scratch); a.table = table; a.samples = samples; a.sampleCap = sampleCapacity;
 	const QueryLayout ql(tableCapacity);
-	a.lay = ql.x; a.lay.take_rest(scratchBytes);
+	a.lay = ql.x; a.lay.items += frontBytes; a.lay.take_rest(scratchBytes);
 	q.cls = ql.cls;
 	q.counts = counts;
 	bind_leaf_table(ctx, nodes, a);
-	const uint32_t grid = copy_grid(a.lay.itemCap);
+	return 0;
+}
+
+}  // namespace
+
+int launch_query(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region, uint32_t maxLevel,
+                 uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
+                 uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
+	QueryArgs q{};
+	const int rc = prepare_query(ctx, nodes, stats, u, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples, sampleCapacity, counts, 0u, q);
+	if (rc != 0) return rc;
+	const uint32_t grid = copy_grid(q.x.lay.itemCap);
 	SIMLOD_LAUNCH(k_q_hier, dim3(1), dim3(WG_TPB), stream, q);
 	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                        // k_q_dir: one wave per table entry
 	if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
 	SIMLOD_LAUNCH(k_q_count, dim3(grid), dim3(LANE_TPB), stream, q);
 	SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);
 	if (samples != nullptr) SIMLOD_LAUNCH(k_q_write, dim3(grid), dim3(LANE_TPB), stream, q);
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+uint64_t footprint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return query_min_bytes(nodeCapacity, sampleBound) + FOOT_BLOCK_BYTES; }
+
+// simlod_query_footprint with a footprint (without one the entry point forwards to launch_query): the polygon, widened to fp64 edges, goes into
+// the scratch buffer's block in front of the items by a copy on `stream`; then the region query's sequence with k_f_hier / k_f_count / k_f_write.
+int launch_footprint(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
+                     const SimlodFootprint* fp, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
+                     uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
+	if (fp == nullptr || fp->numVertices < 3u || fp->numVertices > SIMLOD_FOOTPRINT_MAX_VERTICES) return (int)hipErrorInvalidValue;
+	if (fp->reserved[0] != 0u || fp->reserved[1] != 0u || fp->reserved[2] != 0u) return (int)hipErrorInvalidValue;
+	FootArgs fa{};
+	const uint32_t n = fp->numVertices;
+	for (int k = 0; k < 4; k++) {
+		if (!std::isfinite(fp->axisU[k]) || !std::isfinite(fp->axisV[k])) return (int)hipErrorInvalidValue;
+		fa.f.axU[k] = (double)fp->axisU[k]; fa.f.axV[k] = (double)fp->axisV[k];
+	}
+	FootEdge edges[SIMLOD_FOOTPRINT_MAX_VERTICES];
+	for (uint32_t i = 0; i < n; i++) {
+		if (!std::isfinite(fp->vertices[i][0]) || !std::isfinite(fp->vertices[i][1])) return (int)hipErrorInvalidValue;
+		const uint32_t j = i + 1u == n ? 0u : i + 1u;
+		const double au = (double)fp->vertices[i][0], av = (double)fp->vertices[i][1];
+		edges[i] = FootEdge{au, av, (double)fp->vertices[j][0] - au, (double)fp->vertices[j][1] - av};
+	}
+	const int rc = prepare_query(ctx, nodes, stats, u, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples, sampleCapacity, counts,
+	                             FOOT_BLOCK_BYTES, fa.q);
+	if (rc != 0) return rc;
+	fa.f.n = n;
+	fa.f.edges = fa.q.x.lay.items - FOOT_BLOCK_BYTES;
+	// (pageable host memory: the runtime has read `edges` when the call returns)
+	const hipError_t e = hipMemcpyAsync(fa.q.x.scratch + fa.f.edges, edges, (size_t)n * sizeof(FootEdge), hipMemcpyHostToDevice, stream);
+	if (e != hipSuccess) return (int)e;
+	const uint32_t grid = copy_grid(fa.q.x.lay.itemCap);
+	SIMLOD_LAUNCH(k_f_hier, dim3(1), dim3(WG_TPB), stream, fa);
+	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                        // k_q_dir: one wave per table entry
+	if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, fa.q);
+	SIMLOD_LAUNCH(k_f_count, dim3(grid), dim3(LANE_TPB), stream, fa);
+	SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, fa.q);
+	if (samples != nullptr) SIMLOD_LAUNCH(k_f_write, dim3(grid), dim3(LANE_TPB), stream, fa);
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();
 }

@@ -1,5 +1,5 @@
-// export_region.inc — part of export.hip: region queries.  QueryGeom, classify, QItem, QueryLayout, QueryArgs, k_q_hier, k_q_dir, passes,
-// k_q_count, k_q_scan, k_q_write.
+// export_region.inc — part of export.hip: region queries.  QueryGeom, classify, QItem, QueryLayout, QueryArgs, query_totals, k_q_hier, k_q_dir,
+// passes, q_count, k_q_count, k_q_scan, q_write, k_q_write.
 // ---- region query ---------------------------------------------------------------------------------------------------------------------
 // simlod_query_region (simlod_hip.h, "region queries"): five launches on the caller's stream.
 //   k_q_hier   ONE workgroup: k_x_hier's walk with the classification (children outside the region are not listed; every listed entry gets its
@@ -62,12 +62,9 @@ struct QueryArgs {
 	SimlodQueryCounts* counts;
 };
 
-__global__ __launch_bounds__(WG_TPB) void k_q_hier(QueryArgs q) {
-	__shared__ uint64_t sh_scan[WG_WAVES];
-	const ExportArgs& a = q.x;
-	uint32_t* cls = reinterpret_cast<uint32_t*>(a.scratch + q.cls);
-	hier_walk<true>(a, [&](uint32_t level, uint32_t X, uint32_t Y, uint32_t Z) { return classify(q.g, level, X, Y, Z); }, cls);
-	__syncthreads();
+// The scans behind a query's walk (ONE workgroup; k_q_hier, k_f_hier): the chunks per node (-> the node's first item) and the totals before the
+// test.  `sh_scan`: WG_WAVES words.
+__device__ __forceinline__ void query_totals(const ExportArgs& a, const uint32_t* cls, uint64_t* sh_scan) {
 	Header* hdr = reinterpret_cast<Header*>(a.scratch);
 	uint32_t* first = reinterpret_cast<uint32_t*>(a.scratch + a.lay.first);
 	const uint32_t n = hdr->numListed;
@@ -96,6 +93,15 @@ __global__ __launch_bounds__(WG_TPB) void k_q_hier(QueryArgs q) {
 		hdr->counts[0] = (uint32_t)nFiltered; hdr->counts[1] = (uint32_t)nCopied;
 		hdr->counts[2] = (uint32_t)cand; hdr->counts[3] = (uint32_t)(cand >> 32);
 	}
+}
+
+__global__ __launch_bounds__(WG_TPB) void k_q_hier(QueryArgs q) {
+	__shared__ uint64_t sh_scan[WG_WAVES];
+	const ExportArgs& a = q.x;
+	uint32_t* cls = reinterpret_cast<uint32_t*>(a.scratch + q.cls);
+	hier_walk<true>(a, [&](uint32_t level, uint32_t X, uint32_t Y, uint32_t Z) { return classify(q.g, level, X, Y, Z); }, cls);
+	__syncthreads();
+	query_totals(a, cls, sh_scan);
 }
 
 // One WAVE per table entry: while the builder's table is valid lane k looks chunk k up (a row holds at most 50, LEAF_ROW_SLOTS), all at once;
@@ -158,7 +164,18 @@ __device__ __forceinline__ bool passes(const QueryGeom& g, const u32x4& v) {
 	return ok;
 }
 
-__global__ __launch_bounds__(LANE_TPB) void k_q_count(QueryArgs q) {
+// The bodies of k_q_count and k_q_write take their kernel's argument block WHOLE, as `Args` says — `const QueryArgs&`, `const QueryArgs` or
+// `const FootArgs&`, whichever leaves the kernel as it was (DESIGN §11: q_write by value keeps k_q_write's code, q_count by reference keeps
+// k_q_count's registers; a member of a larger block handed on by value would be copied, and the planes' dynamic index puts such a copy into
+// scratch memory).  query_of(args): the QueryArgs in it.
+__device__ __forceinline__ const QueryArgs& query_of(const QueryArgs& q) { return q; }
+// (the plane-only query: no footprint to ask — k_f_count / k_f_write, export_footprint.inc, bring theirs)
+struct NoFootprint { __device__ __forceinline__ bool operator()(const u32x4&) const { return true; } };
+
+// k_q_count's body; extra(v): what a sample has to pass on top of the planes (rule F1 of a footprint query)
+template <typename Args, typename Extra>
+__device__ __forceinline__ void q_count(Args args, Extra extra) {
+	const QueryArgs& q = query_of(args);
 	__shared__ uint32_t sh_cnt[2][LANE_TPB / SIMLOD_WAVE];
 	const Header* hdr = reinterpret_cast<const Header*>(q.x.scratch);
 	if (hdr->counts[0] == 0u) return;                                      // no filtered node
@@ -176,7 +193,7 @@ __global__ __launch_bounds__(LANE_TPB) void k_q_count(QueryArgs q) {
 #pragma unroll
 		for (int j = 0; j < 4; j++) {
 			const uint32_t k = threadIdx.x + (uint32_t)j * LANE_TPB;
-			c += (uint32_t)__popcll(__ballot(k < cnt && passes(q.g, v[j])));
+			c += (uint32_t)__popcll(__ballot(k < cnt && passes(q.g, v[j]) && extra(v[j])));
 		}
 		if (lane == 0) sh_cnt[turn][w] = c;
 		__syncthreads();                    // (two buffers: the next turn's writes cannot overtake this turn's read)
@@ -184,6 +201,7 @@ __global__ __launch_bounds__(LANE_TPB) void k_q_count(QueryArgs q) {
 		turn ^= 1u;
 	}
 }
+__global__ __launch_bounds__(LANE_TPB) void k_q_count(QueryArgs q) { q_count<const QueryArgs&>(q, NoFootprint()); }
 static_assert(LANE_TPB / SIMLOD_WAVE == 4, "k_q_count / k_q_write: four waves");
 
 __global__ __launch_bounds__(WG_TPB) void k_q_scan(QueryArgs q) {
@@ -232,7 +250,10 @@ __global__ __launch_bounds__(WG_TPB) void k_q_scan(QueryArgs q) {
 	}
 }
 
-__global__ __launch_bounds__(LANE_TPB) void k_q_write(QueryArgs q) {
+// k_q_write's body; extra(v) as in q_count
+template <typename Args, typename Extra>
+__device__ __forceinline__ void q_write(Args args, Extra extra) {
+	const QueryArgs& q = query_of(args);
 	__shared__ uint32_t sh_seg[2][16];
 	const ExportArgs& a = q.x;
 	const Header* hdr = reinterpret_cast<const Header*>(a.scratch);
@@ -254,7 +275,7 @@ __global__ __launch_bounds__(LANE_TPB) void k_q_write(QueryArgs q) {
 #pragma unroll
 		for (int j = 0; j < 4; j++) {
 			const uint32_t k = threadIdx.x + (uint32_t)j * LANE_TPB;
-			b[j] = __ballot(k < it.count && passes(q.g, v[j]));
+			b[j] = __ballot(k < it.count && passes(q.g, v[j]) && extra(v[j]));
 			if (lane == 0) sh_seg[turn][j * 4 + w] = (uint32_t)__popcll(b[j]);
 		}
 		__syncthreads();                    // (two buffers, as in k_q_count)
@@ -272,3 +293,4 @@ __global__ __launch_bounds__(LANE_TPB) void k_q_write(QueryArgs q) {
 		turn ^= 1u;
 	}
 }
+__global__ __launch_bounds__(LANE_TPB) void k_q_write(QueryArgs q) { q_write<const QueryArgs>(q, NoFootprint()); }

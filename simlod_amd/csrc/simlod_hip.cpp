@@ -451,6 +451,19 @@ int simlod_query_region(const SimlodNode* nodes, const SimlodStats* stats, const
 	                    sampleCapacity, counts, (hipStream_t)stream);
 }
 
+uint64_t simlod_footprint_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return footprint_min_bytes(nodeCapacity, sampleBound); }
+
+int simlod_query_footprint(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                           const SimlodFootprint* footprint, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                           SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts,
+                           void* stream) {
+	if (footprint == nullptr)                                                   // rule F6: exactly simlod_query_region
+		return launch_query(context_of(nodes), nodes, stats, uniforms, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples,
+		                    sampleCapacity, counts, (hipStream_t)stream);
+	return launch_footprint(context_of(nodes), nodes, stats, uniforms, region, footprint, maxLevel, select, scratch, scratchBytes, table, tableCapacity,
+	                        samples, sampleCapacity, counts, (hipStream_t)stream);
+}
+
 uint64_t simlod_rays_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates) {
 	return rays_min_bytes(nodeCapacity, sampleBound, numRays, numPairs, numCandidates);
 }

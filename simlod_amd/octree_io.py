@@ -21,6 +21,9 @@ File format (little-endian throughout):
 Region queries (include/simlod_hip.h, "region queries"): `Region` holds the half-spaces, and `OctreeExport.crop` is the host mirror of
 simlod_query_region — every rule restated in numpy float64, which reproduces the device's fp64 arithmetic bit for bit.
 
+Footprint queries (include/simlod_hip.h, "footprint queries"): `Footprint` holds the polygon and the affine map into its plane,
+`OctreeExport.crop(region, footprint=...)` is the host mirror of simlod_query_footprint, in the same float64 operation order.
+
 Ray queries (include/simlod_hip.h, "ray queries"): `Rays` holds a batch of SimlodRay records, `OctreeExport.cast` (on a full export) and
 `OctreeExport.cast_selected` (on any export) are the host mirror of simlod_query_rays, in the same float64 operation order.
 
@@ -116,9 +119,11 @@ class OctreeExport:
             return False
         return True
 
-    def crop(self, region, max_level=None, select="all", return_counts=False):
+    def crop(self, region, max_level=None, select="all", return_counts=False, footprint=None):
         """The host mirror of simlod_query_region: what the device returns for `region` on the octree this FULL export (select "all", max level
-        20; anything else ValueError) was taken from, as an OctreeExport on the host — and, return_counts, the SimlodQueryCounts record too."""
+        20; anything else ValueError) was taken from, as an OctreeExport on the host — and, return_counts, the SimlodQueryCounts record too.
+        footprint (a Footprint): the mirror of simlod_query_footprint — rules F1-F4 on top of the planes; rule F5's promise is asserted for
+        every copied and every outside node."""
         if self.select != abi.EXPORT_ALL or self.max_level < abi.MAX_DEPTH:
             raise ValueError(f"crop needs a full export (select all, max level 20), not select {self.select} / max level {self.max_level}")
         sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
@@ -129,6 +134,10 @@ class OctreeExport:
         pl = np.asarray(region.planes, dtype=np.float32).astype(np.float64)
         mn, size = _box_of(self.box_min, self.box_max)
         outside, inside = classify_nodes(pl, src, self.box_min, self.box_max)
+        if footprint is not None:
+            # rule F4: outside by either, copied iff copied by both
+            near, corner = classify_footprint(footprint, src, self.box_min, self.box_max)
+            outside, inside = outside | (~near & ~corner), inside & ~near & corner
         # the breadth-first walk over the listed nodes
         order, parent, masks, firsts = [0], [abi.EXPORT_NONE], [], []
         t = 0
@@ -164,6 +173,11 @@ class OctreeExport:
             for nx, ny, nz, d in pl:
                 ok &= ((nx * x + ny * y) + nz * z) + d >= 0
             inbox = (x >= mn[0]) & (x < mn[0] + size) & (y >= mn[1]) & (y < mn[1] + size) & (z >= mn[2]) & (z < mn[2] + size)
+        if footprint is not None:
+            ok &= footprint.contains(smp)
+            # rule F5 for every outside node of the source, listed or not: none of its samples of the contract passes (the copied ones below)
+            bad = ok & inbox & np.repeat(outside, src["numSamples"].astype(np.int64))
+            assert not bad.any(), f"node {int(np.repeat(np.arange(len(src)), src['numSamples'].astype(np.int64))[bad][0])} is outside and holds a sample of the box that passes the test"
         parts, ns_out = [], np.zeros(len(out), np.int64)
         n_filtered = n_copied = 0
         for t in np.nonzero(cand)[0]:
@@ -490,6 +504,98 @@ class Region:
         r["numPlanes"] = len(self.planes)
         r["planes"][0, : len(self.planes)] = self.planes
         return r
+
+
+class Footprint:
+    """An extruded polygon (include/simlod_hip.h, "footprint queries"): 3 .. 256 vertices (u, v) as float32, closed from the last to the first,
+    in the plane a point is mapped into by u = ((ux*x + uy*y) + uz*z) + u0 and v likewise (axis_u, axis_v as float32).  Inside is the even-odd
+    rule F1, so the polygon may be non-convex or cross itself."""
+
+    def __init__(self, vertices, axis_u=(1, 0, 0, 0), axis_v=(0, 1, 0, 0)):
+        v = np.asarray(vertices, dtype=np.float64).reshape(-1, 2)
+        if not 3 <= len(v) <= abi.FOOTPRINT_MAX_VERTICES:
+            raise ValueError(f"{len(v)} vertices: a footprint has 3 .. {abi.FOOTPRINT_MAX_VERTICES}")
+        with np.errstate(over="ignore"):
+            self.vertices = v.astype(np.float32)
+            self.axis_u = np.asarray(axis_u, dtype=np.float64).reshape(4).astype(np.float32)
+            self.axis_v = np.asarray(axis_v, dtype=np.float64).reshape(4).astype(np.float32)
+        if not (np.isfinite(self.vertices).all() and np.isfinite(self.axis_u).all() and np.isfinite(self.axis_v).all()):
+            raise ValueError("a vertex or an axis coefficient is not finite (as float32)")
+
+    @classmethod
+    def from_xy(cls, polygon):
+        """A plan-view outline: u = x, v = y, extruded along z."""
+        return cls(polygon)
+
+    @classmethod
+    def from_rect(cls, lo, hi):
+        """The plan-view rectangle from (lo_x, lo_y) to (hi_x, hi_y), clockwise from lo.  By rule F1 as the header states it a point on an
+        edge that runs towards smaller v counts as left of it, so this orientation gives lo_x <= x <= hi_x and lo_y <= y < hi_y."""
+        lo, hi = np.asarray(lo, np.float64).reshape(-1), np.asarray(hi, np.float64).reshape(-1)
+        return cls([(lo[0], lo[1]), (lo[0], hi[1]), (hi[0], hi[1]), (hi[0], lo[1])])
+
+    def __len__(self):
+        return len(self.vertices)
+
+    def record(self):
+        """The SimlodFootprint the C ABI takes (abi.footprint_dtype, one record)."""
+        r = np.zeros(1, dtype=abi.footprint_dtype)
+        r["numVertices"] = len(self.vertices)
+        r["axisU"], r["axisV"] = self.axis_u, self.axis_v
+        r["vertices"][0, : len(self.vertices)] = self.vertices
+        return r
+
+    def edges(self):
+        """(a_u, a_v, b_v, du, dv) per edge as float64 arrays: the edge from a = P[i] to b = P[(i + 1) mod n]."""
+        a = self.vertices.astype(np.float64)
+        b = np.roll(a, -1, axis=0)
+        return a[:, 0], a[:, 1], b[:, 1], b[:, 0] - a[:, 0], b[:, 1] - a[:, 1]
+
+    def project(self, x, y, z):
+        """(u, v) of float64 coordinates, in the header's operation order."""
+        au, av = self.axis_u.astype(np.float64), self.axis_v.astype(np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            return ((au[0] * x + au[1] * y) + au[2] * z) + au[3], ((av[0] * x + av[1] * y) + av[2] * z) + av[3]
+
+    def contains_uv(self, u, v):
+        """Rule F1 at float64 (u, v): the number of crossed edges is odd."""
+        odd = np.zeros(np.shape(u), bool)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for a_u, a_v, b_v, du, dv in zip(*self.edges()):
+                c = du * (v - a_v) - dv * (u - a_u)
+                odd ^= ((a_v > v) != (b_v > v)) & ((c > 0) == (dv > 0))
+        return odd
+
+    def contains(self, points):
+        """Rule F1 on point records (abi.point_dtype) -> a boolean per point."""
+        p = np.asarray(points)
+        return self.contains_uv(*self.project(*(p[a].astype(np.float64) for a in ("x", "y", "z"))))
+
+
+def classify_footprint(footprint, nodes, box_min, box_max):
+    """Rules F2-F4 of the footprint query for every entry of a table: (near, corner) as boolean arrays — whether the node's projected rectangle
+    has a NEAR edge (the node is filtered), and rule F1's verdict at (U_lo, V_lo) (without a NEAR edge: copied if it passes, else outside)."""
+    mn, size = _box_of(box_min, box_max)
+    s = np.ldexp(size, -nodes["level"].astype(np.int64))[:, None]
+    e = np.ldexp(size, -abi.MAX_DEPTH)
+    A = np.stack([nodes["X"], nodes["Y"], nodes["Z"]], axis=1).astype(np.float64)
+    lo, hi = (mn + A * s) - e, (mn + (A + 1.0) * s) + e
+
+    def span(ax):
+        ax = ax.astype(np.float64)
+        f = [(lo if ax[k] >= 0 else hi)[:, k] for k in range(3)]
+        g = [(hi if ax[k] >= 0 else lo)[:, k] for k in range(3)]
+        return ((ax[0] * f[0] + ax[1] * f[1]) + ax[2] * f[2]) + ax[3], ((ax[0] * g[0] + ax[1] * g[1]) + ax[2] * g[2]) + ax[3]
+
+    (Ulo, Uhi), (Vlo, Vhi) = span(footprint.axis_u), span(footprint.axis_v)
+    near, corner = np.zeros(len(nodes), bool), np.zeros(len(nodes), bool)
+    for a_u, a_v, b_v, du, dv in zip(*footprint.edges()):
+        pl, ph, ql, qh = du * (Vlo - a_v), du * (Vhi - a_v), dv * (Ulo - a_u), dv * (Uhi - a_u)
+        c00, c01, c10, c11 = pl - ql, ph - ql, pl - qh, ph - qh
+        far = (max(a_v, b_v) < Vlo) | (min(a_v, b_v) > Vhi) | ((c00 > 0) & (c01 > 0) & (c10 > 0) & (c11 > 0)) | ((c00 < 0) & (c01 < 0) & (c10 < 0) & (c11 < 0))
+        near |= ~far
+        corner ^= ((a_v > Vlo) != (b_v > Vlo)) & ((c00 > 0) == (dv > 0))
+    return near, corner
 
 
 def _slab(lo, hi, o, d, tmin, tmax, R):

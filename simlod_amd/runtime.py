@@ -91,6 +91,9 @@ def lib():
         L.simlod_query_buffer_min_bytes.restype = u64
         L.simlod_query_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_query_region.argtypes = [vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
+        L.simlod_footprint_buffer_min_bytes.restype = u64
+        L.simlod_footprint_buffer_min_bytes.argtypes = [u32, u64]
+        L.simlod_query_footprint.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
         L.simlod_rays_buffer_min_bytes.restype = u64
         L.simlod_rays_buffer_min_bytes.argtypes = [u32, u64, u32, u64, u64]
         L.simlod_query_rays.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, u64, vp, u32, vp, vp, vp]
@@ -114,7 +117,7 @@ EXPORTED_SYMBOLS = [
     "simlod_profile_enable", "simlod_profile_collect", "simlod_generate_terrain", "simlod_generate_terrain_scan", "simlod_launch_colorfilter", "simlod_colorfilter_buffer_min_bytes",
     "simlod_export_buffer_min_bytes", "simlod_export_octree", "simlod_import_octree", "simlod_import_octree_buildable",
     "simlod_query_buffer_min_bytes", "simlod_query_region", "simlod_rays_buffer_min_bytes", "simlod_query_rays",
-    "simlod_neighbours_buffer_min_bytes", "simlod_query_neighbours",
+    "simlod_neighbours_buffer_min_bytes", "simlod_query_neighbours", "simlod_footprint_buffer_min_bytes", "simlod_query_footprint",
 ]
 
 
@@ -619,19 +622,29 @@ class DeviceOctree:
                             u["boxMin"], u["boxMax"], ml, sel)
 
     # -- region queries (include/simlod_hip.h, "region queries") ---------------------------------------------------------------------------
-    def _query(self, uniforms, region, ml, sel, table, samples, sample_capacity, bound):
-        """One simlod_query_region call -> the SimlodQueryCounts record (host).  samples None: count only."""
+    def _query(self, uniforms, region, ml, sel, table, samples, sample_capacity, bound, footprint=None):
+        """One simlod_query_region call — with a footprint (an octree_io.Footprint) one simlod_query_footprint call — -> the SimlodQueryCounts
+        record (host).  samples None: count only."""
         u, up = self._u(uniforms)
         r = region.record()
         nn = table.numel() // abi.export_node_dtype.itemsize
-        scratch = self._export_scratch(int(self.L.simlod_query_buffer_min_bytes(nn, bound)))
         counts = torch.zeros(abi.query_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
-        _check(self.L.simlod_query_region(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data), ml, sel, self._p(scratch),
-                                          ctypes.c_uint64(scratch.numel()), self._p(table), nn, None if samples is None else self._p(samples),
-                                          ctypes.c_uint64(sample_capacity), self._p(counts), self._stream()), "simlod_query_region")
+        tail = (self._p(table), nn, None if samples is None else self._p(samples), ctypes.c_uint64(sample_capacity), self._p(counts), self._stream())
+        if footprint is None:
+            what = "simlod_query_region"
+            scratch = self._export_scratch(int(self.L.simlod_query_buffer_min_bytes(nn, bound)))
+            rc = self.L.simlod_query_region(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data), ml, sel, self._p(scratch),
+                                            ctypes.c_uint64(scratch.numel()), *tail)
+        else:
+            what = "simlod_query_footprint"
+            f = footprint.record()
+            scratch = self._export_scratch(int(self.L.simlod_footprint_buffer_min_bytes(nn, bound)))
+            rc = self.L.simlod_query_footprint(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data), ctypes.c_void_p(f.ctypes.data),
+                                               ml, sel, self._p(scratch), ctypes.c_uint64(scratch.numel()), *tail)
+        _check(rc, what)
         c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
         if int(c["error"]) != 0:
-            raise SimlodError(f"simlod_query_region reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples)")
+            raise SimlodError(f"{what} reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples)")
         return c
 
     def _query_setup(self, max_level, select):
@@ -643,23 +656,25 @@ class DeviceOctree:
     def _table(self, nn):
         return torch.empty(max(nn, 1) * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
 
-    def count_region(self, uniforms, region, max_level=None, select="cut"):
+    def count_region(self, uniforms, region, max_level=None, select="cut", footprint=None):
         """How much of the octree lies in `region` (an octree_io.Region) at `max_level`: the SimlodQueryCounts record of a count-only
-        simlod_query_region call (numNodes, numSamples, numCandidates, numFilteredNodes, numCopiedNodes).  No sample is written."""
+        simlod_query_region call (numNodes, numSamples, numCandidates, numFilteredNodes, numCopiedNodes).  No sample is written.
+        footprint (an octree_io.Footprint): inside that extruded polygon as well, by simlod_query_footprint."""
         sel, ml, nn, bound = self._query_setup(max_level, select)
-        return self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound)
+        return self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound, footprint)
 
-    def query_region(self, uniforms, region, max_level=None, select="cut", return_counts=False):
+    def query_region(self, uniforms, region, max_level=None, select="cut", return_counts=False, footprint=None):
         """The samples inside `region` as an octree_io.OctreeExport on this device (select abi.EXPORT_REGION): the pruned table and, in chunk-list
         order, the samples of the selected nodes ("cut": source leaves and the nodes at max_level; "all": every listed node) that pass the
-        region's test.  A count-only call first, then the outputs sized exactly.  Raises SimlodError when the device reports an error."""
+        region's test.  A count-only call first, then the outputs sized exactly.  Raises SimlodError when the device reports an error.
+        footprint (an octree_io.Footprint): the samples that are inside that extruded polygon as well, by simlod_query_footprint."""
         from .octree_io import OctreeExport
         sel, ml, nn, bound = self._query_setup(max_level, select)
-        c = self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound)
+        c = self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound, footprint)
         nn, ns = int(c["numNodes"]), int(c["numSamples"])
         table = torch.empty(nn * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
         samples = torch.empty(max(ns, 1) * abi.point_dtype.itemsize, dtype=torch.uint8, device=self.device)
-        c = self._query(uniforms, region, ml, sel, table, samples, ns, bound)
+        c = self._query(uniforms, region, ml, sel, table, samples, ns, bound, footprint)
         u = np.asarray(uniforms).reshape(-1)[0]
         ex = OctreeExport(table, samples[: int(c["numSamples"]) * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_REGION)
         return (ex, c) if return_counts else ex

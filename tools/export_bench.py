@@ -10,7 +10,11 @@ query of a thin box around the same ray, the two alternating rep by rep; 4 096 v
 and the distinct chunk bytes of the paired nodes — and the device-to-device copy, all in this one run.
 --neighbours: instead, simlod_query_neighbours CUT@20 on the same octree — 4 096 queries at random input points, at a radius for which the
 host mirror's median `within` (on the first 256 of them) is about 30, with k = 1, 8 and 16 and the count-only call alone — and, for scale, the
---rays case of 4 096 vertical rays and the device-to-device copy, all in this one run."""
+--rays case of 4 096 vertical rays and the device-to-device copy, all in this one run.
+--footprint: instead, simlod_query_footprint CUT@20 on the same octree — half the terrain (a triangle scaled so that about half the points
+pass) with its count-only call; the rectangle of 30-70 % x 20-90 % of the extents beside the same rectangle as a four-plane
+simlod_query_region, the two alternating rep by rep; the count-only calls of a 14-vertex and a 256-vertex star, alternating — and the
+device-to-device copy, all in this one run."""
 import argparse
 import ctypes
 import json
@@ -132,6 +136,100 @@ def region_bench(dev, u, box, st, reps):
     t_block, t_block_count = timed_alternating([lambda: query("city_block"), lambda: query("city_block", True)], reps)
     out["city_block"] = row("city_block", t_block)
     out["city_block"]["count_only_ms"] = round(t_block_count[0], 4)
+    print(json.dumps(out))
+
+
+def footprint_bench(dev, u, box, st, reps):
+    from simlod_amd import fingerprint
+    from simlod_amd.octree_io import Footprint, Region, classify_footprint
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    need = int(L.simlod_footprint_buffer_min_bytes(nn, bound))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    table = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    samples = torch.empty(bound * 16, dtype=torch.uint8, device=dev.device)
+    counts = torch.zeros(32, dtype=torch.uint8, device=dev.device)
+    uu, up = dev._u(u)
+    b = np.asarray(box, dtype=np.float64)
+
+    def star(n):
+        k = np.arange(2 * n)
+        r = np.where(k % 2 == 0, 0.45, 0.15) * min(b[0], b[1])
+        return Footprint.from_xy(np.stack([b[0] / 2 + r * np.cos(k * np.pi / n), b[1] / 2 + r * np.sin(k * np.pi / n)], axis=1))
+
+    tri = 0.5 + (np.array([(50 / 600, 50 / 400), (550 / 600, 80 / 400), (250 / 600, 380 / 400)]) - 0.5) * 1.25
+    rect_lo, rect_hi = (0.3 * b[0], 0.2 * b[1]), (0.7 * b[0], 0.9 * b[1])
+    prints = {"half_terrain": Footprint.from_xy(tri * b[:2]), "rect": Footprint.from_rect(rect_lo, rect_hi), "star7": star(7), "star128": star(128)}
+    records = {k: f.record() for k, f in prints.items()}
+    none = Region().record()
+    planes = Region.from_box((*rect_lo, -1.0), (*rect_hi, b[2] + 1.0)).record()
+    planes["numPlanes"] = 4                                                      # the x and y planes: the rectangle alone
+
+    def query(kind, count_only=False):
+        rc = L.simlod_query_footprint(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(none.ctypes.data), ctypes.c_void_p(records[kind].ctypes.data), 20,
+                                      abi.EXPORT_CUT, p(scratch), ctypes.c_uint64(need), p(table), nn, None if count_only else p(samples),
+                                      ctypes.c_uint64(bound), p(counts), stream)
+        assert rc == 0
+
+    def region_rect():
+        rc = L.simlod_query_region(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(planes.ctypes.data), 20, abi.EXPORT_CUT, p(scratch),
+                                   ctypes.c_uint64(need), p(table), nn, p(samples), ctypes.c_uint64(bound), p(counts), stream)
+        assert rc == 0
+
+    def read_counts():
+        torch.cuda.synchronize()
+        c = counts.cpu().numpy().view(abi.query_counts_dtype)[0].copy()
+        assert int(c["error"]) == 0
+        return c
+
+    copy_dst = torch.empty(int(st["numPoints"]) * 16, dtype=torch.uint8, device=dev.device)
+    copy_src = samples[: copy_dst.numel()]
+    t_copy = timed(lambda: copy_dst.copy_(copy_src), reps)
+    copy_gbs = 2 * copy_dst.numel() / (t_copy[0] * 1e6)
+    out = {"points": int(st["numPoints"]), "numNodes": nn, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(),
+           "d2d_copy": {"ms": round(t_copy[0], 4), "bytes": 2 * copy_dst.numel(), "GBs": round(copy_gbs, 1)}}
+
+    def row(kind, ms, c):
+        nbytes = int(c["numCandidates"]) * 16 + int(c["numSamples"]) * 16 + int(c["numNodes"]) * 40
+        gbs = nbytes / (ms[0] * 1e6)
+        return {"ms": round(ms[0], 4), "ms_min": round(ms[1], 4), "vertices": len(prints[kind]) if kind in prints else 0, "nodes_listed": int(c["numNodes"]),
+                "nodes_copied": int(c["numCopiedNodes"]), "nodes_filtered": int(c["numFilteredNodes"]), "numCandidates": int(c["numCandidates"]),
+                "numSamples": int(c["numSamples"]), "algorithmic_bytes": nbytes, "GBs": round(gbs, 1), "frac_of_copy": round(gbs / copy_gbs, 4)}
+
+    def f_of(kind):
+        # the share of the candidates that lie in filtered nodes (the table holds the counts after the test: ask a covering query for those before it)
+        query(kind)
+        c = read_counts()
+        t = table[: int(c["numNodes"]) * 40].cpu().numpy().view(abi.export_node_dtype)
+        near, corner = classify_footprint(prints[kind], t, u["boxMin"], u["boxMax"])
+        rc = L.simlod_query_region(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(none.ctypes.data), 20, abi.EXPORT_CUT, p(scratch),
+                                   ctypes.c_uint64(need), p(table), nn, None, ctypes.c_uint64(0), p(counts), stream)
+        assert rc == 0
+        torch.cuda.synchronize()
+        full = table.cpu().numpy().view(abi.export_node_dtype)
+        key = lambda a: (a["level"].astype(np.uint64) << np.uint64(60)) | (a["X"].astype(np.uint64) << np.uint64(40)) | (a["Y"].astype(np.uint64) << np.uint64(20)) | a["Z"].astype(np.uint64)
+        before = dict(zip(key(full).tolist(), full["numSamples"].tolist()))
+        sel = (t["flags"] & abi.EXPORT_FLAG_SELECTED) != 0
+        cand = np.array([before[k] for k in key(t).tolist()], dtype=np.int64) * (sel & (near | corner))
+        assert int(cand.sum()) == int(c["numCandidates"])
+        return round(float(cand[near].sum()) / max(int(c["numCandidates"]), 1), 4), c
+
+    t_half, t_half_count = timed_alternating([lambda: query("half_terrain"), lambda: query("half_terrain", True)], reps)
+    f, c = f_of("half_terrain")
+    out["half_terrain"] = row("half_terrain", t_half, c)
+    out["half_terrain"].update({"count_only_ms": round(t_half_count[0], 4), "f_candidates_in_filtered_nodes": f, "target": ">= 50 % of the copy rate",
+                                "target_held": bool(out["half_terrain"]["frac_of_copy"] >= 0.5)})
+    t_rect, t_planes = timed_alternating([lambda: query("rect"), region_rect], reps)
+    f, c = f_of("rect")
+    out["rect"] = row("rect", t_rect, c)
+    out["rect"]["f_candidates_in_filtered_nodes"] = f
+    region_rect()
+    out["rect_as_four_planes"] = row("planes", t_planes, read_counts())
+    out["rect"]["over_four_planes"] = round(t_rect[0] / t_planes[0], 4)
+    t7, t128 = timed_alternating([lambda: query("star7", True), lambda: query("star128", True)], reps)
+    for kind, t in (("star7", t7), ("star128", t128)):
+        query(kind, True)
+        out[kind + "_count_only"] = row(kind, t, read_counts())
     print(json.dumps(out))
 
 
@@ -293,6 +391,7 @@ def main():
     ap.add_argument("--persistent-gb", type=int, default=16)
     ap.add_argument("--buildable", action="store_true", help="also time simlod_import_octree_buildable (grid rebuild included)")
     ap.add_argument("--region", action="store_true", help="time simlod_query_region (whole box, half the terrain, a city block) instead")
+    ap.add_argument("--footprint", action="store_true", help="time simlod_query_footprint (half the terrain, a rectangle beside its four planes, two stars) instead")
     ap.add_argument("--rays", action="store_true", help="time simlod_query_rays (one pixel cone, 4 096 vertical rays) instead")
     ap.add_argument("--neighbours", action="store_true", help="time simlod_query_neighbours (4 096 queries, k = 1, 8, 16, count-only) instead")
     args = ap.parse_args()
@@ -315,6 +414,8 @@ def main():
     nn, ns = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
     if args.region:
         return region_bench(dev, u, box, st, args.reps)
+    if args.footprint:
+        return footprint_bench(dev, u, box, st, args.reps)
     if args.rays:
         return rays_bench(dev, u, box, st, args.reps, T, 1920, 1080)
     if args.neighbours:
