@@ -427,6 +427,49 @@ int simlod_query_region(const SimlodNode* nodes, const SimlodStats* stats, const
                         uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
                         SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, void* stream);
 
+/* ---- clip regions: a frame that shows the inside of a region, cuts it away, or highlights it ---------------------------------------------
+ * A clip is a SimlodRegion, a mode and a colour, kept by the context and honoured by every frame entry point (simlod_launch_render,
+ * simlod_launch_render_part, simlod_render_frame_composed, simlod_render_frame_rccl).  Nothing is copied: the frame's own kernels decide per
+ * node and per sample.  It is read when a frame (or a part of one) is enqueued and travels as a kernel argument, so frames already enqueued
+ * keep theirs.  The setter does no device work.
+ *
+ * The box and all arithmetic are the region section's: min = uniforms.boxMin, size = the largest fp32 extent; fp64 from the fp32 inputs, no
+ * fused multiply-add, every sum in the order written there.
+ *  C1. A sample PASSES iff it passes region rule 3: ((nx*x + ny*y) + nz*z) + d >= 0 for every plane (a NaN fails).
+ *  C2. A node's class is OUTSIDE, COPIED or FILTERED exactly as region rules 1 and 4 say (the cube inflated by one level-20 cell), for
+ *      each node on its own from (level, X, Y, Z) — not through its parent.
+ *  C3. A clipped frame is the frame kernel_render draws, with the same uniforms, of the same octree image after this edit:
+ *          mode                        OUTSIDE node   COPIED node                        FILTERED node
+ *          SIMLOD_CLIP_INSIDE          emptied        as it is                           failing samples removed
+ *          SIMLOD_CLIP_OUTSIDE         as it is       emptied                            passing samples removed
+ *          SIMLOD_CLIP_HIGHLIGHT       as it is       every sample's colour := color     passing samples' colour := color
+ *      EMPTIED: numPoints = numVoxels = 0.  By render.cu:760-861 such a node is not visible: not listed, not drawn, no bounding-box lines,
+ *      not counted in Stats; Node.visible is written as 0 in the node array too, so SIMLOD_EXPORT_VISIBLE follows the clip.  Other nodes
+ *      decide as before (emission depends on the node's own flags and its parent's geometry only).
+ *      REMOVED: the sample draws nothing.  The node's counts stay: numVisiblePoints / numVisibleVoxels count whole nodes, as the reference
+ *      does for samples off screen.  Points and voxels are samples alike.
+ *  C4. Uniforms.colorByNode / colorByLOD win over HIGHLIGHT: with either set a HIGHLIGHT frame is the unclipped frame.
+ *  C5. Zero planes: every node with samples is COPIED — INSIDE is the unclipped frame, OUTSIDE a clear frame without a visible node.
+ *  C6. The clip is geometry of the world: it applies whether or not transform_updateBound differs from transform.
+ *  OUTSIDE THE CONTRACT, as in region rule 4: samples outside the half-open box, on its max faces, or non-finite. */
+#define SIMLOD_CLIP_OFF       0u
+#define SIMLOD_CLIP_INSIDE    1u
+#define SIMLOD_CLIP_OUTSIDE   2u       /* cut-away */
+#define SIMLOD_CLIP_HIGHLIGHT 3u
+typedef struct SimlodClip {            /* host memory, read before the call returns */
+	uint32_t     mode;                 /* SIMLOD_CLIP_* */
+	uint32_t     color;                /* HIGHLIGHT: the colour word (as Point.color) */
+	uint32_t     reserved[2];          /* 0 */
+	SimlodRegion region;
+} SimlodClip;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodClip) == 288, "Clip");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClip, region) == 16, "Clip.region");
+/* Sets the clip of `ctx` (NULL: the default context) for the frames enqueued from now on; clip == NULL or mode SIMLOD_CLIP_OFF: no clip.
+ * hipErrorInvalidValue, the context's clip left as it was: a mode above 3, numPlanes > 16, a non-finite coefficient, nonzero `reserved` in
+ * either struct. */
+int simlod_context_set_clip(SimlodContext* ctx, const SimlodClip* clip);
+int simlod_set_clip(const SimlodClip* clip);   /* the default context */
+
 /* ---- footprint queries: the samples inside an extruded polygon at a chosen level of detail ------------------------------------------------
  * simlod_query_footprint is simlod_query_region plus a footprint: a polygon of up to 256 vertices in a plane the points are mapped into by an
  * affine map, extruded along the map's null direction (a parcel, a building outline, a lasso drawn in an orthographic view).  The polygon need

@@ -138,6 +138,12 @@ query_counts_dtype = np.dtype({"names": ["numNodes", "error", "numSamples", "num
                                "formats": ["<u4", "<u4", "<u8", "<u8", "<u4", "<u4"], "offsets": [0, 4, 8, 16, 24, 28], "itemsize": 32})
 assert region_dtype.itemsize == 272 and query_counts_dtype.itemsize == 32
 
+# ---- clip regions (include/simlod_hip.h, "clip regions") --------------------------------------------------------------------------------
+CLIP_OFF, CLIP_INSIDE, CLIP_OUTSIDE, CLIP_HIGHLIGHT = 0, 1, 2, 3
+CLIP_MODES = {"off": CLIP_OFF, "inside": CLIP_INSIDE, "outside": CLIP_OUTSIDE, "highlight": CLIP_HIGHLIGHT}
+clip_dtype = np.dtype({"names": ["mode", "color", "reserved", "region"], "formats": ["<u4", "<u4", ("<u4", 2), region_dtype], "offsets": [0, 4, 8, 16], "itemsize": 288})
+assert clip_dtype.itemsize == 288 and clip_dtype.fields["region"][1] == 16
+
 # ---- footprint queries (include/simlod_hip.h, "footprint queries") ----------------------------------------------------------------------
 FOOTPRINT_MAX_VERTICES = 256
 footprint_dtype = np.dtype({"names": ["numVertices", "reserved", "axisU", "axisV", "vertices"],

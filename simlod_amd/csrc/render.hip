@@ -14,6 +14,8 @@
 //   RENDER_RESOLVE  HQS: r_resolve, then the lines (r_lines_emit, r_lines_raster) — unless the resolve is fused into r_output: a whole frame without
 //                   debug lines that has a colour buffer (SIMLOD_RASTER_FUSED_RESOLVE)
 //   RENDER_OUTPUT   r_output<fused>: always — Stats, EDL, the RGBA8 image
+// A frame whose context has a clip (simlod_context_set_clip) runs r_visible and r_draw<mode> WITH the clip as a second kernel argument: the same
+// definitions under the Clip policy (render_common.inc).  Every other kernel of the frame is the same.
 //
 // Arithmetic contract: projection = four fp32 dot products evaluated left to right, IEEE divide,
 // pixel coordinate in fp64 exactly as `int x = (ndc.x * 0.5 + 0.5) * width` does (render.cu:66-67), no FMA
@@ -25,13 +27,14 @@
 #include "simlod_hip.h"
 #include "simlod_internal.hpp"
 #include "render_layout.hpp"
+#include "clip_rules.hpp"
 #include <atomic>
 #include <chrono>
 
 namespace simlod {
 
 // The device code, pass by pass (textual parts of THIS translation unit; each names what it holds in its first line):
-#include "render_common.inc"    // RenderArgs, DrawItem, BinSeg, tile and bin constants, probe macros, dot_row, DPP wave sums, the clears, wait_frame_ready
+#include "render_common.inc"    // RenderArgs, DrawItem, BinSeg, tile and bin constants, probe macros, dot_row, DPP wave sums, the clears, wait_frame_ready, the clip policies
 #include "render_visible.inc"   // frustum_plane, node_geometry, visible_nodes, r_visible
 #include "render_draw.inc"      // DrawCtx, the hot table, draw_sample / draw_wave / draw_staged / draw_item, tile_clear / tile_flush, r_draw
 #include "render_bins.inc"      // bin_item (r_draw calls it: declared in render_draw.inc), r_overflow
@@ -139,24 +142,33 @@ int launch_render(Context& ctx, uint32_t* buffer, const SimlodUniforms* u, Simlo
 	// finish later (HQS frame 0.227 ms against 0.231 ms).
 	const uint32_t gridDraw = dev.numCUs * (uint32_t)ctx.tune(KNOB_DRAW_MULT, 1);
 	const bool whole = parts == RENDER_ALL;
+	// the context's clip, as it is now: copied once, widened on the host, handed to the kernels by value (frames already enqueued keep theirs).
+	// colorByNode / colorByLOD win over HIGHLIGHT: such a frame is the unclipped one.
+	const SimlodClip clip = clip_of(ctx);
+	const bool clipped = clip.mode != SIMLOD_CLIP_OFF && !(clip.mode == SIMLOD_CLIP_HIGHLIGHT && (a.colorByNode || a.colorByLOD));
+	const ClipArgs k = clipped ? clip_args(clip, a.cubeSize, a.minx, a.miny, a.minz) : ClipArgs{};
 	auto lines = [&]() {
 		if (!u->showBoundingBox) return;
 		SIMLOD_LAUNCH(r_lines_emit, dim3((SIMLOD_MAX_VISIBLE_NODES + TPB - 1) / TPB), dim3(TPB), stream, a, u->transformInv_updateBound);
 		SIMLOD_LAUNCH(r_lines_raster, dim3((LINE_VERTEX_CAP / 2 + TPB - 1) / TPB), dim3(TPB), stream, a);
 	};
 	if (parts & RENDER_FIRST) {
-		SIMLOD_LAUNCH(r_visible, dim3(gridNodes), dim3(TPB), stream, a);
+		if (clipped) SIMLOD_LAUNCH(r_visible, dim3(gridNodes), dim3(TPB), stream, a, k);
+		else SIMLOD_LAUNCH(r_visible, dim3(gridNodes), dim3(TPB), stream, a);
 		if (a.hqs) {
-			SIMLOD_LAUNCH(r_draw<MODE_DEPTH>, dim3(gridDraw), dim3(DTPB), stream, a);
+			if (clipped) SIMLOD_LAUNCH(r_draw<MODE_DEPTH>, dim3(gridDraw), dim3(DTPB), stream, a, k);
+			else SIMLOD_LAUNCH(r_draw<MODE_DEPTH>, dim3(gridDraw), dim3(DTPB), stream, a);
 			if (a.useBins) SIMLOD_LAUNCH(r_overflow<MODE_DEPTH>, dim3(a.lay.binTiles), dim3(OTPB), stream, a);
 		} else {
-			SIMLOD_LAUNCH(r_draw<MODE_MIN64>, dim3(gridDraw), dim3(DTPB), stream, a);
+			if (clipped) SIMLOD_LAUNCH(r_draw<MODE_MIN64>, dim3(gridDraw), dim3(DTPB), stream, a, k);
+			else SIMLOD_LAUNCH(r_draw<MODE_MIN64>, dim3(gridDraw), dim3(DTPB), stream, a);
 			if (a.useBins) SIMLOD_LAUNCH(r_overflow<MODE_MIN64>, dim3(a.lay.binTiles), dim3(OTPB), stream, a);
 			lines();
 		}
 	}
 	if (a.hqs && (parts & RENDER_COLOR)) {
-		SIMLOD_LAUNCH(r_draw<MODE_COLOR>, dim3(gridDraw), dim3(DTPB), stream, a);
+		if (clipped) SIMLOD_LAUNCH(r_draw<MODE_COLOR>, dim3(gridDraw), dim3(DTPB), stream, a, k);
+		else SIMLOD_LAUNCH(r_draw<MODE_COLOR>, dim3(gridDraw), dim3(DTPB), stream, a);
 		if (a.useBins) SIMLOD_LAUNCH(r_overflow<MODE_COLOR>, dim3(a.lay.binTiles), dim3(OTPB), stream, a);
 		if (!whole) SIMLOD_LAUNCH(r_unpack, dim3(gridPixels), dim3(TPB), stream, a);     // ranks all-reduce(SUM) the {R,G,B,count} plane
 	}

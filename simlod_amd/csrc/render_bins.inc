@@ -5,9 +5,9 @@
 // item and bin on it took 11 ns each, 200 us a frame) and lists one segment per bin with samples; then every sample writes its entry.
 // Value: depth | colour (plain frames), depth (HQS depth pass), colour of an ACCEPTED sample (HQS colour pass, render.cu:485-493).  Pool
 // exhausted: the item's samples take the device-scope atomics, as before; a bin's list full: that bin's.
-template <int MODE>
+template <int MODE, typename POLICY>
 __device__ __forceinline__ void bin_item(const DrawCtx& c, const RenderArgs& a, uint32_t* lds, const SimlodChunk* const* dir, uint32_t count, uint32_t overrideColor, bool useOverride,
-                                         uint32_t& outside) {
+                                         uint32_t& outside, const POLICY& clip) {
 	// (opaque to the optimiser: what depends on the thread only — chunk and offset of each of its 16 samples, the addresses of its bins' words —
 	// was hoisted out of r_draw's item loop and occupied 40 registers for the whole kernel: every draw path spilled)
 	uint32_t tid = threadIdx.x;
@@ -34,6 +34,7 @@ __device__ __forceinline__ void bin_item(const DrawCtx& c, const RenderArgs& a, 
 			have[u] = sIdx < count;
 			p[u] = have[u] ? reinterpret_cast<const float4*>(dir[sIdx / SIMLOD_POINTS_PER_CHUNK]->points)[sIdx % SIMLOD_POINTS_PER_CHUNK] : make_float4(0, 0, 0, 0);
 		}
+		clip.test(p, have);                                                 // (before a sample becomes a bin entry)
 		uint32_t pixel[DU];
 		float depth[DU];
 		bool valid[DU];

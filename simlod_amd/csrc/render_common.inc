@@ -1,5 +1,6 @@
 // render_common.inc — what every pass of the rasteriser shares: RenderArgs, DrawItem, BinSeg, the tile and bin constants, the probe macros, dot_row, the DPP
-// wave sums, and the clears with the frame-ready handshake (clear_frame, clear_colour_planes, clear_counters, wait_frame_ready).
+// wave sums, the clears with the frame-ready handshake (clear_frame, clear_colour_planes, clear_counters, wait_frame_ready), and the clip policies
+// (NoClip, Clip, ClipStore).
 static constexpr uint32_t TPB = 256;
 
 struct RenderArgs {
@@ -140,3 +141,52 @@ __device__ __forceinline__ void clear_counters(const RenderArgs& a) {     // one
 	lines[0] = 0;                                                      // lines->count = 0, render.cu:1118
 	__hip_atomic_store(frame_ready_word(a.mom, a.lay), a.launchSeq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
+
+// ---- the frame's clip (include/simlod_hip.h, "clip regions"; clip_rules.hpp) ------------------------------------------------------------------
+// r_visible, r_draw and what they call take a policy.  NoClip: nothing — the instantiations of a frame without a clip are what they were before
+// there was one.  Clip: the kernel's second argument (the box, the mode, the colour) and the planes, which the workgroup stages in LDS once
+// (512 bytes): a node's class is computed from (level, X, Y, Z) where it is needed — by r_visible's lane for its node, by r_draw once per item from
+// the item's visible record, every lane the same — and the per-sample test sits right behind the sample load, one plane at a time.
+struct NoClip {
+	static constexpr bool ON = false;
+	__device__ __forceinline__ bool empties(uint32_t, uint32_t, uint32_t, uint32_t) const { return false; }
+	template <uint32_t DU> __device__ __forceinline__ void test(float4 (&)[DU], bool (&)[DU]) const {}
+};
+struct Clip {
+	static constexpr bool ON = true;
+	const ClipArgs& k;                   // (the scalars are read from the kernel's argument block where they are used)
+	const double (*pl)[4];               // LDS
+	uint32_t action;                     // r_draw: CLIP_ACT_* of the item in hand — the same for the whole workgroup
+	__device__ __forceinline__ uint32_t action_of(uint32_t level, uint32_t X, uint32_t Y, uint32_t Z) const {
+		return clip_action(k.mode, classify_node(k.min, k.size, k.numPlanes, pl, level, X, Y, Z));
+	}
+	__device__ __forceinline__ bool empties(uint32_t level, uint32_t X, uint32_t Y, uint32_t Z) const { return action_of(level, X, Y, Z) == CLIP_ACT_EMPTY; }
+	// behind the load of DU samples per lane: a removed sample is one the lane does not have; a highlighted one carries the clip's colour
+	template <uint32_t DU> __device__ __forceinline__ void test(float4 (&p)[DU], bool (&have)[DU]) const {
+		if (action != CLIP_ACT_KEEP_PASSING && action != CLIP_ACT_KEEP_FAILING && action != CLIP_ACT_COLOUR_PASSING) return;      // (uniform)
+		bool ok[DU];
+#pragma unroll
+		for (uint32_t u = 0; u < DU; u++) ok[u] = true;
+#pragma unroll 1
+		for (uint32_t q = 0; q < k.numPlanes; q++) {
+#pragma unroll
+			for (uint32_t u = 0; u < DU; u++) ok[u] = ok[u] && plane_passes(pl[q], p[u].x, p[u].y, p[u].z);
+		}
+#pragma unroll
+		for (uint32_t u = 0; u < DU; u++) {
+			if (action == CLIP_ACT_KEEP_PASSING) have[u] = have[u] && ok[u];
+			else if (action == CLIP_ACT_KEEP_FAILING) have[u] = have[u] && !ok[u];
+			else if (ok[u]) p[u].w = __uint_as_float(k.color);
+		}
+	}
+};
+// the policy of a kernel from its trailing arguments: none -> NoClip; the ClipArgs -> Clip, with the planes staged in the workgroup's LDS
+template <bool ON> struct ClipStore { __device__ __forceinline__ NoClip policy() const { return NoClip(); } };
+template <> struct ClipStore<true> {
+	__device__ __forceinline__ Clip policy(const ClipArgs& k) const {
+		__shared__ double sh_planes[SIMLOD_REGION_MAX_PLANES][4];
+		if (threadIdx.x < 4u * SIMLOD_REGION_MAX_PLANES) sh_planes[threadIdx.x / 4u][threadIdx.x % 4u] = k.pl[threadIdx.x / 4u][threadIdx.x % 4u];
+		__syncthreads();
+		return Clip{k, sh_planes, CLIP_ACT_NONE};
+	}
+};

@@ -306,8 +306,8 @@ __device__ __forceinline__ void draw_staged(const DrawCtx& c, const float4 (&p)[
 	}
 }
 
-template <int MODE>
-__device__ __forceinline__ void draw_item(const DrawCtx& c, const SimlodChunk* const* dir, uint32_t count, uint32_t overrideColor, bool useOverride, uint32_t& outside) {
+template <int MODE, typename POLICY>
+__device__ __forceinline__ void draw_item(const DrawCtx& c, const SimlodChunk* const* dir, uint32_t count, uint32_t overrideColor, bool useOverride, uint32_t& outside, const POLICY& clip) {
 	// render.cu:106-159: chunk i holds samples [1000 i, 1000 i + 1000); the chunk addresses come from the frame's directory (staged in LDS).
 	// Four samples per thread are loaded before the first is drawn: the loads overlap instead of queueing behind the atomics.
 	constexpr uint32_t DU = 4;
@@ -324,6 +324,7 @@ __device__ __forceinline__ void draw_item(const DrawCtx& c, const SimlodChunk* c
 			have[u] = s < count;
 			p[u] = have[u] ? reinterpret_cast<const float4*>(dir[s / SIMLOD_POINTS_PER_CHUNK]->points)[s % SIMLOD_POINTS_PER_CHUNK] : make_float4(0, 0, 0, 0);
 		}
+		clip.test(p, have);                                                 // (the three draw paths below see what the frame's clip left)
 		if (wave && merge) {
 #pragma unroll
 			for (uint32_t u = 0; u < DU; u++) draw_wave<MODE>(c, p[u], have[u], overrideColor, useOverride, outside);
@@ -337,9 +338,9 @@ __device__ __forceinline__ void draw_item(const DrawCtx& c, const SimlodChunk* c
 }
 
 // (render_bins.inc)
-template <int MODE>
+template <int MODE, typename POLICY>
 __device__ __forceinline__ void bin_item(const DrawCtx& c, const RenderArgs& a, uint32_t* lds, const SimlodChunk* const* dir, uint32_t count, uint32_t overrideColor, bool useOverride,
-                                         uint32_t& outside);
+                                         uint32_t& outside, const POLICY& clip);
 
 template <int MODE>
 __device__ __forceinline__ void tile_clear(const DrawCtx& c) {
@@ -389,8 +390,11 @@ __device__ __forceinline__ void tile_flush(const DrawCtx& c) {
 	}
 }
 
-template <int MODE>
-__global__ __launch_bounds__(DTPB) void r_draw(RenderArgs a) {
+// (one definition for both kinds of frame, as r_visible: r_draw<MODE>(a) and r_draw<MODE>(a, k) under a clip, the planes in LDS beside the tile and the hot table)
+template <int MODE, typename... CLIP>
+__global__ __launch_bounds__(DTPB) void r_draw(RenderArgs a, CLIP... k) {
+	ClipStore<sizeof...(CLIP) != 0> sh_clip;
+	auto clip = sh_clip.policy(k...);
 	if (MODE == MODE_DEPTH) clear_colour_planes(a);
 	if (!a.showPoints) return;
 	__shared__ uint32_t sh_idx;
@@ -433,6 +437,14 @@ __global__ __launch_bounds__(DTPB) void r_draw(RenderArgs a) {
 			overrideColor = a.colorByNode ? node_color(node) : lod_color((int)node->level);
 			useOverride = true;
 		}
+		if constexpr (decltype(clip)::ON) {
+			// the class of the item's node, from its visible record: every lane computes the same, and the branches on it are scalar
+			const SimlodNode* node = visible + min(it.visibleIdx, VISIBLE_NODES - 1u);
+			uint32_t act = __builtin_amdgcn_readfirstlane(clip.action_of(node->level, node->X, node->Y, node->Z));
+			if (MODE == MODE_DEPTH && (act == CLIP_ACT_COLOUR_PASSING || act == CLIP_ACT_COLOUR_ALL)) act = CLIP_ACT_NONE;      // (the depth pass reads no colour)
+			if (act == CLIP_ACT_COLOUR_ALL) { overrideColor = clip.k.color; useOverride = true; }
+			clip.action = act;
+		}
 		const bool binned = it.tileX == TILE_BINNED;
 		c.tileX = binned ? -1 : it.tileX; c.tileY = it.tileY; c.tileW = (int)(it.tileWH & 0xffffu); c.tileH = (int)(it.tileWH >> 16);
 		if (it.tileX < 0) { c.tileW = 0; c.tileH = 0; }                                       // no tile: nothing is inside it
@@ -452,8 +464,8 @@ __global__ __launch_bounds__(DTPB) void r_draw(RenderArgs a) {
 			while (whole < ITEM_CHUNKS && whole * SIMLOD_POINTS_PER_CHUNK < it.samples && sh_dir[whole] != nullptr) whole++;
 			samples = min(samples, whole * SIMLOD_POINTS_PER_CHUNK);
 		}
-		if (binned) bin_item<MODE>(c, a, reinterpret_cast<uint32_t*>(sh_tile), sh_dir, samples, overrideColor, useOverride, outside);
-		else draw_item<MODE>(c, sh_dir, samples, overrideColor, useOverride, outside);
+		if (binned) bin_item<MODE>(c, a, reinterpret_cast<uint32_t*>(sh_tile), sh_dir, samples, overrideColor, useOverride, outside, clip);
+		else draw_item<MODE>(c, sh_dir, samples, overrideColor, useOverride, outside, clip);
 		if (it.tileX >= 0) { __syncthreads(); tile_flush<MODE>(c); }
 		__syncthreads();
 		if (SIMLOD_MEASURE != 0 && threadIdx.x == 0) const_cast<DrawItem*>(items)[itemAt].took = (uint32_t)(wall_clock64() - itemStart);

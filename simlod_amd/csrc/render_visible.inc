@@ -74,7 +74,9 @@ __device__ __forceinline__ void node_geometry(const RenderArgs& a, const float (
 // (node fields; one reservation per wave; the chunk-table row; stores) instead of three kernels with twelve.
 // Draw items: a lane writes its node's chunk addresses into the frame's directory — copied from the builder's chunk table when that is
 // valid, else by walking the list (the only serial pointer chase left in a frame) — and cuts the list into items of <= 64 chunks.
-__device__ __forceinline__ void visible_nodes(const RenderArgs& a, const float (&planes)[6][4], const uint32_t numNodes, SimlodNode* staged, const uint32_t readyEarly) {
+// `clip` (render_common.inc: NoClip, Clip): a node the frame's clip empties counts as holding nothing — not visible, in the node array either.
+template <typename POLICY>
+__device__ __forceinline__ void visible_nodes(const RenderArgs& a, const float (&planes)[6][4], const uint32_t numNodes, SimlodNode* staged, const uint32_t readyEarly, const POLICY& clip) {
 	const uint32_t i = blockIdx.x * TPB + threadIdx.x;
 	const bool active = i < numNodes;
 	// the workgroup's 256 nodes were staged in LDS with coalesced loads (r_visible): a lane reading ITS 152-byte node from memory touched a
@@ -101,7 +103,8 @@ __device__ __forceinline__ void visible_nodes(const RenderArgs& a, const float (
 	for (int k = 0; k < 8; k++) leaf = leaf && n->children[k] == nullptr;
 	bool inside, large, unused, parentLarge = false;
 	node_geometry<true>(a, planes, level, X, Y, Z, inside, large);
-	const bool visible = inside && (counts[0] > 0u || counts[1] > 0u);
+	bool visible = inside && (counts[0] > 0u || counts[1] > 0u);
+	if constexpr (POLICY::ON) visible = visible && !clip.empties(level, X, Y, Z);
 	if (active) { n->visible = visible ? 1 : 0; n->isLarge = large ? 1 : 0; nGlobal->visible = visible ? 1 : 0; nGlobal->isLarge = large ? 1 : 0; }      // (the staged copy goes to the visible list)
 	if (active && visible && !large && level > 0u) node_geometry<false>(a, planes, level - 1u, X >> 1, Y >> 1, Z >> 1, unused, parentLarge);   // only who needs it
 	const bool emit = active && visible && (large ? leaf : parentLarge);
@@ -254,7 +257,12 @@ __device__ __forceinline__ void visible_nodes(const RenderArgs& a, const float (
 	if (lane_id() == 0 && waveTable != 0u) atomicAdd(counter_at(a.mom, C_TABLE_LISTS), waveTable);
 }
 
-__global__ __launch_bounds__(TPB) void r_visible(RenderArgs a) {
+// One definition for both kinds of frame: r_visible(a) — no clip, the kernel as it was before there were clips — and r_visible(a, k) with the
+// frame's clip as a second argument (RenderArgs goes to every kernel of the frame: the clip stays out of it), its planes staged in LDS.
+template <typename... CLIP>
+__global__ __launch_bounds__(TPB) void r_visible(RenderArgs a, CLIP... k) {
+	ClipStore<sizeof...(CLIP) != 0> sh_clip;
+	const auto clip = sh_clip.policy(k...);
 	R_PROBE_MIN(0);
 	if (blockIdx.x == 0 && threadIdx.x == 0) clear_counters(a);
 	const uint32_t numNodes = min(a.stats->numNodes, a.nodeCapacity);
@@ -274,7 +282,7 @@ __global__ __launch_bounds__(TPB) void r_visible(RenderArgs a) {
 		const uint32_t readyEarly = __hip_atomic_load(frame_ready_word(a.mom, a.lay), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		if (threadIdx.x < 6) frustum_plane(a.transformUpdate, (int)threadIdx.x, planes[threadIdx.x]);
 		__syncthreads();
-		visible_nodes(a, planes, numNodes, reinterpret_cast<SimlodNode*>(staged), readyEarly);
+		visible_nodes(a, planes, numNodes, reinterpret_cast<SimlodNode*>(staged), readyEarly, clip);
 		R_PROBE_MAX(5);
 	}
 	clear_frame(a);

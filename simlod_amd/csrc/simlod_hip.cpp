@@ -15,6 +15,7 @@
 #include "simlod_hip.h"
 #include "simlod_internal.hpp"
 #include "render_layout.hpp"
+#include "clip_rules.hpp"
 
 namespace simlod {
 
@@ -150,6 +151,8 @@ void array_event(Context& ctx, const void* nodes, ArrayEvent e) {
 	Locked o(ctx, nodes, e != ARRAY_RESET && e != ARRAY_CONSTRUCT);                 // (those two: nothing to forget of an array without a record)
 	if (o.o != nullptr) o->on(e);
 }
+void set_clip(Context& ctx, const SimlodClip& clip) { std::lock_guard<std::mutex> hold(ctx.octreesLock); ctx.clip = clip; }
+SimlodClip clip_of(Context& ctx) { std::lock_guard<std::mutex> hold(ctx.octreesLock); return ctx.clip; }
 ArrayState array_state(Context& ctx, const void* nodes) { Locked o(ctx, nodes, false); return o.o != nullptr ? ArrayState{o->rendered, o->imported} : ArrayState{false, false}; }
 
 // ---- launch sizing (octree_state.hpp size_launch): the upload counters the host has told about, and the part of launch_plan that needs the process ----
@@ -362,6 +365,12 @@ int simlod_context_set_knob(SimlodContext* c, const char* name, int value, int s
 		if (std::strcmp(name, KNOB_NAMES[k]) == 0) { ctx_or_default(c).knob[k] = set ? value : KNOB_UNSET; return 0; }
 	return (int)hipErrorNotFound;
 }
+int simlod_context_set_clip(SimlodContext* c, const SimlodClip* clip) {
+	if (clip != nullptr && !clip_acceptable(*clip)) return (int)hipErrorInvalidValue;      // (the context's clip stays as it was)
+	set_clip(ctx_or_default(c), clip != nullptr ? *clip : SimlodClip{});
+	return 0;
+}
+int simlod_set_clip(const SimlodClip* clip) { return simlod_context_set_clip(nullptr, clip); }
 int simlod_context_reload_env(SimlodContext* c) { ctx_or_default(c).reload_env(); return 0; }
 
 int simlod_set_node_capacity(uint32_t numNodes) { return simlod_context_set_node_capacity(nullptr, numNodes); }

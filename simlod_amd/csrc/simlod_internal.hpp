@@ -82,6 +82,7 @@ struct Context {
 	SideStream* side[64] = {};                               // per device ordinal, made by the first launch that wants it
 	std::mutex octreesLock;
 	std::vector<OctreeState> octrees;                        // per node array: its leaf chunk table, rendered / imported, stale side tables, launch feedback (octree_state.hpp)
+	SimlodClip clip{};                                       // simlod_context_set_clip (mode SIMLOD_CLIP_OFF: none), under octreesLock; launch_render copies it once per call
 	std::mutex framesLock;
 	std::vector<FrameFeedback> frames;
 	hipEvent_t gateEvent[64] = {};                            // per device ordinal: the end of this context's latest k_expand, when it runs without a second stream (expand_gate)
@@ -97,6 +98,8 @@ uint32_t* frame_feedback(Context& ctx, const void* buffer, uint32_t parts, bool&
 void frame_feedback_no_bins(Context& ctx, const void* buffer);
 void array_event(Context& ctx, const void* nodes, ArrayEvent e);
 ArrayState array_state(Context& ctx, const void* nodes);      // {false, false} for an array nothing was recorded for
+void set_clip(Context& ctx, const SimlodClip& clip);          // (validated by the caller)
+SimlodClip clip_of(Context& ctx);                            // the context's clip as it is now
 Context& context_of(const void* nodes);                      // the context `nodes` is attached to, else the default one
 uint32_t live_contexts();                                    // contexts that exist right now (the default one included once it has been used)
 

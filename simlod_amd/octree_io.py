@@ -506,6 +506,27 @@ class Region:
         return r
 
 
+class Clip:
+    """What a frame does with a region (include/simlod_hip.h, "clip regions"): mode "inside" shows what is inside it, "outside" cuts it away,
+    "highlight" gives what is inside it the colour word `color`; "off" is no clip.  DeviceOctree.set_clip takes one."""
+
+    def __init__(self, region, mode="inside", color=0):
+        if not isinstance(region, Region):
+            region = Region(region)                                        # (planes: validated there)
+        if mode not in abi.CLIP_MODES:
+            raise ValueError(f"mode {mode!r}: a clip's mode is one of {sorted(abi.CLIP_MODES)}")
+        if not 0 <= int(color) <= 0xFFFFFFFF:
+            raise ValueError("a colour word is a 32-bit unsigned integer")
+        self.region, self.mode, self.color = region, mode, int(color)
+
+    def record(self):
+        """The SimlodClip the C ABI takes (abi.clip_dtype, one record)."""
+        r = np.zeros(1, dtype=abi.clip_dtype)
+        r["mode"], r["color"] = abi.CLIP_MODES[self.mode], self.color
+        r["region"] = self.region.record()
+        return r
+
+
 class Footprint:
     """An extruded polygon (include/simlod_hip.h, "footprint queries"): 3 .. 256 vertices (u, v) as float32, closed from the last to the first,
     in the plane a point is mapped into by u = ((ux*x + uy*y) + uz*z) + u0 and v likewise (axis_u, axis_v as float32).  Inside is the even-odd

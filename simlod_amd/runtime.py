@@ -51,6 +51,8 @@ def lib():
         L.simlod_upload_counter_written.argtypes = [vp, u32]
         L.simlod_context_set_knob.argtypes = [vp, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]
         L.simlod_context_reload_env.argtypes = [vp]
+        L.simlod_context_set_clip.argtypes = [vp, vp]
+        L.simlod_set_clip.argtypes = [vp]
         L.simlod_context_set_trunk_mask.argtypes = [vp, u64, u64]
         L.simlod_context_construct_buffer_min_bytes.restype = u64
         L.simlod_context_construct_buffer_min_bytes.argtypes = [vp]
@@ -118,6 +120,7 @@ EXPORTED_SYMBOLS = [
     "simlod_export_buffer_min_bytes", "simlod_export_octree", "simlod_import_octree", "simlod_import_octree_buildable",
     "simlod_query_buffer_min_bytes", "simlod_query_region", "simlod_rays_buffer_min_bytes", "simlod_query_rays",
     "simlod_neighbours_buffer_min_bytes", "simlod_query_neighbours", "simlod_footprint_buffer_min_bytes", "simlod_query_footprint",
+    "simlod_context_set_clip", "simlod_set_clip",
 ]
 
 
@@ -214,6 +217,12 @@ class DeviceOctree:
     def reload_env(self):
         """Read the tuning knobs from the environment again (they are read once, when the context is made)."""
         _check(self.L.simlod_context_reload_env(self.ctx), "simlod_context_reload_env")
+
+    def set_clip(self, clip):
+        """The clip of THIS octree's frames from now on (simlod_context_set_clip; octree_io.Clip): render, render_part and render_composed
+        honour it, nothing is copied.  None, or a clip of mode "off": no clip."""
+        rec = clip.record() if clip is not None else None
+        _check(self.L.simlod_context_set_clip(self.ctx, ctypes.c_void_p(rec.ctypes.data) if rec is not None else None), "simlod_context_set_clip")
 
     def set_trunk_mask(self, lo, hi):
         """Multi-GPU jobs: the nodes of levels 0-2 that split whatever this rank holds under them (simlod_context_set_trunk_mask; the mask
