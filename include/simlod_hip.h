@@ -701,6 +701,78 @@ int simlod_query_neighbours(const SimlodNode* nodes, const SimlodStats* stats, c
                             SimlodExportNode* table, uint32_t tableCapacity, SimlodNeighbour* neighbours, uint32_t* within,
                             SimlodNeighbourCounts* counts, void* stream);
 
+/* ---- view queries: the level-of-detail cut a camera needs, within a sample budget --------------------------------------------------------------
+ * simlod_query_view writes what simlod_export_octree(maxLevel, SIMLOD_EXPORT_VISIBLE) writes after a frame — without a frame: no render buffer,
+ * nothing written to the source, and with a ladder of what coarser cuts would cost, from which a sample budget chooses one.
+ *
+ * The camera is `uniforms`: width, height, transform_updateBound, minNodeSize, boxMin, boxMax, as simlod_launch_render takes them (cube size = the
+ * largest fp32 extent, min = boxMin).  All geometry is the fp32 arithmetic of kernel_render's visibility pass (render.cu:760-861), without fused
+ * multiply-add, divisions and square roots correctly rounded:
+ *   planes   row vectors r_j = (M[j].x, M[j].y, M[j].z, M[j].w) of M = transform_updateBound; the six planes r3 - r0, r3 + r0, r3 + r1, r3 - r1,
+ *            r3 - r2, r3 + r2, each divided by len = sqrtf((x*x + y*y) + z*z) of its first three components.
+ *   cube     s = size / 2^level; mn_a = min_a + ((float)A + 0.0f) * s, mx_a = min_a + ((float)A + 1.0f) * s for the node's coordinate A on axis a.
+ *   inside   for every plane (nx, ny, nz, c): v_a = n_a > 0 ? mx_a : mn_a; d = (((nx*vx) + ny*vy) + nz*vz) + c; inside iff no plane has d < 0.
+ *   extents  the corners p000, p001, p010, p011, p100, p101, p110, p111 (bit 2 of the corner number picks mx on x, bit 1 on y, bit 0 on z);
+ *            dot(r, p) = (((r.x*p.x) + r.y*p.y) + r.z*p.z) + r.w*1.0f; sx = ((dot(r0, p) / dot(r3, p)) * 0.5f + 0.5f) * width, sy likewise from r1
+ *            and height; min and max over the corners as the trees fminf(fminf(fminf(s0, s1), fminf(s2, s3)), fminf(fminf(s4, s5), fminf(s6, s7)))
+ *            and fmaxf likewise (fminf / fmaxf drop a NaN); dx = maxx - minx, dy = maxy - miny.
+ *  V1. Listed nodes: exactly as simlod_export_octree — breadth-first, every node with level <= maxLevel; FLAG_LEAF as there.
+ *  V2. inside(n) as above, or true under SIMLOD_VIEW_NO_CULL.  has(n): the node's sample count (numPoints of a source leaf, else numVoxels) > 0.
+ *      visible(n) = inside && has.  numInside counts the listed nodes that are visible.
+ *  V3. large_b(n) iff (double)dx > L_b || (double)dy > L_b with L_b = 2.0 * (double)minNodeSize * 2^b (exact; a NaN extent is never large).
+ *      R(n) = the number of b in 0..20 with large_b(n).  P(root) = 21 under SIMLOD_VIEW_DRAW_SMALL_ROOT, else 0; P(n) = R(parent of n) otherwise.
+ *  V4. drawn_b(n) iff visible(n) && (b < R(n) ? leaf(n) : b < P(n)) — render.cu:905-935 with minNodeSize * 2^b.
+ *  V5. S(b) = the sum of the sample counts of the listed nodes drawn at b, for every b in 0..20: samplesAt, whatever minBias / maxBias say.
+ *  V6. bias = the smallest b in [minBias, maxBias] with S(b) <= sampleBudget (S need not be monotone: the finest cut that fits wins).  If none
+ *      fits: SIMLOD_EXPORT_ERR_BUDGET, bias = maxBias, the table is complete for maxBias, numSamples = S(maxBias), and no sample is written.
+ *      S may be 0: once the root is not large nothing is drawn, as in a frame (SIMLOD_VIEW_DRAW_SMALL_ROOT draws it then).
+ *  V7. SELECTED, numSamples and firstSample follow drawn_bias; numSelected counts the selected nodes.  Samples in chunk-list order, as the export
+ *      writes them.  samples == NULL: count only — the table and the counts are complete, nothing else is written (sampleCapacity is ignored).
+ *      Capacity errors as simlod_export_octree; a scratch buffer too small for the chunk items sets SIMLOD_EXPORT_ERR_CAPACITY.
+ *  V8. With flags == 0 and no budget the table and the samples equal, byte for byte, simlod_export_octree(maxLevel, SIMLOD_EXPORT_VISIBLE) after a
+ *      simlod_launch_render (no clip set) with the same uniforms except minNodeSize * 2^bias.
+ *  V9. The source is only read: Node.visible / isLarge keep the last frame's values. */
+typedef struct SimlodView {            /* host memory, read before the call returns */
+	uint32_t flags;                    /* SIMLOD_VIEW_* */
+	uint32_t minBias, maxBias;         /* 0 <= minBias <= maxBias <= 20 */
+	uint32_t reserved;                 /* 0 */
+	uint64_t sampleBudget;             /* 0xffffffffffffffff: none */
+} SimlodView;
+#define SIMLOD_VIEW_MAX_BIAS        20u
+#define SIMLOD_VIEW_NO_CULL         0x1u   /* every node counts as inside the frustum */
+#define SIMLOD_VIEW_DRAW_SMALL_ROOT 0x2u   /* the root counts as having a large parent */
+#define SIMLOD_EXPORT_ERR_BUDGET    0x8u   /* SimlodViewCounts.error: no bias in [minBias, maxBias] fits sampleBudget */
+typedef struct SimlodViewCounts {      /* written by the device */
+	uint32_t numNodes;                 /* table entries written                                                                  */
+	uint32_t error;                    /* SIMLOD_EXPORT_ERR_* bits                                                               */
+	uint64_t numSamples;               /* S(bias) (= written, unless count-only or an error)                                     */
+	uint32_t bias;                     /* the chosen bias                                                                        */
+	uint32_t numSelected;              /* listed nodes drawn at `bias`                                                           */
+	uint32_t numInside;                /* listed nodes that are visible (V2)                                                     */
+	uint32_t reserved;                 /* 0                                                                                      */
+	uint64_t samplesAt[SIMLOD_VIEW_MAX_BIAS + 1u];   /* S(b) for b = 0..20                                                       */
+} SimlodViewCounts;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodView) == 24, "View");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodView, minBias) == 4, "View.minBias");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodView, maxBias) == 8, "View.maxBias");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodView, sampleBudget) == 16, "View.sampleBudget");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodViewCounts) == 200, "ViewCounts");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodViewCounts, numSamples) == 8, "ViewCounts.numSamples");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodViewCounts, bias) == 16, "ViewCounts.bias");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodViewCounts, numSelected) == 20, "ViewCounts.numSelected");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodViewCounts, numInside) == 24, "ViewCounts.numInside");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodViewCounts, samplesAt) == 32, "ViewCounts.samplesAt");
+
+/* The view query (rules above).  Asynchronous on `stream`; everything in between lives in `scratch`, whose chunk items (32 bytes per 1 000-sample
+ * chunk of the result) take what the buffer has behind simlod_export_buffer_min_bytes(tableCapacity, 0): size it by
+ * simlod_export_buffer_min_bytes(tableCapacity, samples of the result).  hipErrorInvalidValue with nothing enqueued: a null pointer other than
+ * `samples`, unknown flag bits, nonzero `reserved`, minBias > maxBias, maxBias > 20, a non-finite minNodeSize, width, height or entry of
+ * transform_updateBound, scratchBytes below simlod_export_buffer_min_bytes(tableCapacity, 0).  While the builder's chunk table for `nodes` is
+ * valid the first chunks of each list come from it, the rest by `next` (as simlod_export_octree). */
+int simlod_query_view(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodView* view, uint32_t maxLevel,
+                      void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
+                      uint64_t sampleCapacity, SimlodViewCounts* counts, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

@@ -138,6 +138,28 @@ query_counts_dtype = np.dtype({"names": ["numNodes", "error", "numSamples", "num
                                "formats": ["<u4", "<u4", "<u8", "<u8", "<u4", "<u4"], "offsets": [0, 4, 8, 16, 24, 28], "itemsize": 32})
 assert region_dtype.itemsize == 272 and query_counts_dtype.itemsize == 32
 
+# ---- view queries (include/simlod_hip.h, "view queries") --------------------------------------------------------------------------------
+VIEW_MAX_BIAS = 20
+VIEW_NO_CULL, VIEW_DRAW_SMALL_ROOT = 0x1, 0x2
+VIEW_NO_BUDGET = 0xFFFFFFFFFFFFFFFF
+EXPORT_ERR_BUDGET = 0x8
+view_dtype = np.dtype({"names": ["flags", "minBias", "maxBias", "reserved", "sampleBudget"], "formats": ["<u4", "<u4", "<u4", "<u4", "<u8"],
+                       "offsets": [0, 4, 8, 12, 16], "itemsize": 24})
+view_counts_dtype = np.dtype({"names": ["numNodes", "error", "numSamples", "bias", "numSelected", "numInside", "reserved", "samplesAt"],
+                              "formats": ["<u4", "<u4", "<u8", "<u4", "<u4", "<u4", "<u4", ("<u8", VIEW_MAX_BIAS + 1)],
+                              "offsets": [0, 4, 8, 16, 20, 24, 28, 32], "itemsize": 200})
+assert view_dtype.itemsize == 24 and view_counts_dtype.itemsize == 200
+
+
+def view_record(bias=0, max_bias=VIEW_MAX_BIAS, budget=None, cull=True, draw_small_root=False):
+    """The SimlodView record of a view query: the biases [bias, max_bias], the sample budget (None: none) and the two flags."""
+    v = np.zeros(1, dtype=view_dtype)
+    v["flags"] = (0 if cull else VIEW_NO_CULL) | (VIEW_DRAW_SMALL_ROOT if draw_small_root else 0)
+    v["minBias"], v["maxBias"] = int(bias), int(max_bias)
+    v["sampleBudget"] = VIEW_NO_BUDGET if budget is None else int(budget)
+    return v
+
+
 # ---- clip regions (include/simlod_hip.h, "clip regions") --------------------------------------------------------------------------------
 CLIP_OFF, CLIP_INSIDE, CLIP_OUTSIDE, CLIP_HIGHLIGHT = 0, 1, 2, 3
 CLIP_MODES = {"off": CLIP_OFF, "inside": CLIP_INSIDE, "outside": CLIP_OUTSIDE, "highlight": CLIP_HIGHLIGHT}

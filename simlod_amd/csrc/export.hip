@@ -18,6 +18,8 @@
 // Region query (simlod_query_region): k_q_hier -> k_q_dir -> k_q_count -> k_q_scan -> k_q_write, described in export_region.inc.
 // Footprint query (simlod_query_footprint): k_f_hier -> k_q_dir -> k_f_count -> k_q_scan -> k_f_write, the region query's sequence with an extruded
 // polygon on top of the planes, in export_footprint.inc.
+// View query (simlod_query_view): k_v_hier -> k_v_scan -> k_x_dir -> k_copy, the export's sequence with the camera's rules in the walk, in
+// export_view.inc; the rules themselves in view_rules.hpp.
 // Pair queries: k_p_hier -> k_q_dir -> k_p_pairs<Q, count> -> k_p_scan<Q> -> k_p_pairs<Q, fill> -> Q's test kernel -> Q's reduce kernel; the pipeline
 // is written once over a query trait Q, in export_pairs.inc.  Ray query (simlod_query_rays): RayQuery, k_r_test, k_r_reduce, in export_rays.inc.
 // Neighbour query (simlod_query_neighbours): NbQuery, k_n_test, k_n_reduce, in export_neighbours.inc.
@@ -33,6 +35,7 @@
 #include "simlod_device.hpp"
 #include "simlod_hip.h"
 #include "simlod_internal.hpp"
+#include "view_rules.hpp"
 
 namespace simlod {
 namespace {
@@ -42,6 +45,7 @@ namespace {
 #include "export_table.inc"    // hier_walk, k_x_hier, k_x_scan, k_x_dir
 #include "export_region.inc"   // QueryGeom, classify, QItem, QueryLayout, QueryArgs, k_q_hier, k_q_dir, k_q_count, k_q_scan, k_q_write
 #include "export_footprint.inc"  // FootEdge, FootGeom, FootArgs, stage_edges, Footprint, classify_footprint, k_f_hier, k_f_count, k_f_write
+#include "export_view.inc"     // ViewArgs, k_v_hier, k_v_scan
 #include "export_pairs.inc"    // the pair records, PairLayout, PairArgs, k_p_hier, wave_descend, k_p_pairs, k_p_scan, TestView, test_chunk
 #include "export_rays.inc"     // RayArgs, ray_load, slab, sample_t, RayQuery, k_r_test, k_r_reduce
 #include "export_neighbours.inc"  // NbArgs, sphere_load, sphere_cube, sphere_d2, NbQuery, k_n_test, k_n_reduce
@@ -176,6 +180,37 @@ int launch_footprint(Context& ctx, const SimlodNode* nodes, const SimlodStats* s
 	SIMLOD_LAUNCH(k_f_count, dim3(grid), dim3(LANE_TPB), stream, fa);
 	SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, fa.q);
 	if (samples != nullptr) SIMLOD_LAUNCH(k_f_write, dim3(grid), dim3(LANE_TPB), stream, fa);
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+// simlod_query_view: the export's launches with k_v_hier / k_v_scan in the place of k_x_hier / k_x_scan.  The scratch buffer is the export's; the
+// chunk items take what it has behind the table's part, and the device reports a buffer that holds too few of them.
+int launch_view(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodView* view, uint32_t maxLevel,
+                void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity,
+                SimlodViewCounts* counts, hipStream_t stream) {
+	if (nodes == nullptr || stats == nullptr || u == nullptr || view == nullptr || scratch == nullptr || table == nullptr || counts == nullptr)
+		return (int)hipErrorInvalidValue;
+	if (!view_acceptable(*view, *u) || scratchBytes < export_min_bytes(tableCapacity, 0u)) return (int)hipErrorInvalidValue;
+	ViewArgs v{};
+	ExportArgs& a = v.x;
+	a.nodes = nodes; a.stats = stats; a.maxLevel = maxLevel; a.select = SIMLOD_EXPORT_ALL; a.cap = tableCapacity;   // (the walk lists and selects everything: k_v_hier takes away)
+	a.scratch = reinterpret_cast<uint8_t*>(scratch); a.table = table; a.samples = samples; a.sampleCap = samples != nullptr ? sampleCapacity : 0u;
+	a.counts = reinterpret_cast<SimlodExportCounts*>(counts);
+	a.lay = Layout(tableCapacity, 0u); a.lay.take_rest(scratchBytes);
+	if (samples == nullptr) a.lay.itemCap = 0xffffffffull;                      // count only: no item is written, none can be missing
+	bind_leaf_table(ctx, nodes, a);
+	v.g.m = u->transform_updateBound;
+	octree_box(u, v.g.cubeSize, v.g.minx, v.g.miny, v.g.minz);                  // render.cu:1135-1137, as launch_render
+	v.g.width = u->width; v.g.height = u->height; v.g.minNodeSize = u->minNodeSize;
+	v.flags = view->flags; v.minBias = view->minBias; v.maxBias = view->maxBias; v.budget = view->sampleBudget;
+	v.counts = counts;
+	SIMLOD_LAUNCH(k_v_hier, dim3(1), dim3(WG_TPB), stream, v);
+	SIMLOD_LAUNCH(k_v_scan, dim3(1), dim3(WG_TPB), stream, a);
+	if (samples != nullptr) {
+		if (tableCapacity != 0u) SIMLOD_LAUNCH(k_x_dir, dim3((tableCapacity + LANE_TPB - 1u) / LANE_TPB), dim3(LANE_TPB), stream, a);
+		SIMLOD_LAUNCH(k_copy, dim3(copy_grid(a.lay.itemCap)), dim3(LANE_TPB), stream, (const uint8_t*)a.scratch, a.lay.items);
+	}
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();
 }

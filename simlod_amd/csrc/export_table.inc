@@ -1,11 +1,14 @@
-// export_table.inc — part of export.hip: the export's table.  hier_walk (the breadth-first walk every call family starts with), k_x_hier,
+// export_table.inc — part of export.hip: the export's table.  hier_walk (the breadth-first walk every call family starts with), NoEntry, k_x_hier,
 // k_x_scan, k_x_dir.
 
 // The breadth-first walk of k_x_hier and, QUERY, of k_q_hier: there a child that lies outside the region is not listed (it counts as cut off
 // for the node-count check), and cls[t] gets the class of every listed entry; numSamples then holds the samples BEFORE the test.
 // classify(level, X, Y, Z): the class of that cube (QUERY only; NoRegion where there is no region to ask).
-template <bool QUERY, typename Classify>
-__device__ __forceinline__ void hier_walk(const ExportArgs& a, Classify classify, uint32_t* cls) {
+// entry(t, e, srcLeaf): what a walk does per listed entry on top, with the entry as it is about to be written (k_v_hier, export_view.inc: the
+// entries of the levels above are written, and a barrier lies in between); NoEntry: nothing.
+struct NoEntry { __device__ __forceinline__ void operator()(uint32_t, const SimlodExportNode&, bool) const {} };
+template <bool QUERY, typename Classify, typename Entry = NoEntry>
+__device__ __forceinline__ void hier_walk(const ExportArgs& a, Classify classify, uint32_t* cls, Entry entry = Entry()) {
 	__shared__ uint32_t sh_scan[WG_WAVES];
 	__shared__ uint32_t sh_err, sh_trunc;
 	Header* hdr = reinterpret_cast<Header*>(a.scratch);
@@ -82,6 +85,7 @@ __device__ __forceinline__ void hier_walk(const ExportArgs& a, Classify classify
 					if (c == Q_OUTSIDE) e.numSamples = 0u;
 					cls[t] = c;
 				}
+				entry(t, e, srcLeaf);
 				a.table[t] = e;
 			}
 			next += total;

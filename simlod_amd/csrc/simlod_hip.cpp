@@ -473,6 +473,14 @@ int simlod_query_footprint(const SimlodNode* nodes, const SimlodStats* stats, co
 	                        samples, sampleCapacity, counts, (hipStream_t)stream);
 }
 
+int simlod_query_view(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodView* view, uint32_t maxLevel,
+                      void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
+                      uint64_t sampleCapacity, SimlodViewCounts* counts, void* stream) {
+	if (nodes == nullptr) return (int)hipErrorInvalidValue;
+	return launch_view(context_of(nodes), nodes, stats, uniforms, view, maxLevel, scratch, scratchBytes, table, tableCapacity, samples, sampleCapacity,
+	                   counts, (hipStream_t)stream);
+}
+
 uint64_t simlod_rays_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates) {
 	return rays_min_bytes(nodeCapacity, sampleBound, numRays, numPairs, numCandidates);
 }

@@ -24,6 +24,9 @@ simlod_query_region — every rule restated in numpy float64, which reproduces t
 Footprint queries (include/simlod_hip.h, "footprint queries"): `Footprint` holds the polygon and the affine map into its plane,
 `OctreeExport.crop(region, footprint=...)` is the host mirror of simlod_query_footprint, in the same float64 operation order.
 
+View queries (include/simlod_hip.h, "view queries"): `OctreeExport.view` (on a full export) is the host mirror of simlod_query_view and
+`view_geometry` of its rules V2 and V3 — the rasteriser's visibility arithmetic in numpy float32, in the device's operation order.
+
 Ray queries (include/simlod_hip.h, "ray queries"): `Rays` holds a batch of SimlodRay records, `OctreeExport.cast` (on a full export) and
 `OctreeExport.cast_selected` (on any export) are the host mirror of simlod_query_rays, in the same float64 operation order.
 
@@ -201,6 +204,43 @@ class OctreeExport:
         c = np.zeros((), dtype=abi.query_counts_dtype)
         c["numNodes"], c["numSamples"], c["numCandidates"] = len(out), len(samples), int(cand.sum())
         c["numFilteredNodes"], c["numCopiedNodes"] = n_filtered, n_copied
+        return ex, c
+
+    # -- view queries (include/simlod_hip.h, "view queries") ---------------------------------------------------------------------------------
+    def view(self, uniforms, bias=0, max_bias=abi.VIEW_MAX_BIAS, budget=None, cull=True, draw_small_root=False, max_level=None, return_counts=False):
+        """The host mirror of simlod_query_view on the octree this FULL export was taken from: what the device returns for the camera of
+        `uniforms`, as an OctreeExport on the host (select "visible") — and, return_counts, the SimlodViewCounts record too, with the ladder
+        samplesAt.  numpy float32 throughout (view_geometry).  When no bias in [bias, max_bias] fits `budget`: ValueError — or,
+        return_counts, the table of max_bias without samples and counts whose error has abi.EXPORT_ERR_BUDGET, as the device leaves them."""
+        if not 0 <= int(bias) <= int(max_bias) <= abi.VIEW_MAX_BIAS:
+            raise ValueError("0 <= bias <= max_bias <= 20")
+        full = self.truncated(max_level, "all")                   # rule V1: the listed nodes, every one with its count
+        out, smp = full.nodes.copy(), full.samples
+        inside, _, _, rank = view_geometry(uniforms, out)
+        ns = out["numSamples"].astype(np.int64)
+        leaf = (out["flags"] & abi.EXPORT_FLAG_LEAF) != 0
+        visible = (inside | (not cull)) & (ns > 0)
+        par = out["parent"].astype(np.int64)
+        P = np.where(par == abi.EXPORT_NONE, abi.VIEW_MAX_BIAS + 1 if draw_small_root else 0, rank[np.where(par == abi.EXPORT_NONE, 0, par)])
+        b = np.arange(abi.VIEW_MAX_BIAS + 1)[:, None]
+        drawn = visible[None, :] & np.where(b < rank[None, :], leaf[None, :], b < P[None, :])            # rule V4, bias by node
+        ladder = (drawn * ns[None, :]).sum(axis=1)
+        limit = abi.VIEW_NO_BUDGET if budget is None else int(budget)
+        fits = [k for k in range(int(bias), int(max_bias) + 1) if int(ladder[k]) <= limit]
+        chosen = fits[0] if fits else int(max_bias)
+        if not fits and not return_counts:
+            raise ValueError(f"no bias in [{int(bias)}, {int(max_bias)}] fits {limit} samples (the coarsest holds {int(ladder[chosen])})")
+        sel = drawn[chosen]
+        out["flags"] = np.where(leaf, abi.EXPORT_FLAG_LEAF, 0) | np.where(sel, abi.EXPORT_FLAG_SELECTED, 0)
+        out["numSamples"] = np.where(sel, ns, 0)
+        out["firstSample"] = np.concatenate([[0], np.cumsum(np.where(sel, ns, 0))[:-1]]).astype(np.uint64)
+        samples = smp[np.repeat(sel, ns)] if fits else np.zeros(0, dtype=abi.point_dtype)
+        ex = OctreeExport(out, samples, self.box_min, self.box_max, full.max_level, abi.EXPORT_VISIBLE)
+        if not return_counts:
+            return ex
+        c = np.zeros((), dtype=abi.view_counts_dtype)
+        c["numNodes"], c["error"], c["numSamples"] = len(out), 0 if fits else abi.EXPORT_ERR_BUDGET, int(ladder[chosen])
+        c["bias"], c["numSelected"], c["numInside"], c["samplesAt"] = chosen, int(sel.sum()), int(visible.sum()), ladder
         return ex, c
 
     # -- ray queries (include/simlod_hip.h, "ray queries") -----------------------------------------------------------------------------------
@@ -462,6 +502,68 @@ def classify_nodes(planes, nodes, box_min, box_max):
         outside |= ((nx * fx + ny * fy) + nz * fz) + d < 0
         inside &= ((nx * gx + ny * gy) + nz * gz) + d >= 0
     return outside, inside
+
+
+def view_planes(transform):
+    """The six frustum planes of a view query (include/simlod_hip.h, "view queries": planes) from the 4 x 4 matrix, normalised: 6 x 4 float32."""
+    r = np.asarray(transform, dtype=np.float32).reshape(4, 4)
+    with np.errstate(all="ignore"):
+        P = np.stack([r[3] - r[0], r[3] + r[0], r[3] + r[1], r[3] - r[1], r[3] - r[2], r[3] + r[2]])
+        d2 = P[:, 0] * P[:, 0]
+        d2 = d2 + P[:, 1] * P[:, 1]
+        d2 = d2 + P[:, 2] * P[:, 2]
+        return P / np.sqrt(d2)[:, None]
+
+
+def view_geometry(uniforms, nodes):
+    """Rules V2 and V3 of the view query for every entry of a table (or any records with level, X, Y, Z) under the camera of `uniforms`:
+    (inside, dx, dy, rank) — does the node's cube meet the frustum of transform_updateBound, the float32 extents of its screen box, and R,
+    the number of biases 0..20 at which it is large.  numpy float32 in the header's operation order; fmin / fmax drop a NaN as fminf / fmaxf do."""
+    f = np.float32
+    u = np.asarray(uniforms).reshape(-1)[0]
+    M = np.asarray(u["transform_updateBound"], dtype=f).reshape(4, 4)
+    mn3, mx3 = np.asarray(u["boxMin"], dtype=f).reshape(3), np.asarray(u["boxMax"], dtype=f).reshape(3)
+    width, height = f(u["width"]), f(u["height"])
+    with np.errstate(all="ignore"):
+        planes = view_planes(M)
+        ext = mx3 - mn3
+        size = np.fmax(np.fmax(ext[0], ext[1]), ext[2])
+        s = (size / np.ldexp(f(1.0), nodes["level"].astype(np.int32))).astype(f)
+        A = [nodes[a].astype(f) for a in ("X", "Y", "Z")]
+        lo = [mn3[k] + (A[k] + f(0.0)) * s for k in range(3)]
+        hi = [mn3[k] + (A[k] + f(1.0)) * s for k in range(3)]
+        inside = np.ones(len(s), bool)
+        for nx, ny, nz, c in planes:
+            d = nx * (hi[0] if nx > 0 else lo[0])
+            d = d + ny * (hi[1] if ny > 0 else lo[1])
+            d = d + nz * (hi[2] if nz > 0 else lo[2])
+            d = d + c
+            inside &= ~(d < 0)
+
+        def dot(r, x, y, z):
+            t = r[0] * x
+            t = t + r[1] * y
+            t = t + r[2] * z
+            return t + r[3] * f(1.0)
+
+        sx, sy = [], []
+        for k in range(8):                      # p000, p001, p010, p011, p100, p101, p110, p111
+            x, y, z = (hi if k & 4 else lo)[0], (hi if k & 2 else lo)[1], (hi if k & 1 else lo)[2]
+            cw = dot(M[3], x, y, z)
+            sx.append(((dot(M[0], x, y, z) / cw) * f(0.5) + f(0.5)) * width)
+            sy.append(((dot(M[1], x, y, z) / cw) * f(0.5) + f(0.5)) * height)
+
+        def tree(op, v):
+            return op(op(op(v[0], v[1]), op(v[2], v[3])), op(op(v[4], v[5]), op(v[6], v[7])))
+
+        dx, dy = tree(np.fmax, sx) - tree(np.fmin, sx), tree(np.fmax, sy) - tree(np.fmin, sy)
+        assert dx.dtype == f and dy.dtype == f and s.dtype == f
+        lim = 2.0 * np.float64(f(u["minNodeSize"]))
+        rank = np.zeros(len(s), np.int64)
+        for b in range(abi.VIEW_MAX_BIAS + 1):
+            lb = np.ldexp(lim, b)
+            rank += (dx.astype(np.float64) > lb) | (dy.astype(np.float64) > lb)
+    return inside, dx, dy, rank
 
 
 class Region:

@@ -96,6 +96,7 @@ def lib():
         L.simlod_footprint_buffer_min_bytes.restype = u64
         L.simlod_footprint_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_query_footprint.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
+        L.simlod_query_view.argtypes = [vp, vp, vp, vp, u32, vp, u64, vp, u32, vp, u64, vp, vp]
         L.simlod_rays_buffer_min_bytes.restype = u64
         L.simlod_rays_buffer_min_bytes.argtypes = [u32, u64, u32, u64, u64]
         L.simlod_query_rays.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, u64, vp, u32, vp, vp, vp]
@@ -120,7 +121,7 @@ EXPORTED_SYMBOLS = [
     "simlod_export_buffer_min_bytes", "simlod_export_octree", "simlod_import_octree", "simlod_import_octree_buildable",
     "simlod_query_buffer_min_bytes", "simlod_query_region", "simlod_rays_buffer_min_bytes", "simlod_query_rays",
     "simlod_neighbours_buffer_min_bytes", "simlod_query_neighbours", "simlod_footprint_buffer_min_bytes", "simlod_query_footprint",
-    "simlod_context_set_clip", "simlod_set_clip",
+    "simlod_context_set_clip", "simlod_set_clip", "simlod_query_view",
 ]
 
 
@@ -686,6 +687,50 @@ class DeviceOctree:
         c = self._query(uniforms, region, ml, sel, table, samples, ns, bound, footprint)
         u = np.asarray(uniforms).reshape(-1)[0]
         ex = OctreeExport(table, samples[: int(c["numSamples"]) * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_REGION)
+        return (ex, c) if return_counts else ex
+
+    # -- view queries (include/simlod_hip.h, "view queries") -------------------------------------------------------------------------------
+    def _view(self, uniforms, view, ml, table, samples, sample_capacity, bound):
+        """One simlod_query_view call -> the SimlodViewCounts record (host).  samples None: count only.  SIMLOD_EXPORT_ERR_BUDGET is the
+        caller's to judge; any other error bit raises SimlodError."""
+        u, up = self._u(uniforms)
+        nn = table.numel() // abi.export_node_dtype.itemsize
+        counts = torch.zeros(abi.view_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        scratch = self._export_scratch(int(self.L.simlod_export_buffer_min_bytes(nn, bound)))
+        _check(self.L.simlod_query_view(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(view.ctypes.data), ml, self._p(scratch),
+                                        ctypes.c_uint64(scratch.numel()), self._p(table), nn, None if samples is None else self._p(samples),
+                                        ctypes.c_uint64(sample_capacity), self._p(counts), self._stream()), "simlod_query_view")
+        c = counts.cpu().numpy().view(abi.view_counts_dtype)[0]
+        if int(c["error"]) & ~abi.EXPORT_ERR_BUDGET:
+            raise SimlodError(f"simlod_query_view reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples)")
+        return c
+
+    def count_view(self, uniforms, bias=0, max_bias=abi.VIEW_MAX_BIAS, budget=None, cull=True, draw_small_root=False, max_level=None):
+        """What the camera of `uniforms` (width, height, transform_updateBound, minNodeSize, the box) would take from the octree: the
+        SimlodViewCounts record of a count-only simlod_query_view call — the chosen bias (the smallest in [bias, max_bias] whose cut holds at
+        most `budget` samples; error has abi.EXPORT_ERR_BUDGET when none does), numSamples, numSelected, numInside and the ladder samplesAt[b]
+        of every bias.  No frame is rendered, nothing is copied, the octree's frame state stays as it is."""
+        _, ml, nn, _ = self._query_setup(max_level, "all")
+        return self._view(uniforms, abi.view_record(bias, max_bias, budget, cull, draw_small_root), ml, self._table(nn), None, 0, 0)
+
+    def query_view(self, uniforms, bias=0, max_bias=abi.VIEW_MAX_BIAS, budget=None, cull=True, draw_small_root=False, max_level=None, return_counts=False):
+        """The cut the camera of `uniforms` needs as an octree_io.OctreeExport on this device (select abi.EXPORT_VISIBLE): what render(uniforms
+        with minNodeSize * 2^bias) followed by export_octree(select="visible") gives, without the frame.  A count-only call first, then the
+        outputs sized exactly.  When no bias in [bias, max_bias] fits `budget`: SimlodError — or, return_counts, the table of max_bias without
+        samples and counts whose error has abi.EXPORT_ERR_BUDGET."""
+        from .octree_io import OctreeExport
+        _, ml, nn, _ = self._query_setup(max_level, "all")
+        view = abi.view_record(bias, max_bias, budget, cull, draw_small_root)
+        c = self._view(uniforms, view, ml, self._table(nn), None, 0, 0)
+        if int(c["error"]) & abi.EXPORT_ERR_BUDGET and not return_counts:
+            raise SimlodError(f"simlod_query_view: no bias in [{int(bias)}, {int(max_bias)}] fits {int(budget)} samples (the coarsest holds {int(c['numSamples'])})")
+        nn, ns = int(c["numNodes"]), int(c["numSamples"])
+        table = torch.empty(nn * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        samples = torch.empty(max(ns, 1) * abi.point_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        c = self._view(uniforms, view, ml, table, samples, ns, ns)
+        written = 0 if int(c["error"]) & abi.EXPORT_ERR_BUDGET else int(c["numSamples"])
+        u = np.asarray(uniforms).reshape(-1)[0]
+        ex = OctreeExport(table, samples[: written * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_VISIBLE)
         return (ex, c) if return_counts else ex
 
     # -- pair queries: what the ray and the neighbour query share (csrc/export_pairs.inc) ------------------------------------------------------

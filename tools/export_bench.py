@@ -14,7 +14,10 @@ host mirror's median `within` (on the first 256 of them) is about 30, with k = 1
 --footprint: instead, simlod_query_footprint CUT@20 on the same octree — half the terrain (a triangle scaled so that about half the points
 pass) with its count-only call; the rectangle of 30-70 % x 20-90 % of the extents beside the same rectangle as a four-plane
 simlod_query_region, the two alternating rep by rep; the count-only calls of a 14-vertex and a 256-vertex star, alternating — and the
-device-to-device copy, all in this one run."""
+device-to-device copy, all in this one run.
+--view: instead, simlod_query_view on the same octree under bench.py's bird and close-up cameras at 1920 x 1080 — without a budget beside
+simlod_export_octree VISIBLE of the same frame into the same buffers, the two alternating rep by rep; the count-only call; the path the
+query replaces, simlod_launch_render + the VISIBLE export — and the device-to-device copy, all in this one run."""
 import argparse
 import ctypes
 import json
@@ -384,6 +387,72 @@ def neighbours_bench(dev, u, box, st, reps, pts):
     print(json.dumps(out))
 
 
+def view_bench(dev, u, box, st, reps):
+    from simlod_amd import fingerprint
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    need = int(L.simlod_export_buffer_min_bytes(nn, bound))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    table = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    samples = torch.empty(bound * 16, dtype=torch.uint8, device=dev.device)
+    counts = torch.zeros(abi.view_counts_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+    x_counts = torch.zeros(16, dtype=torch.uint8, device=dev.device)
+    W, H = 1920, 1080
+    # bench.py's "Morro Bay - bird" and "- close" (main_progressive_octree.cpp:1314-1328), scaled to the stand-in's box
+    cx, cy = 2750.218 * float(box[0]) / 6000.0, 974.775 * float(box[1]) / 4000.0
+    cams = {"bird": camera.world_view_proj(camera.orbit_view(-0.207, -0.797, 3866.886 * float(box[0]) / 6000.0, (box[0] / 2, box[1] / 2, 0.35 * box[2])),
+                                           camera.perspective(aspect=W / H)),
+            "close": camera.world_view_proj(camera.orbit_view(-11.270, -0.225, 93.982, (cx, cy, synthetic.terrain_height(cx, cy, seed=7, box=tuple(float(v) for v in box)))),
+                                            camera.perspective(aspect=W / H))}
+    view = abi.view_record()
+    copy_dst = torch.empty(int(st["numPoints"]) * 16, dtype=torch.uint8, device=dev.device)
+    copy_src = samples[: copy_dst.numel()]
+    t_copy = timed(lambda: copy_dst.copy_(copy_src), reps)
+    copy_gbs = 2 * copy_dst.numel() / (t_copy[0] * 1e6)
+    out = {"points": int(st["numPoints"]), "numNodes": nn, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(),
+           "d2d_copy": {"ms": round(t_copy[0], 4), "bytes": 2 * copy_dst.numel(), "GBs": round(copy_gbs, 1)}}
+    for name, T in cams.items():
+        uc = dev.uniforms(W, H, T, box, hqs=True)
+        uu, up = dev._u(uc)
+
+        def query(count_only=False):
+            rc = L.simlod_query_view(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(view.ctypes.data), 20, p(scratch), ctypes.c_uint64(need), p(table), nn,
+                                     None if count_only else p(samples), ctypes.c_uint64(bound), p(counts), stream)
+            assert rc == 0
+
+        def export_visible():
+            rc = L.simlod_export_octree(p(dev.nodes), p(dev.stats), 20, abi.EXPORT_VISIBLE, p(scratch), ctypes.c_uint64(need), p(table), nn, p(samples),
+                                        ctypes.c_uint64(bound), p(x_counts), stream)
+            assert rc == 0
+
+        def frame_and_export():
+            dev.render(uc)
+            export_visible()
+
+        dev.render(uc)                                                              # the frame the VISIBLE export describes
+        export_visible()
+        torch.cuda.synchronize()
+        xc = x_counts.cpu().numpy().view(abi.export_counts_dtype)[0].copy()
+        want_t, want_s = table.clone(), samples[: int(xc["numSamples"]) * 16].clone()
+        query()
+        torch.cuda.synchronize()
+        c = counts.cpu().numpy().view(abi.view_counts_dtype)[0].copy()
+        assert int(c["error"]) == 0 and int(xc["error"]) == 0 and int(c["numSamples"]) == int(xc["numSamples"]) and int(c["numNodes"]) == int(xc["numNodes"])
+        assert torch.equal(table, want_t) and torch.equal(samples[: want_s.numel()], want_s), "the view query is not the frame's VISIBLE export"
+        t_view, t_vis = timed_alternating([query, export_visible], reps)
+        t_count = timed(lambda: query(True), reps)
+        t_path = timed(frame_and_export, reps)
+        nbytes = 2 * int(c["numSamples"]) * 16 + nn * 40
+        out[name] = {"ms": round(t_view[0], 4), "ms_min": round(t_view[1], 4), "export_visible_ms": round(t_vis[0], 4), "export_visible_ms_min": round(t_vis[1], 4),
+                     "over_export_visible": round(t_view[0] / t_vis[0], 4), "bound": "t_view <= 1.10 * t_export_visible of the same run",
+                     "bound_held": bool(t_view[0] <= 1.10 * t_vis[0]), "count_only_ms": round(t_count[0], 4), "count_only_ms_min": round(t_count[1], 4),
+                     "render_plus_export_visible_ms": round(t_path[0], 4), "render_plus_export_over_view": round(t_path[0] / t_view[0], 4),
+                     "numSelected": int(c["numSelected"]), "numInside": int(c["numInside"]), "numSamples": int(c["numSamples"]),
+                     "samplesAt": [int(v) for v in c["samplesAt"][:12]], "algorithmic_bytes": nbytes, "GBs": round(nbytes / (t_view[0] * 1e6), 1),
+                     "frac_of_copy": round(nbytes / (t_view[0] * 1e6) / copy_gbs, 4)}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=36_000_000)
@@ -394,6 +463,7 @@ def main():
     ap.add_argument("--footprint", action="store_true", help="time simlod_query_footprint (half the terrain, a rectangle beside its four planes, two stars) instead")
     ap.add_argument("--rays", action="store_true", help="time simlod_query_rays (one pixel cone, 4 096 vertical rays) instead")
     ap.add_argument("--neighbours", action="store_true", help="time simlod_query_neighbours (4 096 queries, k = 1, 8, 16, count-only) instead")
+    ap.add_argument("--view", action="store_true", help="time simlod_query_view (bird and close-up cameras beside the VISIBLE export of the same frame, count-only) instead")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
     pts, box = synthetic.terrain(n_points, seed=7)
@@ -420,6 +490,8 @@ def main():
         return rays_bench(dev, u, box, st, args.reps, T, 1920, 1080)
     if args.neighbours:
         return neighbours_bench(dev, u, box, st, args.reps, pts)
+    if args.view:
+        return view_bench(dev, u, box, st, args.reps)
     L = dev.L
     need = int(L.simlod_export_buffer_min_bytes(nn, ns))
     scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
