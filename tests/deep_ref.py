@@ -1,5 +1,5 @@
 """Shared by tests/test_deep_io.py and tests/test_gpu_deep_octrees.py: octrees 13 and 20 levels deep, built by the port oracle, the query
-sets aimed at their deepest nodes, and the guards that keep a comparison on them from passing on nothing.
+sets, regions and footprints aimed at their deepest nodes, and the guards that keep a comparison on them from passing on nothing.
 
   D13   test_gpu_deep_paths.deep_case(11): four batches A to D, 562 000 points in the level-11 cell at the origin of a unit box; 161 nodes
         (the root, twelve times eight, 64 leaves at level 13);
@@ -12,10 +12,11 @@ sets aimed at their deepest nodes, and the guards that keep a comparison on them
 import numpy as np
 
 import cases
+import footprint_ref as fr
 from export_ref import export_host
 from region_ref import host_octree
 from simlod_amd import abi, camera, synthetic
-from simlod_amd.octree_io import OctreeExport, Rays, Region, Spheres, classify_nodes
+from simlod_amd.octree_io import Footprint, OctreeExport, Rays, Region, Spheres, classify_footprint, classify_nodes
 from test_gpu_deep_paths import SIZES, assert_input_arithmetic, deep_case
 
 CELL_LEVEL = 11
@@ -143,7 +144,7 @@ def assert_d20_shape(export, k, what):
     return e
 
 
-# ---- D13 / D13x: rays, spheres, regions ----------------------------------------------------------------------------------------------------
+# ---- D13 / D13x: rays, spheres, regions, footprints ----------------------------------------------------------------------------------------
 def _chosen(pts, n, seed):
     return pts[np.sort(np.random.RandomState(seed).choice(len(pts), n, replace=False))]
 
@@ -220,6 +221,58 @@ def assert_region_not_vacuous(export, region, level, what):
     return filtered, copied
 
 
+CLOSE_OFFSET = (3.0, -2.5, 2.5)          # of the eye from the middle of D13x's level-11 cell, in level-13 node sizes
+
+
+def close_cam(d, width=cases.W, height=cases.H):
+    """A camera a few level-13 node sizes from D13x's cell: at the cases' camera the whole cloud is one pixel."""
+    mid = d.origin + 0.5 * np.ldexp(d.size, -CELL_LEVEL)
+    return camera.lookat_transform(tuple(mid + np.asarray(CLOSE_OFFSET) * np.ldexp(d.size, -LEAF_LEVEL)), tuple(mid), width, height)
+
+
+def d13_footprints(d):
+    """{name: Footprint} for D13 / D13x, in the level-11 cell the points fill: a seven-pointed star around its centre; the xy face of
+    d13_regions' cell12 (the level-12 cell (1, 0, .), widened by two level-20 cells); footprint_ref's oblique triangle, a cell size across, at
+    the cell's centre."""
+    c11 = np.ldexp(d.size, -CELL_LEVEL)
+    c12, e = 0.5 * c11, np.ldexp(d.size, -abi.MAX_DEPTH)
+    mid = d.origin + 0.5 * c11
+    lo = d.origin + np.array([1.0, 0.0, 1.0]) * c12
+    uc = float(np.dot(fr.OBLIQUE_U[:3], mid) + fr.OBLIQUE_U[3])
+    vc = float(np.dot(fr.OBLIQUE_V[:3], mid) + fr.OBLIQUE_V[3])
+    out = {"star7": Footprint.from_xy(fr.star(mid[0], mid[1], 0.45 * c11, 0.15 * c11, 7)),
+           "cell12": Footprint.from_rect((lo[0] - 2.0 * e, lo[1] - 2.0 * e), (lo[0] + c12 + 2.0 * e, lo[1] + c12 + 2.0 * e)),
+           "oblique": Footprint([(uc - 0.35 * c11, vc - 0.25 * c11), (uc + 0.40 * c11, vc - 0.10 * c11), (uc - 0.05 * c11, vc + 0.35 * c11)], fr.OBLIQUE_U, fr.OBLIQUE_V)}
+    for key, f in out.items():
+        assert len(np.unique(f.vertices, axis=0)) == len(f), f"{d.name} {key}: two vertices are one fp32 point"
+    return out
+
+
+def footprint_classes(export, footprint, level, max_level=20, select="cut"):
+    """region_classes for a footprint, from classify_footprint (rules F2-F4): how many entries of level `level` with samples have a NEAR edge
+    and are filtered sample by sample, how many entries of any level are copied whole, and how many entries of that level are outside."""
+    t = export.truncated(max_level, select).nodes
+    near, corner = classify_footprint(footprint, t, export.box_min, export.box_max)
+    has = ((t["flags"] & abi.EXPORT_FLAG_SELECTED) != 0) & (t["numSamples"] > 0)
+    at = has & (t["level"] == level)
+    return int((at & near).sum()), int((has & ~near & corner).sum()), int((at & ~near & ~corner).sum())
+
+
+# Which of d13_footprints can copy a node whole.  The projected rectangle of a level-13 node is a quarter of the level-11 cell wide in plan
+# view and 0.375 of it in the oblique axes' u; the star's inner radius is 0.15 of the cell and the triangle is 0.75 wide at its base, so
+# neither holds a whole leaf, and a leaf is all that carries samples in a cut.  They are told from an empty answer by their outside leaves.
+D13_COPIES = {"star7": False, "cell12": True, "oblique": False}
+
+
+def assert_footprint_not_vacuous(export, footprint, level, what, copies=True):
+    """At least one filtered node with samples at `level`, and at least one node copied whole — or, for a footprint too narrow to hold a
+    node (copies=False), none copied and at least one node of that level outside."""
+    filtered, copied, outside = footprint_classes(export, footprint, level)
+    assert filtered >= 1 and (copied >= 1 if copies else copied == 0 and outside >= 1), \
+        f"{what}: {filtered} filtered and {outside} outside nodes at level {level}, {copied} copied nodes"
+    return filtered, copied
+
+
 def assert_hits_at_level(hits, table, level, what, share=0.9):
     hit = hits["node"] != NONE
     at = float((table["level"][hits["node"][hit]] == level).mean())
@@ -288,3 +341,33 @@ def d20_regions(export):
     return {"x>=below": (Region.from_planes([[1.0, 0.0, 0.0, -float(below)]]), "all"),
             "x>=above": (Region.from_planes([[1.0, 0.0, 0.0, -float(above)]]), "none"),
             "cell20": (Region.from_box(lo - 0.5 * cell, lo + 1.5 * cell), "all")}
+
+
+FRACTION_DECIDED = ("lo_x=x", "hi_x=x")           # the point lies ON a vertical edge of these: c == 0 exactly, for all k identical points
+
+
+def d20_footprints():
+    """{name: (Footprint, how many of the k identical points it keeps: 'all' or 'none')}: plan-view rectangles whose corners are fp32 numbers
+    (asserted: record() holds them unrounded).  `cell` is the level-20 cell of POINT with half a cell more on every side; the others have one
+    side at the point's own x or y, or one fp32 step from it, and take a share of the uniform points too.  Footprint.from_rect's convention
+    is lo_x <= x <= hi_x and lo_y <= y < hi_y."""
+    x, y = np.float32(POINT[0]), np.float32(POINT[1])
+    nxt = lambda v, to: float(np.nextafter(v, np.float32(to)))
+    x, y, x_below, x_above, y_above = float(x), float(y), nxt(x, 0.0), nxt(x, 1.0), nxt(y, 1.0)
+    cell = np.ldexp(1.0, -abi.MAX_DEPTH)
+    cx, cy = np.floor(x / cell) * cell, np.floor(y / cell) * cell
+    rects = {"cell": ((cx - 0.5 * cell, cy - 0.5 * cell), (cx + 1.5 * cell, cy + 1.5 * cell), "all"),
+             "lo_x=x": ((x, 0.125), (0.5, 0.875), "all"),
+             "lo_x=above": ((x_above, 0.125), (0.5, 0.875), "none"),
+             "hi_x=x": ((0.125, 0.125), (x, 0.875), "all"),
+             "hi_x=below": ((0.125, 0.125), (x_below, 0.875), "none"),
+             "lo_y=y": ((0.125, y), (0.5, 0.75), "all"),
+             "hi_y=y": ((0.125, 0.5), (0.5, y), "none"),
+             "hi_y=above": ((0.125, 0.5), (0.5, y_above), "all")}
+    out = {}
+    for key, (lo, hi, keeps) in rects.items():
+        f = Footprint.from_rect(lo, hi)
+        want = np.array([(lo[0], lo[1]), (lo[0], hi[1]), (hi[0], hi[1]), (hi[0], lo[1])], dtype=np.float64)
+        assert np.array_equal(f.record()["vertices"][0, :4].astype(np.float64), want), f"{key}: a corner is not an fp32 number"
+        out[key] = (f, keeps)
+    return out

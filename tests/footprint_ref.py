@@ -1,5 +1,7 @@
-"""Shared by the footprint-query tests: the footprints they use, placed relative to a case's box, and the two footprints of the 3 M-point
-terrain."""
+"""Shared by the footprint-query tests: the footprints they use, placed relative to a case's box, the two footprints of the 3 M-point
+terrain, the shifted inputs of the box-offset tests, and `contains_exact`, rule F1 with every edge's side decided exactly."""
+from fractions import Fraction
+
 import numpy as np
 
 from simlod_amd.octree_io import Footprint
@@ -7,6 +9,47 @@ from simlod_amd.octree_io import Footprint
 FOOTPRINT_NAMES = ["star7", "star128", "oblique", "rect", "cover", "miss", "bowtie"]
 SLOW_FOOTPRINTS = {"star128": ("ragged_tiny", "terrain_4x100k")}          # 256 edges: the numpy loop over them is the slow part
 OBLIQUE_U, OBLIQUE_V = (0.8, 0.6, 0.1, -3.0), (-0.6, 0.8, 0.2, 5.0)
+# footprints in a box off the origin (tests/test_gpu_box_origin.py, tests/test_footprint_io.py): the (case, offset) pairs of the region query's
+# test there, the footprints every pair gets, and the pairs that get the 256-edge star too
+SHIFTED = [("uniform_3x40k", "inexact"), ("terrain_4x100k", "georef"), ("hotspot_150k", "dyadic"), ("terrain_4x100k", "inexact")]
+SHIFTED_KINDS = ["star7", "oblique", "rect", "bowtie", "miss"]
+SHIFTED_STAR128 = ("uniform_3x40k", "hotspot_150k")
+SURE = 2.0 ** -50
+
+
+def contains_exact(footprint, points, return_decided=False):
+    """Rule F1 with the EXACT sign of c = du * (v - a_v) - dv * (u - a_u) per edge, for the fp64 (u, v) of Footprint.project (the header's
+    operation order, taken as data) and the fp64 edge values of Footprint.edges.
+
+    Per point and edge p = du * (v - a_v), q = dv * (u - a_u) and c = p - q in fp64 carry five roundings of at most 2^-53 each (the two
+    differences, the two products, the last difference): the error of c is below 2^-51 (|p| + |q|), so where |c| > 2^-50 (|p| + |q|) the
+    fp64 sign is the exact one.  A point with an edge that crosses its v and is not decided that way is decided edge by edge in
+    fractions.Fraction on the same fp64 values, once per distinct (u, v).
+    -> a boolean per point; return_decided: and a boolean per point, whether Fractions decided it."""
+    p = np.asarray(points)
+    u, v = footprint.project(*(p[a].astype(np.float64) for a in ("x", "y", "z")))
+    if not (np.isfinite(u).all() and np.isfinite(v).all()):
+        raise ValueError("a projected coordinate is not finite: the exact rule has no side for it")
+    edges = list(zip(*footprint.edges()))
+    odd, hard = np.zeros(len(p), bool), np.zeros(len(p), bool)
+    for a_u, a_v, b_v, du, dv in edges:
+        pp, qq = du * (v - a_v), dv * (u - a_u)
+        c = pp - qq
+        sure = np.abs(c) > SURE * (np.abs(pp) + np.abs(qq))
+        crosses = (a_v > v) != (b_v > v)
+        odd ^= crosses & sure & ((c > 0) == (dv > 0))
+        hard |= crosses & ~sure
+    if hard.any():
+        uv, inverse = np.unique(np.stack([u[hard], v[hard]], axis=1), axis=0, return_inverse=True)
+        verdict = np.zeros(len(uv), bool)
+        for k, (uk, vk) in enumerate(uv):
+            fu, fv = Fraction(float(uk)), Fraction(float(vk))
+            for a_u, a_v, b_v, du, dv in edges:
+                if (a_v > vk) != (b_v > vk):
+                    c = Fraction(float(du)) * (fv - Fraction(float(a_v))) - Fraction(float(dv)) * (fu - Fraction(float(a_u)))
+                    verdict[k] ^= (c > 0) == (dv > 0)
+        odd[hard] = verdict[inverse.reshape(-1)]
+    return (odd, hard) if return_decided else odd
 
 
 def star(cx, cy, r0, r1, n):

@@ -1,9 +1,13 @@
 """CPU tier: the preconditions of tests/test_gpu_deep_octrees.py, from the oracle, the mirrors of simlod_amd/octree_io.py and brute force alone —
 octrees 13 and 20 levels deep (tests/deep_ref.py) are what they are said to be, the mirrors' cuts, casts, neighbour searches, crops and
-rebuilt grids hold on them, and every query set reaches the deepest nodes."""
+rebuilt grids hold on them, and every query set reaches the deepest nodes.  Footprints are held against footprint_ref.contains_exact, rule F1
+with every edge's side decided exactly: on these inputs it agrees with the fp64 formula on every point, so the crops equal both filters."""
 import numpy as np
 import pytest
 
+import cases
+import clip_ref
+import footprint_ref as fr
 import neighbours_ref as nr
 import rays_ref as yr
 import region_ref as rr
@@ -11,7 +15,9 @@ import deep_ref as dr
 from export_ref import entry_index, export_host
 from resume_ref import grid_of_image, rebuild_grids
 from simlod_amd import abi
+from simlod_amd.octree_io import Region
 from test_gpu_deep_paths import CELL_LEVELS, OFF_ORIGIN_MARGIN, assert_input_arithmetic, deep_case
+from util import node_keys, oracle_frame
 
 NONE = abi.EXPORT_NONE
 
@@ -163,6 +169,47 @@ def test_d13_regions_equal_the_brute_force_filter(built_libs):
         crop.validate()
 
 
+# the input points inside each footprint of deep_ref.d13_footprints, and how many of them contains_exact decided in Fractions
+D13_INSIDE = {"d13": {"star7": 114_655, "cell12": 142_863, "oblique": 113_429}, "d13x": {"star7": 114_537, "cell12": 140_826, "oblique": 114_155}}
+D13_FRACTIONS = {"d13": {"star7": 0, "cell12": 0, "oblique": 0}, "d13x": {"star7": 1, "cell12": 23, "oblique": 0}}
+
+
+@pytest.mark.parametrize("name", ["d13", "d13x"])
+def test_d13_footprints_equal_the_exact_brute_force_filter(built_libs, name):
+    d = dr.built(name)
+    for key, f in dr.d13_footprints(d).items():
+        filtered, copied = dr.assert_footprint_not_vacuous(d.export, f, dr.LEAF_LEVEL, f"{name} {key}", dr.D13_COPIES[key])
+        inside = f.contains(d.pts)
+        exact, decided = fr.contains_exact(f, d.pts, return_decided=True)
+        print(name, key, f"{filtered} filtered at level 13, {copied} copied, {int(inside.sum())} points inside, {int(decided.sum())} decided in Fractions")
+        assert np.array_equal(inside, exact), f"{name} {key}: rule F1 in fp64 and the exact rule disagree on {int((inside != exact).sum())} points"
+        assert int(inside.sum()) == D13_INSIDE[name][key] and int(decided.sum()) == D13_FRACTIONS[name][key]
+        crop, cnt = d.export.crop(Region(), 20, "cut", return_counts=True, footprint=f)
+        assert int(cnt["numFilteredNodes"]) >= filtered and int(cnt["numCopiedNodes"]) == copied
+        rr.assert_same_multiset(crop.samples, d.pts[exact], f"{name} {key}")
+        crop.validate()
+    # composed with the slab of d13_regions: outside by either, copied iff copied by both
+    f, slab = dr.d13_footprints(d)["star7"], dr.d13_regions(d)["slab"]
+    both = fr.contains_exact(f, d.pts) & rr.brute_mask(slab, d.pts)
+    assert 0 < both.sum() < min(int(fr.contains_exact(f, d.pts).sum()), int(rr.brute_mask(slab, d.pts).sum()))
+    crop = d.export.crop(slab, 20, "cut", footprint=f)
+    rr.assert_same_multiset(crop.samples, d.pts[both], f"{name} star7 and slab")
+
+
+def test_d13x_close_up_lists_level_13_nodes_of_every_clip_class(built_libs):
+    """What the clip tests of tests/test_gpu_deep_octrees.py rest on, from the oracle's own image and rasteriser: under the close camera the
+    unclipped visible list is 57 nodes, 56 of them at level 13, and every region of d13_regions leaves some of those outside, filters some
+    and copies some."""
+    d = dr.built("d13x")
+    u = cases.uniforms_for(d.box, dr.close_cam(d))
+    fb, _, st, vis = oracle_frame(d.ho.nodes, d.nn, u)
+    assert len(vis) == 57 and int((vis["level"] == dr.LEAF_LEVEL).sum()) == 56 and int((fb != abi.CLEAR_PIXEL).sum()) == 53_638
+    want = {"cell12": [30, 18, 8], "slab": [8, 33, 15], "frustum": [4, 32, 20]}
+    for key, region in dr.d13_regions(d).items():
+        cls = clip_ref.node_classes(vis, len(vis), region, u)[vis["level"] == dr.LEAF_LEVEL]
+        assert [int((cls == c).sum()) for c in (clip_ref.OUTSIDE, clip_ref.FILTERED, clip_ref.COPIED)] == want[key], key
+
+
 # ---- D20 queries -------------------------------------------------------------------------------------------------------------------------------
 def test_d20_rays_through_the_point_hit_the_first_of_the_identical_samples(built_libs):
     d = dr.built("d20")
@@ -251,6 +298,60 @@ def test_d20_regions_keep_all_of_the_identical_samples_or_none(built_libs):
     # level is three cells wide
     f, c = dr.region_classes(d.export, dr.d20_regions(d.export)["x>=below"][0], abi.MAX_DEPTH)
     assert f == 1 and c >= 1
+
+
+def test_d20_footprints_keep_all_of_the_identical_samples_or_none(built_libs):
+    d = dr.built("d20")
+    e, k = dr.deep_entry(d.export)
+    same = (d.pts["x"] == np.float32(dr.POINT[0])) & (d.pts["y"] == np.float32(dr.POINT[1])) & (d.pts["z"] == np.float32(dr.POINT[2]))
+    assert int(same.sum()) == k == d.k
+    prints = dr.d20_footprints()
+    assert sorted(key for key, (f, keeps) in prints.items() if keeps == "none") == ["hi_x=below", "hi_y=y", "lo_x=above"]
+    for key, (f, keeps) in prints.items():
+        inside = f.contains(d.pts)
+        exact, decided = fr.contains_exact(f, d.pts, return_decided=True)
+        print(key, f"keeps {int((inside & same).sum())} of the identical points, {int((inside & ~same).sum())} of the others; {int(decided.sum())} decided in Fractions")
+        assert np.array_equal(inside, exact), f"{key}: rule F1 in fp64 and the exact rule disagree on {int((inside != exact).sum())} points"
+        assert int((exact & same).sum()) == (k if keeps == "all" else 0), key
+        # on a vertical edge through the point c is 0: all k points are decided in Fractions, and are one (u, v)
+        assert int(decided.sum()) == (k if key in dr.FRACTION_DECIDED else 0) and not (decided & ~same).any(), key
+        # an empty answer is no match: every boundary rectangle keeps some of the uniform points too, the cell keeps none
+        others = int((exact & ~same).sum())
+        assert others == 0 if key == "cell" else others >= 2000, (key, others)
+        # the level-20 node is filtered sample by sample: inflated by one level-20 cell, it is cut by an edge of every rectangle
+        assert dr.footprint_classes(d.export, f, abi.MAX_DEPTH)[0] == 1, key
+        for select in ("cut", "all"):
+            crop, cnt = d.export.crop(Region(), 20, select, return_counts=True, footprint=f)
+            deep = crop.nodes[(crop.nodes["level"] == abi.MAX_DEPTH) & (crop.nodes["numSamples"] > 0)]
+            assert (len(deep) == 1 and int(deep["numSamples"][0]) == k) if keeps == "all" else len(deep) == 0, (key, select)
+            crop.validate()
+        crop = d.export.crop(Region(), 20, "cut", footprint=f)
+        rr.assert_same_multiset(crop.samples, d.pts[exact], key)
+        # ... and without the identical points, which the oracle counts and does not store
+        rr.assert_same_multiset(crop.samples[(crop.samples["x"] != np.float32(dr.POINT[0])) | (crop.samples["y"] != np.float32(dr.POINT[1]))], d.pts[exact & ~same], key)
+        if key == "cell":
+            assert crop.num_samples == k
+    # one of them with the half-space x >= the fp32 below the point's x: still all k
+    both, _ = dr.d20_regions(d.export)["x>=below"]
+    crop = d.export.crop(both, 20, "cut", footprint=prints["hi_x=x"][0])
+    want = fr.contains_exact(prints["hi_x=x"][0], d.pts) & rr.brute_mask(both, d.pts)
+    assert int((want & same).sum()) == k and int((want & ~same).sum()) == 0
+    rr.assert_same_multiset(crop.samples, d.pts[want], "hi_x=x and x>=below")
+
+
+def test_d20_leaf_is_listed_only_without_a_minimum_node_size(built_libs):
+    """A level-20 node is 2^-20 of the box, a ten-thousandth of a pixel under the cases' camera: the oracle's visibility pass lists the leaf
+    only with minNodeSize 0, where every node with a nonzero extent on screen counts as large.  (showPoints 0: the oracle keeps the leaf's
+    count and no chunks, so its own image cannot be drawn there; the clip test draws the device's.)"""
+    d = dr.built("d20")
+    leaf = node_keys(d.ho.nodes[dr.deep_leaf(d.ho):][:1])[0]
+    listed = {}
+    for size in (64.0, 1.0, 0.0):
+        u = cases.uniforms_for(d.box, cases._cam(d.box))
+        u["minNodeSize"], u["showPoints"] = size, 0
+        vis = oracle_frame(d.ho.nodes, d.nn, u)[3]
+        listed[size] = bool((node_keys(vis) == leaf).any())
+    assert listed == {64.0: False, 1.0: False, 0.0: True}, listed
 
 
 # ---- grids ----------------------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,7 @@
 """CPU tier: footprint queries (include/simlod_hip.h, "footprint queries") — the ABI struct, octree_io.Footprint, classify_footprint and the
-host mirror OctreeExport.crop(footprint=) against a brute-force filter of the input points, on octrees built by the oracle's port."""
+host mirror OctreeExport.crop(footprint=) against a brute-force filter of the input points, on octrees built by the oracle's port, at the
+origin and in the shifted boxes of tests/test_gpu_box_origin.py; there the filter is footprint_ref.contains_exact as well, rule F1 with every
+edge's side decided exactly."""
 import os
 import re
 
@@ -208,6 +210,61 @@ def test_rect_footprint_against_the_box_region(built):
     assert a.num_samples > 0 or "hotspot" in name
     rr.assert_same_multiset(a.samples, b.samples, f"{name} rect")
     rr.assert_same_multiset(a.samples, pts[rr.brute_mask(r, pts)], f"{name} rect, brute force")
+
+
+# ---- a box off the origin: the inputs of tests/test_gpu_box_origin.py ----------------------------------------------------------------------
+@pytest.mark.parametrize("name,offset", fr.SHIFTED)
+def test_footprints_in_a_box_off_the_origin(name, offset):
+    """The oracle's octree of a shifted case: the crop is the brute-force filter by Footprint.contains and by contains_exact alike (they agree on
+    every point), every footprint filters a node at the deepest level, and star7 composes with the slab."""
+    off = cases.offset_of(offset, cases.case(name)[1])
+    ex, pts, box, ho = rr.host_octree(name, box_min=off)
+    box_min = ex.box_min
+    assert box_min == tuple(float(np.float32(v)) for v in off)
+    deepest = int(ex.nodes["level"].max())
+    has = ex.truncated(20, "cut").nodes["numSamples"] > 0
+    copied = {}
+    for kind in fr.SHIFTED_KINDS:
+        f = fr.footprint(kind, box, box_min)
+        inside = f.contains(pts)
+        exact, decided = fr.contains_exact(f, pts, return_decided=True)
+        assert np.array_equal(inside, exact), f"{name}@{offset} {kind}: rule F1 in fp64 and the exact rule disagree on {int((inside != exact).sum())} points"
+        c, cnt = ex.crop(Region(), 20, "cut", return_counts=True, footprint=f)
+        c.validate()
+        rr.assert_same_multiset(c.samples, pts[exact], f"{name}@{offset} {kind}")
+        near, corner = classify_footprint(f, ex.nodes, ex.box_min, ex.box_max)
+        print(name, offset, kind, {k: int(cnt[k]) for k in cnt.dtype.names}, f"{int(inside.sum())} inside, {int(decided.sum())} decided in Fractions")
+        if kind == "miss":
+            assert not inside.any() and [int(cnt[k]) for k in cnt.dtype.names] == [1, 0, 0, 0, 0, 0]
+        else:
+            assert 0 < inside.sum() < len(pts), (name, kind)
+            assert (has & near & (ex.nodes["level"] == deepest)).any(), f"{name}@{offset} {kind}: no filtered node at level {deepest}"
+            assert int(cnt["numFilteredNodes"]) >= 1 and int(cnt["numCopiedNodes"]) == int((has & ~near & corner).sum()), (name, kind)
+            copied[kind] = int(cnt["numCopiedNodes"])
+    # these octrees are two to four levels deep: only the hotspot's leaves are small enough to lie inside a footprint (the rectangle) whole.
+    # tests/test_deep_io.py has footprints that copy nodes at level 13
+    assert copied["rect"] >= 1 or name != "hotspot_150k", copied
+    f, r = fr.footprint("star7", box, box_min), rr.region("slab", box, box_min)
+    both = fr.contains_exact(f, pts) & rr.brute_mask(r, pts)
+    assert 0 < both.sum() < min(f.contains(pts).sum(), rr.brute_mask(r, pts).sum()) or "hotspot" in name
+    rr.assert_same_multiset(ex.crop(r, 20, "cut", footprint=f).samples, pts[both], f"{name}@{offset} star7 and slab")
+
+
+def test_the_exact_path_is_not_dead():
+    """At the georef offset one fp32 step is 1/32 m in x and 0.25 m in y: input points lie ON edges of the rectangle and the bowtie, where c is 0
+    or too close for fp64, and Fractions decide them — the same way as the fp64 formula."""
+    pts, box_min, box, _ = cases.shifted("terrain_4x100k", cases.GEOREF)
+    for kind, n in (("rect", 31), ("bowtie", 28)):
+        f = fr.footprint(kind, box, box_min)
+        exact, decided = fr.contains_exact(f, pts, return_decided=True)
+        assert np.array_equal(exact, f.contains(pts)), kind
+        assert int(decided.sum()) == n, (kind, int(decided.sum()))
+    # a point on a rectangle's edges by from_rect's convention: lo_x <= x <= hi_x, lo_y <= y < hi_y
+    r = Footprint.from_rect((1, 2), (3, 4))
+    on = _pts([(1, 3, 0), (3, 3, 0), (2, 2, 0), (2, 4, 0), (1, 2, 0), (3, 4, 0), (2, 3, 0), (0.5, 3, 0)])
+    exact, decided = fr.contains_exact(r, on, return_decided=True)
+    assert exact.tolist() == [True, True, True, False, True, False, True, False] and np.array_equal(exact, r.contains(on))
+    assert decided.tolist() == [True, True, False, False, True, False, False, False]
 
 
 @pytest.fixture(scope="module")

@@ -1,18 +1,20 @@
 """GPU tier: an octree whose box does not start at the origin (Uniforms.boxMin != 0).  The reference's kernels honour boxMin everywhere, its
 host always sends 0; this library is an ABI for other hosts, and every kernel family reads boxMin: the builder's quantisation and voxel
 centres, the node boxes of the frame, the debug lines, the colour filter, the grid rebuild of the buildable import, the plane geometry of
-region queries.  Here the whole chain runs on shifted inputs (tests/cases.py: dyadic, inexact, georef) against the oracle on the same inputs /
+region queries, the projected node rectangles of footprint queries.  Here the whole chain runs on shifted inputs (tests/cases.py: dyadic, inexact, georef) against the oracle on the same inputs /
 the same downloaded image, by the comparisons of the suites for the origin box.  Every case that builds on small inputs also shows that it
 can tell "honours boxMin" from "ignores it": the oracle, given the same points in the box [0, boxMax], builds another octree."""
 import numpy as np
 import pytest
 
 import cases
+import footprint_ref as fr
 import oracle
 import region_ref as rr
+import test_gpu_footprint as on_footprints
 from export_ref import export_host
 from simlod_amd import abi, camera, synthetic
-from simlod_amd.octree_io import OctreeExport
+from simlod_amd.octree_io import OctreeExport, Region
 from test_gpu_export import _assert_export, _variants
 from test_gpu_groups import _drive
 from test_gpu_parity import GRANULARITY_FREE_FIELDS, GRANULARITY_FREE_STATS, _device, _ingest
@@ -454,3 +456,51 @@ def test_query_region_in_a_box_off_the_origin(built_libs, name, offset):
         if kind in ("oblique", "box"):
             ign = dev.count_region(cases.origin_box_uniforms(u), r)
             assert [int(ign[f]) for f in COUNT_FIELDS] != [int(c[f]) for f in COUNT_FIELDS]
+
+
+# ---- footprint queries -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,offset", fr.SHIFTED)
+def test_query_footprint_in_a_box_off_the_origin(built_libs, name, offset):
+    """simlod_query_footprint on shifted octrees, the footprints placed relative to the shifted box: byte-equal to the host mirror
+    OctreeExport.crop(footprint=) at full depth, one level cut and with the inner nodes' voxels, from the builder's chunk table and from walked
+    lists; multiset-equal to the input filtered by footprint_ref.contains_exact; the count-only call consistent.  At the georef offset one
+    fp32 step in y is 0.25 m, and the node rectangles (boxMin + X * size) - e and the fp64 edge products are six orders larger than at the
+    origin."""
+    off = cases.offset_of(offset, cases.case(name)[1])
+    pts, box_min, box, batch = cases.shifted(name, off)
+    dev = _device(persistent_bytes=2 << 30)
+    u = dev.uniforms(W, H, cases.shifted_cam(box, off), box, box_min=box_min)
+    dev.reset(u)
+    _feed(dev, u, cases.batches_of(name, pts, batch))
+    assert int(dev.read_stats()["dbg"]) == 0
+    full = dev.export_octree(u)
+    assert full.box_min == box_min
+    prints = {kind: fr.footprint(kind, box, box_min) for kind in fr.SHIFTED_KINDS + (["star128"] if name in fr.SHIFTED_STAR128 else [])}
+    slab = rr.region("slab", box, box_min)
+    modes = (("cut", 20), ("cut", 2), ("all", 20))
+    crops = {(kind, sel, ml): full.crop(Region(), ml, sel, return_counts=True, footprint=f) for kind, f in prints.items() for sel, ml in modes}
+    crops["star7+slab", "cut", 20] = full.crop(slab, 20, "cut", return_counts=True, footprint=prints["star7"])
+    for source in ("chunk table", "walk"):
+        for (kind, sel, ml), (mirror, cnt) in crops.items():
+            f, r = (prints["star7"], slab) if kind == "star7+slab" else (prints[kind], None)
+            on_footprints._assert_matches(on_footprints.Raw(dev, u, f, r, ml, sel), mirror, cnt, f"{name}@{offset} {kind} {sel}@{ml} ({source})")
+        dev.L.simlod_octree_image_replaced(dev._p(dev.nodes))        # the builder's chunk table no longer counts: every list is walked
+    for kind, f in prints.items():
+        exact = fr.contains_exact(f, pts)
+        if kind == "miss":
+            assert not exact.any()
+        else:
+            assert exact.any() and not exact.all(), "the footprint must cut the cloud"
+        mirror, cnt = crops[kind, "cut", 20]
+        ex, c = dev.query_region(u, Region(), return_counts=True, footprint=f)
+        assert ex.nodes.tobytes() == mirror.nodes.tobytes() and ex.samples.tobytes() == mirror.samples.tobytes()
+        rr.assert_same_multiset(ex.samples, pts[exact], f"{name}@{offset} {kind}")
+        cc = dev.count_region(u, Region(), footprint=f)
+        assert [int(cc[k]) for k in COUNT_FIELDS] == [int(c[k]) for k in COUNT_FIELDS] == [int(cnt[k]) for k in COUNT_FIELDS]
+        # the same footprint against the origin box is another answer (or none): the query reads boxMin
+        if kind in ("star7", "rect"):
+            ign = dev.count_region(cases.origin_box_uniforms(u), Region(), footprint=f)
+            assert [int(ign[k]) for k in COUNT_FIELDS] != [int(c[k]) for k in COUNT_FIELDS]
+    both = fr.contains_exact(prints["star7"], pts) & rr.brute_mask(slab, pts)
+    assert both.any()
+    rr.assert_same_multiset(crops["star7+slab", "cut", 20][0].samples, pts[both], f"{name}@{offset} star7 and slab")

@@ -1,38 +1,41 @@
-"""GPU tier: export, import, buildable import, resumed ingest and the region, ray and neighbour queries on octrees 13 and 20 levels deep
-(tests/deep_ref.py), where every suite before this one stopped at about level 4.  The device octrees are built once per module; each test
-asserts its precondition from the oracle, the mirrors and brute force (tests/test_deep_io.py states them on the CPU) and then compares:
-export == the host restatement on the downloaded image == the oracle's export; import == source; resume == the continuous build; queries ==
-the mirror on the device's own export == brute force over the raw input.  All comparisons are equalities."""
+"""GPU tier: export, import, buildable import, resumed ingest, the region, ray, neighbour and footprint queries and clip regions on octrees 13
+and 20 levels deep (tests/deep_ref.py), where every suite before this one stopped at about level 4.  The device octrees are built once per
+module; each test asserts its precondition from the oracle, the mirrors and brute force (tests/test_deep_io.py states them on the CPU) and
+then compares: export == the host restatement on the downloaded image == the oracle's export; import == source; resume == the continuous
+build; queries == the mirror on the device's own export == brute force over the raw input (footprints: footprint_ref.contains_exact, rule F1
+with exact signs); clipped frames == the oracle's rasteriser on the image edited by tests/clip_ref.py.  All comparisons are equalities, but
+for the RGBA8 of a frame after EDL (within 1 per channel, util.assert_frame_equals_oracle)."""
 import numpy as np
 import pytest
 
 import cases
+import clip_ref
 import deep_ref as dr
+import footprint_ref as fr
 import neighbours_ref as nr
 import oracle
 import rays_ref as yr
 import region_ref as rr
+import test_gpu_clip as on_clips
+import test_gpu_footprint as on_footprints
 import test_gpu_neighbours as on_spheres
 import test_gpu_rays as on_rays
 import test_gpu_region as on_regions
-from simlod_amd import abi, camera
-from simlod_amd.octree_io import OctreeExport
+from simlod_amd import abi
+from simlod_amd.octree_io import Clip, OctreeExport, Region
 from test_gpu_export import _assert_export, _device, _frames_equal, _host_export
 from test_gpu_resume import (RESUME_FIELDS, _assert_fields, _assert_stats, _check_import, _export_through_file, _feed, _import,
                              _resume_batches)
-from util import assert_frame_equals_oracle, assert_stats_equal, host_image_of
+from util import assert_frame_equals_oracle, assert_stats_equal, host_image_of, node_keys
 
 pytestmark = pytest.mark.gpu
 W, H = cases.W, cases.H
 NONE = abi.EXPORT_NONE
-CLOSE_OFFSET = (3.0, -2.5, 2.5)          # of the eye from the middle of D13x's level-11 cell, in level-13 node sizes
 _DEV, _MIRROR = {}, {}
 
 
 def _close_cam(d):
-    """A camera a few level-13 node sizes from D13x's cell: at the cases' camera the whole cloud is one pixel."""
-    mid = d.origin + 0.5 * np.ldexp(d.size, -dr.CELL_LEVEL)
-    return camera.lookat_transform(tuple(mid + np.asarray(CLOSE_OFFSET) * np.ldexp(d.size, -dr.LEAF_LEVEL)), tuple(mid), W, H)
+    return dr.close_cam(d, W, H)
 
 
 def _frame_floor(name):
@@ -62,6 +65,9 @@ def _release(built_libs):
     yield
     _DEV.clear()
     _MIRROR.clear()
+    for cache in (on_clips._MIRRORS, on_clips._UNCLIPPED):          # the clipped images of this module's octrees
+        for k in [k for k in cache if k[0][0].startswith(("d13x", "d20"))]:
+            del cache[k]
 
 
 def _assert_shape(name, export, what):
@@ -303,18 +309,36 @@ def _assert_region(dev, u, full, region, sel, what):
     return mirror
 
 
+def _assert_footprint(dev, u, full, footprint, sel, what, region=None, ml=20):
+    mirror, cnt = full.crop(Region() if region is None else region, ml, sel, return_counts=True, footprint=footprint)
+    raw = on_footprints.Raw(dev, u, footprint, region, ml, sel)
+    on_footprints._assert_matches(raw, mirror, cnt, what)
+    only = on_footprints.Raw(dev, u, footprint, region, ml, sel, count_only=True)
+    assert only.rc == 0 and _count_fields(only.counts) == _count_fields(cnt), f"{what}: the count-only call"
+    return mirror
+
+
+def _deep_samples(mirror):
+    """The level-20 entries of a crop that hold samples."""
+    return mirror.nodes[(mirror.nodes["level"] == abi.MAX_DEPTH) & (mirror.nodes["numSamples"] > 0)]
+
+
 def _query_once(name, dev, u, full, what):
-    """One ray set and one sphere set on another device object that holds the octree `full` was exported from."""
+    """One ray set, one sphere set and one footprint on another device object that holds the octree `full` was exported from."""
     if name.startswith("d13"):
         d = dr.built(name)
         _assert_rays(dev, u, full, dr.d13_rays(d)["thin"][0], "cut", f"{what} thin rays")
         _assert_spheres(dev, u, full, dr.d13_spheres(d)["r-15"], dr.SPHERE_K, "cut", f"{what} spheres")
+        mirror = _assert_footprint(dev, u, full, dr.d13_footprints(d)["cell12"], "cut", f"{what} footprint")
+        assert 0 < mirror.num_samples < full.truncated(20, "cut").num_samples
     else:
         e, n = dr.deep_entry(full)
         hits, _ = _assert_rays(dev, u, full, dr.d20_rays()[0], "cut", f"{what} rays")
         assert (hits["node"][:-1] == e).all() and (hits["ordinal"][:-1] == 0).all()
         nb, within = _assert_spheres(dev, u, full, dr.d20_spheres(), dr.SPHERE_K, "cut", f"{what} spheres")
         assert (nb["node"] == e).all() and within[0] == n
+        deep = _deep_samples(_assert_footprint(dev, u, full, dr.d20_footprints()["lo_x=x"][0], "cut", f"{what} footprint"))
+        assert len(deep) == 1 and int(deep["numSamples"][0]) == n
 
 
 @pytest.mark.parametrize("name", ["d13", "d13x"])
@@ -415,3 +439,135 @@ def test_regions_at_the_level_20_leaf(built_libs):
             assert (len(deep) == 1 and int(deep["numSamples"][0]) == k) if keeps == "all" else len(deep) == 0, (key, sel)
             if sel == "cut":
                 rr.assert_same_multiset(mirror.samples, d.pts[rr.brute_mask(region, d.pts)], key)
+
+
+# ---- 6. footprints -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["d13", "d13x"])
+def test_footprints_across_level_13(built_libs, name):
+    """Per footprint of dr.d13_footprints: nodes of level 13 are filtered (and, cell12, copied whole) by the ORACLE's export; then the device
+    == the mirror on its own export, the cut == the input filtered by the exact rule F1, the count-only call agrees.  In D13x a level-13
+    node is 1 wide at coordinates near 5 000: the rectangle (boxMin + X * size) - e has its inflation e = 2^-7 at the 20th bit."""
+    b = _built(name)
+    d = b.d
+    prints = dr.d13_footprints(d)
+    for key, f in prints.items():
+        dr.assert_footprint_not_vacuous(d.export, f, dr.LEAF_LEVEL, f"{name} {key}", dr.D13_COPIES[key])
+        mirror = _assert_footprint(b.dev, b.u, b.full, f, "cut", f"{name} {key} cut")
+        rr.assert_same_multiset(mirror.samples, d.pts[fr.contains_exact(f, d.pts)], f"{name} {key}")
+        _assert_footprint(b.dev, b.u, b.full, f, "all", f"{name} {key} all")
+    slab = dr.d13_regions(d)["slab"]
+    mirror = _assert_footprint(b.dev, b.u, b.full, prints["star7"], "cut", f"{name} star7 and slab", region=slab)
+    both = fr.contains_exact(prints["star7"], d.pts) & rr.brute_mask(slab, d.pts)
+    assert 0 < both.sum() < min(int(fr.contains_exact(prints["star7"], d.pts).sum()), int(rr.brute_mask(slab, d.pts).sum()))
+    rr.assert_same_multiset(mirror.samples, d.pts[both], f"{name} star7 and slab")
+
+
+def test_footprints_at_the_level_20_leaf(built_libs):
+    """Rectangles with a side at the point's own fp32 x or y, or one step from it (Footprint.from_rect keeps lo_x <= x <= hi_x, lo_y <= y <
+    hi_y): the level-20 entry comes back with all k samples or not at all."""
+    b = _built("d20")
+    d = b.d
+    e, k = dr.deep_entry(d.export)
+    prints = dr.d20_footprints()
+    assert k == d.k and all(dr.footprint_classes(d.export, f, abi.MAX_DEPTH)[0] == 1 for f, _ in prints.values())
+    for key, (f, keeps) in prints.items():
+        for sel in ("cut", "all"):
+            mirror = _assert_footprint(b.dev, b.u, b.full, f, sel, f"d20 {key} {sel}")
+            deep = _deep_samples(mirror)
+            assert (len(deep) == 1 and int(deep["numSamples"][0]) == k) if keeps == "all" else len(deep) == 0, (key, sel)
+            if sel == "cut":
+                exact = fr.contains_exact(f, d.pts)
+                assert exact.any()
+                rr.assert_same_multiset(mirror.samples, d.pts[exact], key)
+        for ml in (19, 20):
+            _assert_footprint(b.dev, b.u, b.full, f, "all", f"d20 {key} all@{ml}", ml=ml)
+
+
+# ---- 7. clip regions ---------------------------------------------------------------------------------------------------------------------------
+def _image(name):
+    """The downloaded image of a module octree, once."""
+    b = _built(name)
+    if not hasattr(b, "image"):
+        b.image = host_image_of(b.dev)
+    return b.image
+
+
+def _level_classes(vis, region, u, level):
+    """How many records of `level` in an oracle's visible list a region leaves outside / filters / copies (rules 1 and 4)."""
+    cls = clip_ref.node_classes(vis, len(vis), region, u)[vis["level"] == level]
+    return [int((cls == c).sum()) for c in (clip_ref.OUTSIDE, clip_ref.FILTERED, clip_ref.COPIED)]
+
+
+@pytest.mark.parametrize("hqs", [False, True], ids=["plain", "hqs"])
+@pytest.mark.parametrize("mode", on_clips.MODES)
+@pytest.mark.parametrize("region_kind", ["cell12", "slab", "frustum"])
+def test_clipped_close_up_of_level_13(built_libs, region_kind, mode, hqs):
+    """D13x under the close camera: the clip's node classes are decided for level-13 nodes 1 wide at coordinates near 5 000, in the draw and in
+    the visibility pass.  The oracle's UNCLIPPED visible list holds level-13 nodes of every class."""
+    b = _built("d13x")
+    d, dev = b.d, b.dev
+    nodes, pers, nn = _image("d13x")
+    u = dev.uniforms(W, H, _close_cam(d), d.box, hqs=hqs)
+    region = dr.d13_regions(d)[region_kind]
+    vis_un = on_clips._unclipped(("d13x",), nodes, nn, u)[3]
+    counts = _level_classes(vis_un, region, u, dr.LEAF_LEVEL)
+    print(f"unclipped visible list: {len(vis_un)} nodes; at level 13 {counts[0]} outside / {counts[1]} filtered / {counts[2]} copied")
+    assert min(counts) >= 1, counts
+    on_clips._clipped_frame(dev, ("d13x",), nodes, pers, nn, u, Clip(region, mode, on_clips.COLOUR), region_kind, f"d13x close-up {region_kind} {mode} hqs={int(hqs)}")
+
+
+@pytest.mark.parametrize("mode", on_clips.MODES)
+def test_clipped_close_up_on_an_imported_octree(built_libs, tmp_path, mode):
+    """The same octree after a plain import through a file: the clipped frames are the source's bit for bit (and the oracle's on the imported
+    image)."""
+    b = _built("d13x")
+    d, src = b.d, b.dev
+    dst = _device()
+    dst.nodes.fill_(0xA5)
+    dst.import_octree(_through_file(b.full, tmp_path))
+    assert int(dst.read_stats()["dbg"]) == 0
+    u = dst.uniforms(W, H, _close_cam(d), d.box, hqs=True)
+    clip = Clip(dr.d13_regions(d)["slab"], mode, on_clips.COLOUR)
+    nodes, pers, nn = host_image_of(dst)
+    _, fb, _, _ = on_clips._clipped_frame(dst, ("d13x imported", mode), nodes, pers, nn, u, clip, "slab", f"d13x imported slab {mode}")
+    src.set_clip(clip)
+    try:
+        src.render(u)
+        assert np.array_equal(src.framebuffer(W, H), fb) and np.array_equal(src.color(W, H), dst.color(W, H)), "the imported octree draws another clipped frame"
+    finally:
+        src.set_clip(None)
+
+
+def _leaf_uniforms(dev, d, nodes, nn, leaf):
+    """The cases' camera with minNodeSize lowered until the ORACLE's visible list of this image holds the level-20 leaf: a level-20 node is
+    2^-20 of the box, far below a pixel."""
+    key = node_keys(nodes[leaf: leaf + 1])[0]
+    for size in (0.0, -1.0):
+        u = dev.uniforms(W, H, cases._cam(d.box), d.box)
+        u["minNodeSize"] = size
+        vis = on_clips._unclipped(("d20",), nodes, nn, u)[3]
+        if (node_keys(vis) == key).any():
+            return u
+    raise AssertionError("no minNodeSize makes the oracle draw the level-20 leaf")
+
+
+@pytest.mark.parametrize("mode", on_clips.MODES)
+def test_clip_at_the_level_20_leaf(built_libs, mode):
+    """The identical samples under a clip: the leaf is drawn (asserted from the oracle's visible list), and per region the mirror's image keeps
+    all k of them or none — inside keeps what the region keeps, outside the rest, highlight recolours them.  They cover one pixel, so the
+    frame need not differ from the unclipped one."""
+    b = _built("d20")
+    d, dev = b.d, b.dev
+    nodes, pers, nn = _image("d20")
+    at = np.nonzero((nodes["level"][:nn] == abi.MAX_DEPTH) & (nodes["numPoints"][:nn] > 0))[0]
+    assert len(at) == 1 and int(nodes["numPoints"][at[0]]) == d.k
+    leaf = int(at[0])
+    u = _leaf_uniforms(dev, d, nodes, nn, leaf)
+    for key, (region, keeps) in dr.d20_regions(b.full).items():
+        clip = Clip(region, mode, on_clips.COLOUR)
+        img, *_ = on_clips._clipped_frame(dev, ("d20",), nodes, pers, nn, u, clip, key, f"d20 {key} {mode}", floor=0, differs=False)
+        kept = clip_ref.kept_samples(img, leaf)
+        if mode == "highlight":
+            assert len(kept) == d.k and ((kept["color"] == on_clips.COLOUR).all() if keeps == "all" else (kept["color"] != on_clips.COLOUR).all()), (key, mode)
+        else:
+            assert len(kept) == (d.k if (keeps == "all") == (mode == "inside") else 0), (key, mode, len(kept))
