@@ -773,6 +773,96 @@ int simlod_query_view(const SimlodNode* nodes, const SimlodStats* stats, const S
                       void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
                       uint64_t sampleCapacity, SimlodViewCounts* counts, void* stream);
 
+/* ---- view deltas: what a camera move adds to the cut a receiver holds ------------------------------------------------------------------------
+ * simlod_query_view_delta answers simlod_query_view's question for a receiver that still holds the result of an earlier call: it writes the
+ * new cut's table, per entry what the receiver has of it already, the samples it lacks, and the held entries it may drop.
+ * simlod_merge_view_delta puts a held sample array and a delta together into the new cut's sample array.
+ *
+ * A table's entries ascend by (level, Morton(X, Y, Z)) — breadth-first, children in octant order —, so an entry's counterpart in another table
+ * is found by key, without walking that table.
+ *  D1. `table` and `counts.view` are byte for byte what simlod_query_view writes for the same nodes / uniforms / view / maxLevel: the chosen
+ *      bias, the ladder, SIMLOD_EXPORT_ERR_BUDGET.  On a budget error no sample is written and every entry has state NONE (numKept = numDelta =
+ *      0).  The table is an ordinary table: it validates, and it is the `held` of the next call.
+ *  D2. entries[t].held = the index h < numHeld with held[h].(level, X, Y, Z) == table[t].(level, X, Y, Z), else SIMLOD_EXPORT_NONE.  `held`
+ *      must be a table this library wrote (any export, query or merge; of an older, a cropped or a truncated octree).  For any other content
+ *      the result is unspecified, but nothing outside held[0, numHeld) is read and nothing outside the outputs is written.  held == NULL
+ *      requires numHeld == 0.
+ *  D3. An entry that is not SELECTED has state NONE.  For a SELECTED entry with n = numSamples: hs = held[h].numSamples where the held entry is
+ *      SELECTED, 0 otherwise or without h; the kind agrees when FLAG_LEAF is equal on both sides.  KEPT iff the kinds agree and hs == n and
+ *      n > 0: numKept = n.
+ *  D4. GROWN iff SIMLOD_DELTA_TAILS is set, the kinds agree and 0 < hs < n: numKept = hs, and the node contributes the samples [hs, n) of its
+ *      chunk list.  This rests on an invariant of kernel_construct: while a node keeps its kind its list is only appended to — stored samples
+ *      are neither moved nor rewritten.  The caller must not set the flag across a reset, an import or a colour-filter launch.  hs > n: ADDED.
+ *  D5. Every other SELECTED entry is ADDED (one with n == 0 too), numKept = 0.  numDelta = numSamples - numKept, firstDelta the exclusive scan
+ *      of numDelta in table order; `delta` holds numDelta samples per entry at firstDelta, inside a node in chunk-list order.
+ *  D6. `dropped` lists, in ascending order, the held indices h with held[h] SELECTED, held[h].numSamples > 0 and no KEPT or GROWN entry whose
+ *      `held` is h.  numDropped is exact whatever droppedCapacity is; more than droppedCapacity of them set SIMLOD_EXPORT_ERR_CAPACITY
+ *      (dropped == NULL: the list is only counted), and nothing is written beyond the capacity.  The same holds for deltaCapacity
+ *      (delta == NULL: count only — table, entries, dropped and counts are complete, no sample is written) and tableCapacity.
+ *  D7. With numHeld == 0 every selected entry is ADDED, firstDelta == firstSample, and `delta` equals simlod_query_view's samples byte for byte.
+ *  D8. The source octree and `held` are only read.  Rule V9 carries over.
+ *  D9. simlod_merge_view_delta: the samples [firstSample, firstSample + numKept + numDelta) of each entry whose state is not NONE are
+ *      heldSamples[held[h].firstSample .. + numKept) followed by delta[firstDelta .. + numDelta).  After a delta on an unchanged octree the
+ *      result equals simlod_query_view's sample array byte for byte; after growth exactly when the invariant of D4 holds.  `counts` as the
+ *      export writes them (numNodes, error, numSamples = the samples assembled); an entry that reaches beyond sampleCapacity sets
+ *      SIMLOD_EXPORT_ERR_CAPACITY and nothing is written; a KEPT or GROWN entry whose `held` is not below numHeld sets
+ *      SIMLOD_EXPORT_ERR_SHORT_LIST and is left out. */
+typedef struct SimlodDeltaEntry {      /* one per entry of `table`, same index; written by the device */
+	uint32_t held;                     /* index of the held-table entry with this entry's (level, X, Y, Z); SIMLOD_EXPORT_NONE: none */
+	uint32_t state;                    /* SIMLOD_DELTA_*                                                                          */
+	uint32_t numKept;                  /* leading samples of the node that the receiver holds already                            */
+	uint32_t numDelta;                 /* table[t].numSamples - numKept: this node's samples in the delta array                  */
+	uint64_t firstDelta;               /* exclusive scan of numDelta in table order                                              */
+} SimlodDeltaEntry;
+#define SIMLOD_DELTA_NONE  0u
+#define SIMLOD_DELTA_KEPT  1u
+#define SIMLOD_DELTA_GROWN 2u
+#define SIMLOD_DELTA_ADDED 3u
+#define SIMLOD_DELTA_TAILS 0x1u        /* deltaFlags: allow GROWN (rule D4) */
+typedef struct SimlodDeltaCounts {     /* written by the device */
+	SimlodViewCounts view;             /* exactly what simlod_query_view reports for the same arguments (error: with the delta's own bits) */
+	uint64_t numDeltaSamples;          /* the sum of numDelta (= written, unless count-only or an error)                         */
+	uint64_t numKeptSamples;           /* the sum of numKept                                                                     */
+	uint32_t numKept, numGrown, numAdded;   /* entries in each state                                                             */
+	uint32_t numDropped;               /* rule D6                                                                                */
+} SimlodDeltaCounts;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodDeltaEntry) == 24, "DeltaEntry");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodDeltaEntry, state) == 4, "DeltaEntry.state");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodDeltaEntry, numKept) == 8, "DeltaEntry.numKept");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodDeltaEntry, numDelta) == 12, "DeltaEntry.numDelta");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodDeltaEntry, firstDelta) == 16, "DeltaEntry.firstDelta");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodDeltaCounts) == 232, "DeltaCounts");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodDeltaCounts, numDeltaSamples) == 200, "DeltaCounts.numDeltaSamples");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodDeltaCounts, numKeptSamples) == 208, "DeltaCounts.numKeptSamples");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodDeltaCounts, numKept) == 216, "DeltaCounts.numKept");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodDeltaCounts, numGrown) == 220, "DeltaCounts.numGrown");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodDeltaCounts, numAdded) == 224, "DeltaCounts.numAdded");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodDeltaCounts, numDropped) == 228, "DeltaCounts.numDropped");
+
+/* Bytes of the `scratch` buffer the two calls below need for tables of up to nodeCapacity entries, results of up to sampleBound samples and
+ * a held table of numHeld entries. */
+uint64_t simlod_view_delta_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numHeld);
+
+/* The view delta (rules above).  Asynchronous on `stream`; `entries` has room for tableCapacity records.  The copy items (32 bytes per piece of
+ * at most 1 000 samples) take what `scratch` has behind simlod_view_delta_buffer_min_bytes(tableCapacity, 0, numHeld): size it by
+ * simlod_view_delta_buffer_min_bytes(tableCapacity, samples of the delta, numHeld); too few set SIMLOD_EXPORT_ERR_CAPACITY.
+ * hipErrorInvalidValue with nothing enqueued: everything simlod_query_view refuses, unknown deltaFlags, held == NULL with numHeld != 0,
+ * dropped == NULL with droppedCapacity != 0, a null pointer other than `delta`, `held` and `dropped`, scratchBytes below
+ * simlod_view_delta_buffer_min_bytes(tableCapacity, 0, numHeld). */
+int simlod_query_view_delta(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodView* view, uint32_t maxLevel,
+                            const SimlodExportNode* held, uint32_t numHeld, uint32_t deltaFlags, void* scratch, uint64_t scratchBytes,
+                            SimlodExportNode* table, uint32_t tableCapacity, SimlodDeltaEntry* entries, SimlodPoint* delta, uint64_t deltaCapacity,
+                            uint32_t* dropped, uint32_t droppedCapacity, SimlodDeltaCounts* counts, void* stream);
+
+/* The merge (rule D9) of the arrays a receiver has: the held table and its samples, and the table, entries and delta of a
+ * simlod_query_view_delta call against that held table; numNodes entries.  All device memory; asynchronous on `stream`.  The scratch bound is
+ * simlod_view_delta_buffer_min_bytes(numNodes, samples of the result, numHeld), refused below (numNodes, 0, numHeld) as above.
+ * hipErrorInvalidValue with nothing enqueued: a null pointer other than `held` (with numHeld == 0), `heldSamples`, `delta` and `samples` (with
+ * sampleCapacity == 0); a scratch buffer below the bound. */
+int simlod_merge_view_delta(const SimlodExportNode* held, uint32_t numHeld, const SimlodPoint* heldSamples, const SimlodExportNode* table,
+                            const SimlodDeltaEntry* entries, uint32_t numNodes, const SimlodPoint* delta, void* scratch, uint64_t scratchBytes,
+                            SimlodPoint* samples, uint64_t sampleCapacity, SimlodExportCounts* counts, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

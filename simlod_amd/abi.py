@@ -160,6 +160,17 @@ def view_record(bias=0, max_bias=VIEW_MAX_BIAS, budget=None, cull=True, draw_sma
     return v
 
 
+# ---- view deltas (include/simlod_hip.h, "view deltas") -----------------------------------------------------------------------------------
+DELTA_NONE, DELTA_KEPT, DELTA_GROWN, DELTA_ADDED = 0, 1, 2, 3
+DELTA_TAILS = 0x1
+delta_entry_dtype = np.dtype({"names": ["held", "state", "numKept", "numDelta", "firstDelta"], "formats": ["<u4", "<u4", "<u4", "<u4", "<u8"],
+                              "offsets": [0, 4, 8, 12, 16], "itemsize": 24})
+delta_counts_dtype = np.dtype({"names": ["view", "numDeltaSamples", "numKeptSamples", "numKept", "numGrown", "numAdded", "numDropped"],
+                               "formats": [view_counts_dtype, "<u8", "<u8", "<u4", "<u4", "<u4", "<u4"],
+                               "offsets": [0, 200, 208, 216, 220, 224, 228], "itemsize": 232})
+assert delta_entry_dtype.itemsize == 24 and delta_counts_dtype.itemsize == 232
+
+
 # ---- clip regions (include/simlod_hip.h, "clip regions") --------------------------------------------------------------------------------
 CLIP_OFF, CLIP_INSIDE, CLIP_OUTSIDE, CLIP_HIGHLIGHT = 0, 1, 2, 3
 CLIP_MODES = {"off": CLIP_OFF, "inside": CLIP_INSIDE, "outside": CLIP_OUTSIDE, "highlight": CLIP_HIGHLIGHT}

@@ -20,6 +20,8 @@
 // polygon on top of the planes, in export_footprint.inc.
 // View query (simlod_query_view): k_v_hier -> k_v_scan -> k_x_dir -> k_copy, the export's sequence with the camera's rules in the walk, in
 // export_view.inc; the rules themselves in view_rules.hpp.
+// View delta (simlod_query_view_delta): k_v_hier -> k_v_scan -> k_d_match -> k_d_scan -> k_d_dir -> k_copy -> k_d_drop; its merge
+// (simlod_merge_view_delta): k_d_merge_scan -> k_d_merge_dir -> k_copy, in export_delta.inc; the rules in delta_rules.hpp.
 // Pair queries: k_p_hier -> k_q_dir -> k_p_pairs<Q, count> -> k_p_scan<Q> -> k_p_pairs<Q, fill> -> Q's test kernel -> Q's reduce kernel; the pipeline
 // is written once over a query trait Q, in export_pairs.inc.  Ray query (simlod_query_rays): RayQuery, k_r_test, k_r_reduce, in export_rays.inc.
 // Neighbour query (simlod_query_neighbours): NbQuery, k_n_test, k_n_reduce, in export_neighbours.inc.
@@ -36,6 +38,7 @@
 #include "simlod_hip.h"
 #include "simlod_internal.hpp"
 #include "view_rules.hpp"
+#include "delta_rules.hpp"
 
 namespace simlod {
 namespace {
@@ -46,6 +49,7 @@ namespace {
 #include "export_region.inc"   // QueryGeom, classify, QItem, QueryLayout, QueryArgs, k_q_hier, k_q_dir, k_q_count, k_q_scan, k_q_write
 #include "export_footprint.inc"  // FootEdge, FootGeom, FootArgs, stage_edges, Footprint, classify_footprint, k_f_hier, k_f_count, k_f_write
 #include "export_view.inc"     // ViewArgs, k_v_hier, k_v_scan
+#include "export_delta.inc"    // DeltaLayout, DeltaArgs, k_d_match, k_d_scan, k_d_dir, k_d_drop, MergeArgs, k_d_merge_scan, k_d_merge_dir
 #include "export_pairs.inc"    // the pair records, PairLayout, PairArgs, k_p_hier, wave_descend, k_p_pairs, k_p_scan, TestView, test_chunk
 #include "export_rays.inc"     // RayArgs, ray_load, slab, sample_t, RayQuery, k_r_test, k_r_reduce
 #include "export_neighbours.inc"  // NbArgs, sphere_load, sphere_cube, sphere_d2, NbQuery, k_n_test, k_n_reduce
@@ -211,6 +215,69 @@ int launch_view(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats,
 		if (tableCapacity != 0u) SIMLOD_LAUNCH(k_x_dir, dim3((tableCapacity + LANE_TPB - 1u) / LANE_TPB), dim3(LANE_TPB), stream, a);
 		SIMLOD_LAUNCH(k_copy, dim3(copy_grid(a.lay.itemCap)), dim3(LANE_TPB), stream, (const uint8_t*)a.scratch, a.lay.items);
 	}
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+uint64_t view_delta_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numHeld) {
+	return DeltaLayout(nodeCapacity, numHeld).x.items + delta_item_bound(nodeCapacity, sampleBound) * sizeof(CopyItem);
+}
+
+// simlod_query_view_delta: the view query's two single-workgroup kernels with the arguments of a count-only call, then the delta's own.
+int launch_view_delta(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodView* view, uint32_t maxLevel,
+                      const SimlodExportNode* held, uint32_t numHeld, uint32_t deltaFlags, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
+                      uint32_t tableCapacity, SimlodDeltaEntry* entries, SimlodPoint* delta, uint64_t deltaCapacity, uint32_t* dropped,
+                      uint32_t droppedCapacity, SimlodDeltaCounts* counts, hipStream_t stream) {
+	if (nodes == nullptr || stats == nullptr || u == nullptr || view == nullptr || scratch == nullptr || table == nullptr || entries == nullptr || counts == nullptr)
+		return (int)hipErrorInvalidValue;
+	if (!view_acceptable(*view, *u) || !delta_acceptable(deltaFlags, held, numHeld, dropped, droppedCapacity)) return (int)hipErrorInvalidValue;
+	if (scratchBytes < view_delta_min_bytes(tableCapacity, 0u, numHeld)) return (int)hipErrorInvalidValue;
+	const DeltaLayout dl(tableCapacity, numHeld);
+	ViewArgs v{};
+	ExportArgs& a = v.x;
+	a.nodes = nodes; a.stats = stats; a.maxLevel = maxLevel; a.select = SIMLOD_EXPORT_ALL; a.cap = tableCapacity;
+	a.scratch = reinterpret_cast<uint8_t*>(scratch); a.table = table; a.samples = nullptr; a.sampleCap = 0u;    // (k_v_scan: a count-only call)
+	a.counts = reinterpret_cast<SimlodExportCounts*>(&counts->view);
+	a.lay = dl.x; a.lay.take_rest(scratchBytes);
+	bind_leaf_table(ctx, nodes, a);
+	v.g.m = u->transform_updateBound;
+	octree_box(u, v.g.cubeSize, v.g.minx, v.g.miny, v.g.minz);
+	v.g.width = u->width; v.g.height = u->height; v.g.minNodeSize = u->minNodeSize;
+	v.flags = view->flags; v.minBias = view->minBias; v.maxBias = view->maxBias; v.budget = view->sampleBudget;
+	v.counts = &counts->view;
+	DeltaArgs d{};
+	d.x = a;                                                                    // (the delta's kernels: the items the buffer really has)
+	d.held = held; d.numHeld = numHeld; d.deltaFlags = deltaFlags; d.mark = dl.mark; d.entries = entries;
+	d.delta = delta; d.deltaCap = delta != nullptr ? deltaCapacity : 0u; d.dropped = dropped; d.droppedCap = droppedCapacity; d.counts = counts;
+	a.lay.itemCap = 0xffffffffull;                                              // k_v_scan's items are not written: none can be missing
+	SIMLOD_LAUNCH(k_v_hier, dim3(1), dim3(WG_TPB), stream, v);
+	SIMLOD_LAUNCH(k_v_scan, dim3(1), dim3(WG_TPB), stream, a);
+	if (tableCapacity != 0u) SIMLOD_LAUNCH(k_d_match, dim3((tableCapacity + LANE_TPB - 1u) / LANE_TPB), dim3(LANE_TPB), stream, d);
+	SIMLOD_LAUNCH(k_d_scan, dim3(1), dim3(WG_TPB), stream, d);
+	if (delta != nullptr) {
+		constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                      // k_d_dir: one wave per table entry
+		if (tableCapacity != 0u) SIMLOD_LAUNCH(k_d_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, d);
+		SIMLOD_LAUNCH(k_copy, dim3(copy_grid(d.x.lay.itemCap)), dim3(LANE_TPB), stream, (const uint8_t*)d.x.scratch, d.x.lay.items);
+	}
+	SIMLOD_LAUNCH(k_d_drop, dim3(1), dim3(WG_TPB), stream, d);
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+int launch_merge_view_delta(const SimlodExportNode* held, uint32_t numHeld, const SimlodPoint* heldSamples, const SimlodExportNode* table,
+                            const SimlodDeltaEntry* entries, uint32_t numNodes, const SimlodPoint* delta, void* scratch, uint64_t scratchBytes,
+                            SimlodPoint* samples, uint64_t sampleCapacity, SimlodExportCounts* counts, hipStream_t stream) {
+	if (table == nullptr || entries == nullptr || scratch == nullptr || counts == nullptr) return (int)hipErrorInvalidValue;
+	if ((held == nullptr && numHeld != 0u) || (samples == nullptr && sampleCapacity != 0u)) return (int)hipErrorInvalidValue;
+	if (scratchBytes < view_delta_min_bytes(numNodes, 0u, numHeld)) return (int)hipErrorInvalidValue;
+	MergeArgs m{};
+	m.held = held; m.numHeld = numHeld; m.n = numNodes; m.heldSamples = heldSamples; m.table = table; m.entries = entries; m.delta = delta;
+	m.scratch = reinterpret_cast<uint8_t*>(scratch);
+	m.lay = DeltaLayout(numNodes, numHeld).x; m.lay.take_rest(scratchBytes);
+	m.samples = samples; m.sampleCap = sampleCapacity; m.counts = counts;
+	SIMLOD_LAUNCH(k_d_merge_scan, dim3(1), dim3(WG_TPB), stream, m);
+	if (numNodes != 0u) SIMLOD_LAUNCH(k_d_merge_dir, dim3((numNodes + LANE_TPB - 1u) / LANE_TPB), dim3(LANE_TPB), stream, m);
+	SIMLOD_LAUNCH(k_copy, dim3(copy_grid(m.lay.itemCap)), dim3(LANE_TPB), stream, (const uint8_t*)m.scratch, m.lay.items);
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();
 }

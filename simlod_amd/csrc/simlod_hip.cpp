@@ -481,6 +481,26 @@ int simlod_query_view(const SimlodNode* nodes, const SimlodStats* stats, const S
 	                   counts, (hipStream_t)stream);
 }
 
+uint64_t simlod_view_delta_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numHeld) {
+	return view_delta_min_bytes(nodeCapacity, sampleBound, numHeld);
+}
+
+int simlod_query_view_delta(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodView* view, uint32_t maxLevel,
+                            const SimlodExportNode* held, uint32_t numHeld, uint32_t deltaFlags, void* scratch, uint64_t scratchBytes,
+                            SimlodExportNode* table, uint32_t tableCapacity, SimlodDeltaEntry* entries, SimlodPoint* delta, uint64_t deltaCapacity,
+                            uint32_t* dropped, uint32_t droppedCapacity, SimlodDeltaCounts* counts, void* stream) {
+	if (nodes == nullptr) return (int)hipErrorInvalidValue;
+	return launch_view_delta(context_of(nodes), nodes, stats, uniforms, view, maxLevel, held, numHeld, deltaFlags, scratch, scratchBytes, table,
+	                         tableCapacity, entries, delta, deltaCapacity, dropped, droppedCapacity, counts, (hipStream_t)stream);
+}
+
+int simlod_merge_view_delta(const SimlodExportNode* held, uint32_t numHeld, const SimlodPoint* heldSamples, const SimlodExportNode* table,
+                            const SimlodDeltaEntry* entries, uint32_t numNodes, const SimlodPoint* delta, void* scratch, uint64_t scratchBytes,
+                            SimlodPoint* samples, uint64_t sampleCapacity, SimlodExportCounts* counts, void* stream) {
+	return launch_merge_view_delta(held, numHeld, heldSamples, table, entries, numNodes, delta, scratch, scratchBytes, samples, sampleCapacity, counts,
+	                               (hipStream_t)stream);
+}
+
 uint64_t simlod_rays_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates) {
 	return rays_min_bytes(nodeCapacity, sampleBound, numRays, numPairs, numCandidates);
 }

@@ -27,6 +27,9 @@ Footprint queries (include/simlod_hip.h, "footprint queries"): `Footprint` holds
 View queries (include/simlod_hip.h, "view queries"): `OctreeExport.view` (on a full export) is the host mirror of simlod_query_view and
 `view_geometry` of its rules V2 and V3 — the rasteriser's visibility arithmetic in numpy float32, in the device's operation order.
 
+View deltas (include/simlod_hip.h, "view deltas"): `OctreeExport.view_delta` is the host mirror of simlod_query_view_delta — `view` plus the
+rules D2-D6 (`delta_between`) — and `ViewDelta.apply` of simlod_merge_view_delta (rule D9).
+
 Ray queries (include/simlod_hip.h, "ray queries"): `Rays` holds a batch of SimlodRay records, `OctreeExport.cast` (on a full export) and
 `OctreeExport.cast_selected` (on any export) are the host mirror of simlod_query_rays, in the same float64 operation order.
 
@@ -242,6 +245,14 @@ class OctreeExport:
         c["numNodes"], c["error"], c["numSamples"] = len(out), 0 if fits else abi.EXPORT_ERR_BUDGET, int(ladder[chosen])
         c["bias"], c["numSelected"], c["numInside"], c["samplesAt"] = chosen, int(sel.sum()), int(visible.sum()), ladder
         return ex, c
+
+    # -- view deltas (include/simlod_hip.h, "view deltas") ---------------------------------------------------------------------------------
+    def view_delta(self, uniforms, held, bias=0, max_bias=abi.VIEW_MAX_BIAS, budget=None, cull=True, draw_small_root=False, max_level=None, tails=False):
+        """The host mirror of simlod_query_view_delta on the octree this FULL export was taken from: `view` with the same arguments, and what
+        of its cut a receiver that holds `held` (an OctreeExport, or None: nothing) lacks — a ViewDelta on the host, whose counts are the
+        SimlodDeltaCounts record.  When no bias fits the budget the delta is empty and counts["view"]["error"] has abi.EXPORT_ERR_BUDGET."""
+        new, vc = self.view(uniforms, bias, max_bias, budget, cull, draw_small_root, max_level, return_counts=True)
+        return delta_between(new, held, tails, vc)
 
     # -- ray queries (include/simlod_hip.h, "ray queries") -----------------------------------------------------------------------------------
     def truncated(self, max_level=None, select="cut"):
@@ -564,6 +575,149 @@ def view_geometry(uniforms, nodes):
             lb = np.ldexp(lim, b)
             rank += (dx.astype(np.float64) > lb) | (dy.astype(np.float64) > lb)
     return inside, dx, dy, rank
+
+
+def delta_keys(nodes):
+    """The order of a table's entries as keys: (level, Morton(X, Y, Z)) per entry, the Morton code as uint64 with bit i of X at 3 i + 2, of Y at
+    3 i + 1, of Z at 3 i (delta_rules.hpp delta_key)."""
+    m = np.zeros(len(nodes), np.uint64)
+    for i in range(21):
+        for a, sh in (("X", 2), ("Y", 1), ("Z", 0)):
+            m |= ((nodes[a].astype(np.uint64) >> np.uint64(i)) & np.uint64(1)) << np.uint64(3 * i + sh)
+    return nodes["level"].astype(np.int64), m
+
+
+def delta_find(held, nodes):
+    """Rule D2 for every entry of `nodes`: the index of the held entry with its (level, X, Y, Z), else abi.EXPORT_NONE — by the device's search
+    (delta_rules.hpp delta_find: the first held entry whose key is not below the wanted one, then the four words compared), so that a held
+    table that is not in key order misses what the device misses."""
+    n, nh = len(nodes), len(held)
+    out = np.full(n, abi.EXPORT_NONE, np.int64)
+    if n == 0 or nh == 0:
+        return out
+    hl, hm = delta_keys(held)
+    wl, wm = delta_keys(nodes)
+    lo, hi = np.zeros(n, np.int64), np.full(n, nh, np.int64)
+    while (lo < hi).any():
+        act = lo < hi
+        mid = np.where(act, lo + ((hi - lo) >> 1), 0)
+        less = (hl[mid] < wl) | ((hl[mid] == wl) & (hm[mid] < wm))
+        lo = np.where(act & less, mid + 1, lo)
+        hi = np.where(act & ~less, mid, hi)
+    at = np.minimum(lo, nh - 1)
+    same = (lo < nh) & (held["level"][at] == nodes["level"]) & (held["X"][at] == nodes["X"]) & (held["Y"][at] == nodes["Y"]) & (held["Z"][at] == nodes["Z"])
+    out[same] = lo[same]
+    return out
+
+
+def delta_between(new, held, tails=False, view_counts=None):
+    """Rules D2-D6 between a cut `new` (an OctreeExport as `view` returns it) and a held table (an OctreeExport or None) -> a ViewDelta on the
+    host.  view_counts: the SimlodViewCounts record that goes with `new` (None: one with numNodes, numSamples and numSelected alone); with
+    abi.EXPORT_ERR_BUDGET in its error every entry has state NONE (rule D1)."""
+    tb, smp = new.nodes, new.samples
+    ht = held.nodes if held is not None else np.zeros(0, dtype=abi.export_node_dtype)
+    n = len(tb)
+    budget_error = view_counts is not None and bool(int(view_counts["error"]) & abi.EXPORT_ERR_BUDGET)
+    h = delta_find(ht, tb)
+    found = h != abi.EXPORT_NONE
+    hh = np.where(found, h, 0)
+    hflags = ht["flags"][hh] if len(ht) else np.zeros(n, np.uint8)
+    hns = ht["numSamples"][hh].astype(np.int64) if len(ht) else np.zeros(n, np.int64)
+    ns = tb["numSamples"].astype(np.int64)
+    selected = (tb["flags"] & abi.EXPORT_FLAG_SELECTED) != 0
+    hs = np.where(found & ((hflags & abi.EXPORT_FLAG_SELECTED) != 0), hns, 0)
+    kind = found & (((tb["flags"] ^ hflags) & abi.EXPORT_FLAG_LEAF) == 0)
+    kept = selected & kind & (hs == ns) & (ns > 0)
+    grown = selected & ~kept & bool(tails) & kind & (hs > 0) & (hs < ns)
+    state = np.where(kept, abi.DELTA_KEPT, np.where(grown, abi.DELTA_GROWN, np.where(selected, abi.DELTA_ADDED, abi.DELTA_NONE)))
+    num_kept = np.where(kept, ns, np.where(grown, hs, 0))
+    num_delta = ns - num_kept
+    if budget_error:
+        state[:], num_kept[:], num_delta[:] = abi.DELTA_NONE, 0, 0
+    entries = np.zeros(n, dtype=abi.delta_entry_dtype)
+    entries["held"], entries["state"], entries["numKept"], entries["numDelta"] = h, state, num_kept, num_delta
+    entries["firstDelta"] = np.concatenate([[0], np.cumsum(num_delta)[:-1]]).astype(np.uint64) if n else 0
+    parts = []
+    if not budget_error:
+        for t in np.nonzero(num_delta)[0]:
+            a = int(tb["firstSample"][t])
+            parts.append(smp[a + int(num_kept[t]): a + int(ns[t])])
+    delta = np.concatenate(parts) if parts else np.zeros(0, dtype=abi.point_dtype)
+    # rule D6
+    taken = np.zeros(len(ht), bool)
+    taken[h[(state == abi.DELTA_KEPT) | (state == abi.DELTA_GROWN)]] = True
+    dropped = np.nonzero(((ht["flags"] & abi.EXPORT_FLAG_SELECTED) != 0) & (ht["numSamples"] > 0) & ~taken)[0].astype(np.uint32)
+    c = np.zeros((), dtype=abi.delta_counts_dtype)
+    if view_counts is not None:
+        c["view"] = view_counts
+    else:
+        c["view"]["numNodes"], c["view"]["numSamples"], c["view"]["numSelected"] = n, int(ns.sum()), int(selected.sum())
+    c["numDeltaSamples"], c["numKeptSamples"] = int(num_delta.sum()), int(num_kept.sum())
+    c["numKept"], c["numGrown"], c["numAdded"] = int((state == abi.DELTA_KEPT).sum()), int((state == abi.DELTA_GROWN).sum()), int((state == abi.DELTA_ADDED).sum())
+    c["numDropped"] = len(dropped)
+    return ViewDelta(tb, entries, delta, dropped, new.box_min, new.box_max, new.max_level, c)
+
+
+class ViewDelta:
+    """What simlod_query_view_delta returns (include/simlod_hip.h, "view deltas"): the new cut's table (abi.export_node_dtype), one
+    abi.delta_entry_dtype record per table entry, the delta samples (abi.point_dtype), the held indices to drop (uint32), each as a uint8
+    tensor on the host or on a device, with the box, max_level and the SimlodDeltaCounts record (host)."""
+
+    def __init__(self, table, entries, samples, dropped, box_min, box_max, max_level=20, counts=None):
+        self.table_tensor, self.entries_tensor = _as_bytes_tensor(table), _as_bytes_tensor(entries)
+        self.samples_tensor, self.dropped_tensor = _as_bytes_tensor(samples), _as_bytes_tensor(dropped)
+        if self.table_tensor.numel() // abi.export_node_dtype.itemsize != self.entries_tensor.numel() // abi.delta_entry_dtype.itemsize:
+            raise ValueError("table and entries differ in length")
+        self.box_min = tuple(float(v) for v in np.asarray(box_min, dtype=np.float32).reshape(3))
+        self.box_max = tuple(float(v) for v in np.asarray(box_max, dtype=np.float32).reshape(3))
+        self.max_level = int(max_level)
+        self.counts = counts
+
+    @property
+    def device(self):
+        return self.table_tensor.device
+
+    @property
+    def num_nodes(self):
+        return self.table_tensor.numel() // abi.export_node_dtype.itemsize
+
+    @property
+    def num_samples(self):
+        return self.samples_tensor.numel() // abi.point_dtype.itemsize
+
+    @property
+    def nodes(self):
+        return self.table_tensor.cpu().numpy().view(abi.export_node_dtype)
+
+    @property
+    def entries(self):
+        return self.entries_tensor.cpu().numpy().view(abi.delta_entry_dtype)
+
+    @property
+    def samples(self):
+        return self.samples_tensor.cpu().numpy().view(abi.point_dtype)
+
+    @property
+    def dropped(self):
+        return self.dropped_tensor.cpu().numpy().view(np.uint32)
+
+    def apply(self, held):
+        """Rule D9 in numpy: the new cut as an OctreeExport on the host (select "visible") from `held` (the OctreeExport this delta was taken
+        against, or None) and this delta — per entry the first numKept samples of its held entry, then its numDelta samples of the delta."""
+        tb, en, dl = self.nodes, self.entries, self.samples
+        hs = held.samples if held is not None else np.zeros(0, dtype=abi.point_dtype)
+        ht = held.nodes if held is not None else np.zeros(0, dtype=abi.export_node_dtype)
+        parts = []
+        for t in np.nonzero(en["state"] != abi.DELTA_NONE)[0]:
+            k, d = int(en["numKept"][t]), int(en["numDelta"][t])
+            if k:
+                a = int(ht["firstSample"][int(en["held"][t])])
+                parts.append(hs[a: a + k])
+            if d:
+                a = int(en["firstDelta"][t])
+                parts.append(dl[a: a + d])
+        samples = np.concatenate(parts) if parts else np.zeros(0, dtype=abi.point_dtype)
+        return OctreeExport(tb, samples, self.box_min, self.box_max, self.max_level, abi.EXPORT_VISIBLE)
 
 
 class Region:

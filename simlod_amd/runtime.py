@@ -97,6 +97,10 @@ def lib():
         L.simlod_footprint_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_query_footprint.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
         L.simlod_query_view.argtypes = [vp, vp, vp, vp, u32, vp, u64, vp, u32, vp, u64, vp, vp]
+        L.simlod_view_delta_buffer_min_bytes.restype = u64
+        L.simlod_view_delta_buffer_min_bytes.argtypes = [u32, u64, u32]
+        L.simlod_query_view_delta.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, vp, u64, vp, u32, vp, vp, u64, vp, u32, vp, vp]
+        L.simlod_merge_view_delta.argtypes = [vp, u32, vp, vp, vp, u32, vp, vp, u64, vp, u64, vp, vp]
         L.simlod_rays_buffer_min_bytes.restype = u64
         L.simlod_rays_buffer_min_bytes.argtypes = [u32, u64, u32, u64, u64]
         L.simlod_query_rays.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, u64, vp, u32, vp, vp, vp]
@@ -122,6 +126,7 @@ EXPORTED_SYMBOLS = [
     "simlod_query_buffer_min_bytes", "simlod_query_region", "simlod_rays_buffer_min_bytes", "simlod_query_rays",
     "simlod_neighbours_buffer_min_bytes", "simlod_query_neighbours", "simlod_footprint_buffer_min_bytes", "simlod_query_footprint",
     "simlod_context_set_clip", "simlod_set_clip", "simlod_query_view",
+    "simlod_view_delta_buffer_min_bytes", "simlod_query_view_delta", "simlod_merge_view_delta",
 ]
 
 
@@ -732,6 +737,87 @@ class DeviceOctree:
         u = np.asarray(uniforms).reshape(-1)[0]
         ex = OctreeExport(table, samples[: written * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_VISIBLE)
         return (ex, c) if return_counts else ex
+
+    # -- view deltas (include/simlod_hip.h, "view deltas") -------------------------------------------------------------------------------
+    def _held_table(self, held):
+        """(the held table as a uint8 tensor on this device or None, its entries)"""
+        if held is None or held.num_nodes == 0:
+            return None, 0
+        return held.table_tensor.to(self.device), held.num_nodes
+
+    def _view_delta(self, uniforms, view, ml, held_t, num_held, tails, table, entries, delta, delta_capacity, dropped, dropped_capacity, bound):
+        """One simlod_query_view_delta call -> the SimlodDeltaCounts record (host).  delta None: count only; dropped None: counted only.
+        SIMLOD_EXPORT_ERR_BUDGET is the caller's to judge; any other error bit raises SimlodError."""
+        u, up = self._u(uniforms)
+        nn = table.numel() // abi.export_node_dtype.itemsize
+        counts = torch.zeros(abi.delta_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        scratch = self._export_scratch(int(self.L.simlod_view_delta_buffer_min_bytes(nn, bound, num_held)))
+        opt = lambda t: None if t is None else self._p(t)
+        _check(self.L.simlod_query_view_delta(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(view.ctypes.data), ml, opt(held_t), num_held,
+                                              abi.DELTA_TAILS if tails else 0, self._p(scratch), ctypes.c_uint64(scratch.numel()), self._p(table), nn,
+                                              self._p(entries), opt(delta), ctypes.c_uint64(delta_capacity), opt(dropped), dropped_capacity, self._p(counts),
+                                              self._stream()), "simlod_query_view_delta")
+        c = counts.cpu().numpy().view(abi.delta_counts_dtype)[0]
+        if int(c["view"]["error"]) & ~abi.EXPORT_ERR_BUDGET:
+            raise SimlodError(f"simlod_query_view_delta reported error bits {int(c['view']['error']):#x} ({int(c['view']['numNodes'])} nodes, {int(c['numDeltaSamples'])} delta samples)")
+        return c
+
+    def _entries(self, nn):
+        return torch.empty(max(nn, 1) * abi.delta_entry_dtype.itemsize, dtype=torch.uint8, device=self.device)
+
+    def count_view_delta(self, uniforms, held, bias=0, max_bias=abi.VIEW_MAX_BIAS, budget=None, cull=True, draw_small_root=False, max_level=None, tails=False):
+        """What the camera of `uniforms` needs on top of the cut `held` (an octree_io.OctreeExport, or None): the SimlodDeltaCounts record of a
+        count-only simlod_query_view_delta call — the view's counts as count_view gives them, numDeltaSamples, numKeptSamples, the entries kept,
+        grown and added, and the held entries to drop.  No sample is written."""
+        _, ml, nn, _ = self._query_setup(max_level, "all")
+        held_t, nh = self._held_table(held)
+        return self._view_delta(uniforms, abi.view_record(bias, max_bias, budget, cull, draw_small_root), ml, held_t, nh, tails, self._table(nn),
+                                self._entries(nn), None, 0, None, 0, 0)
+
+    def query_view_delta(self, uniforms, held, bias=0, max_bias=abi.VIEW_MAX_BIAS, budget=None, cull=True, draw_small_root=False, max_level=None,
+                         tails=False, return_counts=False):
+        """The cut the camera of `uniforms` needs, as a difference to the cut `held` (an octree_io.OctreeExport — a table this library wrote —
+        or None): an octree_io.ViewDelta on this device with the new cut's table, per entry what the receiver holds of it (KEPT, GROWN under
+        tails=True, else ADDED), the samples it lacks, and the held entries to drop.  A count-only call first, then the outputs sized exactly.
+        tails=True sends only the new samples of a node that grew: not across a reset, an import or a colour-filter launch.  When no bias in
+        [bias, max_bias] fits `budget`: SimlodError — or, return_counts, an empty delta whose counts["view"]["error"] has abi.EXPORT_ERR_BUDGET."""
+        from .octree_io import ViewDelta
+        _, ml, nn, _ = self._query_setup(max_level, "all")
+        view = abi.view_record(bias, max_bias, budget, cull, draw_small_root)
+        held_t, nh = self._held_table(held)
+        c = self._view_delta(uniforms, view, ml, held_t, nh, tails, self._table(nn), self._entries(nn), None, 0, None, 0, 0)
+        if int(c["view"]["error"]) & abi.EXPORT_ERR_BUDGET and not return_counts:
+            raise SimlodError(f"simlod_query_view_delta: no bias in [{int(bias)}, {int(max_bias)}] fits {int(budget)} samples (the coarsest holds {int(c['view']['numSamples'])})")
+        nn, ns, nd = int(c["view"]["numNodes"]), int(c["numDeltaSamples"]), int(c["numDropped"])
+        table = torch.empty(nn * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        entries = torch.empty(nn * abi.delta_entry_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        delta = torch.empty(max(ns, 1) * abi.point_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        dropped = torch.empty(max(nd, 1) * 4, dtype=torch.uint8, device=self.device)
+        c = self._view_delta(uniforms, view, ml, held_t, nh, tails, table, entries, delta, ns, dropped, nd, ns)
+        u = np.asarray(uniforms).reshape(-1)[0]
+        vd = ViewDelta(table, entries, delta[: int(c["numDeltaSamples"]) * abi.point_dtype.itemsize], dropped[: int(c["numDropped"]) * 4], u["boxMin"], u["boxMax"], ml, c)
+        return (vd, c) if return_counts else vd
+
+    def merge_view_delta(self, held, delta):
+        """The new cut as an octree_io.OctreeExport on this device (select abi.EXPORT_VISIBLE) from the cut `held` (the OctreeExport the delta
+        was taken against, or None) and `delta` (an octree_io.ViewDelta): one simlod_merge_view_delta call."""
+        from .octree_io import OctreeExport
+        held_t, nh = self._held_table(held)
+        held_s = None if held_t is None else held.samples_tensor.to(self.device)
+        table, entries, dl = (t.to(self.device) for t in (delta.table_tensor, delta.entries_tensor, delta.samples_tensor))
+        nn = delta.num_nodes
+        ns = int(delta.counts["numDeltaSamples"]) + int(delta.counts["numKeptSamples"])
+        scratch = self._export_scratch(int(self.L.simlod_view_delta_buffer_min_bytes(nn, ns, nh)))
+        samples = torch.empty(max(ns, 1) * abi.point_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        counts = torch.zeros(abi.export_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        opt = lambda t: None if t is None or t.numel() == 0 else self._p(t)
+        _check(self.L.simlod_merge_view_delta(opt(held_t), nh, opt(held_s), self._p(table), self._p(entries), nn, opt(dl), self._p(scratch),
+                                              ctypes.c_uint64(scratch.numel()), self._p(samples), ctypes.c_uint64(ns), self._p(counts), self._stream()),
+               "simlod_merge_view_delta")
+        c = counts.cpu().numpy().view(abi.export_counts_dtype)[0]
+        if int(c["error"]) != 0:
+            raise SimlodError(f"simlod_merge_view_delta reported error bits {int(c['error']):#x} ({int(c['numNodes'])} nodes, {int(c['numSamples'])} samples)")
+        return OctreeExport(table, samples[: int(c["numSamples"]) * abi.point_dtype.itemsize], delta.box_min, delta.box_max, delta.max_level, abi.EXPORT_VISIBLE)
 
     # -- pair queries: what the ray and the neighbour query share (csrc/export_pairs.inc) ------------------------------------------------------
     # per C call simlod_query_<what>: the record's dtype, its name in messages, its C name, the counts record's dtype.  What _pair_query

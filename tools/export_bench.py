@@ -17,7 +17,10 @@ simlod_query_region, the two alternating rep by rep; the count-only calls of a 1
 device-to-device copy, all in this one run.
 --view: instead, simlod_query_view on the same octree under bench.py's bird and close-up cameras at 1920 x 1080 — without a budget beside
 simlod_export_octree VISIBLE of the same frame into the same buffers, the two alternating rep by rep; the count-only call; the path the
-query replaces, simlod_launch_render + the VISIBLE export — and the device-to-device copy, all in this one run."""
+query replaces, simlod_launch_render + the VISIBLE export — and the device-to-device copy, all in this one run.
+--view-delta: instead, simlod_query_view_delta of bench.py's bird camera against four held cuts — the same camera's, the bird camera's orbited by
+2 degrees, the close-up camera's, none — each alternating rep by rep with simlod_query_view (full and count-only) of the bird camera; per held
+cut the samples sent, the ratios to the two view calls, the count-only delta and the merge — and the device-to-device copy, all in this one run."""
 import argparse
 import ctypes
 import json
@@ -453,6 +456,91 @@ def view_bench(dev, u, box, st, reps):
     print(json.dumps(out))
 
 
+def view_delta_bench(dev, u, box, st, reps, only=None):
+    import math
+    from simlod_amd import fingerprint
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    need = max(int(L.simlod_view_delta_buffer_min_bytes(nn, bound, nn)), int(L.simlod_export_buffer_min_bytes(nn, bound)))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    table, entries = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device), torch.empty(nn * 24, dtype=torch.uint8, device=dev.device)
+    v_table = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    samples, delta, merged = (torch.empty(bound * 16, dtype=torch.uint8, device=dev.device) for _ in range(3))
+    dropped = torch.empty(nn * 4, dtype=torch.uint8, device=dev.device)
+    counts = torch.zeros(abi.delta_counts_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+    v_counts = torch.zeros(abi.view_counts_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+    x_counts = torch.zeros(16, dtype=torch.uint8, device=dev.device)
+    W, H = 1920, 1080
+    # bench.py's "Morro Bay - bird" and "- close" (main_progressive_octree.cpp:1314-1328), scaled to the stand-in's box, as --view
+    cx, cy = 2750.218 * float(box[0]) / 6000.0, 974.775 * float(box[1]) / 4000.0
+    bird = lambda yaw: camera.world_view_proj(camera.orbit_view(yaw, -0.797, 3866.886 * float(box[0]) / 6000.0, (box[0] / 2, box[1] / 2, 0.35 * box[2])),
+                                              camera.perspective(aspect=W / H))
+    close = camera.world_view_proj(camera.orbit_view(-11.270, -0.225, 93.982, (cx, cy, synthetic.terrain_height(cx, cy, seed=7, box=tuple(float(v) for v in box)))),
+                                   camera.perspective(aspect=W / H))
+    view = abi.view_record()
+    uu, up = dev._u(dev.uniforms(W, H, bird(-0.207), box, hqs=True))
+
+    def query(count_only=False, uptr=up, tb=v_table, smp=samples):
+        rc = L.simlod_query_view(p(dev.nodes), p(dev.stats), uptr, ctypes.c_void_p(view.ctypes.data), 20, p(scratch), ctypes.c_uint64(need), p(tb), nn,
+                                 None if count_only else p(smp), ctypes.c_uint64(bound), p(v_counts), stream)
+        assert rc == 0
+
+    copy_dst = torch.empty(int(st["numPoints"]) * 16, dtype=torch.uint8, device=dev.device)
+    t_copy = timed(lambda: copy_dst.copy_(samples[: copy_dst.numel()]), reps)
+    out = {"points": int(st["numPoints"]), "numNodes": nn, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(),
+           "d2d_copy": {"ms": round(t_copy[0], 4), "bytes": 2 * copy_dst.numel(), "GBs": round(2 * copy_dst.numel() / (t_copy[0] * 1e6), 1)}}
+    held_cams = {"same_camera": bird(-0.207), "orbit_2deg": bird(-0.207 + math.radians(2.0)), "other_preset": close, "nothing": None}
+    for name, T in held_cams.items():
+        if only is not None and name != only:
+            continue
+        if T is None:
+            held_t, held_s, nh = None, None, 0
+        else:
+            hu, hup = dev._u(dev.uniforms(W, H, T, box, hqs=True))
+            h_table, h_samples = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device), torch.empty(bound * 16, dtype=torch.uint8, device=dev.device)
+            query(uptr=hup, tb=h_table, smp=h_samples)
+            torch.cuda.synchronize()
+            hc = v_counts.cpu().numpy().view(abi.view_counts_dtype)[0].copy()
+            assert int(hc["error"]) == 0
+            nh = int(hc["numNodes"])
+            held_t, held_s = h_table[: nh * 40].clone(), h_samples[: int(hc["numSamples"]) * 16].clone()
+            del h_table, h_samples
+
+        def delta_call(count_only=False):
+            rc = L.simlod_query_view_delta(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(view.ctypes.data), 20, None if held_t is None else p(held_t), nh, 0,
+                                           p(scratch), ctypes.c_uint64(need), p(table), nn, p(entries), None if count_only else p(delta), ctypes.c_uint64(bound),
+                                           p(dropped), nn, p(counts), stream)
+            assert rc == 0
+
+        def merge():
+            rc = L.simlod_merge_view_delta(None if held_t is None else p(held_t), nh, None if held_s is None else p(held_s), p(table), p(entries), n_new, p(delta),
+                                           p(scratch), ctypes.c_uint64(need), p(merged), ctypes.c_uint64(bound), p(x_counts), stream)
+            assert rc == 0
+
+        query()
+        delta_call()
+        torch.cuda.synchronize()
+        c = counts.cpu().numpy().view(abi.delta_counts_dtype)[0].copy()
+        vc = v_counts.cpu().numpy().view(abi.view_counts_dtype)[0].copy()
+        n_new, ns = int(vc["numNodes"]), int(vc["numSamples"])
+        assert int(c["view"]["error"]) == 0 and c["view"].tobytes() == vc.tobytes() and torch.equal(table[: n_new * 40], v_table[: n_new * 40])
+        merge()
+        torch.cuda.synchronize()
+        xc = x_counts.cpu().numpy().view(abi.export_counts_dtype)[0]
+        assert int(xc["error"]) == 0 and int(xc["numSamples"]) == ns and torch.equal(merged[: ns * 16], samples[: ns * 16]), "the merge is not the view"
+        t_delta, t_view, t_count = timed_alternating([delta_call, query, lambda: query(True)], reps)
+        t_dcount = timed(lambda: delta_call(True), reps)
+        delta_call()                                                                # (the merge's inputs, as the timed calls left other bytes in scratch only)
+        t_merge = timed(merge, reps)
+        out[name] = {"ms": round(t_delta[0], 4), "ms_min": round(t_delta[1], 4), "view_ms": round(t_view[0], 4), "view_ms_min": round(t_view[1], 4),
+                     "view_count_only_ms": round(t_count[0], 4), "over_view": round(t_delta[0] / t_view[0], 4), "over_view_count_only": round(t_delta[0] / t_count[0], 4),
+                     "delta_count_only_ms": round(t_dcount[0], 4), "merge_ms": round(t_merge[0], 4), "numHeld": nh,
+                     "viewSamples": ns, "deltaSamples": int(c["numDeltaSamples"]), "keptSamples": int(c["numKeptSamples"]),
+                     "sent_share": round(int(c["numDeltaSamples"]) / max(ns, 1), 4),
+                     "kept": int(c["numKept"]), "grown": int(c["numGrown"]), "added": int(c["numAdded"]), "dropped": int(c["numDropped"])}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=36_000_000)
@@ -464,6 +552,8 @@ def main():
     ap.add_argument("--rays", action="store_true", help="time simlod_query_rays (one pixel cone, 4 096 vertical rays) instead")
     ap.add_argument("--neighbours", action="store_true", help="time simlod_query_neighbours (4 096 queries, k = 1, 8, 16, count-only) instead")
     ap.add_argument("--view", action="store_true", help="time simlod_query_view (bird and close-up cameras beside the VISIBLE export of the same frame, count-only) instead")
+    ap.add_argument("--view-delta", action="store_true", help="time simlod_query_view_delta (the bird camera against four held cuts, beside simlod_query_view) instead")
+    ap.add_argument("--held", default=None, choices=["same_camera", "orbit_2deg", "other_preset", "nothing"], help="--view-delta: this held cut alone (a per-kernel trace of one case)")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
     pts, box = synthetic.terrain(n_points, seed=7)
@@ -492,6 +582,8 @@ def main():
         return neighbours_bench(dev, u, box, st, args.reps, pts)
     if args.view:
         return view_bench(dev, u, box, st, args.reps)
+    if args.view_delta:
+        return view_delta_bench(dev, u, box, st, args.reps, args.held)
     L = dev.L
     need = int(L.simlod_export_buffer_min_bytes(nn, ns))
     scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
