@@ -92,10 +92,12 @@ struct ExportArgs {
 enum : uint32_t { Q_OUTSIDE = 0u, Q_FILTERED = 1u, Q_COPIED = 2u };
 
 // Does the builder's chunk table describe node `src` of this octree as it is now (render.hip visible_nodes: the same four stamp words), and
-// does its row start at the list's head?
-__device__ __forceinline__ bool leaf_rows_valid(const ExportArgs& a, uint32_t src, const SimlodChunk* head) {
+// does its row start at the list's head?  `leaf`: the list is the node's points.  Never the voxel row of the ROOT: the builder keeps no such
+// row (construct_voxelize.inc vox_chunk_publish), but k_begin's rebuild_side_tables fills row 0 from the root's voxel list as it is THEN — it
+// starts at the head from then on, and the slots behind what the list held at the rebuild are whatever was there.
+__device__ __forceinline__ bool leaf_rows_valid(const ExportArgs& a, uint32_t src, const SimlodChunk* head, bool leaf) {
 	bool rows = false;
-	if (a.lt != nullptr && src < a.ltRows) {
+	if (a.lt != nullptr && src < a.ltRows && (src != 0u || leaf)) {
 		rows = *a.ltMagic == a.ltMagicValue && *a.ltBatch == a.stats->batchletIndex && *a.ltNodes == (uint64_t)a.nodes && *a.ltSig == table_signature(a.stats);
 		rows = rows && leaf_row_get(a.lt, a.ltPers, src, 0u) == head;
 	}

@@ -124,8 +124,9 @@ __global__ __launch_bounds__(LANE_TPB) void k_d_dir(DeltaArgs d) {
 	if (nd == 0u) return;
 	const uint32_t ns = kept + nd, src = map[t];
 	const SimlodNode* n = a.nodes + src;
-	const SimlodChunk* head = (a.table[t].flags & SIMLOD_EXPORT_FLAG_LEAF) ? n->points : n->voxelChunks;
-	const bool rows = leaf_rows_valid(a, src, head);
+	const bool leaf = (a.table[t].flags & SIMLOD_EXPORT_FLAG_LEAF) != 0u;
+	const SimlodChunk* head = leaf ? n->points : n->voxelChunks;
+	const bool rows = leaf_rows_valid(a, src, head, leaf);
 	const uint32_t nch = ceil_chunks(ns), k0 = kept / SIMLOD_POINTS_PER_CHUNK, f = first[t];
 	const uint64_t dst0 = reinterpret_cast<uint64_t>(d.delta + de.firstDelta);
 	auto put = [&](uint32_t k, const SimlodChunk* c) {                      // k >= k0

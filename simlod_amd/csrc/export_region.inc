@@ -121,8 +121,9 @@ __global__ __launch_bounds__(LANE_TPB) void k_q_dir(QueryArgs q) {
 	if (ns == 0u) return;
 	const uint32_t src = map[t], tag = cls[t];
 	const SimlodNode* n = a.nodes + src;
-	const SimlodChunk* head = (e.flags & SIMLOD_EXPORT_FLAG_LEAF) ? n->points : n->voxelChunks;
-	const bool rows = leaf_rows_valid(a, src, head);
+	const bool leaf = (e.flags & SIMLOD_EXPORT_FLAG_LEAF) != 0u;
+	const SimlodChunk* head = leaf ? n->points : n->voxelChunks;
+	const bool rows = leaf_rows_valid(a, src, head, leaf);
 	const uint32_t nch = ceil_chunks(ns), f = first[t];
 	auto put = [&](uint32_t k, const SimlodChunk* c) {
 		QItem it;

@@ -135,8 +135,9 @@ __global__ __launch_bounds__(LANE_TPB) void k_x_dir(ExportArgs a) {
 	if (ns == 0u) return;
 	const uint32_t src = map[t];
 	const SimlodNode* n = a.nodes + src;
-	const SimlodChunk* c = (e.flags & SIMLOD_EXPORT_FLAG_LEAF) ? n->points : n->voxelChunks;
-	const bool rows = leaf_rows_valid(a, src, c);
+	const bool leaf = (e.flags & SIMLOD_EXPORT_FLAG_LEAF) != 0u;
+	const SimlodChunk* c = leaf ? n->points : n->voxelChunks;
+	const bool rows = leaf_rows_valid(a, src, c, leaf);
 	const uint32_t nch = ceil_chunks(ns), f = first[t];
 	const uint64_t dst0 = reinterpret_cast<uint64_t>(a.samples + e.firstSample);
 	uint32_t k = 0;

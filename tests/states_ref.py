@@ -1,0 +1,428 @@
+"""Shared by tests/test_gpu_builder_states.py and tests/test_builder_states_io.py: the inputs of the builder states, the query sets one
+battery asks of every state, the guards that keep a comparison from passing on nothing, the precondition helpers, and `collapse`, which
+turns a full export into the octree a builder without free node slots leaves behind (leaves of more than 50 chunks).  Everything here is
+numpy on host arrays: nothing depends on the code under test."""
+from collections import namedtuple
+
+import numpy as np
+
+import cases
+import footprint_ref as fr
+import neighbours_ref as nr
+import oracle
+import rays_ref as yr
+import region_ref as rr
+import view_ref as vr
+from export_ref import export_host
+from simlod_amd import abi, synthetic
+from simlod_amd.octree_io import Footprint, OctreeExport, Rays, Spheres
+
+State = namedtuple("State", "dev u pts box")            # the device object, its uniforms, the points the octree holds NOW, the box
+ROW = 50                                                 # chunk addresses a row of the builder's chunk table holds (LEAF_ROW_SLOTS)
+OVER = abi.MAX_POINTS_PER_NODE                           # a leaf above this has a split pending
+N_QUERIES, K = 64, 16
+H_POINTS = 600_000                                       # the smallest multiple of 300 000 terrain points at which state H exists (test_builder_states_io)
+ERR_SPILLED, ERR_NODES = 0x2, 0x8                        # SIMLOD_ERR_SPILLED_OVERFLOW, SIMLOD_ERR_NODES_EXHAUSTED (include/simlod_hip.h)
+
+
+# ---- inputs ------------------------------------------------------------------------------------------------------------------------------------
+def a_input():
+    """State A: 600 000 uniform points in four batches; with room for nine nodes the root splits once and its eight leaves keep growing.
+    -> (points, box, batches)"""
+    pts, box = synthetic.uniform_cube(600_000, seed=5)
+    return pts, box, [pts[i:i + 150_000] for i in range(0, len(pts), 150_000)]
+
+
+def b_input():
+    """State B: A's points and 200 000 more of the same stream -> (all 800 000 points, box, the 200 000 in two batches)"""
+    pts, box = synthetic.uniform_cube(800_000, seed=5)
+    assert pts[:600_000].tobytes() == a_input()[0].tobytes()
+    return pts, box, [pts[600_000:700_000], pts[700_000:]]
+
+
+def e_input():
+    """State E: the terrain of the case terrain_4x100k, six batches of 100 000 -> (points, box, batches)"""
+    pts, box = synthetic.terrain(600_000, seed=3, box=(600.0, 400.0, 40.0), tile=50.0)
+    return pts, box, [pts[i:i + 100_000] for i in range(0, len(pts), 100_000)]
+
+
+def f_input():
+    """State F: four uniform batches of 500 000 -> (points, box, batches)"""
+    pts, box = synthetic.uniform_cube(2_000_000, seed=17)
+    return pts, box, [pts[i:i + 500_000] for i in range(0, len(pts), 500_000)]
+
+
+def c_input(n):
+    """State C: the slab of test_scarce_scratch_defers_splits_without_losing_a_point (a uniform cube with z * 0.02: leaves fill up together) with
+    n points, in batches of 500 000 -> (points, box, batches)"""
+    pts, box = synthetic.uniform_cube(n, seed=99)
+    pts["z"] *= np.float32(0.02)
+    return pts, box, [pts[i:i + 500_000] for i in range(0, len(pts), 500_000)]
+
+
+def oracle_build(box, batches, persistent=1 << 30, capacity=None, mask=None):
+    """The port oracle's octree of `batches`, one launch per batch -> (HostOctree, uniforms, allocatedBytes_persistent after each batch taken)"""
+    u = cases.uniforms_for(box, np.eye(4, dtype=np.float32), persistent=capacity or persistent)
+    ho = oracle.HostOctree("port", persistent_bytes=persistent, ring_slots=abi.BATCH_STREAM_SIZE)
+    if mask is not None:
+        ho.set_trunk_mask(*mask)
+    ho.reset(u)
+    after = []
+    for b in batches:
+        ho.upload(b)
+        ho.construct(u)
+        assert ho.last_error() == 0
+        after.append(int(ho.stats["allocatedBytes_persistent"][0]))
+    return ho, u, after
+
+
+def export_of(ho, u):
+    t, s = export_host(ho.nodes, int(ho.stats["numNodes"][0]))
+    return OctreeExport(t, s, u["boxMin"], u["boxMax"])
+
+
+def f_capacity(box, batches):
+    """State F's persistentBufferCapacity: the guard takes a batch while allocator offset + 200 MB < capacity, so a capacity midway between
+    the oracle's allocator offsets after one and after two batches (+ 200 MB) lets the second batch in and refuses the third."""
+    _, _, after = oracle_build(box, batches[:2])
+    assert after[0] < after[1]
+    return (after[0] + after[1]) // 2 + 200_000_000, after
+
+
+# ---- collapse ----------------------------------------------------------------------------------------------------------------------------------
+def collapse(ex, level=1):
+    """The full export `ex` with everything below `level` folded into its ancestor at `level`: those entries become leaves that hold the
+    points of every leaf under them (in table order), the entries above keep their voxels.  What a builder leaves that could not split
+    below `level`, up to the order of a leaf's points."""
+    t, s = ex.nodes, ex.samples
+    n = len(t)
+    lv = t["level"].astype(np.int64)
+    anc = np.arange(n)
+    par = t["parent"].astype(np.int64)
+    for i in range(1, n):                                   # (breadth-first: a parent comes before its children)
+        if lv[i] > level:
+            anc[i] = anc[par[i]]
+    keep = int((lv <= level).sum())
+    assert (lv[:keep] <= level).all()
+    out = t[:keep].copy()
+    leaf_src = (t["flags"] & abi.EXPORT_FLAG_LEAF) != 0
+    ns = t["numSamples"].astype(np.int64)
+    first = t["firstSample"].astype(np.int64)
+    parts, counts = [], np.zeros(keep, np.int64)
+    for i in range(keep):
+        if lv[i] < level and not leaf_src[i]:
+            idx = [i]                                        # an inner node above the level: its voxels
+        else:
+            idx = [j for j in np.nonzero(anc == i)[0] if leaf_src[j]]
+        for j in idx:
+            parts.append(s[first[j]: first[j] + ns[j]])
+            counts[i] += ns[j]
+    at = lv[:keep] == level
+    out["childMask"][at], out["firstChild"][at] = 0, abi.EXPORT_NONE
+    out["flags"] = np.where(out["childMask"] == 0, abi.EXPORT_FLAG_LEAF, 0) | abi.EXPORT_FLAG_SELECTED
+    out["numSamples"] = counts
+    out["firstSample"] = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.uint64)
+    samples = np.concatenate(parts) if parts else np.zeros(0, dtype=abi.point_dtype)
+    return OctreeExport(out, samples, ex.box_min, ex.box_max)
+
+
+# ---- per-node comparisons ----------------------------------------------------------------------------------------------------------------------
+def per_node(ex, leaves):
+    """The samples of the leaves (16 bytes each) or of the inner nodes (positions only: which point coloured a voxel depends on the launch),
+    sorted within each node, with the node's key in front: equal arrays <=> equal multisets per node."""
+    t = ex.nodes
+    owner = np.repeat(np.arange(len(t)), t["numSamples"].astype(np.int64))
+    pick = ((t["flags"][owner] & abi.EXPORT_FLAG_LEAF) != 0) == leaves
+    w = ex.samples.view(np.uint32).reshape(-1, 4)[pick].astype(np.uint64)
+    if not leaves:
+        w[:, 3] = 0
+    from util import node_keys
+    key = node_keys(t)[owner[pick]]
+    rows = np.concatenate([key[:, None], w], axis=1)
+    return rows[np.lexsort([rows[:, c] for c in range(4, -1, -1)])]
+
+
+def assert_same_per_node(got, want, what):
+    assert got.nodes.tobytes() == want.nodes.tobytes(), f"{what}: the tables differ"
+    for leaves in (True, False):
+        assert np.array_equal(per_node(got, leaves), per_node(want, leaves)), f"{what}: the samples differ per node (leaves={leaves})"
+
+
+# ---- preconditions -----------------------------------------------------------------------------------------------------------------------------
+def overfull_leaves(table):
+    """The leaf entries of an export's table that hold more than SIMLOD_MAX_POINTS_PER_NODE samples."""
+    t = np.asarray(table)
+    return np.nonzero(((t["flags"] & abi.EXPORT_FLAG_LEAF) != 0) & (t["numSamples"] > OVER))[0]
+
+
+def assert_state_a(dbg, table):
+    """Node array full: the error bit, nine nodes, eight leaves of more than 50 000 points (more chunks than a table row has slots)."""
+    assert int(dbg) == ERR_NODES, f"Stats.dbg {int(dbg):#x}"
+    assert len(table) == 9, f"{len(table)} nodes"
+    over = overfull_leaves(table)
+    assert len(over) == 8 and (table["level"][over] == 1).all(), f"{len(over)} over-full leaves"
+    assert (table["numSamples"][over] > ROW * abi.POINTS_PER_CHUNK).all()
+
+
+def assert_state_c(dbg, table):
+    """Scarce scratch: the spill bit alone, at least one leaf with a pending split beside leaves that did split (an inner node below the root)."""
+    assert int(dbg) == ERR_SPILLED, f"Stats.dbg {int(dbg):#x}"
+    assert len(overfull_leaves(table)) >= 1, "no leaf with a pending split"
+    assert int(((table["flags"] & abi.EXPORT_FLAG_LEAF) == 0).sum()) > 1, "no leaf split"
+    return len(overfull_leaves(table))
+
+
+def assert_stopped_short(stats, taken, pending, guard=False):
+    """A launch sequence that left batches pending: `taken` ingested, `pending` of them still in the ring (the host knows how many it uploaded)."""
+    assert int(stats["dbg"]) == 0 and int(stats["batchletIndex"]) == taken and pending > 0, (int(stats["dbg"]), int(stats["batchletIndex"]), pending)
+    assert int(stats["memCapacityReached"]) == int(guard), f"memCapacityReached {int(stats['memCapacityReached'])}"
+
+
+def assert_no_overfull(table):
+    over = overfull_leaves(table)
+    assert len(over) == 0, f"{len(over)} leaves above {OVER} points, the largest {int(np.asarray(table)['numSamples'][over].max())}"
+
+
+def h_input(partition, n=H_POINTS):
+    """State H: rank 0's share of an n-point terrain split over two ranks (partition: test_gpu_trunk._partition), in batches of 300 000
+    -> (all points, box, the trunk mask, the rank's points, its batches)"""
+    pts, box = synthetic.terrain(n, seed=4, box=(600.0, 400.0, 40.0))
+    dest, mask = partition(pts, box, 2)
+    mine = pts[dest == 0]
+    return pts, box, tuple(int(m) for m in mask), mine, [mine[i:i + 300_000] for i in range(0, len(mine), 300_000)]
+
+
+def points_in_nodes(table, pts, box):
+    """How many of `pts` lie in the cube of each table entry (the builder's cell arithmetic: floor(2^level * p / size), fp32)."""
+    size = np.float32(max(box))
+    out = np.zeros(len(table), np.int64)
+    for lv in np.unique(table["level"]):
+        at = np.nonzero(table["level"] == lv)[0]
+        c = [np.minimum((np.float32(2.0 ** int(lv)) * pts[a] / size).astype(np.int64), 2 ** int(lv) - 1) for a in "xyz"]
+        key = (c[0] << 42) | (c[1] << 21) | c[2]
+        keys, cnt = np.unique(key, return_counts=True)
+        want = (table["X"][at].astype(np.int64) << 42) | (table["Y"][at].astype(np.int64) << 21) | table["Z"][at].astype(np.int64)
+        pos = np.searchsorted(keys, want)
+        hit = (pos < len(keys)) & (keys[np.minimum(pos, len(keys) - 1)] == want)
+        out[at] = np.where(hit, cnt[np.minimum(pos, len(keys) - 1)], 0)
+    return out
+
+
+def assert_masked_rank(table, pts, mine, box, mask):
+    """State H: a mask is set, and it forces something — at least one node of the rank's octree holds none of the rank's points although the
+    whole input has points in its cube (it exists for the other rank's sake).  -> how many"""
+    assert tuple(int(m) for m in mask) != (0, 0), "no trunk mask"
+    forced = int(((points_in_nodes(table, mine, box) == 0) & (points_in_nodes(table, pts, box) > 0)).sum())
+    assert forced >= 1, "every node holds points of the rank or of nobody: the mask forces nothing"
+    return forced
+
+
+# ---- the battery's queries and their guards ----------------------------------------------------------------------------------------------------
+Queries = namedtuple("Queries", "region footprint rays spheres radius")
+
+
+def queries(pts, box):
+    """One query of each kind for an octree that holds `pts` in `box`, made from the points alone (a launch that stopped short holds
+    points in a part of its box only, the hotspot in one level-3 cell: every query is placed by the points' bounding box, `the cube` below is
+    its larger xy extent — for a filled box the octree's cube): region_ref's oblique half-space through the middle of that box; a
+    seven-pointed star around the xy middle of its lower-left quarter, radii 0.6 and 0.5 of the cube — the LINE through any of its
+    edges passes the middle at 0.49, outside the quarter's corners at 0.3536, so rule F3 finds every edge far from the nodes over that
+    quarter and they are copied whole, while the nodes its points cross are filtered; 64 rays, each through a chosen point from 0.3 extents
+    away in a random direction, and 64 spheres at the same points, with the radius at which a sphere around a chosen point holds 32 points in
+    the median (twice k = 16: the top-k drops something; a ray's cylinder of half that radius holds its own point and, in the median, more)."""
+    lo = np.array([float(pts[a].min()) for a in "xyz"])
+    ext = np.array([float(pts[a].max()) for a in "xyz"]) - lo
+    size = float(ext[:2].max())
+    star = Footprint.from_xy(fr.star(lo[0] + 0.25 * size, lo[1] + 0.25 * size, 0.6 * size, 0.5 * size, 7))
+    rs = np.random.RandomState(77)
+    at = np.sort(rs.choice(len(pts), N_QUERIES, replace=False))
+    c = np.stack([pts[a][at] for a in "xyz"], axis=1).astype(np.float64)
+    xyz = np.stack([pts[a] for a in "xyz"], axis=1).astype(np.float64)
+    d32 = np.array([np.partition(((xyz - q) ** 2).sum(1), 2 * K)[2 * K] for q in c])
+    radius = float(np.sqrt(np.median(d32)))
+    d = rs.randn(N_QUERIES, 3)
+    d *= 0.3 * nr.extent(pts) / np.linalg.norm(d, axis=1)[:, None]
+    rays = Rays(c - d, d, 0.0, 2.0, 0.5 * radius, 0.0)
+    return Queries(rr.region("oblique", ext, lo), star, rays, Spheres(c, radius), radius)
+
+
+def assert_crop_not_vacuous(cnt, what, copies=True):
+    """As the region and footprint modules guard theirs: some nodes copied whole, some filtered, and the filter drops something.
+    copies=False: an octree on which the query CANNOT copy a node (state A's root and eight octants under a plane through the middle) — then
+    none is, and every node with samples is filtered."""
+    copied, filtered = int(cnt["numCopiedNodes"]), int(cnt["numFilteredNodes"])
+    assert (copied > 0 if copies else copied == 0) and filtered > 0, f"{what}: {copied} copied / {filtered} filtered"
+    assert 0 < int(cnt["numSamples"]) < int(cnt["numCandidates"]), f"{what}: {int(cnt['numSamples'])} of {int(cnt['numCandidates'])} candidates"
+
+
+def assert_rays_not_vacuous(hits, passing, what):
+    yr.assert_not_vacuous(hits, False, what)
+    hit = hits["node"] != abi.EXPORT_NONE
+    assert float((passing[hit] > 1).mean()) >= 0.5, f"{what}: the arg-min has nothing to choose from"
+
+
+def assert_spheres_not_vacuous(within, what):
+    nr.assert_wide_not_vacuous(within, what, K)
+
+
+def view_uniforms(box, camera="closer"):
+    """The uniforms of the battery's view on the host (the device's differ in the buffer capacities, which no view rule reads)."""
+    return vr.uniforms_of(box, vr.transform_of(camera, box))
+
+
+def coarser_budget(ladder):
+    """A sample budget that bias 0 misses and a later bias fits: S(b) of the first b with 0 < S(b) < S(0) -> (budget, b)"""
+    for b in range(1, len(ladder)):
+        if all(s > ladder[b] for s in ladder[:b]) and 0 < ladder[b]:
+            return ladder[b], b
+    raise AssertionError(f"no coarser cut with samples in the ladder {ladder}")
+
+
+def assert_view_not_vacuous(cnt, what):
+    assert int(cnt["error"]) == 0 and 0 < int(cnt["numSelected"]) and 0 < int(cnt["numSamples"]), f"{what}: {cnt}"
+
+
+def assert_delta_not_vacuous(delta, what, adds=True):
+    """The bias-2 cut against the bias-0 cut: the finer cut adds nodes and sends their samples.  adds=False: an octree whose two cuts are the
+    same nodes (state A: the eight leaves or nothing) — everything is kept and nothing is sent."""
+    s = delta.entries["state"]
+    if adds:
+        assert delta.num_samples > 0 and int((s == abi.DELTA_ADDED).sum()) > 0, f"{what}: nothing added"
+    else:
+        assert delta.num_samples == 0 and int((s == abi.DELTA_KEPT).sum()) > 0 and int((s == abi.DELTA_ADDED).sum()) == 0, f"{what}: not all kept"
+
+
+# ---- the mirrors of one battery, guarded and held against brute force ------------------------------------------------------------------------
+# What the guards can ask of an octree, stated per state (a flag that is False asserts the OPPOSITE, so each is a fact about the octree and not
+# a check left out): `camera` of the view; whether the region / the footprint copies a node whole; whether the bias-0 cut adds nodes to the
+# bias-2 cut; whether the view's ladder has a coarser rung with samples (without one a budget of S(0) - 1 chooses the first EMPTY cut).
+Shape = namedtuple("Shape", "camera region_copies footprint_copies delta_adds coarser", defaults=("closer", True, True, True, True))
+NINE_NODES = Shape("inside", region_copies=False, delta_adds=False)     # a root and eight leaves: the plane through the middle cuts all eight
+ROOT_LEAF = Shape("closer", False, False, False, False)                 # one node: filtered by everything, the only cut there is
+
+
+def mirrors(full, pts, uv, what, shape=Shape(), pairs_all=False):
+    """What the battery expects of an octree whose anchored full export is `full` and which holds `pts`, from the numpy mirrors alone: every
+    answer guarded (above), the cuts equal to the brute-force filters of `pts`, the rays' t and the spheres' d2 bit-equal to the brute force
+    over `pts`, the delta consistent in itself.  `uv`: the view's uniforms at bias 0.  pairs_all: rays and spheres with select "all" too."""
+    import delta_ref
+    from simlod_amd.octree_io import Region
+    mn, size = np.asarray(full.box_min, np.float64), np.asarray(full.box_max, np.float64) - np.asarray(full.box_min, np.float64)
+    assert not mn.any()
+    q = queries(pts, tuple(size))
+    m = {"q": q, "crop": {}, "rays": {}, "spheres": {}}
+    for kind, region, foot in (("region", q.region, None), ("footprint", Region(), q.footprint)):
+        for sel in ("cut", "all"):
+            m["crop"][kind, sel] = full.crop(region, 20, sel, return_counts=True, footprint=foot)
+        assert_crop_not_vacuous(m["crop"][kind, "cut"][1], f"{what} {kind}", shape.region_copies if kind == "region" else shape.footprint_copies)
+    rr.assert_same_multiset(m["crop"]["region", "cut"][0].samples, pts[rr.brute_mask(q.region, pts)], f"{what} region")
+    rr.assert_same_multiset(m["crop"]["footprint", "cut"][0].samples, pts[fr.contains_exact(q.footprint, pts)], f"{what} footprint")
+    for sel in ("cut", "all") if pairs_all else ("cut",):
+        hits, cnt, passing = full.cast(q.rays, 20, sel, return_counts=True, return_passing=True)
+        nb, within, ncnt = full.neighbours(q.spheres, K, 20, sel, return_counts=True)
+        m["rays"][sel], m["spheres"][sel] = (hits, cnt), (nb, within, ncnt)
+        if sel == "cut":
+            assert_rays_not_vacuous(hits, passing, f"{what} rays")
+            assert_spheres_not_vacuous(within, f"{what} spheres")
+            assert_hits_are_brute(hits, q.rays, pts, f"{what} rays")
+            nr.assert_found_are_brute(nb, within, q.spheres, pts, K, f"{what} spheres")
+    m["view"] = full.view(uv, return_counts=True)
+    assert_view_not_vacuous(m["view"][1], f"{what} view")
+    ladder = [int(v) for v in m["view"][1]["samplesAt"]]
+    if shape.coarser:
+        m["budget"], b = coarser_budget(ladder)
+        m["coarser"] = full.view(uv, budget=m["budget"], return_counts=True)
+        assert int(m["coarser"][1]["bias"]) == b > 0 and int(m["coarser"][1]["error"]) == 0 and 0 < int(m["coarser"][1]["numSamples"]) < ladder[0]
+    else:
+        assert all(s in (0, ladder[0]) for s in ladder), f"{what}: the ladder {ladder} has a coarser rung"
+        m["budget"] = ladder[0] - 1
+        m["coarser"] = full.view(uv, budget=m["budget"], return_counts=True)
+        assert (int(m["coarser"][1]["error"]), int(m["coarser"][1]["numSamples"])) == (0, 0) and int(m["coarser"][1]["bias"]) > 0     # the empty cut fits
+    m["held"] = full.view(uv, bias=2)
+    m["delta"] = full.view_delta(uv, m["held"], tails=True)
+    assert_delta_not_vacuous(m["delta"], f"{what} delta", shape.delta_adds)
+    delta_ref.assert_delta_consistent(m["delta"], m["held"], m["view"][0])
+    return m
+
+
+def assert_hits_are_brute(hits, rays, pts, what):
+    """rays_ref.assert_hits_are_brute with one pass over the points per ray: hit / miss, t bit-equal to the brute-force minimum of rule 2 over
+    `pts`, and the sample one of the input points that attain it."""
+    rec = rays.record()
+    x, y, z = (pts[a].astype(np.float64) for a in "xyz")
+    keys = pts.view(np.uint64).reshape(-1, 2)
+    for i in range(len(rec)):
+        t, ok = yr.sample_test(rec, i, x, y, z)
+        if not ok.any():
+            assert hits["node"][i] == abi.EXPORT_NONE and np.isposinf(hits["t"][i]), f"{what}: ray {i} hits, the brute force misses"
+            continue
+        tmin = t[ok].min()
+        assert hits["node"][i] != abi.EXPORT_NONE and hits["t"][i:i + 1].view(np.uint64)[0] == np.float64(tmin).view(np.uint64), f"{what}: ray {i}: t {hits['t'][i]} against {tmin}"
+        best = np.nonzero(ok & (t == tmin))[0]
+        smp = np.ascontiguousarray(hits["sample"][i:i + 1]).view(np.uint64).reshape(2)
+        assert ((keys[best, 0] == smp[0]) & (keys[best, 1] == smp[1])).any(), f"{what}: ray {i}'s sample is not an input point at the minimum"
+
+
+def held_table(view, counts):
+    """`view` (a cut) with the sample counts of its first len(counts) selected entries lowered to `counts`: what a receiver holds that saw
+    those nodes when they were shorter -> (OctreeExport, the entries' indices)"""
+    import delta_ref
+    return delta_ref.lowered(view, counts=tuple(counts), floor=max(counts))
+
+
+# ---- the states' shapes, and their oracle twins ----------------------------------------------------------------------------------------------------
+# (what the GPU tier passes to the battery; tests/test_builder_states_io.py holds every one of them against the oracle's octree of the same input)
+SHAPES = {"A": NINE_NODES, "C": Shape(), "D hotspot_150k": Shape(region_copies=False), "D dense_cube": Shape(), "E": Shape(), "E1": Shape(delta_adds=False), "F": Shape(), "H": Shape(),
+          "G 600000 poisoned": Shape(), "G 600000 continued": Shape(), "G 90000 poisoned": ROOT_LEAF, "G 90000 continued": Shape("inside", delta_adds=False, coarser=False),
+          "I A": Shape("bird"), "I B": Shape("inside", delta_adds=False)}
+G_CASES = [(600_000, 300_000, 100_000), (90_000, 30_000, 15_000)]
+
+
+def d_input(name):
+    """State D's inputs -> (points, box, batches, how many of them are built before the resume's export).  The hotspot in batches of 100 000
+    and 50 000: its root splits in the first batch whatever the granularity (a root that ends a batch as a leaf samples itself, and what its
+    voxel list keeps of that depends on where the batches end)."""
+    if name == "hotspot_150k":
+        pts, box, _, _ = cases.case(name)
+        return pts, box, [pts[:100_000], pts[100_000:]], 1
+    pts, box = synthetic.uniform_cube(600_000, seed=9)
+    return pts, box, [pts[i:i + 200_000] for i in range(0, len(pts), 200_000)], 2
+
+
+def g_input(total, first, batch):
+    pts, box = synthetic.terrain(total, seed=7)
+    return pts, box, [pts[i:i + batch] for i in range(0, total, batch)], first // batch
+
+
+def twin(name, partition=None):
+    """The oracle's octree of a state's input -> (full export, the points it holds, box, the Shape the GPU tier uses, the HostOctree)"""
+    key = name
+    if name == "A":
+        pts, box, batches = a_input()
+    elif name.startswith("E"):
+        pts, box, batches = e_input()
+        batches, key = batches[: int(name[1:])], name if name in SHAPES else "E"
+    elif name == "F":
+        pts, box, batches = f_input()
+        ho, u, _ = oracle_build(box, batches, capacity=f_capacity(box, batches)[0])
+        taken = int(ho.stats["batchletIndex"][0])
+        return export_of(ho, u), np.concatenate(batches[:taken]), box, SHAPES[key], ho
+    elif name == "H":
+        allpts, box, mask, mine, batches = h_input(partition)
+        ho, u, _ = oracle_build(box, batches, mask=mask)
+        return export_of(ho, u), mine, box, SHAPES[key], ho
+    elif name.startswith("D "):
+        pts, box, batches, _ = d_input(name[2:])
+    elif name.startswith("G "):
+        total, when = name.split()[1:]
+        pts, box, batches, cut = g_input(*[c for c in G_CASES if c[0] == int(total)][0])
+        batches = batches[:cut] if when == "poisoned" else batches
+    elif name.startswith("I "):
+        case = "terrain_4x100k" if name == "I A" else "uniform_3x40k"
+        pts, box, batch, _ = cases.case(case)
+        batches = cases.batches_of(case, pts, batch)
+    else:
+        raise KeyError(name)
+    ho, u, _ = oracle_build(box, batches)
+    ex = export_of(ho, u)
+    return (collapse(ex) if name == "A" else ex), np.concatenate(batches), box, SHAPES[key], ho

@@ -1,0 +1,189 @@
+"""CPU tier of tests/test_gpu_builder_states.py: what that module holds the device against must stand on its own first.  `collapse` (the
+mirrors' first leaves of more than 50 chunks) against brute force and against itself; the oracle twins of the states, each through the
+guards the GPU battery uses, with the Shape it uses; the oracle's continuous build that a resumed import of over-full leaves must reach; and
+the precondition helpers, each against a hand-made input that does not take the path.  Oracle, numpy mirrors and brute force only."""
+import numpy as np
+import pytest
+
+import cases
+import delta_ref
+import neighbours_ref as nr
+import rays_ref as yr
+import region_ref as rr
+import states_ref as sr
+from simlod_amd import abi
+from simlod_amd.octree_io import delta_between
+from test_gpu_trunk import _partition
+
+_TWINS = {}
+
+
+def _twin(name):
+    if name not in _TWINS:
+        _TWINS[name] = sr.twin(name, _partition)
+    return _TWINS[name]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _release(built_libs):
+    yield
+    _TWINS.clear()
+
+
+# ---- collapse ----------------------------------------------------------------------------------------------------------------------------------
+def test_collapse_is_an_octree_of_overfull_leaves_that_holds_the_input(built_libs):
+    c, pts, box, shape, ho = _twin("A")
+    c.validate(buildable=True)
+    sr.assert_state_a(sr.ERR_NODES, c.nodes)
+    n = c.nodes["numSamples"][1:]
+    assert (int(n.min()), int(n.max())) == (74_517, 75_680) and ((n + 999) // 1000 > sr.ROW).all()      # 75 or 76 chunks: the row and 25 behind it
+    rr.assert_same_multiset(c.truncated(20, "cut").samples, pts, "collapse")
+    pts3 = np.concatenate(sr.a_input()[2][:3])
+    ho3, u3, _ = sr.oracle_build(box, sr.a_input()[2][:3])
+    n3 = sr.collapse(sr.export_of(ho3, u3)).nodes["numSamples"][1:]
+    assert (int(n3.min()), int(n3.max())) == (55_905, 56_863) and int(n3.sum()) == len(pts3)
+    # folding nothing changes nothing; the leaves of a level-1 collapse are the oracle's subtrees
+    full = sr.export_of(ho, cases.uniforms_for(box, np.eye(4, dtype=np.float32)))
+    deep = sr.collapse(full, 20)
+    assert deep.nodes.tobytes() == full.nodes.tobytes() and deep.samples.tobytes() == full.samples.tobytes()
+    assert c.nodes["numSamples"][0] == full.nodes["numSamples"][0] and c.samples[: int(c.nodes["numSamples"][0])].tobytes() == full.samples[: int(full.nodes["numSamples"][0])].tobytes()
+
+
+def test_mirrors_on_the_collapsed_octree_agree_with_brute_force_and_each_other(built_libs):
+    c, pts, box, shape, _ = _twin("A")
+    m = sr.mirrors(c, pts, sr.view_uniforms(box, shape.camera), "A (collapsed)", shape, pairs_all=True)
+    q = m["q"]
+    for sel in ("cut", "all"):
+        table = c.truncated(20, sel)
+        hits, cnt = m["rays"][sel]
+        assert hits.tobytes() == yr.exhaustive(table, q.rays).tobytes(), f"cast {sel} against the exhaustive search"
+        yr.assert_hits_index_export(hits, table, f"cast {sel}")
+        nb, within, _ = m["spheres"][sel]
+        want, ww = nr.exhaustive(table, q.spheres, sr.K)
+        assert nb.tobytes() == want.tobytes() and np.array_equal(within, ww), f"neighbours {sel} against the exhaustive search"
+        nr.assert_found_index_export(nb, table, f"neighbours {sel}")
+    # hits and neighbours behind the row: ordinals of 50 000 and more
+    assert int((m["rays"]["cut"][0]["ordinal"][m["rays"]["cut"][0]["node"] != abi.EXPORT_NONE] >= sr.OVER).sum()) >= 8
+    f = m["spheres"]["cut"][0]
+    assert int((f["ordinal"][f["node"] != abi.EXPORT_NONE] >= sr.OVER).sum()) >= 64
+    # the crops keep whole leaves (the star) and parts of them, and a crop is an octree
+    for key, (crop, cnt) in m["crop"].items():
+        crop.validate()
+    assert int(m["crop"]["footprint", "cut"][1]["numCopiedNodes"]) == 2
+    assert int(m["delta"].counts["numKept"]) == 5 and int(m["coarser"][1]["bias"]) == 6
+
+
+def test_held_counts_around_the_row_end_send_exactly_the_tails(built_libs):
+    """A receiver that holds 49 999, 50 000, 50 001 and 56 000 samples of four 75 000-sample leaves: with tails the delta is samples[held:] of
+    each — first pieces that begin in chunk 49 (the row's last slot), 50 (the first behind it) and 56 —, without them the leaves come whole."""
+    c, pts, box, shape, _ = _twin("A")
+    fresh = c.view(sr.view_uniforms(box, "closer"))
+    assert int(((fresh.nodes["flags"] & abi.EXPORT_FLAG_SELECTED) != 0).sum()) == 8 and fresh.num_samples == len(pts)
+    counts = (49_999, 50_000, 50_001, 56_000)
+    held, idx = sr.held_table(fresh, counts)
+    assert [int(v) for v in held.nodes["numSamples"][idx]] == list(counts) and [k // 1000 for k in counts] == [49, 50, 50, 56]
+    d = delta_between(fresh, held, tails=True)
+    delta_ref.assert_delta_consistent(d, held, fresh)
+    want = np.concatenate([fresh.samples[int(a) + k: int(a) + int(n)] for a, k, n in zip(fresh.nodes["firstSample"][idx], counts, fresh.nodes["numSamples"][idx])])
+    assert d.samples.tobytes() == want.tobytes() and delta_ref.states(d) == (4, 4, 0, 0)
+    w = delta_between(fresh, held, tails=False)
+    delta_ref.assert_delta_consistent(w, held, fresh)
+    assert delta_ref.states(w) == (4, 0, 4, 4) and w.num_samples == int(fresh.nodes["numSamples"][idx].astype(np.int64).sum())
+
+
+# ---- the oracle twins of the states ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["E1", "E2", "E3", "E4", "E5", "F", "H", "D hotspot_150k", "D dense_cube", "G 600000 poisoned", "G 600000 continued",
+                                  "G 90000 poisoned", "G 90000 continued", "I A", "I B"])
+def test_oracle_twin_passes_the_guards_of_its_state(built_libs, name):
+    """The battery's mirrors on the oracle's octree of the state's input, with the Shape the GPU tier passes: every guard holds, the cuts are
+    the brute-force filters, t and d2 are the brute force's.  (E1 .. E5: whatever number of batches a launch under the time budget takes.)"""
+    ex, pts, box, shape, ho = _twin(name)
+    ex.validate(buildable=True)
+    rr.assert_same_multiset(ex.truncated(20, "cut").samples, pts, name)
+    sr.mirrors(ex, pts, sr.view_uniforms(box, shape.camera), name, shape)
+
+
+def test_twin_of_e_is_the_octree_of_two_of_six_batches(built_libs):
+    ex, pts, box, _, ho = _twin("E2")
+    st = ho.stats[0]
+    sr.assert_stopped_short(st, 2, len(sr.e_input()[2]) - 2)
+    assert len(pts) == 200_000 == int(st["numPoints"]) and ex.num_nodes == 41
+
+
+def test_twin_of_f_stops_at_the_guard_between_the_first_and_the_third_batch(built_libs):
+    pts, box, batches = sr.f_input()
+    cap, after = sr.f_capacity(box, batches)
+    assert after[0] + 200_000_000 < cap < after[1] + 200_000_000        # the second batch is let in, the third is not
+    ex, held, _, _, ho = _twin("F")
+    sr.assert_stopped_short(ho.stats[0], 2, 2, guard=True)
+    assert len(held) == 1_000_000 and int(ho.stats["allocatedBytes_persistent"][0]) == after[1]
+
+
+def test_twin_of_h_has_nodes_the_mask_forces(built_libs):
+    pts, box, mask, mine, batches = sr.h_input(_partition)
+    ex, _, _, _, _ = _twin("H")
+    assert sr.assert_masked_rank(ex.nodes, pts, mine, box, mask) == 9
+    # ... and half the points are too few: the mask of 300 000 names nodes that every rank splits anyway
+    p2, b2, m2, mine2, bt2 = sr.h_input(_partition, 300_000)
+    ho2, u2, _ = sr.oracle_build(b2, bt2, mask=m2)
+    with pytest.raises(AssertionError, match="forces nothing"):
+        sr.assert_masked_rank(sr.export_of(ho2, u2).nodes, p2, mine2, b2, m2)
+
+
+def test_twin_of_b_is_the_level_2_octree_the_resume_must_reach(built_libs):
+    pts, box, more = sr.b_input()
+    ho, u, _ = sr.oracle_build(box, sr.a_input()[2] + more)
+    ex = sr.export_of(ho, u)
+    sr.assert_no_overfull(ex.nodes)
+    t = ex.nodes
+    leaf = (t["flags"] & abi.EXPORT_FLAG_LEAF) != 0
+    assert ex.num_nodes == 73 and [int((t["level"] == l).sum()) for l in range(3)] == [1, 8, 64]
+    assert not leaf[t["level"] < 2].any() and leaf[t["level"] == 2].all() and int(t["numSamples"][leaf].sum()) == 800_000
+    # every one of the 200 000 resumed points' octants is touched
+    octant = (pts["x"][600_000:] >= 0.5).astype(int) * 4 + (pts["y"][600_000:] >= 0.5).astype(int) * 2 + (pts["z"][600_000:] >= 0.5).astype(int)
+    assert len(np.unique(octant)) == 8
+
+
+# ---- the precondition helpers reject what does not take the path ---------------------------------------------------------------------------------
+def test_precondition_helpers_reject_octrees_off_the_path(built_libs):
+    c, pts, box, _, ho = _twin("A")
+    sr.assert_state_a(sr.ERR_NODES, c.nodes)
+    with pytest.raises(AssertionError):
+        sr.assert_state_a(0, c.nodes)                                    # no error bit: the node array was not full
+    uncollapsed = _twin("D dense_cube")[0]
+    with pytest.raises(AssertionError):
+        sr.assert_state_a(sr.ERR_NODES, uncollapsed.nodes)               # 73 nodes: the splits went through
+    small = c.nodes.copy()
+    small["numSamples"][3] = sr.OVER                                     # a leaf that is exactly full has nothing pending
+    with pytest.raises(AssertionError):
+        sr.assert_state_a(sr.ERR_NODES, small)
+    with pytest.raises(AssertionError):
+        sr.assert_no_overfull(c.nodes)
+    sr.assert_no_overfull(uncollapsed.nodes)
+    # state C: the spill bit alone, a pending leaf beside a split one
+    mixed = uncollapsed.nodes.copy()
+    first_leaf = int(np.nonzero((mixed["flags"] & abi.EXPORT_FLAG_LEAF) != 0)[0][0])
+    mixed["numSamples"][first_leaf] = sr.OVER + 1
+    assert sr.assert_state_c(sr.ERR_SPILLED, mixed) == 1
+    for dbg, table in ((0, mixed), (sr.ERR_SPILLED | sr.ERR_NODES, mixed), (sr.ERR_SPILLED, uncollapsed.nodes), (sr.ERR_SPILLED, c.nodes[:1])):
+        with pytest.raises(AssertionError):
+            sr.assert_state_c(dbg, table)
+    # a launch that stopped short
+    st = np.zeros(1, dtype=abi.stats_dtype)[0]
+    st["batchletIndex"] = 2
+    sr.assert_stopped_short(st, 2, 4)
+    for taken, pending, guard in ((3, 3, False), (2, 0, False), (2, 4, True)):
+        with pytest.raises(AssertionError):
+            sr.assert_stopped_short(st, taken, pending, guard)
+    # the guards
+    with pytest.raises(AssertionError):
+        sr.coarser_budget([600_000, 600_000, 600_000, 0, 0])
+    assert sr.coarser_budget([9, 9, 5, 7, 0]) == (5, 2)
+    cnt = np.zeros((), dtype=abi.query_counts_dtype)
+    cnt["numSamples"], cnt["numCandidates"], cnt["numFilteredNodes"] = 5, 10, 3
+    sr.assert_crop_not_vacuous(cnt, "hand-made", copies=False)
+    with pytest.raises(AssertionError):
+        sr.assert_crop_not_vacuous(cnt, "hand-made")
+    cnt["numCopiedNodes"], cnt["numSamples"] = 1, 10
+    with pytest.raises(AssertionError):
+        sr.assert_crop_not_vacuous(cnt, "hand-made")

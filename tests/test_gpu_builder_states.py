@@ -1,0 +1,455 @@
+"""GPU tier: export and every query of the read side (export.hip) on each octree state an ingest can leave behind — a full node array
+(leaves of 75 chunks, half again a chunk-table row), an import of those leaves and the resumed ingest that has to split them, deferred splits,
+coalesced mode, a launch that stopped short with no host wait before the export, a tripped memory guard, a foreign image, a rank's octree
+under a trunk mask, two octrees in one context and a rebuild in the same buffers.  Every state first asserts its precondition from Stats and
+the downloaded image, then goes through ONE battery: the export anchored byte for byte to export_ref.export_host of the downloaded image,
+the chunk table's stamp through the rasteriser's counter, one query of each kind against the numpy mirrors on the anchored export (guarded
+and held against brute force over the points the octree holds, tests/states_ref.py), and all of it again with the table dropped."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import cases
+import oracle
+import region_ref as rr
+import states_ref as sr
+import test_gpu_footprint as on_footprints
+import test_gpu_neighbours as on_spheres
+import test_gpu_rays as on_rays
+import test_gpu_region as on_regions
+import test_gpu_view as on_view
+import test_gpu_view_delta as on_delta
+import view_ref as vr
+from export_ref import export_host
+from simlod_amd import abi, synthetic
+from simlod_amd.octree_io import OctreeExport
+from states_ref import State
+from test_gpu_deep_octrees import _count_fields, _feed_one_by_one, _feed_one_group
+from test_gpu_export import _assert_export, _device, _frames_equal
+from test_gpu_parity import GRANULARITY_FREE_FIELDS
+from test_gpu_resume import _assert_fields, _feed, _import, _resume_batches
+from test_gpu_trunk import _partition
+from util import host_image_of, points_multiset_hash
+
+pytestmark = pytest.mark.gpu
+W, H = cases.W, cases.H
+NODE_CAPACITY = 263_157
+
+
+# ---- the battery -----------------------------------------------------------------------------------------------------------------------------
+def _anchor(S, what):
+    """Point 1: the full export, the cut one level above the deepest and `visible` after a frame, each byte-equal to export_host of the
+    downloaded image; the cut's samples are the points held.  -> (the anchored full export, chunk lists the frame read through the table)"""
+    dev, u = S.dev, S.u
+    nodes, pers, nn = host_image_of(dev)
+    t, s = export_host(nodes, nn)
+    full = dev.export_octree(u)
+    _assert_export(full, t, s, f"{what} all@20")
+    ml = max(int(t["level"].max()) - 1, 0)
+    tc, sc = export_host(nodes, nn, ml, abi.EXPORT_CUT)
+    _assert_export(dev.export_octree(u, max_level=ml, select="cut"), tc, sc, f"{what} cut@{ml}")
+    rr.assert_same_multiset(full.truncated(20, "cut").samples, S.pts, f"{what}: the cut against the points held")
+    # the stamp's frame: minNodeSize 1 makes every node on the screen large, so leaves are drawn — the rasteriser takes a list from the table only
+    # when it fits a row, and the inner nodes the cases' frames draw of a dense octree hold more voxel chunks than that
+    us = np.array(u, copy=True)
+    us["minNodeSize"] = 1.0
+    dev.render(us)
+    used = dev.lists_read_through_table()
+    dev.render(u)
+    nodes, pers, nn = host_image_of(dev)
+    tv, sv = export_host(nodes, nn, 20, abi.EXPORT_VISIBLE)
+    assert len(sv) > 0, f"{what}: the frame draws nothing"
+    _assert_export(dev.export_octree(u, select="visible"), tv, sv, f"{what} visible")
+    return full, used
+
+
+def _crops(S, M, what):
+    for (kind, sel), (mirror, cnt) in M["crop"].items():
+        q = M["q"]
+        mk = (lambda **kw: on_regions.Raw(S.dev, S.u, q.region, 20, sel, **kw)) if kind == "region" else (lambda **kw: on_footprints.Raw(S.dev, S.u, q.footprint, None, 20, sel, **kw))
+        (on_regions if kind == "region" else on_footprints)._assert_matches(mk(), mirror, cnt, f"{what} {kind} {sel}")
+        only = mk(count_only=True)
+        assert only.rc == 0 and _count_fields(only.counts) == _count_fields(cnt), f"{what} {kind} {sel}: the count-only call"
+
+
+def _pairs(S, full, M, what):
+    q = M["q"]
+    for sel, (hits, cnt) in M["rays"].items():
+        on_rays._assert_matches(on_rays.Raw(S.dev, S.u, q.rays, 20, sel), hits, cnt, f"{what} rays {sel}", full.truncated(20, sel))
+        only = on_rays.Raw(S.dev, S.u, q.rays, 20, sel, count_only=True)
+        assert only.rc == 0 and _count_fields(only.counts) == _count_fields(cnt), f"{what} rays {sel}: the count-only call"
+    for sel, want in M["spheres"].items():
+        on_spheres._assert_matches(on_spheres.Raw(S.dev, S.u, q.spheres, sr.K, 20, sel), want, f"{what} spheres {sel}", full.truncated(20, sel))
+        only = on_spheres.Raw(S.dev, S.u, q.spheres, sr.K, 20, sel, count_only=True)
+        fields = on_spheres.COUNT_FIELDS
+        assert only.rc == 0 and all(int(only.counts[f]) == int(want[2][f]) for f in fields[:6]) and int(only.counts["numFound"]) == 0, f"{what} spheres {sel}: the count-only call"
+
+
+def _views(S, uv, M, what):
+    dev = S.dev
+    for tag, view, (mirror, cnt) in (("view", abi.view_record(), M["view"]), ("budget", abi.view_record(budget=M["budget"]), M["coarser"])):
+        on_view._assert_matches(on_view.Raw(dev, uv, view), mirror, cnt, f"{what} {tag}")
+        only = on_view.Raw(dev, uv, view, count_only=True)
+        assert only.rc == 0 and only.counts.tobytes() == cnt.tobytes() and only.poison_behind(mirror.num_nodes, 0), f"{what} {tag}: the count-only call"
+    raw = on_delta.RawDelta(dev, uv, M["held"], abi.view_record(), tails=True)
+    on_delta._assert_delta(raw, M["delta"], f"{what} delta")
+    on_delta._assert_merge(dev, raw, M["held"], uv, abi.view_record(), f"{what} delta")
+    only = on_delta.RawDelta(dev, uv, M["held"], abi.view_record(), tails=True, count_only=True)
+    assert only.rc == 0 and only.counts.tobytes() == M["delta"].counts.tobytes(), f"{what} delta: the count-only call"
+
+
+def _battery(S, table, what, shape=sr.Shape(), pairs_all=False, between=None):
+    """Points 1-4 of the battery on one state.  table: whether the state claims a valid chunk table — True: a frame reads lists through it;
+    False: it must not; "long": the stamp holds, but every list a frame can draw is longer than a row and the rasteriser, which takes whole
+    rows only, reads none (the read side takes the row and follows `next` behind it: the fault table of DESIGN §7 shows that it does).
+    between(): called between the crops and the pair queries (a host whose launches keep coming).  -> the anchored full export"""
+    dev = S.dev
+    full, used = _anchor(S, what)
+    print(f"{what}: {full.num_nodes} nodes, {full.num_samples} samples, {used} lists read through the table")
+    assert (used > 0) if table is True else (used == 0), f"{what}: {used} chunk lists read through the table"
+    uv = on_view._uniforms(dev, S.u, vr.transform_of(shape.camera, S.box))
+    M = sr.mirrors(full, S.pts, uv, what, shape, pairs_all)
+    for source in ("chunk table" if table else "no table", "walk"):
+        _crops(S, M, f"{what} ({source})")
+        if between is not None:
+            between()
+        _pairs(S, full, M, f"{what} ({source})")
+        _views(S, uv, M, f"{what} ({source})")
+        if source != "walk":
+            assert dev.L.simlod_octree_image_replaced(dev._p(dev.nodes)) == 0    # point 4, last: the builder's side tables go with it
+    dev.render(S.u)
+    assert dev.lists_read_through_table() == 0, f"{what}: the table is still read after simlod_octree_image_replaced"
+    return full
+
+
+def _new(box, **kw):
+    dev = _device(**kw)
+    u = dev.uniforms(W, H, cases._cam(box), box)
+    dev.reset(u)
+    return dev, u
+
+
+def _oracle_export(box, batches, **kw):
+    ho, u, _ = sr.oracle_build(box, batches, **kw)
+    return sr.export_of(ho, u), ho
+
+
+# ---- A. node array full: over-full leaves ----------------------------------------------------------------------------------------------------
+_A = {}
+
+
+def _state_a():
+    """State A once per module, with the delta of its growth across slot 50 checked on the way: -> (device, uniforms, points, box, the full
+    export before the battery dropped the table)"""
+    if "dev" not in _A:
+        pts, box, batches = sr.a_input()
+        dev, u = _new(box, ring_slots=4, max_nodes=9)
+        _feed(dev, u, batches[:3])
+        uc = on_view._uniforms(dev, u, vr.transform_of("closer", box))
+        view = abi.view_record()
+        held = on_delta._host(on_view.Raw(dev, uc, view), u)
+        _feed(dev, u, batches[3:])
+        st = dev.read_stats()
+        full = dev.export_octree(u)
+        sr.assert_state_a(st["dbg"], full.nodes)
+        assert int(st["numNodes"]) == 9 and int(st["numPoints"]) == len(pts) == int(st["numPointsProcessed"])
+        _A.update(dev=dev, u=u, pts=pts, box=box, full=full, held=held, uc=uc)
+    return _A
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _release(built_libs):
+    from simlod_amd.runtime import lib
+    yield
+    _A.clear()
+    lib().simlod_set_node_capacity(NODE_CAPACITY)
+
+
+def test_a_growth_across_slot_50_is_sent_as_tails(built_libs):
+    """Held after three batches (55 905 .. 56 863 points per leaf), asked after the fourth (74 517 .. 75 680): all eight leaves GROWN, each
+    first piece begins in chunk 55 or 56 — behind the row's 50 slots — and the merge is the raw view."""
+    a = _state_a()
+    dev, held, uc, full = a["dev"], a["held"], a["uc"], a["full"]
+    hn = held.nodes["numSamples"][1:].astype(np.int64)
+    assert held.num_nodes == 9 and (hn > sr.ROW * abi.POINTS_PER_CHUNK).all() and set((hn // abi.POINTS_PER_CHUNK).tolist()) <= {55, 56}, hn
+    view = abi.view_record()
+    for tails in (True, False):
+        mirror = full.view_delta(uc, held, tails=tails)
+        raw = on_delta.RawDelta(dev, uc, held, view, tails=tails)
+        on_delta._assert_delta(raw, mirror, f"A growth, tails {tails}")
+        on_delta._assert_merge(dev, raw, held, uc, view, f"A growth, tails {tails}")
+        e = mirror.entries[1:]
+        if tails:
+            assert (e["state"] == abi.DELTA_GROWN).all() and np.array_equal(e["numKept"].astype(np.int64), hn) and (e["numDelta"] > 18_000).all()
+            assert int(mirror.counts["numGrown"]) == 8 and mirror.num_samples == 600_000 - int(hn.sum())
+        else:
+            assert (e["state"] == abi.DELTA_ADDED).all() and mirror.num_samples == 600_000
+
+
+def test_a_leaves_hold_what_the_oracles_subtrees_hold(built_libs):
+    a = _state_a()
+    pts, box, batches = sr.a_input()
+    want, _ = _oracle_export(box, batches)
+    assert want.num_nodes == 73 and not len(sr.overfull_leaves(want.nodes))
+    sr.assert_same_per_node(a["full"], sr.collapse(want), "A against the oracle's octree collapsed onto level 1")
+
+
+def test_a_battery(built_libs):
+    a = _state_a()
+    _battery(State(a["dev"], a["u"], a["pts"], a["box"]), "long", "A", sr.SHAPES["A"], pairs_all=True)
+
+
+# ---- B. import of A ---------------------------------------------------------------------------------------------------------------------------
+def test_b_plain_import_through_a_file(built_libs, tmp_path):
+    a = _state_a()
+    src, u, full = a["dev"], a["u"], a["full"]
+    full.save(tmp_path / "a.simlodx")
+    ld = OctreeExport.load(tmp_path / "a.simlodx")
+    dst = _device()
+    dst.nodes.fill_(0xA5)
+    dst.import_octree(ld)
+    assert int(dst.read_stats()["dbg"]) == 0
+    re = dst.export_octree(u)
+    assert re.nodes.tobytes() == full.nodes.tobytes() and re.samples.tobytes() == full.samples.tobytes(), "the re-export differs"
+    _frames_equal(src, dst, u, "B plain import")
+
+
+@pytest.mark.parametrize("mode", ["batch_by_batch", "one_group"])
+def test_b_resume_splits_the_imported_overfull_leaves(built_libs, tmp_path, mode):
+    """The outcome: the resumed ingest catches up — the late splits of the eight imported leaves run from tables the import rebuilt, and the
+    octree ends as the oracle's continuous build of all 800 000 points."""
+    a = _state_a()
+    pts, box, more = sr.b_input()
+    a["full"].save(tmp_path / "a.simlodx")
+    ld = OctreeExport.load(tmp_path / "a.simlodx")
+    assert ld.is_buildable and len(sr.overfull_leaves(ld.nodes)) == 8
+    dst = _device()
+    dst.tune("SIMLOD_EXACT_GROUP", 1 if mode == "batch_by_batch" else 2)
+    uu = _import(dst, ld, a["u"])
+    (_feed_one_by_one if mode == "batch_by_batch" else _feed_one_group)(dst, uu, more)
+    st = dst.read_stats()
+    assert int(st["dbg"]) == 0 and int(st["numPoints"]) == len(pts) and int(st["numPointsProcessed"]) == 200_000
+    want, ho = _oracle_export(box, sr.a_input()[2] + more)
+    sr.assert_no_overfull(want.nodes)
+    nodes, pers, nn = host_image_of(dst)
+    got = oracle.dump_image(nodes, nn)
+    _assert_fields(got, ho.dump(), GRANULARITY_FREE_FIELDS, f"B {mode} (resume vs continuous)")
+    oracle.check_invariants(nodes, nn)
+    hs, hx = points_multiset_hash(pts)
+    with np.errstate(over="ignore"):
+        assert hs == np.uint64(got["pointsSum"].sum()) and hx == np.bitwise_xor.reduce(got["pointsXor"])
+    re = dst.export_octree(uu)
+    sr.assert_no_overfull(re.nodes)
+    assert re.nodes.tobytes() == want.nodes.tobytes()
+
+
+# ---- C. deferred splits by scarce scratch -----------------------------------------------------------------------------------------------------
+C_POINTS, C_PENDING = 1_000_000, 4          # (found on the device: at 500 000 nothing spills)
+
+
+def _device_c():
+    """A device whose launches are told a momentary buffer of the minimum plus 6 MB (the buffer itself has the default size, so that the
+    capacity can be raised later) -> (device, the small capacity)"""
+    from simlod_amd.runtime import lib
+    small = int(lib().simlod_construct_buffer_min_bytes()) + 6_000_000
+    dev = _device(ring_slots=8)
+    assert small < dev.momentary_bytes
+    return dev, small
+
+
+def test_c_deferred_splits_and_the_catch_up(built_libs):
+    """C_POINTS is the smallest multiple of 500 000 slab points that leaves the device with SIMLOD_ERR_SPILLED_OVERFLOW and leaves whose split
+    is pending beside leaves that did split (C_PENDING of them); one more batch under the full capacity lets every late split catch up."""
+    pts, box, batches = sr.c_input(C_POINTS + 500_000)
+    dev, small = _device_c()
+    u = dev.uniforms(W, H, cases._cam(box), box)
+    full_capacity = int(u["momentaryBufferCapacity"])
+    u["momentaryBufferCapacity"] = small
+    dev.reset(u)
+    _feed(dev, u, batches[:-1])
+    st = dev.read_stats()
+    assert int(st["numPoints"]) == C_POINTS == int(st["numPointsProcessed"])
+    before = dev.export_octree(u)
+    assert sr.assert_state_c(st["dbg"], before.nodes) == C_PENDING
+    _battery(State(dev, u, pts[:C_POINTS], box), True, "C deferred", sr.SHAPES["C"])
+    u["momentaryBufferCapacity"] = full_capacity
+    _feed(dev, u, batches[-1:])
+    st = dev.read_stats()
+    assert int(st["numPoints"]) == len(pts) and int(st["dbg"]) & ~sr.ERR_SPILLED == 0
+    after = _battery(State(dev, u, pts, box), True, "C caught up", sr.SHAPES["C"])
+    sr.assert_no_overfull(after.nodes)
+    nodes, pers, nn = host_image_of(dev)
+    oracle.check_invariants(nodes, nn)
+
+
+# ---- D. coalesced mode as the source ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["hotspot_150k", "dense_cube"])
+def test_d_coalesced_source(built_libs, tmp_path, name):
+    pts, box, batches, cut = sr.d_input(name)
+    shape = sr.SHAPES[f"D {name}"]
+    dev, u = _new(box, coalesce=True)
+    _feed(dev, u, batches)
+    assert int(dev.read_stats()["dbg"]) == 0
+    full = _battery(State(dev, u, pts, box), True, f"D {name}", shape)
+    want, _ = _oracle_export(box, batches)
+    sr.assert_same_per_node(full, want, f"D {name} against the oracle")
+    del dev
+    src = _device(coalesce=True)
+    _resume_batches(f"D {name}", box, batches, cut, tmp_path, src=src, check_import=name == "dense_cube")       # (the hotspot fills one level-3 cell: its frame stays under _check_import's floor)
+
+
+# ---- E. a launch that stops short, and no host wait -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("stop", ["batch_limit", "time_budget"])
+def test_e_export_directly_behind_a_launch_that_stops_short(built_libs, stop):
+    pts, box, batches = sr.e_input()
+    dev, u = _new(box)
+    if stop == "batch_limit":
+        dev.set_batch_limit(2)
+    else:
+        dev.tune("SIMLOD_DEBUG_BUDGET_US", 100)
+    for b in batches:
+        dev.upload(b)
+    # capacities from what the host knows without a look at Stats: the node array's size, and two samples per uploaded point
+    nn, ns = dev.max_nodes, 2 * len(pts)
+    need = int(dev.L.simlod_export_buffer_min_bytes(nn, ns))
+    scratch, table = torch.empty(need, dtype=torch.uint8, device=dev.device), torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    samples, counts = torch.empty(ns * 16, dtype=torch.uint8, device=dev.device), torch.zeros(abi.export_counts_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+    torch.cuda.synchronize()
+    dev.construct(u)                                                     # ... and, with nothing in between on the host, the export behind it
+    rc = dev.L.simlod_export_octree(dev._p(dev.nodes), dev._p(dev.stats), abi.MAX_DEPTH, abi.EXPORT_ALL, dev._p(scratch), ctypes.c_uint64(need), dev._p(table), nn,
+                                    dev._p(samples), ctypes.c_uint64(ns), dev._p(counts), dev._stream())
+    torch.cuda.synchronize()
+    assert rc == 0
+    c = counts.cpu().numpy().view(abi.export_counts_dtype)[0]
+    st = dev.read_stats()
+    b = int(st["batchletIndex"])
+    assert (b == 2) if stop == "batch_limit" else (1 <= b < 6), f"{b} batches taken"
+    sr.assert_stopped_short(st, b, len(batches) - b)
+    assert int(c["error"]) == 0, f"export error bits {int(c['error']):#x}"
+    ex = OctreeExport(table[: int(c["numNodes"]) * 40], samples[: int(c["numSamples"]) * 16], u["boxMin"], u["boxMax"])
+    nodes, pers, n = host_image_of(dev)
+    _assert_export(ex, *export_host(nodes, n), f"E {stop}: the export behind the launch")
+    want, _ = _oracle_export(box, batches[:b])
+    sr.assert_same_per_node(ex, want, f"E {stop} against the oracle's octree of {b} batches")
+    _battery(State(dev, u, np.concatenate(batches[:b]), box), True, f"E {stop}", sr.SHAPES.get(f"E{b}", sr.SHAPES["E"]))
+
+
+# ---- F. memory guard tripped ------------------------------------------------------------------------------------------------------------------
+def test_f_memory_guard_tripped(built_libs):
+    pts, box, batches = sr.f_input()
+    cap, _ = sr.f_capacity(box, batches)
+    want, ho = _oracle_export(box, batches, capacity=cap)
+    taken = int(ho.stats["batchletIndex"][0])
+    dev = _device(ring_slots=8, persistent_bytes=cap + 4096)
+    dev.persistent[cap:].fill_(0x3C)
+    u = dev.uniforms(W, H, cases._cam(box), box)
+    u["persistentBufferCapacity"] = cap
+    dev.persistent_bytes = cap
+    dev.reset(u)
+    for b in batches:
+        dev.upload(b)
+    for _ in range(4):
+        dev.construct(u)
+    st = dev.read_stats()
+    assert int(ho.stats["memCapacityReached"][0]) == 1 and 0 < taken < 4
+    sr.assert_stopped_short(st, taken, len(batches) - taken, guard=True)
+    full = _battery(State(dev, u, np.concatenate(batches[:taken]), box), True, "F", sr.SHAPES["F"], between=lambda: dev.construct(u))
+    sr.assert_same_per_node(full, want, "F against the oracle's octree at the guard")
+    st = dev.read_stats()
+    sr.assert_stopped_short(st, taken, len(batches) - taken, guard=True)
+    assert bool((dev.persistent[cap:] == 0x3C).all())
+
+
+# ---- G. a foreign image, continued ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("total,first,batch", sr.G_CASES)
+def test_g_foreign_image_continued(built_libs, total, first, batch):
+    pts, box = synthetic.terrain(total, seed=7)
+    dev, u = _new(box, ring_slots=8)
+    _feed(dev, u, [pts[i:i + batch] for i in range(0, first, batch)])
+    nodes, pers, nn, nodes_base, pers_base = dev.download_image()
+    st = dev.read_stats()
+    heads = np.concatenate([nodes["points"][:nn], nodes["voxelChunks"][:nn]]).astype(np.uint64)
+    heads = heads[heads != 0]
+    assert (len(heads) > 20 and nodes["voxelChunks"][0] != 0 and nodes["points"][0] == 0) if total > 100_000 else (nn == 1 and len(heads) == 2)     # an inner root / a root that is a leaf
+    # the image as another implementation leaves it (test_ingest_continues_into_an_image_this_library_did_not_build): the spare words of the lists'
+    # head chunks poisoned, nothing in the momentary buffer but the recycle stack — and uploaded, so that nothing trusts the old stamp
+    for h in heads:
+        off = int(h - np.uint64(pers_base)) + 16000
+        pers[off: off + 8] = 0xA5
+    dev.momentary[4096 + 8_000_000:].fill_(0xA5)
+    dev.upload_image(nodes, pers, nn, stats=st)
+    small = total < 100_000
+    _battery(State(dev, u, pts[:first], box), False, f"G {total} poisoned", sr.SHAPES[f"G {total} poisoned"])
+    assert dev.uploaded_host == dev.processed_host == first // batch
+    for i in range(first, total, batch):
+        dev.upload(pts[i:i + batch])
+        if small:
+            dev.drain(u)
+    dev.drain(u)
+    ds = dev.read_stats()
+    assert int(ds["dbg"]) == 0 and int(ds["numPoints"]) == total
+    full = _battery(State(dev, u, pts, box), True, f"G {total} continued", sr.SHAPES[f"G {total} continued"])
+    want, _ = _oracle_export(box, [pts[i:i + batch] for i in range(0, total, batch)])
+    sr.assert_same_per_node(full, want, f"G {total} continued against the oracle")
+
+
+# ---- H. a rank's octree under a trunk mask ----------------------------------------------------------------------------------------------------
+def test_h_rank_octree_under_a_trunk_mask(built_libs):
+    pts, box, mask, mine, batches = sr.h_input(_partition)
+    dev, u = _new(box, ring_slots=8)
+    dev.set_trunk_mask(*mask)
+    _feed(dev, u, batches)
+    assert int(dev.read_stats()["dbg"]) == 0
+    want, _ = _oracle_export(box, batches, mask=mask)
+    sr.assert_masked_rank(want.nodes, pts, mine, box, mask)
+    full = _battery(State(dev, u, mine, box), True, "H", sr.SHAPES["H"])
+    sr.assert_masked_rank(full.nodes, pts, mine, box, mask)
+    sr.assert_same_per_node(full, want, "H against the oracle with the same mask")
+
+
+# ---- I. two octrees in one context, and a rebuild in the same buffers --------------------------------------------------------------------------
+def test_i_two_octrees_in_one_context_and_a_rebuild(built_libs):
+    pa, box_a, batch_a, Ta = cases.case("terrain_4x100k")
+    pb, box_b, batch_b, Tb = cases.case("uniform_3x40k")
+    ba, bb = cases.batches_of("terrain_4x100k", pa, batch_a), cases.batches_of("uniform_3x40k", pb, batch_b)
+    A, B = _device(persistent_bytes=1 << 30, ring_slots=8), _device(persistent_bytes=1 << 30, ring_slots=8)
+    try:
+        assert A.L.simlod_context_attach(A.ctx, B._p(B.nodes)) == 0      # both node arrays in A's context
+        A.tune("SIMLOD_EXACT_GROUP", 1)
+        ua, ub = A.uniforms(W, H, Ta, box_a), B.uniforms(W, H, Tb, box_b)
+
+        def ingest(dev, u, batches, done):
+            for k, b in enumerate(batches):
+                dev.upload(b)
+                dev.construct(u)
+                assert dev.processed() == done + k + 1
+
+        A.reset(ua)
+        ingest(A, ua, ba[:2], 0)
+        assert A.L.simlod_octree_image_replaced(A._p(A.nodes)) == 0
+        B.reset(ub)
+        ingest(B, ub, bb[:1], 0)
+        ingest(A, ua, ba[2:], 2)
+        ingest(B, ub, bb[1:], 1)
+        assert int(A.read_stats()["dbg"]) == 0 and int(B.read_stats()["dbg"]) == 0
+        # the stamps first, while both tables stand: the battery of A drops A's alone
+        for dev, u in ((A, ua), (B, ub)):
+            u1 = np.array(u, copy=True)
+            u1["minNodeSize"] = 1.0
+            dev.render(u1)
+            assert dev.lists_read_through_table() > 0
+        fa = _battery(State(A, ua, pa, box_a), True, "I A", sr.SHAPES["I A"])
+        fb = _battery(State(B, ub, pb, box_b), True, "I B", sr.SHAPES["I B"])
+        assert fa.num_nodes > fb.num_nodes
+        # the smaller octree into A's buffers: the rows of the larger one lie behind it
+        A.reset(ua := A.uniforms(W, H, Tb, box_b))
+        ingest(A, ua, bb, 0)
+        assert int(A.read_stats()["dbg"]) == 0
+        again = _battery(State(A, ua, pb, box_b), True, "I A rebuilt", sr.SHAPES["I B"])
+        assert again.nodes.tobytes() == fb.nodes.tobytes()
+    finally:
+        A.L.simlod_context_attach(B.ctx, B._p(B.nodes))                  # back to its own context: each close() then destroys its own
+        B.close()
+        A.close()

@@ -131,11 +131,11 @@ def _resume(name, tmp_path, dst=None, check_import=True, **kw):
     return _resume_batches(name, box, batches, cut, tmp_path, dst=dst, check_import=check_import, pts=pts, **kw)
 
 
-def _resume_batches(name, box, batches, cut, tmp_path, dst=None, check_import=True, pts=None, feed=_feed, **kw):
-    """Build batches[:cut], export through a file, import buildable into `dst` (a fresh device by default), feed batches[cut:] with `feed`, and
-    compare with the oracle's continuous build of all batches.  -> (dst, its uniforms, the export)"""
+def _resume_batches(name, box, batches, cut, tmp_path, dst=None, check_import=True, pts=None, feed=_feed, src=None, **kw):
+    """Build batches[:cut] (on `src`: a fresh exact-mode device by default), export through a file, import buildable into `dst` (a fresh device by
+    default), feed batches[cut:] with `feed`, and compare with the oracle's continuous build of all batches.  -> (dst, its uniforms, the export)"""
     T = cases._cam(box)
-    src = _device()
+    src = src or _device()
     u = src.uniforms(W, H, T, box)
     src.reset(u)
     _feed(src, u, batches[:cut])
