@@ -19,7 +19,9 @@
 // time (-DSIMLOD_REF_HOST_EXTRACT=...; nothing of it is stored in this repository) and compiled against shim/cuda.h — the proof that
 // the unchanged host functions drive libsimlod_hip.so.
 //
-// Usage: simlod_headless <file.simlod | synthetic:N> [out.ppm] [width height]
+// Usage: simlod_headless <file.simlod | file.las | synthetic:N> [out.ppm] [width height] [--las-colour rgb|intensity|classification|elevation]
+// --las-colour: a .las file's points take their colour from that attribute (simlod_decode_las_styled: intensity over the full 16-bit window,
+// elevation over the header's z range); without it the file is decoded as before (simlod_decode_las).
 // Prints the Stats the reference shows in its UI and the update/render kernel timings of "benchmark mode" (main.cpp:411-422).
 #include <algorithm>
 #include <atomic>
@@ -324,8 +326,27 @@ static void setCamera(double yaw, double pitch, double radius, const double targ
 	for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { float s = 0; for (int k = 0; k < 4; k++) s += p32[4 * i + k] * v32[4 * k + j]; viewProj[4 * i + j] = s; }
 }
 
+// --las-colour: the table of a SimlodLasStyle from a few control colours (0x00BBGGRR), evenly spaced, by integer linear interpolation
+static void lasRamp(uint32_t* lut, const uint32_t* stops, int numStops) {
+	for (int i = 0; i < 256; i++) {
+		const int pos = i * (numStops - 1), seg = std::min(pos / 255, numStops - 2), f = pos - seg * 255;
+		uint32_t c = 0;
+		for (int k = 0; k < 24; k += 8) c |= ((((stops[seg] >> k) & 255u) * (255 - f) + ((stops[seg + 1] >> k) & 255u) * f + 127) / 255) << k;
+		lut[i] = c;
+	}
+}
+
 int main(int argc, char** argv) {
-	if (argc < 2) { std::printf("usage: %s <file.simlod | file.las | synthetic:N> [out.ppm] [width height]\n", argv[0]); return 2; }
+	// --las-colour rgb|intensity|classification|elevation, anywhere on the line: a .las file is decoded by simlod_decode_las_styled
+	const char* lasColour = nullptr;
+	for (int i = 1; i + 1 < argc; i++) {
+		if (std::strcmp(argv[i], "--las-colour") != 0) continue;
+		lasColour = argv[i + 1];
+		for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+		argc -= 2;
+		break;
+	}
+	if (argc < 2) { std::printf("usage: %s <file.simlod | file.las | synthetic:N> [out.ppm] [width height] [--las-colour rgb|intensity|classification|elevation]\n", argv[0]); return 2; }
 	const std::string path = argv[1];
 	const char* outPath = argc > 2 ? argv[2] : nullptr;
 	if (argc > 4) { width = std::atoi(argv[3]); height = std::atoi(argv[4]); }
@@ -338,6 +359,7 @@ int main(int argc, char** argv) {
 	uint32_t lasBytesPerPoint = 0, lasFormat = 0;
 	double lasScale[3] = {0, 0, 0}, lasOffset[3] = {0, 0, 0};
 	uint64_t lasNumPoints = 0;
+	SimlodLasStyle lasStyle = {};
 	const bool isLas = path.size() > 4 && (path.substr(path.size() - 4) == ".las" || path.substr(path.size() - 4) == ".LAS");
 	if (isLas) {
 		FILE* f = std::fopen(path.c_str(), "rb");
@@ -353,6 +375,23 @@ int main(int argc, char** argv) {
 		for (int k = 0; k < 3; k++) { rd(lasScale[k], 131 + 8 * k); rd(lasOffset[k], 155 + 8 * k); rd(mx[k], 179 + 16 * k); rd(mn[k], 187 + 16 * k); }
 		for (int k = 0; k < 3; k++) lasOffset[k] += -mn[k];                                  // translation = -boxMin, main.cpp:868, LasLoader.cpp:197-199
 		boxSize = {(float)(mx[0] - mn[0]), (float)(mx[1] - mn[1]), (float)(mx[2] - mn[2])};
+		if (lasColour != nullptr) {
+			const std::string c = lasColour;
+			lasStyle.lo = 0.0; lasStyle.hi = 256.0;
+			if (c == "rgb") lasStyle.attribute = SIMLOD_LAS_RGB;
+			else if (c == "intensity") {                             // the full 16-bit window onto a grey ramp
+				const uint32_t grey[2] = {0x000000u, 0xffffffu};
+				lasStyle.attribute = SIMLOD_LAS_INTENSITY; lasStyle.hi = 65536.0; lasRamp(lasStyle.lut, grey, 2);
+			} else if (c == "classification") {                      // the class byte indexes the table: ground, three vegetation heights, building, water; grey otherwise
+				for (int k = 0; k < 256; k++) lasStyle.lut[k] = 0xaaaaaau;
+				lasStyle.attribute = SIMLOD_LAS_CLASSIFICATION;
+				lasStyle.lut[2] = 0x3c6996u; lasStyle.lut[3] = 0x5ac896u; lasStyle.lut[4] = 0x3ca046u; lasStyle.lut[5] = 0x286414u; lasStyle.lut[6] = 0x3246d7u; lasStyle.lut[9] = 0xdc6e32u;
+			} else if (c == "elevation") {                           // the header's z range, in the translated frame the decode writes
+				const uint32_t terrain[5] = {0x6e3c18u, 0x46782eu, 0x50aa96u, 0x4678aau, 0xf0f5f5u};
+				lasStyle.attribute = SIMLOD_LAS_ELEVATION; lasStyle.lo = 0.0; lasStyle.hi = mx[2] - mn[2]; lasRamp(lasStyle.lut, terrain, 5);
+			} else { std::fprintf(stderr, "--las-colour %s: rgb, intensity, classification or elevation\n", lasColour); return 2; }
+			std::printf("las colour: %s\n", lasColour);
+		}
 		lasRecords.resize((size_t)lasNumPoints * lasBytesPerPoint);
 		std::fseek(f, (long)offsetToPointData, SEEK_SET);
 		if (std::fread(lasRecords.data(), 1, lasRecords.size(), f) != lasRecords.size()) { std::fprintf(stderr, "short LAS point data\n"); return 1; }
@@ -486,8 +525,15 @@ int main(int argc, char** argv) {
 				const void* src = lasRecords.data() + first * lasBytesPerPoint;
 				if (!sourcePinned) { std::memcpy(pinned[slot], src, bytes); src = pinned[slot]; }
 				cuMemcpyHtoDAsync(lasStage[slot], src, bytes, stream_upload);
-				simlod_decode_las((const void*)(uintptr_t)lasStage[slot], count, lasBytesPerPoint, lasFormat, lasScale, lasOffset,
-				                  (SimlodPoint*)(uintptr_t)cptr_points_ring[uploadRingIndex], (void*)stream_upload);
+				if (lasColour == nullptr) {
+					simlod_decode_las((const void*)(uintptr_t)lasStage[slot], count, lasBytesPerPoint, lasFormat, lasScale, lasOffset,
+					                  (SimlodPoint*)(uintptr_t)cptr_points_ring[uploadRingIndex], (void*)stream_upload);
+				} else if (const int rc = simlod_decode_las_styled((const void*)(uintptr_t)lasStage[slot], count, lasBytesPerPoint, lasFormat, lasScale, lasOffset, &lasStyle,
+				                                                   (SimlodPoint*)(uintptr_t)cptr_points_ring[uploadRingIndex], (void*)stream_upload)) {
+					// (a format without the attribute, a flat file under "elevation": nothing was decoded, so there is nothing to build)
+					std::fprintf(stderr, "--las-colour %s refused (hipError %d): format %u, %u bytes per point\n", lasColour, rc, lasFormat, lasBytesPerPoint);
+					std::_Exit(1);
+				}
 			} else {
 				const void* src = points.data() + first;
 				if (!sourcePinned) { std::memcpy(pinned[slot], src, (size_t)count * sizeof(Point)); src = pinned[slot]; }

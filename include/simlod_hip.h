@@ -264,6 +264,48 @@ int simlod_profile_collect(SimlodProfileEntry* out, int capacity, int* count);
 int simlod_decode_las(const void* records, uint64_t numPoints, uint32_t bytesPerPoint, uint32_t format,
                       const double scale[3], const double offset[3], SimlodPoint* out, void* stream);
 
+/* ---- styled decode: colour by attribute (no counterpart in the reference, whose loader takes RGB or nothing) -------------------------
+ * simlod_decode_las with the colour taken from one attribute of the record through a 256-entry table.  Positions are simlod_decode_las's.
+ *
+ * The colour of a scalar attribute with value v (fp64):
+ *     inv = 256.0 / (hi - lo)            formed once, on the host
+ *     t   = (v - lo) * inv               fp64 subtract, then fp64 multiply, never contracted
+ *     idx = t >= 0 ? (t < 256 ? (uint32)t : 255) : 0          (a NaN gives 0)
+ *     colour = 0xff000000 | (lut[idx] & 0xffffff)
+ * With lo = 0, hi = 256 a byte attribute indexes the table with itself.  v and its place in the record (ASPRS LAS 1.4 R15, tables 7-17):
+ *     attribute           formats 0-5                             formats 6-10
+ *     intensity           u16 @ 12                                u16 @ 12
+ *     return number       byte 14, bits 0-2                       byte 14, bits 0-3
+ *     number of returns   byte 14, bits 3-5                       byte 14, bits 4-7
+ *     classification      byte 15, bits 0-4 (flags masked off)    u8 @ 16
+ *     user data           u8 @ 17                                 u8 @ 17
+ *     scan angle (deg)    i8 @ 16                                 i16 @ 18, times 0.006 (one fp64 multiply)
+ *     point source id     u16 @ 18                                u16 @ 20
+ *     GPS time            f64 @ 20 (formats 1, 3, 4, 5 only)      f64 @ 22
+ *     elevation           (double)Z * scale[2] + offset[2]        the same
+ * Elevation is the fp64 value the position's z is rounded from: it is in the frame `offset` translates into.
+ * SIMLOD_LAS_RGB takes the RGB triple (c > 255 ? c / 256 : c per channel) of every format that has one — 2, 3, 5 at 20, 28, 28 and 7, 8, 10 at
+ * 30 — and leaves the others black; lo, hi and lut are ignored.  For formats 2, 3, 5, 7 that is simlod_decode_las's output, byte for byte.
+ * style == NULL is simlod_decode_las itself.  hipErrorInvalidValue, nothing launched or written: whatever simlod_decode_las refuses, format > 10,
+ * an unknown attribute, reserved != 0, lo or hi not finite or hi <= lo, an attribute the format lacks, a field that ends beyond bytesPerPoint.
+ * Asynchronous on `stream`; no allocation, synchronisation or copy of its own: the style travels in the kernel's arguments. */
+enum { SIMLOD_LAS_RGB = 0, SIMLOD_LAS_INTENSITY, SIMLOD_LAS_CLASSIFICATION, SIMLOD_LAS_RETURN_NUMBER,
+       SIMLOD_LAS_NUMBER_OF_RETURNS, SIMLOD_LAS_USER_DATA, SIMLOD_LAS_POINT_SOURCE_ID, SIMLOD_LAS_SCAN_ANGLE,
+       SIMLOD_LAS_GPS_TIME, SIMLOD_LAS_ELEVATION, SIMLOD_LAS_ATTRIBUTE_COUNT };
+typedef struct SimlodLasStyle {      /* host memory; read completely before the call returns */
+	uint32_t attribute;              /* SIMLOD_LAS_* */
+	uint32_t reserved;               /* 0 */
+	double   lo, hi;                 /* the window mapped onto the table; finite, hi > lo (ignored for RGB) */
+	uint32_t lut[256];               /* 0x00BBGGRR; the top byte is ignored, the alpha written is always 255 */
+} SimlodLasStyle;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodLasStyle) == 1048, "LasStyle");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodLasStyle, lo) == 8, "LasStyle.lo");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodLasStyle, hi) == 16, "LasStyle.hi");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodLasStyle, lut) == 24, "LasStyle.lut");
+int simlod_decode_las_styled(const void* records, uint64_t numPoints, uint32_t bytesPerPoint, uint32_t format,
+                             const double scale[3], const double offset[3], const SimlodLasStyle* style,
+                             SimlodPoint* out, void* stream);
+
 /* ---- workload generator (BASELINE config 4; no counterpart in the reference) ------------------------------------------------------------
  * Points firstIndex .. firstIndex + numPoints - 1 of a procedurally generated, tiled terrain, written to `out` (device memory): the
  * stream is tile after tile (`pointsPerTile` points each, tiles laid out row-major with `tilesX` tiles per row, each tileExtent[0] x

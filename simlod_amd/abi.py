@@ -202,6 +202,16 @@ neighbour_counts_dtype = np.dtype({"names": ["numNodes", "error", "numInvalid", 
                                    "formats": ["<u4", "<u4", "<u4", "<u4", "<u8", "<u8", "<u8", "<u8"], "offsets": [0, 4, 8, 12, 16, 24, 32, 40], "itemsize": 48})
 assert sphere_dtype.itemsize == 16 and neighbour_dtype.itemsize == 32 and neighbour_counts_dtype.itemsize == 48
 
+# ---- styled LAS decode (include/simlod_hip.h, "styled decode") ---------------------------------------------------------------------------
+(LAS_RGB, LAS_INTENSITY, LAS_CLASSIFICATION, LAS_RETURN_NUMBER, LAS_NUMBER_OF_RETURNS, LAS_USER_DATA, LAS_POINT_SOURCE_ID, LAS_SCAN_ANGLE,
+ LAS_GPS_TIME, LAS_ELEVATION, LAS_ATTRIBUTE_COUNT) = range(11)
+LAS_ATTRIBUTES = {"rgb": LAS_RGB, "intensity": LAS_INTENSITY, "classification": LAS_CLASSIFICATION, "return_number": LAS_RETURN_NUMBER,
+                  "number_of_returns": LAS_NUMBER_OF_RETURNS, "user_data": LAS_USER_DATA, "point_source_id": LAS_POINT_SOURCE_ID,
+                  "scan_angle": LAS_SCAN_ANGLE, "gps_time": LAS_GPS_TIME, "elevation": LAS_ELEVATION}
+las_style_dtype = np.dtype({"names": ["attribute", "reserved", "lo", "hi", "lut"], "formats": ["<u4", "<u4", "<f8", "<f8", ("<u4", 256)],
+                            "offsets": [0, 4, 8, 16, 24], "itemsize": 1048})
+assert las_style_dtype.itemsize == 1048
+
 # ---- kernel_render's buffer (include/simlod_hip.h simlod_render_frame_layout; simlod_amd/csrc/render_layout.hpp states the layout) -------
 frame_layout_dtype = np.dtype([(n, "<u8") for n in (
     "visible", "counters", "lines", "vertices", "probe", "framebuffer", "work", "items", "depth", "colour", "sums", "dir",

@@ -424,6 +424,11 @@ int simlod_decode_las(const void* records, uint64_t numPoints, uint32_t bytesPer
 	return launch_decode_las(records, numPoints, bytesPerPoint, format, scale, offset, out, (hipStream_t)stream);
 }
 
+int simlod_decode_las_styled(const void* records, uint64_t numPoints, uint32_t bytesPerPoint, uint32_t format, const double scale[3],
+                             const double offset[3], const SimlodLasStyle* style, SimlodPoint* out, void* stream) {
+	return launch_decode_las_styled(records, numPoints, bytesPerPoint, format, scale, offset, style, out, (hipStream_t)stream);
+}
+
 int simlod_launch_colorfilter(const SimlodUniforms* uniforms, uint32_t* buffer, SimlodNode* nodes, uint32_t* numNodes, SimlodStats* stats, void* stream) {
 	if (!uniforms || !buffer || !nodes || (!numNodes && !stats)) return (int)hipErrorInvalidValue;
 	Context& ctx = context_of(nodes);

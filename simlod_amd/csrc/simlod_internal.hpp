@@ -164,6 +164,8 @@ int launch_reset(Context& ctx, const SimlodUniforms* u, uint8_t* pers, SimlodNod
                  uint32_t* batchSizes, hipStream_t stream);
 int launch_decode_las(const void* records, uint64_t numPoints, uint32_t bytesPerPoint, uint32_t format, const double* scale,
                       const double* offset, SimlodPoint* out, hipStream_t stream);
+int launch_decode_las_styled(const void* records, uint64_t numPoints, uint32_t bytesPerPoint, uint32_t format, const double* scale,
+                             const double* offset, const SimlodLasStyle* style, SimlodPoint* out, hipStream_t stream);
 int launch_colorfilter(Context& ctx, const SimlodUniforms* u, uint32_t* buffer, SimlodNode* nodes, const uint32_t* numNodes, SimlodStats* stats, hipStream_t stream);
 uint64_t colorfilter_min_bytes(uint32_t nodeCapacity);
 int launch_export(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,

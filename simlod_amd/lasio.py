@@ -17,6 +17,8 @@ from . import abi
 
 # RGB byte offset inside a point record, for the formats the reference takes colour from (LasLoader.cpp:177-185)
 RGB_OFFSET = {2: 20, 3: 28, 5: 28, 7: 30}
+# ... and of every format that carries the triple (the styled decode's RGB, and what las_records plants)
+RGB_OFFSET_ALL = {2: 20, 3: 28, 5: 28, 7: 30, 8: 30, 10: 30}
 # minimum record length of the LAS point data record formats 0-10 (ASPRS LAS 1.4 R15, tables 7-17)
 FORMAT_BYTES = {0: 20, 1: 28, 2: 26, 3: 34, 4: 57, 5: 63, 6: 30, 7: 36, 8: 38, 9: 59, 10: 67}
 
@@ -86,17 +88,191 @@ def read_simlod(path):
     return pts, (hdr[3:6] - hdr[0:3]).astype(np.float32)
 
 
-def las_records(xyz_int, rgb16, fmt, bytes_per_point=None, seed=0):
+def las_records(xyz_int, rgb16, fmt, bytes_per_point=None, seed=0, attributes=None):
     """Raw point records (uint8 [n, bytesPerPoint]) of LAS point format `fmt`: int32 X,Y,Z at bytes 0-11, RGB16 where the
-    format has it, every other byte pseudo-random (intensity, flags, gps time, extra bytes ... — a decoder must ignore them)."""
+    format has it, every other byte pseudo-random (intensity, flags, gps time, extra bytes ... — a decoder must ignore them).
+    attributes: {name (abi.LAS_ATTRIBUTES): values} written into their fields afterwards (a bit field keeps the byte's other bits)."""
     n = len(xyz_int)
     bpp = FORMAT_BYTES[fmt] if bytes_per_point is None else bytes_per_point
     rec = np.random.RandomState(seed).randint(0, 256, size=(n, bpp), dtype=np.uint8)
     rec[:, 0:12] = np.ascontiguousarray(xyz_int.astype("<i4")).view(np.uint8).reshape(n, 12)
-    off = {2: 20, 3: 28, 5: 28, 7: 30, 8: 30, 10: 30}.get(fmt)
+    off = RGB_OFFSET_ALL.get(fmt)
     if off is not None and rgb16 is not None:
         rec[:, off:off + 6] = np.ascontiguousarray(rgb16.astype("<u2")).view(np.uint8).reshape(n, 6)
+    for name, values in (attributes or {}).items():
+        off, kind, shift, mask = las_field(name, fmt)
+        if kind == "f8":
+            rec[:, off:off + 8] = np.ascontiguousarray(np.asarray(values, "<f8")).view(np.uint8).reshape(n, 8)
+            continue
+        size = int(kind[1])
+        raw = (np.asarray(values).astype(np.int64) & mask) << shift
+        old = np.ascontiguousarray(rec[:, off:off + size]).view(f"<u{size}").reshape(n).astype(np.int64)
+        new = ((old & ~(mask << shift)) | raw).astype(f"<u{size}")
+        rec[:, off:off + size] = np.ascontiguousarray(new).view(np.uint8).reshape(n, size)
     return rec
+
+
+# ---- colour by attribute (include/simlod_hip.h, "styled decode") ------------------------------------------------------------------------
+
+def las_field(attribute, fmt):
+    """(byte offset, kind, shift, mask) of a scalar attribute in a record of format `fmt` (ASPRS LAS 1.4 R15, tables 7-17): kind "u1" / "u2" /
+    "i1" / "i2" / "f8"; the value is sign_extend((field >> shift) & mask).  ValueError: the format has no such attribute."""
+    a = abi.LAS_ATTRIBUTES[attribute] if isinstance(attribute, str) else int(attribute)
+    if not 0 <= fmt <= 10:
+        raise ValueError(f"LAS point format {fmt}")
+    ext = fmt >= 6
+    if a == abi.LAS_INTENSITY:
+        return 12, "u2", 0, 0xffff
+    if a == abi.LAS_RETURN_NUMBER:
+        return 14, "u1", 0, 0xf if ext else 0x7
+    if a == abi.LAS_NUMBER_OF_RETURNS:
+        return 14, "u1", 4 if ext else 3, 0xf if ext else 0x7
+    if a == abi.LAS_CLASSIFICATION:
+        return (16, "u1", 0, 0xff) if ext else (15, "u1", 0, 0x1f)
+    if a == abi.LAS_USER_DATA:
+        return 17, "u1", 0, 0xff
+    if a == abi.LAS_SCAN_ANGLE:
+        return (18, "i2", 0, 0xffff) if ext else (16, "i1", 0, 0xff)
+    if a == abi.LAS_POINT_SOURCE_ID:
+        return 20 if ext else 18, "u2", 0, 0xffff
+    if a == abi.LAS_GPS_TIME and fmt not in (0, 2):
+        return 22 if ext else 20, "f8", 0, 0
+    raise ValueError(f"LAS point format {fmt} has no attribute {attribute}")
+
+
+def _ramp(stops):
+    """256 colour words (0x00BBGGRR) through `stops` (r, g, b), evenly spaced, by integer linear interpolation."""
+    lut = np.zeros(256, dtype=np.uint32)
+    for i in range(256):
+        pos = i * (len(stops) - 1)
+        seg = min(pos // 255, len(stops) - 2)
+        f = pos - seg * 255
+        r, g, b = ((stops[seg][k] * (255 - f) + stops[seg + 1][k] * f + 127) // 255 for k in range(3))
+        lut[i] = r | (g << 8) | (b << 16)
+    return lut
+
+
+# this project's own tables: control colours (r, g, b) of the ramps, and the colour of each ASPRS class
+RAMPS = {
+    "gray": [(0, 0, 0), (255, 255, 255)],
+    "terrain": [(24, 60, 110), (46, 120, 70), (150, 170, 80), (170, 120, 70), (245, 245, 240)],       # water's edge, meadow, scrub, rock, snow
+    "heat": [(10, 10, 60), (140, 20, 120), (230, 90, 30), (255, 230, 120)],
+}
+CLASS_FALLBACK = (200, 60, 200)
+CLASS_COLOURS = {
+    0: (110, 110, 110), 1: (170, 170, 170),                     # never classified, unclassified
+    2: (150, 105, 60),                                           # ground
+    3: (150, 200, 90), 4: (70, 160, 60), 5: (20, 100, 40),       # low, medium, high vegetation
+    6: (215, 70, 50),                                            # building
+    7: (255, 0, 255), 18: (255, 0, 255),                         # low / high noise
+    9: (50, 110, 220),                                           # water
+    10: (90, 80, 100), 11: (60, 60, 70),                         # rail, road surface
+    13: (240, 200, 40), 14: (240, 170, 40), 15: (200, 140, 30), 16: (240, 220, 120),     # wire guard, conductor, tower, connector
+    17: (120, 130, 150),                                         # bridge deck
+}
+
+
+@dataclasses.dataclass
+class Style:
+    """How a decode colours its points: the attribute, the window [lo, hi) mapped onto the table, and the table (256 x 0x00BBGGRR).
+    The SimlodLasStyle of include/simlod_hip.h; the colour rule is stated there and restated by decode_records."""
+    attribute: int
+    lo: float = 0.0
+    hi: float = 256.0
+    lut: np.ndarray = None
+
+    def __post_init__(self):
+        self.attribute = abi.LAS_ATTRIBUTES[self.attribute] if isinstance(self.attribute, str) else int(self.attribute)
+        self.lut = _ramp(RAMPS["gray"]) if self.lut is None else np.ascontiguousarray(self.lut, dtype=np.uint32).reshape(256)
+
+    @classmethod
+    def of(cls, attribute, lo, hi, ramp="gray"):
+        return cls(attribute, float(lo), float(hi), _ramp(RAMPS[ramp]) if isinstance(ramp, str) else ramp)
+
+    @classmethod
+    def rgb(cls):
+        return cls(abi.LAS_RGB)
+
+    @classmethod
+    def intensity(cls, lo=0, hi=65536, ramp="gray"):
+        return cls.of(abi.LAS_INTENSITY, lo, hi, ramp)
+
+    @classmethod
+    def classification(cls, palette=None):
+        """The class byte indexes the table with itself.  palette: {class: (r, g, b)} over CLASS_COLOURS."""
+        colours = {**CLASS_COLOURS, **(palette or {})}
+        rgb = [colours.get(c, CLASS_FALLBACK) for c in range(256)]
+        return cls(abi.LAS_CLASSIFICATION, 0.0, 256.0, np.array([r | (g << 8) | (b << 16) for r, g, b in rgb], dtype=np.uint32))
+
+    @classmethod
+    def elevation(cls, lo, hi, ramp="terrain"):
+        """lo, hi: heights in the file's world units (DeviceOctree.upload_las moves them into the decode's frame)."""
+        return cls.of(abi.LAS_ELEVATION, lo, hi, ramp)
+
+    @classmethod
+    def auto(cls, header):
+        """RGB when the header's format has it, grey intensity otherwise."""
+        return cls.rgb() if header.format in RGB_OFFSET_ALL else cls.intensity()
+
+    def in_frame(self, translation):
+        """This style in the frame a decode with `translation` writes: an elevation window moves by translation[2], all else stays."""
+        if self.attribute != abi.LAS_ELEVATION:
+            return self
+        t = np.float64(translation[2])
+        return Style(self.attribute, float(np.float64(self.lo) + t), float(np.float64(self.hi) + t), self.lut)
+
+    def record(self):
+        """The SimlodLasStyle record (abi.las_style_dtype)."""
+        r = np.zeros(1, dtype=abi.las_style_dtype)
+        r["attribute"], r["lo"], r["hi"], r["lut"] = self.attribute, self.lo, self.hi, self.lut
+        return r
+
+
+def decode_records(records, bytes_per_point, fmt, scale, offset, style=None):
+    """What simlod_decode_las_styled writes for these raw records, in numpy float64 (offset = header.offset + translation, as decode_offset forms
+    it; an elevation window is in that frame: Style.in_frame).  style None: what simlod_decode_las writes.  ValueError where the call refuses."""
+    rec = np.ascontiguousarray(records, dtype=np.uint8).reshape(-1, bytes_per_point)
+    n = len(rec)
+    field = lambda off, dt: np.ascontiguousarray(rec[:, off:off + int(dt[1])]).view("<" + dt).reshape(n)
+    rgb_off = (RGB_OFFSET if style is None else RGB_OFFSET_ALL).get(fmt, 0)
+    if not 12 <= bytes_per_point <= 255 or (style is not None and not 0 <= fmt <= 10) or (rgb_off and rgb_off + 6 > bytes_per_point):
+        raise ValueError(f"format {fmt} in records of {bytes_per_point} bytes")
+    out = np.zeros(n, dtype=abi.point_dtype)
+    xyz = np.ascontiguousarray(rec[:, 0:12]).view("<i4").reshape(n, 3).astype(np.float64)
+    pos = [xyz[:, k] * np.float64(scale[k]) + np.float64(offset[k]) for k in range(3)]           # one fp64 multiply, one fp64 add
+    for k, name in enumerate("xyz"):
+        out[name] = pos[k].astype(np.float32)
+    color = np.full(n, 0xff000000, dtype=np.uint32)
+    if style is None or style.attribute == abi.LAS_RGB:
+        if rgb_off:
+            c = np.ascontiguousarray(rec[:, rgb_off:rgb_off + 6]).view("<u2").reshape(n, 3).astype(np.uint32)
+            c = np.where(c > 255, c // 256, c)
+            color |= c[:, 0] | (c[:, 1] << 8) | (c[:, 2] << 16)
+        out["color"] = color
+        return out
+    lo, hi = np.float64(style.lo), np.float64(style.hi)
+    if not 0 <= style.attribute < abi.LAS_ATTRIBUTE_COUNT or not (np.isfinite(lo) and np.isfinite(hi) and hi > lo):
+        raise ValueError(f"attribute {style.attribute} over [{lo}, {hi})")
+    if style.attribute == abi.LAS_ELEVATION:
+        v = pos[2]                                                 # the fp64 value z is rounded from
+    else:
+        off, kind, shift, mask = las_field(style.attribute, fmt)
+        if off + int(kind[1]) > bytes_per_point:
+            raise ValueError(f"the field ends beyond the record's {bytes_per_point} bytes")
+        if kind == "f8":
+            v = field(off, "f8")
+        else:
+            bits = (field(off, "u" + kind[1]).astype(np.int64) >> shift) & mask
+            sign = (mask + 1) >> 1 if kind[0] == "i" else 0
+            v = ((bits ^ sign) - sign).astype(np.float64)
+            if kind == "i2":
+                v = v * np.float64(0.006)                          # degrees per step of the 16-bit scan angle
+    with np.errstate(all="ignore"):
+        inv = np.float64(256.0) / (hi - lo)
+        t = (v - lo) * inv                                         # fp64 subtract, then fp64 multiply
+        idx = np.where(t >= 256.0, 255, np.where((t >= 0.0) & (t < 256.0), t, 0.0).astype(np.uint32))      # a NaN: 0
+    out["color"] = color | (style.lut[idx] & np.uint32(0xffffff))
+    return out
 
 
 def write_las(path, records, fmt, scale, offset, mins, maxs, version=(1, 2), header_size=None, vlr_bytes=0, num_points=None):

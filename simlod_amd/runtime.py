@@ -81,6 +81,8 @@ def lib():
         L.simlod_build_info.restype = ctypes.c_char_p
         L.simlod_decode_las.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_double), vp, vp]
+        L.simlod_decode_las_styled.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
+                                               ctypes.POINTER(ctypes.c_double), vp, vp, vp]
         L.simlod_launch_colorfilter.argtypes = [vp] * 6
         L.simlod_colorfilter_buffer_min_bytes.restype = u64
         L.simlod_generate_terrain.argtypes = [vp, u64, u64, u64, u32, u32, ctypes.POINTER(ctypes.c_float), vp]
@@ -127,6 +129,7 @@ EXPORTED_SYMBOLS = [
     "simlod_neighbours_buffer_min_bytes", "simlod_query_neighbours", "simlod_footprint_buffer_min_bytes", "simlod_query_footprint",
     "simlod_context_set_clip", "simlod_set_clip", "simlod_query_view",
     "simlod_view_delta_buffer_min_bytes", "simlod_query_view_delta", "simlod_merge_view_delta",
+    "simlod_decode_las_styled",
 ]
 
 
@@ -296,9 +299,10 @@ class DeviceOctree:
         if self.notifies:
             _check(self.L.simlod_upload_counter_written(self._p(self.num_uploaded), int(num_batches)), "simlod_upload_counter_written")
 
-    def upload_las(self, records, header, translation):
+    def upload_las(self, records, header, translation, style=None):
         """One batch of RAW LAS point records (uint8 host array or device tensor) into the next ring slot, decoded on the
-        device (simlod_decode_las); translation = -boxMin as at main_progressive_octree.cpp:868."""
+        device (simlod_decode_las); translation = -boxMin as at main_progressive_octree.cpp:868.  style (a lasio.Style): the colour from
+        that attribute (simlod_decode_las_styled); an elevation window is given in the file's world units and shifted by translation[2] here."""
         from . import lasio
         bpp = int(header.bytesPerPoint)
         raw = records if isinstance(records, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(records).reshape(-1))
@@ -312,14 +316,19 @@ class DeviceOctree:
         scale = (ctypes.c_double * 3)(*header.scale)
         offset = (ctypes.c_double * 3)(*lasio.decode_offset(header, translation))
         dst = self.ring.data_ptr() + slot * abi.MAX_BATCH_SIZE * 16
-        _check(self.L.simlod_decode_las(self._p(self.las_stage), ctypes.c_uint64(n), ctypes.c_uint32(bpp), ctypes.c_uint32(int(header.format)),
-                                        scale, offset, ctypes.c_void_p(dst), self._stream()), "simlod_decode_las")
+        if style is None:
+            _check(self.L.simlod_decode_las(self._p(self.las_stage), ctypes.c_uint64(n), ctypes.c_uint32(bpp), ctypes.c_uint32(int(header.format)),
+                                            scale, offset, ctypes.c_void_p(dst), self._stream()), "simlod_decode_las")
+        else:
+            rec = style.in_frame(translation).record()
+            _check(self.L.simlod_decode_las_styled(self._p(self.las_stage), ctypes.c_uint64(n), ctypes.c_uint32(bpp), ctypes.c_uint32(int(header.format)),
+                                                   scale, offset, ctypes.c_void_p(rec.ctypes.data), ctypes.c_void_p(dst), self._stream()), "simlod_decode_las_styled")
         self.batch_sizes[slot] = n
         self.uploaded_host += 1
         self.publish(self.uploaded_host)
 
-    def add_las(self, uniforms, path, translation=None, batch=abi.MAX_BATCH_SIZE):
-        """Stream a LAS file through the ring: read raw bytes, decode on the device, ingest."""
+    def add_las(self, uniforms, path, translation=None, batch=abi.MAX_BATCH_SIZE, style=None):
+        """Stream a LAS file through the ring: read raw bytes, decode on the device, ingest.  style: as upload_las."""
         from . import lasio
         h = lasio.load_header(path)
         t = tuple(-float(v) for v in h.min) if translation is None else translation
@@ -327,7 +336,7 @@ class DeviceOctree:
             if self.uploaded_host - self.processed_host >= self.ring_slots:
                 self.drain(uniforms)                   # (sets processed_host to what it read back)
                 assert self.uploaded_host - self.processed_host < self.ring_slots, "kernel_construct left the ring full"
-            self.upload_las(lasio.read_records(path, h, first, count), h, t)
+            self.upload_las(lasio.read_records(path, h, first, count), h, t, style)
         self.drain(uniforms)
         return h
 

@@ -13,7 +13,49 @@ from simlod_amd.runtime import lib
 
 L = lib()
 batch, NSET = 1_000_000, 42
-for fmt, bpp in ((2, 26), (3, 34), (7, 36)):
+
+
+def styled_against_plain():
+    """--style: k_decode_las_styled beside k_decode_las on the SAME rotating record set, in this process, alternating rep by rep (a rep: the 42
+    launches of one kernel, HIP events around them) — the plain decode of this run is the yardstick, its rep-to-rep spread the resolution."""
+    from simlod_amd import fingerprint
+    from simlod_amd.lasio import Style
+    print(f"kernel sources: csrc sha {fingerprint.csrc_sha16()}")
+    REPS = 7
+    for fmt, style in ((1, Style.intensity()), (6, Style.classification()), (3, Style.of("gps_time", 0.0, 1e9, "heat"))):
+        bpp = lasio.FORMAT_BYTES[fmt]
+        rs = np.random.RandomState(5)
+        rec = lasio.las_records(rs.randint(0, 6_000_000, size=(batch, 3)).astype(np.int32), rs.randint(0, 65536, size=(batch, 3)).astype(np.uint16), fmt,
+                                attributes={"gps_time": rs.uniform(0.0, 1e9, size=batch)} if fmt == 3 else None)
+        d_raw = torch.from_numpy(rec.reshape(-1)).to("cuda:0").repeat(NSET).reshape(NSET, -1)
+        d_out = torch.empty((NSET, batch * 16), dtype=torch.uint8, device="cuda:0")
+        scale3, off3 = (ctypes.c_double * 3)(1e-3, 1e-3, 1e-3), (ctypes.c_double * 3)(0.0, 0.0, 0.0)
+        record = style.record()
+        head = lambda k: (ctypes.c_void_p(d_raw[k].data_ptr()), ctypes.c_uint64(batch), ctypes.c_uint32(bpp), ctypes.c_uint32(fmt), scale3, off3)
+        tail = lambda k: (ctypes.c_void_p(d_out[k].data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        calls = {"plain": lambda k: L.simlod_decode_las(*head(k), *tail(k)),
+                 "styled": lambda k: L.simlod_decode_las_styled(*head(k), ctypes.c_void_p(record.ctypes.data), *tail(k))}
+        us = {"plain": [], "styled": []}
+        for rep in range(REPS + 1):                      # (rep 0 warms both up)
+            for which in ("plain", "styled"):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for k in range(NSET):
+                    assert calls[which](k) == 0
+                e1.record(); torch.cuda.synchronize()
+                if rep:
+                    us[which].append(e0.elapsed_time(e1) * 1e3 / NSET)
+        med = {w: float(np.median(v)) for w, v in us.items()}
+        for w in ("plain", "styled"):
+            print(f"format {fmt} ({bpp} B records) {w:6s}: median {med[w]:6.2f} us per 1 M-point launch (min {min(us[w]):6.2f}, max {max(us[w]):6.2f} over {REPS} reps) = "
+                  f"{batch / med[w]:7.0f} M points/s, {(bpp + 16) * batch / med[w] / 1e6:5.2f} TB/s", flush=True)
+        print(f"format {fmt}: styled / plain rate = {med['plain'] / med['styled']:.3f} (plain's own spread: {min(us['plain']) / max(us['plain']):.3f} .. 1)", flush=True)
+        del d_raw, d_out
+
+
+if "--style" in sys.argv[1:]:
+    styled_against_plain()
+for fmt, bpp in () if "--style" in sys.argv[1:] else ((2, 26), (3, 34), (7, 36)):
     rs = np.random.RandomState(5)
     rec = lasio.las_records(rs.randint(0, 6_000_000, size=(batch, 3)).astype(np.int32), rs.randint(0, 65536, size=(batch, 3)).astype(np.uint16), fmt)
     assert rec.shape[1] == bpp, rec.shape
