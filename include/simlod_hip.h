@@ -562,6 +562,80 @@ int simlod_query_footprint(const SimlodNode* nodes, const SimlodStats* stats, co
                            SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity,
                            SimlodQueryCounts* counts, void* stream);
 
+/* ---- profile queries: the samples in a corridor along a polyline, each with its station, offset and height ---------------------------------
+ * simlod_query_profile is simlod_query_region plus a profile: a polyline of up to 64 vertices in a plane the points are mapped into by an affine
+ * map (as a footprint's), and a half-width.  The result is the samples within the half-width of a segment, at the chosen level of detail, and
+ * for each of them a SimlodProfileSample: the segment it belongs to, its distance along the polyline, its signed distance from the segment's
+ * line and its height — a road's, a river bank's or a power line's cross-section.  Everything the region section says stays in force: the box,
+ * the inflated cube lo_a / hi_a of rule 1, the listing and selection rules, rule 5's count-only calls and capacities, SimlodQueryCounts,
+ * SIMLOD_EXPORT_REGION, the chunk-table / `next` sources.  The profile composes with the region's half-spaces (a height band, say), and the
+ * table and `samples` are an ordinary export table; records[k] belongs to samples[k].
+ * THE CORRIDOR is the union of one rectangle per segment, with square ends (as Potree's height profile).  On the outside of a bend the wedge
+ * between two rectangles belongs to no segment: a sample there is not returned.  On the inside the rectangles overlap: the lower segment owns.
+ *
+ * All new geometry is fp64 computed from the fp32 inputs without fused multiply-add, every sum in the order written here.  The device neither
+ * divides nor takes a square root.
+ *  P0. Segments.  Segment i runs from a = P[i] to b = P[i+1]: du = b_u - a_u, dv = b_v - a_v, L2 = du*du + dv*dv, W2 = (w*w)*L2 with
+ *      w = halfWidth.  The launcher computes, on the host, len = sqrt(L2), inv = 1.0/len, s0_0 = 0 and s0_(i+1) = s0_i + len_i, and places
+ *      {a_u, a_v, du, dv, L2, W2, inv, s0} (64 bytes per segment) in a block of the scratch buffer.  A segment with L2 == 0 is refused.
+ *  P1. Sample rule.  u and v as footprint rule F1.  For segment i: pu = u - a_u, pv = v - a_v, al = du*pu + dv*pv, c = du*pv - dv*pu.  The sample
+ *      is IN segment i iff al >= 0 && al <= L2 && c*c <= W2 (a NaN fails).  It passes iff it passes region rule 3 and is in some segment; ITS
+ *      segment is the lowest such i.
+ *  P2. Record.  station = (float)(s0_i + al*inv_i), offset = (float)(c*inv_i) (positive to the left of the direction of travel),
+ *      height = (float)(((hx*x + hy*y) + hz*z) + h0) from axisH, segment = i.
+ *  P3. Node class by the profile.  With the projected rectangle [U_lo, U_hi] x [V_lo, V_hi] of footprint rule F2: per segment al and c at the
+ *      four corners (U_lo,V_lo), (U_lo,V_hi), (U_hi,V_lo), (U_hi,V_hi), as al = du*(U - a_u) + dv*(V - a_v) and c = du*(V - a_v) - dv*(U - a_u),
+ *      and their minima and maxima al_min, al_max, c_min, c_max.  The segment is FAR iff al_max < 0 || al_min > L2 ||
+ *      (c_min > 0 && c_min*c_min > W2) || (c_max < 0 && c_max*c_max > W2).  It COVERS the node iff al_min >= 0 && al_max <= L2 &&
+ *      c_min*c_min <= W2 && c_max*c_max <= W2.  The node is OUTSIDE iff every segment is FAR, COPIED iff some segment covers it, else FILTERED.
+ *      The final class combines with the planes' as footprint rule F4 does: OUTSIDE if outside by either, COPIED iff copied by both, else
+ *      FILTERED.  A COPIED node's samples all pass without a test and are not counted one by one; each still gets its record, with the lowest
+ *      segment it is in (which need not be the one that covers the node).
+ *  P4. al and c as computed are monotone in u and in v (every product and every sum is), so they take their extremes at the corners in floating
+ *      point too: for finite samples in the half-open box P3 changes nothing against P1 applied to every sample, without a grazing exception.
+ *      The host mirror asserts this per query.  A sample OUTSIDE that contract in a COPIED node is returned as every sample of such a node is;
+ *      if it is in no segment its record has station = offset = 0 and segment = SIMLOD_PROFILE_NO_SEGMENT.
+ *  P5. profile == NULL gives exactly simlod_query_region, byte for byte, and `records` is not written.  records == NULL with samples != NULL
+ *      gives the crop by the corridor without records.  records != NULL with samples == NULL is refused.  `records` has room for
+ *      sampleCapacity records and is 16-byte aligned.
+ *  P6. hipErrorInvalidValue with nothing enqueued: everything simlod_query_region refuses, numVertices outside 2..64, halfWidth not finite or
+ *      <= 0, a non-finite vertex or axis coefficient, a segment of length zero, nonzero `reserved`, records without samples, scratchBytes below
+ *      simlod_profile_buffer_min_bytes(tableCapacity, 0).  Neither capacity error writes anything past the capacity. */
+#define SIMLOD_PROFILE_MAX_VERTICES 64u
+#define SIMLOD_PROFILE_NO_SEGMENT   0xffffffffu
+typedef struct SimlodProfile {         /* host memory, read before the call returns */
+	uint32_t numVertices;              /* 2..64: numVertices - 1 segments */
+	float    halfWidth;                /* > 0, finite: the corridor reaches this far to either side of a segment */
+	uint32_t reserved[2];              /* 0 */
+	float    axisU[4], axisV[4];       /* the plan coordinates, as SimlodFootprint's */
+	float    axisH[4];                 /* the reported height h = ((hx*x + hy*y) + hz*z) + h0 */
+	float    vertices[SIMLOD_PROFILE_MAX_VERTICES][2];   /* (u, v) */
+} SimlodProfile;
+typedef struct SimlodProfileSample {   /* written by the device, one per returned sample, same index as the sample */
+	float    station;                  /* distance along the polyline from vertex 0 */
+	float    offset;                   /* signed distance from the segment's line, positive to the left of the direction of travel */
+	float    height;
+	uint32_t segment;
+} SimlodProfileSample;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodProfile) == 576, "Profile");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodProfile, halfWidth) == 4, "Profile.halfWidth");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodProfile, axisU) == 16, "Profile.axisU");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodProfile, axisV) == 32, "Profile.axisV");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodProfile, axisH) == 48, "Profile.axisH");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodProfile, vertices) == 64, "Profile.vertices");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodProfileSample) == 16, "ProfileSample");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodProfileSample, height) == 8, "ProfileSample.height");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodProfileSample, segment) == 12, "ProfileSample.segment");
+
+/* simlod_query_buffer_min_bytes plus a fixed block for the segments (4 KB). */
+uint64_t simlod_profile_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+
+/* The profile query (rules above; arguments as simlod_query_footprint's, plus `records`).  Asynchronous on `stream` once `profile` has been read. */
+int simlod_query_profile(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                         const SimlodProfile* profile, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                         SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity,
+                         SimlodProfileSample* records, SimlodQueryCounts* counts, void* stream);
+
 /* ---- ray queries: the first sample in a cone along each ray of a batch ----------------------------------------------------------------------
  * simlod_query_rays answers "what does this ray hit" for up to 2^20 rays at once: per ray the sample with the smallest parameter t that lies
  * within radius + spread * t of the ray, among the samples of the nodes simlod_export_octree(maxLevel, select) selects.  The source is only read.

@@ -184,6 +184,18 @@ footprint_dtype = np.dtype({"names": ["numVertices", "reserved", "axisU", "axisV
                             "offsets": [0, 4, 16, 32, 48], "itemsize": 2096})
 assert footprint_dtype.itemsize == 2096
 
+# ---- profile queries (include/simlod_hip.h, "profile queries") --------------------------------------------------------------------------
+PROFILE_MAX_VERTICES = 64
+PROFILE_NO_SEGMENT = 0xFFFFFFFF
+profile_dtype = np.dtype({"names": ["numVertices", "halfWidth", "reserved", "axisU", "axisV", "axisH", "vertices"],
+                          "formats": ["<u4", "<f4", ("<u4", 2), ("<f4", 4), ("<f4", 4), ("<f4", 4), ("<f4", (PROFILE_MAX_VERTICES, 2))],
+                          "offsets": [0, 4, 8, 16, 32, 48, 64], "itemsize": 576})
+profile_sample_dtype = np.dtype({"names": ["station", "offset", "height", "segment"], "formats": ["<f4", "<f4", "<f4", "<u4"],
+                                 "offsets": [0, 4, 8, 12], "itemsize": 16})
+# the fp64 block of rule P0, one row per segment, as the launcher places it in the scratch buffer
+profile_segment_dtype = np.dtype({"names": ["au", "av", "du", "dv", "L2", "W2", "inv", "s0"], "formats": ["<f8"] * 8})
+assert profile_dtype.itemsize == 576 and profile_sample_dtype.itemsize == 16 and profile_segment_dtype.itemsize == 64
+
 # ---- ray queries (include/simlod_hip.h, "ray queries") -----------------------------------------------------------------------------------
 RAYS_MAX = 1 << 20
 ray_dtype = np.dtype({"names": ["origin", "tMin", "dir", "tMax", "radius", "spread", "reserved"],

@@ -18,6 +18,8 @@
 // Region query (simlod_query_region): k_q_hier -> k_q_dir -> k_q_count -> k_q_scan -> k_q_write, described in export_region.inc.
 // Footprint query (simlod_query_footprint): k_f_hier -> k_q_dir -> k_f_count -> k_q_scan -> k_f_write, the region query's sequence with an extruded
 // polygon on top of the planes, in export_footprint.inc.
+// Profile query (simlod_query_profile): k_pr_hier -> k_q_dir -> k_pr_count -> k_q_scan -> k_pr_write, the same sequence with a corridor along a
+// polyline on top of the planes and a record per returned sample, in export_profile.inc; the rules themselves in profile_rules.hpp.
 // View query (simlod_query_view): k_v_hier -> k_v_scan -> k_x_dir -> k_copy, the export's sequence with the camera's rules in the walk, in
 // export_view.inc; the rules themselves in view_rules.hpp.
 // View delta (simlod_query_view_delta): k_v_hier -> k_v_scan -> k_d_match -> k_d_scan -> k_d_dir -> k_copy -> k_d_drop; its merge
@@ -39,6 +41,7 @@
 #include "simlod_internal.hpp"
 #include "view_rules.hpp"
 #include "delta_rules.hpp"
+#include "profile_rules.hpp"
 
 namespace simlod {
 namespace {
@@ -48,6 +51,7 @@ namespace {
 #include "export_table.inc"    // hier_walk, k_x_hier, k_x_scan, k_x_dir
 #include "export_region.inc"   // QueryGeom, classify, QItem, QueryLayout, QueryArgs, k_q_hier, k_q_dir, k_q_count, k_q_scan, k_q_write
 #include "export_footprint.inc"  // FootEdge, FootGeom, FootArgs, stage_edges, Footprint, classify_footprint, k_f_hier, k_f_count, k_f_write
+#include "export_profile.inc"  // ProfGeom, ProfArgs, stage_segments, Profile, k_pr_hier, k_pr_count, locate_record, k_pr_write
 #include "export_view.inc"     // ViewArgs, k_v_hier, k_v_scan
 #include "export_delta.inc"    // DeltaLayout, DeltaArgs, k_d_match, k_d_scan, k_d_dir, k_d_drop, MergeArgs, k_d_merge_scan, k_d_merge_dir
 #include "export_pairs.inc"    // the pair records, PairLayout, PairArgs, k_p_hier, wave_descend, k_p_pairs, k_p_scan, TestView, test_chunk
@@ -184,6 +188,39 @@ int launch_footprint(Context& ctx, const SimlodNode* nodes, const SimlodStats* s
 	SIMLOD_LAUNCH(k_f_count, dim3(grid), dim3(LANE_TPB), stream, fa);
 	SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, fa.q);
 	if (samples != nullptr) SIMLOD_LAUNCH(k_f_write, dim3(grid), dim3(LANE_TPB), stream, fa);
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+uint64_t profile_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return query_min_bytes(nodeCapacity, sampleBound) + PROFILE_BLOCK_BYTES; }
+
+// simlod_query_profile with a profile (without one the entry point forwards to launch_query): the segments of rule P0 go into the scratch
+// buffer's block in front of the items by a copy on `stream`; then the region query's sequence with k_pr_hier / k_pr_count / k_pr_write.
+int launch_profile(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
+                   const SimlodProfile* pf, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
+                   uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodProfileSample* records, SimlodQueryCounts* counts,
+                   hipStream_t stream) {
+	if (pf == nullptr || !profile_acceptable(*pf) || (records != nullptr && samples == nullptr)) return (int)hipErrorInvalidValue;
+	ProfileSegment segs[PROFILE_MAX_SEGMENTS];
+	if (!profile_segments(*pf, segs)) return (int)hipErrorInvalidValue;
+	ProfArgs pa{};
+	for (int k = 0; k < 4; k++) { pa.f.axU[k] = (double)pf->axisU[k]; pa.f.axV[k] = (double)pf->axisV[k]; pa.f.axH[k] = (double)pf->axisH[k]; }
+	const int rc = prepare_query(ctx, nodes, stats, u, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples, sampleCapacity, counts,
+	                             PROFILE_BLOCK_BYTES, pa.q);
+	if (rc != 0) return rc;
+	pa.f.n = pf->numVertices - 1u;
+	pa.f.segs = pa.q.x.lay.items - PROFILE_BLOCK_BYTES;
+	pa.records = records;
+	// (pageable host memory: the runtime has read `segs` when the call returns)
+	const hipError_t e = hipMemcpyAsync(pa.q.x.scratch + pa.f.segs, segs, (size_t)pa.f.n * sizeof(ProfileSegment), hipMemcpyHostToDevice, stream);
+	if (e != hipSuccess) return (int)e;
+	const uint32_t grid = copy_grid(pa.q.x.lay.itemCap);
+	SIMLOD_LAUNCH(k_pr_hier, dim3(1), dim3(WG_TPB), stream, pa);
+	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                        // k_q_dir: one wave per table entry
+	if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, pa.q);
+	SIMLOD_LAUNCH(k_pr_count, dim3(grid), dim3(LANE_TPB), stream, pa);
+	SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, pa.q);
+	if (samples != nullptr) SIMLOD_LAUNCH(k_pr_write, dim3(grid), dim3(LANE_TPB), stream, pa);
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();
 }

@@ -478,6 +478,19 @@ int simlod_query_footprint(const SimlodNode* nodes, const SimlodStats* stats, co
 	                        samples, sampleCapacity, counts, (hipStream_t)stream);
 }
 
+uint64_t simlod_profile_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return profile_min_bytes(nodeCapacity, sampleBound); }
+
+int simlod_query_profile(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                         const SimlodProfile* profile, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                         SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodProfileSample* records,
+                         SimlodQueryCounts* counts, void* stream) {
+	if (profile == nullptr)                                                     // rule P5: exactly simlod_query_region; `records` is not written
+		return launch_query(context_of(nodes), nodes, stats, uniforms, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples,
+		                    sampleCapacity, counts, (hipStream_t)stream);
+	return launch_profile(context_of(nodes), nodes, stats, uniforms, region, profile, maxLevel, select, scratch, scratchBytes, table, tableCapacity,
+	                      samples, sampleCapacity, records, counts, (hipStream_t)stream);
+}
+
 int simlod_query_view(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodView* view, uint32_t maxLevel,
                       void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
                       uint64_t sampleCapacity, SimlodViewCounts* counts, void* stream) {

@@ -184,6 +184,11 @@ int launch_footprint(Context& ctx, const SimlodNode* nodes, const SimlodStats* s
                      const SimlodFootprint* footprint, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
                      uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream);
 uint64_t footprint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+int launch_profile(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
+                   const SimlodProfile* profile, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
+                   uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodProfileSample* records, SimlodQueryCounts* counts,
+                   hipStream_t stream);
+uint64_t profile_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
 int launch_view(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodView* view, uint32_t maxLevel,
                 void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity,
                 SimlodViewCounts* counts, hipStream_t stream);

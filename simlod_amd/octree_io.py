@@ -24,6 +24,9 @@ simlod_query_region — every rule restated in numpy float64, which reproduces t
 Footprint queries (include/simlod_hip.h, "footprint queries"): `Footprint` holds the polygon and the affine map into its plane,
 `OctreeExport.crop(region, footprint=...)` is the host mirror of simlod_query_footprint, in the same float64 operation order.
 
+Profile queries (include/simlod_hip.h, "profile queries"): `Profile` holds the polyline, the half-width and the three affine maps,
+`OctreeExport.profile` is the host mirror of simlod_query_profile — samples and records — and `classify_profile` of its rule P3.
+
 View queries (include/simlod_hip.h, "view queries"): `OctreeExport.view` (on a full export) is the host mirror of simlod_query_view and
 `view_geometry` of its rules V2 and V3 — the rasteriser's visibility arithmetic in numpy float32, in the device's operation order.
 
@@ -125,11 +128,13 @@ class OctreeExport:
             return False
         return True
 
-    def crop(self, region, max_level=None, select="all", return_counts=False, footprint=None):
+    def crop(self, region, max_level=None, select="all", return_counts=False, footprint=None, profile=None, test_every_sample=False):
         """The host mirror of simlod_query_region: what the device returns for `region` on the octree this FULL export (select "all", max level
         20; anything else ValueError) was taken from, as an OctreeExport on the host — and, return_counts, the SimlodQueryCounts record too.
         footprint (a Footprint): the mirror of simlod_query_footprint — rules F1-F4 on top of the planes; rule F5's promise is asserted for
-        every copied and every outside node."""
+        every copied and every outside node.
+        profile (a Profile): the samples of simlod_query_profile (OctreeExport.profile adds the records) — rules P1 and P3 on top of the planes;
+        rule P4's promise is asserted likewise.  test_every_sample: the same nodes are listed, but none counts as copied."""
         if self.select != abi.EXPORT_ALL or self.max_level < abi.MAX_DEPTH:
             raise ValueError(f"crop needs a full export (select all, max level 20), not select {self.select} / max level {self.max_level}")
         sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
@@ -144,6 +149,12 @@ class OctreeExport:
             # rule F4: outside by either, copied iff copied by both
             near, corner = classify_footprint(footprint, src, self.box_min, self.box_max)
             outside, inside = outside | (~near & ~corner), inside & ~near & corner
+        if profile is not None:
+            # rule P3, combined as rule F4 combines: outside by either, copied iff copied by both
+            far, covered = classify_profile(profile, src, self.box_min, self.box_max)
+            outside, inside = outside | far, inside & covered
+        if test_every_sample:
+            inside = np.zeros_like(inside)
         # the breadth-first walk over the listed nodes
         order, parent, masks, firsts = [0], [abi.EXPORT_NONE], [], []
         t = 0
@@ -179,9 +190,12 @@ class OctreeExport:
             for nx, ny, nz, d in pl:
                 ok &= ((nx * x + ny * y) + nz * z) + d >= 0
             inbox = (x >= mn[0]) & (x < mn[0] + size) & (y >= mn[1]) & (y < mn[1] + size) & (z >= mn[2]) & (z < mn[2] + size)
-        if footprint is not None:
-            ok &= footprint.contains(smp)
-            # rule F5 for every outside node of the source, listed or not: none of its samples of the contract passes (the copied ones below)
+        if profile is not None:
+            ok &= profile.locate(smp)[0] >= 0
+        if footprint is not None or profile is not None:
+            if footprint is not None:
+                ok &= footprint.contains(smp)
+            # rule F5 / P4 for every outside node of the source, listed or not: none of its samples of the contract passes (the copied ones below)
             bad = ok & inbox & np.repeat(outside, src["numSamples"].astype(np.int64))
             assert not bad.any(), f"node {int(np.repeat(np.arange(len(src)), src['numSamples'].astype(np.int64))[bad][0])} is outside and holds a sample of the box that passes the test"
         parts, ns_out = [], np.zeros(len(out), np.int64)
@@ -208,6 +222,17 @@ class OctreeExport:
         c["numNodes"], c["numSamples"], c["numCandidates"] = len(out), len(samples), int(cand.sum())
         c["numFilteredNodes"], c["numCopiedNodes"] = n_filtered, n_copied
         return ex, c
+
+    # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
+    def profile(self, profile, region=None, max_level=None, select="all", return_counts=False, test_every_sample=False):
+        """The host mirror of simlod_query_profile on the octree this FULL export was taken from: (the samples in the corridor as an OctreeExport
+        on the host, their records as an array of abi.profile_sample_dtype) — and, return_counts, the SimlodQueryCounts record too.  Rule P4 is
+        asserted for every copied and every outside node (crop).  test_every_sample: rule P3 prunes the table as it does, but no node is copied
+        without a test; by rule P4 the samples and records are the same."""
+        got = self.crop(Region() if region is None else region, max_level, select, return_counts, profile=profile, test_every_sample=test_every_sample)
+        ex = got[0] if return_counts else got
+        records = profile.records(ex.samples)
+        return (ex, records, got[1]) if return_counts else (ex, records)
 
     # -- view queries (include/simlod_hip.h, "view queries") ---------------------------------------------------------------------------------
     def view(self, uniforms, bias=0, max_bias=abi.VIEW_MAX_BIAS, budget=None, cull=True, draw_small_root=False, max_level=None, return_counts=False):
@@ -873,6 +898,140 @@ def classify_footprint(footprint, nodes, box_min, box_max):
         near |= ~far
         corner ^= ((a_v > Vlo) != (b_v > Vlo)) & ((c00 > 0) == (dv > 0))
     return near, corner
+
+
+class Profile:
+    """A corridor along a polyline (include/simlod_hip.h, "profile queries"): 2 .. 64 vertices (u, v) as float32 and a half-width, in the plane a
+    point is mapped into by axis_u / axis_v as a Footprint's; axis_h gives the reported height.  The corridor is the union of one square-ended
+    rectangle per segment; where rectangles overlap the lower segment owns the sample."""
+
+    def __init__(self, vertices, half_width, axis_u=(1, 0, 0, 0), axis_v=(0, 1, 0, 0), axis_h=(0, 0, 1, 0)):
+        with np.errstate(over="ignore"):
+            self.vertices = np.asarray(vertices, dtype=np.float64).reshape(-1, 2).astype(np.float32)
+            self.half_width = np.float32(half_width)
+            self.axis_u, self.axis_v, self.axis_h = (np.asarray(a, dtype=np.float64).reshape(4).astype(np.float32) for a in (axis_u, axis_v, axis_h))
+        self._check()
+
+    def _check(self):
+        """What rule P6 refuses in a profile, as ValueError."""
+        if not 2 <= len(self.vertices) <= abi.PROFILE_MAX_VERTICES:
+            raise ValueError(f"{len(self.vertices)} vertices: a profile has 2 .. {abi.PROFILE_MAX_VERTICES}")
+        if not (np.isfinite(self.vertices).all() and np.isfinite(self.axis_u).all() and np.isfinite(self.axis_v).all() and np.isfinite(self.axis_h).all()):
+            raise ValueError("a vertex or an axis coefficient is not finite (as float32)")
+        if not (np.isfinite(self.half_width) and self.half_width > 0):
+            raise ValueError("the half-width is not a positive finite float32")
+        if (self.vertices[1:] == self.vertices[:-1]).all(axis=1).any():
+            raise ValueError("a segment of length zero")
+
+    @classmethod
+    def from_xy(cls, polyline, half_width):
+        """A plan-view profile: u = x, v = y, h = z."""
+        return cls(polyline, half_width)
+
+    def __len__(self):
+        return len(self.vertices)
+
+    def reversed(self):
+        """The same corridor travelled the other way."""
+        return Profile(self.vertices[::-1], self.half_width, self.axis_u, self.axis_v, self.axis_h)
+
+    def record(self):
+        """The SimlodProfile the C ABI takes (abi.profile_dtype, one record); ValueError for what the call would refuse (rule P6)."""
+        self._check()
+        r = np.zeros(1, dtype=abi.profile_dtype)
+        r["numVertices"], r["halfWidth"] = len(self.vertices), self.half_width
+        r["axisU"], r["axisV"], r["axisH"] = self.axis_u, self.axis_v, self.axis_h
+        r["vertices"][0, : len(self.vertices)] = self.vertices
+        return r
+
+    def segments(self):
+        """The fp64 block of rule P0 (abi.profile_segment_dtype, one row per segment), as the launcher computes it."""
+        a = self.vertices.astype(np.float64)
+        s = np.zeros(len(a) - 1, dtype=abi.profile_segment_dtype)
+        s["au"], s["av"] = a[:-1, 0], a[:-1, 1]
+        s["du"], s["dv"] = a[1:, 0] - a[:-1, 0], a[1:, 1] - a[:-1, 1]
+        s["L2"] = s["du"] * s["du"] + s["dv"] * s["dv"]
+        w = np.float64(self.half_width)
+        s["W2"] = (w * w) * s["L2"]
+        ln = np.sqrt(s["L2"])
+        s["inv"] = 1.0 / ln
+        s0 = np.float64(0.0)
+        for i in range(len(s)):                               # (s0_(i+1) = s0_i + len_i, one addition at a time)
+            s["s0"][i] = s0
+            s0 = s0 + ln[i]
+        return s
+
+    @property
+    def length(self):
+        """The polyline's length as rule P0 sums it (float64)."""
+        s = self.segments()
+        return float(s["s0"][-1] + np.sqrt(s["L2"][-1]))
+
+    def project(self, x, y, z):
+        """(u, v) of float64 coordinates, in the header's operation order."""
+        au, av = self.axis_u.astype(np.float64), self.axis_v.astype(np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            return ((au[0] * x + au[1] * y) + au[2] * z) + au[3], ((av[0] * x + av[1] * y) + av[2] * z) + av[3]
+
+    def locate(self, points):
+        """Rules P1 and P2 on point records (abi.point_dtype), every point on its own: (segment as int64, -1: in none; station, offset, height as
+        float32 — station and offset 0 where the point is in no segment)."""
+        p = np.asarray(points)
+        x, y, z = (p[a].astype(np.float64) for a in ("x", "y", "z"))
+        u, v = self.project(x, y, z)
+        ah = self.axis_h.astype(np.float64)
+        seg = np.full(len(p), -1, np.int64)
+        station, offset = np.zeros(len(p), np.float64), np.zeros(len(p), np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            h = ((ah[0] * x + ah[1] * y) + ah[2] * z) + ah[3]
+            left = np.arange(len(p))                           # the points in no segment so far
+            for i, s in enumerate(self.segments()):
+                pu, pv = u[left] - s["au"], v[left] - s["av"]
+                al, c = s["du"] * pu + s["dv"] * pv, s["du"] * pv - s["dv"] * pu
+                new = (al >= 0) & (al <= s["L2"]) & (c * c <= s["W2"])
+                at = left[new]
+                seg[at] = i
+                station[at] = s["s0"] + al[new] * s["inv"]
+                offset[at] = c[new] * s["inv"]
+                left = left[~new]
+            return seg, station.astype(np.float32), offset.astype(np.float32), h.astype(np.float32)
+
+    def records(self, points):
+        """The SimlodProfileSample of every point (abi.profile_sample_dtype): `locate` in the device's layout."""
+        seg, station, offset, h = self.locate(points)
+        r = np.zeros(len(seg), dtype=abi.profile_sample_dtype)
+        r["station"], r["offset"], r["height"] = station, offset, h
+        r["segment"] = np.where(seg < 0, abi.PROFILE_NO_SEGMENT, seg).astype(np.uint32)
+        return r
+
+
+def classify_profile(profile, nodes, box_min, box_max):
+    """Rule P3 of the profile query for every entry of a table: (far, covered) as boolean arrays — every segment is FAR from the node's projected
+    rectangle (the node is outside), some segment COVERS it (the node is copied).  Neither: the node is filtered sample by sample."""
+    mn, size = _box_of(box_min, box_max)
+    s = np.ldexp(size, -nodes["level"].astype(np.int64))[:, None]
+    e = np.ldexp(size, -abi.MAX_DEPTH)
+    A = np.stack([nodes["X"], nodes["Y"], nodes["Z"]], axis=1).astype(np.float64)
+    lo, hi = (mn + A * s) - e, (mn + (A + 1.0) * s) + e
+
+    def span(ax):
+        ax = ax.astype(np.float64)
+        f = [(lo if ax[k] >= 0 else hi)[:, k] for k in range(3)]
+        g = [(hi if ax[k] >= 0 else lo)[:, k] for k in range(3)]
+        return ((ax[0] * f[0] + ax[1] * f[1]) + ax[2] * f[2]) + ax[3], ((ax[0] * g[0] + ax[1] * g[1]) + ax[2] * g[2]) + ax[3]
+
+    (Ulo, Uhi), (Vlo, Vhi) = span(profile.axis_u), span(profile.axis_v)
+    far, covered = np.ones(len(nodes), bool), np.zeros(len(nodes), bool)
+    for sg in profile.segments():
+        du, dv, L2, W2 = sg["du"], sg["dv"], sg["L2"], sg["W2"]
+        ul, uh, vl, vh = du * (Ulo - sg["au"]), du * (Uhi - sg["au"]), dv * (Vlo - sg["av"]), dv * (Vhi - sg["av"])
+        al = np.stack([ul + vl, ul + vh, uh + vl, uh + vh])
+        pl, ph, ql, qh = du * (Vlo - sg["av"]), du * (Vhi - sg["av"]), dv * (Ulo - sg["au"]), dv * (Uhi - sg["au"])
+        c = np.stack([pl - ql, ph - ql, pl - qh, ph - qh])
+        amin, amax, cmin, cmax = al.min(axis=0), al.max(axis=0), c.min(axis=0), c.max(axis=0)
+        far &= (amax < 0) | (amin > L2) | ((cmin > 0) & (cmin * cmin > W2)) | ((cmax < 0) & (cmax * cmax > W2))
+        covered |= (amin >= 0) & (amax <= L2) & (cmin * cmin <= W2) & (cmax * cmax <= W2)
+    return far, covered
 
 
 def _slab(lo, hi, o, d, tmin, tmax, R):

@@ -98,6 +98,9 @@ def lib():
         L.simlod_footprint_buffer_min_bytes.restype = u64
         L.simlod_footprint_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_query_footprint.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
+        L.simlod_profile_buffer_min_bytes.restype = u64
+        L.simlod_profile_buffer_min_bytes.argtypes = [u32, u64]
+        L.simlod_query_profile.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp, vp]
         L.simlod_query_view.argtypes = [vp, vp, vp, vp, u32, vp, u64, vp, u32, vp, u64, vp, vp]
         L.simlod_view_delta_buffer_min_bytes.restype = u64
         L.simlod_view_delta_buffer_min_bytes.argtypes = [u32, u64, u32]
@@ -129,7 +132,7 @@ EXPORTED_SYMBOLS = [
     "simlod_neighbours_buffer_min_bytes", "simlod_query_neighbours", "simlod_footprint_buffer_min_bytes", "simlod_query_footprint",
     "simlod_context_set_clip", "simlod_set_clip", "simlod_query_view",
     "simlod_view_delta_buffer_min_bytes", "simlod_query_view_delta", "simlod_merge_view_delta",
-    "simlod_decode_las_styled",
+    "simlod_decode_las_styled", "simlod_profile_buffer_min_bytes", "simlod_query_profile",
 ]
 
 
@@ -702,6 +705,49 @@ class DeviceOctree:
         u = np.asarray(uniforms).reshape(-1)[0]
         ex = OctreeExport(table, samples[: int(c["numSamples"]) * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_REGION)
         return (ex, c) if return_counts else ex
+
+    # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
+    def _profile(self, uniforms, profile, region, ml, sel, table, samples, records, sample_capacity, bound):
+        """One simlod_query_profile call -> the SimlodQueryCounts record (host).  samples None: count only."""
+        from .octree_io import Region
+        u, up = self._u(uniforms)
+        r, f = (Region() if region is None else region).record(), profile.record()
+        nn = table.numel() // abi.export_node_dtype.itemsize
+        counts = torch.zeros(abi.query_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        scratch = self._export_scratch(int(self.L.simlod_profile_buffer_min_bytes(nn, bound)))
+        _check(self.L.simlod_query_profile(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data), ctypes.c_void_p(f.ctypes.data), ml, sel,
+                                           self._p(scratch), ctypes.c_uint64(scratch.numel()), self._p(table), nn, None if samples is None else self._p(samples),
+                                           ctypes.c_uint64(sample_capacity), None if records is None else self._p(records), self._p(counts), self._stream()),
+               "simlod_query_profile")
+        c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
+        if int(c["error"]) != 0:
+            raise SimlodError(f"simlod_query_profile reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples)")
+        return c
+
+    def count_profile(self, uniforms, profile, region=None, max_level=None, select="cut"):
+        """How much of the octree lies in the corridor of `profile` (an octree_io.Profile) and in `region` at `max_level`: the SimlodQueryCounts
+        record of a count-only simlod_query_profile call.  No sample is written."""
+        sel, ml, nn, bound = self._query_setup(max_level, select)
+        return self._profile(uniforms, profile, region, ml, sel, self._table(nn), None, None, 0, bound)
+
+    def query_profile(self, uniforms, profile, region=None, max_level=None, select="cut", return_counts=False):
+        """The samples in the corridor of `profile` (an octree_io.Profile) — and in `region`, an octree_io.Region — as an octree_io.OctreeExport on
+        this device (select abi.EXPORT_REGION), and their records: a uint8 tensor of numSamples x abi.profile_sample_dtype (station along the
+        polyline, signed offset from the segment's line, height, segment), records[k] for samples[k].  A count-only call first, then the
+        outputs sized exactly.  Raises SimlodError when the device reports an error."""
+        from .octree_io import OctreeExport
+        sel, ml, nn, bound = self._query_setup(max_level, select)
+        c = self._profile(uniforms, profile, region, ml, sel, self._table(nn), None, None, 0, bound)
+        nn, ns = int(c["numNodes"]), int(c["numSamples"])
+        table = torch.empty(nn * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        samples = torch.empty(max(ns, 1) * abi.point_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        records = torch.empty(max(ns, 1) * abi.profile_sample_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        c = self._profile(uniforms, profile, region, ml, sel, table, samples, records, ns, bound)
+        u = np.asarray(uniforms).reshape(-1)[0]
+        ns = int(c["numSamples"])
+        ex = OctreeExport(table, samples[: ns * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_REGION)
+        records = records[: ns * abi.profile_sample_dtype.itemsize]
+        return (ex, records, c) if return_counts else (ex, records)
 
     # -- view queries (include/simlod_hip.h, "view queries") -------------------------------------------------------------------------------
     def _view(self, uniforms, view, ml, table, samples, sample_capacity, bound):

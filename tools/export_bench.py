@@ -15,6 +15,9 @@ host mirror's median `within` (on the first 256 of them) is about 30, with k = 1
 pass) with its count-only call; the rectangle of 30-70 % x 20-90 % of the extents beside the same rectangle as a four-plane
 simlod_query_region, the two alternating rep by rep; the count-only calls of a 14-vertex and a 256-vertex star, alternating — and the
 device-to-device copy, all in this one run.
+--profile: instead, simlod_query_profile CUT@20 on the same octree — a 5-vertex polyline across the terrain whose half-width gives the
+corridor 1 % of the plan area, with records, without records, and simlod_query_footprint with the corridor's outline polygon, the three
+alternating rep by rep; the count-only call — and the device-to-device copy, all in this one run.
 --view: instead, simlod_query_view on the same octree under bench.py's bird and close-up cameras at 1920 x 1080 — without a budget beside
 simlod_export_octree VISIBLE of the same frame into the same buffers, the two alternating rep by rep; the count-only call; the path the
 query replaces, simlod_launch_render + the VISIBLE export — and the device-to-device copy, all in this one run.
@@ -541,6 +544,77 @@ def view_delta_bench(dev, u, box, st, reps, only=None):
     print(json.dumps(out))
 
 
+def profile_bench(dev, u, box, st, reps):
+    from simlod_amd import fingerprint
+    from simlod_amd.octree_io import Footprint, Profile, Region
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    need = max(int(L.simlod_profile_buffer_min_bytes(nn, bound)), int(L.simlod_footprint_buffer_min_bytes(nn, bound)))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    table = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    samples = torch.empty(bound * 16, dtype=torch.uint8, device=dev.device)
+    records = torch.empty(bound * 16, dtype=torch.uint8, device=dev.device)
+    counts = torch.zeros(32, dtype=torch.uint8, device=dev.device)
+    uu, up = dev._u(u)
+    b = np.asarray(box, dtype=np.float64)
+    # five vertices across the terrain; the half-width that gives the corridor 1 % of the plan area
+    line = np.array([(0.05, 0.2), (0.3, 0.8), (0.5, 0.25), (0.72, 0.85), (0.95, 0.4)]) * b[:2]
+    seg = np.diff(line, axis=0)
+    length = float(np.linalg.norm(seg, axis=1).sum())
+    w = 0.01 * b[0] * b[1] / (2.0 * length)
+    prof = Profile.from_xy(line, w)
+    # the corridor's outline as a footprint: the polyline offset by w to either side with mitred bends (the set only approximately: the
+    # rectangles' square ends at a bend are not a polygon of ten vertices)
+    nrm = np.stack([-seg[:, 1], seg[:, 0]], axis=1) / np.linalg.norm(seg, axis=1)[:, None]
+    off = [nrm[0]] + [(nrm[i - 1] + nrm[i]) / (1.0 + float(nrm[i - 1] @ nrm[i])) for i in range(1, len(seg))] + [nrm[-1]]
+    outline = Footprint.from_xy(np.concatenate([line + w * np.array(off), (line - w * np.array(off))[::-1]]))
+    prec, frec, none = prof.record(), outline.record(), Region().record()
+
+    def profile(with_records=True, count_only=False):
+        rc = L.simlod_query_profile(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(none.ctypes.data), ctypes.c_void_p(prec.ctypes.data), 20, abi.EXPORT_CUT,
+                                    p(scratch), ctypes.c_uint64(need), p(table), nn, None if count_only else p(samples), ctypes.c_uint64(bound),
+                                    p(records) if with_records and not count_only else None, p(counts), stream)
+        assert rc == 0
+
+    def footprint():
+        rc = L.simlod_query_footprint(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(none.ctypes.data), ctypes.c_void_p(frec.ctypes.data), 20, abi.EXPORT_CUT,
+                                      p(scratch), ctypes.c_uint64(need), p(table), nn, p(samples), ctypes.c_uint64(bound), p(counts), stream)
+        assert rc == 0
+
+    def read_counts():
+        torch.cuda.synchronize()
+        c = counts.cpu().numpy().view(abi.query_counts_dtype)[0].copy()
+        assert int(c["error"]) == 0
+        return c
+
+    def row(ms, c):
+        return {"ms": round(ms[0], 4), "ms_min": round(ms[1], 4), "nodes_listed": int(c["numNodes"]), "nodes_copied": int(c["numCopiedNodes"]),
+                "nodes_filtered": int(c["numFilteredNodes"]), "numCandidates": int(c["numCandidates"]), "numSamples": int(c["numSamples"])}
+
+    copy_dst = torch.empty(int(st["numPoints"]) * 16, dtype=torch.uint8, device=dev.device)
+    copy_src = samples[: copy_dst.numel()]
+    t_rec, t_plain, t_foot = timed_alternating([lambda: profile(True), lambda: profile(False), footprint], reps)
+    t_count = timed(lambda: profile(count_only=True), reps)
+    t_copy = timed(lambda: copy_dst.copy_(copy_src), reps)
+    copied_per_ms = copy_dst.numel() / t_copy[0]                                # bytes copied (each read once and written once) per ms
+    out = {"points": int(st["numPoints"]), "numNodes": nn, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(), "half_width": round(w, 4),
+           "polyline_length": round(length, 2),
+           "d2d_copy": {"ms": round(t_copy[0], 4), "bytes": 2 * copy_dst.numel(), "GBs": round(2 * copy_dst.numel() / (t_copy[0] * 1e6), 1)}}
+    profile(True)
+    c = read_counts()
+    out["profile_with_records"] = row(t_rec, c)
+    out["profile_with_records"]["share_of_points"] = round(int(c["numSamples"]) / max(int(st["numPoints"]), 1), 5)
+    out["profile_with_records"]["count_only_ms"] = round(t_count[0], 4)
+    out["profile_without_records"] = row(t_plain, c)
+    footprint()
+    out["footprint_outline"] = row(t_foot, read_counts())
+    t_records = int(c["numSamples"]) * 16 / copied_per_ms
+    limit = 1.2 * (t_foot[0] + t_records)
+    out["bound"] = {"what": "t(profile with records) <= 1.2 * (t(footprint of the outline) + numSamples * 16 bytes at the copy's rate), same run",
+                    "records_copy_ms": round(t_records, 5), "limit_ms": round(limit, 4), "ratio": round(t_rec[0] / limit, 4), "held": bool(t_rec[0] <= limit)}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=36_000_000)
@@ -549,6 +623,7 @@ def main():
     ap.add_argument("--buildable", action="store_true", help="also time simlod_import_octree_buildable (grid rebuild included)")
     ap.add_argument("--region", action="store_true", help="time simlod_query_region (whole box, half the terrain, a city block) instead")
     ap.add_argument("--footprint", action="store_true", help="time simlod_query_footprint (half the terrain, a rectangle beside its four planes, two stars) instead")
+    ap.add_argument("--profile", action="store_true", help="time simlod_query_profile (a 5-vertex corridor over 1 % of the terrain, with and without records, beside the footprint of its outline) instead")
     ap.add_argument("--rays", action="store_true", help="time simlod_query_rays (one pixel cone, 4 096 vertical rays) instead")
     ap.add_argument("--neighbours", action="store_true", help="time simlod_query_neighbours (4 096 queries, k = 1, 8, 16, count-only) instead")
     ap.add_argument("--view", action="store_true", help="time simlod_query_view (bird and close-up cameras beside the VISIBLE export of the same frame, count-only) instead")
@@ -576,6 +651,8 @@ def main():
         return region_bench(dev, u, box, st, args.reps)
     if args.footprint:
         return footprint_bench(dev, u, box, st, args.reps)
+    if args.profile:
+        return profile_bench(dev, u, box, st, args.reps)
     if args.rays:
         return rays_bench(dev, u, box, st, args.reps, T, 1920, 1080)
     if args.neighbours:
