@@ -979,6 +979,72 @@ int simlod_merge_view_delta(const SimlodExportNode* held, uint32_t numHeld, cons
                             const SimlodDeltaEntry* entries, uint32_t numNodes, const SimlodPoint* delta, void* scratch, uint64_t scratchBytes,
                             SimlodPoint* samples, uint64_t sampleCapacity, SimlodExportCounts* counts, void* stream);
 
+/* ---- packed samples: 8-byte records for export, query and delta results -------------------------------------------------------------------------
+ * Every way out of the octree ends in 16-byte SimlodPoint records.  simlod_pack_samples turns the samples of any table + samples pair this library
+ * wrote — an export, a region / footprint / profile / view query, a view delta — into 8-byte records, simlod_unpack_samples turns them back.
+ * A voxel is a cell of its node's 128^3 grid and comes back bit for bit; a point is stored relative to its leaf's cube with 13 bits per axis.
+ *
+ * Box: min = uniforms.boxMin, size = the largest fp32 extent, as in the region queries.  All fp64 arithmetic works from the fp32 inputs, without
+ * contraction, in the order written.
+ *  K0. A packed sample is one little-endian uint64_t: bits 0-23 the low 24 bits of the colour word, bits 24-36 qx, bits 37-49 qy, bits 50-62 qz,
+ *      bit 63 zero.  Alpha is not carried: unpack writes 0xff000000 | rgb.
+ *  K1. Per node, in fp64: ns = size * 2^-level (exact); nmin_a = (double)min_a + (double)A * ns for the node's coordinate A on axis a.
+ *  K2. Points (the entry has SIMLOD_EXPORT_FLAG_LEAF): k = 8192.0 / ns, formed once per node; t = ((double)p_a - nmin_a) * k;
+ *      q_a = t >= 0 ? (t < 8192 ? (uint32)t : 8191) : 0 (a NaN gives 0).  The sample is CLAMPED iff some axis fails t >= 0 && t < 8192.
+ *  K3. Point decode: p'_a = (float)(nmin_a + ((double)q_a + 0.5) * (ns / 8192.0)).
+ *  K4. Voxels (no SIMLOD_EXPORT_FLAG_LEAF): K2 with 128 in the place of 8192, so the fields hold values below 128 (CLAMPED likewise).  Decode is
+ *      the builder's fp32 sequence for a cell centre, operation by operation: nodeSize = size / 2^level, nmin_a = ((float)A + 0.0f) * nodeSize +
+ *      min_a, p'_a = nmin_a + (nodeSize * ((float)q_a + 0.5f)) / 128.0f.  A voxel is INEXACT iff a decoded coordinate differs in bits from the
+ *      original; it is packed all the same.  On octrees the builder made no voxel is.
+ *  K5. Which samples.  entries == NULL: per table entry with SIMLOD_EXPORT_FLAG_SELECTED the range [firstSample, firstSample + numSamples).
+ *      With `entries` (SimlodDeltaEntry, same index as the table): per entry with state != SIMLOD_DELTA_NONE the range [firstDelta, firstDelta +
+ *      numDelta) of the delta array.  packed[i] belongs to samples[i]: same index, same ranges; indices no range covers are not written.
+ *  K6. SimlodPackCounts: numSamples packed or unpacked, numClamped, numInexact, numAlpha (samples whose top colour byte is not 0xff), error.
+ *      Unpack reports numSamples and error only; the rest is 0.
+ *  K7. An entry whose range reaches beyond sampleCapacity sets SIMLOD_EXPORT_ERR_CAPACITY and writes nothing (every other entry is complete, and
+ *      numSamples counts those).  Too few scratch items for the pieces of all ranges set SIMLOD_EXPORT_ERR_CAPACITY too; then nothing at all is
+ *      written and numSamples is 0.  An entry with level > 20 sets SIMLOD_EXPORT_ERR_NODE_COUNT and is skipped.  The table must be one this
+ *      library wrote; for other content the result is unspecified, but nothing outside the given arrays is read or written.
+ *  K8. Unpack masks every field to its width (13 bits; 7 for voxels) and ignores bit 63.  For a voxel node with numInexact == 0 and numAlpha == 0,
+ *      unpack(pack(samples)) is the sample array byte for byte.  For a point that was not clamped |p'_a - p_a| <= ns / 16384 + ulp32(p'_a) / 2 +
+ *      ns * 2^-40 (the last term covers the two fp64 roundings of K2).
+ *  K9. Pack and unpack only read their inputs; they need no octree, no context and no Stats. */
+#define SIMLOD_PACK_COLOR_BITS 24u
+#define SIMLOD_PACK_POINT_BITS 13u     /* per axis, points */
+#define SIMLOD_PACK_VOXEL_BITS 7u      /* per axis, voxels: the low bits of the same fields */
+#define SIMLOD_PACK_SHIFT_X    24u
+#define SIMLOD_PACK_SHIFT_Y    37u
+#define SIMLOD_PACK_SHIFT_Z    50u
+typedef struct SimlodPackCounts {      /* written by the device */
+	uint64_t numSamples;               /* samples packed / unpacked                                                              */
+	uint64_t numClamped;               /* rule K2 / K4                                                                           */
+	uint64_t numInexact;               /* rule K4                                                                                */
+	uint64_t numAlpha;                 /* samples whose top colour byte is not 0xff                                              */
+	uint32_t error;                    /* SIMLOD_EXPORT_ERR_* bits (rule K7)                                                     */
+	uint32_t reserved;                 /* 0                                                                                      */
+} SimlodPackCounts;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodPackCounts) == 40, "PackCounts");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodPackCounts, numSamples) == 0, "PackCounts.numSamples");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodPackCounts, numClamped) == 8, "PackCounts.numClamped");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodPackCounts, numInexact) == 16, "PackCounts.numInexact");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodPackCounts, numAlpha) == 24, "PackCounts.numAlpha");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodPackCounts, error) == 32, "PackCounts.error");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodPackCounts, reserved) == 36, "PackCounts.reserved");
+
+/* Bytes of the `scratch` buffer the two calls below need for a table of numNodes entries whose ranges hold up to sampleBound samples: a header,
+ * a word per entry and 64 bytes per piece of at most 1 000 samples. */
+uint64_t simlod_pack_buffer_min_bytes(uint32_t numNodes, uint64_t sampleBound);
+
+/* Pack (rules above) and unpack.  All pointers other than `uniforms` are device memory; asynchronous on `stream`; nothing is allocated,
+ * synchronised or copied.  `samples` / `packed` have sampleCapacity records.  hipErrorInvalidValue with nothing enqueued: a null pointer other
+ * than `entries`, numNodes == 0, a box that is not finite or has no extent, scratchBytes below simlod_pack_buffer_min_bytes(numNodes, 0). */
+int simlod_pack_samples(const SimlodUniforms* uniforms /*host*/, const SimlodExportNode* table, const SimlodDeltaEntry* entries /*or NULL*/,
+                        uint32_t numNodes, const SimlodPoint* samples, uint64_t sampleCapacity, void* scratch, uint64_t scratchBytes,
+                        uint64_t* packed, SimlodPackCounts* counts, void* stream);
+int simlod_unpack_samples(const SimlodUniforms* uniforms /*host*/, const SimlodExportNode* table, const SimlodDeltaEntry* entries /*or NULL*/,
+                          uint32_t numNodes, const uint64_t* packed, uint64_t sampleCapacity, void* scratch, uint64_t scratchBytes,
+                          SimlodPoint* samples, SimlodPackCounts* counts, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

@@ -170,6 +170,14 @@ delta_counts_dtype = np.dtype({"names": ["view", "numDeltaSamples", "numKeptSamp
                                "offsets": [0, 200, 208, 216, 220, 224, 228], "itemsize": 232})
 assert delta_entry_dtype.itemsize == 24 and delta_counts_dtype.itemsize == 232
 
+# ---- packed samples (include/simlod_hip.h, "packed samples") ------------------------------------------------------------------------------
+PACK_COLOR_BITS, PACK_POINT_BITS, PACK_VOXEL_BITS = 24, 13, 7               # rule K0: bits 0-23 rgb, then 13 bits per axis; voxels use the low 7
+PACK_SHIFT_X, PACK_SHIFT_Y, PACK_SHIFT_Z = 24, 37, 50
+PACK_ITEM_BYTES = 64                                                       # of the scratch buffer per piece of at most 1 000 samples
+pack_counts_dtype = np.dtype({"names": ["numSamples", "numClamped", "numInexact", "numAlpha", "error", "reserved"],
+                              "formats": ["<u8", "<u8", "<u8", "<u8", "<u4", "<u4"], "offsets": [0, 8, 16, 24, 32, 36], "itemsize": 40})
+assert pack_counts_dtype.itemsize == 40
+
 
 # ---- clip regions (include/simlod_hip.h, "clip regions") --------------------------------------------------------------------------------
 CLIP_OFF, CLIP_INSIDE, CLIP_OUTSIDE, CLIP_HIGHLIGHT = 0, 1, 2, 3

@@ -24,6 +24,8 @@
 // export_view.inc; the rules themselves in view_rules.hpp.
 // View delta (simlod_query_view_delta): k_v_hier -> k_v_scan -> k_d_match -> k_d_scan -> k_d_dir -> k_copy -> k_d_drop; its merge
 // (simlod_merge_view_delta): k_d_merge_scan -> k_d_merge_dir -> k_copy, in export_delta.inc; the rules in delta_rules.hpp.
+// Packed samples (simlod_pack_samples / simlod_unpack_samples): k_pk_scan -> k_pk_dir -> k_pk_pack / k_pk_unpack, in export_pack.inc; the rules
+// in pack_rules.hpp.  They read a table and a sample array, no octree.
 // Pair queries: k_p_hier -> k_q_dir -> k_p_pairs<Q, count> -> k_p_scan<Q> -> k_p_pairs<Q, fill> -> Q's test kernel -> Q's reduce kernel; the pipeline
 // is written once over a query trait Q, in export_pairs.inc.  Ray query (simlod_query_rays): RayQuery, k_r_test, k_r_reduce, in export_rays.inc.
 // Neighbour query (simlod_query_neighbours): NbQuery, k_n_test, k_n_reduce, in export_neighbours.inc.
@@ -42,6 +44,7 @@
 #include "view_rules.hpp"
 #include "delta_rules.hpp"
 #include "profile_rules.hpp"
+#include "pack_rules.hpp"
 
 namespace simlod {
 namespace {
@@ -54,6 +57,7 @@ namespace {
 #include "export_profile.inc"  // ProfGeom, ProfArgs, stage_segments, Profile, k_pr_hier, k_pr_count, locate_record, k_pr_write
 #include "export_view.inc"     // ViewArgs, k_v_hier, k_v_scan
 #include "export_delta.inc"    // DeltaLayout, DeltaArgs, k_d_match, k_d_scan, k_d_dir, k_d_drop, MergeArgs, k_d_merge_scan, k_d_merge_dir
+#include "export_pack.inc"     // PackItem, PackLayout, PackArgs, k_pk_scan, k_pk_dir, pack_reduce, k_pk_pack, k_pk_unpack
 #include "export_pairs.inc"    // the pair records, PairLayout, PairArgs, k_p_hier, wave_descend, k_p_pairs, k_p_scan, TestView, test_chunk
 #include "export_rays.inc"     // RayArgs, ray_load, slab, sample_t, RayQuery, k_r_test, k_r_reduce
 #include "export_neighbours.inc"  // NbArgs, sphere_load, sphere_cube, sphere_d2, NbQuery, k_n_test, k_n_reduce
@@ -315,6 +319,32 @@ int launch_merge_view_delta(const SimlodExportNode* held, uint32_t numHeld, cons
 	SIMLOD_LAUNCH(k_d_merge_scan, dim3(1), dim3(WG_TPB), stream, m);
 	if (numNodes != 0u) SIMLOD_LAUNCH(k_d_merge_dir, dim3((numNodes + LANE_TPB - 1u) / LANE_TPB), dim3(LANE_TPB), stream, m);
 	SIMLOD_LAUNCH(k_copy, dim3(copy_grid(m.lay.itemCap)), dim3(LANE_TPB), stream, (const uint8_t*)m.scratch, m.lay.items);
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+uint64_t pack_min_bytes(uint32_t numNodes, uint64_t sampleBound) {
+	return PackLayout(numNodes).items + pack_item_bound(numNodes, sampleBound) * sizeof(PackItem);
+}
+
+// simlod_pack_samples (unpack false) and simlod_unpack_samples: the checks, then k_pk_scan -> k_pk_dir -> the hot kernel.  The items take what
+// the buffer has behind the words per entry; the device reports a buffer that holds too few of them.
+int launch_pack(bool unpack, const SimlodUniforms* u, const SimlodExportNode* table, const SimlodDeltaEntry* entries, uint32_t numNodes, const void* in,
+                uint64_t sampleCapacity, void* scratch, uint64_t scratchBytes, void* out, SimlodPackCounts* counts, hipStream_t stream) {
+	if (u == nullptr || table == nullptr || in == nullptr || scratch == nullptr || out == nullptr || counts == nullptr || numNodes == 0u)
+		return (int)hipErrorInvalidValue;
+	if (scratchBytes < pack_min_bytes(numNodes, 0u)) return (int)hipErrorInvalidValue;
+	PackArgs a{};
+	const float mn[3] = {u->boxMin.x, u->boxMin.y, u->boxMin.z}, mx[3] = {u->boxMax.x, u->boxMax.y, u->boxMax.z};
+	if (!pack_box(mn, mx, a.box)) return (int)hipErrorInvalidValue;
+	const PackLayout pl(numNodes);
+	a.table = table; a.entries = entries; a.n = numNodes; a.sampleCap = sampleCapacity; a.scratch = reinterpret_cast<uint8_t*>(scratch);
+	a.first = pl.first; a.items = pl.items; a.itemCap = std::min<uint64_t>((scratchBytes - pl.items) / sizeof(PackItem), 0xffffffffull);
+	a.in = in; a.out = out; a.counts = counts;
+	SIMLOD_LAUNCH(k_pk_scan, dim3(1), dim3(WG_TPB), stream, a);
+	SIMLOD_LAUNCH(k_pk_dir, dim3((numNodes + LANE_TPB - 1u) / LANE_TPB), dim3(LANE_TPB), stream, a);
+	if (unpack) SIMLOD_LAUNCH(k_pk_unpack, dim3(copy_grid(a.itemCap)), dim3(LANE_TPB), stream, a);
+	else SIMLOD_LAUNCH(k_pk_pack, dim3(copy_grid(a.itemCap)), dim3(LANE_TPB), stream, a);
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();
 }

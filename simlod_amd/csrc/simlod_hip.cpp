@@ -519,6 +519,20 @@ int simlod_merge_view_delta(const SimlodExportNode* held, uint32_t numHeld, cons
 	                               (hipStream_t)stream);
 }
 
+uint64_t simlod_pack_buffer_min_bytes(uint32_t numNodes, uint64_t sampleBound) { return pack_min_bytes(numNodes, sampleBound); }
+
+int simlod_pack_samples(const SimlodUniforms* uniforms, const SimlodExportNode* table, const SimlodDeltaEntry* entries, uint32_t numNodes,
+                        const SimlodPoint* samples, uint64_t sampleCapacity, void* scratch, uint64_t scratchBytes, uint64_t* packed,
+                        SimlodPackCounts* counts, void* stream) {
+	return launch_pack(false, uniforms, table, entries, numNodes, samples, sampleCapacity, scratch, scratchBytes, packed, counts, (hipStream_t)stream);
+}
+
+int simlod_unpack_samples(const SimlodUniforms* uniforms, const SimlodExportNode* table, const SimlodDeltaEntry* entries, uint32_t numNodes,
+                          const uint64_t* packed, uint64_t sampleCapacity, void* scratch, uint64_t scratchBytes, SimlodPoint* samples,
+                          SimlodPackCounts* counts, void* stream) {
+	return launch_pack(true, uniforms, table, entries, numNodes, packed, sampleCapacity, scratch, scratchBytes, samples, counts, (hipStream_t)stream);
+}
+
 uint64_t simlod_rays_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates) {
 	return rays_min_bytes(nodeCapacity, sampleBound, numRays, numPairs, numCandidates);
 }

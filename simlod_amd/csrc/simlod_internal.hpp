@@ -200,6 +200,9 @@ int launch_merge_view_delta(const SimlodExportNode* held, uint32_t numHeld, cons
                             const SimlodDeltaEntry* entries, uint32_t numNodes, const SimlodPoint* delta, void* scratch, uint64_t scratchBytes,
                             SimlodPoint* samples, uint64_t sampleCapacity, SimlodExportCounts* counts, hipStream_t stream);
 uint64_t view_delta_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numHeld);
+int launch_pack(bool unpack, const SimlodUniforms* u, const SimlodExportNode* table, const SimlodDeltaEntry* entries, uint32_t numNodes, const void* in,
+                uint64_t sampleCapacity, void* scratch, uint64_t scratchBytes, void* out, SimlodPackCounts* counts, hipStream_t stream);
+uint64_t pack_min_bytes(uint32_t numNodes, uint64_t sampleBound);
 int launch_rays(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRay* rays, uint32_t numRays,
                 uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
                 SimlodRayHit* hits, SimlodRayCounts* counts, hipStream_t stream);

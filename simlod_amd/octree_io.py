@@ -33,6 +33,11 @@ View queries (include/simlod_hip.h, "view queries"): `OctreeExport.view` (on a f
 View deltas (include/simlod_hip.h, "view deltas"): `OctreeExport.view_delta` is the host mirror of simlod_query_view_delta — `view` plus the
 rules D2-D6 (`delta_between`) — and `ViewDelta.apply` of simlod_merge_view_delta (rule D9).
 
+Packed samples (include/simlod_hip.h, "packed samples"): `pack_samples` / `unpack_samples` are the host mirror of simlod_pack_samples /
+simlod_unpack_samples (rules K0-K8, numpy float64 / float32 in the device's operation order), `OctreeExport.pack` and `ViewDelta.pack` apply them,
+and `PackedExport` has a file format of its own: magic b"SIMLODP\\0", version 1, the same 64-byte header (numSamples counts the 8-byte records)
+and table, then numSamples x 8 bytes; `PackedExport.load` checks header, size and table like `OctreeExport.load`.
+
 Ray queries (include/simlod_hip.h, "ray queries"): `Rays` holds a batch of SimlodRay records, `OctreeExport.cast` (on a full export) and
 `OctreeExport.cast_selected` (on any export) are the host mirror of simlod_query_rays, in the same float64 operation order.
 
@@ -516,6 +521,13 @@ class OctreeExport:
         ex = cls(raw[HEADER_BYTES: HEADER_BYTES + tb].copy(), raw[HEADER_BYTES + tb:].copy(), h["box_min"], h["box_max"], int(h["max_level"]), int(h["select"]))
         return ex.validate()
 
+    def pack(self, return_counts=False):
+        """The same export with 8-byte samples (rules K0-K7 of "packed samples", in numpy): a PackedExport on the host, and with return_counts
+        the SimlodPackCounts record.  DeviceOctree.pack does the same on the device."""
+        packed, c = pack_samples(self.nodes, self.samples, self.box_min, self.box_max)
+        px = PackedExport(self.nodes, packed, self.box_min, self.box_max, self.max_level, self.select)
+        return (px, c) if return_counts else px
+
 
 def _box_of(box_min, box_max):
     """(min as float64, size): the box as construct.hip derives it — the largest of the fp32 differences boxMax - boxMin."""
@@ -743,6 +755,264 @@ class ViewDelta:
                 parts.append(dl[a: a + d])
         samples = np.concatenate(parts) if parts else np.zeros(0, dtype=abi.point_dtype)
         return OctreeExport(tb, samples, self.box_min, self.box_max, self.max_level, abi.EXPORT_VISIBLE)
+
+    def pack(self, return_counts=False):
+        """This delta with 8-byte samples (rule K5 with the entries): a PackedViewDelta on the host."""
+        packed, c = pack_samples(self.nodes, self.samples, self.box_min, self.box_max, self.entries)
+        pd = PackedViewDelta(self.nodes, self.entries, packed, self.dropped, self.box_min, self.box_max, self.max_level, self.counts)
+        return (pd, c) if return_counts else pd
+
+
+# ---- packed samples (include/simlod_hip.h, "packed samples"; simlod_amd/csrc/pack_rules.hpp) ------------------------------------------------
+PACKED_MAGIC = b"SIMLODP\0"
+PACKED_VERSION = 1
+
+
+def _pack_box(box_min, box_max):
+    """(min fp32, size fp32) of rule K7's box; ValueError for what the calls refuse: a corner that is not finite, a box without extent."""
+    mn, mx = np.asarray(box_min, np.float32).reshape(3), np.asarray(box_max, np.float32).reshape(3)
+    if not (np.isfinite(mn).all() and np.isfinite(mx).all()):
+        raise ValueError("the box is not finite")
+    with np.errstate(over="ignore"):
+        size = (mx - mn).max()
+    if not np.isfinite(size) or not size > 0:
+        raise ValueError("the box has no extent")
+    return mn, np.float32(size)
+
+
+def _pack_ranges(table, entries, capacity):
+    """Rules K5 and K7 per table entry: (the entries that are touched, first, n of each, the error bits)."""
+    t = np.asarray(table).view(abi.export_node_dtype).reshape(-1)
+    if len(t) == 0:
+        raise ValueError("empty table")
+    if entries is None:
+        on = (t["flags"] & abi.EXPORT_FLAG_SELECTED) != 0
+        first, n = t["firstSample"].astype(np.uint64), t["numSamples"].astype(np.uint64)
+    else:
+        e = np.asarray(entries).view(abi.delta_entry_dtype).reshape(-1)
+        if len(e) != len(t):
+            raise ValueError("table and entries differ in length")
+        on = e["state"] != abi.DELTA_NONE
+        first, n = e["firstDelta"].astype(np.uint64), e["numDelta"].astype(np.uint64)
+    on = on & (n > 0)
+    deep = on & (t["level"] > abi.MAX_DEPTH)
+    cap = np.uint64(capacity)
+    beyond = on & ~deep & ((first > cap) | (n > cap - np.minimum(first, cap)))
+    err = (abi.EXPORT_ERR_NODE_COUNT if deep.any() else 0) | (abi.EXPORT_ERR_CAPACITY if beyond.any() else 0)
+    idx = np.nonzero(on & ~deep & ~beyond)[0]
+    return t, idx, first[idx].astype(np.int64), n[idx].astype(np.int64), err
+
+
+def _pack_frames(t, idx, mn, size):
+    """Rules K1, K2 and K4 per touched entry: leaf, ns, nmin (n x 3, float64), k, the fp32 node size and corner of the voxel decode."""
+    level = t["level"][idx].astype(np.int64)
+    leaf = (t["flags"][idx] & abi.EXPORT_FLAG_LEAF) != 0
+    A = np.stack([t["X"][idx], t["Y"][idx], t["Z"][idx]], axis=1)
+    ns = np.ldexp(np.float64(size), -level)
+    nmin = mn.astype(np.float64)[None, :] + A.astype(np.float64) * ns[:, None]
+    k = np.where(leaf, 8192.0, 128.0) / ns
+    fns = (size / np.ldexp(np.float32(1.0), level).astype(np.float32)).astype(np.float32)
+    fmin = ((A.astype(np.float32) + np.float32(0.0)) * fns[:, None] + mn[None, :]).astype(np.float32)
+    return leaf, ns, nmin, k, fns, fmin
+
+
+def _pack_expand(first, n):
+    """(the sample index, the position in idx of its entry) of every sample of the ranges"""
+    ent = np.repeat(np.arange(len(n), dtype=np.int64), n)
+    start = np.repeat(np.cumsum(n) - n, n)
+    return np.repeat(first, n) + (np.arange(int(n.sum()), dtype=np.int64) - start), ent
+
+
+def _voxel_axis(fmin, fns, q):
+    return (fmin + (fns * (q.astype(np.float32) + np.float32(0.5))) / np.float32(128.0)).astype(np.float32)
+
+
+def pack_samples(table, samples, box_min, box_max, entries=None, out=None):
+    """simlod_pack_samples in numpy (rules K0-K7): -> (the uint64 records, one per element of `samples` — those no range covers keep what `out`
+    had, zero without one —, the SimlodPackCounts record).  `entries` (abi.delta_entry_dtype): the ranges of a view delta.  ValueError for what
+    the call refuses: an empty table, a box that is not finite or has no extent."""
+    mn, size = _pack_box(box_min, box_max)
+    smp = np.asarray(samples).view(abi.point_dtype).reshape(-1)
+    t, idx, first, n, err = _pack_ranges(table, entries, len(smp))
+    packed = np.zeros(len(smp), np.uint64) if out is None else np.asarray(out, np.uint64).copy()
+    c = np.zeros((), dtype=abi.pack_counts_dtype)
+    c["error"], c["numSamples"] = err, int(n.sum())
+    if len(idx):
+        leaf, ns, nmin, k, fns, fmin = _pack_frames(t, idx, mn, size)
+        si, ent = _pack_expand(first, n)
+        p = smp[si]
+        lf = leaf[ent]
+        lim = np.where(lf, 8192.0, 128.0)
+        clamped = np.zeros(len(si), bool)
+        inexact = np.zeros(len(si), bool)
+        word = (p["color"] & np.uint32(0xFFFFFF)).astype(np.uint64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for a, (name, shift) in enumerate((("x", abi.PACK_SHIFT_X), ("y", abi.PACK_SHIFT_Y), ("z", abi.PACK_SHIFT_Z))):
+                tt = (p[name].astype(np.float64) - nmin[ent, a]) * k[ent]
+                inside = (tt >= 0) & (tt < lim)
+                q = np.where(inside, tt, 0.0).astype(np.uint64)
+                q = np.where(tt >= lim, (lim - 1).astype(np.uint64), q)
+                clamped |= ~inside
+                back = _voxel_axis(fmin[ent, a], fns[ent], q)
+                inexact |= ~lf & (back.view(np.uint32) != p[name].view(np.uint32))
+                word |= q << np.uint64(shift)
+        packed[si] = word
+        c["numClamped"], c["numInexact"], c["numAlpha"] = int(clamped.sum()), int(inexact.sum()), int(((p["color"] >> 24) != 0xFF).sum())
+    return packed, c
+
+
+def unpack_samples(table, packed, box_min, box_max, entries=None, out=None):
+    """simlod_unpack_samples in numpy (rules K3, K4, K8): -> (the samples as abi.point_dtype, one per record of `packed` — those no range
+    covers keep what `out` had, zero without one —, the SimlodPackCounts record: numSamples and error)."""
+    mn, size = _pack_box(box_min, box_max)
+    pk = np.asarray(packed).view(np.uint64).reshape(-1)
+    t, idx, first, n, err = _pack_ranges(table, entries, len(pk))
+    smp = np.zeros(len(pk), dtype=abi.point_dtype) if out is None else np.asarray(out).view(abi.point_dtype).reshape(-1).copy()
+    c = np.zeros((), dtype=abi.pack_counts_dtype)
+    c["error"], c["numSamples"] = err, int(n.sum())
+    if len(idx):
+        leaf, ns, nmin, k, fns, fmin = _pack_frames(t, idx, mn, size)
+        si, ent = _pack_expand(first, n)
+        w = pk[si]
+        lf = leaf[ent]
+        mask = np.where(lf, (1 << abi.PACK_POINT_BITS) - 1, (1 << abi.PACK_VOXEL_BITS) - 1).astype(np.uint64)
+        step = ns[ent] / 8192.0
+        o = np.zeros(len(si), dtype=abi.point_dtype)
+        for a, (name, shift) in enumerate((("x", abi.PACK_SHIFT_X), ("y", abi.PACK_SHIFT_Y), ("z", abi.PACK_SHIFT_Z))):
+            q = (w >> np.uint64(shift)) & mask
+            pt = (nmin[ent, a] + (q.astype(np.float64) + 0.5) * step).astype(np.float32)
+            o[name] = np.where(lf, pt, _voxel_axis(fmin[ent, a], fns[ent], q))
+        o["color"] = (w & np.uint64(0xFFFFFF)).astype(np.uint32) | np.uint32(0xFF000000)
+        smp[si] = o
+    return smp, c
+
+
+class PackedExport:
+    """An OctreeExport whose samples are 8-byte records (include/simlod_hip.h, "packed samples"): the table and numSamples x uint64 as uint8
+    tensors on the host or on a device, with the box, max_level and select of the export it came from."""
+
+    def __init__(self, table, packed, box_min, box_max, max_level=20, select=abi.EXPORT_ALL):
+        self.table_tensor = _as_bytes_tensor(table)
+        self.packed_tensor = _as_bytes_tensor(packed)
+        if self.table_tensor.numel() % abi.export_node_dtype.itemsize or self.packed_tensor.numel() % 8:
+            raise ValueError("table / packed samples are not whole records")
+        self.box_min = tuple(float(v) for v in np.asarray(box_min, dtype=np.float32).reshape(3))
+        self.box_max = tuple(float(v) for v in np.asarray(box_max, dtype=np.float32).reshape(3))
+        self.max_level = int(max_level)
+        self.select = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
+
+    @property
+    def num_nodes(self):
+        return self.table_tensor.numel() // abi.export_node_dtype.itemsize
+
+    @property
+    def num_samples(self):
+        return self.packed_tensor.numel() // 8
+
+    @property
+    def device(self):
+        return self.table_tensor.device
+
+    @property
+    def nodes(self):
+        return self.table_tensor.cpu().numpy().view(abi.export_node_dtype)
+
+    @property
+    def packed(self):
+        return self.packed_tensor.cpu().numpy().view(np.uint64)
+
+    def to(self, device):
+        return PackedExport(self.table_tensor.to(device), self.packed_tensor.to(device), self.box_min, self.box_max, self.max_level, self.select)
+
+    def unpack(self, return_counts=False):
+        """The OctreeExport these records decode to (rule K8, in numpy), on the host.  DeviceOctree.unpack does the same on the device."""
+        samples, c = unpack_samples(self.nodes, self.packed, self.box_min, self.box_max)
+        ex = OctreeExport(self.nodes, samples, self.box_min, self.box_max, self.max_level, self.select)
+        return (ex, c) if return_counts else ex
+
+    def save(self, path):
+        h = np.zeros(1, dtype=header_dtype)
+        h["magic"], h["version"], h["select"], h["max_level"], h["header_bytes"] = PACKED_MAGIC, PACKED_VERSION, self.select, self.max_level, HEADER_BYTES
+        h["numNodes"], h["numSamples"] = self.num_nodes, self.num_samples
+        h["box_min"], h["box_max"] = self.box_min, self.box_max
+        with open(path, "wb") as f:
+            f.write(h.tobytes())
+            f.write(self.table_tensor.cpu().numpy().tobytes())
+            f.write(self.packed_tensor.cpu().numpy().tobytes())
+
+    @classmethod
+    def load(cls, path):
+        """Read a file written by save(); header, size and table are checked before the packed export is returned (host tensors)."""
+        raw = np.fromfile(path, dtype=np.uint8)
+        if raw.size < HEADER_BYTES:
+            raise ValueError(f"{path}: truncated header")
+        h = raw[:HEADER_BYTES].view(header_dtype)[0]
+        if bytes(h["magic"]).ljust(8, b"\0") != PACKED_MAGIC:
+            raise ValueError(f"{path}: not a packed octree export (magic)")
+        if int(h["version"]) != PACKED_VERSION or int(h["header_bytes"]) != HEADER_BYTES:
+            raise ValueError(f"{path}: unsupported version {int(h['version'])}")
+        if int(h["select"]) > abi.EXPORT_REGION:
+            raise ValueError(f"{path}: unknown selection {int(h['select'])}")
+        n, m = int(h["numNodes"]), int(h["numSamples"])
+        tb, sb = n * abi.export_node_dtype.itemsize, m * 8
+        if raw.size != HEADER_BYTES + tb + sb:
+            raise ValueError(f"{path}: {raw.size} bytes, the header announces {HEADER_BYTES + tb + sb}")
+        _pack_box(h["box_min"], h["box_max"])
+        px = cls(raw[HEADER_BYTES: HEADER_BYTES + tb].copy(), raw[HEADER_BYTES + tb:].copy(), h["box_min"], h["box_max"], int(h["max_level"]), int(h["select"]))
+        validate_table(px.nodes, m)
+        return px
+
+
+class PackedViewDelta:
+    """A ViewDelta whose samples are 8-byte records: table, entries, numDeltaSamples x uint64 and the dropped list as uint8 tensors."""
+
+    def __init__(self, table, entries, packed, dropped, box_min, box_max, max_level=20, counts=None):
+        self.table_tensor, self.entries_tensor = _as_bytes_tensor(table), _as_bytes_tensor(entries)
+        self.packed_tensor, self.dropped_tensor = _as_bytes_tensor(packed), _as_bytes_tensor(dropped)
+        if self.table_tensor.numel() // abi.export_node_dtype.itemsize != self.entries_tensor.numel() // abi.delta_entry_dtype.itemsize:
+            raise ValueError("table and entries differ in length")
+        self.box_min = tuple(float(v) for v in np.asarray(box_min, dtype=np.float32).reshape(3))
+        self.box_max = tuple(float(v) for v in np.asarray(box_max, dtype=np.float32).reshape(3))
+        self.max_level = int(max_level)
+        self.counts = counts
+
+    @property
+    def device(self):
+        return self.table_tensor.device
+
+    @property
+    def num_nodes(self):
+        return self.table_tensor.numel() // abi.export_node_dtype.itemsize
+
+    @property
+    def num_samples(self):
+        return self.packed_tensor.numel() // 8
+
+    @property
+    def nodes(self):
+        return self.table_tensor.cpu().numpy().view(abi.export_node_dtype)
+
+    @property
+    def entries(self):
+        return self.entries_tensor.cpu().numpy().view(abi.delta_entry_dtype)
+
+    @property
+    def packed(self):
+        return self.packed_tensor.cpu().numpy().view(np.uint64)
+
+    @property
+    def dropped(self):
+        return self.dropped_tensor.cpu().numpy().view(np.uint32)
+
+    def to(self, device):
+        return PackedViewDelta(*(x.to(device) for x in (self.table_tensor, self.entries_tensor, self.packed_tensor, self.dropped_tensor)),
+                               self.box_min, self.box_max, self.max_level, self.counts)
+
+    def unpack(self, return_counts=False):
+        """The ViewDelta these records decode to (rule K8, in numpy), on the host."""
+        samples, c = unpack_samples(self.nodes, self.packed, self.box_min, self.box_max, self.entries)
+        vd = ViewDelta(self.nodes, self.entries, samples, self.dropped, self.box_min, self.box_max, self.max_level, self.counts)
+        return (vd, c) if return_counts else vd
 
 
 class Region:

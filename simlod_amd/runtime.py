@@ -106,6 +106,10 @@ def lib():
         L.simlod_view_delta_buffer_min_bytes.argtypes = [u32, u64, u32]
         L.simlod_query_view_delta.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, vp, u64, vp, u32, vp, vp, u64, vp, u32, vp, vp]
         L.simlod_merge_view_delta.argtypes = [vp, u32, vp, vp, vp, u32, vp, vp, u64, vp, u64, vp, vp]
+        L.simlod_pack_buffer_min_bytes.restype = u64
+        L.simlod_pack_buffer_min_bytes.argtypes = [u32, u64]
+        L.simlod_pack_samples.argtypes = [vp, vp, vp, u32, vp, u64, vp, u64, vp, vp, vp]
+        L.simlod_unpack_samples.argtypes = [vp, vp, vp, u32, vp, u64, vp, u64, vp, vp, vp]
         L.simlod_rays_buffer_min_bytes.restype = u64
         L.simlod_rays_buffer_min_bytes.argtypes = [u32, u64, u32, u64, u64]
         L.simlod_query_rays.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, u64, vp, u32, vp, vp, vp]
@@ -133,6 +137,7 @@ EXPORTED_SYMBOLS = [
     "simlod_context_set_clip", "simlod_set_clip", "simlod_query_view",
     "simlod_view_delta_buffer_min_bytes", "simlod_query_view_delta", "simlod_merge_view_delta",
     "simlod_decode_las_styled", "simlod_profile_buffer_min_bytes", "simlod_query_profile",
+    "simlod_pack_buffer_min_bytes", "simlod_pack_samples", "simlod_unpack_samples",
 ]
 
 
@@ -873,6 +878,64 @@ class DeviceOctree:
         if int(c["error"]) != 0:
             raise SimlodError(f"simlod_merge_view_delta reported error bits {int(c['error']):#x} ({int(c['numNodes'])} nodes, {int(c['numSamples'])} samples)")
         return OctreeExport(table, samples[: int(c["numSamples"]) * abi.point_dtype.itemsize], delta.box_min, delta.box_max, delta.max_level, abi.EXPORT_VISIBLE)
+
+    # -- packed samples (include/simlod_hip.h, "packed samples") ---------------------------------------------------------------------------
+    def _pack_call(self, unpack, obj, src, dst, entries):
+        """One simlod_pack_samples / simlod_unpack_samples call on the arrays of `obj` -> the SimlodPackCounts record (host); error bits raise."""
+        name = "simlod_unpack_samples" if unpack else "simlod_pack_samples"
+        if obj.num_nodes == 0:
+            raise SimlodError(f"{name}: an empty table")
+        u = np.zeros(1, dtype=abi.uniforms_dtype)
+        u["boxMin"], u["boxMax"] = obj.box_min, obj.box_max
+        table = obj.table_tensor.to(self.device)
+        n = src.numel() // (8 if unpack else abi.point_dtype.itemsize)
+        scratch = self._export_scratch(int(self.L.simlod_pack_buffer_min_bytes(obj.num_nodes, n)))
+        counts = torch.zeros(abi.pack_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        call = self.L.simlod_unpack_samples if unpack else self.L.simlod_pack_samples
+        _check(call(ctypes.c_void_p(u.ctypes.data), self._p(table), None if entries is None else self._p(entries), obj.num_nodes, self._p(src),
+                    ctypes.c_uint64(n), self._p(scratch), ctypes.c_uint64(scratch.numel()), self._p(dst), self._p(counts), self._stream()), name)
+        c = counts.cpu().numpy().view(abi.pack_counts_dtype)[0]
+        if int(c["error"]) != 0:
+            raise SimlodError(f"{name} reported error bits {int(c['error']):#x} ({int(c['numSamples'])} of {n} samples)")
+        return table, c
+
+    def pack(self, obj, return_counts=False):
+        """`obj` (an octree_io.OctreeExport or ViewDelta, on any device) with 8-byte samples: a PackedExport / PackedViewDelta on this device —
+        one simlod_pack_samples call.  return_counts: also the SimlodPackCounts record (numClamped, numInexact, numAlpha)."""
+        from .octree_io import PackedExport, PackedViewDelta, ViewDelta
+        delta = isinstance(obj, ViewDelta)
+        src = obj.samples_tensor.to(self.device)
+        entries = obj.entries_tensor.to(self.device) if delta else None
+        n = obj.num_samples
+        if n == 0:                                                              # (no array to give the call)
+            packed, c, table = torch.zeros(0, dtype=torch.uint8, device=self.device), np.zeros((), dtype=abi.pack_counts_dtype), obj.table_tensor.to(self.device)
+        else:
+            packed = torch.zeros(n * 8, dtype=torch.uint8, device=self.device)
+            table, c = self._pack_call(False, obj, src, packed, entries)
+        if delta:
+            out = PackedViewDelta(table, entries, packed, obj.dropped_tensor.to(self.device), obj.box_min, obj.box_max, obj.max_level, obj.counts)
+        else:
+            out = PackedExport(table, packed, obj.box_min, obj.box_max, obj.max_level, obj.select)
+        return (out, c) if return_counts else out
+
+    def unpack(self, obj, return_counts=False):
+        """`obj` (an octree_io.PackedExport or PackedViewDelta) with 16-byte samples again: an OctreeExport / ViewDelta on this device — one
+        simlod_unpack_samples call."""
+        from .octree_io import OctreeExport, PackedViewDelta, ViewDelta
+        delta = isinstance(obj, PackedViewDelta)
+        src = obj.packed_tensor.to(self.device)
+        entries = obj.entries_tensor.to(self.device) if delta else None
+        n = obj.num_samples
+        if n == 0:
+            samples, c, table = torch.zeros(0, dtype=torch.uint8, device=self.device), np.zeros((), dtype=abi.pack_counts_dtype), obj.table_tensor.to(self.device)
+        else:
+            samples = torch.zeros(n * abi.point_dtype.itemsize, dtype=torch.uint8, device=self.device)
+            table, c = self._pack_call(True, obj, src, samples, entries)
+        if delta:
+            out = ViewDelta(table, entries, samples, obj.dropped_tensor.to(self.device), obj.box_min, obj.box_max, obj.max_level, obj.counts)
+        else:
+            out = OctreeExport(table, samples, obj.box_min, obj.box_max, obj.max_level, obj.select)
+        return (out, c) if return_counts else out
 
     # -- pair queries: what the ray and the neighbour query share (csrc/export_pairs.inc) ------------------------------------------------------
     # per C call simlod_query_<what>: the record's dtype, its name in messages, its C name, the counts record's dtype.  What _pair_query

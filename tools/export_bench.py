@@ -23,7 +23,10 @@ simlod_export_octree VISIBLE of the same frame into the same buffers, the two al
 query replaces, simlod_launch_render + the VISIBLE export — and the device-to-device copy, all in this one run.
 --view-delta: instead, simlod_query_view_delta of bench.py's bird camera against four held cuts — the same camera's, the bird camera's orbited by
 2 degrees, the close-up camera's, none — each alternating rep by rep with simlod_query_view (full and count-only) of the bird camera; per held
-cut the samples sent, the ratios to the two view calls, the count-only delta and the merge — and the device-to-device copy, all in this one run."""
+cut the samples sent, the ratios to the two view calls, the count-only delta and the merge — and the device-to-device copy, all in this one run.
+--pack: instead, simlod_pack_samples and simlod_unpack_samples of the CUT@20 export and the device-to-device copy of its 16-byte samples, the
+three alternating rep by rep (algorithmic bytes: 24 per sample plus the table) — and, for scale on the host it runs on only, the device-to-host
+copy of 8 against 16 bytes per sample into page-locked memory."""
 import argparse
 import ctypes
 import json
@@ -615,6 +618,54 @@ def profile_bench(dev, u, box, st, reps):
     print(json.dumps(out))
 
 
+def pack_bench(dev, u, box, st, reps):
+    """simlod_pack_samples / simlod_unpack_samples of the CUT@20 export beside the same run's device-to-device copy of its 16-byte samples, in
+    turns; events around the bare C calls.  Algorithmic bytes: 24 per sample (16 + 8) plus the table.  Then, for scale on this host only, the
+    device-to-host copy of 8 against 16 bytes per sample into pinned memory."""
+    from simlod_amd import fingerprint
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    ex = dev.export_octree(u, 20, "cut")
+    ns = ex.num_samples
+    table, samples = ex.table_tensor, ex.samples_tensor
+    need = int(L.simlod_pack_buffer_min_bytes(nn, ns))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    packed = torch.empty(ns * 8, dtype=torch.uint8, device=dev.device)
+    back = torch.empty(ns * 16, dtype=torch.uint8, device=dev.device)
+    copy_dst = torch.empty_like(samples)
+    counts = torch.zeros(abi.pack_counts_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+    uu, up = dev._u(u)
+
+    def pack():
+        rc = L.simlod_pack_samples(up, p(table), None, ex.num_nodes, p(samples), ctypes.c_uint64(ns), p(scratch), ctypes.c_uint64(need), p(packed), p(counts), stream)
+        assert rc == 0
+
+    def unpack():
+        rc = L.simlod_unpack_samples(up, p(table), None, ex.num_nodes, p(packed), ctypes.c_uint64(ns), p(scratch), ctypes.c_uint64(need), p(back), p(counts), stream)
+        assert rc == 0
+
+    pack()
+    c = counts.cpu().numpy().view(abi.pack_counts_dtype)[0].copy()
+    assert int(c["error"]) == 0 and int(c["numSamples"]) == ns and int(c["numInexact"]) == 0 and int(c["numAlpha"]) == 0, c
+    ms_pack, ms_unpack, ms_copy = timed_alternating([pack, unpack, lambda: copy_dst.copy_(samples)], reps)
+    copy_gbs = 2 * ns * 16 / (ms_copy[0] * 1e6)
+    b = ns * 24 + ex.num_nodes * 40
+
+    def row(ms):
+        gbs = b / (ms[0] * 1e6)
+        return {"ms": round(ms[0], 4), "ms_min": round(ms[1], 4), "algorithmic_bytes": b, "GBs": round(gbs, 1), "frac_of_peak": round(gbs / PEAK_GBS, 4),
+                "frac_of_copy": round(gbs / copy_gbs, 4)}
+    out = {"points": int(st["numPoints"]), "numNodes": ex.num_nodes, "numSamples": ns, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(), "scratch_bytes": need,
+           "numClamped": int(c["numClamped"]), "pack": row(ms_pack), "unpack": row(ms_unpack),
+           "d2d_copy": {"ms": round(ms_copy[0], 4), "bytes": 2 * ns * 16, "GBs": round(copy_gbs, 1), "frac_of_peak": round(copy_gbs / PEAK_GBS, 4)},
+           "target": "pack and unpack >= 50 % of the copy rate"}
+    host16 = torch.empty(ns * 16, dtype=torch.uint8).pin_memory()
+    host8 = torch.empty(ns * 8, dtype=torch.uint8).pin_memory()
+    ms16, ms8 = timed_alternating([lambda: host16.copy_(samples, non_blocking=True), lambda: host8.copy_(packed, non_blocking=True)], max(reps // 4, 3))
+    out["d2h_on_this_host"] = {"ms_16B": round(ms16[0], 3), "ms_8B": round(ms8[0], 3), "GBs_16B": round(ns * 16 / (ms16[0] * 1e6), 1), "GBs_8B": round(ns * 8 / (ms8[0] * 1e6), 1)}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=36_000_000)
@@ -629,6 +680,7 @@ def main():
     ap.add_argument("--view", action="store_true", help="time simlod_query_view (bird and close-up cameras beside the VISIBLE export of the same frame, count-only) instead")
     ap.add_argument("--view-delta", action="store_true", help="time simlod_query_view_delta (the bird camera against four held cuts, beside simlod_query_view) instead")
     ap.add_argument("--held", default=None, choices=["same_camera", "orbit_2deg", "other_preset", "nothing"], help="--view-delta: this held cut alone (a per-kernel trace of one case)")
+    ap.add_argument("--pack", action="store_true", help="time simlod_pack_samples / simlod_unpack_samples of the CUT@20 export beside the copy of its samples instead")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
     pts, box = synthetic.terrain(n_points, seed=7)
@@ -661,6 +713,8 @@ def main():
         return view_bench(dev, u, box, st, args.reps)
     if args.view_delta:
         return view_delta_bench(dev, u, box, st, args.reps, args.held)
+    if args.pack:
+        return pack_bench(dev, u, box, st, args.reps)
     L = dev.L
     need = int(L.simlod_export_buffer_min_bytes(nn, ns))
     scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
