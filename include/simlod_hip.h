@@ -636,6 +636,71 @@ int simlod_query_profile(const SimlodNode* nodes, const SimlodStats* stats, cons
                          SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity,
                          SimlodProfileSample* records, SimlodQueryCounts* counts, void* stream);
 
+/* ---- paint regions: recolour the samples inside a region in place, with undo ------------------------------------------------------------------
+ * simlod_paint_region writes a colour into the octree itself, for the samples a footprint query selects: "select, then mark".  What
+ * SIMLOD_CLIP_HIGHLIGHT shows for one region and one frame becomes part of the octree: every later frame, export, query, packed result and
+ * saved file carries it.  It is the one call besides ingest and import that writes the octree, and it writes colour words only.
+ *
+ * Everything the region and the footprint section say stays in force: the box, the classes of a node, rules 3 and F1 per sample, the
+ * chunk-table / `next` sources.
+ *  E0. Target set and order.  The painted samples are exactly the samples, in the order, that simlod_query_footprint(region, footprint,
+ *      maxLevel = 20, SIMLOD_EXPORT_ALL) returns on the same octree (footprint == NULL: simlod_query_region): every level, points and voxels
+ *      alike; a COPIED node is painted whole without a test, a FILTERED node sample by sample.  `table` and `counts` come back as that query's
+ *      count-only call writes them; counts.numSamples is the number painted.  Sample j of that order is "sample j" below.
+ *  E1. SIMLOD_PAINT_SET.  The whole colour word becomes `color`.
+ *  E2. SIMLOD_PAINT_BLEND.  For each of the bytes 0..2: c' = (c*(256 - a) + t*a + 128) >> 8 in integers, c the sample's byte, t that byte of
+ *      `color`, a = strength in 1..255.  Byte 3 is kept.
+ *  E3. SIMLOD_PAINT_RAMP.  t = ((double)z - (double)z0) * (double)scale from the sample's fp32 z, without fused multiply-add; i = 255 if
+ *      t >= 255, (uint32_t)t if t > 0, else 0 (a NaN gives 0); the whole colour word becomes table[i].  `scale` is finite and > 0.
+ *  E4. SIMLOD_PAINT_ARRAY and `previous`.  Sample j gets colors[j].  In every mode, with previous != NULL, the colour word sample j had before
+ *      the call goes to previous[j] (each sample is read before it is written, and by nothing else).  The set and the order depend on positions
+ *      only, and paint never changes a position: `previous` of one call, passed as `colors` to an ARRAY call with the same region and
+ *      footprint, restores the octree byte for byte.  `colors` and `previous` are DEVICE memory of colorCapacity words each and do not overlap.
+ *  E5. All or nothing.  When counts.numSamples > colorCapacity while `colors` or `previous` is given, SIMLOD_EXPORT_ERR_CAPACITY is set in
+ *      counts.error; then, and with any other error bit of the query (a tableCapacity or scratch buffer too small: SIMLOD_EXPORT_ERR_CAPACITY;
+ *      a broken list), no colour and no word of `previous` is written.  colorCapacity is ignored when both arrays are NULL.
+ *  E6. Nothing else changes: positions and sample order, chunk headers, Node records, Stats, the occupancy grids, the allocator header and the
+ *      frame state stay as they are, and the builder's chunk table stays valid (no simlod_octree_image_replaced).  An imported octree,
+ *      render-only or buildable, is painted like a built one.
+ *  E7. Later ingest.  A painted point keeps its colour through leaf splits (a split moves the 16 bytes).  A voxel created later takes its colour
+ *      from its points, as before, painted or not; a painted voxel keeps its colour.  simlod_launch_colorfilter, run afterwards, averages
+ *      whatever colours it finds: no claim is made about its result.
+ *  E8. Not carried.  A receiver's held cut does not learn of a paint: simlod_query_view_delta compares counts, so a painted node that is KEPT is
+ *      not sent again.  The multi-GPU layer has no paint call; each rank may paint its own octree.
+ *  E9. hipErrorInvalidValue with nothing enqueued: everything simlod_query_footprint refuses (with simlod_paint_buffer_min_bytes(tableCapacity, 0)
+ *      as the scratch bound), paint == NULL, a mode above 3, nonzero `reserved` / `reserved2`, BLEND with strength outside 1..255, RAMP with z0 or
+ *      scale not finite or scale <= 0, ARRAY with colors == NULL.  Fields a mode does not use are ignored.
+ * ORDERING.  Asynchronous on `stream` once `region`, `footprint` and `paint` have been read.  The call writes the octree: no frame, query,
+ * export or construct launch on the same `nodes` may overlap it. */
+#define SIMLOD_PAINT_SET    0u         /* colour word := color (what SIMLOD_CLIP_HIGHLIGHT shows, made permanent) */
+#define SIMLOD_PAINT_BLEND  1u         /* bytes 0..2: c' = (c*(256-a) + t*a + 128) >> 8, t = that byte of color, a = strength in 1..255; byte 3 kept */
+#define SIMLOD_PAINT_RAMP   2u         /* colour word := table[i], i from the sample's z (rule E3) */
+#define SIMLOD_PAINT_ARRAY  3u         /* colour word := colors[index of the sample in query order] (undo, or colours computed elsewhere) */
+typedef struct SimlodPaint {           /* host memory, read before the call returns */
+	uint32_t mode;                     /* SIMLOD_PAINT_* */
+	uint32_t color;                    /* SET, BLEND: the colour word (as Point.color) */
+	uint32_t strength;                 /* BLEND: 1..255 */
+	uint32_t reserved;                 /* 0 */
+	float    z0, scale;                /* RAMP: t = (z - z0) * scale */
+	uint32_t reserved2[2];             /* 0 */
+	uint32_t table[256];               /* RAMP: the colour words */
+} SimlodPaint;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodPaint) == 1056, "Paint");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodPaint, color) == 4, "Paint.color");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodPaint, strength) == 8, "Paint.strength");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodPaint, z0) == 16, "Paint.z0");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodPaint, scale) == 20, "Paint.scale");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodPaint, table) == 32, "Paint.table");
+
+/* simlod_footprint_buffer_min_bytes plus a fixed block for the ramp's table (1 KB), with or without a footprint. */
+uint64_t simlod_paint_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+
+/* The paint call (rules above).  `nodes`, `stats`, `uniforms`, `region`, `footprint`, `scratch`, `table` and `counts` as simlod_query_footprint's. */
+int simlod_paint_region(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                        const SimlodFootprint* footprint /*or NULL*/, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes,
+                        SimlodExportNode* table, uint32_t tableCapacity, const uint32_t* colors /*ARRAY only*/, uint32_t* previous /*or NULL*/,
+                        uint64_t colorCapacity, SimlodQueryCounts* counts, void* stream);
+
 /* ---- ray queries: the first sample in a cone along each ray of a batch ----------------------------------------------------------------------
  * simlod_query_rays answers "what does this ray hit" for up to 2^20 rays at once: per ray the sample with the smallest parameter t that lies
  * within radius + spread * t of the ray, among the samples of the nodes simlod_export_octree(maxLevel, select) selects.  The source is only read.

@@ -192,6 +192,14 @@ footprint_dtype = np.dtype({"names": ["numVertices", "reserved", "axisU", "axisV
                             "offsets": [0, 4, 16, 32, 48], "itemsize": 2096})
 assert footprint_dtype.itemsize == 2096
 
+# ---- paint regions (include/simlod_hip.h, "paint regions") -------------------------------------------------------------------------------
+PAINT_SET, PAINT_BLEND, PAINT_RAMP, PAINT_ARRAY = 0, 1, 2, 3
+PAINT_MODES = {"set": PAINT_SET, "blend": PAINT_BLEND, "ramp": PAINT_RAMP, "array": PAINT_ARRAY}
+paint_dtype = np.dtype({"names": ["mode", "color", "strength", "reserved", "z0", "scale", "reserved2", "table"],
+                        "formats": ["<u4", "<u4", "<u4", "<u4", "<f4", "<f4", ("<u4", 2), ("<u4", 256)],
+                        "offsets": [0, 4, 8, 12, 16, 20, 24, 32], "itemsize": 1056})
+assert paint_dtype.itemsize == 1056
+
 # ---- profile queries (include/simlod_hip.h, "profile queries") --------------------------------------------------------------------------
 PROFILE_MAX_VERTICES = 64
 PROFILE_NO_SEGMENT = 0xFFFFFFFF

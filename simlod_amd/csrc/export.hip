@@ -18,6 +18,8 @@
 // Region query (simlod_query_region): k_q_hier -> k_q_dir -> k_q_count -> k_q_scan -> k_q_write, described in export_region.inc.
 // Footprint query (simlod_query_footprint): k_f_hier -> k_q_dir -> k_f_count -> k_q_scan -> k_f_write, the region query's sequence with an extruded
 // polygon on top of the planes, in export_footprint.inc.
+// Paint (simlod_paint_region): that sequence as a count-only call, then k_e_paint / k_ef_paint, which write colour words into the octree's own
+// chunks, in export_paint.inc; the rules in paint_rules.hpp.
 // Profile query (simlod_query_profile): k_pr_hier -> k_q_dir -> k_pr_count -> k_q_scan -> k_pr_write, the same sequence with a corridor along a
 // polyline on top of the planes and a record per returned sample, in export_profile.inc; the rules themselves in profile_rules.hpp.
 // View query (simlod_query_view): k_v_hier -> k_v_scan -> k_x_dir -> k_copy, the export's sequence with the camera's rules in the walk, in
@@ -45,6 +47,7 @@
 #include "delta_rules.hpp"
 #include "profile_rules.hpp"
 #include "pack_rules.hpp"
+#include "paint_rules.hpp"
 
 namespace simlod {
 namespace {
@@ -54,6 +57,7 @@ namespace {
 #include "export_table.inc"    // hier_walk, k_x_hier, k_x_scan, k_x_dir
 #include "export_region.inc"   // QueryGeom, classify, QItem, QueryLayout, QueryArgs, k_q_hier, k_q_dir, k_q_count, k_q_scan, k_q_write
 #include "export_footprint.inc"  // FootEdge, FootGeom, FootArgs, stage_edges, Footprint, classify_footprint, k_f_hier, k_f_count, k_f_write
+#include "export_paint.inc"    // PaintOp, PaintArgs, FootPaintArgs, paint_colour, e_paint, k_e_paint, k_ef_paint
 #include "export_profile.inc"  // ProfGeom, ProfArgs, stage_segments, Profile, k_pr_hier, k_pr_count, locate_record, k_pr_write
 #include "export_view.inc"     // ViewArgs, k_v_hier, k_v_scan
 #include "export_delta.inc"    // DeltaLayout, DeltaArgs, k_d_match, k_d_scan, k_d_dir, k_d_drop, MergeArgs, k_d_merge_scan, k_d_merge_dir
@@ -157,26 +161,37 @@ int launch_query(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats
 
 uint64_t footprint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return query_min_bytes(nodeCapacity, sampleBound) + FOOT_BLOCK_BYTES; }
 
+namespace {
+
+// Rule F7's refusals of the footprint itself (false), else its axes and its edges widened to fp64.
+bool footprint_edges(const SimlodFootprint* fp, FootGeom& f, FootEdge (&edges)[SIMLOD_FOOTPRINT_MAX_VERTICES]) {
+	if (fp == nullptr || fp->numVertices < 3u || fp->numVertices > SIMLOD_FOOTPRINT_MAX_VERTICES) return false;
+	if (fp->reserved[0] != 0u || fp->reserved[1] != 0u || fp->reserved[2] != 0u) return false;
+	const uint32_t n = fp->numVertices;
+	for (int k = 0; k < 4; k++) {
+		if (!std::isfinite(fp->axisU[k]) || !std::isfinite(fp->axisV[k])) return false;
+		f.axU[k] = (double)fp->axisU[k]; f.axV[k] = (double)fp->axisV[k];
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (!std::isfinite(fp->vertices[i][0]) || !std::isfinite(fp->vertices[i][1])) return false;
+		const uint32_t j = i + 1u == n ? 0u : i + 1u;
+		const double au = (double)fp->vertices[i][0], av = (double)fp->vertices[i][1];
+		edges[i] = FootEdge{au, av, (double)fp->vertices[j][0] - au, (double)fp->vertices[j][1] - av};
+	}
+	return true;
+}
+
+}  // namespace
+
 // simlod_query_footprint with a footprint (without one the entry point forwards to launch_query): the polygon, widened to fp64 edges, goes into
 // the scratch buffer's block in front of the items by a copy on `stream`; then the region query's sequence with k_f_hier / k_f_count / k_f_write.
 int launch_footprint(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
                      const SimlodFootprint* fp, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
                      uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
-	if (fp == nullptr || fp->numVertices < 3u || fp->numVertices > SIMLOD_FOOTPRINT_MAX_VERTICES) return (int)hipErrorInvalidValue;
-	if (fp->reserved[0] != 0u || fp->reserved[1] != 0u || fp->reserved[2] != 0u) return (int)hipErrorInvalidValue;
 	FootArgs fa{};
-	const uint32_t n = fp->numVertices;
-	for (int k = 0; k < 4; k++) {
-		if (!std::isfinite(fp->axisU[k]) || !std::isfinite(fp->axisV[k])) return (int)hipErrorInvalidValue;
-		fa.f.axU[k] = (double)fp->axisU[k]; fa.f.axV[k] = (double)fp->axisV[k];
-	}
 	FootEdge edges[SIMLOD_FOOTPRINT_MAX_VERTICES];
-	for (uint32_t i = 0; i < n; i++) {
-		if (!std::isfinite(fp->vertices[i][0]) || !std::isfinite(fp->vertices[i][1])) return (int)hipErrorInvalidValue;
-		const uint32_t j = i + 1u == n ? 0u : i + 1u;
-		const double au = (double)fp->vertices[i][0], av = (double)fp->vertices[i][1];
-		edges[i] = FootEdge{au, av, (double)fp->vertices[j][0] - au, (double)fp->vertices[j][1] - av};
-	}
+	if (!footprint_edges(fp, fa.f, edges)) return (int)hipErrorInvalidValue;
+	const uint32_t n = fp->numVertices;
 	const int rc = prepare_query(ctx, nodes, stats, u, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples, sampleCapacity, counts,
 	                             FOOT_BLOCK_BYTES, fa.q);
 	if (rc != 0) return rc;
@@ -192,6 +207,58 @@ int launch_footprint(Context& ctx, const SimlodNode* nodes, const SimlodStats* s
 	SIMLOD_LAUNCH(k_f_count, dim3(grid), dim3(LANE_TPB), stream, fa);
 	SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, fa.q);
 	if (samples != nullptr) SIMLOD_LAUNCH(k_f_write, dim3(grid), dim3(LANE_TPB), stream, fa);
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+constexpr uint64_t PAINT_BLOCK_BYTES = 256u * sizeof(uint32_t);                     // the ramp's table, in front of the items (behind the polygon's block)
+
+uint64_t paint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return footprint_min_bytes(nodeCapacity, sampleBound) + PAINT_BLOCK_BYTES; }
+
+// simlod_paint_region: the footprint query's launches as a count-only call (maxLevel 20, every node selected), the polygon and the ramp's table
+// in the scratch buffer's blocks in front of the items, then k_e_paint (fp == nullptr) or k_ef_paint.
+int launch_paint(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
+                 const SimlodFootprint* fp, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
+                 const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
+	if (paint == nullptr || !paint_acceptable(*paint, colors != nullptr)) return (int)hipErrorInvalidValue;
+	FootPaintArgs fa{};
+	FootEdge edges[SIMLOD_FOOTPRINT_MAX_VERTICES];
+	if (fp != nullptr && !footprint_edges(fp, fa.f.f, edges)) return (int)hipErrorInvalidValue;
+	constexpr uint64_t front = FOOT_BLOCK_BYTES + PAINT_BLOCK_BYTES;
+	QueryArgs& q = fa.f.q;
+	const int rc = prepare_query(ctx, nodes, stats, u, region, SIMLOD_MAX_DEPTH, SIMLOD_EXPORT_ALL, scratch, scratchBytes, table, tableCapacity, nullptr, 0u,
+	                             counts, front, q);
+	if (rc != 0) return rc;
+	PaintOp& p = fa.p;
+	p.mode = paint->mode; p.color = paint->color; p.strength = paint->strength; p.z0 = paint->z0; p.scale = paint->scale;
+	p.table = q.x.lay.items - PAINT_BLOCK_BYTES;
+	p.colors = paint->mode == SIMLOD_PAINT_ARRAY ? colors : nullptr;
+	p.previous = previous; p.colorCap = colorCapacity; p.checkCap = (colors != nullptr || previous != nullptr) ? 1u : 0u;
+	// (pageable host memory: the runtime has read `paint` and `edges` when the calls return)
+	if (paint->mode == SIMLOD_PAINT_RAMP) {
+		const hipError_t e = hipMemcpyAsync(q.x.scratch + p.table, paint->table, PAINT_BLOCK_BYTES, hipMemcpyHostToDevice, stream);
+		if (e != hipSuccess) return (int)e;
+	}
+	const uint32_t grid = copy_grid(q.x.lay.itemCap);
+	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                        // k_q_dir: one wave per table entry
+	if (fp != nullptr) {
+		fa.f.f.n = fp->numVertices;
+		fa.f.f.edges = q.x.lay.items - front;
+		const hipError_t e = hipMemcpyAsync(q.x.scratch + fa.f.f.edges, edges, (size_t)fa.f.f.n * sizeof(FootEdge), hipMemcpyHostToDevice, stream);
+		if (e != hipSuccess) return (int)e;
+		SIMLOD_LAUNCH(k_f_hier, dim3(1), dim3(WG_TPB), stream, fa.f);
+		if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
+		SIMLOD_LAUNCH(k_f_count, dim3(grid), dim3(LANE_TPB), stream, fa.f);
+		SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);
+		SIMLOD_LAUNCH(k_ef_paint, dim3(grid), dim3(LANE_TPB), stream, fa);
+	} else {
+		PaintArgs pa{q, p};
+		SIMLOD_LAUNCH(k_q_hier, dim3(1), dim3(WG_TPB), stream, q);
+		if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
+		SIMLOD_LAUNCH(k_q_count, dim3(grid), dim3(LANE_TPB), stream, q);
+		SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);
+		SIMLOD_LAUNCH(k_e_paint, dim3(grid), dim3(LANE_TPB), stream, pa);
+	}
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();
 }

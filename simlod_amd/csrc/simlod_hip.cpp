@@ -478,6 +478,17 @@ int simlod_query_footprint(const SimlodNode* nodes, const SimlodStats* stats, co
 	                        samples, sampleCapacity, counts, (hipStream_t)stream);
 }
 
+uint64_t simlod_paint_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return paint_min_bytes(nodeCapacity, sampleBound); }
+
+int simlod_paint_region(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                        const SimlodFootprint* footprint, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
+                        uint32_t tableCapacity, const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts,
+                        void* stream) {
+	if (nodes == nullptr) return (int)hipErrorInvalidValue;
+	return launch_paint(context_of(nodes), nodes, stats, uniforms, region, footprint, paint, scratch, scratchBytes, table, tableCapacity, colors, previous,
+	                    colorCapacity, counts, (hipStream_t)stream);
+}
+
 uint64_t simlod_profile_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return profile_min_bytes(nodeCapacity, sampleBound); }
 
 int simlod_query_profile(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,

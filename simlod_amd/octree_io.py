@@ -24,6 +24,9 @@ simlod_query_region — every rule restated in numpy float64, which reproduces t
 Footprint queries (include/simlod_hip.h, "footprint queries"): `Footprint` holds the polygon and the affine map into its plane,
 `OctreeExport.crop(region, footprint=...)` is the host mirror of simlod_query_footprint, in the same float64 operation order.
 
+Paint regions (include/simlod_hip.h, "paint regions"): `Paint` holds the mode and its parameters, `OctreeExport.paint` is the host mirror of
+simlod_paint_region — the same export with the colours of crop's samples changed, and the colours they had.
+
 Profile queries (include/simlod_hip.h, "profile queries"): `Profile` holds the polyline, the half-width and the three affine maps,
 `OctreeExport.profile` is the host mirror of simlod_query_profile — samples and records — and `classify_profile` of its rule P3.
 
@@ -133,13 +136,14 @@ class OctreeExport:
             return False
         return True
 
-    def crop(self, region, max_level=None, select="all", return_counts=False, footprint=None, profile=None, test_every_sample=False):
+    def crop(self, region, max_level=None, select="all", return_counts=False, footprint=None, profile=None, test_every_sample=False, return_index=False):
         """The host mirror of simlod_query_region: what the device returns for `region` on the octree this FULL export (select "all", max level
         20; anything else ValueError) was taken from, as an OctreeExport on the host — and, return_counts, the SimlodQueryCounts record too.
         footprint (a Footprint): the mirror of simlod_query_footprint — rules F1-F4 on top of the planes; rule F5's promise is asserted for
         every copied and every outside node.
         profile (a Profile): the samples of simlod_query_profile (OctreeExport.profile adds the records) — rules P1 and P3 on top of the planes;
-        rule P4's promise is asserted likewise.  test_every_sample: the same nodes are listed, but none counts as copied."""
+        rule P4's promise is asserted likewise.  test_every_sample: the same nodes are listed, but none counts as copied.
+        return_index: the last element of the result is, per returned sample, its index in this export's samples (int64)."""
         if self.select != abi.EXPORT_ALL or self.max_level < abi.MAX_DEPTH:
             raise ValueError(f"crop needs a full export (select all, max level 20), not select {self.select} / max level {self.max_level}")
         sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
@@ -211,22 +215,47 @@ class OctreeExport:
             seg = slice(a, a + int(cand[t]))
             if inside[i]:
                 assert (ok[seg] | ~inbox[seg]).all(), f"node {i} is copied and holds a sample of the box that fails the test"
-                parts.append(smp[seg])
+                parts.append(np.arange(seg.start, seg.stop, dtype=np.int64))
                 n_copied += 1
             else:
-                parts.append(smp[seg][ok[seg]])
+                parts.append(seg.start + np.nonzero(ok[seg])[0].astype(np.int64))
                 n_filtered += 1
             ns_out[t] = len(parts[-1])
         out["numSamples"] = ns_out
         out["firstSample"] = np.concatenate([[0], np.cumsum(ns_out)[:-1]]).astype(np.uint64)
-        samples = np.concatenate(parts) if parts else np.zeros(0, dtype=abi.point_dtype)
+        index = np.concatenate(parts) if parts else np.zeros(0, np.int64)
+        samples = smp[index]
         ex = OctreeExport(out, samples, self.box_min, self.box_max, ml, abi.EXPORT_REGION)
-        if not return_counts:
-            return ex
         c = np.zeros((), dtype=abi.query_counts_dtype)
         c["numNodes"], c["numSamples"], c["numCandidates"] = len(out), len(samples), int(cand.sum())
         c["numFilteredNodes"], c["numCopiedNodes"] = n_filtered, n_copied
-        return ex, c
+        got = (ex, c) if return_counts else (ex,)
+        if return_index:
+            got += (index,)
+        return got if len(got) > 1 else ex
+
+    # -- paint regions (include/simlod_hip.h, "paint regions") -----------------------------------------------------------------------------
+    def paint(self, region, paint, footprint=None, colors=None, return_previous=False):
+        """The host mirror of simlod_paint_region on the octree this FULL export was taken from: (this export with the colours of the target
+        samples changed — a new OctreeExport on the host; table, positions and order are this one's —, the SimlodQueryCounts record) and,
+        return_previous, the colour words those samples had, in the query's order (uint32).  The target set and its order are crop's (rule
+        E0: max level 20, select "all"), so rule F5's assertion stays in force.  colors: the uint32 words of an ARRAY paint, one per target
+        sample at least."""
+        _, c, index = self.crop(region, abi.MAX_DEPTH, "all", return_counts=True, footprint=footprint, return_index=True)
+        smp = self.samples.copy()
+        previous = smp["color"][index].copy()
+        if paint.mode == abi.PAINT_ARRAY:
+            if colors is None:
+                raise ValueError("an ARRAY paint needs colors")
+            colors = np.asarray(colors, dtype=np.uint32).reshape(-1)
+            if len(colors) < len(index):
+                raise ValueError(f"{len(colors)} colours for {len(index)} samples")
+            new = colors[: len(index)]
+        else:
+            new = paint.apply(previous, smp["z"][index])
+        smp["color"][index] = new
+        ex = OctreeExport(self.nodes.copy(), smp, self.box_min, self.box_max, self.max_level, self.select)
+        return (ex, c, previous) if return_previous else (ex, c)
 
     # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
     def profile(self, profile, region=None, max_level=None, select="all", return_counts=False, test_every_sample=False):
@@ -1076,6 +1105,80 @@ class Clip:
         r["mode"], r["color"] = abi.CLIP_MODES[self.mode], self.color
         r["region"] = self.region.record()
         return r
+
+
+class Paint:
+    """What simlod_paint_region does to the colour word of a sample (include/simlod_hip.h, "paint regions", rules E1-E4): `set` it, `blend` its
+    three colour bytes towards a colour, look it up in a 256-entry `ramp` by height, or take it from an `array` in the query's order."""
+
+    def __init__(self, mode, color=0, strength=0, z0=0.0, scale=0.0, table=None):
+        self.mode = abi.PAINT_MODES[mode] if isinstance(mode, str) else int(mode)
+        if not 0 <= self.mode <= abi.PAINT_ARRAY:
+            raise ValueError(f"paint mode {mode!r}")
+        if not 0 <= int(color) <= 0xFFFFFFFF:
+            raise ValueError("a colour word is a 32-bit unsigned integer")
+        self.color, self.strength = int(color), int(strength)
+        with np.errstate(over="ignore"):
+            self.z0, self.scale = np.float32(z0), np.float32(scale)
+        self.table = np.zeros(256, np.uint32) if table is None else np.asarray(table, dtype=np.uint32).reshape(-1).copy()
+        if len(self.table) != 256:
+            raise ValueError(f"{len(self.table)} table entries: a ramp has 256")
+        if self.mode == abi.PAINT_BLEND and not 1 <= self.strength <= 255:
+            raise ValueError(f"strength {self.strength}: 1 .. 255")
+        if self.mode == abi.PAINT_RAMP and not (np.isfinite(self.z0) and np.isfinite(self.scale) and self.scale > 0):
+            raise ValueError("a ramp needs a finite z0 and a finite scale > 0 (as float32)")
+
+    @classmethod
+    def set(cls, color):
+        """Rule E1: the colour word becomes `color`."""
+        return cls(abi.PAINT_SET, color)
+
+    @classmethod
+    def blend(cls, color, strength):
+        """Rule E2: bytes 0..2 become (c*(256 - strength) + t*strength + 128) >> 8, t that byte of `color`; strength 1 .. 255."""
+        return cls(abi.PAINT_BLEND, color, strength)
+
+    @classmethod
+    def ramp(cls, z0, z1, table):
+        """Rule E3 with scale = float32(256 / (z1 - z0)): the 256 words of `table` spread evenly over z0 <= z < z1, the ends held outside."""
+        z0, z1 = float(z0), float(z1)
+        if not z1 > z0:
+            raise ValueError("a ramp needs z1 > z0")
+        return cls(abi.PAINT_RAMP, z0=z0, scale=256.0 / (z1 - z0), table=table)
+
+    @classmethod
+    def array(cls):
+        """Rule E4: sample j of the query's order gets colors[j] (an undo, or colours computed elsewhere)."""
+        return cls(abi.PAINT_ARRAY)
+
+    def record(self):
+        """The SimlodPaint the C ABI takes (abi.paint_dtype, one record)."""
+        r = np.zeros(1, dtype=abi.paint_dtype)
+        r["mode"], r["color"], r["strength"], r["z0"], r["scale"] = self.mode, self.color, self.strength, self.z0, self.scale
+        r["table"][0] = self.table
+        return r
+
+    def ramp_index(self, z):
+        """Rule E3's table index of float32 heights, in numpy float64."""
+        with np.errstate(invalid="ignore", over="ignore"):
+            t = (np.asarray(z, np.float32).astype(np.float64) - np.float64(self.z0)) * np.float64(self.scale)
+            return np.where(t >= 255.0, 255, np.where(t > 0.0, np.minimum(np.nan_to_num(t, nan=0.0), 255.0), 0.0)).astype(np.int64)
+
+    def apply(self, color, z):
+        """The new colour words of samples with the words `color` (uint32) and the heights `z` (float32): rules E1-E3, vectorised."""
+        c = np.asarray(color, dtype=np.uint32)
+        if self.mode == abi.PAINT_SET:
+            return np.full(c.shape, self.color, np.uint32)
+        if self.mode == abi.PAINT_BLEND:
+            out = c & np.uint32(0xFF000000)
+            a = np.uint32(self.strength)
+            for sh in (0, 8, 16):
+                old, t = (c >> np.uint32(sh)) & np.uint32(0xFF), np.uint32((self.color >> sh) & 0xFF)
+                out = out | ((((old * (np.uint32(256) - a) + t * a + np.uint32(128)) >> np.uint32(8))) << np.uint32(sh))
+            return out.astype(np.uint32)
+        if self.mode == abi.PAINT_RAMP:
+            return self.table[self.ramp_index(z)]
+        raise ValueError("an ARRAY paint takes its colours from the caller")
 
 
 class Footprint:

@@ -98,6 +98,9 @@ def lib():
         L.simlod_footprint_buffer_min_bytes.restype = u64
         L.simlod_footprint_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_query_footprint.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
+        L.simlod_paint_buffer_min_bytes.restype = u64
+        L.simlod_paint_buffer_min_bytes.argtypes = [u32, u64]
+        L.simlod_paint_region.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, u32, vp, vp, u64, vp, vp]
         L.simlod_profile_buffer_min_bytes.restype = u64
         L.simlod_profile_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_query_profile.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp, vp]
@@ -138,6 +141,7 @@ EXPORTED_SYMBOLS = [
     "simlod_view_delta_buffer_min_bytes", "simlod_query_view_delta", "simlod_merge_view_delta",
     "simlod_decode_las_styled", "simlod_profile_buffer_min_bytes", "simlod_query_profile",
     "simlod_pack_buffer_min_bytes", "simlod_pack_samples", "simlod_unpack_samples",
+    "simlod_paint_buffer_min_bytes", "simlod_paint_region",
 ]
 
 
@@ -710,6 +714,43 @@ class DeviceOctree:
         u = np.asarray(uniforms).reshape(-1)[0]
         ex = OctreeExport(table, samples[: int(c["numSamples"]) * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_REGION)
         return (ex, c) if return_counts else ex
+
+    # -- paint regions (include/simlod_hip.h, "paint regions") -----------------------------------------------------------------------------
+    def paint_region(self, uniforms, region, paint, footprint=None, colors=None, return_previous=False):
+        """Recolour, in the octree itself, the samples simlod_query_footprint(region, footprint, 20, "all") returns — `paint` (an
+        octree_io.Paint) says how: set, blend, ramp by height, or array (then `colors`: one uint32 word per sample in the query's order, a
+        tensor on this device or anything numpy takes) — by one simlod_paint_region call.  -> the SimlodQueryCounts record (numSamples: the
+        number painted), and with return_previous (that record, the colour words the samples had: a uint32 tensor on this device, which an
+        array paint of the same region and footprint puts back).  Raises SimlodError when the device reports an error; then nothing was
+        painted.  No frame, query or ingest of this octree may be in flight on another stream."""
+        from .octree_io import Region
+        u, up = self._u(uniforms)
+        st = self.read_stats()
+        nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+        r, pr = (Region() if region is None else region).record(), paint.record()
+        f = None if footprint is None else footprint.record()
+        col = None
+        if paint.mode == abi.PAINT_ARRAY:
+            if colors is None:
+                raise ValueError("an ARRAY paint needs colors")
+            col = colors if isinstance(colors, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(colors, dtype=np.uint32)).view(np.int32))
+            col = col.reshape(-1).contiguous().to(self.device)
+            if col.element_size() != 4:
+                raise ValueError("colors are 32-bit words")
+        prev = torch.empty(max(bound, 1), dtype=torch.int32, device=self.device) if return_previous else None
+        cap = min(t.numel() for t in (col, prev) if t is not None) if (col is not None or prev is not None) else 0
+        table = self._table(nn)
+        counts = torch.zeros(abi.query_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        scratch = self._export_scratch(int(self.L.simlod_paint_buffer_min_bytes(nn, bound)))
+        opt = lambda t: None if t is None else self._p(t)
+        _check(self.L.simlod_paint_region(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data),
+                                          None if f is None else ctypes.c_void_p(f.ctypes.data), ctypes.c_void_p(pr.ctypes.data), self._p(scratch),
+                                          ctypes.c_uint64(scratch.numel()), self._p(table), nn, opt(col), opt(prev), ctypes.c_uint64(cap), self._p(counts),
+                                          self._stream()), "simlod_paint_region")
+        c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
+        if int(c["error"]) != 0:
+            raise SimlodError(f"simlod_paint_region reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples); nothing was painted")
+        return (c, prev[: int(c["numSamples"])]) if return_previous else c
 
     # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
     def _profile(self, uniforms, profile, region, ml, sel, table, samples, records, sample_capacity, bound):

@@ -26,7 +26,11 @@ query replaces, simlod_launch_render + the VISIBLE export — and the device-to-
 cut the samples sent, the ratios to the two view calls, the count-only delta and the merge — and the device-to-device copy, all in this one run.
 --pack: instead, simlod_pack_samples and simlod_unpack_samples of the CUT@20 export and the device-to-device copy of its 16-byte samples, the
 three alternating rep by rep (algorithmic bytes: 24 per sample plus the table) — and, for scale on the host it runs on only, the device-to-host
-copy of 8 against 16 bytes per sample into page-locked memory."""
+copy of 8 against 16 bytes per sample into page-locked memory.
+--paint: instead, simlod_paint_region on the same octree — the whole box, half the terrain and the city block of --region, each as SET without
+arrays, BLEND and SET with `previous`; every paint alternates rep by rep with simlod_query_region ALL@20 of the same region (with samples) and
+the device-to-device copy (paint, copy, query, copy: both calls start behind the copy); the ratio to the query (expected <= 1.10) and the share
+of the copy rate by algorithmic bytes.  --paint-only REGION:MODE: that case alone."""
 import argparse
 import ctypes
 import json
@@ -148,6 +152,76 @@ def region_bench(dev, u, box, st, reps):
     t_block, t_block_count = timed_alternating([lambda: query("city_block"), lambda: query("city_block", True)], reps)
     out["city_block"] = row("city_block", t_block)
     out["city_block"]["count_only_ms"] = round(t_block_count[0], 4)
+    print(json.dumps(out))
+
+
+def paint_bench(dev, u, box, st, reps, only=None):
+    from simlod_amd import fingerprint
+    from simlod_amd.octree_io import Paint, Region, classify_nodes
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    need = int(L.simlod_paint_buffer_min_bytes(nn, bound))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    table = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    samples = torch.empty(bound * 16, dtype=torch.uint8, device=dev.device)
+    previous = torch.empty(bound, dtype=torch.int32, device=dev.device)
+    counts = torch.zeros(32, dtype=torch.uint8, device=dev.device)
+    uu, up = dev._u(u)
+    b = np.asarray(box, dtype=np.float64)
+    n = np.array([0.6, 0.8, 0.1])
+    regions = {"whole_box": Region(), "half_terrain": Region.from_planes([[*n, -float(n @ (b / 2))]]),
+               "city_block": Region.from_box((0.45 * b[0], 0.45 * b[1], -1.0), (0.55 * b[0], 0.55 * b[1], b[2] + 1.0))}
+    records = {k: r.record() for k, r in regions.items()}
+    paints = {"set": (Paint.set(0xFF2060E0).record(), False), "blend": (Paint.blend(0x002060E0, 64).record(), False),
+              "set_previous": (Paint.set(0xFF2060E0).record(), True)}
+
+    def paint(kind, mode):
+        rec, prev = paints[mode]
+        rc = L.simlod_paint_region(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(records[kind].ctypes.data), None, ctypes.c_void_p(rec.ctypes.data), p(scratch),
+                                   ctypes.c_uint64(need), p(table), nn, None, p(previous) if prev else None, ctypes.c_uint64(bound), p(counts), stream)
+        assert rc == 0
+
+    def query(kind, count_only=False):
+        rc = L.simlod_query_region(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(records[kind].ctypes.data), 20, abi.EXPORT_ALL, p(scratch),
+                                   ctypes.c_uint64(need), p(table), nn, None if count_only else p(samples), ctypes.c_uint64(bound), p(counts), stream)
+        assert rc == 0
+
+    copy_dst = torch.empty(int(st["numPoints"]) * 16, dtype=torch.uint8, device=dev.device)
+    copy_src = samples[: copy_dst.numel()]
+    out = {"points": int(st["numPoints"]), "numNodes": nn, "numSamples": bound, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(),
+           "lib": os.environ.get("SIMLOD_HIP_LIB", "product"), "bound": "t_paint <= 1.10 * t_query of the same run"}
+    for kind in regions:
+        # the candidates in filtered nodes: the classes on the host from a zero-plane count-only call's table (the counts before the test)
+        query("whole_box", count_only=True)
+        torch.cuda.synchronize()
+        full = table.cpu().numpy().view(abi.export_node_dtype)
+        outside, inside = classify_nodes(regions[kind].planes, full, u["boxMin"], u["boxMax"])
+        cand_filtered = int(full["numSamples"][~outside & ~inside].astype(np.int64).sum())
+        out[kind] = {}
+        for mode in paints:
+            if only is not None and only != f"{kind}:{mode}":
+                continue
+            # paint, copy, query, copy: both calls run behind the 1.1 GB copy, which leaves neither the nodes nor the region's chunks in the
+            # caches (behind the paint of the same region the query would find them there)
+            copy = lambda: copy_dst.copy_(copy_src)
+            t_paint, t_copy, t_query, _ = timed_alternating([lambda: paint(kind, mode), copy, lambda: query(kind), copy], reps)
+            paint(kind, mode)
+            torch.cuda.synchronize()
+            c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
+            assert int(c["error"]) == 0
+            painted, cand = int(c["numSamples"]), int(c["numCandidates"])
+            copy_gbs = 2 * copy_dst.numel() / (t_copy[0] * 1e6)
+            # what the call has to move: the filtered candidates are read for the count, every sample that is read for its colour 16 bytes
+            # (SET without previous reads no copied chunk), 4 bytes written per painted sample and 4 more for `previous`, the table
+            read = cand_filtered if mode == "set" else cand
+            nbytes = read * 16 + painted * (8 if mode == "set_previous" else 4) + int(c["numNodes"]) * 40
+            qbytes = cand * 16 + painted * 16 + int(c["numNodes"]) * 40
+            gbs = nbytes / (t_paint[0] * 1e6)
+            out[kind][mode] = {"ms": round(t_paint[0], 4), "ms_min": round(t_paint[1], 4), "query_all20_ms": round(t_query[0], 4), "d2d_copy_ms": round(t_copy[0], 4),
+                               "d2d_copy_GBs": round(copy_gbs, 1), "over_query": round(t_paint[0] / t_query[0], 4), "bound_held": bool(t_paint[0] <= 1.10 * t_query[0]),
+                               "numSamples": painted, "numCandidates": cand, "candidates_in_filtered_nodes": cand_filtered, "nodes_copied": int(c["numCopiedNodes"]),
+                               "nodes_filtered": int(c["numFilteredNodes"]), "algorithmic_bytes": nbytes, "GBs": round(gbs, 1), "frac_of_copy": round(gbs / copy_gbs, 4),
+                               "query_algorithmic_bytes": qbytes, "query_frac_of_copy": round(qbytes / (t_query[0] * 1e6) / copy_gbs, 4)}
     print(json.dumps(out))
 
 
@@ -681,6 +755,8 @@ def main():
     ap.add_argument("--view-delta", action="store_true", help="time simlod_query_view_delta (the bird camera against four held cuts, beside simlod_query_view) instead")
     ap.add_argument("--held", default=None, choices=["same_camera", "orbit_2deg", "other_preset", "nothing"], help="--view-delta: this held cut alone (a per-kernel trace of one case)")
     ap.add_argument("--pack", action="store_true", help="time simlod_pack_samples / simlod_unpack_samples of the CUT@20 export beside the copy of its samples instead")
+    ap.add_argument("--paint", action="store_true", help="time simlod_paint_region (whole box, half the terrain, a city block; SET, BLEND, SET with previous) beside the ALL@20 region query instead")
+    ap.add_argument("--paint-only", default=None, metavar="REGION:MODE", help="--paint: this case alone, e.g. city_block:set (a per-kernel trace of one case)")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
     pts, box = synthetic.terrain(n_points, seed=7)
@@ -715,6 +791,8 @@ def main():
         return view_delta_bench(dev, u, box, st, args.reps, args.held)
     if args.pack:
         return pack_bench(dev, u, box, st, args.reps)
+    if args.paint:
+        return paint_bench(dev, u, box, st, args.reps, args.paint_only)
     L = dev.L
     need = int(L.simlod_export_buffer_min_bytes(nn, ns))
     scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
