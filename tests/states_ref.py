@@ -10,12 +10,15 @@ import cases
 import footprint_ref as fr
 import neighbours_ref as nr
 import oracle
+import pack_ref as kr
+import paint_ref as pf
+import profile_ref as pr
 import rays_ref as yr
 import region_ref as rr
 import view_ref as vr
 from export_ref import export_host
 from simlod_amd import abi, synthetic
-from simlod_amd.octree_io import Footprint, OctreeExport, Rays, Spheres
+from simlod_amd.octree_io import Footprint, OctreeExport, Paint, Profile, Rays, Region, Spheres
 
 State = namedtuple("State", "dev u pts box")            # the device object, its uniforms, the points the octree holds NOW, the box
 ROW = 50                                                 # chunk addresses a row of the builder's chunk table holds (LEAF_ROW_SLOTS)
@@ -218,7 +221,7 @@ def assert_masked_rank(table, pts, mine, box, mask):
 
 
 # ---- the battery's queries and their guards ----------------------------------------------------------------------------------------------------
-Queries = namedtuple("Queries", "region footprint rays spheres radius")
+Queries = namedtuple("Queries", "region footprint rays spheres radius profile")
 
 
 def queries(pts, box):
@@ -229,7 +232,13 @@ def queries(pts, box):
     edges passes the middle at 0.49, outside the quarter's corners at 0.3536, so rule F3 finds every edge far from the nodes over that
     quarter and they are copied whole, while the nodes its points cross are filtered; 64 rays, each through a chosen point from 0.3 extents
     away in a random direction, and 64 spheres at the same points, with the radius at which a sphere around a chosen point holds 32 points in
-    the median (twice k = 16: the top-k drops something; a ray's cylinder of half that radius holds its own point and, in the median, more)."""
+    the median (twice k = 16: the top-k drops something; a ray's cylinder of half that radius holds its own point and, in the median, more);
+    a corridor of half-width 0.27 cubes along three vertices: from 0.1 cubes left of the box at a quarter of its y extent to the bend at 0.6
+    of its x extent, and up to 0.9 of its y extent.  On a filled square that is (-0.1, 0.25), (0.6, 0.25), (0.6, 0.9): segment 0's rectangle holds
+    the whole plan square of the lower-left quarter (x -0.1 .. 0.6, y -0.02 .. 0.52), so rule P3 copies the nodes over it as the star does, its rim
+    and segment 1 filter their neighbours, and the two rectangles overlap over x 0.33 .. 0.6, y 0.25 .. 0.52, where the lower segment owns the
+    samples.  The bend and the end go by the extent of EACH axis, so that on a strip of points (the first batches of a terrain, whose cube is the
+    long side) both segments and their overlap still hold points; only the half-width is the cube's."""
     lo = np.array([float(pts[a].min()) for a in "xyz"])
     ext = np.array([float(pts[a].max()) for a in "xyz"]) - lo
     size = float(ext[:2].max())
@@ -243,7 +252,9 @@ def queries(pts, box):
     d = rs.randn(N_QUERIES, 3)
     d *= 0.3 * nr.extent(pts) / np.linalg.norm(d, axis=1)[:, None]
     rays = Rays(c - d, d, 0.0, 2.0, 0.5 * radius, 0.0)
-    return Queries(rr.region("oblique", ext, lo), star, rays, Spheres(c, radius), radius)
+    bend = (lo[0] + 0.6 * ext[0], lo[1] + 0.25 * ext[1])
+    corridor = Profile.from_xy([(lo[0] - 0.1 * size, bend[1]), bend, (bend[0], lo[1] + 0.9 * ext[1])], 0.27 * size)
+    return Queries(rr.region("oblique", ext, lo), star, rays, Spheres(c, radius), radius, corridor)
 
 
 def assert_crop_not_vacuous(cnt, what, copies=True):
@@ -295,18 +306,20 @@ def assert_delta_not_vacuous(delta, what, adds=True):
 # ---- the mirrors of one battery, guarded and held against brute force ------------------------------------------------------------------------
 # What the guards can ask of an octree, stated per state (a flag that is False asserts the OPPOSITE, so each is a fact about the octree and not
 # a check left out): `camera` of the view; whether the region / the footprint copies a node whole; whether the bias-0 cut adds nodes to the
-# bias-2 cut; whether the view's ladder has a coarser rung with samples (without one a budget of S(0) - 1 chooses the first EMPTY cut).
-Shape = namedtuple("Shape", "camera region_copies footprint_copies delta_adds coarser", defaults=("closer", True, True, True, True))
+# bias-2 cut; whether the view's ladder has a coarser rung with samples (without one a budget of S(0) - 1 chooses the first EMPTY cut); whether
+# the profile copies a node whole.
+Shape = namedtuple("Shape", "camera region_copies footprint_copies delta_adds coarser profile_copies", defaults=("closer", True, True, True, True, True))
 NINE_NODES = Shape("inside", region_copies=False, delta_adds=False)     # a root and eight leaves: the plane through the middle cuts all eight
-ROOT_LEAF = Shape("closer", False, False, False, False)                 # one node: filtered by everything, the only cut there is
+ROOT_LEAF = Shape("closer", False, False, False, False, False)          # one node: filtered by everything, the only cut there is
+PAINT_SEED = 91                                                         # of the colours of the battery's ARRAY paint
 
 
 def mirrors(full, pts, uv, what, shape=Shape(), pairs_all=False):
     """What the battery expects of an octree whose anchored full export is `full` and which holds `pts`, from the numpy mirrors alone: every
     answer guarded (above), the cuts equal to the brute-force filters of `pts`, the rays' t and the spheres' d2 bit-equal to the brute force
-    over `pts`, the delta consistent in itself.  `uv`: the view's uniforms at bias 0.  pairs_all: rays and spheres with select "all" too."""
+    over `pts`, the delta consistent in itself; the profile, the two paint calls and the packed export as profile_mirrors, paint_mirrors and
+    pack_mirror (below) hold them.  `uv`: the view's uniforms at bias 0.  pairs_all: rays and spheres with select "all" too."""
     import delta_ref
-    from simlod_amd.octree_io import Region
     mn, size = np.asarray(full.box_min, np.float64), np.asarray(full.box_max, np.float64) - np.asarray(full.box_min, np.float64)
     assert not mn.any()
     q = queries(pts, tuple(size))
@@ -342,7 +355,79 @@ def mirrors(full, pts, uv, what, shape=Shape(), pairs_all=False):
     m["delta"] = full.view_delta(uv, m["held"], tails=True)
     assert_delta_not_vacuous(m["delta"], f"{what} delta", shape.delta_adds)
     delta_ref.assert_delta_consistent(m["delta"], m["held"], m["view"][0])
+    m["profile"] = profile_mirrors(full, q.profile, pts, what, shape.profile_copies)
+    m["paint"] = paint_mirrors(full, q, tuple(size), m["crop"], what)
+    m["pack"] = pack_mirror(full, what)
     return m
+
+
+def words(a):
+    """16-byte records as rows of four uint32 words"""
+    return np.ascontiguousarray(a).view(np.uint32).reshape(-1, 4)
+
+
+def sorted_rows(a):
+    """The rows of a 2-D array in one fixed order (that of their bytes): equal results <=> equal multisets of rows"""
+    a = np.ascontiguousarray(a)
+    return np.sort(a.view(np.dtype((np.void, a.shape[1] * a.itemsize))).ravel())
+
+
+def profile_mirrors(full, profile, pts, what, copies=True):
+    """OctreeExport.profile at level 20 for "cut" and "all" -> {sel: (export, records, counts)}.  The cut is guarded as the crops are and held
+    against rule P1 decided exactly over `pts`: its samples are the points in some segment, its (sample, record) pairs those of Profile.records on
+    them, as multisets.  Conditions on the corridor, not measurements: it has samples in segment 0 and in segment 1, and the bend's overlap holds a
+    point that lies in both rectangles and is recorded under the lower segment."""
+    m = {sel: full.profile(profile, None, 20, sel, return_counts=True) for sel in ("cut", "all")}
+    ex, rec, cnt = m["cut"]
+    assert_crop_not_vacuous(cnt, f"{what} profile", copies)
+    seg = pr.locate_exact(profile, pts)
+    inside = pts[seg >= 0]
+    rr.assert_same_multiset(ex.samples, inside, f"{what} profile")
+    records = profile.records(inside)
+    got = np.concatenate([words(ex.samples), words(rec)], axis=1)
+    ref = np.concatenate([words(inside), words(records)], axis=1)
+    assert np.array_equal(sorted_rows(got), sorted_rows(ref)), f"{what} profile: (sample, record) pairs differ from Profile.records on the points held"
+    assert np.array_equal(records["segment"].astype(np.int64), seg[seg >= 0]), f"{what} profile: a record's segment is not the exact rule's"
+    assert len(profile) == 3
+    second = pr.locate_exact(Profile(profile.vertices[1:], profile.half_width, profile.axis_u, profile.axis_v, profile.axis_h), pts) >= 0
+    assert (seg == 0).any() and (seg == 1).any() and ((seg == 0) & second).any(), \
+        f"{what} profile: {int((seg == 0).sum())} / {int((seg == 1).sum())} points in segments 0 / 1, {int(((seg == 0) & second).sum())} in the overlap under segment 0"
+    return m
+
+
+PaintCall = namedtuple("PaintCall", "region footprint paint colors export counts previous")
+
+
+def paint_mirrors(full, q, size, crops, what):
+    """The battery's two paint calls on the host, the second on top of the first -> [PaintCall, PaintCall]: BLEND on (q.region, no footprint),
+    then ARRAY with seeded random colours on (no planes, q.footprint); each with the export after it, its counts and `previous`.  Rule E0: a
+    call's counts are the "all" crop's of the same region and footprint, so the crops' guards cover the paint.  The two `previous` arrays painted
+    back in reverse order give `full` back."""
+    blend = pf.paints(size)["blend"]
+    e1, c1, p1 = full.paint(q.region, blend, return_previous=True)
+    n2 = int(crops["footprint", "all"][1]["numSamples"])
+    colors = np.random.RandomState(PAINT_SEED).randint(0, 1 << 32, n2, dtype=np.uint64).astype(np.uint32)
+    e2, c2, p2 = e1.paint(Region(), Paint.array(), footprint=q.footprint, colors=colors, return_previous=True)
+    for kind, c, prev in (("region", c1, p1), ("footprint", c2, p2)):
+        assert c.tobytes() == crops[kind, "all"][1].tobytes() and len(prev) == int(c["numSamples"]) > 0, f"{what} paint {kind}: not the crop's counts"
+    assert (e1.samples["color"] != full.samples["color"]).any() and (e2.samples["color"] != e1.samples["color"]).any(), f"{what} paint: a call changes nothing"
+    back = e2.paint(Region(), Paint.array(), footprint=q.footprint, colors=p2)[0].paint(q.region, Paint.array(), colors=p1)[0]
+    assert back.samples.tobytes() == full.samples.tobytes() and back.nodes.tobytes() == full.nodes.tobytes(), f"{what} paint: the undo is not the octree before"
+    return [PaintCall(q.region, None, blend, None, e1, c1, p1), PaintCall(Region(), q.footprint, Paint.array(), colors, e2, c2, p2)]
+
+
+def pack_mirror(full, what):
+    """OctreeExport.pack of the full export and its unpack -> (PackedExport, pack counts, unpacked export, unpack counts): every voxel is a cell
+    centre and no colour has alpha bits (rule K3), voxels come back bit for bit, leaf points within rule K8's bound."""
+    px, pc = full.pack(return_counts=True)
+    back, uc = px.unpack(return_counts=True)
+    t, before, after = full.nodes, full.samples, back.samples
+    assert int(pc["error"]) == 0 and int(pc["numInexact"]) == 0 and int(pc["numAlpha"]) == 0 and int(pc["numSamples"]) == len(before) > 0, f"{what} pack: {pc}"
+    kr.assert_points_within_bound(t, before, after, full.box_min, full.box_max, what=f"{what} pack")
+    vox = kr.voxel_mask(t, len(before))
+    assert after[vox].tobytes() == before[vox].tobytes(), f"{what} pack: a voxel moved"
+    assert (after["color"] == before["color"]).all(), f"{what} pack: a colour changed"
+    return px, pc, back, uc
 
 
 def assert_hits_are_brute(hits, rays, pts, what):
@@ -372,8 +457,9 @@ def held_table(view, counts):
 
 # ---- the states' shapes, and their oracle twins ----------------------------------------------------------------------------------------------------
 # (what the GPU tier passes to the battery; tests/test_builder_states_io.py holds every one of them against the oracle's octree of the same input)
-SHAPES = {"A": NINE_NODES, "C": Shape(), "D hotspot_150k": Shape(region_copies=False), "D dense_cube": Shape(), "E": Shape(), "E1": Shape(delta_adds=False), "F": Shape(), "H": Shape(),
-          "G 600000 poisoned": Shape(), "G 600000 continued": Shape(), "G 90000 poisoned": ROOT_LEAF, "G 90000 continued": Shape("inside", delta_adds=False, coarser=False),
+SHAPES = {"A": NINE_NODES, "C": Shape(), "D hotspot_150k": Shape(region_copies=False), "D dense_cube": Shape(), "E": Shape(), "E1": Shape(delta_adds=False, profile_copies=False), "F": Shape(), "H": Shape(),
+          "G 600000 poisoned": Shape(), "G 600000 continued": Shape(), "G 90000 poisoned": ROOT_LEAF,
+          "G 90000 continued": Shape("inside", delta_adds=False, coarser=False, profile_copies=False),
           "I A": Shape("bird"), "I B": Shape("inside", delta_adds=False)}
 G_CASES = [(600_000, 300_000, 100_000), (90_000, 30_000, 15_000)]
 

@@ -8,14 +8,18 @@ import pytest
 import cases
 import delta_ref
 import neighbours_ref as nr
+import pack_ref as kr
+import paint_ref as pf
+import profile_ref as pr
 import rays_ref as yr
 import region_ref as rr
 import states_ref as sr
 from simlod_amd import abi
-from simlod_amd.octree_io import delta_between
+from simlod_amd.octree_io import Region, classify_footprint, classify_nodes, classify_profile, delta_between
 from test_gpu_trunk import _partition
 
-_TWINS = {}
+_TWINS, _MIRRORS = {}, {}
+SMALL_TWINS = ["G 90000 poisoned", "G 90000 continued", "I B"]          # under 300 000 samples: small enough for one Python loop per sample
 
 
 def _twin(name):
@@ -24,10 +28,23 @@ def _twin(name):
     return _TWINS[name]
 
 
+def _mirrors(name):
+    """The battery's mirrors on a twin (state A with the pair queries' "all" too, as its GPU battery asks); kept for the twins that further
+    tests look into."""
+    if name in _MIRRORS:
+        return _MIRRORS[name]
+    ex, pts, box, shape, _ = _twin(name)
+    m = sr.mirrors(ex, pts, sr.view_uniforms(box, shape.camera), name, shape, pairs_all=name == "A")
+    if name == "A" or name in SMALL_TWINS:
+        _MIRRORS[name] = m
+    return m
+
+
 @pytest.fixture(scope="module", autouse=True)
 def _release(built_libs):
     yield
     _TWINS.clear()
+    _MIRRORS.clear()
 
 
 # ---- collapse ----------------------------------------------------------------------------------------------------------------------------------
@@ -51,7 +68,7 @@ def test_collapse_is_an_octree_of_overfull_leaves_that_holds_the_input(built_lib
 
 def test_mirrors_on_the_collapsed_octree_agree_with_brute_force_and_each_other(built_libs):
     c, pts, box, shape, _ = _twin("A")
-    m = sr.mirrors(c, pts, sr.view_uniforms(box, shape.camera), "A (collapsed)", shape, pairs_all=True)
+    m = _mirrors("A")
     q = m["q"]
     for sel in ("cut", "all"):
         table = c.truncated(20, sel)
@@ -91,6 +108,110 @@ def test_held_counts_around_the_row_end_send_exactly_the_tails(built_libs):
     assert delta_ref.states(w) == (4, 0, 4, 4) and w.num_samples == int(fresh.nodes["numSamples"][idx].astype(np.int64).sum())
 
 
+def _result_classes(full, result, region, footprint=None, profile=None):
+    """Per entry of a crop's table, by the node rules alone (region rule 2, footprint rules F3 / F4, profile rule P3):
+    -> (its entry in `full`, whether the node is copied whole, whether it is filtered sample by sample)"""
+    key = lambda a: list(zip(a["level"].tolist(), a["X"].tolist(), a["Y"].tolist(), a["Z"].tolist()))
+    at = {k: i for i, k in enumerate(key(full.nodes))}
+    src = np.array([at[k] for k in key(result.nodes)])
+    out, ins = classify_nodes(np.asarray(region.planes, dtype=np.float32).astype(np.float64), full.nodes, full.box_min, full.box_max)
+    if footprint is not None:
+        near, corner = classify_footprint(footprint, full.nodes, full.box_min, full.box_max)
+        out, ins = out | (~near & ~corner), ins & ~near & corner
+    if profile is not None:
+        far, covered = classify_profile(profile, full.nodes, full.box_min, full.box_max)
+        out, ins = out | far, ins & covered
+    return src, ins[src], ~out[src] & ~ins[src]
+
+
+def test_profile_and_paint_on_the_collapsed_octree_reach_behind_the_row(built_libs):
+    """What makes state A worth running for the profile and the paint: items with k >= 50 and offsets of 50 000 and more.  The corridor's cut
+    copies leaves of 75 chunks whole (k_pr_write stores chunk k at firstSample + 1000 k) and filters others, and in a filtered leaf samples
+    pass whose ordinal in the leaf is 50 000 or more (they lie in chunks the `next` chain reaches, not the row); both paint calls write
+    previous[firstSample + offset] with a per-node offset of 50 000 or more — in a copied node (the star's two leaves: offset 1000 k + rank) and
+    in a filtered one (offset it.off + rank, the samples that passed before the item)."""
+    c, pts, box, shape, _ = _twin("A")
+    m = _mirrors("A")
+    q = m["q"]
+    ex, rec, cnt = m["profile"]["cut"]
+    again, index = c.crop(Region(), 20, "cut", profile=q.profile, return_index=True)
+    assert again.samples.tobytes() == ex.samples.tobytes() and again.nodes.tobytes() == ex.nodes.tobytes()
+    src, copied, filtered = _result_classes(c, ex, Region(), profile=q.profile)
+    leaf = (ex.nodes["flags"] & abi.EXPORT_FLAG_LEAF) != 0
+    n, first = ex.nodes["numSamples"].astype(np.int64), ex.nodes["firstSample"].astype(np.int64)
+    assert (int((copied & leaf).sum()), int((filtered & leaf).sum())) == (int(cnt["numCopiedNodes"]), int(cnt["numFilteredNodes"])) == (2, 6)
+    assert (n[copied & leaf] == c.nodes["numSamples"][src[copied & leaf]]).all() and (n[copied & leaf] > sr.ROW * abi.POINTS_PER_CHUNK).all()
+    behind = [int((index[first[t]: first[t] + n[t]] - int(c.nodes["firstSample"][src[t]]) >= sr.OVER).sum()) for t in np.nonzero(filtered & leaf)[0]]
+    assert max(behind) >= 1, "no filtered leaf has a passing sample behind the row"
+    print(f"profile on A: passing samples at ordinals >= 50 000 per filtered leaf {behind}, samples per filtered leaf {n[filtered & leaf].tolist()}")
+    state, far = c, {"copied": 0, "filtered": 0}
+    for call in m["paint"]:
+        res, index = state.crop(call.region, 20, "all", footprint=call.footprint, return_index=True)
+        assert np.array_equal(state.samples["color"][index], call.previous)              # previous[j] belongs to sample j of the query's order
+        src, copied, filtered = _result_classes(c, res, call.region, call.footprint)
+        n = res.nodes["numSamples"].astype(np.int64)
+        far["copied"] += int((copied & (n > sr.OVER)).sum())
+        far["filtered"] += int((filtered & (n > sr.OVER)).sum())
+        state = call.export
+    print(f"paint on A: nodes with previous at a per-node offset >= 50 000: {far}")
+    assert far["copied"] >= 1 and far["filtered"] >= 1, far
+
+
+@pytest.mark.parametrize("name", SMALL_TWINS)
+def test_mirrors_of_paint_and_profile_against_the_per_sample_references(built_libs, name):
+    """On the twins small enough for a Python loop per sample: both battery paint calls of OctreeExport.paint against paint_ref.targets and
+    paint_ref.paint (target set, order, previous and the colour column after the call), and the segment of every sample OctreeExport.profile
+    returns against rule P1 decided exactly — with every sample it does not return in no segment."""
+    ex, pts, box, shape, _ = _twin(name)
+    assert ex.num_samples < 300_000
+    m = _mirrors(name)
+    q = m["q"]
+    assert pf.in_contract(ex.samples, ex.box_min, ex.box_max)
+    state = ex
+    for k, call in enumerate(m["paint"]):
+        idx = pf.targets(state.samples, call.region.planes, call.footprint)
+        col, prev = pf.paint(state.samples, idx, call.paint.record(), call.colors)
+        assert len(idx) == int(call.counts["numSamples"]) > 0, f"{name} call {k + 1}"
+        assert np.array_equal(np.asarray(prev, np.uint32), call.previous), f"{name} call {k + 1}: previous"
+        assert np.array_equal(col, call.export.samples["color"]), f"{name} call {k + 1}: the colours after the call"
+        assert all(call.export.samples[a].tobytes() == state.samples[a].tobytes() for a in "xyz")
+        state = call.export
+    mirror, rec, cnt = m["profile"]["all"]
+    seg = pr.locate_exact(q.profile, mirror.samples)
+    assert (seg >= 0).all() and np.array_equal(rec["segment"].astype(np.int64), seg), f"{name}: a returned sample's segment"
+    assert int((pr.locate_exact(q.profile, ex.samples) >= 0).sum()) == mirror.num_samples, f"{name}: a sample in the corridor was not returned"
+
+
+def test_packed_tails_around_the_row_end_merge_within_the_bound(built_libs):
+    """The tails delta of test_held_counts_around_the_row_end_send_exactly_the_tails, packed: GROWN ranges that begin at 49 999, 50 000, 50 001
+    and 56 000 of leaves of 75 000 points.  The words at both ends of every range are pack_ref's record by record; unpacked and merged into the
+    held table the delta gives the exact merge's table, its voxel entries bit for bit, its leaf entries within rule K8's bound."""
+    c, pts, box, shape, _ = _twin("A")
+    fresh = c.view(sr.view_uniforms(box, "closer"))
+    counts = (49_999, 50_000, 50_001, 56_000)
+    held, idx = sr.held_table(fresh, counts)
+    d = delta_between(fresh, held, tails=True)
+    assert delta_ref.states(d) == (4, 4, 0, 0)
+    pd, pc = d.pack(return_counts=True)
+    assert (int(pc["numSamples"]), int(pc["numInexact"]), int(pc["numAlpha"]), int(pc["error"])) == (d.num_samples, 0, 0, 0)
+    ends = {i for t, f, n in kr.ranges(d.nodes, d.entries) for i in (f, f + 1, f + n - 1)}
+    want = kr.pack_ref(d.nodes, d.samples, d.box_min, d.box_max, d.entries, pick=ends)
+    assert len(want) == len(ends) == 12 and all(int(pd.packed[i]) == int(w[0]) for i, w in want.items())
+    back = pd.unpack()
+    assert back.entries.tobytes() == d.entries.tobytes() and back.nodes.tobytes() == d.nodes.tobytes()
+    exact, lossy = d.apply(held), back.apply(held)
+    assert lossy.nodes.tobytes() == exact.nodes.tobytes() == fresh.nodes.tobytes() and exact.samples.tobytes() == fresh.samples.tobytes()
+    vox = kr.voxel_mask(exact.nodes, exact.num_samples)
+    assert lossy.samples[vox].tobytes() == exact.samples[vox].tobytes()
+    n, worst = kr.assert_points_within_bound(exact.nodes, exact.samples, lossy.samples, exact.box_min, exact.box_max, what="merged leaf entries")
+    assert n == int((~vox).sum()) == len(pts) and (lossy.samples["color"] == exact.samples["color"]).all()
+    # the heads are the receiver's own and stay exact, the tails moved
+    for t, k in zip(idx, counts):
+        a = int(exact.nodes["firstSample"][t])
+        assert lossy.samples[a: a + k].tobytes() == exact.samples[a: a + k].tobytes()
+        assert lossy.samples[a + k: a + int(exact.nodes["numSamples"][t])].tobytes() != exact.samples[a + k: a + int(exact.nodes["numSamples"][t])].tobytes()
+
+
 # ---- the oracle twins of the states ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["E1", "E2", "E3", "E4", "E5", "F", "H", "D hotspot_150k", "D dense_cube", "G 600000 poisoned", "G 600000 continued",
                                   "G 90000 poisoned", "G 90000 continued", "I A", "I B"])
@@ -100,7 +221,7 @@ def test_oracle_twin_passes_the_guards_of_its_state(built_libs, name):
     ex, pts, box, shape, ho = _twin(name)
     ex.validate(buildable=True)
     rr.assert_same_multiset(ex.truncated(20, "cut").samples, pts, name)
-    sr.mirrors(ex, pts, sr.view_uniforms(box, shape.camera), name, shape)
+    _mirrors(name)
 
 
 def test_twin_of_e_is_the_octree_of_two_of_six_batches(built_libs):

@@ -4,7 +4,9 @@ coalesced mode, a launch that stopped short with no host wait before the export,
 under a trunk mask, two octrees in one context and a rebuild in the same buffers.  Every state first asserts its precondition from Stats and
 the downloaded image, then goes through ONE battery: the export anchored byte for byte to export_ref.export_host of the downloaded image,
 the chunk table's stamp through the rasteriser's counter, one query of each kind against the numpy mirrors on the anchored export (guarded
-and held against brute force over the points the octree holds, tests/states_ref.py), and all of it again with the table dropped."""
+and held against brute force over the points the octree holds, tests/states_ref.py) — a profile, pack / unpack of the export and two paint
+calls with their undo among them —, and all of it again with the table dropped.  Where the builder goes on after a state (B, C, E), the octree
+is painted whole first and must end as the oracle's octree of the recoloured input (paint rule E7)."""
 import ctypes
 
 import numpy as np
@@ -17,6 +19,9 @@ import region_ref as rr
 import states_ref as sr
 import test_gpu_footprint as on_footprints
 import test_gpu_neighbours as on_spheres
+import test_gpu_pack as on_pack
+import test_gpu_paint as on_paint
+import test_gpu_profile as on_profile
 import test_gpu_rays as on_rays
 import test_gpu_region as on_regions
 import test_gpu_view as on_view
@@ -24,7 +29,7 @@ import test_gpu_view_delta as on_delta
 import view_ref as vr
 from export_ref import export_host
 from simlod_amd import abi, synthetic
-from simlod_amd.octree_io import OctreeExport
+from simlod_amd.octree_io import OctreeExport, Paint, Region
 from states_ref import State
 from test_gpu_deep_octrees import _count_fields, _feed_one_by_one, _feed_one_group
 from test_gpu_export import _assert_export, _device, _frames_equal
@@ -100,6 +105,61 @@ def _views(S, uv, M, what):
     assert only.rc == 0 and only.counts.tobytes() == M["delta"].counts.tobytes(), f"{what} delta: the count-only call"
 
 
+def _profiles(S, M, what):
+    """The corridor, cut and all: counts, table, samples and records byte for byte, poison behind them; the count-only call.
+    -> the device's counts of the cut"""
+    q = M["q"]
+    for sel, (mirror, rec, cnt) in M["profile"].items():
+        raw = on_profile.Raw(S.dev, S.u, q.profile, None, 20, sel)
+        on_profile._assert_matches(raw, mirror, rec, cnt, f"{what} profile {sel}")
+        only = on_profile.Raw(S.dev, S.u, q.profile, None, 20, sel, count_only=True, null_records=True)
+        assert only.rc == 0 and _count_fields(only.counts) == _count_fields(cnt) and only.table_bytes() == mirror.nodes.tobytes(), f"{what} profile {sel}: the count-only call"
+        assert only.poison_behind(mirror.num_nodes, 0), f"{what} profile {sel}: the count-only call wrote a sample or a record"
+        if sel == "cut":
+            counts = raw.counts
+    return counts
+
+
+def _packs(S, full, M, what):
+    """simlod_pack_samples and simlod_unpack_samples on the anchored full export against the mirror; the calls leave their inputs alone."""
+    px, pc, mback, uc = M["pack"]
+    packed, c, back = on_pack._assert_raw_is_mirror(S.dev, full.nodes, full.samples, full.box_min, full.box_max, what=f"{what} pack")
+    assert packed.tobytes() == px.packed.tobytes() and c.tobytes() == pc.tobytes() and back.tobytes() == mback.samples.tobytes(), f"{what} pack: not the battery's mirror"
+
+
+def _paints(S, M, what):
+    """The two paint calls of the mirror, then their undo in reverse order.  After each call: counts and table are the count-only query's,
+    `previous` is the mirror's with poison behind numSamples, the export is the mirror's, the Node array and Stats are as before.  After the
+    undo the image — Node array, Stats, every allocated byte of the persistent buffer — is the one taken before.  -> samples painted per call"""
+    dev, u = S.dev, S.u
+    before = on_paint._image(dev)
+    painted = []
+    for k, call in enumerate(M["paint"]):
+        tag = f"{what} paint call {k + 1}"
+        n = int(call.counts["numSamples"])
+        qtable, qc = on_paint._count_only(dev, u, call.region, call.footprint)
+        raw = on_paint.Raw(dev, u, call.paint, call.region, call.footprint, colors=call.colors)
+        assert raw.rc == 0 and _count_fields(raw.counts) == _count_fields(call.counts), f"{tag}: counts {raw.counts}, the mirror has {call.counts}"
+        assert raw.counts.tobytes() == qc.tobytes() and raw.table_bytes(int(qc["numNodes"])) == qtable, f"{tag}: not the count-only query's table"
+        assert bool((raw.table[int(qc["numNodes"]) * 40:] == 0xA5).all()), f"{tag}: the table was written past numNodes"
+        got = raw.previous()
+        assert np.array_equal(got[:n], call.previous), f"{tag}: {int((got[:n] != call.previous).sum())} words of previous differ, the first at {int(np.argmax(got[:n] != call.previous))}"
+        assert (got[n:] == on_paint.POISON).all(), f"{tag}: previous was written past numSamples"
+        ex = dev.export_octree(u)
+        assert ex.nodes.tobytes() == call.export.nodes.tobytes(), f"{tag}: the table of the export moved"
+        assert ex.samples.tobytes() == call.export.samples.tobytes(), f"{tag}: {int((ex.samples['color'] != call.export.samples['color']).sum())} colours differ from the mirror's"
+        nodes, stats, pers = on_paint._image(dev)
+        assert nodes == before[0] and stats == before[1] and pers != before[2], f"{tag}: the Node array or Stats moved, or nothing was painted"
+        painted.append(int(raw.counts["numSamples"]))
+    for call in reversed(M["paint"]):
+        raw = on_paint.Raw(dev, u, Paint.array(), call.region, call.footprint, colors=call.previous, previous=False)
+        assert raw.rc == 0 and _count_fields(raw.counts) == _count_fields(call.counts), f"{what}: the undo's counts"
+    after = on_paint._image(dev)
+    assert after[0] == before[0] and after[1] == before[1], f"{what}: the Node array or Stats differ after the undo"
+    assert after[2] == before[2], f"{what}: the persistent buffer differs after the undo"
+    return painted
+
+
 def _battery(S, table, what, shape=sr.Shape(), pairs_all=False, between=None):
     """Points 1-4 of the battery on one state.  table: whether the state claims a valid chunk table — True: a frame reads lists through it;
     False: it must not; "long": the stamp holds, but every list a frame can draw is longer than a row and the rasteriser, which takes whole
@@ -117,11 +177,43 @@ def _battery(S, table, what, shape=sr.Shape(), pairs_all=False, between=None):
             between()
         _pairs(S, full, M, f"{what} ({source})")
         _views(S, uv, M, f"{what} ({source})")
+        pc = _profiles(S, M, f"{what} ({source})")
+        _packs(S, full, M, f"{what} ({source})")
+        painted = _paints(S, M, f"{what} ({source})")           # last: it writes the octree, and undoes it
+        print(f"{what} ({source}): the profile copies {int(pc['numCopiedNodes'])} nodes and filters {int(pc['numFilteredNodes'])} ({int(pc['numSamples'])} samples), "
+              f"the paint calls recolour {painted[0]} and {painted[1]} samples")
         if source != "walk":
             assert dev.L.simlod_octree_image_replaced(dev._p(dev.nodes)) == 0    # point 4, last: the builder's side tables go with it
     dev.render(S.u)
     assert dev.lists_read_through_table() == 0, f"{what}: the table is still read after simlod_octree_image_replaced"
     return full
+
+
+PAINTED = 0xFF57C0DE                         # a colour no input point carries (each test asserts it)
+
+
+def _paint_everything(dev, u, pts):
+    """Rule E7's setup: a whole-box SET with PAINTED, one simlod_paint_region call and nothing else -> its counts"""
+    assert not (pts["color"] == PAINTED).any()
+    c = dev.paint_region(u, Region(), Paint.set(PAINTED))
+    assert int(c["numFilteredNodes"]) == 0 and int(c["numSamples"]) == int(c["numCandidates"]) > 0
+    return c
+
+
+def _recoloured(pts, n):
+    """`pts` with the first n points in PAINTED: what the oracle is fed where the device painted after n points"""
+    out = pts.copy()
+    out["color"][:n] = PAINTED
+    return out
+
+
+def _leaf_mask(ex):
+    return np.repeat((ex.nodes["flags"] & abi.EXPORT_FLAG_LEAF) != 0, ex.nodes["numSamples"].astype(np.int64))
+
+
+def _positions(p):
+    w = np.stack([p[a].view(np.uint32) for a in ("x", "y", "z")], axis=1)
+    return w[np.lexsort(w.T)]
 
 
 def _new(box, **kw):
@@ -184,8 +276,45 @@ def test_a_growth_across_slot_50_is_sent_as_tails(built_libs):
         if tails:
             assert (e["state"] == abi.DELTA_GROWN).all() and np.array_equal(e["numKept"].astype(np.int64), hn) and (e["numDelta"] > 18_000).all()
             assert int(mirror.counts["numGrown"]) == 8 and mirror.num_samples == 600_000 - int(hn.sum())
+            _pack_the_grown_delta(dev, uc, held, mirror, hn)
         else:
             assert (e["state"] == abi.DELTA_ADDED).all() and mirror.num_samples == 600_000
+
+
+def _pack_the_grown_delta(dev, uc, held, mirror, hn):
+    """Rule K5 on GROWN entries made by the device: eight ranges of 18 000 and more samples that begin at firstDelta behind numKept of 55 905 ..
+    56 863 (no multiple of a piece), in level-1 leaf frames of 75 000 points — the packed words and counts are the mirror's, the unpacked delta
+    is the mirror's, and the merge of the unpacked delta has the exact merge's table, its voxels bit for bit and its leaf points within rule
+    K8's bound with their colours."""
+    import pack_ref as kr
+    delta = dev.query_view_delta(uc, held, tails=True)
+    assert delta.entries.tobytes() == mirror.entries.tobytes() and delta.samples.tobytes() == mirror.samples.tobytes() and delta.nodes.tobytes() == mirror.nodes.tobytes()
+    before = [x.clone() for x in (delta.table_tensor, delta.entries_tensor, delta.samples_tensor)]
+    pd, c = dev.pack(delta, return_counts=True)
+    mp, mc = mirror.pack(return_counts=True)
+    assert c.tobytes() == mc.tobytes(), f"A growth, packed: counts {c}, the mirror has {mc}"
+    assert int(c["numSamples"]) == delta.num_samples == 600_000 - int(hn.sum()) and int(c["numInexact"]) == 0 and int(c["numAlpha"]) == 0 and int(c["error"]) == 0
+    assert pd.packed.tobytes() == mp.packed.tobytes(), f"A growth, packed: {int((pd.packed != mp.packed).sum())} words differ from the mirror's"
+    back = dev.unpack(pd)
+    assert back.samples.tobytes() == mp.unpack().samples.tobytes(), "A growth, unpacked: the samples differ from the mirror's"
+    assert back.entries.tobytes() == delta.entries.tobytes() and back.nodes.tobytes() == delta.nodes.tobytes()
+    assert all(bool((a == b).all()) for a, b in zip(before, (delta.table_tensor, delta.entries_tensor, delta.samples_tensor))), "A growth: pack or unpack changed its inputs"
+    # the delta's own ranges: every sample of the eight GROWN leaf entries within the bound of a level-1 frame
+    n, worst = kr.assert_points_within_bound(delta.nodes, delta.samples, back.samples, delta.box_min, delta.box_max, entries=delta.entries, what="A growth, the delta's ranges")
+    assert n == delta.num_samples, f"{n} of {delta.num_samples} delta samples checked"
+    exact, lossy = dev.merge_view_delta(held, delta), dev.merge_view_delta(held, back)
+    assert lossy.nodes.tobytes() == exact.nodes.tobytes() and lossy.num_samples == exact.num_samples
+    vox = kr.voxel_mask(exact.nodes, exact.num_samples)                     # (the root's voxels, where the camera selects it)
+    assert int((~vox).sum()) == 600_000 and lossy.samples[vox].tobytes() == exact.samples[vox].tobytes()
+    leaf = np.nonzero((exact.nodes["flags"] & abi.EXPORT_FLAG_LEAF) != 0)[0]
+    assert len(leaf) == 8 and (exact.nodes["level"][leaf] == 1).all()
+    n, worst = kr.assert_points_within_bound(exact.nodes, exact.samples, lossy.samples, exact.box_min, exact.box_max, what="A growth, merged leaf entries")
+    assert n == 600_000 and (lossy.samples[~vox]["color"] == exact.samples[~vox]["color"]).all()
+    # the kept heads are the receiver's own samples, exact; the tails did change (13 bits per axis)
+    for t, k in zip(leaf, hn):
+        a = int(exact.nodes["firstSample"][t])
+        assert lossy.samples[a: a + int(k)].tobytes() == exact.samples[a: a + int(k)].tobytes()
+    assert lossy.samples.tobytes() != exact.samples.tobytes()
 
 
 def test_a_leaves_hold_what_the_oracles_subtrees_hold(built_libs):
@@ -245,6 +374,39 @@ def test_b_resume_splits_the_imported_overfull_leaves(built_libs, tmp_path, mode
     assert re.nodes.tobytes() == want.nodes.tobytes()
 
 
+@pytest.mark.parametrize("mode", ["batch_by_batch", "one_group"])
+def test_b_painted_import_keeps_its_colours_through_the_late_splits(built_libs, tmp_path, mode):
+    """Rule E7 on the late splits of imported over-full leaves: the buildable import of A painted whole, then the 200 000 further points.  Colour
+    never steers the build, so the resumed octree is the oracle's continuous build of the 600 000 points recoloured and the 200 000 as they are
+    — every leaf's 16-byte records, every inner node's voxel positions —, and the root, which exists at paint time, keeps its painted voxels."""
+    a = _state_a()
+    pts, box, more = sr.b_input()
+    a["full"].save(tmp_path / "a.simlodx")
+    ld = OctreeExport.load(tmp_path / "a.simlodx")
+    dst = _device()
+    dst.tune("SIMLOD_EXACT_GROUP", 1 if mode == "batch_by_batch" else 2)
+    uu = _import(dst, ld, a["u"])
+    imported = dst.export_octree(uu)
+    n0 = int(imported.nodes["numSamples"][0])
+    assert len(sr.overfull_leaves(imported.nodes)) == 8 and n0 > 0 and not imported.nodes["flags"][0] & abi.EXPORT_FLAG_LEAF
+    c = _paint_everything(dst, uu, pts)
+    assert int(c["numSamples"]) == imported.num_samples and (dst.export_octree(uu).samples["color"] == PAINTED).all()
+    (_feed_one_by_one if mode == "batch_by_batch" else _feed_one_group)(dst, uu, more)
+    st = dst.read_stats()
+    assert int(st["dbg"]) == 0 and int(st["numPoints"]) == len(pts) and int(st["numPointsProcessed"]) == 200_000
+    early = _recoloured(pts[:600_000], 600_000)
+    want, _ = _oracle_export(box, [early[i:i + 150_000] for i in range(0, 600_000, 150_000)] + more)
+    re = dst.export_octree(uu)
+    sr.assert_no_overfull(re.nodes)
+    sr.assert_same_per_node(re, want, f"B {mode}, painted before the resume, against the oracle's build of the recoloured input")
+    nodes, pers, nn = host_image_of(dst)
+    oracle.check_invariants(nodes, nn)
+    leaf = _leaf_mask(re)
+    assert int((re.samples["color"][leaf] == PAINTED).sum()) == 600_000
+    root = re.samples[: int(re.nodes["numSamples"][0])]
+    assert int(re.nodes["firstSample"][0]) == 0 and int((root["color"] == PAINTED).sum()) >= n0, f"the root lost painted voxels: {int((root['color'] == PAINTED).sum())} of {n0}"
+
+
 # ---- C. deferred splits by scarce scratch -----------------------------------------------------------------------------------------------------
 C_POINTS, C_PENDING = 1_000_000, 4          # (found on the device: at 500 000 nothing spills, DESIGN §7)
 
@@ -274,14 +436,28 @@ def test_c_deferred_splits_and_the_catch_up(built_libs):
     before = dev.export_octree(u)
     assert sr.assert_state_c(st["dbg"], before.nodes) == C_PENDING
     _battery(State(dev, u, pts[:C_POINTS], box), True, "C deferred", sr.SHAPES["C"])
+    # rule E7 across the catch-up: everything painted while the splits are pending — the next batch moves those leaves' points
+    st = dev.read_stats()
+    pending = dev.export_octree(u)
+    assert sr.assert_state_c(st["dbg"], pending.nodes) == C_PENDING and pending.nodes.tobytes() == before.nodes.tobytes()
+    c = _paint_everything(dev, u, pts)
+    assert int(c["numSamples"]) == pending.num_samples
+    painted = _recoloured(pts, C_POINTS)
     u["momentaryBufferCapacity"] = full_capacity
     _feed(dev, u, batches[-1:])
     st = dev.read_stats()
     assert int(st["numPoints"]) == len(pts) and int(st["dbg"]) & ~sr.ERR_SPILLED == 0
-    after = _battery(State(dev, u, pts, box), True, "C caught up", sr.SHAPES["C"])
+    after = _battery(State(dev, u, painted, box), True, "C caught up", sr.SHAPES["C"])
     sr.assert_no_overfull(after.nodes)
     nodes, pers, nn = host_image_of(dev)
     oracle.check_invariants(nodes, nn)
+    leaf = _leaf_mask(after)
+    smp = after.samples
+    assert int(leaf.sum()) == len(pts) and int((smp["color"][leaf] == PAINTED).sum()) == C_POINTS
+    assert np.array_equal(_positions(smp[leaf & (smp["color"] == PAINTED)]), _positions(pts[:C_POINTS])), "the painted leaf points are not the points ingested before the paint"
+    # the leaves per node are the oracle's of the recoloured input (its inner nodes sample their voxels at other moments: not compared)
+    want, _ = _oracle_export(box, [painted[i:i + 500_000] for i in range(0, len(painted), 500_000)])
+    assert np.array_equal(sr.per_node(after, True), sr.per_node(want, True)), "C caught up: the leaves differ per node from the oracle's of the recoloured input"
 
 
 # ---- D. coalesced mode as the source ----------------------------------------------------------------------------------------------------------
@@ -334,6 +510,23 @@ def test_e_export_directly_behind_a_launch_that_stops_short(built_libs, stop):
     want, _ = _oracle_export(box, batches[:b])
     sr.assert_same_per_node(ex, want, f"E {stop} against the oracle's octree of {b} batches")
     _battery(State(dev, u, np.concatenate(batches[:b]), box), True, f"E {stop}", sr.SHAPES.get(f"E{b}", sr.SHAPES["E"]))
+    if stop != "batch_limit":
+        return
+    # rule E7 across a resumed launch sequence: paint with four batches pending in the ring, lift the limit, and the next launch directly
+    # behind the paint — the host waits for nothing but what paint_region itself waits for
+    sr.assert_stopped_short(dev.read_stats(), 2, 4)
+    torch.cuda.synchronize()
+    c = _paint_everything(dev, u, pts)
+    dev.set_batch_limit(abi.MAX_BATCHES_PER_LAUNCH)
+    dev.construct(u)
+    dev.drain(u)
+    st = dev.read_stats()
+    assert int(st["dbg"]) == 0 and int(st["batchletIndex"]) == len(batches) and int(st["numPoints"]) == len(pts)
+    assert int(c["numSamples"]) == ex.num_samples
+    want, _ = _oracle_export(box, [_recoloured(bt, len(bt)) for bt in batches[:2]] + batches[2:])
+    final = dev.export_octree(u)
+    sr.assert_same_per_node(final, want, "E batch_limit, painted at two batches and drained, against the oracle's build of the recoloured input")
+    assert int((final.samples["color"][_leaf_mask(final)] == PAINTED).sum()) == 200_000
 
 
 # ---- F. memory guard tripped ------------------------------------------------------------------------------------------------------------------
@@ -440,8 +633,21 @@ def test_i_two_octrees_in_one_context_and_a_rebuild(built_libs):
             u1["minNodeSize"] = 1.0
             dev.render(u1)
             assert dev.lists_read_through_table() > 0
+        # each battery paints its octree (and undoes it): the OTHER octree of the context — Node array, Stats, every allocated byte — stays
+        other = on_paint._image(B)
         fa = _battery(State(A, ua, pa, box_a), True, "I A", sr.SHAPES["I A"])
+        assert on_paint._image(B) == other, "I: the battery of A, its paint calls among it, changed B"
+        other = on_paint._image(A)
         fb = _battery(State(B, ub, pb, box_b), True, "I B", sr.SHAPES["I B"])
+        assert on_paint._image(A) == other, "I: the battery of B, its paint calls among it, changed A"
+        # ... and not only after the undo: one octree painted whole, the other looked at WHILE the paint stands
+        for dev, u, pts, oth, full in ((A, ua, pa, B, fa), (B, ub, pb, A, fb)):
+            other, own = on_paint._image(oth), on_paint._image(dev)
+            c, prev = dev.paint_region(u, Region(), Paint.set(PAINTED), return_previous=True)
+            assert not (pts["color"] == PAINTED).any() and int(c["numSamples"]) == full.num_samples
+            assert (dev.export_octree(u).samples["color"] == PAINTED).all() and on_paint._image(oth) == other, "I: painting one octree changed the other"
+            dev.paint_region(u, Region(), Paint.array(), colors=prev)
+            assert on_paint._image(dev) == own
         assert fa.num_nodes > fb.num_nodes
         # the smaller octree into A's buffers: the rows of the larger one lie behind it
         A.reset(ua := A.uniforms(W, H, Tb, box_b))
