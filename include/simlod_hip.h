@@ -69,7 +69,8 @@ int simlod_context_set_ingest_mode(SimlodContext* ctx, uint32_t mode);
 int simlod_context_set_construct_batch_limit(SimlodContext* ctx, uint32_t maxBatches);
 /* "That many ring batches are pending right now" (uploaded and not ingested, not counting what launches already enqueued will take): for the NEXT
  * kernel_construct launch of the context only — it enqueues kernels for that many batches (0: none, an idle frame), whatever the library would have
- * guessed.  The hint is consumed by the context's next launch, whichever octree that launch is for.  Optional: hosts whose upload-counter writes reach simlod_upload_counter_written (shim/cuda.h does that for the reference's) need not call it. */
+ * guessed.  The hint is consumed by the context's next launch, whichever octree that launch is for (a launch uses at most its batch limit of it, a chain —
+ * simlod_launch_construct_chain — up to launches x that).  Optional: hosts whose upload-counter writes reach simlod_upload_counter_written (shim/cuda.h does that for the reference's) need not call it. */
 int simlod_context_hint_pending_batches(SimlodContext* ctx, uint32_t pending);
 /* The host has enqueued a write of `value` to the 4-byte upload counter at `numBatchesUploaded` (main_progressive_octree.cpp:1047-1050:
  * cuMemsetD32Async(cptr_numBatchesUploaded, batchStreamUploadIndex + 1, 1, stream_upload)).  kernel_construct reads the counter on the device when it
@@ -145,6 +146,34 @@ int simlod_launch_construct(const SimlodUniforms* uniforms /*host*/, SimlodPoint
                             uint8_t* buffer_persistent, SimlodNode* nodes, SimlodStats* stats,
                             uint64_t* frameStartTimestamp, void* cudaprint, uint32_t* numBatchesUploaded_volatile,
                             uint32_t* batchSizes, void* stream);
+
+/* A CHAIN of kernel_construct launches: one call that stands for `launches` (>= 1) consecutive simlod_launch_construct calls with NOTHING between
+ * them on the stream — a host that drains a burst of uploaded batches and looks at the octree only afterwards.  Between two such launches the
+ * builder's two-stream pipeline would drain (the last group's back half, the tail kernels, the next launch's k_begin, its first group's front half,
+ * one after the other); inside a chain that seam is an ordinary group boundary.  Contract:
+ *   - the effect is that of `launches` consecutive simlod_launch_construct calls with nothing between them; the octree, Stats and the launch report
+ *     are those of the LAST of them.  No intermediate state is observable — whatever the caller enqueues next on `stream` sees the complete octree
+ *     and complete Stats, as after simlod_launch_construct;
+ *   - launches == 1 IS simlod_launch_construct: the same code path, the same kernels in the same order;
+ *   - the upload counter is read ONCE, by the chain's k_begin: batches published while the chain runs are taken by the next launch, as with a
+ *     launch today (consecutive launches would each have looked);
+ *   - a SEGMENT is what one of those launches would have taken: L = min(the context's construct batch limit, 20) batches, counted from the chain's
+ *     first batch.  Groups of batches (SIMLOD_EXACT_GROUP, coalesced mode) never straddle a segment boundary: 36 batches in groups of five are
+ *     ingested as 5,5,5,5 | 5,5,5,1, the groups — and so the voxel colours — of the two-launch run.  The 10 ms time budget is per segment;
+ *   - the chain is sized as ONE launch for up to launches x L batches (told counter, hint, reports, prediction; the cap when nothing is known), and
+ *     simlod_context_hint_pending_batches may name up to launches x L for it;
+ *   - a chain that would go batch by batch (exact mode near the memory guard, a forced time budget, SIMLOD_EXACT_GROUP=1) or that finds at most
+ *     one group is issued as plain launches, one per segment, exactly as today; a chain whose groups exceed what one device launch can number
+ *     (20) is cut into several device launches inside the call;
+ *   - a chain may STOP earlier than the launches it stands for would: once a segment stops (time budget, memory guard), the segments behind it take
+ *     nothing, and the memory guard treats the first group of a later segment like any group inside a launch (conservatively, while the voxel half
+ *     of the group before may still allocate).  The host launches again, as it does after any launch that left batches pending; that launch's first
+ *     group is decided exactly, and the end state is the reference's.
+ * A host that renders, reads Stats or uploads by Stats between launches keeps calling simlod_launch_construct. */
+int simlod_launch_construct_chain(const SimlodUniforms* uniforms /*host*/, SimlodPoint* points, uint32_t* buffer,
+                                  uint8_t* buffer_persistent, SimlodNode* nodes, SimlodStats* stats,
+                                  uint64_t* frameStartTimestamp, void* cudaprint, uint32_t* numBatchesUploaded_volatile,
+                                  uint32_t* batchSizes, uint32_t launches, void* stream);
 
 /* render.cu:1084-1093  `kernel_render`; `colorbuffer` stands for the GL surface: a linear width*height RGBA8 image */
 int simlod_launch_render(uint32_t* buffer, const SimlodUniforms* uniforms /*host*/, SimlodNode* nodes,

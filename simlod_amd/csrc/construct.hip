@@ -160,8 +160,12 @@ static SideStream* side_stream(Context& ctx) {
 	return ctx.side[dev];
 }
 
-int launch_construct(Context& ctx, const SimlodUniforms* u, SimlodPoint* points, uint32_t* buffer, uint8_t* pers, SimlodNode* nodes,
-                     SimlodStats* stats, uint64_t* frameStart, uint32_t* numBatchesUploaded, uint32_t* batchSizes, hipStream_t stream) {
+// ONE device launch: k_begin, the groups, the tail.  launches: how many launches of the caller's it may stand for (a chain: simlod_launch_construct_chain); -> *taken:
+// how many it stood for — fewer where the groups of more would not fit the ordinal tables (chain_segments_per_launch), ONE where the chain goes launch by launch
+// (chain_goes_plain).  hinted: the context's hint for what is left of the chain (< 0: none).
+static int launch_construct_part(Context& ctx, const SimlodUniforms* u, SimlodPoint* points, uint32_t* buffer, uint8_t* pers, SimlodNode* nodes,
+                                 SimlodStats* stats, uint64_t* frameStart, uint32_t* numBatchesUploaded, uint32_t* batchSizes, hipStream_t stream,
+                                 uint32_t launches, int hinted, uint32_t* taken) {
 	BuildArgs a{};
 	a.ring = points; a.mom = reinterpret_cast<uint8_t*>(buffer); a.pers = pers; a.nodes = nodes; a.stats = stats;
 	a.frameStart = frameStart; a.numBatchesUploaded = numBatchesUploaded; a.batchSizes = batchSizes;
@@ -189,14 +193,20 @@ int launch_construct(Context& ctx, const SimlodUniforms* u, SimlodPoint* points,
 	const DeviceInfo& dev = device_info();
 
 	note_upload_counter(numBatchesUploaded, 0u, false, true);
-	const LaunchPlan plan = launch_plan(ctx, nodes, numBatchesUploaded);
-	const uint32_t limit = plan.batches;
+	// A chain: one k_begin, then the groups of every SEGMENT (what one of its launches would have taken: segLen batches from the chain's first) in order — no
+	// group straddles a segment boundary, so the groups are those of the launch-by-launch run —, then one tail.  The seam between two segments is an ordinary
+	// group boundary: the front half of the next segment's first group runs beside the back half of this segment's last.
+	const uint32_t segLen = std::min<uint32_t>(ctx.batchLimit.load(), SIMLOD_MAX_BATCHES_PER_LAUNCH);
+	uint32_t segments = fits ? std::min<uint32_t>(launches, chain_segments_per_launch(segLen, a.groupMax)) : 1u;
+	const LaunchPlan plan = launch_plan(ctx, nodes, numBatchesUploaded, hinted, a.groupMax, a.acct != 0u, &segments);
+	*taken = segments;
+	const uint32_t limit = plan.batches, chainCap = segments * segLen;
 	// batches per group this launch aims at: the layout's, or — exact mode, when the latest launch reported that groups of several batches are out of the
 	// question for now (LaunchPlan::mayGroup) — one, with one group of kernels per batch
 	const uint32_t take = a.acct != 0u && !plan.mayGroup ? 1u : a.groupMax;
 	// (one workgroup does the launch's bookkeeping; all of them restore the side tables when the stamp is stale: the first launch of an octree, as a rule)
 	SIMLOD_LAUNCH(k_begin, dim3(fits ? dev.numCUs * 2 : 1u), dim3(TPB), stream, a, fits ? 0u : 1u, limit, ((uint32_t)ctx.tune(KNOB_DEBUG_FORCE_BARRIER_TIMEOUT, 0) & 1u) | (ctx.tune(KNOB_DEBUG_VOXELIZE_CLOCK, 0) != 0 ? 2u : 0u) | (plan.sideTablesStale ? 4u : 0u) | (ctx.tune(KNOB_DEBUG_IRREGULAR_CHILDREN, 0) != 0 ? 8u : 0u) | (((uint32_t)ctx.tune(KNOB_DEBUG_PHASE_WG, 0) & 0xffffu) << 8),
-	              (uint32_t)std::max(0, ctx.tune(KNOB_DEBUG_BUDGET_US, 0)), take);
+	              (uint32_t)std::max(0, ctx.tune(KNOB_DEBUG_BUDGET_US, 0)), take, chainCap, segLen);
 	if (fits) {
 		const uint32_t gridPoints = dev.numCUs * (uint32_t)ctx.tune(KNOB_GRID_MULT, 8);
 		// k_expand's workgroups meet at grid barriers: never more than one per CU (all must be resident).  One per TWO CUs is the
@@ -205,7 +215,7 @@ int launch_construct(Context& ctx, const SimlodUniforms* u, SimlodPoint* points,
 		// (with the previous batch's voxel half running beside it on the side stream: one per FOUR CUs — 256: 8.3 ms per ingest, 128: 7.8,
 		// 96: 7.5, 64: 7.2, 48: 7.3, 32: 7.5)
 		// kernel groups to enqueue: one per ring batch, or per groupMax of them (coalesced mode, exact mode in groups)
-		const uint32_t numGroups = (limit + take - 1u) / take;
+		const uint32_t numGroups = chain_groups(limit, segLen, take);      // (one launch: limit <= segLen, ceil(limit / take))
 		const bool overlap = ctx.tune(KNOB_OVERLAP_TAIL, 1) != 0 && !profile_enabled() && numGroups > 1u;   // (two streams: see below)
 		// (coalesced mode: a group's later rounds pass over tens of millions of samples inside k_expand — every CU takes part: 3.49 -> 2.78 ms per 36 M)
 		const bool single = take == 1u || limit <= 1u;      // every group of this launch is ONE ring batch (k_begin takes no more than `limit` batches)
@@ -253,7 +263,7 @@ int launch_construct(Context& ctx, const SimlodUniforms* u, SimlodPoint* points,
 			SIMLOD_LAUNCH_STOP(k_expand<false>, dim3(expandWgs), dim3(ETPB), stream, expanded, a, b, single ? 0u : 1u, (uint32_t)SIMLOD_MAX_EXPAND_ROUNDS);
 			expand_gate_leave(ctx, stream, expanded, gated);
 			if (side != nullptr) { const hipError_t e = hipStreamWaitEvent(back, expanded, 0); if (e != hipSuccess) return fail(e); }
-			if (!single && a.acct != 0u) SIMLOD_LAUNCH(k_rootpre, dim3(1), dim3(1024), back, a, b);
+			if (!single) SIMLOD_LAUNCH(k_rootpre, dim3(1), dim3(1024), back, a, b);      // (coalesced groups too: a root that splits behind the group's first batch)
 			if (single) SIMLOD_LAUNCH_STOP(k_insert<true>, dim3(gridPoints), dim3(TPB), back, inserted, a, b);   // grid clears, points, end-of-batch bookkeeping, the previous group's voxel lists
 			else SIMLOD_LAUNCH_STOP(k_insert<false>, dim3(gridPoints), dim3(TPB), back, inserted, a, b);
 			if (profile_dominant()) {      // bench.py's roofline: the dominant kernel timed in the headline configuration, by the launch's own start / stop events
@@ -280,6 +290,22 @@ int launch_construct(Context& ctx, const SimlodUniforms* u, SimlodPoint* points,
 	hipError_t e = hipGetLastError();
 	if (e != hipSuccess) return (int)e;
 	return fits ? 0 : (int)hipErrorInvalidValue;
+}
+
+// simlod_launch_construct (launches = 1) and simlod_launch_construct_chain: device launches until the chain's launches are all stood for
+int launch_construct(Context& ctx, const SimlodUniforms* u, SimlodPoint* points, uint32_t* buffer, uint8_t* pers, SimlodNode* nodes,
+                     SimlodStats* stats, uint64_t* frameStart, uint32_t* numBatchesUploaded, uint32_t* batchSizes, hipStream_t stream, uint32_t launches) {
+	int hinted = ctx.hintPending.exchange(-1);                      // simlod_context_hint_pending_batches: for THIS call
+	const uint32_t segLen = std::min<uint32_t>(ctx.batchLimit.load(), SIMLOD_MAX_BATCHES_PER_LAUNCH);
+	while (launches != 0u) {
+		uint32_t taken = 1u;
+		const int rc = launch_construct_part(ctx, u, points, buffer, pers, nodes, stats, frameStart, numBatchesUploaded, batchSizes, stream, launches, hinted, &taken);
+		if (rc != 0) return rc;
+		taken = std::max(1u, std::min(taken, launches));
+		launches -= taken;
+		if (hinted >= 0) hinted = (int)((uint32_t)hinted > taken * segLen ? (uint32_t)hinted - taken * segLen : 0u);      // (what the launches that follow can still find)
+	}
+	return 0;
 }
 
 uint64_t construct_min_bytes(uint32_t nodeCapacity) {

@@ -8,11 +8,17 @@
 // full clear every 2^19 batches keeps them unambiguous.)  Every thread of the launch reads the stamp for itself — nobody writes those words
 // while k_begin runs: the stamp is taken off by the launch's first k_count —, so the decision needs no second kernel (round 4: a memset and two
 // kernels per launch; round 5, first: two kernels that exited at once; 9 us each on a chain that is one batch long).
+// The tag-wrap test asks for the clear from the first launch that BEGINS within TAG_WRAP_WINDOW batches behind a multiple of 2^19: no launch may step
+// over that window, so it is as wide as the most any device launch can take — a chained launch (simlod_launch_construct_chain) holds up to 20 groups
+// of up to 20 batches.  WIDENED from 20 for chains (rather than cutting chains at the boundary): a plain launch that follows a chain across the wrap
+// must see it too, and the price is a rebuild for a few launches once in 524 288 batches.
+static constexpr uint32_t TAG_WRAP_WINDOW = 512;
+static_assert(TAG_WRAP_WINDOW >= SIMLOD_MAX_BATCHES_PER_LAUNCH * SIMLOD_MAX_BATCHES_PER_LAUNCH, "a device launch takes at most 20 groups of at most 20 batches");
 __device__ __forceinline__ bool stamp_is_stale(const BuildArgs& a, const Ctl* ctl) {
 	const uint32_t first = a.stats->batchletIndex;
 	return ctl->tableMagic != TABLE_MAGIC || ctl->tableBatch != first || ctl->tableNodes != (uint64_t)a.nodes || ctl->tablePers != (uint64_t)a.pers ||
 	       ctl->tableLayout != layout_signature(a) || ctl->tableSig != table_signature(a.stats) ||
-	       (first >= 0x80000u && (first & 0x7ffffu) < SIMLOD_MAX_BATCHES_PER_LAUNCH);
+	       (first >= 0x80000u && (first & 0x7ffffu) < TAG_WRAP_WINDOW);
 }
 
 // (the 8 spare bytes Chunk::size / padding_0 of a list's HEAD chunk: the address of the list's last chunk)
@@ -103,7 +109,7 @@ __device__ void rebuild_side_tables(const BuildArgs& a, bool irregular) {      /
 	}
 }
 
-__global__ __launch_bounds__(TPB) void k_begin(BuildArgs a, uint32_t momentaryTooSmall, uint32_t batchLimit, uint32_t debugFlags, uint32_t budgetUs, uint32_t groupMax) {
+__global__ __launch_bounds__(TPB) void k_begin(BuildArgs a, uint32_t momentaryTooSmall, uint32_t batchLimit, uint32_t debugFlags, uint32_t budgetUs, uint32_t groupMax, uint32_t chainCap, uint32_t segLen) {
 	Ctl* ctl = ctl_of(a);
 	const bool stale = momentaryTooSmall != 0u || (debugFlags & 4u) != 0u || stamp_is_stale(a, ctl);      // (debugFlags bit 2: the host knows the image was replaced — simlod_octree_image_replaced, a reset)
 	if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -125,8 +131,9 @@ __global__ __launch_bounds__(TPB) void k_begin(BuildArgs a, uint32_t momentaryTo
 		const uint32_t first = a.stats->batchletIndex;
 		uint32_t n = uploaded - first;
 		if ((int32_t)n < 0) n = 0;
-		if (n > SIMLOD_MAX_BATCHES_PER_LAUNCH) n = SIMLOD_MAX_BATCHES_PER_LAUNCH;
+		if (n > chainCap) n = chainCap;      // voxels.cu:883: 20 — a chained launch: 20 (or the context's limit) per launch it stands for
 		if (n > batchLimit) n = batchLimit;
+		ctl->chainCap = chainCap; ctl->segLen = max(segLen, 1u);
 		ctl->uploaded = uploaded;
 		ctl->firstBatch = first;
 		ctl->numBatches = n;

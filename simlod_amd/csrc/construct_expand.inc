@@ -671,6 +671,19 @@ __global__ __launch_bounds__(ETPB) void k_expand(BuildArgs a, uint32_t ordinal, 
 				}
 				__syncthreads();
 			}
+			else if (t == 0u && L == 0u && rec.born == NONE && GB > 1u) {
+				// coalesced groups keep no counts per batch, but a root that is still a leaf is the whole octree: every sample of batch k of the group lies in it.
+				// The batch it splits in — by the rule above — follows from the batches' sizes alone, and the batches in front of it met the root's grid as a
+				// leaf's (voxels.cu:449-463) before the split cleared it (voxels.cu:371-382): k_rootpre replays that, as for exact groups
+				const bool forcedL = trunk_any(a) && trunk_forced(a, l, sh.LX, sh.LY, sh.LZ);
+				uint32_t c = rec.stored, sL = GB - 1u;
+				for (uint32_t k = 0; k < GB; k++) {
+					const uint32_t g = bc->start[k + 1u] - bc->start[k];
+					if (forcedL || (g != 0u && c + g > SIMLOD_MAX_POINTS_PER_NODE)) { sL = k; break; }
+					c += g;
+				}
+				bc->rootSplitAt = sL;
+			}
 			pd.mark(33);      // exact groups: when every node split, chunks taken and returned per batch
 			// ---- the slots of the next round and every grid this slot needs, in ONE go ----
 			// A great-grandchild that is still too full after three levels gets a slot of its own for the next round (its eight children reserved now, no stored

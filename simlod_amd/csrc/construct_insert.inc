@@ -28,7 +28,7 @@ __global__ __launch_bounds__(TPB) void k_voxdone(BuildArgs a) {
 	voxdone_nodes(a, ctl, ctl->tagOf[ctl->processed - 1u], min(a.stats->numNodes, a.nodeCapacity), blockIdx.x * TPB + threadIdx.x, gridDim.x * TPB);   // (the launch's last group)
 }
 
-// ---- rootpre: an exact group of several batches in which the ROOT splits ------------------------------------------------------------------
+// ---- rootpre: a group of several batches (exact or coalesced) in which the ROOT splits ------------------------------------------------------------------
 // A root that is still a leaf samples ITSELF (voxels.cu:449-463: every node of the path that has a grid, and the root has one from the reset on), and the
 // batch that splits it clears that grid and samples everything again from nothing (voxels.cu:371-382): the root's voxel list keeps what the batches
 // before the split put there AND gets every cell again.  Ingested batch by batch that is what happens; in a group, the batches in front of the
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(TPB) void k_voxdone(BuildArgs a) {
 __global__ __launch_bounds__(1024) void k_rootpre(BuildArgs a, uint32_t ordinal) {
 	Ctl* ctl = ctl_of(a);
 	BatchCtl* bc = batch_of(ctl, ordinal);
-	if (bc == nullptr || ctl->abortBatch || bc->acct == 0u) return;
+	if (bc == nullptr || ctl->abortBatch || bc->groupBatches <= 1u) return;      // (exact groups: k_expand's accounting names the batch; coalesced groups: from the batches' sizes)
 	const uint32_t sR = bc->rootSplitAt;
 	if (sR == NONE || sR == 0u) return;
 	// the root's voxel list as the group before left it (its k_voxelize has ended: stream order): closed here, in front of this group's first voxels
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(TPB) void k_insert(BuildArgs a, uint32_t ordinal) {
 			const uint32_t back = gridDim.x - 1u - blockIdx.x;
 			if (back >= 1u && back <= DONE_WGS && bc->ordinal != 0u)
 				voxdone_nodes(a, ctl, ctl->tagOf[bc->ordinal - 1u], min(a.stats->numNodes, a.nodeCapacity), (back - 1u) * TPB + threadIdx.x, DONE_WGS * TPB,
-				              bc->acct != 0u && bc->rootSplitAt != 0xffffffffu && bc->rootSplitAt != 0u);      // (k_rootpre has closed the root's list and appended to it since)
+				              bc->groupBatches > 1u && bc->rootSplitAt != 0xffffffffu && bc->rootSplitAt != 0u);      // (k_rootpre has closed the root's list and appended to it since)
 		}
 		ph.mark(pb + 0);
 		// the occupancy grids of the nodes this batch split (k_count's tail and k_expand listed them): cleared here, by everybody, before

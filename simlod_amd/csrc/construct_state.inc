@@ -17,7 +17,7 @@ struct BatchCtl {
 	unsigned long long reserve0;       // ... as the group began (k_count's first workgroup): what k_queue's entries count from
 	// per-batch chunk accounting of an exact group (acct): point chunks batch k of the group would have taken / given back had the batches been ingested one
 	// by one (voxels.cu:346-357, 485-538), filled by k_expand; the chunk counters as they stood when the group began (k_count's first workgroup)
-	uint32_t acctAlloc0, acctPool0, rootSplitAt, pad5;      // rootSplitAt: an exact group in which the ROOT splits: the batch of the group it splits in (k_rootpre); NONE otherwise
+	uint32_t acctAlloc0, acctPool0, rootSplitAt, pad5;      // rootSplitAt: a group of several batches (exact or coalesced) in which the ROOT splits: the batch of the group it splits in (k_rootpre); NONE otherwise
 	uint32_t acctD[SIMLOD_MAX_BATCHES_PER_LAUNCH], acctF[SIMLOD_MAX_BATCHES_PER_LAUNCH];
 };
 
@@ -34,12 +34,17 @@ struct Ctl {
 	uint64_t tableSig;                 // table_signature() of the Stats the table belongs to
 	uint64_t tableLayout;              // layout_signature() of the momentary buffer the side tables were built in
 	uint64_t pointsTaken;              // samples of all batches taken so far, this launch's included (Stats.numPointsProcessed follows when their back halves have run)
-	uint64_t unused1[2];
+	uint32_t chainCap, segLen;         // a chained launch (simlod_launch_construct_chain): batches it may take in all | ... per SEGMENT — what one of the launches it stands for would take; a plain launch is one segment
+	uint64_t unused1;
 	uint64_t expandNs[8];              // byte 152: k_expand phase times of workgroup 0 (in-kernel histogram pass, barrier, decide + build, barrier, [4] = groups ingested so far (bench.py), rounds, calls; tools/probe.py), [7] = spilled points so far (bench.py)
 	uint64_t voxT[SIMLOD_MAX_BATCHES_PER_LAUNCH][3];   // byte 216: k_voxelize of group #ordinal of the last launch: first workgroup in, last piece done, last workgroup out (tools/probe.py)
 	uint64_t phaseNs[48];              // byte 696: phase times of one workgroup per kernel, summed over the launches since the host last cleared them (tools/probe.py)
 	BatchCtl batch[BATCH_COPIES];
 	uint32_t tagOf[SIMLOD_MAX_BATCHES_PER_LAUNCH];     // tag of group #ordinal of this launch (whoever closes a group's voxel lists later needs it: its parity copy is recycled by then)
+	// when the SEGMENT of group #ordinal began (prepare_batch of the segment's first group; the groups behind it copy it): what end_of_batch measures the time
+	// budget from.  Per ordinal, not per launch: the back half lags the front, which may have begun the next segment already.  (BatchCtl has no room for
+	// 8 more bytes — tools read it by offset — so the group's copy lives here)
+	uint64_t segStart[SIMLOD_MAX_BATCHES_PER_LAUNCH];
 };
 static_assert(offsetof(Ctl, voxT) == 216 && offsetof(Ctl, phaseNs) == 696, "tools/probe.py reads Ctl.voxT at byte 216, Ctl.phaseNs at byte 696");
 static_assert(offsetof(Ctl, expandNs) == 152, "bench.py / tools read Ctl.expandNs at byte 152");
@@ -306,7 +311,11 @@ __device__ void prepare_batch(const BuildArgs& a, Ctl* ctl, uint32_t ordinal) {
 	a.stats->memCapacityReached = full ? 1 : 0;
 	if (full) { ctl->stop = 1; return; }
 	const uint32_t batchIndex = ctl->firstBatch + ctl->consumed;       // (Stats.batchletIndex itself is advanced by the back half, which may lag)
-	uint32_t take = min(ctl->groupMax, ctl->numBatches - ctl->consumed);
+	// (a chain: no group straddles a segment boundary — the groups are those of the launches the chain stands for, and so are the voxel colours)
+	const uint32_t intoSegment = ctl->consumed % ctl->segLen;
+	uint32_t take = min(min(ctl->groupMax, ctl->numBatches - ctl->consumed), ctl->segLen - intoSegment);
+	// voxels.cu:936-949: the 10 ms are a launch's — here a segment's: stamped when its first group is prepared (the chain's first: the launch's own start)
+	ctl->segStart[ordinal] = ordinal == 0u ? ctl->startNs : intoSegment == 0u ? wall_ns() : ctl->segStart[ordinal - 1u];
 	if (a.acct != 0u && take > 1u) {
 		// An EXACT group of several batches is taken only where the reference's guard — looked at before EVERY batch (voxels.cu:896-912) — cannot
 		// trip inside it: the allocator must be a worst-case group away from it.  Closer than that, the launch goes batch by batch as before.

@@ -292,7 +292,8 @@ __device__ void end_of_batch(const BuildArgs& a, Ctl* ctl, BatchCtl* bc) {
 		ctl->expandNs[4] += 1;                                   // ... and groups of batches ingested so far: the launches of a per-group kernel that had work (bench.py's roofline)
 		// voxels.cu:936-949: no further batch once the launch has run for 10 ms.  The front half of the next batch (or two) may be under way
 		// already; what has been prepared is completed, nothing more is prepared.
-		const float elapsedMs = (float)(wall_ns() - ctl->startNs) / 1000000.0f;
+		// (a chained launch: 10 ms per SEGMENT, from this group's own copy of its segment's start — the front half may have begun the next segment)
+		const float elapsedMs = (float)(wall_ns() - ctl->segStart[bc->ordinal]) / 1000000.0f;
 		if (elapsedMs > (float)ctl->budgetUs / 1000.0f) __hip_atomic_store(&ctl->stop, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	}
 }

@@ -3,6 +3,7 @@
 // a function of plain numbers — tests/host/octree_state_check.cpp runs both on a machine without a GPU.
 #pragma once
 #include <stdint.h>
+#include <algorithm>
 #include <mutex>
 #include <vector>
 #ifndef SIMLOD_MAX_BATCHES_PER_LAUNCH
@@ -92,6 +93,8 @@ inline OctreeState& octree_of(std::vector<OctreeState>& octrees, const void* nod
 // uploader's pace, and never less than one group — a host that uploads, launches once and waits must not wait for ever.
 // The launch is numbered ++h.seq.  seen: the four words of h.seen, read once | hinted: simlod_context_hint_pending_batches for this launch, else < 0 |
 // hostKnown, uploadedHost: the host has said what it wrote to the upload counter, and what (simlod_upload_counter_written; a reset: zero)
+// limit: the most this launch may take — the context's batch limit L (<= 20); a CHAIN of n launches (simlod_launch_construct_chain) is sized as ONE launch
+// with limit n x L, and counts as one in enq[].
 inline LaunchPlan size_launch(LaunchHistory* h, const uint32_t seen[4], int hinted, uint32_t limit, bool hostKnown, uint32_t uploadedHost) {
 	LaunchPlan plan{SIMLOD_MAX_BATCHES_PER_LAUNCH, true, nullptr, 0u, false};
 	const uint32_t seq = ++h->seq;
@@ -121,7 +124,7 @@ inline LaunchPlan size_launch(LaunchHistory* h, const uint32_t seen[4], int hint
 		// ... and nothing at all is enqueued only on the word of a host that has been HEARD since the reset or whose launches have reported: "zero uploaded"
 		// right after a reset is also what a host that tells nothing looks like (it uploads, launches once and waits)
 		if (want == 0u && !reported) want = 1u;
-	} else if (!reported) want = SIMLOD_MAX_BATCHES_PER_LAUNCH;                          // nothing is known: everything
+	} else if (!reported) want = std::max<uint32_t>(SIMLOD_MAX_BATCHES_PER_LAUNCH, limit);   // nothing is known: everything (a chain: its cap)
 	else {
 		// the host says nothing: what the latest report saw pending + what was uploaded between the last two reports (the uploader's pace per launch)
 		const uint32_t pending = uploadedSeen > index ? uploadedSeen - index : 0u;
@@ -136,6 +139,33 @@ inline LaunchPlan size_launch(LaunchHistory* h, const uint32_t seen[4], int hint
 	h->enq[seq % 32u] = plan.batches;
 	return plan;
 }
+// ---- chained launches (simlod_launch_construct_chain): one k_begin, the groups of every segment, one tail ----------------------------------------
+// A SEGMENT is what one of the chain's launches would have taken: L batches, counted from the chain's first.  Groups never straddle a segment
+// boundary (voxel colours depend on the grouping: the chain's groups are those of the launch-by-launch run), so a launch sized for `batches`
+// enqueues ceil(L / take) groups per whole segment and ceil(rest / take) for the last.
+inline uint32_t chain_groups(uint32_t batches, uint32_t L, uint32_t take) {
+	if (L == 0u || take == 0u) return 0u;
+	return batches / L * ((L + take - 1u) / take) + (batches % L + take - 1u) / take;
+}
+// Group ordinals index tables of SIMLOD_MAX_BATCHES_PER_LAUNCH entries (events, Ctl.tagOf / voxT / segStart): the segments ONE device launch can hold.
+// A chain of more is cut by the entry point into several device launches.
+inline uint32_t chain_segments_per_launch(uint32_t L, uint32_t take) {
+	const uint32_t perSegment = chain_groups(L, L, take);
+	return perSegment == 0u ? 1u : std::max<uint32_t>(1u, SIMLOD_MAX_BATCHES_PER_LAUNCH / perSegment);
+}
+// the device launches of a chain of `launches`: how many segments device launch #k takes (k = 0, 1, ...; 0 when the chain has ended before it)
+inline uint32_t chain_cut(uint32_t launches, uint32_t L, uint32_t take, uint32_t k) {
+	const uint32_t per = chain_segments_per_launch(L, take);
+	return (uint64_t)k * per >= launches ? 0u : std::min<uint32_t>(per, launches - k * per);
+}
+// A chain goes launch by launch, one plain launch per segment, when it would go batch by batch (take == 1) or finds at most one group: nothing to overlap at a seam
+inline bool chain_goes_plain(uint32_t batches, uint32_t L, uint32_t take) { return take <= 1u || chain_groups(batches, L, take) <= 1u; }
+// ... and the plan of a chain that goes plain becomes the plan of its first launch (the others are sized when they are enqueued)
+inline void shrink_planned(LaunchHistory* h, LaunchPlan* plan, uint32_t L) {
+	plan->batches = std::min<uint32_t>(plan->batches, L);
+	if (h != nullptr && plan->feedback != nullptr) h->enq[plan->seq % 32u] = plan->batches;
+}
+
 // A reset through this library (the reset is numbered ++h.seq, the return value): nothing ingested, nothing uploaded, as k_reset will report in stream order
 inline uint32_t forget_history(LaunchHistory* h) {
 	h->seen[0] = NOTHING_SEEN; h->seen[1] = NOTHING_SEEN; h->seen[2] = 1u;

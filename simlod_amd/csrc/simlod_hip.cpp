@@ -176,9 +176,9 @@ void note_upload_counter(const void* counter, uint32_t value, bool written, bool
 	g_counters.push_back(UploadCounter{counter, value, written});
 }
 
-LaunchPlan launch_plan(Context& ctx, const void* nodes, const void* uploadCounter) {
-	const uint32_t limit = std::min<uint32_t>(ctx.batchLimit.load(), SIMLOD_MAX_BATCHES_PER_LAUNCH);
-	const int hinted = ctx.hintPending.exchange(-1);                      // simlod_context_hint_pending_batches: for THIS launch
+LaunchPlan launch_plan(Context& ctx, const void* nodes, const void* uploadCounter, int hinted, uint32_t groupMax, bool acct, uint32_t* launches) {
+	const uint32_t L = std::min<uint32_t>(ctx.batchLimit.load(), SIMLOD_MAX_BATCHES_PER_LAUNCH);
+	const uint32_t limit = *launches * L;
 	uint32_t uploadedHost = 0;
 	const bool hostKnown = host_uploaded(uploadCounter, uploadedHost);
 	Locked o(ctx, nodes, true);
@@ -186,6 +186,10 @@ LaunchPlan launch_plan(Context& ctx, const void* nodes, const void* uploadCounte
 	if (ctx.tune(KNOB_ADAPTIVE_GROUPS, 1) != 0 && o->history.seen != nullptr) {
 		const uint32_t seen[4] = {o->history.seen[0], o->history.seen[1], o->history.seen[2], o->history.seen[3]};
 		plan = size_launch(&o->history, seen, hinted, limit, hostKnown, uploadedHost);
+	}
+	if (*launches > 1u && chain_goes_plain(plan.batches, L, acct && !plan.mayGroup ? 1u : groupMax)) {
+		shrink_planned(&o->history, &plan, L);
+		*launches = 1u;
 	}
 	plan.sideTablesStale = o->take_stale();
 	return plan;
@@ -339,7 +343,7 @@ int simlod_context_set_construct_batch_limit(SimlodContext* c, uint32_t maxBatch
 	return 0;
 }
 int simlod_context_hint_pending_batches(SimlodContext* c, uint32_t pending) {
-	ctx_or_default(c).hintPending.store((int)std::min<uint32_t>(pending, SIMLOD_MAX_BATCHES_PER_LAUNCH));
+	ctx_or_default(c).hintPending.store((int)std::min<uint32_t>(pending, 0x7fffffffu));      // (cut to what the launch — or the chain — can take where it is used)
 	return 0;
 }
 int simlod_upload_counter_written(const void* numBatchesUploaded, uint32_t value) {
@@ -407,16 +411,22 @@ int simlod_launch_reset(const SimlodUniforms* uniforms, uint8_t* buffer_octree, 
 	return launch_reset(ctx, uniforms, buffer_octree, nodes, stats, numBatchesUploaded, batchSizes, (hipStream_t)stream);
 }
 
-int simlod_launch_construct(const SimlodUniforms* uniforms, SimlodPoint* points, uint32_t* buffer, uint8_t* buffer_persistent,
-                            SimlodNode* nodes, SimlodStats* stats, uint64_t* frameStartTimestamp, void* cudaprint,
-                            uint32_t* numBatchesUploaded_volatile, uint32_t* batchSizes, void* stream) {
+int simlod_launch_construct_chain(const SimlodUniforms* uniforms, SimlodPoint* points, uint32_t* buffer, uint8_t* buffer_persistent,
+                                  SimlodNode* nodes, SimlodStats* stats, uint64_t* frameStartTimestamp, void* cudaprint,
+                                  uint32_t* numBatchesUploaded_volatile, uint32_t* batchSizes, uint32_t launches, void* stream) {
 	(void)cudaprint;
 	if (!uniforms || !points || !buffer || !buffer_persistent || !nodes || !stats || !frameStartTimestamp ||
-	    !numBatchesUploaded_volatile || !batchSizes) return (int)hipErrorInvalidValue;
+	    !numBatchesUploaded_volatile || !batchSizes || launches == 0u) return (int)hipErrorInvalidValue;
 	Context& ctx = context_of(nodes);
 	if (array_state(ctx, nodes).imported) return (int)hipErrorInvalidValue;      // an imported octree has no grids and no builder state
 	array_event(ctx, nodes, ARRAY_CONSTRUCT);
-	return build::launch_construct(ctx, uniforms, points, buffer, buffer_persistent, nodes, stats, frameStartTimestamp, numBatchesUploaded_volatile, batchSizes, (hipStream_t)stream);
+	return build::launch_construct(ctx, uniforms, points, buffer, buffer_persistent, nodes, stats, frameStartTimestamp, numBatchesUploaded_volatile, batchSizes, (hipStream_t)stream, launches);
+}
+
+int simlod_launch_construct(const SimlodUniforms* uniforms, SimlodPoint* points, uint32_t* buffer, uint8_t* buffer_persistent,
+                            SimlodNode* nodes, SimlodStats* stats, uint64_t* frameStartTimestamp, void* cudaprint,
+                            uint32_t* numBatchesUploaded_volatile, uint32_t* batchSizes, void* stream) {
+	return simlod_launch_construct_chain(uniforms, points, buffer, buffer_persistent, nodes, stats, frameStartTimestamp, cudaprint, numBatchesUploaded_volatile, batchSizes, 1u, stream);
 }
 
 int simlod_decode_las(const void* records, uint64_t numPoints, uint32_t bytesPerPoint, uint32_t format, const double scale[3],

@@ -114,7 +114,7 @@ void expand_gate_forget(Context& ctx);                                         /
 namespace build {  // construct.hip: kernel_construct — one ring batch at a time (exact mode) or groups of pending batches (coalesced mode)
 
 int launch_construct(Context& ctx, const SimlodUniforms* u, SimlodPoint* points, uint32_t* buffer, uint8_t* pers, SimlodNode* nodes,
-                     SimlodStats* stats, uint64_t* frameStart, uint32_t* numBatchesUploaded, uint32_t* batchSizes, hipStream_t stream);
+                     SimlodStats* stats, uint64_t* frameStart, uint32_t* numBatchesUploaded, uint32_t* batchSizes, hipStream_t stream, uint32_t launches = 1u);   // launches > 1: simlod_launch_construct_chain
 uint64_t construct_min_bytes(uint32_t nodeCapacity);
 
 }  // namespace build
@@ -125,7 +125,10 @@ void octree_image_replaced(Context& ctx, const void* nodes);                 // 
 bool find_leaf_table(Context& ctx, const void* nodes, LeafTableRef& ref);    // false also when the table's buffer is no longer a live device allocation
 
 // How many batches a kernel_construct launch should enqueue kernels for (simlod_hip.cpp: launch sizing).
-LaunchPlan launch_plan(Context& ctx, const void* nodes, const void* uploadCounter);
+// launches: the launch stands for that many (a chain: sized for up to launches x the context's batch limit) | hinted: the context's hint as the entry point
+// took it (< 0: none) | take: batches per group the layout allows — a chain that would go launch by launch (chain_goes_plain) comes back as the plan of its
+// first launch, *launches = 1
+LaunchPlan launch_plan(Context& ctx, const void* nodes, const void* uploadCounter, int hinted, uint32_t groupMax, bool acct, uint32_t* launches);
 void forget_launch_history(Context& ctx, const void* nodes, const void* uploadCounter, uint32_t** words, uint32_t* seq);   // reset (words: where k_reset reports, as launch *seq)
 void note_upload_counter(const void* counter, uint32_t value, bool written, bool create);     // written: the host has enqueued a write of `value` to the upload counter at `counter`; else: `counter` is named as one
 

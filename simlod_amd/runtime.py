@@ -62,6 +62,7 @@ def lib():
         L.simlod_construct_buffer_min_bytes.restype = u64
         L.simlod_launch_reset.argtypes = [vp] * 8
         L.simlod_launch_construct.argtypes = [vp] * 11
+        L.simlod_launch_construct_chain.argtypes = [vp] * 10 + [u32, vp]
         L.simlod_launch_render.argtypes = [vp] * 8
         L.simlod_launch_render_part.argtypes = [ctypes.c_uint32] + [vp] * 8
         L.simlod_render_frame_composed.argtypes = [vp] * 10
@@ -125,7 +126,7 @@ def lib():
 
 EXPORTED_SYMBOLS = [
     "simlod_set_node_capacity", "simlod_render_framebuffer_offset", "simlod_render_buffer_bytes",
-    "simlod_construct_buffer_min_bytes", "simlod_launch_reset", "simlod_launch_construct", "simlod_launch_render",
+    "simlod_construct_buffer_min_bytes", "simlod_launch_reset", "simlod_launch_construct", "simlod_launch_construct_chain", "simlod_launch_render",
     "simlod_program_create", "simlod_program_destroy", "simlod_program_kernel", "simlod_function_max_active_blocks",
     "simlod_launch_cooperative", "simlod_build_info", "simlod_decode_las", "simlod_launch_render_part",
     "simlod_render_depth_plane_offset", "simlod_render_sum_planes_offset", "simlod_render_frame_layout", "simlod_set_ingest_mode", "simlod_set_construct_batch_limit",
@@ -171,7 +172,7 @@ class DeviceOctree:
     """Device buffers of initCudaProgram() + the three launches, on one GPU."""
 
     def __init__(self, device="cuda:0", *, persistent_bytes=4 << 30, momentary_bytes=300_000_000, max_nodes=263_157,
-                 ring_slots=abi.BATCH_STREAM_SIZE, max_pixels=1920 * 1080, coalesce=False, sizes_launches=True):
+                 ring_slots=abi.BATCH_STREAM_SIZE, max_pixels=1920 * 1080, coalesce=False, sizes_launches=True, chain=True):
         if not torch.cuda.is_available():
             raise SimlodError("no GPU visible: the SimLOD hot paths only exist as gfx950 kernels")
         self.L = lib()
@@ -194,6 +195,9 @@ class DeviceOctree:
         # nothing (the library predicts from its launches' reports alone).  SIMLOD_HOST_HINT=1: drain() / stream() also say how many batches are
         # pending in front of every launch (simlod_context_hint_pending_batches): the two must give the same rates (bench.py reports both).
         self.notifies = sizes_launches
+        # drain() enqueues the launches of a round as ONE chain (simlod_launch_construct_chain: the builder's pipeline stays full across the launch
+        # boundaries).  chain=False or SIMLOD_CHAIN=0: launch by launch, as the reference host does.
+        self.chain = bool(chain) and os.environ.get("SIMLOD_CHAIN", "1") != "0"
         self.hint_pending = sizes_launches and os.environ.get("SIMLOD_HOST_HINT", "0") == "1"
         z = dict(dtype=torch.uint8, device=self.device)
         # H11: the reference renders before any reset and relies on fresh VRAM reading as zero
@@ -259,10 +263,10 @@ class DeviceOctree:
         self.batch_limit = max(1, min(int(max_batches), abi.MAX_BATCHES_PER_LAUNCH))
         _check(self.L.simlod_context_set_construct_batch_limit(self.ctx, max_batches), "simlod_context_set_construct_batch_limit")
 
-    def _hint(self, pending=None):
-        """Tell the library how many batches are pending for the next launch (SIMLOD_HOST_HINT=1 only; None: nothing to say)."""
+    def _hint(self, pending=None, launches=1):
+        """Tell the library how many batches are pending for the next launch — or chain of `launches` — (SIMLOD_HOST_HINT=1 only; None: nothing to say)."""
         if self.hint_pending and pending is not None:
-            _check(self.L.simlod_context_hint_pending_batches(self.ctx, max(0, min(int(pending), self.batch_limit))), "simlod_context_hint_pending_batches")
+            _check(self.L.simlod_context_hint_pending_batches(self.ctx, max(0, min(int(pending), launches * self.batch_limit))), "simlod_context_hint_pending_batches")
 
     # -- helpers ---------------------------------------------------------------------------------------------
     def uniforms(self, width, height, transform, box_size, **kw):
@@ -377,6 +381,14 @@ class DeviceOctree:
         _check(self.L.simlod_launch_construct(up, self._p(self.ring), self._p(self.momentary), self._p(self.persistent),
                                               self._p(self.nodes), self._p(self.stats), self._p(self.frame_start), None,
                                               self._p(self.num_uploaded), self._p(self.batch_sizes), self._stream()), "kernel_construct")
+
+    def construct_chain(self, uniforms, launches):
+        """`launches` consecutive kernel_construct launches with nothing between them, as ONE call (simlod_launch_construct_chain): the octree and
+        Stats afterwards are those of the last; launches=1 is construct()."""
+        u, up = self._u(uniforms)
+        _check(self.L.simlod_launch_construct_chain(up, self._p(self.ring), self._p(self.momentary), self._p(self.persistent),
+                                                    self._p(self.nodes), self._p(self.stats), self._p(self.frame_start), None,
+                                                    self._p(self.num_uploaded), self._p(self.batch_sizes), int(launches), self._stream()), "kernel_construct (chain)")
 
     def _launch_frame(self, uniforms, launch, what):
         """One kernel_render-shaped call: the two buffers grown to what the uniforms' W x H frame needs, then launch(the eight arguments).  -> (W, H), which the readers below take as the last frame's size"""
@@ -526,7 +538,9 @@ class DeviceOctree:
     def drain(self, uniforms, max_launches=1000):
         """Launch kernel_construct until every uploaded batch is ingested.  One launch takes at most 20 batches and stops
         early once it has run for 10 ms (progressive_octree_voxels.cu:883, :939-949) — the reference host simply launches
-        again next frame; so does this loop.  Returns the number of launches."""
+        again next frame; so does this loop.  Returns the number of launches.
+        With chain=True (the default) the launches of a round go to the library as ONE chain (construct_chain).  The arithmetic and the return value
+        stay what they are: the number of <= 20-batch launches the chains stand for — launch counts asserted or reported anywhere stay comparable."""
         launches = 0
         idle = 0
         before = self.processed_host              # (what the host last saw: 0 after a reset; too low only costs a launch that exits at once)
@@ -534,9 +548,13 @@ class DeviceOctree:
             # as many launches as the pending batches need at 20 per launch, enqueued back to back (the reference's frame loop does not wait
             # for a launch either before it enqueues the next frame's); then ONE look at Stats
             need = -(-(self.uploaded_host - before) // self.batch_limit)
-            for k in range(need):
-                self._hint(self.uploaded_host - before - k * self.batch_limit)
-                self.construct(uniforms)
+            if self.chain and need > 1:
+                self._hint(self.uploaded_host - before, need)
+                self.construct_chain(uniforms, need)
+            else:
+                for k in range(need):
+                    self._hint(self.uploaded_host - before - k * self.batch_limit)
+                    self.construct(uniforms)
             self._hint()
             launches += need
             after = self.processed()
