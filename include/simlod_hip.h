@@ -730,6 +730,81 @@ int simlod_paint_region(const SimlodNode* nodes, const SimlodStats* stats, const
                         SimlodExportNode* table, uint32_t tableCapacity, const uint32_t* colors /*ARRAY only*/, uint32_t* previous /*or NULL*/,
                         uint64_t colorCapacity, SimlodQueryCounts* counts, void* stream);
 
+/* ---- summary queries: a selection's extent, histograms and moments in place ------------------------------------------------------------------
+ * simlod_query_summary says something ABOUT the samples a footprint query selects without copying them out: how many there are, the box they
+ * span, the sums a centroid and a covariance come from, the histogram of their heights in the bins a RAMP paint would use, and the histograms
+ * of the four bytes of their colour words.  It is a read-only reduction: each selected sample is read once, one fixed-size record is written,
+ * and every field of it is an integer count, an integer sum or a minimum / maximum under a total order — exact, and independent of the order
+ * in which the samples are visited.
+ *
+ * Everything the region and the footprint section say stays in force: the box, the classes of a node, rules 3 and F1 per sample, the
+ * chunk-table / `next` sources.
+ *  S0. Set.  The summarised samples are exactly the samples that simlod_query_footprint(region, footprint, maxLevel, select) returns on the same
+ *      octree (footprint == NULL: simlod_query_region).  Unlike paint, maxLevel and select are the caller's: the summary of one level-of-detail
+ *      cut is the meaningful one.  `table` and `counts` come back as that query's count-only call writes them, byte for byte.  A COPIED node
+ *      contributes every sample without a test, a FILTERED node the samples that pass.
+ *  S1. Extent.  Per axis, over the samples whose coordinate on that axis is not a NaN: the minimum and the maximum under the total order of the
+ *      key k(bits) = bits ^ ((bits >> 31) ? 0xffffffff : 0x80000000) of the coordinate's 32 bits, compared as unsigned integers.  Under that key
+ *      -0 < +0 and the infinities take part, so the result does not depend on the order of visiting.  With no such sample min = +inf and
+ *      max = -inf.
+ *  S2. Moments.  Per axis a, t = ((double)x_a - (double)boxMin_a) * inv with inv = 1048576.0 / (double)size, `size` the box size of the region
+ *      section; inv is one IEEE division made by the launcher on the host.  The device does not divide and uses no fused multiply-add.
+ *      c20 = 1048575 if t >= 1048575.0, (uint32_t)t if t > 0.0, else 0 (a NaN gives 0); c16 = c20 >> 4.  sum[a] is the sum of c20_a; sum2 holds
+ *      the sums of the six products c16_a * c16_b in the order xx, yy, zz, xy, xz, yz.  All sums are 64-bit unsigned integers: a term of `sum`
+ *      is below 2^20 and a term of `sum2` below 2^32, so no sum can overflow while numSamples < 2^32; neither can a histogram's 32-bit
+ *      partial count.  numSamples is bounded by Stats.numPoints + Stats.numVoxels; past 2^32 selected samples (64 GB of them) the sums and
+ *      the histograms may wrap, and no error bit says so.
+ *  S3. histZ.  histZ[i] counts the samples with i = rule E3's index of their z under params.z0 and params.scale: exactly the number of samples
+ *      a SIMLOD_PAINT_RAMP paint of the same selection (at maxLevel = 20, SIMLOD_EXPORT_ALL) would give table[i].
+ *  S4. histC.  histC[k][(color >> 8k) & 255] counts, for k = 0..3, byte k of the colour word.
+ *  S5. All or nothing.  With any error bit in counts.error (a tableCapacity or scratch buffer too small: SIMLOD_EXPORT_ERR_CAPACITY; a broken
+ *      list) `summary` is not written at all.
+ *  S6. Nothing is written but `scratch`, `table`, `counts` and `summary`: the octree, its frame state and the builder's chunk table are
+ *      untouched.  Any octree the footprint query accepts is accepted: built, imported (render-only or buildable), shifted, deep.
+ *  S7. Grid independence.  The record does not depend on params.maxWorkgroups.
+ *  S8. hipErrorInvalidValue with nothing enqueued: everything simlod_query_footprint refuses (with simlod_summary_buffer_min_bytes(tableCapacity, 0)
+ *      as the scratch bound), params == NULL, summary == NULL, z0 or scale not finite, scale <= 0, nonzero `reserved`, `summary` not 8-byte
+ *      aligned.
+ * numNonFinite counts the samples with a NaN or an infinity in x, y or z.  Asynchronous on `stream` once `region`, `footprint` and `params`
+ * have been read; `summary` is DEVICE memory. */
+typedef struct SimlodSummaryParams {   /* host memory, read before the call returns */
+	float    z0, scale;                /* the z histogram's bins: rule E3's index of (z, z0, scale) */
+	uint32_t maxWorkgroups;            /* 0: the library's choice; else the reduction launches at most this many workgroups */
+	uint32_t reserved;                 /* 0 */
+} SimlodSummaryParams;
+typedef struct SimlodSummary {         /* written by the device */
+	uint64_t numSamples;               /* == counts.numSamples */
+	uint64_t numNonFinite;             /* samples with a NaN or an infinity in x, y or z */
+	float    min[3], max[3];           /* rule S1 */
+	uint64_t sum[3];                   /* rule S2: sum of c20 per axis */
+	uint64_t sum2[6];                  /* rule S2: sum of c16_a * c16_b for xx, yy, zz, xy, xz, yz */
+	uint64_t histZ[256];               /* rule S3 */
+	uint64_t histC[4][256];            /* rule S4: byte k of the colour word */
+} SimlodSummary;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodSummaryParams) == 16, "SummaryParams");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSummaryParams, scale) == 4, "SummaryParams.scale");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSummaryParams, maxWorkgroups) == 8, "SummaryParams.maxWorkgroups");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSummaryParams, reserved) == 12, "SummaryParams.reserved");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodSummary) == 10352, "Summary");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSummary, numNonFinite) == 8, "Summary.numNonFinite");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSummary, min) == 16, "Summary.min");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSummary, max) == 28, "Summary.max");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSummary, sum) == 40, "Summary.sum");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSummary, sum2) == 64, "Summary.sum2");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSummary, histZ) == 112, "Summary.histZ");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSummary, histC) == 2160, "Summary.histC");
+
+/* simlod_footprint_buffer_min_bytes plus the partial records of the largest grid the library ever chooses (about 5 MB), with or without a
+ * footprint; params.maxWorkgroups only lowers the grid. */
+uint64_t simlod_summary_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+
+/* The summary query (rules above).  `nodes`, `stats`, `uniforms`, `region`, `footprint`, `maxLevel`, `select`, `scratch`, `table` and `counts`
+ * as simlod_query_footprint's. */
+int simlod_query_summary(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                         const SimlodFootprint* footprint /*or NULL*/, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select,
+                         void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary /*device*/,
+                         SimlodQueryCounts* counts, void* stream);
+
 /* ---- ray queries: the first sample in a cone along each ray of a batch ----------------------------------------------------------------------
  * simlod_query_rays answers "what does this ray hit" for up to 2^20 rays at once: per ray the sample with the smallest parameter t that lies
  * within radius + spread * t of the ray, among the samples of the nodes simlod_export_octree(maxLevel, select) selects.  The source is only read.

@@ -200,6 +200,16 @@ paint_dtype = np.dtype({"names": ["mode", "color", "strength", "reserved", "z0",
                         "offsets": [0, 4, 8, 12, 16, 20, 24, 32], "itemsize": 1056})
 assert paint_dtype.itemsize == 1056
 
+# ---- summary queries (include/simlod_hip.h, "summary queries") ---------------------------------------------------------------------------
+SUMMARY_CELLS = 1 << 20                                                     # rule S2: cells per axis; the products use the top 16 bits
+SUMMARY_MOMENTS = ("xx", "yy", "zz", "xy", "xz", "yz")                      # the order of SimlodSummary.sum2
+summary_params_dtype = np.dtype({"names": ["z0", "scale", "maxWorkgroups", "reserved"], "formats": ["<f4", "<f4", "<u4", "<u4"],
+                                 "offsets": [0, 4, 8, 12], "itemsize": 16})
+summary_dtype = np.dtype({"names": ["numSamples", "numNonFinite", "min", "max", "sum", "sum2", "histZ", "histC"],
+                          "formats": ["<u8", "<u8", ("<f4", 3), ("<f4", 3), ("<u8", 3), ("<u8", 6), ("<u8", 256), ("<u8", (4, 256))],
+                          "offsets": [0, 8, 16, 28, 40, 64, 112, 2160], "itemsize": 10352})
+assert summary_params_dtype.itemsize == 16 and summary_dtype.itemsize == 10352
+
 # ---- profile queries (include/simlod_hip.h, "profile queries") --------------------------------------------------------------------------
 PROFILE_MAX_VERTICES = 64
 PROFILE_NO_SEGMENT = 0xFFFFFFFF

@@ -20,6 +20,8 @@
 // polygon on top of the planes, in export_footprint.inc.
 // Paint (simlod_paint_region): that sequence as a count-only call, then k_e_paint / k_ef_paint, which write colour words into the octree's own
 // chunks, in export_paint.inc; the rules in paint_rules.hpp.
+// Summary (simlod_query_summary): that sequence as a count-only call, then k_s_partial / k_fs_partial and k_s_final, which reduce the selected
+// samples to one SimlodSummary record, in export_summary.inc; the rules in summary_rules.hpp.
 // Profile query (simlod_query_profile): k_pr_hier -> k_q_dir -> k_pr_count -> k_q_scan -> k_pr_write, the same sequence with a corridor along a
 // polyline on top of the planes and a record per returned sample, in export_profile.inc; the rules themselves in profile_rules.hpp.
 // View query (simlod_query_view): k_v_hier -> k_v_scan -> k_x_dir -> k_copy, the export's sequence with the camera's rules in the walk, in
@@ -48,6 +50,7 @@
 #include "profile_rules.hpp"
 #include "pack_rules.hpp"
 #include "paint_rules.hpp"
+#include "summary_rules.hpp"
 
 namespace simlod {
 namespace {
@@ -58,6 +61,7 @@ namespace {
 #include "export_region.inc"   // QueryGeom, classify, QItem, QueryLayout, QueryArgs, k_q_hier, k_q_dir, k_q_count, k_q_scan, k_q_write
 #include "export_footprint.inc"  // FootEdge, FootGeom, FootArgs, stage_edges, Footprint, classify_footprint, k_f_hier, k_f_count, k_f_write
 #include "export_paint.inc"    // PaintOp, PaintArgs, FootPaintArgs, paint_colour, e_paint, k_e_paint, k_ef_paint
+#include "export_summary.inc"  // SummaryPart, SummaryOp, SummaryArgs, FootSummaryArgs, hist_add, s_partial, k_s_partial, k_fs_partial, k_s_final
 #include "export_profile.inc"  // ProfGeom, ProfArgs, stage_segments, Profile, k_pr_hier, k_pr_count, locate_record, k_pr_write
 #include "export_view.inc"     // ViewArgs, k_v_hier, k_v_scan
 #include "export_delta.inc"    // DeltaLayout, DeltaArgs, k_d_match, k_d_scan, k_d_dir, k_d_drop, MergeArgs, k_d_merge_scan, k_d_merge_dir
@@ -259,6 +263,65 @@ int launch_paint(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats
 		SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);
 		SIMLOD_LAUNCH(k_e_paint, dim3(grid), dim3(LANE_TPB), stream, pa);
 	}
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+uint64_t summary_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return footprint_min_bytes(nodeCapacity, sampleBound) + SUMMARY_BLOCK_BYTES; }
+
+namespace {
+
+// k_s_partial's grid: four workgroups of 256 lanes per CU (the kernel is bound by its arithmetic from there on: DESIGN §11 has the times by
+// grid), SUMMARY_MAX_PARTS at most (the scratch buffer's block holds that many parts), no more than the buffer can hold items, and no more
+// than the caller allows (0: no limit of the caller's)
+uint32_t summary_grid(uint64_t itemCap, uint32_t maxWorkgroups) {
+	uint64_t g = std::min<uint64_t>((uint64_t)device_info().numCUs * 4u, SUMMARY_MAX_PARTS);
+	g = std::min<uint64_t>(g, itemCap == 0u ? 1u : itemCap);
+	if (maxWorkgroups != 0u) g = std::min<uint64_t>(g, maxWorkgroups);
+	return (uint32_t)std::max<uint64_t>(g, 1u);
+}
+
+}  // namespace
+
+// simlod_query_summary: the footprint query's launches as a count-only call with the caller's maxLevel and select, the polygon and the partial
+// records in the scratch buffer's blocks in front of the items, then k_s_partial (fp == nullptr) or k_fs_partial, then k_s_final.
+int launch_summary(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
+                   const SimlodFootprint* fp, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                   SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts, hipStream_t stream) {
+	if (params == nullptr || summary == nullptr || !summary_acceptable(*params) || (reinterpret_cast<uintptr_t>(summary) & 7u) != 0u) return (int)hipErrorInvalidValue;
+	FootSummaryArgs fa{};
+	FootEdge edges[SIMLOD_FOOTPRINT_MAX_VERTICES];
+	if (fp != nullptr && !footprint_edges(fp, fa.f.f, edges)) return (int)hipErrorInvalidValue;
+	constexpr uint64_t front = FOOT_BLOCK_BYTES + SUMMARY_BLOCK_BYTES;
+	QueryArgs& q = fa.f.q;
+	const int rc = prepare_query(ctx, nodes, stats, u, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, nullptr, 0u, counts, front, q);
+	if (rc != 0) return rc;
+	SummaryOp& s = fa.s;
+	s.inv = summary_inv((float)q.g.size); s.z0 = params->z0; s.scale = params->scale;
+	s.parts = q.x.lay.items - SUMMARY_BLOCK_BYTES;
+	const uint32_t grid = copy_grid(q.x.lay.itemCap), sgrid = summary_grid(q.x.lay.itemCap, params->maxWorkgroups);
+	const SummaryFinalArgs fin{q.x.scratch, s.parts, sgrid, 0u, counts, summary};
+	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                        // k_q_dir: one wave per table entry
+	if (fp != nullptr) {
+		fa.f.f.n = fp->numVertices;
+		fa.f.f.edges = q.x.lay.items - front;
+		// (pageable host memory: the runtime has read `edges` when the call returns)
+		const hipError_t e = hipMemcpyAsync(q.x.scratch + fa.f.f.edges, edges, (size_t)fa.f.f.n * sizeof(FootEdge), hipMemcpyHostToDevice, stream);
+		if (e != hipSuccess) return (int)e;
+		SIMLOD_LAUNCH(k_f_hier, dim3(1), dim3(WG_TPB), stream, fa.f);
+		if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
+		SIMLOD_LAUNCH(k_f_count, dim3(grid), dim3(LANE_TPB), stream, fa.f);
+		SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);
+		SIMLOD_LAUNCH(k_fs_partial, dim3(sgrid), dim3(LANE_TPB), stream, fa);
+	} else {
+		SummaryArgs sa{q, s};
+		SIMLOD_LAUNCH(k_q_hier, dim3(1), dim3(WG_TPB), stream, q);
+		if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
+		SIMLOD_LAUNCH(k_q_count, dim3(grid), dim3(LANE_TPB), stream, q);
+		SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);
+		SIMLOD_LAUNCH(k_s_partial, dim3(sgrid), dim3(LANE_TPB), stream, sa);
+	}
+	SIMLOD_LAUNCH(k_s_final, dim3(SUMMARY_FINAL_HIST_WGS + 1u), dim3(WG_TPB), stream, fin);
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();
 }

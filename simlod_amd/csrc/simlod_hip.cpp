@@ -499,6 +499,17 @@ int simlod_paint_region(const SimlodNode* nodes, const SimlodStats* stats, const
 	                    colorCapacity, counts, (hipStream_t)stream);
 }
 
+uint64_t simlod_summary_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return summary_min_bytes(nodeCapacity, sampleBound); }
+
+int simlod_query_summary(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                         const SimlodFootprint* footprint, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select, void* scratch,
+                         uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts,
+                         void* stream) {
+	if (nodes == nullptr) return (int)hipErrorInvalidValue;
+	return launch_summary(context_of(nodes), nodes, stats, uniforms, region, footprint, params, maxLevel, select, scratch, scratchBytes, table,
+	                      tableCapacity, summary, counts, (hipStream_t)stream);
+}
+
 uint64_t simlod_profile_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return profile_min_bytes(nodeCapacity, sampleBound); }
 
 int simlod_query_profile(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,

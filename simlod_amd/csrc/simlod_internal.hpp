@@ -191,6 +191,11 @@ int launch_paint(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats
                  const SimlodFootprint* footprint, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
                  uint32_t tableCapacity, const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts, hipStream_t stream);
 uint64_t paint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+int launch_summary(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
+                   const SimlodFootprint* footprint, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select, void* scratch,
+                   uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts,
+                   hipStream_t stream);
+uint64_t summary_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
 int launch_profile(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
                    const SimlodProfile* profile, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
                    uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodProfileSample* records, SimlodQueryCounts* counts,

@@ -27,6 +27,10 @@ Footprint queries (include/simlod_hip.h, "footprint queries"): `Footprint` holds
 Paint regions (include/simlod_hip.h, "paint regions"): `Paint` holds the mode and its parameters, `OctreeExport.paint` is the host mirror of
 simlod_paint_region — the same export with the colours of crop's samples changed, and the colours they had.
 
+Summary queries (include/simlod_hip.h, "summary queries"): `OctreeExport.summarize` is the host mirror of simlod_query_summary — crop's samples
+reduced to one record in numpy float64 and integers —, `Summary` wraps that record (extent, centroid, covariance, the range and the equalised
+table of a height ramp) and `Paint.ramp_from` turns one into a RAMP paint.
+
 Profile queries (include/simlod_hip.h, "profile queries"): `Profile` holds the polyline, the half-width and the three affine maps,
 `OctreeExport.profile` is the host mirror of simlod_query_profile — samples and records — and `classify_profile` of its rule P3.
 
@@ -256,6 +260,45 @@ class OctreeExport:
         smp["color"][index] = new
         ex = OctreeExport(self.nodes.copy(), smp, self.box_min, self.box_max, self.max_level, self.select)
         return (ex, c, previous) if return_previous else (ex, c)
+
+    # -- summary queries (include/simlod_hip.h, "summary queries") -------------------------------------------------------------------------
+    def summarize(self, region, max_level=None, select="cut", footprint=None, z0=0.0, scale=1.0, return_counts=False):
+        """The host mirror of simlod_query_summary on the octree this FULL export was taken from: the Summary of the samples
+        crop(region, max_level, select, footprint=footprint) returns (rule S0: the set is crop's by construction) — and, return_counts, the
+        SimlodQueryCounts record too.  Rules S1-S4 in numpy float64 and unsigned integers, in the order the header gives; the z histogram's
+        index is Paint.ramp_index (rule E3) with z0 and scale as float32."""
+        bins = Paint(abi.PAINT_RAMP, z0=z0, scale=scale)                    # (refuses what rule S8 refuses of z0 and scale)
+        ex, c = self.crop(Region() if region is None else region, max_level, select, return_counts=True, footprint=footprint)
+        smp = ex.samples
+        mn, size = _box_of(self.box_min, self.box_max)
+        rec = np.zeros((), dtype=abi.summary_dtype)
+        rec["numSamples"] = len(smp)
+        bits = [np.ascontiguousarray(smp[a]).view(np.uint32) for a in ("x", "y", "z")]
+        finite = np.ones(len(smp), bool)
+        inv = np.float64(abi.SUMMARY_CELLS) / size                          # rule S2: one IEEE division
+        c16 = []
+        for k, b in enumerate(bits):
+            finite &= (b & np.uint32(0x7F800000)) != np.uint32(0x7F800000)
+            # rule S1: the key's order over the coordinates that are no NaN
+            key = (b ^ np.where(b >> np.uint32(31) != 0, np.uint32(0xFFFFFFFF), np.uint32(0x80000000))).astype(np.uint32)
+            key = key[(b & np.uint32(0x7FFFFFFF)) <= np.uint32(0x7F800000)]
+            lo, hi = (int(key.min()), int(key.max())) if len(key) else (0xFF800000, 0x007FFFFF)
+            unkey = lambda v: v ^ (0x80000000 if v >> 31 else 0xFFFFFFFF)
+            rec["min"][k], rec["max"][k] = np.array([unkey(lo), unkey(hi)], np.uint32).view(np.float32)
+            # rule S2: the 20-bit cell, a NaN in cell 0
+            with np.errstate(invalid="ignore", over="ignore"):
+                t = (b.view(np.float32).astype(np.float64) - mn[k]) * inv
+                c20 = np.where(t >= np.float64(abi.SUMMARY_CELLS - 1), np.float64(abi.SUMMARY_CELLS - 1), np.where(t > 0.0, t, 0.0)).astype(np.uint64)
+            rec["sum"][k] = c20.sum(dtype=np.uint64)
+            c16.append(c20 >> np.uint64(4))
+        for j, (a, b) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+            rec["sum2"][j] = (c16[a] * c16[b]).sum(dtype=np.uint64)
+        rec["numNonFinite"] = int((~finite).sum())
+        rec["histZ"] = np.bincount(bins.ramp_index(smp["z"]), minlength=256).astype(np.uint64)
+        for k in range(4):
+            rec["histC"][k] = np.bincount((smp["color"] >> np.uint32(8 * k)) & np.uint32(255), minlength=256).astype(np.uint64)
+        out = Summary(rec, bins.z0, bins.scale)
+        return (out, c) if return_counts else out
 
     # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
     def profile(self, profile, region=None, max_level=None, select="all", return_counts=False, test_every_sample=False):
@@ -1151,6 +1194,17 @@ class Paint:
         """Rule E4: sample j of the query's order gets colors[j] (an undo, or colours computed elsewhere)."""
         return cls(abi.PAINT_ARRAY)
 
+    @classmethod
+    def ramp_from(cls, summary, colours, equalize=False):
+        """A RAMP paint over the bins `summary` (a Summary) was taken with — its z0 and scale —, so that a sample counted in histZ[i] gets
+        table[i].  colours: the palette, lowest height first, any number of words; spread evenly over the 256 bins, or, equalize, by the
+        cumulative distribution of the heights (Summary.equalized_table): every colour then covers about the same number of samples."""
+        pal = np.asarray(colours, dtype=np.uint32).reshape(-1)
+        if len(pal) == 0:
+            raise ValueError("a ramp needs a colour")
+        table = summary.equalized_table(pal) if equalize else pal[np.arange(256) * len(pal) // 256]
+        return cls(abi.PAINT_RAMP, z0=summary.z0, scale=summary.scale, table=table)
+
     def record(self):
         """The SimlodPaint the C ABI takes (abi.paint_dtype, one record)."""
         r = np.zeros(1, dtype=abi.paint_dtype)
@@ -1179,6 +1233,92 @@ class Paint:
         if self.mode == abi.PAINT_RAMP:
             return self.table[self.ramp_index(z)]
         raise ValueError("an ARRAY paint takes its colours from the caller")
+
+
+class Summary:
+    """The SimlodSummary record of one simlod_query_summary call (include/simlod_hip.h, "summary queries"; abi.summary_dtype) — from
+    DeviceOctree.summarize_region or its mirror OctreeExport.summarize — with the bins (z0, scale as float32) its z histogram was taken in.
+    Every field of the record is exact; what this class derives from it is floating point."""
+
+    def __init__(self, record, z0=0.0, scale=1.0):
+        self.record = np.array(record, dtype=abi.summary_dtype).reshape(())
+        self.z0, self.scale = np.float32(z0), np.float32(scale)
+
+    def __getitem__(self, name):
+        return self.record[name]
+
+    def __eq__(self, other):
+        return isinstance(other, Summary) and self.tobytes() == other.tobytes() and (self.z0, self.scale) == (other.z0, other.scale)
+
+    def tobytes(self):
+        return self.record.tobytes()
+
+    @property
+    def num_samples(self):
+        return int(self.record["numSamples"])
+
+    def extent(self):
+        """(min, max) per axis as float32[3] (rule S1); with no sample (+inf, -inf)."""
+        return self.record["min"].copy(), self.record["max"].copy()
+
+    def centroid(self, box_min, size):
+        """The mean position as float64[3], from the sums of the 20-bit cells (rule S2): each sample stands at the middle of its cell of
+        size / 2^20 of the box that starts at box_min.  No sample: ValueError."""
+        n = self.num_samples
+        if n == 0:
+            raise ValueError("no sample, no centroid")
+        cell = float(size) / abi.SUMMARY_CELLS
+        return np.array([float(box_min[k]) + (int(self.record["sum"][k]) / n + 0.5) * cell for k in range(3)], np.float64)
+
+    def covariance(self, size):
+        """The 3 x 3 covariance matrix of the positions as float64, from the sums of the products of the 16-bit cells (rule S2).  The
+        resolution is that of the 16-bit cell, size / 65536: a sample stands anywhere in its cell, and the mean of the 16-bit cells is taken
+        from the 20-bit sum (c16 = c20 >> 4), which is off by less than one 16-bit cell — so an entry is right to about one cell times the
+        selection's spread on those axes, and a selection thinner than a cell has no measurable variance on that axis.  No sample: ValueError."""
+        n = self.num_samples
+        if n == 0:
+            raise ValueError("no sample, no covariance")
+        cell = float(size) / 65536.0
+        mean = [int(self.record["sum"][k]) / (16.0 * n) for k in range(3)]
+        m = np.zeros((3, 3), np.float64)
+        for j, (a, b) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+            m[a, b] = m[b, a] = (int(self.record["sum2"][j]) / n - mean[a] * mean[b]) * cell * cell
+        return m
+
+    def ramp_range(self):
+        """(z0, scale) as float32 for the bins of a height ramp over this selection: the lowest z falls into bin 0 and the highest into bin
+        255 under rule E3 (scale is the float32 at or above 255 / (max z - min z) whose fp64 product reaches 255).  A selection of one height
+        gives (that height, 1).  No sample, or a z extent that is not finite: ValueError."""
+        lo, hi = np.float32(self.record["min"][2]), np.float32(self.record["max"][2])
+        if not (np.isfinite(lo) and np.isfinite(hi)) or hi < lo:
+            raise ValueError("the selection has no finite z extent")
+        if hi == lo:
+            return lo, np.float32(1.0)
+        span = np.float64(hi) - np.float64(lo)
+        with np.errstate(over="ignore"):
+            scale = np.float32(255.0 / span)
+            while np.isfinite(scale) and span * np.float64(scale) < 255.0:
+                scale = np.nextafter(scale, np.float32(np.inf))
+        if not np.isfinite(scale):
+            raise ValueError("the z extent is too small for a float32 scale")
+        return lo, scale
+
+    def equalized_table(self, colours):
+        """256 colour words from the palette `colours` (lowest height first), bin i taking the colour at the place its samples hold in
+        histZ's cumulative distribution — the middle of the bin: index ((2 * samples below + histZ[i]) * len(colours)) // (2 * numSamples), in
+        integers.  The index never falls from one bin to the next.  No sample: the palette spread evenly."""
+        pal = np.asarray(colours, dtype=np.uint32).reshape(-1)
+        if len(pal) == 0:
+            raise ValueError("a ramp needs a colour")
+        h = [int(v) for v in self.record["histZ"]]
+        n = sum(h)
+        if n == 0:
+            return pal[np.arange(256) * len(pal) // 256]
+        idx, below = [], 0
+        for v in h:
+            idx.append(min(len(pal) - 1, ((2 * below + v) * len(pal)) // (2 * n)))
+            below += v
+        return pal[np.asarray(idx, np.int64)]
 
 
 class Footprint:

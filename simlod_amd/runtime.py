@@ -102,6 +102,9 @@ def lib():
         L.simlod_paint_buffer_min_bytes.restype = u64
         L.simlod_paint_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_paint_region.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, u32, vp, vp, u64, vp, vp]
+        L.simlod_summary_buffer_min_bytes.restype = u64
+        L.simlod_summary_buffer_min_bytes.argtypes = [u32, u64]
+        L.simlod_query_summary.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, vp, vp]
         L.simlod_profile_buffer_min_bytes.restype = u64
         L.simlod_profile_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_query_profile.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp, vp]
@@ -143,6 +146,7 @@ EXPORTED_SYMBOLS = [
     "simlod_decode_las_styled", "simlod_profile_buffer_min_bytes", "simlod_query_profile",
     "simlod_pack_buffer_min_bytes", "simlod_pack_samples", "simlod_unpack_samples",
     "simlod_paint_buffer_min_bytes", "simlod_paint_region",
+    "simlod_summary_buffer_min_bytes", "simlod_query_summary",
 ]
 
 
@@ -769,6 +773,33 @@ class DeviceOctree:
         if int(c["error"]) != 0:
             raise SimlodError(f"simlod_paint_region reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples); nothing was painted")
         return (c, prev[: int(c["numSamples"])]) if return_previous else c
+
+    # -- summary queries (include/simlod_hip.h, "summary queries") -------------------------------------------------------------------------
+    def summarize_region(self, uniforms, region, max_level=None, select="cut", footprint=None, z0=0.0, scale=1.0, max_workgroups=0):
+        """What query_region(region, max_level, select, footprint=footprint) would return, summarised on the device by one simlod_query_summary
+        call instead of copied out: an octree_io.Summary — the number of samples, their extent, the sums behind centroid and covariance, the
+        histogram of their heights in the bins of a ramp paint with (z0, scale), and the histograms of the four colour bytes.  The octree is
+        only read.  max_workgroups: 0, or a limit for the reduction's grid (the result does not depend on it).  Raises SimlodError when the
+        device reports an error; then no summary was written."""
+        from .octree_io import Region, Summary
+        u, up = self._u(uniforms)
+        sel, ml, nn, bound = self._query_setup(max_level, select)
+        r = (Region() if region is None else region).record()
+        f = None if footprint is None else footprint.record()
+        pr = np.zeros(1, dtype=abi.summary_params_dtype)
+        pr["z0"], pr["scale"], pr["maxWorkgroups"] = z0, scale, int(max_workgroups)
+        table = self._table(nn)
+        counts = torch.zeros(abi.query_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        out = torch.zeros(abi.summary_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        scratch = self._export_scratch(int(self.L.simlod_summary_buffer_min_bytes(nn, bound)))
+        _check(self.L.simlod_query_summary(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data),
+                                           None if f is None else ctypes.c_void_p(f.ctypes.data), ctypes.c_void_p(pr.ctypes.data), ml, sel, self._p(scratch),
+                                           ctypes.c_uint64(scratch.numel()), self._p(table), nn, self._p(out), self._p(counts), self._stream()),
+               "simlod_query_summary")
+        c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
+        if int(c["error"]) != 0:
+            raise SimlodError(f"simlod_query_summary reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples); no summary was written")
+        return Summary(out.cpu().numpy().view(abi.summary_dtype)[0], pr["z0"][0], pr["scale"][0])
 
     # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
     def _profile(self, uniforms, profile, region, ml, sel, table, samples, records, sample_capacity, bound):

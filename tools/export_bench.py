@@ -30,7 +30,12 @@ copy of 8 against 16 bytes per sample into page-locked memory.
 --paint: instead, simlod_paint_region on the same octree — the whole box, half the terrain and the city block of --region, each as SET without
 arrays, BLEND and SET with `previous`; every paint alternates rep by rep with simlod_query_region ALL@20 of the same region (with samples) and
 the device-to-device copy (paint, copy, query, copy: both calls start behind the copy); the ratio to the query (expected <= 1.10) and the share
-of the copy rate by algorithmic bytes.  --paint-only REGION:MODE: that case alone."""
+of the copy rate by algorithmic bytes.  --paint-only REGION:MODE: that case alone.
+--summary: instead, simlod_query_summary ALL@20 on the same octree — the whole box, half the terrain and the city block of --region; every
+summary alternates rep by rep with simlod_query_region ALL@20 of the same region with samples, its count-only call and the device-to-device
+copy (each call starts behind the copy); the ratio to the query (the purpose bound: <= 1), the cost over the count-only call and the share of
+the copy rate by algorithmic bytes (the selected samples once, plus the table); the whole box again with smaller grids, and once more
+after a SET paint of everything (one colour: every lane of a wave on one bin).  --summary-only REGION: that case alone."""
 import argparse
 import ctypes
 import json
@@ -222,6 +227,80 @@ def paint_bench(dev, u, box, st, reps, only=None):
                                "numSamples": painted, "numCandidates": cand, "candidates_in_filtered_nodes": cand_filtered, "nodes_copied": int(c["numCopiedNodes"]),
                                "nodes_filtered": int(c["numFilteredNodes"]), "algorithmic_bytes": nbytes, "GBs": round(gbs, 1), "frac_of_copy": round(gbs / copy_gbs, 4),
                                "query_algorithmic_bytes": qbytes, "query_frac_of_copy": round(qbytes / (t_query[0] * 1e6) / copy_gbs, 4)}
+    print(json.dumps(out))
+
+
+def summary_bench(dev, u, box, st, reps, only=None):
+    from simlod_amd import fingerprint
+    from simlod_amd.octree_io import Paint, Region
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    need = max(int(L.simlod_summary_buffer_min_bytes(nn, bound)), int(L.simlod_paint_buffer_min_bytes(nn, bound)))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    table = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    samples = torch.empty(bound * 16, dtype=torch.uint8, device=dev.device)
+    counts = torch.zeros(32, dtype=torch.uint8, device=dev.device)
+    record = torch.zeros(abi.summary_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+    uu, up = dev._u(u)
+    b = np.asarray(box, dtype=np.float64)
+    n = np.array([0.6, 0.8, 0.1])
+    regions = {"whole_box": Region(), "half_terrain": Region.from_planes([[*n, -float(n @ (b / 2))]]),
+               "city_block": Region.from_box((0.45 * b[0], 0.45 * b[1], -1.0), (0.55 * b[0], 0.55 * b[1], b[2] + 1.0))}
+    records = {k: r.record() for k, r in regions.items()}
+    params = {}
+    for wg in (0, 256, 512):
+        params[wg] = np.zeros(1, dtype=abi.summary_params_dtype)
+        params[wg]["z0"], params[wg]["scale"], params[wg]["maxWorkgroups"] = 0.0, 256.0 / b[2], wg
+
+    def summary(kind, wg=0):
+        rc = L.simlod_query_summary(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(records[kind].ctypes.data), None, ctypes.c_void_p(params[wg].ctypes.data), 20,
+                                    abi.EXPORT_ALL, p(scratch), ctypes.c_uint64(need), p(table), nn, p(record), p(counts), stream)
+        assert rc == 0
+
+    def query(kind, count_only=False):
+        rc = L.simlod_query_region(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(records[kind].ctypes.data), 20, abi.EXPORT_ALL, p(scratch),
+                                   ctypes.c_uint64(need), p(table), nn, None if count_only else p(samples), ctypes.c_uint64(bound), p(counts), stream)
+        assert rc == 0
+
+    copy_dst = torch.empty(int(st["numPoints"]) * 16, dtype=torch.uint8, device=dev.device)
+    copy_src = samples[: copy_dst.numel()]
+    copy = lambda: copy_dst.copy_(copy_src)
+    out = {"points": int(st["numPoints"]), "numNodes": nn, "numSamples": bound, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(),
+           "lib": os.environ.get("SIMLOD_HIP_LIB", "product"), "bound": "t_summary <= t_query (with samples) of the same run", "target": ">= 50 % of the copy rate"}
+
+    def row(kind):
+        # summary, copy, query, copy, count-only, copy: every call runs behind the 1.1 GB copy, which leaves neither the nodes nor the region's
+        # chunks in the caches
+        t_sum, t_copy, t_query, _, t_count, _ = timed_alternating([lambda: summary(kind), copy, lambda: query(kind), copy, lambda: query(kind, True), copy], reps)
+        summary(kind)
+        torch.cuda.synchronize()
+        c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
+        r = record.cpu().numpy().view(abi.summary_dtype)[0]
+        assert int(c["error"]) == 0 and int(r["numSamples"]) == int(c["numSamples"]) == int(r["histZ"].sum())
+        copy_gbs = 2 * copy_dst.numel() / (t_copy[0] * 1e6)
+        nbytes = int(c["numSamples"]) * 16 + int(c["numNodes"]) * 40
+        gbs = nbytes / (t_sum[0] * 1e6)
+        return {"ms": round(t_sum[0], 4), "ms_min": round(t_sum[1], 4), "query_all20_ms": round(t_query[0], 4), "count_only_ms": round(t_count[0], 4),
+                "new_kernels_ms": round(t_sum[0] - t_count[0], 4), "d2d_copy_ms": round(t_copy[0], 4), "d2d_copy_GBs": round(copy_gbs, 1),
+                "over_query": round(t_sum[0] / t_query[0], 4), "bound_held": bool(t_sum[0] <= t_query[0]), "numSamples": int(c["numSamples"]),
+                "numCandidates": int(c["numCandidates"]), "nodes_copied": int(c["numCopiedNodes"]), "nodes_filtered": int(c["numFilteredNodes"]),
+                "algorithmic_bytes": nbytes, "GBs": round(gbs, 1), "frac_of_copy": round(gbs / copy_gbs, 4), "target_held": bool(gbs / copy_gbs >= 0.5),
+                "bins_used": {"histZ": int((r["histZ"] > 0).sum()), "histC": [int((h > 0).sum()) for h in r["histC"]]}}
+
+    for kind in regions:
+        if only is None or only == kind:
+            out[kind] = row(kind)
+    if only is None:
+        grids = [256, 512, 0]
+        t = timed_alternating([f for wg in grids for f in ((lambda wg=wg: summary("whole_box", wg)), copy)], reps)
+        out["whole_box_by_grid_ms"] = {str(wg) if wg else "library": round(t[2 * k][0], 4) for k, wg in enumerate(grids)}
+    if only is None or only == "whole_box_one_colour":
+        rec = Paint.set(0xFF2060E0).record()
+        rc = L.simlod_paint_region(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(records["whole_box"].ctypes.data), None, ctypes.c_void_p(rec.ctypes.data), p(scratch),
+                                   ctypes.c_uint64(need), p(table), nn, None, None, ctypes.c_uint64(0), p(counts), stream)
+        assert rc == 0
+        params[0]["z0"], params[0]["scale"] = -1000.0, 1000.0            # every height in bin 255
+        out["whole_box_one_colour"] = row("whole_box")
     print(json.dumps(out))
 
 
@@ -757,6 +836,8 @@ def main():
     ap.add_argument("--pack", action="store_true", help="time simlod_pack_samples / simlod_unpack_samples of the CUT@20 export beside the copy of its samples instead")
     ap.add_argument("--paint", action="store_true", help="time simlod_paint_region (whole box, half the terrain, a city block; SET, BLEND, SET with previous) beside the ALL@20 region query instead")
     ap.add_argument("--paint-only", default=None, metavar="REGION:MODE", help="--paint: this case alone, e.g. city_block:set (a per-kernel trace of one case)")
+    ap.add_argument("--summary", action="store_true", help="time simlod_query_summary (whole box, half the terrain, a city block; the whole box in one colour) beside the ALL@20 region query and its count-only call instead")
+    ap.add_argument("--summary-only", default=None, metavar="REGION", help="--summary: this case alone, e.g. whole_box or whole_box_one_colour (a per-kernel trace of one case)")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
     pts, box = synthetic.terrain(n_points, seed=7)
@@ -793,6 +874,8 @@ def main():
         return pack_bench(dev, u, box, st, args.reps)
     if args.paint:
         return paint_bench(dev, u, box, st, args.reps, args.paint_only)
+    if args.summary:
+        return summary_bench(dev, u, box, st, args.reps, args.summary_only)
     L = dev.L
     need = int(L.simlod_export_buffer_min_bytes(nn, ns))
     scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
