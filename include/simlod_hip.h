@@ -547,7 +547,8 @@ int simlod_set_clip(const SimlodClip* clip);   /* the default context */
  * not be convex.  Everything the region section says stays in force: the box, the inflated cube lo_a / hi_a of rule 1, the listing and
  * selection rules, rule 5's count-only calls and capacities, SimlodQueryCounts, SIMLOD_EXPORT_REGION, the chunk-table / `next` sources.  The
  * footprint composes with the region's half-spaces (polygon, height band and frustum in one call), and the result is an ordinary table.
- * NOT COVERED: perspective lassos (u = x_clip / w); an affine map covers plan-view outlines and any orthographic view.
+ * An affine map covers plan-view outlines and any orthographic view; a polygon on the screen of a perspective camera (u = x_clip / w) is a
+ * lasso: see "lasso queries" below.
  *
  * All new geometry is fp64 computed from the fp32 inputs without fused multiply-add, every sum in the order written here; there is no division.
  *  F1. Sample rule.  u = ((ux*x + uy*y) + uz*z) + u0 and v likewise from axisU / axisV.  For each edge i from a = P[i] to b = P[(i+1) mod n]:
@@ -804,6 +805,80 @@ int simlod_query_summary(const SimlodNode* nodes, const SimlodStats* stats, cons
                          const SimlodFootprint* footprint /*or NULL*/, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select,
                          void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary /*device*/,
                          SimlodQueryCounts* counts, void* stream);
+
+/* ---- lasso queries: select, paint and summarise by a polygon on the screen of a perspective camera ---------------------------------------------
+ * simlod_query_lasso is simlod_query_region plus a lasso: a polygon of up to 256 vertices on a screen the points are mapped onto by a PROJECTIVE
+ * map — three rows U, V, W of a 4 x 4 matrix, the screen position being (U/W, V/W) where W > 0 (in front of the eye).  It is the selection a user
+ * draws with the mouse in a 3-D view; simlod_paint_lasso and simlod_query_summary_lasso are "select, then mark" and "what is this selection" for
+ * it.  The polygon need not be convex.  Everything the region section says stays in force: the box, the inflated cube lo_a / hi_a of rule 1, the
+ * listing and selection rules, rule 5's count-only calls and capacities, SimlodQueryCounts, SIMLOD_EXPORT_REGION, the chunk-table / `next`
+ * sources.  The lasso composes with the region's half-spaces (a frustum, a height slab), and the result is an ordinary table.
+ * NOT COVERED: a lasso on profile queries, clip regions, view queries and deltas; a lasso and a footprint in one call.
+ *
+ * All new geometry is fp64 computed from the fp32 inputs without fused multiply-add, every sum in the order written here; there is NO DIVISION:
+ * the even-odd rule on the screen is multiplied through by W > 0.
+ *  L1. Sample rule.  U = ((ux*x + uy*y) + uz*z) + u0 from rowU, V and W likewise from rowV / rowW.  The sample fails unless W > 0 (a NaN fails).
+ *      For each edge i from a = P[i] to b = P[(i+1) mod n]: du = b_u - a_u, dv = b_v - a_v, sa = a_v*W, sb = b_v*W,
+ *      c = du*(V - sa) - dv*(U - a_u*W); the edge is crossed iff (sa > V) != (sb > V) and (c > 0) == (dv > 0).  The sample passes the lasso iff the
+ *      number of crossed edges is odd (the even-odd rule, as footprint rule F1: self-intersecting polygons are defined, a polygon of zero area
+ *      passes nothing off its own line).  Edge i's sb and edge i+1's sa are the same product, so the rule is watertight at vertices.  A sample
+ *      passes the query iff it passes L1 and region rule 3.
+ *  L2. Corners.  The eight corners of a node's inflated cube are numbered k = 0..7 with bit 0 for x, bit 1 for y and bit 2 for z, each choosing
+ *      hi_a over lo_a; (U_k, V_k, W_k) by L1's formulas at corner k.  fp64 rounding is monotone and the eight corners include the extreme one of
+ *      every row, so a node with W_k <= 0 at all eight holds no passing sample and a node with W_k > 0 at all eight has W > 0 at every sample, in
+ *      floating point and not only in exact arithmetic.
+ *  L3. Far edges, for a node with W_k > 0 at all eight corners.  Edge i is FAR iff c by L1's formula at (U_k, V_k, W_k) is > 0 at all eight
+ *      corners or < 0 at all eight, or sa > V and sb > V at all eight, or neither sa > V nor sb > V at any of the eight (each of these quantities
+ *      is affine in (x, y, z): its sign on the cube is its sign at the corners).  Any other edge is NEAR.
+ *  L4. Node class by the lasso.  OUTSIDE if W_k <= 0 at all eight corners.  FILTERED if the signs of W are mixed or there is a NEAR edge.
+ *      Otherwise L1's verdict at corner 0: COPIED if it passes, else OUTSIDE.  The final class combines with the planes' exactly as rule F4 does:
+ *      OUTSIDE if outside by either, COPIED iff copied by both, else FILTERED.
+ *  L5. For finite samples in the half-open box L2-L4 change nothing against L1 applied to every sample — provided no corner value lies within
+ *      fp64 rounding of zero with the wrong exact sign (an edge's plane through the eye grazing a node's corner).  The host mirror asserts this
+ *      per query.
+ *  L6. lasso == NULL gives exactly simlod_query_region / the footprint-less simlod_paint_region / the footprint-less simlod_query_summary, byte
+ *      for byte.  `region` is required and may have zero planes.
+ *  L7. hipErrorInvalidValue with nothing enqueued: everything simlod_query_region refuses, numVertices outside 3..256, a non-finite vertex or
+ *      row coefficient, nonzero `reserved`, scratchBytes below the call's own minimum (simlod_lasso_buffer_min_bytes(tableCapacity, 0),
+ *      simlod_paint_buffer_min_bytes, simlod_summary_buffer_min_bytes).  A row W of zeros is legal and selects nothing; a vertex behind
+ *      numVertices is not looked at.
+ * For a camera with the row-major world-view-projection matrix M (Uniforms.transform) and a width x height screen whose pixel (i, j) covers ndc
+ * [2i/width - 1, 2(i+1)/width - 1]: rowU = width/2 * (M[0] + M[3]), rowV = height/2 * (M[1] + M[3]), rowW = M[3], vertices in pixels. */
+#define SIMLOD_LASSO_MAX_VERTICES 256u
+typedef struct SimlodLasso {           /* host memory, read before the call returns */
+	uint32_t numVertices;              /* 3..256; the polygon closes from the last vertex to the first */
+	uint32_t reserved[3];              /* 0 */
+	float    rowU[4], rowV[4], rowW[4];   /* U = ((ux*x + uy*y) + uz*z) + u0, V and W likewise: screen position (U/W, V/W) where W > 0 */
+	float    vertices[SIMLOD_LASSO_MAX_VERTICES][2];   /* (u, v) on that screen */
+} SimlodLasso;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodLasso) == 2112, "Lasso");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodLasso, rowU) == 16, "Lasso.rowU");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodLasso, rowV) == 32, "Lasso.rowV");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodLasso, rowW) == 48, "Lasso.rowW");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodLasso, vertices) == 64, "Lasso.vertices");
+
+/* simlod_footprint_buffer_min_bytes' value: simlod_query_buffer_min_bytes plus the fixed block for the polygon widened to fp64 (8 KB). */
+uint64_t simlod_lasso_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+
+/* The lasso query (rules above; arguments as simlod_query_footprint's).  Asynchronous on `stream` once `lasso` has been read. */
+int simlod_query_lasso(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                       const SimlodLasso* lasso /*or NULL*/, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                       SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts,
+                       void* stream);
+
+/* simlod_paint_region with a lasso in the footprint's place: rules E0-E9 with "the samples simlod_query_lasso(region, lasso, maxLevel = 20,
+ * SIMLOD_EXPORT_ALL) returns" as the target set and order.  The scratch minimum is simlod_paint_buffer_min_bytes. */
+int simlod_paint_lasso(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                       const SimlodLasso* lasso /*or NULL*/, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes,
+                       SimlodExportNode* table, uint32_t tableCapacity, const uint32_t* colors /*ARRAY only*/, uint32_t* previous /*or NULL*/,
+                       uint64_t colorCapacity, SimlodQueryCounts* counts, void* stream);
+
+/* simlod_query_summary with a lasso in the footprint's place: rules S0-S8 with "the samples simlod_query_lasso(region, lasso, maxLevel, select)
+ * returns" as the set.  The scratch minimum is simlod_summary_buffer_min_bytes. */
+int simlod_query_summary_lasso(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                               const SimlodLasso* lasso /*or NULL*/, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select,
+                               void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
+                               SimlodSummary* summary /*device*/, SimlodQueryCounts* counts, void* stream);
 
 /* ---- ray queries: the first sample in a cone along each ray of a batch ----------------------------------------------------------------------
  * simlod_query_rays answers "what does this ray hit" for up to 2^20 rays at once: per ray the sample with the smallest parameter t that lies

@@ -210,6 +210,13 @@ summary_dtype = np.dtype({"names": ["numSamples", "numNonFinite", "min", "max", 
                           "offsets": [0, 8, 16, 28, 40, 64, 112, 2160], "itemsize": 10352})
 assert summary_params_dtype.itemsize == 16 and summary_dtype.itemsize == 10352
 
+# ---- lasso queries (include/simlod_hip.h, "lasso queries") -------------------------------------------------------------------------------
+LASSO_MAX_VERTICES = 256
+lasso_dtype = np.dtype({"names": ["numVertices", "reserved", "rowU", "rowV", "rowW", "vertices"],
+                        "formats": ["<u4", ("<u4", 3), ("<f4", 4), ("<f4", 4), ("<f4", 4), ("<f4", (LASSO_MAX_VERTICES, 2))],
+                        "offsets": [0, 4, 16, 32, 48, 64], "itemsize": 2112})
+assert lasso_dtype.itemsize == 2112
+
 # ---- profile queries (include/simlod_hip.h, "profile queries") --------------------------------------------------------------------------
 PROFILE_MAX_VERTICES = 64
 PROFILE_NO_SEGMENT = 0xFFFFFFFF

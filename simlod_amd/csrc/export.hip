@@ -22,6 +22,9 @@
 // chunks, in export_paint.inc; the rules in paint_rules.hpp.
 // Summary (simlod_query_summary): that sequence as a count-only call, then k_s_partial / k_fs_partial and k_s_final, which reduce the selected
 // samples to one SimlodSummary record, in export_summary.inc; the rules in summary_rules.hpp.
+// Lasso query, paint and summary (simlod_query_lasso, simlod_paint_lasso, simlod_query_summary_lasso): the footprint's sequences with a polygon on
+// the screen of a perspective camera in the extruded polygon's place — k_l_hier, k_l_count, k_l_write, k_el_paint, k_ls_partial — in
+// export_lasso.inc; the rules themselves in lasso_rules.hpp.
 // Profile query (simlod_query_profile): k_pr_hier -> k_q_dir -> k_pr_count -> k_q_scan -> k_pr_write, the same sequence with a corridor along a
 // polyline on top of the planes and a record per returned sample, in export_profile.inc; the rules themselves in profile_rules.hpp.
 // View query (simlod_query_view): k_v_hier -> k_v_scan -> k_x_dir -> k_copy, the export's sequence with the camera's rules in the walk, in
@@ -51,6 +54,7 @@
 #include "pack_rules.hpp"
 #include "paint_rules.hpp"
 #include "summary_rules.hpp"
+#include "lasso_rules.hpp"
 
 namespace simlod {
 namespace {
@@ -62,6 +66,7 @@ namespace {
 #include "export_footprint.inc"  // FootEdge, FootGeom, FootArgs, stage_edges, Footprint, classify_footprint, k_f_hier, k_f_count, k_f_write
 #include "export_paint.inc"    // PaintOp, PaintArgs, FootPaintArgs, paint_colour, e_paint, k_e_paint, k_ef_paint
 #include "export_summary.inc"  // SummaryPart, SummaryOp, SummaryArgs, FootSummaryArgs, hist_add, s_partial, k_s_partial, k_fs_partial, k_s_final
+#include "export_lasso.inc"    // LassoGeom, LassoArgs, LassoPaintArgs, LassoSummaryArgs, Lasso, k_l_hier, k_l_count, k_l_write, k_el_paint, k_ls_partial
 #include "export_profile.inc"  // ProfGeom, ProfArgs, stage_segments, Profile, k_pr_hier, k_pr_count, locate_record, k_pr_write
 #include "export_view.inc"     // ViewArgs, k_v_hier, k_v_scan
 #include "export_delta.inc"    // DeltaLayout, DeltaArgs, k_d_match, k_d_scan, k_d_dir, k_d_drop, MergeArgs, k_d_merge_scan, k_d_merge_dir
@@ -144,31 +149,36 @@ int prepare_query(Context& ctx, const SimlodNode* nodes, const SimlodStats* stat
 	return 0;
 }
 
-}  // namespace
+// The selection every call of the family starts with, on `stream`: hier -> k_q_dir -> count -> k_q_scan.  `k_hier` and `k_count` are the region
+// query's, the footprint's or the lasso's and take `args`; k_q_dir and k_q_scan take the QueryArgs `q` in it.  (A macro: SIMLOD_LAUNCH names
+// the kernel it launches.)
+#define SIMLOD_LAUNCH_SELECTION(k_hier, k_count, args, q, tableCapacity, grid, stream)                                           \
+	do {                                                                                                                         \
+		constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE; /* k_q_dir: one wave per table entry */                                \
+		SIMLOD_LAUNCH(k_hier, dim3(1), dim3(WG_TPB), stream, args);                                                              \
+		if ((tableCapacity) != 0u) SIMLOD_LAUNCH(k_q_dir, dim3(((tableCapacity) + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q); \
+		SIMLOD_LAUNCH(k_count, dim3(grid), dim3(LANE_TPB), stream, args);                                                        \
+		SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);                                                               \
+	} while (0)
 
-int launch_query(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region, uint32_t maxLevel,
-                 uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
-                 uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
-	QueryArgs q{};
-	const int rc = prepare_query(ctx, nodes, stats, u, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples, sampleCapacity, counts, 0u, q);
-	if (rc != 0) return rc;
-	const uint32_t grid = copy_grid(q.x.lay.itemCap);
-	SIMLOD_LAUNCH(k_q_hier, dim3(1), dim3(WG_TPB), stream, q);
-	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                        // k_q_dir: one wave per table entry
-	if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
-	SIMLOD_LAUNCH(k_q_count, dim3(grid), dim3(LANE_TPB), stream, q);
-	SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);
-	if (samples != nullptr) SIMLOD_LAUNCH(k_q_write, dim3(grid), dim3(LANE_TPB), stream, q);
-	if (profile_enabled()) profile_close(stream);
-	return (int)hipGetLastError();
-}
-
-uint64_t footprint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return query_min_bytes(nodeCapacity, sampleBound) + FOOT_BLOCK_BYTES; }
-
-namespace {
+// A polygon on top of the planes — a footprint's or a lasso's: its edges widened to fp64 on the host, and where they go.  Both kinds use
+// FootEdge's layout and the same 8 KB block of the scratch buffer, filled by the same copy on the caller's stream.
+struct PolygonEdges {
+	union {
+		FootEdge  foot[SIMLOD_FOOTPRINT_MAX_VERTICES];
+		LassoEdge lasso[SIMLOD_LASSO_MAX_VERTICES];
+	};
+	uint32_t n = 0u;
+	// into the block that starts `front` bytes in front of the items -> its offset in the scratch buffer
+	// (pageable host memory: the runtime has read the edges when the call returns)
+	hipError_t upload(const QueryArgs& q, uint64_t front, hipStream_t stream, uint64_t& offset) const {
+		offset = q.x.lay.items - front;
+		return hipMemcpyAsync(q.x.scratch + offset, foot, (size_t)n * sizeof(FootEdge), hipMemcpyHostToDevice, stream);
+	}
+};
 
 // Rule F7's refusals of the footprint itself (false), else its axes and its edges widened to fp64.
-bool footprint_edges(const SimlodFootprint* fp, FootGeom& f, FootEdge (&edges)[SIMLOD_FOOTPRINT_MAX_VERTICES]) {
+bool footprint_edges(const SimlodFootprint* fp, FootGeom& f, PolygonEdges& pe) {
 	if (fp == nullptr || fp->numVertices < 3u || fp->numVertices > SIMLOD_FOOTPRINT_MAX_VERTICES) return false;
 	if (fp->reserved[0] != 0u || fp->reserved[1] != 0u || fp->reserved[2] != 0u) return false;
 	const uint32_t n = fp->numVertices;
@@ -180,12 +190,36 @@ bool footprint_edges(const SimlodFootprint* fp, FootGeom& f, FootEdge (&edges)[S
 		if (!std::isfinite(fp->vertices[i][0]) || !std::isfinite(fp->vertices[i][1])) return false;
 		const uint32_t j = i + 1u == n ? 0u : i + 1u;
 		const double au = (double)fp->vertices[i][0], av = (double)fp->vertices[i][1];
-		edges[i] = FootEdge{au, av, (double)fp->vertices[j][0] - au, (double)fp->vertices[j][1] - av};
+		pe.foot[i] = FootEdge{au, av, (double)fp->vertices[j][0] - au, (double)fp->vertices[j][1] - av};
 	}
+	f.n = pe.n = n;
+	return true;
+}
+
+// Rule L7's refusals of the lasso itself (false), else its rows and its edges widened to fp64 (lasso_rules.hpp).
+bool lasso_edges(const SimlodLasso* ls, LassoGeom& l, PolygonEdges& pe) {
+	if (ls == nullptr || !lasso_acceptable(*ls)) return false;
+	lasso_widen(*ls, l.rows, pe.lasso);
+	l.n = pe.n = ls->numVertices;
 	return true;
 }
 
 }  // namespace
+
+int launch_query(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region, uint32_t maxLevel,
+                 uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples,
+                 uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
+	QueryArgs q{};
+	const int rc = prepare_query(ctx, nodes, stats, u, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples, sampleCapacity, counts, 0u, q);
+	if (rc != 0) return rc;
+	const uint32_t grid = copy_grid(q.x.lay.itemCap);
+	SIMLOD_LAUNCH_SELECTION(k_q_hier, k_q_count, q, q, tableCapacity, grid, stream);
+	if (samples != nullptr) SIMLOD_LAUNCH(k_q_write, dim3(grid), dim3(LANE_TPB), stream, q);
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+uint64_t footprint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return query_min_bytes(nodeCapacity, sampleBound) + FOOT_BLOCK_BYTES; }
 
 // simlod_query_footprint with a footprint (without one the entry point forwards to launch_query): the polygon, widened to fp64 edges, goes into
 // the scratch buffer's block in front of the items by a copy on `stream`; then the region query's sequence with k_f_hier / k_f_count / k_f_write.
@@ -193,24 +227,38 @@ int launch_footprint(Context& ctx, const SimlodNode* nodes, const SimlodStats* s
                      const SimlodFootprint* fp, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
                      uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
 	FootArgs fa{};
-	FootEdge edges[SIMLOD_FOOTPRINT_MAX_VERTICES];
-	if (!footprint_edges(fp, fa.f, edges)) return (int)hipErrorInvalidValue;
-	const uint32_t n = fp->numVertices;
+	PolygonEdges pe;
+	if (!footprint_edges(fp, fa.f, pe)) return (int)hipErrorInvalidValue;
 	const int rc = prepare_query(ctx, nodes, stats, u, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples, sampleCapacity, counts,
 	                             FOOT_BLOCK_BYTES, fa.q);
 	if (rc != 0) return rc;
-	fa.f.n = n;
-	fa.f.edges = fa.q.x.lay.items - FOOT_BLOCK_BYTES;
-	// (pageable host memory: the runtime has read `edges` when the call returns)
-	const hipError_t e = hipMemcpyAsync(fa.q.x.scratch + fa.f.edges, edges, (size_t)n * sizeof(FootEdge), hipMemcpyHostToDevice, stream);
+	const hipError_t e = pe.upload(fa.q, FOOT_BLOCK_BYTES, stream, fa.f.edges);
 	if (e != hipSuccess) return (int)e;
 	const uint32_t grid = copy_grid(fa.q.x.lay.itemCap);
-	SIMLOD_LAUNCH(k_f_hier, dim3(1), dim3(WG_TPB), stream, fa);
-	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                        // k_q_dir: one wave per table entry
-	if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, fa.q);
-	SIMLOD_LAUNCH(k_f_count, dim3(grid), dim3(LANE_TPB), stream, fa);
-	SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, fa.q);
+	SIMLOD_LAUNCH_SELECTION(k_f_hier, k_f_count, fa, fa.q, tableCapacity, grid, stream);
 	if (samples != nullptr) SIMLOD_LAUNCH(k_f_write, dim3(grid), dim3(LANE_TPB), stream, fa);
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+// simlod_query_lasso with a lasso (without one the entry point forwards to launch_query): launch_footprint with the lasso's rows and kernels; the
+// polygon lies in the same block.
+uint64_t lasso_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return footprint_min_bytes(nodeCapacity, sampleBound); }
+
+int launch_lasso(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
+                 const SimlodLasso* lasso, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
+                 uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
+	LassoArgs la{};
+	PolygonEdges pe;
+	if (!lasso_edges(lasso, la.l, pe)) return (int)hipErrorInvalidValue;
+	const int rc = prepare_query(ctx, nodes, stats, u, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples, sampleCapacity, counts,
+	                             FOOT_BLOCK_BYTES, la.q);
+	if (rc != 0) return rc;
+	const hipError_t e = pe.upload(la.q, FOOT_BLOCK_BYTES, stream, la.l.edges);
+	if (e != hipSuccess) return (int)e;
+	const uint32_t grid = copy_grid(la.q.x.lay.itemCap);
+	SIMLOD_LAUNCH_SELECTION(k_l_hier, k_l_count, la, la.q, tableCapacity, grid, stream);
+	if (samples != nullptr) SIMLOD_LAUNCH(k_l_write, dim3(grid), dim3(LANE_TPB), stream, la);
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();
 }
@@ -219,48 +267,49 @@ constexpr uint64_t PAINT_BLOCK_BYTES = 256u * sizeof(uint32_t);                 
 
 uint64_t paint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return footprint_min_bytes(nodeCapacity, sampleBound) + PAINT_BLOCK_BYTES; }
 
-// simlod_paint_region: the footprint query's launches as a count-only call (maxLevel 20, every node selected), the polygon and the ramp's table
-// in the scratch buffer's blocks in front of the items, then k_e_paint (fp == nullptr) or k_ef_paint.
+// simlod_paint_region / simlod_paint_lasso: the footprint's or the lasso's launches as a count-only call (maxLevel 20, every node selected), the
+// polygon and the ramp's table in the scratch buffer's blocks in front of the items, then k_e_paint (no polygon), k_ef_paint or k_el_paint.
+// At most one of `fp` and `lasso`.
 int launch_paint(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
-                 const SimlodFootprint* fp, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
-                 const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
-	if (paint == nullptr || !paint_acceptable(*paint, colors != nullptr)) return (int)hipErrorInvalidValue;
-	FootPaintArgs fa{};
-	FootEdge edges[SIMLOD_FOOTPRINT_MAX_VERTICES];
-	if (fp != nullptr && !footprint_edges(fp, fa.f.f, edges)) return (int)hipErrorInvalidValue;
+                 const SimlodFootprint* fp, const SimlodLasso* lasso, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
+                 uint32_t tableCapacity, const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
+	if (paint == nullptr || !paint_acceptable(*paint, colors != nullptr) || (fp != nullptr && lasso != nullptr)) return (int)hipErrorInvalidValue;
+	FootGeom fg{};
+	LassoGeom lg{};
+	PolygonEdges pe;
+	if (fp != nullptr && !footprint_edges(fp, fg, pe)) return (int)hipErrorInvalidValue;
+	if (lasso != nullptr && !lasso_edges(lasso, lg, pe)) return (int)hipErrorInvalidValue;
 	constexpr uint64_t front = FOOT_BLOCK_BYTES + PAINT_BLOCK_BYTES;
-	QueryArgs& q = fa.f.q;
+	QueryArgs q{};
 	const int rc = prepare_query(ctx, nodes, stats, u, region, SIMLOD_MAX_DEPTH, SIMLOD_EXPORT_ALL, scratch, scratchBytes, table, tableCapacity, nullptr, 0u,
 	                             counts, front, q);
 	if (rc != 0) return rc;
-	PaintOp& p = fa.p;
+	PaintOp p{};
 	p.mode = paint->mode; p.color = paint->color; p.strength = paint->strength; p.z0 = paint->z0; p.scale = paint->scale;
 	p.table = q.x.lay.items - PAINT_BLOCK_BYTES;
 	p.colors = paint->mode == SIMLOD_PAINT_ARRAY ? colors : nullptr;
 	p.previous = previous; p.colorCap = colorCapacity; p.checkCap = (colors != nullptr || previous != nullptr) ? 1u : 0u;
-	// (pageable host memory: the runtime has read `paint` and `edges` when the calls return)
+	// (pageable host memory: the runtime has read `paint` and the edges when the calls return)
 	if (paint->mode == SIMLOD_PAINT_RAMP) {
 		const hipError_t e = hipMemcpyAsync(q.x.scratch + p.table, paint->table, PAINT_BLOCK_BYTES, hipMemcpyHostToDevice, stream);
 		if (e != hipSuccess) return (int)e;
 	}
 	const uint32_t grid = copy_grid(q.x.lay.itemCap);
-	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                        // k_q_dir: one wave per table entry
 	if (fp != nullptr) {
-		fa.f.f.n = fp->numVertices;
-		fa.f.f.edges = q.x.lay.items - front;
-		const hipError_t e = hipMemcpyAsync(q.x.scratch + fa.f.f.edges, edges, (size_t)fa.f.f.n * sizeof(FootEdge), hipMemcpyHostToDevice, stream);
+		const hipError_t e = pe.upload(q, front, stream, fg.edges);
 		if (e != hipSuccess) return (int)e;
-		SIMLOD_LAUNCH(k_f_hier, dim3(1), dim3(WG_TPB), stream, fa.f);
-		if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
-		SIMLOD_LAUNCH(k_f_count, dim3(grid), dim3(LANE_TPB), stream, fa.f);
-		SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);
+		const FootPaintArgs fa{{q, fg}, p};
+		SIMLOD_LAUNCH_SELECTION(k_f_hier, k_f_count, fa.f, q, tableCapacity, grid, stream);
 		SIMLOD_LAUNCH(k_ef_paint, dim3(grid), dim3(LANE_TPB), stream, fa);
+	} else if (lasso != nullptr) {
+		const hipError_t e = pe.upload(q, front, stream, lg.edges);
+		if (e != hipSuccess) return (int)e;
+		const LassoPaintArgs la{{q, lg}, p};
+		SIMLOD_LAUNCH_SELECTION(k_l_hier, k_l_count, la.f, q, tableCapacity, grid, stream);
+		SIMLOD_LAUNCH(k_el_paint, dim3(grid), dim3(LANE_TPB), stream, la);
 	} else {
-		PaintArgs pa{q, p};
-		SIMLOD_LAUNCH(k_q_hier, dim3(1), dim3(WG_TPB), stream, q);
-		if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
-		SIMLOD_LAUNCH(k_q_count, dim3(grid), dim3(LANE_TPB), stream, q);
-		SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);
+		const PaintArgs pa{q, p};
+		SIMLOD_LAUNCH_SELECTION(k_q_hier, k_q_count, q, q, tableCapacity, grid, stream);
 		SIMLOD_LAUNCH(k_e_paint, dim3(grid), dim3(LANE_TPB), stream, pa);
 	}
 	if (profile_enabled()) profile_close(stream);
@@ -283,42 +332,44 @@ uint32_t summary_grid(uint64_t itemCap, uint32_t maxWorkgroups) {
 
 }  // namespace
 
-// simlod_query_summary: the footprint query's launches as a count-only call with the caller's maxLevel and select, the polygon and the partial
-// records in the scratch buffer's blocks in front of the items, then k_s_partial (fp == nullptr) or k_fs_partial, then k_s_final.
+// simlod_query_summary / simlod_query_summary_lasso: the footprint's or the lasso's launches as a count-only call with the caller's maxLevel and
+// select, the polygon and the partial records in the scratch buffer's blocks in front of the items, then k_s_partial (no polygon), k_fs_partial or
+// k_ls_partial, then k_s_final.  At most one of `fp` and `lasso`.
 int launch_summary(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
-                   const SimlodFootprint* fp, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
-                   SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts, hipStream_t stream) {
+                   const SimlodFootprint* fp, const SimlodLasso* lasso, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select, void* scratch,
+                   uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts, hipStream_t stream) {
 	if (params == nullptr || summary == nullptr || !summary_acceptable(*params) || (reinterpret_cast<uintptr_t>(summary) & 7u) != 0u) return (int)hipErrorInvalidValue;
-	FootSummaryArgs fa{};
-	FootEdge edges[SIMLOD_FOOTPRINT_MAX_VERTICES];
-	if (fp != nullptr && !footprint_edges(fp, fa.f.f, edges)) return (int)hipErrorInvalidValue;
+	if (fp != nullptr && lasso != nullptr) return (int)hipErrorInvalidValue;
+	FootGeom fg{};
+	LassoGeom lg{};
+	PolygonEdges pe;
+	if (fp != nullptr && !footprint_edges(fp, fg, pe)) return (int)hipErrorInvalidValue;
+	if (lasso != nullptr && !lasso_edges(lasso, lg, pe)) return (int)hipErrorInvalidValue;
 	constexpr uint64_t front = FOOT_BLOCK_BYTES + SUMMARY_BLOCK_BYTES;
-	QueryArgs& q = fa.f.q;
+	QueryArgs q{};
 	const int rc = prepare_query(ctx, nodes, stats, u, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, nullptr, 0u, counts, front, q);
 	if (rc != 0) return rc;
-	SummaryOp& s = fa.s;
+	SummaryOp s{};
 	s.inv = summary_inv((float)q.g.size); s.z0 = params->z0; s.scale = params->scale;
 	s.parts = q.x.lay.items - SUMMARY_BLOCK_BYTES;
 	const uint32_t grid = copy_grid(q.x.lay.itemCap), sgrid = summary_grid(q.x.lay.itemCap, params->maxWorkgroups);
 	const SummaryFinalArgs fin{q.x.scratch, s.parts, sgrid, 0u, counts, summary};
-	constexpr uint32_t perWg = LANE_TPB / SIMLOD_WAVE;                        // k_q_dir: one wave per table entry
+	// (pageable host memory: the runtime has read the edges when the call returns)
 	if (fp != nullptr) {
-		fa.f.f.n = fp->numVertices;
-		fa.f.f.edges = q.x.lay.items - front;
-		// (pageable host memory: the runtime has read `edges` when the call returns)
-		const hipError_t e = hipMemcpyAsync(q.x.scratch + fa.f.f.edges, edges, (size_t)fa.f.f.n * sizeof(FootEdge), hipMemcpyHostToDevice, stream);
+		const hipError_t e = pe.upload(q, front, stream, fg.edges);
 		if (e != hipSuccess) return (int)e;
-		SIMLOD_LAUNCH(k_f_hier, dim3(1), dim3(WG_TPB), stream, fa.f);
-		if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
-		SIMLOD_LAUNCH(k_f_count, dim3(grid), dim3(LANE_TPB), stream, fa.f);
-		SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);
+		const FootSummaryArgs fa{{q, fg}, s};
+		SIMLOD_LAUNCH_SELECTION(k_f_hier, k_f_count, fa.f, q, tableCapacity, grid, stream);
 		SIMLOD_LAUNCH(k_fs_partial, dim3(sgrid), dim3(LANE_TPB), stream, fa);
+	} else if (lasso != nullptr) {
+		const hipError_t e = pe.upload(q, front, stream, lg.edges);
+		if (e != hipSuccess) return (int)e;
+		const LassoSummaryArgs la{{q, lg}, s};
+		SIMLOD_LAUNCH_SELECTION(k_l_hier, k_l_count, la.f, q, tableCapacity, grid, stream);
+		SIMLOD_LAUNCH(k_ls_partial, dim3(sgrid), dim3(LANE_TPB), stream, la);
 	} else {
-		SummaryArgs sa{q, s};
-		SIMLOD_LAUNCH(k_q_hier, dim3(1), dim3(WG_TPB), stream, q);
-		if (tableCapacity != 0u) SIMLOD_LAUNCH(k_q_dir, dim3((tableCapacity + perWg - 1u) / perWg), dim3(LANE_TPB), stream, q);
-		SIMLOD_LAUNCH(k_q_count, dim3(grid), dim3(LANE_TPB), stream, q);
-		SIMLOD_LAUNCH(k_q_scan, dim3(1), dim3(WG_TPB), stream, q);
+		const SummaryArgs sa{q, s};
+		SIMLOD_LAUNCH_SELECTION(k_q_hier, k_q_count, q, q, tableCapacity, grid, stream);
 		SIMLOD_LAUNCH(k_s_partial, dim3(sgrid), dim3(LANE_TPB), stream, sa);
 	}
 	SIMLOD_LAUNCH(k_s_final, dim3(SUMMARY_FINAL_HIST_WGS + 1u), dim3(WG_TPB), stream, fin);

@@ -495,7 +495,7 @@ int simlod_paint_region(const SimlodNode* nodes, const SimlodStats* stats, const
                         uint32_t tableCapacity, const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts,
                         void* stream) {
 	if (nodes == nullptr) return (int)hipErrorInvalidValue;
-	return launch_paint(context_of(nodes), nodes, stats, uniforms, region, footprint, paint, scratch, scratchBytes, table, tableCapacity, colors, previous,
+	return launch_paint(context_of(nodes), nodes, stats, uniforms, region, footprint, nullptr, paint, scratch, scratchBytes, table, tableCapacity, colors, previous,
 	                    colorCapacity, counts, (hipStream_t)stream);
 }
 
@@ -506,7 +506,36 @@ int simlod_query_summary(const SimlodNode* nodes, const SimlodStats* stats, cons
                          uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts,
                          void* stream) {
 	if (nodes == nullptr) return (int)hipErrorInvalidValue;
-	return launch_summary(context_of(nodes), nodes, stats, uniforms, region, footprint, params, maxLevel, select, scratch, scratchBytes, table,
+	return launch_summary(context_of(nodes), nodes, stats, uniforms, region, footprint, nullptr, params, maxLevel, select, scratch, scratchBytes, table,
+	                      tableCapacity, summary, counts, (hipStream_t)stream);
+}
+
+uint64_t simlod_lasso_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return lasso_min_bytes(nodeCapacity, sampleBound); }
+
+int simlod_query_lasso(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region, const SimlodLasso* lasso,
+                       uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
+                       SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, void* stream) {
+	if (lasso == nullptr)                                                       // rule L6: exactly simlod_query_region
+		return launch_query(context_of(nodes), nodes, stats, uniforms, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples,
+		                    sampleCapacity, counts, (hipStream_t)stream);
+	return launch_lasso(context_of(nodes), nodes, stats, uniforms, region, lasso, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples,
+	                    sampleCapacity, counts, (hipStream_t)stream);
+}
+
+int simlod_paint_lasso(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region, const SimlodLasso* lasso,
+                       const SimlodPaint* paint, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, const uint32_t* colors,
+                       uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts, void* stream) {
+	if (nodes == nullptr) return (int)hipErrorInvalidValue;
+	return launch_paint(context_of(nodes), nodes, stats, uniforms, region, nullptr, lasso, paint, scratch, scratchBytes, table, tableCapacity, colors, previous,
+	                    colorCapacity, counts, (hipStream_t)stream);
+}
+
+int simlod_query_summary_lasso(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                               const SimlodLasso* lasso, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select, void* scratch,
+                               uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts,
+                               void* stream) {
+	if (nodes == nullptr) return (int)hipErrorInvalidValue;
+	return launch_summary(context_of(nodes), nodes, stats, uniforms, region, nullptr, lasso, params, maxLevel, select, scratch, scratchBytes, table,
 	                      tableCapacity, summary, counts, (hipStream_t)stream);
 }
 

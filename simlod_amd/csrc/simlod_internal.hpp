@@ -187,13 +187,18 @@ int launch_footprint(Context& ctx, const SimlodNode* nodes, const SimlodStats* s
                      const SimlodFootprint* footprint, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
                      uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream);
 uint64_t footprint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+int launch_lasso(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
+                 const SimlodLasso* lasso, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
+                 uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream);
+uint64_t lasso_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+// (paint and summary: at most one of `footprint` and `lasso`)
 int launch_paint(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
-                 const SimlodFootprint* footprint, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
+                 const SimlodFootprint* footprint, const SimlodLasso* lasso, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
                  uint32_t tableCapacity, const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts, hipStream_t stream);
 uint64_t paint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
 int launch_summary(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
-                   const SimlodFootprint* footprint, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select, void* scratch,
-                   uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts,
+                   const SimlodFootprint* footprint, const SimlodLasso* lasso, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select,
+                   void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts,
                    hipStream_t stream);
 uint64_t summary_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
 int launch_profile(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,

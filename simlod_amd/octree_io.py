@@ -24,6 +24,10 @@ simlod_query_region — every rule restated in numpy float64, which reproduces t
 Footprint queries (include/simlod_hip.h, "footprint queries"): `Footprint` holds the polygon and the affine map into its plane,
 `OctreeExport.crop(region, footprint=...)` is the host mirror of simlod_query_footprint, in the same float64 operation order.
 
+Lasso queries (include/simlod_hip.h, "lasso queries"): `Lasso` holds a polygon on the screen of a perspective camera and the three rows that
+project a point onto it, `classify_lasso` is rules L2-L4, and `OctreeExport.crop / paint / summarize(lasso=...)` are the host mirrors of
+simlod_query_lasso, simlod_paint_lasso and simlod_query_summary_lasso, in the same float64 operation order.
+
 Paint regions (include/simlod_hip.h, "paint regions"): `Paint` holds the mode and its parameters, `OctreeExport.paint` is the host mirror of
 simlod_paint_region — the same export with the colours of crop's samples changed, and the colours they had.
 
@@ -140,14 +144,18 @@ class OctreeExport:
             return False
         return True
 
-    def crop(self, region, max_level=None, select="all", return_counts=False, footprint=None, profile=None, test_every_sample=False, return_index=False):
+    def crop(self, region, max_level=None, select="all", return_counts=False, footprint=None, profile=None, test_every_sample=False, return_index=False, lasso=None):
         """The host mirror of simlod_query_region: what the device returns for `region` on the octree this FULL export (select "all", max level
         20; anything else ValueError) was taken from, as an OctreeExport on the host — and, return_counts, the SimlodQueryCounts record too.
         footprint (a Footprint): the mirror of simlod_query_footprint — rules F1-F4 on top of the planes; rule F5's promise is asserted for
         every copied and every outside node.
         profile (a Profile): the samples of simlod_query_profile (OctreeExport.profile adds the records) — rules P1 and P3 on top of the planes;
         rule P4's promise is asserted likewise.  test_every_sample: the same nodes are listed, but none counts as copied.
+        lasso (a Lasso): the mirror of simlod_query_lasso — rules L1-L4 on top of the planes; rule L5's promise is asserted likewise.  A lasso
+        together with a footprint or a profile is a ValueError.
         return_index: the last element of the result is, per returned sample, its index in this export's samples (int64)."""
+        if lasso is not None and (footprint is not None or profile is not None):
+            raise ValueError("a lasso does not combine with a footprint or a profile in one call")
         if self.select != abi.EXPORT_ALL or self.max_level < abi.MAX_DEPTH:
             raise ValueError(f"crop needs a full export (select all, max level 20), not select {self.select} / max level {self.max_level}")
         sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
@@ -162,6 +170,10 @@ class OctreeExport:
             # rule F4: outside by either, copied iff copied by both
             near, corner = classify_footprint(footprint, src, self.box_min, self.box_max)
             outside, inside = outside | (~near & ~corner), inside & ~near & corner
+        if lasso is not None:
+            # rule L4, combined as rule F4 combines: outside by either, copied iff copied by both
+            behind, covered = classify_lasso(lasso, src, self.box_min, self.box_max)
+            outside, inside = outside | behind, inside & covered
         if profile is not None:
             # rule P3, combined as rule F4 combines: outside by either, copied iff copied by both
             far, covered = classify_profile(profile, src, self.box_min, self.box_max)
@@ -205,10 +217,12 @@ class OctreeExport:
             inbox = (x >= mn[0]) & (x < mn[0] + size) & (y >= mn[1]) & (y < mn[1] + size) & (z >= mn[2]) & (z < mn[2] + size)
         if profile is not None:
             ok &= profile.locate(smp)[0] >= 0
-        if footprint is not None or profile is not None:
+        if footprint is not None or profile is not None or lasso is not None:
             if footprint is not None:
                 ok &= footprint.contains(smp)
-            # rule F5 / P4 for every outside node of the source, listed or not: none of its samples of the contract passes (the copied ones below)
+            if lasso is not None:
+                ok &= lasso.contains(smp)
+            # rule F5 / P4 / L5 for every outside node of the source, listed or not: none of its samples of the contract passes (the copied ones below)
             bad = ok & inbox & np.repeat(outside, src["numSamples"].astype(np.int64))
             assert not bad.any(), f"node {int(np.repeat(np.arange(len(src)), src['numSamples'].astype(np.int64))[bad][0])} is outside and holds a sample of the box that passes the test"
         parts, ns_out = [], np.zeros(len(out), np.int64)
@@ -239,13 +253,13 @@ class OctreeExport:
         return got if len(got) > 1 else ex
 
     # -- paint regions (include/simlod_hip.h, "paint regions") -----------------------------------------------------------------------------
-    def paint(self, region, paint, footprint=None, colors=None, return_previous=False):
+    def paint(self, region, paint, footprint=None, colors=None, return_previous=False, lasso=None):
         """The host mirror of simlod_paint_region on the octree this FULL export was taken from: (this export with the colours of the target
         samples changed — a new OctreeExport on the host; table, positions and order are this one's —, the SimlodQueryCounts record) and,
         return_previous, the colour words those samples had, in the query's order (uint32).  The target set and its order are crop's (rule
         E0: max level 20, select "all"), so rule F5's assertion stays in force.  colors: the uint32 words of an ARRAY paint, one per target
-        sample at least."""
-        _, c, index = self.crop(region, abi.MAX_DEPTH, "all", return_counts=True, footprint=footprint, return_index=True)
+        sample at least.  lasso (a Lasso, no footprint then): the mirror of simlod_paint_lasso, the target set being crop(lasso=)'s."""
+        _, c, index = self.crop(region, abi.MAX_DEPTH, "all", return_counts=True, footprint=footprint, return_index=True, lasso=lasso)
         smp = self.samples.copy()
         previous = smp["color"][index].copy()
         if paint.mode == abi.PAINT_ARRAY:
@@ -262,13 +276,14 @@ class OctreeExport:
         return (ex, c, previous) if return_previous else (ex, c)
 
     # -- summary queries (include/simlod_hip.h, "summary queries") -------------------------------------------------------------------------
-    def summarize(self, region, max_level=None, select="cut", footprint=None, z0=0.0, scale=1.0, return_counts=False):
+    def summarize(self, region, max_level=None, select="cut", footprint=None, z0=0.0, scale=1.0, return_counts=False, lasso=None):
         """The host mirror of simlod_query_summary on the octree this FULL export was taken from: the Summary of the samples
         crop(region, max_level, select, footprint=footprint) returns (rule S0: the set is crop's by construction) — and, return_counts, the
         SimlodQueryCounts record too.  Rules S1-S4 in numpy float64 and unsigned integers, in the order the header gives; the z histogram's
-        index is Paint.ramp_index (rule E3) with z0 and scale as float32."""
+        index is Paint.ramp_index (rule E3) with z0 and scale as float32.  lasso (a Lasso, no footprint then): the mirror of
+        simlod_query_summary_lasso, the set being crop(lasso=)'s."""
         bins = Paint(abi.PAINT_RAMP, z0=z0, scale=scale)                    # (refuses what rule S8 refuses of z0 and scale)
-        ex, c = self.crop(Region() if region is None else region, max_level, select, return_counts=True, footprint=footprint)
+        ex, c = self.crop(Region() if region is None else region, max_level, select, return_counts=True, footprint=footprint, lasso=lasso)
         smp = ex.samples
         mn, size = _box_of(self.box_min, self.box_max)
         rec = np.zeros((), dtype=abi.summary_dtype)
@@ -1411,6 +1426,112 @@ def classify_footprint(footprint, nodes, box_min, box_max):
         near |= ~far
         corner ^= ((a_v > Vlo) != (b_v > Vlo)) & ((c00 > 0) == (dv > 0))
     return near, corner
+
+
+class Lasso:
+    """A polygon on the screen of a perspective camera (include/simlod_hip.h, "lasso queries"): 3 .. 256 vertices (u, v) as float32, closed from
+    the last to the first, on the screen a point is mapped onto by the three rows U = ((ux*x + uy*y) + uz*z) + u0, V and W likewise (row_u,
+    row_v, row_w as float32): the screen position is (U/W, V/W) where W > 0.  Inside is the even-odd rule L1, multiplied through by W — nothing
+    here divides —, so the polygon may be non-convex or cross itself, and a point behind the eye (W <= 0) is never inside."""
+
+    def __init__(self, vertices, row_u, row_v, row_w):
+        v = np.asarray(vertices, dtype=np.float64).reshape(-1, 2)
+        if not 3 <= len(v) <= abi.LASSO_MAX_VERTICES:
+            raise ValueError(f"{len(v)} vertices: a lasso has 3 .. {abi.LASSO_MAX_VERTICES}")
+        with np.errstate(over="ignore"):
+            self.vertices = v.astype(np.float32)
+            self.row_u, self.row_v, self.row_w = (np.asarray(r, dtype=np.float64).reshape(4).astype(np.float32) for r in (row_u, row_v, row_w))
+        if not (np.isfinite(self.vertices).all() and np.isfinite(self.row_u).all() and np.isfinite(self.row_v).all() and np.isfinite(self.row_w).all()):
+            raise ValueError("a vertex or a row coefficient is not finite (as float32)")
+
+    @classmethod
+    def from_pixels(cls, transform, width, height, pixels):
+        """A polygon drawn on the width x height screen of the camera `transform` (row-major world-view-projection M as the uniforms store it):
+        vertices in continuous pixel coordinates, pixel (i, j) covering ndc [2i/width - 1, 2(i+1)/width - 1] as Rays.from_pixels states it (its
+        centre is (i + 0.5, j + 0.5)).  The rows are width/2 * (M[0] + M[3]), height/2 * (M[1] + M[3]) and M[3], computed in float64 and
+        narrowed to float32.  The lasso is what the record says: it agrees with the rasteriser's float32 pixel of a sample to a small fraction
+        of a pixel, not bit for bit."""
+        m = np.asarray(transform, dtype=np.float64).reshape(4, 4)
+        return cls(pixels, 0.5 * float(width) * (m[0] + m[3]), 0.5 * float(height) * (m[1] + m[3]), m[3])
+
+    @classmethod
+    def from_ndc(cls, transform, polygon):
+        """A polygon in normalised device coordinates (x_clip / w, y_clip / w, each -1 .. 1 on the screen) of the camera `transform`."""
+        m = np.asarray(transform, dtype=np.float64).reshape(4, 4)
+        return cls(polygon, m[0], m[1], m[3])
+
+    @classmethod
+    def from_footprint(cls, footprint):
+        """The lasso that selects what `footprint` selects: its axes as rows U and V, and row W = (0, 0, 0, 1)."""
+        return cls(footprint.vertices, footprint.axis_u, footprint.axis_v, (0.0, 0.0, 0.0, 1.0))
+
+    def __len__(self):
+        return len(self.vertices)
+
+    def record(self):
+        """The SimlodLasso the C ABI takes (abi.lasso_dtype, one record)."""
+        r = np.zeros(1, dtype=abi.lasso_dtype)
+        r["numVertices"] = len(self.vertices)
+        r["rowU"], r["rowV"], r["rowW"] = self.row_u, self.row_v, self.row_w
+        r["vertices"][0, : len(self.vertices)] = self.vertices
+        return r
+
+    def edges(self):
+        """(a_u, a_v, b_v, du, dv) per edge as float64 arrays: the edge from a = P[i] to b = P[(i + 1) mod n]."""
+        a = self.vertices.astype(np.float64)
+        b = np.roll(a, -1, axis=0)
+        return a[:, 0], a[:, 1], b[:, 1], b[:, 0] - a[:, 0], b[:, 1] - a[:, 1]
+
+    def edge_block(self):
+        """The fp64 block the launcher places in the scratch buffer: {a_u, a_v, du, dv} per edge (n x 4 float64)."""
+        a_u, a_v, _, du, dv = self.edges()
+        return np.ascontiguousarray(np.stack([a_u, a_v, du, dv], axis=1))
+
+    def project(self, x, y, z):
+        """(U, V, W) of float64 coordinates, in the header's operation order."""
+        with np.errstate(invalid="ignore", over="ignore"):
+            return tuple(((r[0] * x + r[1] * y) + r[2] * z) + r[3] for r in (self.row_u.astype(np.float64), self.row_v.astype(np.float64), self.row_w.astype(np.float64)))
+
+    def contains_uvw(self, U, V, W):
+        """Rule L1 at float64 (U, V, W): W > 0 and the number of crossed edges is odd."""
+        odd = np.zeros(np.shape(U), bool)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for a_u, a_v, b_v, du, dv in zip(*self.edges()):
+                sa, sb = a_v * W, b_v * W
+                c = du * (V - sa) - dv * (U - a_u * W)
+                odd ^= ((sa > V) != (sb > V)) & ((c > 0) == (dv > 0))
+            return odd & (W > 0)
+
+    def contains(self, points):
+        """Rule L1 on point records (abi.point_dtype) -> a boolean per point."""
+        p = np.asarray(points)
+        return self.contains_uvw(*self.project(*(p[a].astype(np.float64) for a in ("x", "y", "z"))))
+
+
+def classify_lasso(lasso, nodes, box_min, box_max):
+    """Rules L2-L4 of the lasso query for every entry of a table: (outside, copied) as boolean arrays — neither: the node is filtered sample by
+    sample (mixed signs of W at its eight corners, or a NEAR edge)."""
+    mn, size = _box_of(box_min, box_max)
+    s = np.ldexp(size, -nodes["level"].astype(np.int64))[:, None]
+    e = np.ldexp(size, -abi.MAX_DEPTH)
+    A = np.stack([nodes["X"], nodes["Y"], nodes["Z"]], axis=1).astype(np.float64)
+    lo, hi = (mn + A * s) - e, (mn + (A + 1.0) * s) + e
+    # (U, V, W) at the eight corners: 8 x N
+    with np.errstate(invalid="ignore", over="ignore"):
+        corners = [lasso.project(*((hi if (k >> a) & 1 else lo)[:, a] for a in range(3))) for k in range(8)]
+        U, V, W = (np.stack([c[j] for c in corners]) for j in range(3))
+        behind, front = (W <= 0).all(axis=0), (W > 0).all(axis=0)
+        near, odd = np.zeros(len(nodes), bool), np.zeros(len(nodes), bool)
+        for a_u, a_v, b_v, du, dv in zip(*lasso.edges()):
+            sa, sb = a_v * W, b_v * W
+            c = du * (V - sa) - dv * (U - a_u * W)
+            ua, ub = sa > V, sb > V
+            far = (c > 0).all(axis=0) | (c < 0).all(axis=0) | (ua & ub).all(axis=0) | ~(ua | ub).any(axis=0)
+            near |= ~far
+            odd ^= (ua[0] != ub[0]) & ((c[0] > 0) == (dv > 0))
+    outside = behind | (front & ~near & ~odd)
+    copied = front & ~near & odd
+    return outside, copied
 
 
 class Profile:

@@ -105,6 +105,11 @@ def lib():
         L.simlod_summary_buffer_min_bytes.restype = u64
         L.simlod_summary_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_query_summary.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, vp, vp]
+        L.simlod_lasso_buffer_min_bytes.restype = u64
+        L.simlod_lasso_buffer_min_bytes.argtypes = [u32, u64]
+        L.simlod_query_lasso.argtypes = L.simlod_query_footprint.argtypes
+        L.simlod_paint_lasso.argtypes = L.simlod_paint_region.argtypes
+        L.simlod_query_summary_lasso.argtypes = L.simlod_query_summary.argtypes
         L.simlod_profile_buffer_min_bytes.restype = u64
         L.simlod_profile_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_query_profile.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp, vp]
@@ -147,6 +152,7 @@ EXPORTED_SYMBOLS = [
     "simlod_pack_buffer_min_bytes", "simlod_pack_samples", "simlod_unpack_samples",
     "simlod_paint_buffer_min_bytes", "simlod_paint_region",
     "simlod_summary_buffer_min_bytes", "simlod_query_summary",
+    "simlod_lasso_buffer_min_bytes", "simlod_query_lasso", "simlod_paint_lasso", "simlod_query_summary_lasso",
 ]
 
 
@@ -680,15 +686,27 @@ class DeviceOctree:
                             u["boxMin"], u["boxMax"], ml, sel)
 
     # -- region queries (include/simlod_hip.h, "region queries") ---------------------------------------------------------------------------
-    def _query(self, uniforms, region, ml, sel, table, samples, sample_capacity, bound, footprint=None):
-        """One simlod_query_region call — with a footprint (an octree_io.Footprint) one simlod_query_footprint call — -> the SimlodQueryCounts
-        record (host).  samples None: count only."""
+    @staticmethod
+    def _one_polygon(footprint, lasso):
+        if footprint is not None and lasso is not None:
+            raise ValueError("a lasso does not combine with a footprint in one call")
+
+    def _query(self, uniforms, region, ml, sel, table, samples, sample_capacity, bound, footprint=None, lasso=None):
+        """One simlod_query_region call — with a footprint (an octree_io.Footprint) one simlod_query_footprint call, with a lasso (an
+        octree_io.Lasso) one simlod_query_lasso call — -> the SimlodQueryCounts record (host).  samples None: count only."""
+        self._one_polygon(footprint, lasso)
         u, up = self._u(uniforms)
         r = region.record()
         nn = table.numel() // abi.export_node_dtype.itemsize
         counts = torch.zeros(abi.query_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
         tail = (self._p(table), nn, None if samples is None else self._p(samples), ctypes.c_uint64(sample_capacity), self._p(counts), self._stream())
-        if footprint is None:
+        if lasso is not None:
+            what = "simlod_query_lasso"
+            f = lasso.record()
+            scratch = self._export_scratch(int(self.L.simlod_lasso_buffer_min_bytes(nn, bound)))
+            rc = self.L.simlod_query_lasso(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data), ctypes.c_void_p(f.ctypes.data),
+                                           ml, sel, self._p(scratch), ctypes.c_uint64(scratch.numel()), *tail)
+        elif footprint is None:
             what = "simlod_query_region"
             scratch = self._export_scratch(int(self.L.simlod_query_buffer_min_bytes(nn, bound)))
             rc = self.L.simlod_query_region(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data), ml, sel, self._p(scratch),
@@ -714,43 +732,50 @@ class DeviceOctree:
     def _table(self, nn):
         return torch.empty(max(nn, 1) * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
 
-    def count_region(self, uniforms, region, max_level=None, select="cut", footprint=None):
+    def count_region(self, uniforms, region, max_level=None, select="cut", footprint=None, lasso=None):
         """How much of the octree lies in `region` (an octree_io.Region) at `max_level`: the SimlodQueryCounts record of a count-only
         simlod_query_region call (numNodes, numSamples, numCandidates, numFilteredNodes, numCopiedNodes).  No sample is written.
-        footprint (an octree_io.Footprint): inside that extruded polygon as well, by simlod_query_footprint."""
+        footprint (an octree_io.Footprint): inside that extruded polygon as well, by simlod_query_footprint.
+        lasso (an octree_io.Lasso, no footprint then): inside that polygon on the screen as well, by simlod_query_lasso."""
+        self._one_polygon(footprint, lasso)
         sel, ml, nn, bound = self._query_setup(max_level, select)
-        return self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound, footprint)
+        return self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound, footprint, lasso)
 
-    def query_region(self, uniforms, region, max_level=None, select="cut", return_counts=False, footprint=None):
+    def query_region(self, uniforms, region, max_level=None, select="cut", return_counts=False, footprint=None, lasso=None):
         """The samples inside `region` as an octree_io.OctreeExport on this device (select abi.EXPORT_REGION): the pruned table and, in chunk-list
         order, the samples of the selected nodes ("cut": source leaves and the nodes at max_level; "all": every listed node) that pass the
         region's test.  A count-only call first, then the outputs sized exactly.  Raises SimlodError when the device reports an error.
-        footprint (an octree_io.Footprint): the samples that are inside that extruded polygon as well, by simlod_query_footprint."""
+        footprint (an octree_io.Footprint): the samples that are inside that extruded polygon as well, by simlod_query_footprint.
+        lasso (an octree_io.Lasso, no footprint then): the samples inside that polygon on the screen as well, by simlod_query_lasso."""
         from .octree_io import OctreeExport
+        self._one_polygon(footprint, lasso)
         sel, ml, nn, bound = self._query_setup(max_level, select)
-        c = self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound, footprint)
+        c = self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound, footprint, lasso)
         nn, ns = int(c["numNodes"]), int(c["numSamples"])
         table = torch.empty(nn * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
         samples = torch.empty(max(ns, 1) * abi.point_dtype.itemsize, dtype=torch.uint8, device=self.device)
-        c = self._query(uniforms, region, ml, sel, table, samples, ns, bound, footprint)
+        c = self._query(uniforms, region, ml, sel, table, samples, ns, bound, footprint, lasso)
         u = np.asarray(uniforms).reshape(-1)[0]
         ex = OctreeExport(table, samples[: int(c["numSamples"]) * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_REGION)
         return (ex, c) if return_counts else ex
 
     # -- paint regions (include/simlod_hip.h, "paint regions") -----------------------------------------------------------------------------
-    def paint_region(self, uniforms, region, paint, footprint=None, colors=None, return_previous=False):
+    def paint_region(self, uniforms, region, paint, footprint=None, colors=None, return_previous=False, lasso=None):
         """Recolour, in the octree itself, the samples simlod_query_footprint(region, footprint, 20, "all") returns — `paint` (an
         octree_io.Paint) says how: set, blend, ramp by height, or array (then `colors`: one uint32 word per sample in the query's order, a
         tensor on this device or anything numpy takes) — by one simlod_paint_region call.  -> the SimlodQueryCounts record (numSamples: the
         number painted), and with return_previous (that record, the colour words the samples had: a uint32 tensor on this device, which an
         array paint of the same region and footprint puts back).  Raises SimlodError when the device reports an error; then nothing was
-        painted.  No frame, query or ingest of this octree may be in flight on another stream."""
+        painted.  No frame, query or ingest of this octree may be in flight on another stream.
+        lasso (an octree_io.Lasso, no footprint then): the samples simlod_query_lasso(region, lasso, 20, "all") returns, by simlod_paint_lasso."""
         from .octree_io import Region
+        self._one_polygon(footprint, lasso)
         u, up = self._u(uniforms)
         st = self.read_stats()
         nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
         r, pr = (Region() if region is None else region).record(), paint.record()
-        f = None if footprint is None else footprint.record()
+        f = lasso.record() if lasso is not None else None if footprint is None else footprint.record()
+        call, what = (self.L.simlod_paint_lasso, "simlod_paint_lasso") if lasso is not None else (self.L.simlod_paint_region, "simlod_paint_region")
         col = None
         if paint.mode == abi.PAINT_ARRAY:
             if colors is None:
@@ -765,40 +790,42 @@ class DeviceOctree:
         counts = torch.zeros(abi.query_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
         scratch = self._export_scratch(int(self.L.simlod_paint_buffer_min_bytes(nn, bound)))
         opt = lambda t: None if t is None else self._p(t)
-        _check(self.L.simlod_paint_region(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data),
-                                          None if f is None else ctypes.c_void_p(f.ctypes.data), ctypes.c_void_p(pr.ctypes.data), self._p(scratch),
-                                          ctypes.c_uint64(scratch.numel()), self._p(table), nn, opt(col), opt(prev), ctypes.c_uint64(cap), self._p(counts),
-                                          self._stream()), "simlod_paint_region")
+        _check(call(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data),
+                    None if f is None else ctypes.c_void_p(f.ctypes.data), ctypes.c_void_p(pr.ctypes.data), self._p(scratch),
+                    ctypes.c_uint64(scratch.numel()), self._p(table), nn, opt(col), opt(prev), ctypes.c_uint64(cap), self._p(counts),
+                    self._stream()), what)
         c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
         if int(c["error"]) != 0:
-            raise SimlodError(f"simlod_paint_region reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples); nothing was painted")
+            raise SimlodError(f"{what} reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples); nothing was painted")
         return (c, prev[: int(c["numSamples"])]) if return_previous else c
 
     # -- summary queries (include/simlod_hip.h, "summary queries") -------------------------------------------------------------------------
-    def summarize_region(self, uniforms, region, max_level=None, select="cut", footprint=None, z0=0.0, scale=1.0, max_workgroups=0):
+    def summarize_region(self, uniforms, region, max_level=None, select="cut", footprint=None, z0=0.0, scale=1.0, max_workgroups=0, lasso=None):
         """What query_region(region, max_level, select, footprint=footprint) would return, summarised on the device by one simlod_query_summary
         call instead of copied out: an octree_io.Summary — the number of samples, their extent, the sums behind centroid and covariance, the
         histogram of their heights in the bins of a ramp paint with (z0, scale), and the histograms of the four colour bytes.  The octree is
         only read.  max_workgroups: 0, or a limit for the reduction's grid (the result does not depend on it).  Raises SimlodError when the
-        device reports an error; then no summary was written."""
+        device reports an error; then no summary was written.
+        lasso (an octree_io.Lasso, no footprint then): what query_region(..., lasso=lasso) would return, by simlod_query_summary_lasso."""
         from .octree_io import Region, Summary
+        self._one_polygon(footprint, lasso)
         u, up = self._u(uniforms)
         sel, ml, nn, bound = self._query_setup(max_level, select)
         r = (Region() if region is None else region).record()
-        f = None if footprint is None else footprint.record()
+        f = lasso.record() if lasso is not None else None if footprint is None else footprint.record()
+        call, what = (self.L.simlod_query_summary_lasso, "simlod_query_summary_lasso") if lasso is not None else (self.L.simlod_query_summary, "simlod_query_summary")
         pr = np.zeros(1, dtype=abi.summary_params_dtype)
         pr["z0"], pr["scale"], pr["maxWorkgroups"] = z0, scale, int(max_workgroups)
         table = self._table(nn)
         counts = torch.zeros(abi.query_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
         out = torch.zeros(abi.summary_dtype.itemsize, dtype=torch.uint8, device=self.device)
         scratch = self._export_scratch(int(self.L.simlod_summary_buffer_min_bytes(nn, bound)))
-        _check(self.L.simlod_query_summary(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data),
-                                           None if f is None else ctypes.c_void_p(f.ctypes.data), ctypes.c_void_p(pr.ctypes.data), ml, sel, self._p(scratch),
-                                           ctypes.c_uint64(scratch.numel()), self._p(table), nn, self._p(out), self._p(counts), self._stream()),
-               "simlod_query_summary")
+        _check(call(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data),
+                    None if f is None else ctypes.c_void_p(f.ctypes.data), ctypes.c_void_p(pr.ctypes.data), ml, sel, self._p(scratch),
+                    ctypes.c_uint64(scratch.numel()), self._p(table), nn, self._p(out), self._p(counts), self._stream()), what)
         c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
         if int(c["error"]) != 0:
-            raise SimlodError(f"simlod_query_summary reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples); no summary was written")
+            raise SimlodError(f"{what} reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples); no summary was written")
         return Summary(out.cpu().numpy().view(abi.summary_dtype)[0], pr["z0"][0], pr["scale"][0])
 
     # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------

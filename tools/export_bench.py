@@ -15,6 +15,10 @@ host mirror's median `within` (on the first 256 of them) is about 30, with k = 1
 pass) with its count-only call; the rectangle of 30-70 % x 20-90 % of the extents beside the same rectangle as a four-plane
 simlod_query_region, the two alternating rep by rep; the count-only calls of a 14-vertex and a 256-vertex star, alternating — and the
 device-to-device copy, all in this one run.
+--lasso: instead, simlod_query_lasso CUT@20 on the same octree — the --footprint polygons (half the terrain, the rectangle, the 14-vertex and
+the 256-vertex star) drawn at the terrain's mean height on the bird camera's 1920 x 1080 screen, each alternating rep by rep with
+simlod_query_footprint of the plan-view polygon, full and count-only — and the device-to-device copy, all in this one run.  --lasso-only KIND:
+that polygon alone (a per-kernel trace of one vertex count).
 --profile: instead, simlod_query_profile CUT@20 on the same octree — a 5-vertex polyline across the terrain whose half-width gives the
 corridor 1 % of the plan area, with records, without records, and simlod_query_footprint with the corridor's outline polygon, the three
 alternating rep by rep; the count-only call — and the device-to-device copy, all in this one run.
@@ -395,6 +399,85 @@ def footprint_bench(dev, u, box, st, reps):
     for kind, t in (("star7", t7), ("star128", t128)):
         query(kind, True)
         out[kind + "_count_only"] = row(kind, t, read_counts())
+    print(json.dumps(out))
+
+
+def lasso_bench(dev, u, box, st, reps, T, width, height, only=None):
+    """The --footprint cases as lassos on the screen of the camera T: each plan-view polygon is drawn at the terrain's mean height and projected
+    to pixels, so the lasso selects about what the footprint selects; lasso and footprint of a case alternate rep by rep, full and count-only."""
+    from simlod_amd import fingerprint
+    from simlod_amd.octree_io import Footprint, Lasso, Region
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    need = int(L.simlod_lasso_buffer_min_bytes(nn, bound))
+    assert need == int(L.simlod_footprint_buffer_min_bytes(nn, bound))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    table = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    samples = torch.empty(bound * 16, dtype=torch.uint8, device=dev.device)
+    counts = torch.zeros(32, dtype=torch.uint8, device=dev.device)
+    uu, up = dev._u(u)
+    b = np.asarray(box, dtype=np.float64)
+    m = np.asarray(T, dtype=np.float64).reshape(4, 4)
+
+    def star(n):
+        k = np.arange(2 * n)
+        r = np.where(k % 2 == 0, 0.45, 0.15) * min(b[0], b[1])
+        return np.stack([b[0] / 2 + r * np.cos(k * np.pi / n), b[1] / 2 + r * np.sin(k * np.pi / n)], axis=1)
+
+    def on_screen(xy):
+        h = np.concatenate([xy, np.full((len(xy), 1), 0.5 * b[2]), np.ones((len(xy), 1))], axis=1) @ m.T
+        assert (h[:, 3] > 0).all()
+        return np.stack([0.5 * width * (h[:, 0] / h[:, 3] + 1.0), 0.5 * height * (h[:, 1] / h[:, 3] + 1.0)], axis=1)
+
+    tri = 0.5 + (np.array([(50 / 600, 50 / 400), (550 / 600, 80 / 400), (250 / 600, 380 / 400)]) - 0.5) * 1.25
+    rect_lo, rect_hi = (0.3 * b[0], 0.2 * b[1]), (0.7 * b[0], 0.9 * b[1])
+    plan = {"half_terrain": tri * b[:2], "rect": Footprint.from_rect(rect_lo, rect_hi).vertices.astype(np.float64), "star7": star(7), "star128": star(128)}
+    if only is not None:
+        plan = {only: plan[only]}
+    prints = {k: Footprint.from_xy(v) for k, v in plan.items()}
+    lassos = {k: Lasso.from_pixels(T, width, height, on_screen(v)) for k, v in plan.items()}
+    frec, lrec = {k: f.record() for k, f in prints.items()}, {k: l.record() for k, l in lassos.items()}
+    none = Region().record()
+
+    def query(call, rec, count_only=False):
+        rc = call(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(none.ctypes.data), ctypes.c_void_p(rec.ctypes.data), 20, abi.EXPORT_CUT, p(scratch),
+                  ctypes.c_uint64(need), p(table), nn, None if count_only else p(samples), ctypes.c_uint64(bound), p(counts), stream)
+        assert rc == 0
+
+    def read_counts():
+        torch.cuda.synchronize()
+        c = counts.cpu().numpy().view(abi.query_counts_dtype)[0].copy()
+        assert int(c["error"]) == 0
+        return c
+
+    copy_dst = torch.empty(int(st["numPoints"]) * 16, dtype=torch.uint8, device=dev.device)
+    copy_src = samples[: copy_dst.numel()]
+    t_copy = timed(lambda: copy_dst.copy_(copy_src), reps)
+    copy_gbs = 2 * copy_dst.numel() / (t_copy[0] * 1e6)
+    out = {"points": int(st["numPoints"]), "numNodes": nn, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(), "screen": [width, height],
+           "d2d_copy": {"ms": round(t_copy[0], 4), "bytes": 2 * copy_dst.numel(), "GBs": round(copy_gbs, 1)}}
+
+    def row(kind, ms, ms_count, c):
+        nbytes = int(c["numCandidates"]) * 16 + int(c["numSamples"]) * 16 + int(c["numNodes"]) * 40
+        gbs = nbytes / (ms[0] * 1e6)
+        return {"ms": round(ms[0], 4), "ms_min": round(ms[1], 4), "count_only_ms": round(ms_count[0], 4), "vertices": len(prints[kind]),
+                "nodes_listed": int(c["numNodes"]), "nodes_copied": int(c["numCopiedNodes"]), "nodes_filtered": int(c["numFilteredNodes"]),
+                "numCandidates": int(c["numCandidates"]), "numSamples": int(c["numSamples"]), "algorithmic_bytes": nbytes, "GBs": round(gbs, 1),
+                "frac_of_copy": round(gbs / copy_gbs, 4)}
+
+    for kind in plan:
+        ql, qf = L.simlod_query_lasso, L.simlod_query_footprint
+        t_l, t_f, t_lc, t_fc = timed_alternating([lambda: query(ql, lrec[kind]), lambda: query(qf, frec[kind]), lambda: query(ql, lrec[kind], True),
+                                                  lambda: query(qf, frec[kind], True)], reps)
+        query(ql, lrec[kind])
+        out[kind] = {"lasso": row(kind, t_l, t_lc, read_counts())}
+        query(qf, frec[kind])
+        out[kind]["footprint"] = row(kind, t_f, t_fc, read_counts())
+        out[kind]["lasso_over_footprint"] = round(t_l[0] / t_f[0], 4)
+        out[kind]["lasso_over_footprint_count_only"] = round(t_lc[0] / t_fc[0], 4)
+    if "half_terrain" in out:
+        out["half_terrain"]["target"] = ">= 50 % of the copy rate"
+        out["half_terrain"]["target_held"] = bool(out["half_terrain"]["lasso"]["frac_of_copy"] >= 0.5)
     print(json.dumps(out))
 
 
@@ -827,6 +910,8 @@ def main():
     ap.add_argument("--buildable", action="store_true", help="also time simlod_import_octree_buildable (grid rebuild included)")
     ap.add_argument("--region", action="store_true", help="time simlod_query_region (whole box, half the terrain, a city block) instead")
     ap.add_argument("--footprint", action="store_true", help="time simlod_query_footprint (half the terrain, a rectangle beside its four planes, two stars) instead")
+    ap.add_argument("--lasso", action="store_true", help="time simlod_query_lasso (the --footprint polygons drawn on the bird camera's 1080p screen, each beside its footprint query) instead")
+    ap.add_argument("--lasso-only", default=None, choices=["half_terrain", "rect", "star7", "star128"], help="--lasso: this polygon alone (a per-kernel trace of one case)")
     ap.add_argument("--profile", action="store_true", help="time simlod_query_profile (a 5-vertex corridor over 1 % of the terrain, with and without records, beside the footprint of its outline) instead")
     ap.add_argument("--rays", action="store_true", help="time simlod_query_rays (one pixel cone, 4 096 vertical rays) instead")
     ap.add_argument("--neighbours", action="store_true", help="time simlod_query_neighbours (4 096 queries, k = 1, 8, 16, count-only) instead")
@@ -860,6 +945,8 @@ def main():
         return region_bench(dev, u, box, st, args.reps)
     if args.footprint:
         return footprint_bench(dev, u, box, st, args.reps)
+    if args.lasso:
+        return lasso_bench(dev, u, box, st, args.reps, T, 1920, 1080, args.lasso_only)
     if args.profile:
         return profile_bench(dev, u, box, st, args.reps)
     if args.rays:
