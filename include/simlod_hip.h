@@ -880,6 +880,69 @@ int simlod_query_summary_lasso(const SimlodNode* nodes, const SimlodStats* stats
                                void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
                                SimlodSummary* summary /*device*/, SimlodQueryCounts* counts, void* stream);
 
+/* ---- inverse selections: all but a region, a footprint or a lasso ------------------------------------------------------------------------------
+ * simlod_query_inverse, simlod_paint_inverse and simlod_query_summary_inverse are the three verbs of a selection — copy it out, recolour it in
+ * place, describe it — for the samples the selection does NOT hold: "everything except this tripod, this car, this parcel".  The complement of a
+ * convex region is not convex and that of a lasso is no lasso, so no other call expresses it.  SIMLOD_CLIP_OUTSIDE draws that frame; these calls
+ * turn it into data, and importing the query's result (simlod_import_octree) makes it permanent: the selection is erased.
+ * POSITIVE below is the existing query with the same arguments: simlod_query_footprint if `footprint` is given, simlod_query_lasso if `lasso` is
+ * given, else simlod_query_region.  Everything the region section says about the box, the inflated cube, SimlodQueryCounts and
+ * SIMLOD_EXPORT_REGION stays in force.  The flag is the entry point: no `reserved` word of SimlodRegion, SimlodFootprint or SimlodLasso means
+ * anything new, and a nonzero one is refused as before.
+ * NOT COVERED: inverse profile queries; an inverse clip mode (SIMLOD_CLIP_OUTSIDE exists); inverse on rays, neighbours, views or deltas; a
+ * BUILDABLE import of an inverse result — the voxels are filtered by their own position, so a rebuilt grid's popcount no longer equals the voxel
+ * count and SIMLOD_ERR_IMPORT_GRID would be right to fire (re-deriving the voxels from the surviving points is a later step).
+ *
+ *  I1. Sample rule.  A sample passes the inverse iff it does not pass POSITIVE's sample rule: region rule 3 and, where given, F1 or L1.  A NaN
+ *      coordinate fails the positive rule, so it passes the inverse.  No new arithmetic: the fp64 operations, their order and the absence of
+ *      fused multiply-add are POSITIVE's, bit for bit.
+ *  I2. Node classes.  Each node gets POSITIVE's final class (rules 1 and 4, F4, L4) from its own (level, X, Y, Z); then OUTSIDE becomes COPIED
+ *      (every sample, no test), COPIED becomes EMPTIED (contributes nothing; its samples are not read) and FILTERED stays FILTERED, by I1.
+ *  I3. Listing.  Nothing is culled: the table is simlod_export_octree(maxLevel, select)'s in every field except numSamples and firstSample — the
+ *      same entries, order, parent, firstChild, childMask and flags.  An EMPTIED node is listed with numSamples 0.  So the result imports with
+ *      the source's tree shape: inner nodes stay inner and their samples stay voxels; a node whose children all vanished does not become a leaf
+ *      that draws its voxels as points.
+ *  I4. Counts.  numCandidates: the samples of the selected nodes that are not EMPTIED.  numCopiedNodes / numFilteredNodes: such nodes with at
+ *      least one sample, by the mapped class.  numSamples: the samples after the test.
+ *  I5. Rule 5 (count-only calls, capacities), the chunk-table / `next` sources and the error bits are the region query's.
+ *  I6. Partition.  For one set of arguments a node's POSITIVE samples and its inverse samples are disjoint and together are the node's samples, in
+ *      chunk-list order.  Sample by sample, whatever the coordinates, as long as POSITIVE lists the node (both calls give the node the same
+ *      class, so this covers samples outside the contract too); for a node POSITIVE does not list it holds for the samples of the contract
+ *      (F5 / L5).
+ *  I7. Degenerate selections.  Zero planes and no polygon: every node is EMPTIED and numSamples is 0.  A selection that selects nothing: the
+ *      result equals simlod_export_octree(maxLevel, select) byte for byte.
+ *  I8. simlod_paint_inverse follows rules E0-E9 with "the samples simlod_query_inverse(..., 20, SIMLOD_EXPORT_ALL) returns, in that order" as the
+ *      target set; `previous` followed by an ARRAY paint with the same arguments is the undo.  simlod_query_summary_inverse follows rules S0-S8
+ *      with simlod_query_inverse(..., maxLevel, select) as the set.
+ *  I9. hipErrorInvalidValue with nothing enqueued: everything POSITIVE refuses; `footprint` and `lasso` both non-NULL; scratchBytes below the
+ *      call's own minimum (simlod_inverse_buffer_min_bytes(tableCapacity, 0), simlod_paint_buffer_min_bytes, simlod_summary_buffer_min_bytes) —
+ *      the same with or without a polygon.
+ *  I10. For a selection of planes only, the inverse at maxLevel 20 / SIMLOD_EXPORT_ALL holds, per node, exactly the samples that clip rule C3's
+ *      SIMLOD_CLIP_OUTSIDE edit keeps, in order. */
+
+/* simlod_footprint_buffer_min_bytes' value, whether a polygon is given or not. */
+uint64_t simlod_inverse_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+
+/* The inverse query (rules above; arguments as simlod_query_footprint's and simlod_query_lasso's, at most one of the two polygons).  Asynchronous
+ * on `stream` once the polygon has been read. */
+int simlod_query_inverse(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                         const SimlodFootprint* footprint /*or NULL*/, const SimlodLasso* lasso /*or NULL*/, uint32_t maxLevel, uint32_t select,
+                         void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples /*or NULL*/,
+                         uint64_t sampleCapacity, SimlodQueryCounts* counts, void* stream);
+
+/* simlod_paint_region on the inverse selection (rule I8).  The scratch minimum is simlod_paint_buffer_min_bytes. */
+int simlod_paint_inverse(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                         const SimlodFootprint* footprint /*or NULL*/, const SimlodLasso* lasso /*or NULL*/, const SimlodPaint* paint, void* scratch,
+                         uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, const uint32_t* colors /*ARRAY only*/,
+                         uint32_t* previous /*or NULL*/, uint64_t colorCapacity, SimlodQueryCounts* counts, void* stream);
+
+/* simlod_query_summary on the inverse selection (rule I8).  The scratch minimum is simlod_summary_buffer_min_bytes. */
+int simlod_query_summary_inverse(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                                 const SimlodFootprint* footprint /*or NULL*/, const SimlodLasso* lasso /*or NULL*/,
+                                 const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                                 SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary /*device*/, SimlodQueryCounts* counts,
+                                 void* stream);
+
 /* ---- ray queries: the first sample in a cone along each ray of a batch ----------------------------------------------------------------------
  * simlod_query_rays answers "what does this ray hit" for up to 2^20 rays at once: per ray the sample with the smallest parameter t that lies
  * within radius + spread * t of the ray, among the samples of the nodes simlod_export_octree(maxLevel, select) selects.  The source is only read.

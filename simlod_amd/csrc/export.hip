@@ -25,6 +25,9 @@
 // Lasso query, paint and summary (simlod_query_lasso, simlod_paint_lasso, simlod_query_summary_lasso): the footprint's sequences with a polygon on
 // the screen of a perspective camera in the extruded polygon's place — k_l_hier, k_l_count, k_l_write, k_el_paint, k_ls_partial — in
 // export_lasso.inc; the rules themselves in lasso_rules.hpp.
+// Inverse selections (simlod_query_inverse, simlod_paint_inverse, simlod_query_summary_inverse): the region's, the footprint's or the lasso's
+// sequences with every verdict turned round — k_iq_hier / k_if_hier / k_il_hier, which list every node as k_x_hier does, and the inverse instances
+// of the per-sample kernels — in export_inverse.inc; the rules themselves in inverse_rules.hpp.
 // Profile query (simlod_query_profile): k_pr_hier -> k_q_dir -> k_pr_count -> k_q_scan -> k_pr_write, the same sequence with a corridor along a
 // polyline on top of the planes and a record per returned sample, in export_profile.inc; the rules themselves in profile_rules.hpp.
 // View query (simlod_query_view): k_v_hier -> k_v_scan -> k_x_dir -> k_copy, the export's sequence with the camera's rules in the walk, in
@@ -55,6 +58,7 @@
 #include "paint_rules.hpp"
 #include "summary_rules.hpp"
 #include "lasso_rules.hpp"
+#include "inverse_rules.hpp"
 
 namespace simlod {
 namespace {
@@ -67,6 +71,7 @@ namespace {
 #include "export_paint.inc"    // PaintOp, PaintArgs, FootPaintArgs, paint_colour, e_paint, k_e_paint, k_ef_paint
 #include "export_summary.inc"  // SummaryPart, SummaryOp, SummaryArgs, FootSummaryArgs, hist_add, s_partial, k_s_partial, k_fs_partial, k_s_final
 #include "export_lasso.inc"    // LassoGeom, LassoArgs, LassoPaintArgs, LassoSummaryArgs, Lasso, k_l_hier, k_l_count, k_l_write, k_el_paint, k_ls_partial
+#include "export_inverse.inc"  // k_iq_hier, k_if_hier, k_il_hier, the inverse instances of q_count, q_write, e_paint and s_partial
 #include "export_profile.inc"  // ProfGeom, ProfArgs, stage_segments, Profile, k_pr_hier, k_pr_count, locate_record, k_pr_write
 #include "export_view.inc"     // ViewArgs, k_v_hier, k_v_scan
 #include "export_delta.inc"    // DeltaLayout, DeltaArgs, k_d_match, k_d_scan, k_d_dir, k_d_drop, MergeArgs, k_d_merge_scan, k_d_merge_dir
@@ -263,16 +268,54 @@ int launch_lasso(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats
 	return (int)hipGetLastError();
 }
 
+// simlod_query_inverse: the region's, the footprint's or the lasso's launches with the inverse walk and the inverse per-sample kernels.  The
+// polygon's block is kept free in front of the items whether there is a polygon or not: one minimum for the three (rule I9).
+uint64_t inverse_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return footprint_min_bytes(nodeCapacity, sampleBound); }
+
+int launch_inverse(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
+                   const SimlodFootprint* fp, const SimlodLasso* lasso, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                   SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
+	if (!inverse_polygons_acceptable(fp, lasso)) return (int)hipErrorInvalidValue;
+	FootGeom fg{};
+	LassoGeom lg{};
+	PolygonEdges pe;
+	if (fp != nullptr && !footprint_edges(fp, fg, pe)) return (int)hipErrorInvalidValue;
+	if (lasso != nullptr && !lasso_edges(lasso, lg, pe)) return (int)hipErrorInvalidValue;
+	QueryArgs q{};
+	const int rc = prepare_query(ctx, nodes, stats, u, region, maxLevel, select, scratch, scratchBytes, table, tableCapacity, samples, sampleCapacity, counts,
+	                             FOOT_BLOCK_BYTES, q);
+	if (rc != 0) return rc;
+	const uint32_t grid = copy_grid(q.x.lay.itemCap);
+	if (fp != nullptr) {
+		const hipError_t e = pe.upload(q, FOOT_BLOCK_BYTES, stream, fg.edges);
+		if (e != hipSuccess) return (int)e;
+		const FootArgs fa{q, fg};
+		SIMLOD_LAUNCH_SELECTION(k_if_hier, k_if_count, fa, q, tableCapacity, grid, stream);
+		if (samples != nullptr) SIMLOD_LAUNCH(k_if_write, dim3(grid), dim3(LANE_TPB), stream, fa);
+	} else if (lasso != nullptr) {
+		const hipError_t e = pe.upload(q, FOOT_BLOCK_BYTES, stream, lg.edges);
+		if (e != hipSuccess) return (int)e;
+		const LassoArgs la{q, lg};
+		SIMLOD_LAUNCH_SELECTION(k_il_hier, k_il_count, la, q, tableCapacity, grid, stream);
+		if (samples != nullptr) SIMLOD_LAUNCH(k_il_write, dim3(grid), dim3(LANE_TPB), stream, la);
+	} else {
+		SIMLOD_LAUNCH_SELECTION(k_iq_hier, k_iq_count, q, q, tableCapacity, grid, stream);
+		if (samples != nullptr) SIMLOD_LAUNCH(k_iq_write, dim3(grid), dim3(LANE_TPB), stream, q);
+	}
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
 constexpr uint64_t PAINT_BLOCK_BYTES = 256u * sizeof(uint32_t);                     // the ramp's table, in front of the items (behind the polygon's block)
 
 uint64_t paint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return footprint_min_bytes(nodeCapacity, sampleBound) + PAINT_BLOCK_BYTES; }
 
 // simlod_paint_region / simlod_paint_lasso: the footprint's or the lasso's launches as a count-only call (maxLevel 20, every node selected), the
 // polygon and the ramp's table in the scratch buffer's blocks in front of the items, then k_e_paint (no polygon), k_ef_paint or k_el_paint.
-// At most one of `fp` and `lasso`.
+// At most one of `fp` and `lasso`.  `inverse` (simlod_paint_inverse): the inverse selection's kernels in their places.
 int launch_paint(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
                  const SimlodFootprint* fp, const SimlodLasso* lasso, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
-                 uint32_t tableCapacity, const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts, hipStream_t stream) {
+                 uint32_t tableCapacity, const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts, hipStream_t stream, bool inverse) {
 	if (paint == nullptr || !paint_acceptable(*paint, colors != nullptr) || (fp != nullptr && lasso != nullptr)) return (int)hipErrorInvalidValue;
 	FootGeom fg{};
 	LassoGeom lg{};
@@ -299,18 +342,33 @@ int launch_paint(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats
 		const hipError_t e = pe.upload(q, front, stream, fg.edges);
 		if (e != hipSuccess) return (int)e;
 		const FootPaintArgs fa{{q, fg}, p};
-		SIMLOD_LAUNCH_SELECTION(k_f_hier, k_f_count, fa.f, q, tableCapacity, grid, stream);
-		SIMLOD_LAUNCH(k_ef_paint, dim3(grid), dim3(LANE_TPB), stream, fa);
+		if (inverse) {
+			SIMLOD_LAUNCH_SELECTION(k_if_hier, k_if_count, fa.f, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_ief_paint, dim3(grid), dim3(LANE_TPB), stream, fa);
+		} else {
+			SIMLOD_LAUNCH_SELECTION(k_f_hier, k_f_count, fa.f, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_ef_paint, dim3(grid), dim3(LANE_TPB), stream, fa);
+		}
 	} else if (lasso != nullptr) {
 		const hipError_t e = pe.upload(q, front, stream, lg.edges);
 		if (e != hipSuccess) return (int)e;
 		const LassoPaintArgs la{{q, lg}, p};
-		SIMLOD_LAUNCH_SELECTION(k_l_hier, k_l_count, la.f, q, tableCapacity, grid, stream);
-		SIMLOD_LAUNCH(k_el_paint, dim3(grid), dim3(LANE_TPB), stream, la);
+		if (inverse) {
+			SIMLOD_LAUNCH_SELECTION(k_il_hier, k_il_count, la.f, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_iel_paint, dim3(grid), dim3(LANE_TPB), stream, la);
+		} else {
+			SIMLOD_LAUNCH_SELECTION(k_l_hier, k_l_count, la.f, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_el_paint, dim3(grid), dim3(LANE_TPB), stream, la);
+		}
 	} else {
 		const PaintArgs pa{q, p};
-		SIMLOD_LAUNCH_SELECTION(k_q_hier, k_q_count, q, q, tableCapacity, grid, stream);
-		SIMLOD_LAUNCH(k_e_paint, dim3(grid), dim3(LANE_TPB), stream, pa);
+		if (inverse) {
+			SIMLOD_LAUNCH_SELECTION(k_iq_hier, k_iq_count, q, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_ie_paint, dim3(grid), dim3(LANE_TPB), stream, pa);
+		} else {
+			SIMLOD_LAUNCH_SELECTION(k_q_hier, k_q_count, q, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_e_paint, dim3(grid), dim3(LANE_TPB), stream, pa);
+		}
 	}
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();
@@ -334,10 +392,12 @@ uint32_t summary_grid(uint64_t itemCap, uint32_t maxWorkgroups) {
 
 // simlod_query_summary / simlod_query_summary_lasso: the footprint's or the lasso's launches as a count-only call with the caller's maxLevel and
 // select, the polygon and the partial records in the scratch buffer's blocks in front of the items, then k_s_partial (no polygon), k_fs_partial or
-// k_ls_partial, then k_s_final.  At most one of `fp` and `lasso`.
+// k_ls_partial, then k_s_final.  At most one of `fp` and `lasso`.  `inverse` (simlod_query_summary_inverse): the inverse selection's kernels in
+// their places.
 int launch_summary(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
                    const SimlodFootprint* fp, const SimlodLasso* lasso, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select, void* scratch,
-                   uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts, hipStream_t stream) {
+                   uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts, hipStream_t stream,
+                   bool inverse) {
 	if (params == nullptr || summary == nullptr || !summary_acceptable(*params) || (reinterpret_cast<uintptr_t>(summary) & 7u) != 0u) return (int)hipErrorInvalidValue;
 	if (fp != nullptr && lasso != nullptr) return (int)hipErrorInvalidValue;
 	FootGeom fg{};
@@ -359,18 +419,33 @@ int launch_summary(Context& ctx, const SimlodNode* nodes, const SimlodStats* sta
 		const hipError_t e = pe.upload(q, front, stream, fg.edges);
 		if (e != hipSuccess) return (int)e;
 		const FootSummaryArgs fa{{q, fg}, s};
-		SIMLOD_LAUNCH_SELECTION(k_f_hier, k_f_count, fa.f, q, tableCapacity, grid, stream);
-		SIMLOD_LAUNCH(k_fs_partial, dim3(sgrid), dim3(LANE_TPB), stream, fa);
+		if (inverse) {
+			SIMLOD_LAUNCH_SELECTION(k_if_hier, k_if_count, fa.f, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_ifs_partial, dim3(sgrid), dim3(LANE_TPB), stream, fa);
+		} else {
+			SIMLOD_LAUNCH_SELECTION(k_f_hier, k_f_count, fa.f, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_fs_partial, dim3(sgrid), dim3(LANE_TPB), stream, fa);
+		}
 	} else if (lasso != nullptr) {
 		const hipError_t e = pe.upload(q, front, stream, lg.edges);
 		if (e != hipSuccess) return (int)e;
 		const LassoSummaryArgs la{{q, lg}, s};
-		SIMLOD_LAUNCH_SELECTION(k_l_hier, k_l_count, la.f, q, tableCapacity, grid, stream);
-		SIMLOD_LAUNCH(k_ls_partial, dim3(sgrid), dim3(LANE_TPB), stream, la);
+		if (inverse) {
+			SIMLOD_LAUNCH_SELECTION(k_il_hier, k_il_count, la.f, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_ils_partial, dim3(sgrid), dim3(LANE_TPB), stream, la);
+		} else {
+			SIMLOD_LAUNCH_SELECTION(k_l_hier, k_l_count, la.f, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_ls_partial, dim3(sgrid), dim3(LANE_TPB), stream, la);
+		}
 	} else {
 		const SummaryArgs sa{q, s};
-		SIMLOD_LAUNCH_SELECTION(k_q_hier, k_q_count, q, q, tableCapacity, grid, stream);
-		SIMLOD_LAUNCH(k_s_partial, dim3(sgrid), dim3(LANE_TPB), stream, sa);
+		if (inverse) {
+			SIMLOD_LAUNCH_SELECTION(k_iq_hier, k_iq_count, q, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_is_partial, dim3(sgrid), dim3(LANE_TPB), stream, sa);
+		} else {
+			SIMLOD_LAUNCH_SELECTION(k_q_hier, k_q_count, q, q, tableCapacity, grid, stream);
+			SIMLOD_LAUNCH(k_s_partial, dim3(sgrid), dim3(LANE_TPB), stream, sa);
+		}
 	}
 	SIMLOD_LAUNCH(k_s_final, dim3(SUMMARY_FINAL_HIST_WGS + 1u), dim3(WG_TPB), stream, fin);
 	if (profile_enabled()) profile_close(stream);

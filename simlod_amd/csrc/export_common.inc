@@ -88,8 +88,9 @@ struct ExportArgs {
 	uint32_t           ltMagicValue, ltSlots, ltRows;
 };
 
-// the class of a table entry against a query's region (cls[] in the scratch buffer; the pair queries tag every entry as copied)
-enum : uint32_t { Q_OUTSIDE = 0u, Q_FILTERED = 1u, Q_COPIED = 2u };
+// the class of a table entry against a query's region (cls[] in the scratch buffer; the pair queries tag every entry as copied).  Q_EMPTIED
+// (the inverse selections only, export_inverse.inc): listed, contributes nothing — what an outside root is, for any node
+enum : uint32_t { Q_OUTSIDE = 0u, Q_FILTERED = 1u, Q_COPIED = 2u, Q_EMPTIED = 3u };
 
 // Does the builder's chunk table describe node `src` of this octree as it is now (render.hip visible_nodes: the same four stamp words), and
 // does its row start at the list's head?  `leaf`: the list is the node's points.  Never the voxel row of the ROOT: the builder keeps no such

@@ -48,8 +48,8 @@ __device__ __forceinline__ uint32_t paint_colour(const PaintOp& p, const uint32_
 	}
 }
 
-// the body of both paint kernels; extra(v) as in q_count
-template <typename Args, typename Extra>
+// the body of the paint kernels; extra(v) and INVERT as in q_count
+template <typename Args, bool INVERT = false, typename Extra>
 __device__ __forceinline__ void e_paint(const Args& args, Extra extra) {
 	const QueryArgs& q = query_of(args);
 	const PaintOp& p = args.p;
@@ -99,7 +99,8 @@ __device__ __forceinline__ void e_paint(const Args& args, Extra extra) {
 #pragma unroll
 			for (int j = 0; j < 4; j++) {
 				const uint32_t k = threadIdx.x + (uint32_t)j * LANE_TPB;
-				b[j] = __ballot(k < it.count && passes(q.g, v[j]) && extra(v[j]));
+				if (INVERT) b[j] = __ballot(k < it.count && !(passes(q.g, v[j]) && extra(v[j])));
+				else b[j] = __ballot(k < it.count && passes(q.g, v[j]) && extra(v[j]));
 				on[j] = ((b[j] >> lane) & 1ull) != 0ull;
 				rank[j] = 0u;
 			}

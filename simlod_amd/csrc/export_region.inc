@@ -173,8 +173,10 @@ __device__ __forceinline__ const QueryArgs& query_of(const QueryArgs& q) { retur
 // (the plane-only query: no footprint to ask — k_f_count / k_f_write, export_footprint.inc, bring theirs)
 struct NoFootprint { __device__ __forceinline__ bool operator()(const u32x4&) const { return true; } };
 
-// k_q_count's body; extra(v): what a sample has to pass on top of the planes (rule F1 of a footprint query)
-template <typename Args, typename Extra>
+// k_q_count's body; extra(v): what a sample has to pass on top of the planes (rule F1 of a footprint query).  INVERT (the inverse selections,
+// export_inverse.inc; here and in q_write, e_paint and s_partial): a sample is taken iff it FAILS the planes' and extra's test, rule I1 — a
+// compile-time choice between two expressions, so that the instances without it are the code they were.
+template <typename Args, bool INVERT = false, typename Extra>
 __device__ __forceinline__ void q_count(Args args, Extra extra) {
 	const QueryArgs& q = query_of(args);
 	__shared__ uint32_t sh_cnt[2][LANE_TPB / SIMLOD_WAVE];
@@ -194,7 +196,8 @@ __device__ __forceinline__ void q_count(Args args, Extra extra) {
 #pragma unroll
 		for (int j = 0; j < 4; j++) {
 			const uint32_t k = threadIdx.x + (uint32_t)j * LANE_TPB;
-			c += (uint32_t)__popcll(__ballot(k < cnt && passes(q.g, v[j]) && extra(v[j])));
+			if (INVERT) c += (uint32_t)__popcll(__ballot(k < cnt && !(passes(q.g, v[j]) && extra(v[j]))));
+			else c += (uint32_t)__popcll(__ballot(k < cnt && passes(q.g, v[j]) && extra(v[j])));
 		}
 		if (lane == 0) sh_cnt[turn][w] = c;
 		__syncthreads();                    // (two buffers: the next turn's writes cannot overtake this turn's read)
@@ -251,8 +254,8 @@ __global__ __launch_bounds__(WG_TPB) void k_q_scan(QueryArgs q) {
 	}
 }
 
-// k_q_write's body; extra(v) as in q_count
-template <typename Args, typename Extra>
+// k_q_write's body; extra(v) and INVERT as in q_count
+template <typename Args, bool INVERT = false, typename Extra>
 __device__ __forceinline__ void q_write(Args args, Extra extra) {
 	const QueryArgs& q = query_of(args);
 	__shared__ uint32_t sh_seg[2][16];
@@ -276,7 +279,8 @@ __device__ __forceinline__ void q_write(Args args, Extra extra) {
 #pragma unroll
 		for (int j = 0; j < 4; j++) {
 			const uint32_t k = threadIdx.x + (uint32_t)j * LANE_TPB;
-			b[j] = __ballot(k < it.count && passes(q.g, v[j]) && extra(v[j]));
+			if (INVERT) b[j] = __ballot(k < it.count && !(passes(q.g, v[j]) && extra(v[j])));
+			else b[j] = __ballot(k < it.count && passes(q.g, v[j]) && extra(v[j]));
 			if (lane == 0) sh_seg[turn][j * 4 + w] = (uint32_t)__popcll(b[j]);
 		}
 		__syncthreads();                    // (two buffers, as in k_q_count)

@@ -89,8 +89,8 @@ __device__ __forceinline__ void summary_fetch(const QItem* items, uint64_t i, ui
 	}
 }
 
-// the body of both partial kernels; extra(v) as in q_count
-template <typename Args, typename Extra>
+// the body of the partial kernels; extra(v) and INVERT as in q_count
+template <typename Args, bool INVERT = false, typename Extra>
 __device__ __forceinline__ void s_partial(const Args& args, Extra extra) {
 	const QueryArgs& q = query_of(args);
 	const SummaryOp& sp = args.s;
@@ -123,7 +123,8 @@ __device__ __forceinline__ void s_partial(const Args& args, Extra extra) {
 			for (int j = 0; j < 4; j++) {
 				const uint32_t k = threadIdx.x + (uint32_t)j * LANE_TPB;
 				bool on = k < it.count;
-				if (!copied) on = on && passes(q.g, v[j]) && extra(v[j]);
+				if (INVERT) { if (!copied) on = on && !(passes(q.g, v[j]) && extra(v[j])); }
+				else if (!copied) on = on && passes(q.g, v[j]) && extra(v[j]);
 				if (on) {
 					const uint32_t bits[3] = {v[j].x, v[j].y, v[j].z};
 					uint32_t c16[3];

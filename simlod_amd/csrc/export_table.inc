@@ -6,8 +6,11 @@
 // classify(level, X, Y, Z): the class of that cube (QUERY only; NoRegion where there is no region to ask).
 // entry(t, e, srcLeaf): what a walk does per listed entry on top, with the entry as it is about to be written (k_v_hier, export_view.inc: the
 // entries of the levels above are written, and a barrier lies in between); NoEntry: nothing.
+// QUERY is false (WALK_EXPORT), true (WALK_QUERY) or WALK_INVERSE (the inverse selections, export_inverse.inc): the classes are written, but no
+// child is asked and none is left out — the table is the export's —, and an entry of class Q_EMPTIED loses its samples as an outside root does.
+constexpr uint32_t WALK_EXPORT = 0u, WALK_QUERY = 1u, WALK_INVERSE = 2u;
 struct NoEntry { __device__ __forceinline__ void operator()(uint32_t, const SimlodExportNode&, bool) const {} };
-template <bool QUERY, typename Classify, typename Entry = NoEntry>
+template <uint32_t QUERY, typename Classify, typename Entry = NoEntry>
 __device__ __forceinline__ void hier_walk(const ExportArgs& a, Classify classify, uint32_t* cls, Entry entry = Entry()) {
 	__shared__ uint32_t sh_scan[WG_WAVES];
 	__shared__ uint32_t sh_err, sh_trunc;
@@ -44,7 +47,7 @@ __device__ __forceinline__ void hier_walk(const ExportArgs& a, Classify classify
 					child[k] = (uint32_t)idx;
 					if (L >= maxLevel) continue;
 					// (the child's cube follows from its parent's: no load of the child's record, which would put eight dependent loads in a row)
-					if (QUERY && classify(n->level + 1u, 2u * n->X + ((k >> 2) & 1), 2u * n->Y + ((k >> 1) & 1), 2u * n->Z + (k & 1)) == Q_OUTSIDE) {
+					if (QUERY == WALK_QUERY && classify(n->level + 1u, 2u * n->X + ((k >> 2) & 1), 2u * n->Y + ((k >> 1) & 1), 2u * n->Z + (k & 1)) == Q_OUTSIDE) {
 						atomicOr(&sh_trunc, 1u);
 						continue;
 					}
@@ -82,7 +85,7 @@ __device__ __forceinline__ void hier_walk(const ExportArgs& a, Classify classify
 				e.firstSample = 0;
 				if (QUERY) {
 					const uint32_t c = classify(e.level, e.X, e.Y, e.Z);              // (only the root can be outside here)
-					if (c == Q_OUTSIDE) e.numSamples = 0u;
+					if (c == Q_OUTSIDE || (QUERY == WALK_INVERSE && c == Q_EMPTIED)) e.numSamples = 0u;
 					cls[t] = c;
 				}
 				entry(t, e, srcLeaf);

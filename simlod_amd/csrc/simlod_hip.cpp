@@ -539,6 +539,35 @@ int simlod_query_summary_lasso(const SimlodNode* nodes, const SimlodStats* stats
 	                      tableCapacity, summary, counts, (hipStream_t)stream);
 }
 
+uint64_t simlod_inverse_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return inverse_min_bytes(nodeCapacity, sampleBound); }
+
+int simlod_query_inverse(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                         const SimlodFootprint* footprint, const SimlodLasso* lasso, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                         SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts,
+                         void* stream) {
+	if (nodes == nullptr) return (int)hipErrorInvalidValue;
+	return launch_inverse(context_of(nodes), nodes, stats, uniforms, region, footprint, lasso, maxLevel, select, scratch, scratchBytes, table, tableCapacity,
+	                      samples, sampleCapacity, counts, (hipStream_t)stream);
+}
+
+int simlod_paint_inverse(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                         const SimlodFootprint* footprint, const SimlodLasso* lasso, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes,
+                         SimlodExportNode* table, uint32_t tableCapacity, const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity,
+                         SimlodQueryCounts* counts, void* stream) {
+	if (nodes == nullptr) return (int)hipErrorInvalidValue;
+	return launch_paint(context_of(nodes), nodes, stats, uniforms, region, footprint, lasso, paint, scratch, scratchBytes, table, tableCapacity, colors, previous,
+	                    colorCapacity, counts, (hipStream_t)stream, true);
+}
+
+int simlod_query_summary_inverse(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,
+                                 const SimlodFootprint* footprint, const SimlodLasso* lasso, const SimlodSummaryParams* params, uint32_t maxLevel,
+                                 uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
+                                 SimlodSummary* summary, SimlodQueryCounts* counts, void* stream) {
+	if (nodes == nullptr) return (int)hipErrorInvalidValue;
+	return launch_summary(context_of(nodes), nodes, stats, uniforms, region, footprint, lasso, params, maxLevel, select, scratch, scratchBytes, table,
+	                      tableCapacity, summary, counts, (hipStream_t)stream, true);
+}
+
 uint64_t simlod_profile_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound) { return profile_min_bytes(nodeCapacity, sampleBound); }
 
 int simlod_query_profile(const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* uniforms, const SimlodRegion* region,

@@ -191,15 +191,21 @@ int launch_lasso(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats
                  const SimlodLasso* lasso, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
                  uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream);
 uint64_t lasso_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
-// (paint and summary: at most one of `footprint` and `lasso`)
+// (the inverse selection: at most one of `footprint` and `lasso`, or neither)
+int launch_inverse(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
+                   const SimlodFootprint* footprint, const SimlodLasso* lasso, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes,
+                   SimlodExportNode* table, uint32_t tableCapacity, SimlodPoint* samples, uint64_t sampleCapacity, SimlodQueryCounts* counts, hipStream_t stream);
+uint64_t inverse_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
+// (paint and summary: at most one of `footprint` and `lasso`; `inverse`: simlod_paint_inverse / simlod_query_summary_inverse)
 int launch_paint(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
                  const SimlodFootprint* footprint, const SimlodLasso* lasso, const SimlodPaint* paint, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,
-                 uint32_t tableCapacity, const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts, hipStream_t stream);
+                 uint32_t tableCapacity, const uint32_t* colors, uint32_t* previous, uint64_t colorCapacity, SimlodQueryCounts* counts, hipStream_t stream,
+                 bool inverse = false);
 uint64_t paint_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
 int launch_summary(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
                    const SimlodFootprint* footprint, const SimlodLasso* lasso, const SimlodSummaryParams* params, uint32_t maxLevel, uint32_t select,
                    void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity, SimlodSummary* summary, SimlodQueryCounts* counts,
-                   hipStream_t stream);
+                   hipStream_t stream, bool inverse = false);
 uint64_t summary_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound);
 int launch_profile(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRegion* region,
                    const SimlodProfile* profile, uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table,

@@ -144,7 +144,8 @@ class OctreeExport:
             return False
         return True
 
-    def crop(self, region, max_level=None, select="all", return_counts=False, footprint=None, profile=None, test_every_sample=False, return_index=False, lasso=None):
+    def crop(self, region, max_level=None, select="all", return_counts=False, footprint=None, profile=None, test_every_sample=False, return_index=False, lasso=None,
+             invert=False):
         """The host mirror of simlod_query_region: what the device returns for `region` on the octree this FULL export (select "all", max level
         20; anything else ValueError) was taken from, as an OctreeExport on the host — and, return_counts, the SimlodQueryCounts record too.
         footprint (a Footprint): the mirror of simlod_query_footprint — rules F1-F4 on top of the planes; rule F5's promise is asserted for
@@ -153,9 +154,15 @@ class OctreeExport:
         rule P4's promise is asserted likewise.  test_every_sample: the same nodes are listed, but none counts as copied.
         lasso (a Lasso): the mirror of simlod_query_lasso — rules L1-L4 on top of the planes; rule L5's promise is asserted likewise.  A lasso
         together with a footprint or a profile is a ValueError.
-        return_index: the last element of the result is, per returned sample, its index in this export's samples (int64)."""
+        return_index: the last element of the result is, per returned sample, its index in this export's samples (int64).
+        invert: the mirror of simlod_query_inverse (include/simlod_hip.h, "inverse selections") — the classes the positive path computes,
+        mapped by rule I2 (outside -> copied, copied -> emptied, filtered stays and takes the samples that FAIL the test); no node is left out
+        of the walk (rule I3).  The F5 / L5 assertions stay as they are: an outside node holds no sample of the contract that passes, a copied
+        node none that fails — the two facts the inverse relies on.  With a profile: ValueError."""
         if lasso is not None and (footprint is not None or profile is not None):
             raise ValueError("a lasso does not combine with a footprint or a profile in one call")
+        if invert and profile is not None:
+            raise ValueError("inverse profile queries are not covered")
         if self.select != abi.EXPORT_ALL or self.max_level < abi.MAX_DEPTH:
             raise ValueError(f"crop needs a full export (select all, max level 20), not select {self.select} / max level {self.max_level}")
         sel = abi.EXPORT_SELECT[select] if isinstance(select, str) else int(select)
@@ -191,7 +198,7 @@ class OctreeExport:
                 for k in range(8):
                     if not (int(nd["childMask"]) >> k) & 1:
                         continue
-                    if not outside[c]:
+                    if invert or not outside[c]:
                         if first == abi.EXPORT_NONE:
                             first = len(order)
                         mask |= 1 << k
@@ -207,7 +214,8 @@ class OctreeExport:
         leaf = (out["flags"] & abi.EXPORT_FLAG_LEAF) != 0
         chosen = np.ones(len(out), bool) if sel == abi.EXPORT_ALL else leaf | (out["level"] == ml)
         out["flags"] = np.where(leaf, abi.EXPORT_FLAG_LEAF, 0) | np.where(chosen, abi.EXPORT_FLAG_SELECTED, 0)
-        cand = np.where(chosen & ~outside[order], src["numSamples"][order], 0).astype(np.int64)
+        # (inverse: the emptied nodes — the positive query's copied ones — contribute nothing, rule I4)
+        cand = np.where(chosen & ~(inside if invert else outside)[order], src["numSamples"][order], 0).astype(np.int64)
         # rule 3 on every sample at once; rule 4's promise on the samples of the contract (finite, in the half-open box)
         x, y, z = (smp[a].astype(np.float64) for a in ("x", "y", "z"))
         ok = np.ones(len(smp), bool)
@@ -225,13 +233,26 @@ class OctreeExport:
             # rule F5 / P4 / L5 for every outside node of the source, listed or not: none of its samples of the contract passes (the copied ones below)
             bad = ok & inbox & np.repeat(outside, src["numSamples"].astype(np.int64))
             assert not bad.any(), f"node {int(np.repeat(np.arange(len(src)), src['numSamples'].astype(np.int64))[bad][0])} is outside and holds a sample of the box that passes the test"
+        if invert:
+            # the positive path's assertion for its copied nodes, which the inverse empties: none of their samples of the contract fails
+            for i in np.nonzero(inside & (src["numSamples"] != 0))[0]:
+                a = int(src["firstSample"][i])
+                seg = slice(a, a + int(src["numSamples"][i]))
+                assert (ok[seg] | ~inbox[seg]).all(), f"node {i} is copied and holds a sample of the box that fails the test"
         parts, ns_out = [], np.zeros(len(out), np.int64)
         n_filtered = n_copied = 0
         for t in np.nonzero(cand)[0]:
             i = order[t]
             a = int(src["firstSample"][i])
             seg = slice(a, a + int(cand[t]))
-            if inside[i]:
+            if invert:
+                if outside[i]:                                      # rule I2: every sample, no test
+                    parts.append(np.arange(seg.start, seg.stop, dtype=np.int64))
+                    n_copied += 1
+                else:                                               # rule I1
+                    parts.append(seg.start + np.nonzero(~ok[seg])[0].astype(np.int64))
+                    n_filtered += 1
+            elif inside[i]:
                 assert (ok[seg] | ~inbox[seg]).all(), f"node {i} is copied and holds a sample of the box that fails the test"
                 parts.append(np.arange(seg.start, seg.stop, dtype=np.int64))
                 n_copied += 1
@@ -253,13 +274,14 @@ class OctreeExport:
         return got if len(got) > 1 else ex
 
     # -- paint regions (include/simlod_hip.h, "paint regions") -----------------------------------------------------------------------------
-    def paint(self, region, paint, footprint=None, colors=None, return_previous=False, lasso=None):
+    def paint(self, region, paint, footprint=None, colors=None, return_previous=False, lasso=None, invert=False):
         """The host mirror of simlod_paint_region on the octree this FULL export was taken from: (this export with the colours of the target
         samples changed — a new OctreeExport on the host; table, positions and order are this one's —, the SimlodQueryCounts record) and,
         return_previous, the colour words those samples had, in the query's order (uint32).  The target set and its order are crop's (rule
         E0: max level 20, select "all"), so rule F5's assertion stays in force.  colors: the uint32 words of an ARRAY paint, one per target
-        sample at least.  lasso (a Lasso, no footprint then): the mirror of simlod_paint_lasso, the target set being crop(lasso=)'s."""
-        _, c, index = self.crop(region, abi.MAX_DEPTH, "all", return_counts=True, footprint=footprint, return_index=True, lasso=lasso)
+        sample at least.  lasso (a Lasso, no footprint then): the mirror of simlod_paint_lasso, the target set being crop(lasso=)'s.
+        invert: the mirror of simlod_paint_inverse, the target set being crop(invert=True)'s (rule I8)."""
+        _, c, index = self.crop(region, abi.MAX_DEPTH, "all", return_counts=True, footprint=footprint, return_index=True, lasso=lasso, invert=invert)
         smp = self.samples.copy()
         previous = smp["color"][index].copy()
         if paint.mode == abi.PAINT_ARRAY:
@@ -276,14 +298,15 @@ class OctreeExport:
         return (ex, c, previous) if return_previous else (ex, c)
 
     # -- summary queries (include/simlod_hip.h, "summary queries") -------------------------------------------------------------------------
-    def summarize(self, region, max_level=None, select="cut", footprint=None, z0=0.0, scale=1.0, return_counts=False, lasso=None):
+    def summarize(self, region, max_level=None, select="cut", footprint=None, z0=0.0, scale=1.0, return_counts=False, lasso=None, invert=False):
         """The host mirror of simlod_query_summary on the octree this FULL export was taken from: the Summary of the samples
         crop(region, max_level, select, footprint=footprint) returns (rule S0: the set is crop's by construction) — and, return_counts, the
         SimlodQueryCounts record too.  Rules S1-S4 in numpy float64 and unsigned integers, in the order the header gives; the z histogram's
         index is Paint.ramp_index (rule E3) with z0 and scale as float32.  lasso (a Lasso, no footprint then): the mirror of
-        simlod_query_summary_lasso, the set being crop(lasso=)'s."""
+        simlod_query_summary_lasso, the set being crop(lasso=)'s.  invert: the mirror of simlod_query_summary_inverse, the set being
+        crop(invert=True)'s (rule I8)."""
         bins = Paint(abi.PAINT_RAMP, z0=z0, scale=scale)                    # (refuses what rule S8 refuses of z0 and scale)
-        ex, c = self.crop(Region() if region is None else region, max_level, select, return_counts=True, footprint=footprint, lasso=lasso)
+        ex, c = self.crop(Region() if region is None else region, max_level, select, return_counts=True, footprint=footprint, lasso=lasso, invert=invert)
         smp = ex.samples
         mn, size = _box_of(self.box_min, self.box_max)
         rec = np.zeros((), dtype=abi.summary_dtype)

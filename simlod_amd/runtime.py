@@ -110,6 +110,11 @@ def lib():
         L.simlod_query_lasso.argtypes = L.simlod_query_footprint.argtypes
         L.simlod_paint_lasso.argtypes = L.simlod_paint_region.argtypes
         L.simlod_query_summary_lasso.argtypes = L.simlod_query_summary.argtypes
+        L.simlod_inverse_buffer_min_bytes.restype = u64
+        L.simlod_inverse_buffer_min_bytes.argtypes = [u32, u64]
+        L.simlod_query_inverse.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp]
+        L.simlod_paint_inverse.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64, vp, u32, vp, vp, u64, vp, vp]
+        L.simlod_query_summary_inverse.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, vp, vp]
         L.simlod_profile_buffer_min_bytes.restype = u64
         L.simlod_profile_buffer_min_bytes.argtypes = [u32, u64]
         L.simlod_query_profile.argtypes = [vp, vp, vp, vp, vp, u32, u32, vp, u64, vp, u32, vp, u64, vp, vp, vp]
@@ -153,6 +158,7 @@ EXPORTED_SYMBOLS = [
     "simlod_paint_buffer_min_bytes", "simlod_paint_region",
     "simlod_summary_buffer_min_bytes", "simlod_query_summary",
     "simlod_lasso_buffer_min_bytes", "simlod_query_lasso", "simlod_paint_lasso", "simlod_query_summary_lasso",
+    "simlod_inverse_buffer_min_bytes", "simlod_query_inverse", "simlod_paint_inverse", "simlod_query_summary_inverse",
 ]
 
 
@@ -691,16 +697,24 @@ class DeviceOctree:
         if footprint is not None and lasso is not None:
             raise ValueError("a lasso does not combine with a footprint in one call")
 
-    def _query(self, uniforms, region, ml, sel, table, samples, sample_capacity, bound, footprint=None, lasso=None):
+    def _query(self, uniforms, region, ml, sel, table, samples, sample_capacity, bound, footprint=None, lasso=None, invert=False):
         """One simlod_query_region call — with a footprint (an octree_io.Footprint) one simlod_query_footprint call, with a lasso (an
-        octree_io.Lasso) one simlod_query_lasso call — -> the SimlodQueryCounts record (host).  samples None: count only."""
+        octree_io.Lasso) one simlod_query_lasso call; invert: one simlod_query_inverse call with whichever polygon there is — -> the
+        SimlodQueryCounts record (host).  samples None: count only."""
         self._one_polygon(footprint, lasso)
         u, up = self._u(uniforms)
         r = region.record()
         nn = table.numel() // abi.export_node_dtype.itemsize
         counts = torch.zeros(abi.query_counts_dtype.itemsize, dtype=torch.uint8, device=self.device)
         tail = (self._p(table), nn, None if samples is None else self._p(samples), ctypes.c_uint64(sample_capacity), self._p(counts), self._stream())
-        if lasso is not None:
+        if invert:
+            what = "simlod_query_inverse"
+            f, l = (None if p is None else p.record() for p in (footprint, lasso))
+            scratch = self._export_scratch(int(self.L.simlod_inverse_buffer_min_bytes(nn, bound)))
+            rc = self.L.simlod_query_inverse(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data),
+                                             None if f is None else ctypes.c_void_p(f.ctypes.data), None if l is None else ctypes.c_void_p(l.ctypes.data),
+                                             ml, sel, self._p(scratch), ctypes.c_uint64(scratch.numel()), *tail)
+        elif lasso is not None:
             what = "simlod_query_lasso"
             f = lasso.record()
             scratch = self._export_scratch(int(self.L.simlod_lasso_buffer_min_bytes(nn, bound)))
@@ -732,42 +746,57 @@ class DeviceOctree:
     def _table(self, nn):
         return torch.empty(max(nn, 1) * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
 
-    def count_region(self, uniforms, region, max_level=None, select="cut", footprint=None, lasso=None):
+    def count_region(self, uniforms, region, max_level=None, select="cut", footprint=None, lasso=None, invert=False):
         """How much of the octree lies in `region` (an octree_io.Region) at `max_level`: the SimlodQueryCounts record of a count-only
         simlod_query_region call (numNodes, numSamples, numCandidates, numFilteredNodes, numCopiedNodes).  No sample is written.
         footprint (an octree_io.Footprint): inside that extruded polygon as well, by simlod_query_footprint.
-        lasso (an octree_io.Lasso, no footprint then): inside that polygon on the screen as well, by simlod_query_lasso."""
+        lasso (an octree_io.Lasso, no footprint then): inside that polygon on the screen as well, by simlod_query_lasso.
+        invert: how much lies OUTSIDE that selection, by simlod_query_inverse (numNodes is then the export's: nothing is culled)."""
         self._one_polygon(footprint, lasso)
         sel, ml, nn, bound = self._query_setup(max_level, select)
-        return self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound, footprint, lasso)
+        return self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound, footprint, lasso, invert)
 
-    def query_region(self, uniforms, region, max_level=None, select="cut", return_counts=False, footprint=None, lasso=None):
+    def query_region(self, uniforms, region, max_level=None, select="cut", return_counts=False, footprint=None, lasso=None, invert=False):
         """The samples inside `region` as an octree_io.OctreeExport on this device (select abi.EXPORT_REGION): the pruned table and, in chunk-list
         order, the samples of the selected nodes ("cut": source leaves and the nodes at max_level; "all": every listed node) that pass the
         region's test.  A count-only call first, then the outputs sized exactly.  Raises SimlodError when the device reports an error.
         footprint (an octree_io.Footprint): the samples that are inside that extruded polygon as well, by simlod_query_footprint.
-        lasso (an octree_io.Lasso, no footprint then): the samples inside that polygon on the screen as well, by simlod_query_lasso."""
+        lasso (an octree_io.Lasso, no footprint then): the samples inside that polygon on the screen as well, by simlod_query_lasso.
+        invert: the samples that FAIL the selection's test, by simlod_query_inverse ("inverse selections"): the table is then the export's,
+        unpruned, with the nodes the selection swallows whole listed empty — import_octree(result) is the octree with the selection erased."""
         from .octree_io import OctreeExport
         self._one_polygon(footprint, lasso)
         sel, ml, nn, bound = self._query_setup(max_level, select)
-        c = self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound, footprint, lasso)
+        c = self._query(uniforms, region, ml, sel, self._table(nn), None, 0, bound, footprint, lasso, invert)
         nn, ns = int(c["numNodes"]), int(c["numSamples"])
         table = torch.empty(nn * abi.export_node_dtype.itemsize, dtype=torch.uint8, device=self.device)
         samples = torch.empty(max(ns, 1) * abi.point_dtype.itemsize, dtype=torch.uint8, device=self.device)
-        c = self._query(uniforms, region, ml, sel, table, samples, ns, bound, footprint, lasso)
+        c = self._query(uniforms, region, ml, sel, table, samples, ns, bound, footprint, lasso, invert)
         u = np.asarray(uniforms).reshape(-1)[0]
         ex = OctreeExport(table, samples[: int(c["numSamples"]) * abi.point_dtype.itemsize], u["boxMin"], u["boxMax"], ml, abi.EXPORT_REGION)
         return (ex, c) if return_counts else ex
 
+    def erase_region(self, uniforms, region, footprint=None, lasso=None):
+        """Delete, from this octree, the samples query_region(region, 20, "all", footprint / lasso) returns: the inverse query at level 20,
+        select "all", on the device, then import_octree of its result into this octree — the frame SIMLOD_CLIP_OUTSIDE draws, made permanent.
+        -> the SimlodQueryCounts record of the inverse query (numSamples: the samples that are left).  The tree keeps its shape: a node that
+        lost every sample stays listed, empty.  As after any import_octree the octree is render-only until the next reset: construct() and
+        colorfilter() refuse it.  What is removed is gone — run query_region with the same arguments first to keep it."""
+        ex, c = self.query_region(uniforms, region, abi.MAX_DEPTH, "all", return_counts=True, footprint=footprint, lasso=lasso, invert=True)
+        self.import_octree(ex)
+        return c
+
     # -- paint regions (include/simlod_hip.h, "paint regions") -----------------------------------------------------------------------------
-    def paint_region(self, uniforms, region, paint, footprint=None, colors=None, return_previous=False, lasso=None):
+    def paint_region(self, uniforms, region, paint, footprint=None, colors=None, return_previous=False, lasso=None, invert=False):
         """Recolour, in the octree itself, the samples simlod_query_footprint(region, footprint, 20, "all") returns — `paint` (an
         octree_io.Paint) says how: set, blend, ramp by height, or array (then `colors`: one uint32 word per sample in the query's order, a
         tensor on this device or anything numpy takes) — by one simlod_paint_region call.  -> the SimlodQueryCounts record (numSamples: the
         number painted), and with return_previous (that record, the colour words the samples had: a uint32 tensor on this device, which an
         array paint of the same region and footprint puts back).  Raises SimlodError when the device reports an error; then nothing was
         painted.  No frame, query or ingest of this octree may be in flight on another stream.
-        lasso (an octree_io.Lasso, no footprint then): the samples simlod_query_lasso(region, lasso, 20, "all") returns, by simlod_paint_lasso."""
+        lasso (an octree_io.Lasso, no footprint then): the samples simlod_query_lasso(region, lasso, 20, "all") returns, by simlod_paint_lasso.
+        invert: the samples simlod_query_inverse(region, footprint, lasso, 20, "all") returns — everything but the selection — by
+        simlod_paint_inverse; return_previous and an array paint with invert=True again are the undo."""
         from .octree_io import Region
         self._one_polygon(footprint, lasso)
         u, up = self._u(uniforms)
@@ -776,6 +805,10 @@ class DeviceOctree:
         r, pr = (Region() if region is None else region).record(), paint.record()
         f = lasso.record() if lasso is not None else None if footprint is None else footprint.record()
         call, what = (self.L.simlod_paint_lasso, "simlod_paint_lasso") if lasso is not None else (self.L.simlod_paint_region, "simlod_paint_region")
+        polygon = (None if f is None else ctypes.c_void_p(f.ctypes.data),)
+        if invert:
+            call, what = self.L.simlod_paint_inverse, "simlod_paint_inverse"
+            polygon = (None, polygon[0]) if lasso is not None else (polygon[0], None)
         col = None
         if paint.mode == abi.PAINT_ARRAY:
             if colors is None:
@@ -791,7 +824,7 @@ class DeviceOctree:
         scratch = self._export_scratch(int(self.L.simlod_paint_buffer_min_bytes(nn, bound)))
         opt = lambda t: None if t is None else self._p(t)
         _check(call(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data),
-                    None if f is None else ctypes.c_void_p(f.ctypes.data), ctypes.c_void_p(pr.ctypes.data), self._p(scratch),
+                    *polygon, ctypes.c_void_p(pr.ctypes.data), self._p(scratch),
                     ctypes.c_uint64(scratch.numel()), self._p(table), nn, opt(col), opt(prev), ctypes.c_uint64(cap), self._p(counts),
                     self._stream()), what)
         c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
@@ -800,13 +833,15 @@ class DeviceOctree:
         return (c, prev[: int(c["numSamples"])]) if return_previous else c
 
     # -- summary queries (include/simlod_hip.h, "summary queries") -------------------------------------------------------------------------
-    def summarize_region(self, uniforms, region, max_level=None, select="cut", footprint=None, z0=0.0, scale=1.0, max_workgroups=0, lasso=None):
+    def summarize_region(self, uniforms, region, max_level=None, select="cut", footprint=None, z0=0.0, scale=1.0, max_workgroups=0, lasso=None,
+                         invert=False):
         """What query_region(region, max_level, select, footprint=footprint) would return, summarised on the device by one simlod_query_summary
         call instead of copied out: an octree_io.Summary — the number of samples, their extent, the sums behind centroid and covariance, the
         histogram of their heights in the bins of a ramp paint with (z0, scale), and the histograms of the four colour bytes.  The octree is
         only read.  max_workgroups: 0, or a limit for the reduction's grid (the result does not depend on it).  Raises SimlodError when the
         device reports an error; then no summary was written.
-        lasso (an octree_io.Lasso, no footprint then): what query_region(..., lasso=lasso) would return, by simlod_query_summary_lasso."""
+        lasso (an octree_io.Lasso, no footprint then): what query_region(..., lasso=lasso) would return, by simlod_query_summary_lasso.
+        invert: what query_region(..., invert=True) would return, by simlod_query_summary_inverse."""
         from .octree_io import Region, Summary
         self._one_polygon(footprint, lasso)
         u, up = self._u(uniforms)
@@ -814,6 +849,10 @@ class DeviceOctree:
         r = (Region() if region is None else region).record()
         f = lasso.record() if lasso is not None else None if footprint is None else footprint.record()
         call, what = (self.L.simlod_query_summary_lasso, "simlod_query_summary_lasso") if lasso is not None else (self.L.simlod_query_summary, "simlod_query_summary")
+        polygon = (None if f is None else ctypes.c_void_p(f.ctypes.data),)
+        if invert:
+            call, what = self.L.simlod_query_summary_inverse, "simlod_query_summary_inverse"
+            polygon = (None, polygon[0]) if lasso is not None else (polygon[0], None)
         pr = np.zeros(1, dtype=abi.summary_params_dtype)
         pr["z0"], pr["scale"], pr["maxWorkgroups"] = z0, scale, int(max_workgroups)
         table = self._table(nn)
@@ -821,7 +860,7 @@ class DeviceOctree:
         out = torch.zeros(abi.summary_dtype.itemsize, dtype=torch.uint8, device=self.device)
         scratch = self._export_scratch(int(self.L.simlod_summary_buffer_min_bytes(nn, bound)))
         _check(call(self._p(self.nodes), self._p(self.stats), up, ctypes.c_void_p(r.ctypes.data),
-                    None if f is None else ctypes.c_void_p(f.ctypes.data), ctypes.c_void_p(pr.ctypes.data), ml, sel, self._p(scratch),
+                    *polygon, ctypes.c_void_p(pr.ctypes.data), ml, sel, self._p(scratch),
                     ctypes.c_uint64(scratch.numel()), self._p(table), nn, self._p(out), self._p(counts), self._stream()), what)
         c = counts.cpu().numpy().view(abi.query_counts_dtype)[0]
         if int(c["error"]) != 0:

@@ -19,6 +19,9 @@ device-to-device copy, all in this one run.
 the 256-vertex star) drawn at the terrain's mean height on the bird camera's 1920 x 1080 screen, each alternating rep by rep with
 simlod_query_footprint of the plan-view polygon, full and count-only — and the device-to-device copy, all in this one run.  --lasso-only KIND:
 that polygon alone (a per-kernel trace of one vertex count).
+--inverse: instead, simlod_query_inverse ALL@20 on the same octree — a lasso around the city block of --region (about 1 % of the plan area) and
+the half-terrain triangle of --footprint, both on the bird camera's screen — each alternating rep by rep with simlod_export_octree ALL and the
+positive simlod_query_lasso ALL@20 of the same polygon, full and count-only, all in this one run.
 --profile: instead, simlod_query_profile CUT@20 on the same octree — a 5-vertex polyline across the terrain whose half-width gives the
 corridor 1 % of the plan area, with records, without records, and simlod_query_footprint with the corridor's outline polygon, the three
 alternating rep by rep; the count-only call — and the device-to-device copy, all in this one run.
@@ -481,6 +484,87 @@ def lasso_bench(dev, u, box, st, reps, T, width, height, only=None):
     print(json.dumps(out))
 
 
+def inverse_bench(dev, u, box, st, reps, T, width, height):
+    """simlod_query_inverse ALL@20 with two lassos on the screen of the camera T — the city block of --region (about 1 % of the plan area) and
+    the half-terrain triangle of --footprint — each alternating rep by rep with simlod_export_octree ALL and the positive simlod_query_lasso
+    ALL@20 of the same polygon, full and count-only.  An inverse is read against the export and the positive query of its own run."""
+    from simlod_amd import fingerprint
+    from simlod_amd.octree_io import Lasso, Region
+    L, p, stream = dev.L, dev._p, dev._stream()
+    nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+    need = max(int(L.simlod_inverse_buffer_min_bytes(nn, bound)), int(L.simlod_export_buffer_min_bytes(nn, bound)))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    table = torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
+    samples = torch.empty(bound * 16, dtype=torch.uint8, device=dev.device)
+    counts = torch.zeros(32, dtype=torch.uint8, device=dev.device)
+    uu, up = dev._u(u)
+    b = np.asarray(box, dtype=np.float64)
+    m = np.asarray(T, dtype=np.float64).reshape(4, 4)
+
+    def on_screen(xy):
+        h = np.concatenate([xy, np.full((len(xy), 1), 0.5 * b[2]), np.ones((len(xy), 1))], axis=1) @ m.T
+        assert (h[:, 3] > 0).all()
+        return np.stack([0.5 * width * (h[:, 0] / h[:, 3] + 1.0), 0.5 * height * (h[:, 1] / h[:, 3] + 1.0)], axis=1)
+
+    tri = 0.5 + (np.array([(50 / 600, 50 / 400), (550 / 600, 80 / 400), (250 / 600, 380 / 400)]) - 0.5) * 1.25
+    block = np.array([(0.45, 0.45), (0.45, 0.55), (0.55, 0.55), (0.55, 0.45)])
+    plan = {"city_block": block * b[:2], "half_terrain": tri * b[:2]}
+    lrec = {k: Lasso.from_pixels(T, width, height, on_screen(v)).record() for k, v in plan.items()}
+    none = Region().record()
+
+    def inverse(kind, count_only=False):
+        rc = L.simlod_query_inverse(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(none.ctypes.data), None, ctypes.c_void_p(lrec[kind].ctypes.data), 20,
+                                    abi.EXPORT_ALL, p(scratch), ctypes.c_uint64(need), p(table), nn, None if count_only else p(samples), ctypes.c_uint64(bound),
+                                    p(counts), stream)
+        assert rc == 0
+
+    def positive(kind, count_only=False):
+        rc = L.simlod_query_lasso(p(dev.nodes), p(dev.stats), up, ctypes.c_void_p(none.ctypes.data), ctypes.c_void_p(lrec[kind].ctypes.data), 20, abi.EXPORT_ALL,
+                                  p(scratch), ctypes.c_uint64(need), p(table), nn, None if count_only else p(samples), ctypes.c_uint64(bound), p(counts), stream)
+        assert rc == 0
+
+    def export_all():
+        rc = L.simlod_export_octree(p(dev.nodes), p(dev.stats), 20, abi.EXPORT_ALL, p(scratch), ctypes.c_uint64(need), p(table), nn, p(samples),
+                                    ctypes.c_uint64(bound), p(counts), stream)
+        assert rc == 0
+
+    def read_counts():
+        torch.cuda.synchronize()
+        c = counts.cpu().numpy().view(abi.query_counts_dtype)[0].copy()
+        assert int(c["error"]) == 0
+        return c
+
+    copy_dst = torch.empty(int(st["numPoints"]) * 16, dtype=torch.uint8, device=dev.device)
+    copy_src = samples[: copy_dst.numel()]
+    t_copy = timed(lambda: copy_dst.copy_(copy_src), reps)
+    copy_gbs = 2 * copy_dst.numel() / (t_copy[0] * 1e6)
+    out = {"points": int(st["numPoints"]), "numNodes": nn, "numSamples": bound, "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(), "screen": [width, height],
+           "d2d_copy": {"ms": round(t_copy[0], 4), "bytes": 2 * copy_dst.numel(), "GBs": round(copy_gbs, 1)},
+           "note": "an inverse is read against export_all and the positive lasso query of the same run"}
+
+    def row(ms, ms_count, c):
+        nbytes = int(c["numCandidates"]) * 16 + int(c["numSamples"]) * 16 + int(c["numNodes"]) * 40
+        gbs = nbytes / (ms[0] * 1e6)
+        return {"ms": round(ms[0], 4), "ms_min": round(ms[1], 4), "count_only_ms": round(ms_count[0], 4), "nodes_listed": int(c["numNodes"]),
+                "nodes_copied": int(c["numCopiedNodes"]), "nodes_filtered": int(c["numFilteredNodes"]), "numCandidates": int(c["numCandidates"]),
+                "numSamples": int(c["numSamples"]), "algorithmic_bytes": nbytes, "GBs": round(gbs, 1), "frac_of_copy": round(gbs / copy_gbs, 4)}
+
+    for kind in plan:
+        t_inv, t_exp, t_pos, t_invc, t_posc = timed_alternating([lambda: inverse(kind), export_all, lambda: positive(kind), lambda: inverse(kind, True),
+                                                                 lambda: positive(kind, True)], reps)
+        inverse(kind)
+        ci = read_counts()
+        positive(kind)
+        cp = read_counts()
+        assert int(ci["numSamples"]) + int(cp["numSamples"]) == bound and int(ci["numNodes"]) == nn
+        out[kind] = {"inverse": row(t_inv, t_invc, ci), "lasso": row(t_pos, t_posc, cp),
+                     "export_all": {"ms": round(t_exp[0], 4), "ms_min": round(t_exp[1], 4)},
+                     "removed_share": round(int(cp["numSamples"]) / bound, 4),
+                     "inverse_over_export_all": round(t_inv[0] / t_exp[0], 4), "inverse_over_lasso": round(t_inv[0] / t_pos[0], 4),
+                     "inverse_count_only_over_lasso_count_only": round(t_invc[0] / t_posc[0], 4)}
+    print(json.dumps(out))
+
+
 def rays_bench(dev, u, box, st, reps, T, width, height):
     from simlod_amd import fingerprint
     from simlod_amd.octree_io import OctreeExport, Rays, Region
@@ -912,6 +996,7 @@ def main():
     ap.add_argument("--footprint", action="store_true", help="time simlod_query_footprint (half the terrain, a rectangle beside its four planes, two stars) instead")
     ap.add_argument("--lasso", action="store_true", help="time simlod_query_lasso (the --footprint polygons drawn on the bird camera's 1080p screen, each beside its footprint query) instead")
     ap.add_argument("--lasso-only", default=None, choices=["half_terrain", "rect", "star7", "star128"], help="--lasso: this polygon alone (a per-kernel trace of one case)")
+    ap.add_argument("--inverse", action="store_true", help="time simlod_query_inverse ALL@20 (a lasso removing about a hundredth, one removing about half) beside simlod_export_octree ALL and the positive lasso query of the same polygon instead")
     ap.add_argument("--profile", action="store_true", help="time simlod_query_profile (a 5-vertex corridor over 1 % of the terrain, with and without records, beside the footprint of its outline) instead")
     ap.add_argument("--rays", action="store_true", help="time simlod_query_rays (one pixel cone, 4 096 vertical rays) instead")
     ap.add_argument("--neighbours", action="store_true", help="time simlod_query_neighbours (4 096 queries, k = 1, 8, 16, count-only) instead")
@@ -947,6 +1032,8 @@ def main():
         return footprint_bench(dev, u, box, st, args.reps)
     if args.lasso:
         return lasso_bench(dev, u, box, st, args.reps, T, 1920, 1080, args.lasso_only)
+    if args.inverse:
+        return inverse_bench(dev, u, box, st, args.reps, T, 1920, 1080)
     if args.profile:
         return profile_bench(dev, u, box, st, args.reps)
     if args.rays:
