@@ -1352,6 +1352,113 @@ int simlod_unpack_samples(const SimlodUniforms* uniforms /*host*/, const SimlodE
                           uint32_t numNodes, const uint64_t* packed, uint64_t sampleCapacity, void* scratch, uint64_t scratchBytes,
                           SimlodPoint* samples, SimlodPackCounts* counts, void* stream);
 
+/* ---- compare queries: each sample's distance to the nearest sample of another cloud -----------------------------------------------------------
+ * simlod_compare_samples relates TWO sample arrays: for every sample of `a` the nearest sample of `b` within a radius, how many samples of `b`
+ * lie within that radius, a colour looked up from the squared distance, and one summary record with the histogram of those distances.  With
+ * b == a the same call gives the local density (`within`).  `a` and `b` are flat device arrays of the 16-byte sample — the `samples` of any
+ * export, query, view or unpack result —; the call knows nothing of octrees.  Both arrays are only read.  The search runs on a hash grid over `b`
+ * whose cell is as large as the radius asks for; what the grid lets the kernels skip never changes a result (rule C4).
+ *
+ * All fp64 arithmetic works from the fp32 inputs, without fused multiply-add, every sum in the order written here.  Each field is defined by
+ * its rule alone, whatever work the kernels skip.
+ *  C1. Valid samples.  A sample is valid iff its x, y and z are finite.  An invalid sample of `b` is never a neighbour and is counted in
+ *      numInvalidB.  An invalid sample of `a` gets the miss record and missColor, lands in hist[256] and is counted in numInvalidA.  The radius
+ *      must be finite and >= 0; radius 0 is valid and matches coincident samples only.
+ *  C2. The sample test (neighbour-query rule 2).  With p_a = s_a - c_a per component of the sample s of `b` and the sample c of `a`,
+ *      d2 = (px*px + py*py) + pz*pz and rr = (double)r * (double)r; the sample passes iff d2 <= rr.
+ *  C3. The result.  Over the valid samples of `b` that pass for a valid a[i]: within[i] is their number, nearest[i] the first of them in the
+ *      total order (d2, index in `b`), d2[i] that sample's d2.  With none passing the record is the MISS record: d2 = +infinity,
+ *      nearest = 0xffffffff, within = 0.  A sample compared with its own cloud finds itself at d2 = 0; of duplicates the lowest index wins.
+ *  C4. The grid.  h = max((double)r * (1 + 2^-10), (double)size * 2^-20) with `size` the largest fp32 extent of the uniforms' box and
+ *      min = boxMin (a size that is not finite or not > 0, or a boxMin that is not finite, is refused); inv = 1.0 / h, one IEEE division made
+ *      by the launcher on the host.  A valid sample's cell is, per axis, summary rule S2's c20 with this inv in the place of that rule's:
+ *      t = ((double)x - (double)min) * inv, cell = 1048575 if t >= 1048575.0, (uint32_t)t if t > 0.0, else 0.  Coordinates outside the box
+ *      clamp to the edge cells, so `b` need not share `a`'s box.  numCells is the number of distinct cells that hold a valid sample of `b`,
+ *      maxCellPopulation the largest number of valid samples of `b` in one cell, numCandidates the sum, over the valid samples of `a`, of the
+ *      populations of the up to 27 cells at per-axis offsets -1, 0, +1 from the sample's cell; an offset that leaves [0, 2^20) is skipped, not
+ *      clamped.  Only those cells are searched, and for finite samples that never changes rule C3: two samples with d2 <= rr differ by at most
+ *      r * (1 + 2^-52) on each axis (a square is monotone under IEEE rounding and the sums only add non-negative terms), so their t differ by
+ *      less than r * (1 + 2^-52) / (r * (1 + 2^-10)) < 1 - 2^-11 plus the rounding of the two products, at most 2^-31 each inside the clamp
+ *      range (t < 2^20, 53-bit significands); truncation then puts them into the same cell or into adjacent ones, and the clamp, being
+ *      monotone, never moves two cells further apart.  With h at its floor size * 2^-20 the radius is smaller still and the same holds.
+ *  C5. Colours and histogram.  For a matched sample i = the number of entries of thresholds2 that are <= d2 (0 .. 255; the 255 entries are
+ *      ascending — each >= the one before — and finite; a binary search, no square root is taken anywhere): colors[j] = table[i] and hist[i]
+ *      counts it.  An unmatched or invalid sample of `a` gets missColor and hist[256].
+ *  C6. The budget.  With maxCandidates != 0 and numCandidates > maxCandidates no sample is tested: error = SIMLOD_COMPARE_ERR_BUDGET, no
+ *      record and no colour is written, numMatched = numWithin = 0, maxD2 = 0 and hist is all zero; the other fields are complete.  (A radius
+ *      that puts all of `b` into a few cells would otherwise launch numA x numB tests.)
+ *  C7. Count only.  records == NULL (then colors must be NULL too): the grid is built and error, numCells, maxCellPopulation, numCandidates,
+ *      numInvalidA and numInvalidB are written as above; no distance is computed, numMatched = numWithin = 0, maxD2 = 0, hist all zero.
+ *  C8. Determinism.  Everything returned is a sum of integers, a maximum, or the minimum of a total order: a pure function of the two arrays
+ *      and the parameters, independent of the schedule, of maxWorkgroups and of where the hash table puts a cell.  Two calls give the same
+ *      bytes.
+ * Nothing is written but `scratch`, `records`, `colors` and `summary`.  `a` and `b` may be the same array. */
+#define SIMLOD_COMPARE_ERR_BUDGET 0x1u
+#define SIMLOD_COMPARE_MISS       0xffffffffu
+typedef struct SimlodCompareRecord {   /* DEVICE memory, one per sample of `a`, same index */
+	double   d2;                       /* rule C3; miss: +infinity                                              */
+	uint32_t nearest;                  /* index into `b`; miss: 0xffffffff                                      */
+	uint32_t within;                   /* valid samples of `b` that pass rule C2                                */
+} SimlodCompareRecord;
+typedef struct SimlodCompareParams {   /* host memory; read completely before the call returns */
+	float    radius;                   /* finite, >= 0                                                          */
+	uint32_t missColor;                /* rule C5                                                               */
+	uint64_t maxCandidates;            /* rule C6; 0: no limit                                                  */
+	double   thresholds2[255];         /* rule C5: squared distances, ascending, finite                         */
+	uint32_t table[256];               /* rule C5                                                               */
+	uint32_t maxWorkgroups;            /* 0: the library's choice; else no kernel launches more workgroups      */
+	uint32_t reserved;                 /* 0                                                                     */
+} SimlodCompareParams;
+typedef struct SimlodCompareSummary {  /* written by the device */
+	uint32_t error;                    /* SIMLOD_COMPARE_ERR_* bits                                             */
+	uint32_t numCells;                 /* rule C4                                                               */
+	uint32_t maxCellPopulation;        /* rule C4                                                               */
+	uint32_t numInvalidA;              /* rule C1                                                               */
+	uint32_t numInvalidB;              /* rule C1                                                               */
+	uint32_t numMatched;               /* samples of `a` with within > 0                                        */
+	uint64_t numWithin;                /* the sum of within                                                     */
+	uint64_t numCandidates;            /* rule C4                                                               */
+	double   maxD2;                    /* the largest matched d2; 0 when none matched                           */
+	uint64_t hist[257];                /* rule C5; [256]: unmatched and invalid samples of `a`                  */
+} SimlodCompareSummary;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodCompareRecord) == 16, "CompareRecord");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareRecord, nearest) == 8, "CompareRecord.nearest");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareRecord, within) == 12, "CompareRecord.within");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodCompareParams) == 3088, "CompareParams");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareParams, missColor) == 4, "CompareParams.missColor");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareParams, maxCandidates) == 8, "CompareParams.maxCandidates");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareParams, thresholds2) == 16, "CompareParams.thresholds2");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareParams, table) == 2056, "CompareParams.table");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareParams, maxWorkgroups) == 3080, "CompareParams.maxWorkgroups");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareParams, reserved) == 3084, "CompareParams.reserved");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodCompareSummary) == 2104, "CompareSummary");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareSummary, numCells) == 4, "CompareSummary.numCells");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareSummary, maxCellPopulation) == 8, "CompareSummary.maxCellPopulation");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareSummary, numInvalidA) == 12, "CompareSummary.numInvalidA");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareSummary, numInvalidB) == 16, "CompareSummary.numInvalidB");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareSummary, numMatched) == 20, "CompareSummary.numMatched");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareSummary, numWithin) == 24, "CompareSummary.numWithin");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareSummary, numCandidates) == 32, "CompareSummary.numCandidates");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareSummary, maxD2) == 40, "CompareSummary.maxD2");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodCompareSummary, hist) == 48, "CompareSummary.hist");
+
+/* Bytes of the `scratch` buffer a compare call needs; it depends on the two counts only (in fact on numB): a header, the hash table (16 bytes
+ * per slot), 12 bytes and one 16-byte grid record per sample of `b`, and the partial records of the largest grid the library ever chooses.
+ * There is no capacity error on the device.  0 for counts the call refuses. */
+uint64_t simlod_compare_buffer_min_bytes(uint64_t numA, uint64_t numB);
+/* The hash table's capacity: the smallest power of two >= 2 * numB (0 for a numB the call refuses). */
+uint64_t simlod_compare_table_slots(uint64_t numB);
+
+/* The compare query (rules above).  Asynchronous on `stream` once `uniforms` and `params` have been read.  hipErrorInvalidValue with nothing
+ * enqueued and nothing touched: a null pointer other than `records` / `colors`; colors != NULL while records == NULL; numA or numB equal to 0
+ * or >= 2^32 - 1; a radius that is not finite or < 0; a box whose boxMin is not finite or whose size is not finite or not > 0; thresholds2 not
+ * ascending or not finite; a nonzero `reserved`; scratchBytes below simlod_compare_buffer_min_bytes(numA, numB) (one byte less is refused, the
+ * exact size is accepted); `a`, `b`, `scratch` or `records` not 16-byte aligned, `colors` not 4-byte aligned, `summary` not 8-byte aligned. */
+int simlod_compare_samples(const SimlodUniforms* uniforms /*host*/, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB,
+                           const SimlodCompareParams* params /*host*/, void* scratch, uint64_t scratchBytes,
+                           SimlodCompareRecord* records /*or NULL: count only*/, uint32_t* colors /*or NULL*/,
+                           SimlodCompareSummary* summary, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

@@ -210,6 +210,21 @@ summary_dtype = np.dtype({"names": ["numSamples", "numNonFinite", "min", "max", 
                           "offsets": [0, 8, 16, 28, 40, 64, 112, 2160], "itemsize": 10352})
 assert summary_params_dtype.itemsize == 16 and summary_dtype.itemsize == 10352
 
+# ---- compare queries (include/simlod_hip.h, "compare queries") ---------------------------------------------------------------------------
+COMPARE_ERR_BUDGET = 0x1
+COMPARE_MISS = 0xFFFFFFFF                                                   # `nearest` of the miss record; its d2 is +infinity
+COMPARE_MAX_COUNT = (1 << 32) - 2                                           # numA, numB: 1 .. 2^32 - 2
+COMPARE_HASH_MUL = 0x9E3779B97F4A7C15                                       # compare_rules.hpp compare_home
+compare_record_dtype = np.dtype({"names": ["d2", "nearest", "within"], "formats": ["<f8", "<u4", "<u4"], "offsets": [0, 8, 12], "itemsize": 16})
+compare_params_dtype = np.dtype({"names": ["radius", "missColor", "maxCandidates", "thresholds2", "table", "maxWorkgroups", "reserved"],
+                                 "formats": ["<f4", "<u4", "<u8", ("<f8", 255), ("<u4", 256), "<u4", "<u4"],
+                                 "offsets": [0, 4, 8, 16, 2056, 3080, 3084], "itemsize": 3088})
+compare_summary_dtype = np.dtype({"names": ["error", "numCells", "maxCellPopulation", "numInvalidA", "numInvalidB", "numMatched", "numWithin",
+                                            "numCandidates", "maxD2", "hist"],
+                                  "formats": ["<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<u8", "<u8", "<f8", ("<u8", 257)],
+                                  "offsets": [0, 4, 8, 12, 16, 20, 24, 32, 40, 48], "itemsize": 2104})
+assert compare_record_dtype.itemsize == 16 and compare_params_dtype.itemsize == 3088 and compare_summary_dtype.itemsize == 2104
+
 # ---- lasso queries (include/simlod_hip.h, "lasso queries") -------------------------------------------------------------------------------
 LASSO_MAX_VERTICES = 256
 lasso_dtype = np.dtype({"names": ["numVertices", "reserved", "rowU", "rowV", "rowW", "vertices"],

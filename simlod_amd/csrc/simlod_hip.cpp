@@ -623,6 +623,16 @@ int simlod_unpack_samples(const SimlodUniforms* uniforms, const SimlodExportNode
 	return launch_pack(true, uniforms, table, entries, numNodes, packed, sampleCapacity, scratch, scratchBytes, samples, counts, (hipStream_t)stream);
 }
 
+uint64_t simlod_compare_buffer_min_bytes(uint64_t numA, uint64_t numB) { return compare_min_bytes(numA, numB); }
+
+uint64_t simlod_compare_table_slots(uint64_t numB) { return compare_slots(numB); }
+
+int simlod_compare_samples(const SimlodUniforms* uniforms, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB,
+                           const SimlodCompareParams* params, void* scratch, uint64_t scratchBytes, SimlodCompareRecord* records, uint32_t* colors,
+                           SimlodCompareSummary* summary, void* stream) {
+	return launch_compare(uniforms, a, numA, b, numB, params, scratch, scratchBytes, records, colors, summary, (hipStream_t)stream);
+}
+
 uint64_t simlod_rays_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates) {
 	return rays_min_bytes(nodeCapacity, sampleBound, numRays, numPairs, numCandidates);
 }

@@ -226,6 +226,10 @@ uint64_t view_delta_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint3
 int launch_pack(bool unpack, const SimlodUniforms* u, const SimlodExportNode* table, const SimlodDeltaEntry* entries, uint32_t numNodes, const void* in,
                 uint64_t sampleCapacity, void* scratch, uint64_t scratchBytes, void* out, SimlodPackCounts* counts, hipStream_t stream);
 uint64_t pack_min_bytes(uint32_t numNodes, uint64_t sampleBound);
+int launch_compare(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB, const SimlodCompareParams* params,
+                   void* scratch, uint64_t scratchBytes, SimlodCompareRecord* records, uint32_t* colors, SimlodCompareSummary* summary, hipStream_t stream);
+uint64_t compare_min_bytes(uint64_t numA, uint64_t numB);
+uint64_t compare_slots(uint64_t numB);
 int launch_rays(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRay* rays, uint32_t numRays,
                 uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
                 SimlodRayHit* hits, SimlodRayCounts* counts, hipStream_t stream);

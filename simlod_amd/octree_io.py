@@ -35,6 +35,11 @@ Summary queries (include/simlod_hip.h, "summary queries"): `OctreeExport.summari
 reduced to one record in numpy float64 and integers —, `Summary` wraps that record (extent, centroid, covariance, the range and the equalised
 table of a height ramp) and `Paint.ramp_from` turns one into a RAMP paint.
 
+Compare queries (include/simlod_hip.h, "compare queries"): `Compare` holds the radius, the thresholds, the colour table and the budget,
+`compare_samples` is the host mirror of simlod_compare_samples — two sample arrays in, records, colours and the summary record out, rules
+C1-C5 in numpy float64 and integers —, `OctreeExport.compare` applies it to two exports and `CompareResult` is what
+DeviceOctree.compare_region returns.
+
 Profile queries (include/simlod_hip.h, "profile queries"): `Profile` holds the polyline, the half-width and the three affine maps,
 `OctreeExport.profile` is the host mirror of simlod_query_profile — samples and records — and `classify_profile` of its rule P3.
 
@@ -324,9 +329,7 @@ class OctreeExport:
             unkey = lambda v: v ^ (0x80000000 if v >> 31 else 0xFFFFFFFF)
             rec["min"][k], rec["max"][k] = np.array([unkey(lo), unkey(hi)], np.uint32).view(np.float32)
             # rule S2: the 20-bit cell, a NaN in cell 0
-            with np.errstate(invalid="ignore", over="ignore"):
-                t = (b.view(np.float32).astype(np.float64) - mn[k]) * inv
-                c20 = np.where(t >= np.float64(abi.SUMMARY_CELLS - 1), np.float64(abi.SUMMARY_CELLS - 1), np.where(t > 0.0, t, 0.0)).astype(np.uint64)
+            c20 = cell20(b.view(np.float32), mn[k], inv)
             rec["sum"][k] = c20.sum(dtype=np.uint64)
             c16.append(c20 >> np.uint64(4))
         for j, (a, b) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
@@ -337,6 +340,12 @@ class OctreeExport:
             rec["histC"][k] = np.bincount((smp["color"] >> np.uint32(8 * k)) & np.uint32(255), minlength=256).astype(np.uint64)
         out = Summary(rec, bins.z0, bins.scale)
         return (out, c) if return_counts else out
+
+    # -- compare queries (include/simlod_hip.h, "compare queries") -------------------------------------------------------------------------
+    def compare(self, other, compare, count_only=False):
+        """The host mirror of simlod_compare_samples on this export's samples (A) and `other`'s (B; may be this export), in this export's box:
+        compare_samples' (records, colours, summary)."""
+        return compare_samples(self.samples, other.samples, (self.box_min, self.box_max), compare, count_only=count_only)
 
     # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
     def profile(self, profile, region=None, max_level=None, select="all", return_counts=False, test_every_sample=False):
@@ -637,6 +646,16 @@ class OctreeExport:
         packed, c = pack_samples(self.nodes, self.samples, self.box_min, self.box_max)
         px = PackedExport(self.nodes, packed, self.box_min, self.box_max, self.max_level, self.select)
         return (px, c) if return_counts else px
+
+
+def cell20(x, box_min, inv):
+    """Summary rule S2's 20-bit cell of float32 coordinates on an axis whose box starts at box_min, as uint64 (summary_rules.hpp
+    summary_cell20): t = ((double)x - (double)boxMin) * inv; 1048575 if t >= 1048575.0, (uint32_t)t if t > 0.0, else 0 (a NaN gives 0).  The
+    summary's mirror passes rule S2's inv, the compare mirror rule C4's: the one statement both rules rest on."""
+    top = np.float64(abi.SUMMARY_CELLS - 1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = (np.asarray(x, np.float32).astype(np.float64) - np.float64(box_min)) * np.float64(inv)
+        return np.where(t >= top, top, np.where(t > 0.0, t, 0.0)).astype(np.uint64)
 
 
 def _box_of(box_min, box_max):
@@ -1357,6 +1376,205 @@ class Summary:
             idx.append(min(len(pal) - 1, ((2 * below + v) * len(pal)) // (2 * n)))
             below += v
         return pal[np.asarray(idx, np.int64)]
+
+
+class Compare:
+    """The parameters of a compare query (include/simlod_hip.h, "compare queries"; abi.compare_params_dtype): the radius (float32), the 255
+    ascending squared-distance thresholds and the 256 colour words of rule C5, the miss colour, and the candidate budget of rule C6
+    (max_candidates; None: the device entry points' default — DeviceOctree.compare_samples and compare_region take 64 per sample of A —,
+    0: no limit, said explicitly.  record() and the host mirror compare_samples, which launch nothing, read None as the C call's 0)."""
+
+    def __init__(self, radius, thresholds2, table, miss_color=0, max_candidates=None, max_workgroups=0):
+        with np.errstate(over="ignore"):
+            self.radius = np.float32(radius)
+        self.thresholds2 = np.asarray(thresholds2, dtype=np.float64).reshape(-1).copy()
+        self.table = np.asarray(table, dtype=np.uint32).reshape(-1).copy()
+        self.miss_color, self.max_workgroups = int(miss_color), int(max_workgroups)
+        self.max_candidates = None if max_candidates is None else int(max_candidates)
+        if not (np.isfinite(self.radius) and self.radius >= 0):
+            raise ValueError("a compare query needs a finite radius >= 0 (as float32)")
+        if len(self.thresholds2) != 255 or len(self.table) != 256:
+            raise ValueError(f"{len(self.thresholds2)} thresholds and {len(self.table)} table entries: 255 and 256")
+        if not np.isfinite(self.thresholds2).all() or (np.diff(self.thresholds2) < 0).any():
+            raise ValueError("the thresholds are finite and ascending")
+        if not 0 <= self.miss_color <= 0xFFFFFFFF or (self.max_candidates is not None and self.max_candidates < 0):
+            raise ValueError("a colour word is a 32-bit unsigned integer, a budget is not negative")
+
+    @staticmethod
+    def _spread(colours):
+        pal = np.asarray(colours, dtype=np.uint32).reshape(-1)
+        if len(pal) == 0:
+            raise ValueError("a ramp needs a colour")
+        return pal[np.arange(256) * len(pal) // 256]
+
+    @classmethod
+    def linear(cls, dmax, colours, radius=None, **kw):
+        """Bins of equal width in DISTANCE up to dmax: thresholds2[i] = ((i + 1) * dmax / 255)^2 in float64, so a sample at distance dmax or
+        beyond gets table[255].  colours: the palette, nearest first, any number of words, spread evenly over the 256 bins.  radius: the search
+        radius (None: dmax)."""
+        dmax = np.float64(dmax)
+        if not (np.isfinite(dmax) and dmax > 0):
+            raise ValueError("a linear ramp needs a finite dmax > 0")
+        t = (np.arange(1, 256).astype(np.float64) * dmax) / np.float64(255.0)
+        return cls(dmax if radius is None else radius, t * t, cls._spread(colours), **kw)
+
+    @classmethod
+    def from_summary(cls, summary, colours, radius, **kw):
+        """The linear ramp fitted to a previous result: dmax = sqrt(summary maxD2) — the largest distance that result matched (the radius when it
+        matched nothing or only coincident samples).  The square root is taken here, on the host; the device takes none."""
+        d2 = float(np.asarray(summary)["maxD2"])
+        return cls.linear(np.sqrt(d2) if d2 > 0.0 else float(np.float32(radius)) or 1.0, colours, radius=radius, **kw)
+
+    @classmethod
+    def from_record(cls, record):
+        r = np.asarray(record, dtype=abi.compare_params_dtype).reshape(-1)[0]
+        return cls(r["radius"], r["thresholds2"], r["table"], int(r["missColor"]), int(r["maxCandidates"]), int(r["maxWorkgroups"]))
+
+    def __eq__(self, other):
+        return isinstance(other, Compare) and self.record().tobytes() == other.record().tobytes()
+
+    def record(self, max_candidates=None):
+        """The SimlodCompareParams the C ABI takes (abi.compare_params_dtype, one record); max_candidates overrides the object's."""
+        r = np.zeros(1, dtype=abi.compare_params_dtype)
+        budget = self.max_candidates if max_candidates is None else int(max_candidates)
+        r["radius"], r["missColor"], r["maxCandidates"], r["maxWorkgroups"] = self.radius, self.miss_color, budget or 0, self.max_workgroups
+        r["thresholds2"][0], r["table"][0] = self.thresholds2, self.table
+        return r
+
+    def index(self, d2):
+        """Rule C5's table index of squared distances: the number of thresholds <= d2."""
+        return np.searchsorted(self.thresholds2, np.asarray(d2, np.float64), side="right")
+
+
+def compare_h(radius, size):
+    """Rule C4's cell size in float64 from the float32 radius and box size."""
+    return max(np.float64(np.float32(radius)) * np.float64(1.0 + 2.0 ** -10), np.float64(np.float32(size)) * np.float64(2.0 ** -20))
+
+
+def compare_table_slots(num_b):
+    """simlod_compare_table_slots: the smallest power of two >= 2 * num_b."""
+    s = 2
+    while s < 2 * int(num_b):
+        s <<= 1
+    return s
+
+
+def compare_home(keys, slots):
+    """compare_rules.hpp compare_home: the slot a 60-bit cell key's probing starts at in a table of `slots` (a power of two) slots."""
+    log2 = int(slots).bit_length() - 1
+    return (np.asarray(keys, np.uint64) * np.uint64(abi.COMPARE_HASH_MUL)) >> np.uint64(64 - log2)
+
+
+def compare_cells(points, box_min, inv):
+    """Rule C4 for an array of abi.point_dtype: (valid, keys) — rule C1's validity and, for the valid samples, the 60-bit key
+    cx | cy << 20 | cz << 40 of the cell (0 for the others) — by cell20, the summary mirror's, with rule C4's inv."""
+    valid = np.isfinite(points["x"]) & np.isfinite(points["y"]) & np.isfinite(points["z"])
+    keys = np.zeros(len(points), np.uint64)
+    for k, name in enumerate(("x", "y", "z")):
+        keys |= np.where(valid, cell20(points[name], box_min[k], inv), np.uint64(0)) << np.uint64(20 * k)
+    return valid, keys
+
+
+def compare_samples(a, b, uniforms_box, compare, count_only=False):
+    """The host mirror of simlod_compare_samples (include/simlod_hip.h, "compare queries"): a, b arrays of abi.point_dtype, uniforms_box the
+    (box_min, box_max) of the uniforms, compare a Compare -> (records as abi.compare_record_dtype, colours as uint32, the summary as one
+    abi.compare_summary_dtype record); count_only, or a budget exceeded (rule C6): records and colours are None.  The cells by the same cell20
+    the summary's mirror uses, grouped by np.unique over the keys; rules C2, C3 and C5 in numpy float64 and unsigned integers, in the order
+    the header gives.  Only the cells rule C4 names are searched, as on the device."""
+    a, b = np.asarray(a, dtype=abi.point_dtype).reshape(-1), np.asarray(b, dtype=abi.point_dtype).reshape(-1)
+    if not (0 < len(a) <= abi.COMPARE_MAX_COUNT and 0 < len(b) <= abi.COMPARE_MAX_COUNT):
+        raise ValueError("numA and numB are 1 .. 2^32 - 2")
+    mn, size = _box_of(*uniforms_box)
+    if not (np.isfinite(mn).all() and np.isfinite(size) and size > 0):
+        raise ValueError("the box needs a finite corner and a finite extent > 0")
+    inv = np.float64(1.0) / compare_h(compare.radius, size)
+    rr = np.float64(compare.radius) * np.float64(compare.radius)
+    va, ka = compare_cells(a, mn, inv)
+    vb, kb = compare_cells(b, mn, inv)
+    out = np.zeros((), dtype=abi.compare_summary_dtype)
+    out["numInvalidA"], out["numInvalidB"] = int((~va).sum()), int((~vb).sum())
+    ib = np.flatnonzero(vb)
+    ib = ib[np.argsort(kb[ib], kind="stable")]                             # the grid: b's valid samples by cell, ascending index within a cell
+    cells, first, pop = np.unique(kb[ib], return_index=True, return_counts=True)
+    out["numCells"], out["maxCellPopulation"] = len(cells), int(pop.max()) if len(pop) else 0
+    # the up to 27 cells around each valid sample of a: (sample, first grid record, population) per occupied one
+    ia = np.flatnonzero(va)
+    c = [((ka[ia] >> np.uint64(20 * k)) & np.uint64(0xFFFFF)).astype(np.int64) for k in range(3)]
+    who, start, count = [], [], []
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                n = [c[0] + dx, c[1] + dy, c[2] + dz]
+                ok = np.ones(len(ia), bool)
+                for v in n:
+                    ok &= (v >= 0) & (v < abi.SUMMARY_CELLS)               # (an offset that leaves the grid is skipped, not clamped)
+                key = (n[0][ok] | n[1][ok] << 20 | n[2][ok] << 40).astype(np.uint64)
+                at = np.searchsorted(cells, key)
+                hit = at < len(cells)
+                hit[hit] = cells[at[hit]] == key[hit]
+                who.append(ia[ok][hit]); start.append(first[at[hit]]); count.append(pop[at[hit]])
+    who, start, count = (np.concatenate(v).astype(np.int64) for v in (who, start, count))
+    out["numCandidates"] = int(count.sum())
+    budget = compare.max_candidates or 0
+    if budget != 0 and int(out["numCandidates"]) > budget:
+        out["error"] = abi.COMPARE_ERR_BUDGET
+    if count_only or int(out["error"]) != 0:
+        return None, None, out
+    # every candidate pair (i, j), then rule C2
+    pi = np.repeat(who, count)
+    pj = ib[np.repeat(start, count) + (np.arange(len(pi)) - np.repeat(np.cumsum(count) - count, count))]
+    d = [b[name][pj].astype(np.float64) - a[name][pi].astype(np.float64) for name in ("x", "y", "z")]
+    d2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+    ok = d2 <= rr
+    pi, pj, d2 = pi[ok], pj[ok], d2[ok]
+    rec = np.zeros(len(a), dtype=abi.compare_record_dtype)
+    rec["d2"], rec["nearest"] = np.inf, abi.COMPARE_MISS
+    rec["within"] = np.bincount(pi, minlength=len(a))
+    order = np.lexsort((pj, d2, pi))                                        # rule C3: per sample the first in (d2, index)
+    lead = order[np.r_[True, pi[order][1:] != pi[order][:-1]]] if len(order) else order
+    rec["d2"][pi[lead]], rec["nearest"][pi[lead]] = d2[lead], pj[lead]
+    matched = rec["within"] != 0
+    idx = np.where(matched, compare.index(np.where(matched, rec["d2"], 0.0)), 256)
+    colours = np.where(matched, compare.table[np.minimum(idx, 255)], np.uint32(compare.miss_color)).astype(np.uint32)
+    out["numMatched"], out["numWithin"] = int(matched.sum()), int(rec["within"].sum(dtype=np.uint64))
+    out["maxD2"] = rec["d2"][matched].max() if matched.any() else 0.0
+    out["hist"] = np.bincount(idx, minlength=257).astype(np.uint64)
+    return rec, colours, out
+
+
+class CompareResult:
+    """What DeviceOctree.compare_region returns: `a`, the selection of A as an OctreeExport (query_region's); `b`, the export of B the
+    selection was compared with; `records` (abi.compare_record_dtype, one per sample of a, as bytes) and `colors` (uint32 words) as tensors on
+    the device, in a's order; `summary`, one abi.compare_summary_dtype record on the host; the Compare; and the selection's arguments."""
+
+    def __init__(self, a, b, records, colors, summary, compare, selection):
+        self.a, self.b, self.records, self.colors, self.summary, self.compare, self.selection = a, b, records, colors, summary, compare, selection
+
+    def records_host(self):
+        """The records as a numpy array of abi.compare_record_dtype."""
+        return self.records.cpu().numpy().view(abi.compare_record_dtype)
+
+    def nearest_nodes(self):
+        """Per sample of a the index, in b's table, of the node that holds its nearest sample (-1: a miss), by a search over firstSample."""
+        t = self.b.nodes
+        sel = np.flatnonzero(((t["flags"] & abi.EXPORT_FLAG_SELECTED) != 0) & (t["numSamples"] > 0))
+        sel = sel[np.argsort(t["firstSample"][sel], kind="stable")]
+        near = self.records_host()["nearest"]
+        hit = near != abi.COMPARE_MISS
+        out = np.full(len(near), -1, np.int64)
+        if len(sel):
+            out[hit] = sel[np.searchsorted(t["firstSample"][sel], near[hit].astype(np.uint64), side="right") - 1]
+        return out
+
+    def paint(self, dev, uniforms, return_previous=False):
+        """Write the colours into the octree `dev` the selection was taken from — an ARRAY paint of the same selection, which takes one word
+        per sample in the query's order.  Only a result of max_level=20, select="all" has that order.  -> paint_region's result (with
+        return_previous the old words too: an ARRAY paint of them is the undo)."""
+        s = self.selection
+        if s["max_level"] != abi.MAX_DEPTH or s["select"] != "all":
+            raise ValueError("only a compare_region(max_level=20, select='all') result is in the order paint_region takes")
+        return dev.paint_region(uniforms, s["region"], Paint.array(), footprint=s["footprint"], colors=self.colors, return_previous=return_previous,
+                                lasso=s["lasso"], invert=s["invert"])
 
 
 class Footprint:

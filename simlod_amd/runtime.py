@@ -133,6 +133,11 @@ def lib():
         L.simlod_neighbours_buffer_min_bytes.restype = u64
         L.simlod_neighbours_buffer_min_bytes.argtypes = [u32, u64, u32, u32, u64, u64]
         L.simlod_query_neighbours.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, vp, u64, vp, u32, vp, vp, vp, vp]
+        L.simlod_compare_buffer_min_bytes.restype = u64
+        L.simlod_compare_buffer_min_bytes.argtypes = [u64, u64]
+        L.simlod_compare_table_slots.restype = u64
+        L.simlod_compare_table_slots.argtypes = [u64]
+        L.simlod_compare_samples.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -159,6 +164,7 @@ EXPORTED_SYMBOLS = [
     "simlod_summary_buffer_min_bytes", "simlod_query_summary",
     "simlod_lasso_buffer_min_bytes", "simlod_query_lasso", "simlod_paint_lasso", "simlod_query_summary_lasso",
     "simlod_inverse_buffer_min_bytes", "simlod_query_inverse", "simlod_paint_inverse", "simlod_query_summary_inverse",
+    "simlod_compare_buffer_min_bytes", "simlod_compare_table_slots", "simlod_compare_samples",
 ]
 
 
@@ -866,6 +872,90 @@ class DeviceOctree:
         if int(c["error"]) != 0:
             raise SimlodError(f"{what} reported error bits {int(c['error']):#x} (counts: {int(c['numNodes'])} nodes, {int(c['numSamples'])} samples); no summary was written")
         return Summary(out.cpu().numpy().view(abi.summary_dtype)[0], pr["z0"][0], pr["scale"][0])
+
+    # -- compare queries (include/simlod_hip.h, "compare queries") -------------------------------------------------------------------------
+    COMPARE_BUDGET_PER_SAMPLE = 64                                          # compare_region's default budget: candidates per sample of A
+
+    def _samples_tensor(self, s):
+        """Samples as a uint8 tensor on this device: a tensor of whole 16-byte records, an OctreeExport, or anything numpy takes."""
+        if hasattr(s, "samples_tensor"):
+            s = s.samples_tensor
+        if not isinstance(s, torch.Tensor):
+            s = torch.from_numpy(np.ascontiguousarray(np.asarray(s, dtype=abi.point_dtype)).view(np.uint8).reshape(-1))
+        s = s.reshape(-1).view(torch.uint8).contiguous().to(self.device)
+        if s.numel() == 0 or s.numel() % abi.point_dtype.itemsize:
+            raise ValueError("samples are whole 16-byte records, at least one")
+        return s
+
+    def compare_samples(self, uniforms, a, b, compare, count_only=False, max_candidates=None):
+        """One simlod_compare_samples call on two sample arrays (device tensors of 16-byte records, OctreeExports, or anything numpy takes):
+        per sample of `a` the nearest sample of `b` within compare.radius.  -> (records: a uint8 tensor of abi.compare_record_dtype records,
+        colors: an int32 tensor of colour words, both on this device and in a's order, and the abi.compare_summary_dtype record on the host);
+        count_only: (None, None, record) — the grid's fields only (rule C7).  The call ALWAYS carries a candidate budget (rule C6):
+        max_candidates if given, else compare.max_candidates, else — both None — 64 candidates per sample of `a`, compare_region's default;
+        an explicit 0, here or in the Compare, is the opt-out (no limit).  A budget exceeded comes back as (None, None, record) with
+        SIMLOD_COMPARE_ERR_BUDGET in the record's error field: no sample was tested, no record or colour written, and numCandidates and
+        maxCellPopulation say why."""
+        u, up = self._u(uniforms)
+        ta, tb = self._samples_tensor(a), self._samples_tensor(b)
+        na, nb = ta.numel() // abi.point_dtype.itemsize, tb.numel() // abi.point_dtype.itemsize
+        budget = max_candidates if max_candidates is not None else compare.max_candidates
+        pr = compare.record(self.COMPARE_BUDGET_PER_SAMPLE * na if budget is None else int(budget))
+        need = int(self.L.simlod_compare_buffer_min_bytes(na, nb))
+        if need == 0:
+            raise ValueError("numA and numB are 1 .. 2^32 - 2")
+        scratch = self._export_scratch(need)
+        out = torch.zeros(abi.compare_summary_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        records = colors = None
+        if not count_only:
+            records = torch.empty(na * abi.compare_record_dtype.itemsize, dtype=torch.uint8, device=self.device)
+            colors = torch.empty(na, dtype=torch.int32, device=self.device)
+        opt = lambda t: None if t is None else self._p(t)
+        _check(self.L.simlod_compare_samples(up, self._p(ta), ctypes.c_uint64(na), self._p(tb), ctypes.c_uint64(nb), ctypes.c_void_p(pr.ctypes.data),
+                                             self._p(scratch), ctypes.c_uint64(scratch.numel()), opt(records), opt(colors), self._p(out), self._stream()),
+               "simlod_compare_samples")
+        rec = out.cpu().numpy().view(abi.compare_summary_dtype)[0]
+        return (None, None, rec) if int(rec["error"]) != 0 else (records, colors, rec)
+
+    def _compare_inputs(self, uniforms, other, region, max_level, select, footprint, lasso, invert, other_max_level, other_select):
+        from .octree_io import Region
+        region = Region() if region is None else region
+        a = self.query_region(uniforms, region, max_level, select, footprint=footprint, lasso=lasso, invert=invert)
+        b = other.export_octree(uniforms, other_max_level, other_select)
+        if a.num_samples == 0 or b.num_samples == 0:
+            raise SimlodError(f"nothing to compare: the selection holds {a.num_samples} samples, the other octree's export {b.num_samples}")
+        sel = {"region": region, "max_level": abi.MAX_DEPTH if max_level is None else int(max_level), "select": select, "footprint": footprint,
+               "lasso": lasso, "invert": invert}
+        return a, b, sel
+
+    def count_compare(self, uniforms, other, region, compare, max_level=None, select="cut", footprint=None, lasso=None, invert=False,
+                      other_max_level=None, other_select="cut"):
+        """What compare_region would cost: the abi.compare_summary_dtype record of the count-only call (numCells, maxCellPopulation,
+        numCandidates, the invalid counts) for the same arguments; no distance is computed and no budget applies."""
+        a, b, _ = self._compare_inputs(uniforms, other, region, max_level, select, footprint, lasso, invert, other_max_level, other_select)
+        return self.compare_samples(uniforms, a, b, compare, count_only=True, max_candidates=0)[2]
+
+    def compare_region(self, uniforms, other, region, compare, max_level=None, select="cut", footprint=None, lasso=None, invert=False,
+                       other_max_level=None, other_select="cut"):
+        """Each sample of a selection of THIS octree against the nearest sample of `other` (a DeviceOctree on this device; may be this one)
+        within compare.radius: A = query_region(region, max_level, select, footprint / lasso / invert), B = other.export_octree(
+        other_max_level, other_select), a count-only simlod_compare_samples call, the budget check, then the call with results -> an
+        octree_io.CompareResult (A, B, the records, the colours, the summary).  The budget is compare.max_candidates (None: 64 candidates per
+        sample of A; 0: none); a count above it raises SimlodError naming numCandidates and maxCellPopulation — pick a smaller radius or a
+        coarser cut of B.  With max_level=20, select="all" the colours are in the order paint_region's ARRAY paint takes:
+        CompareResult.paint(dev, uniforms) writes them into the octree."""
+        from .octree_io import CompareResult
+        a, b, sel = self._compare_inputs(uniforms, other, region, max_level, select, footprint, lasso, invert, other_max_level, other_select)
+        budget = self.COMPARE_BUDGET_PER_SAMPLE * a.num_samples if compare.max_candidates is None else compare.max_candidates
+        c = self.compare_samples(uniforms, a, b, compare, count_only=True, max_candidates=0)[2]
+        if budget != 0 and int(c["numCandidates"]) > budget:
+            raise SimlodError(f"comparing {a.num_samples} samples with {b.num_samples} at radius {float(compare.radius)} would test numCandidates = "
+                              f"{int(c['numCandidates'])} pairs, above the budget of {budget} (maxCellPopulation = {int(c['maxCellPopulation'])} in "
+                              f"{int(c['numCells'])} cells): pick a smaller radius or a coarser cut of the other octree")
+        records, colors, s = self.compare_samples(uniforms, a, b, compare, max_candidates=budget)
+        if int(s["error"]) != 0:
+            raise SimlodError(f"simlod_compare_samples reported error bits {int(s['error']):#x}; no record was written")
+        return CompareResult(a, b, records, colors, s, compare, sel)
 
     # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
     def _profile(self, uniforms, profile, region, ml, sel, table, samples, records, sample_capacity, bound):

@@ -42,7 +42,13 @@ of the copy rate by algorithmic bytes.  --paint-only REGION:MODE: that case alon
 summary alternates rep by rep with simlod_query_region ALL@20 of the same region with samples, its count-only call and the device-to-device
 copy (each call starts behind the copy); the ratio to the query (the purpose bound: <= 1), the cost over the count-only call and the share of
 the copy rate by algorithmic bytes (the selected samples once, plus the table); the whole box again with smaller grids, and once more
-after a SET paint of everything (one colour: every lane of a wave on one bin).  --summary-only REGION: that case alone."""
+after a SET paint of everything (one colour: every lane of a wave on one bin).  --summary-only REGION: that case alone.
+--compare: instead, simlod_compare_samples — A the CUT@20 region query of a box of 1/36 of the plan area (about 1 M samples), B the octree's
+full CUT@20 export, radius 2.167 as --neighbours' in DESIGN §11: the call with results and the count-only call alternating rep by rep, each
+kernel's time from one call between the library's own events, candidates per sample and the largest cell, the rate on the ideal bytes against
+the device-to-device copy — and, for scale, the same positions through simlod_query_neighbours at k = 1, in batches of 65 536.  --compare-radius R:
+another radius, for cells of hundreds or thousands of samples, without that yardstick.
+--compare-whole: the same with A = B = the full export.  --compare-workgroups N: SimlodCompareParams.maxWorkgroups for either."""
 import argparse
 import ctypes
 import json
@@ -716,6 +722,106 @@ def neighbours_bench(dev, u, box, st, reps, pts):
     print(json.dumps(out))
 
 
+def compare_bench(dev, u, box, st, reps, pts, whole=False, workgroups=0, radius_arg=None):
+    """simlod_compare_samples: A = the CUT@20 selection of a box of 1/36 of the plan area (about 1 M samples), B = the octree's full CUT@20
+    export, at --neighbours' radius of DESIGN §11 (2.167)."""
+    from simlod_amd import fingerprint
+    from simlod_amd.octree_io import Compare, Region, Spheres
+    L, p, stream = dev.L, dev._p, dev._stream()
+    uu, up = dev._u(u)
+    b = np.asarray(box, dtype=np.float64)
+    radius = 2.167 if radius_arg is None else float(radius_arg)
+    side = 1.0 / 6.0
+    region = Region.from_box((b[0] * (0.5 - side / 2), b[1] * (0.5 - side / 2), -1.0), (b[0] * (0.5 + side / 2), b[1] * (0.5 + side / 2), b[2] + 1.0))
+    ex_b = dev.export_octree(u, 20, "cut")
+    ex_a = ex_b if whole else dev.query_region(u, region, 20, "cut")
+    ta, tb = ex_a.samples_tensor, ex_b.samples_tensor
+    na, nb = ex_a.num_samples, ex_b.num_samples
+    cmp = Compare.linear(radius, [0xFF0000FF, 0xFF00FFFF, 0xFF00FF00, 0xFFFF0000], miss_color=0xFF808080, max_workgroups=workgroups)
+    pr = cmp.record(0)
+    need = int(L.simlod_compare_buffer_min_bytes(na, nb))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev.device)
+    records = torch.empty(na * 16, dtype=torch.uint8, device=dev.device)
+    colors = torch.empty(na, dtype=torch.int32, device=dev.device)
+    summary = torch.zeros(abi.compare_summary_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+
+    def call(count_only=False):
+        rc = L.simlod_compare_samples(up, p(ta), ctypes.c_uint64(na), p(tb), ctypes.c_uint64(nb), ctypes.c_void_p(pr.ctypes.data), p(scratch),
+                                      ctypes.c_uint64(need), None if count_only else p(records), None if count_only else p(colors), p(summary), stream)
+        assert rc == 0
+
+    copy_dst = torch.empty(nb * 16, dtype=torch.uint8, device=dev.device)
+    t_copy = timed(lambda: copy_dst.copy_(tb), reps)
+    copy_gbs = 2 * copy_dst.numel() / (t_copy[0] * 1e6)
+    del copy_dst
+    call(True)
+    torch.cuda.synchronize()
+    c0 = summary.cpu().numpy().view(abi.compare_summary_dtype)[0].copy()
+    out = {"points": int(st["numPoints"]), "reps": reps, "csrc_sha16": fingerprint.csrc_sha16(), "numA": na, "numB": nb, "radius": radius, "maxWorkgroups": workgroups, "scratch_bytes": need,
+           "table_slots": int(L.simlod_compare_table_slots(nb)), "numCells": int(c0["numCells"]), "maxCellPopulation": int(c0["maxCellPopulation"]),
+           "numCandidates": int(c0["numCandidates"]), "candidates_per_sample": round(int(c0["numCandidates"]) / na, 2),
+           "d2d_copy": {"ms": round(t_copy[0], 4), "bytes": 2 * nb * 16, "GBs": round(copy_gbs, 1)}}
+    if int(c0["numCandidates"]) > 4096 * na:
+        out["skipped"] = "more than 4 096 candidates per sample: the call with results is not run"
+        print(json.dumps(out))
+        return
+    ts = timed_alternating([lambda: call(), lambda: call(True)], reps)
+    call()
+    torch.cuda.synchronize()
+    c = summary.cpu().numpy().view(abi.compare_summary_dtype)[0]
+    assert int(c["error"]) == 0
+    # the ideal bytes: b read once and its grid records written once and read once, a read once, a record and a colour written per sample of a
+    ideal = nb * 16 * 3 + na * (16 + 16 + 4)
+    ideal_test = int(c["numCandidates"]) * 16 + na * (16 + 16 + 4)
+    out["results"] = {"ms": round(ts[0][0], 4), "ms_min": round(ts[0][1], 4), "ideal_bytes": ideal, "GBs": round(ideal / (ts[0][0] * 1e6), 1),
+                      "frac_of_copy": round(ideal / (ts[0][0] * 1e6) / copy_gbs, 4), "numMatched": int(c["numMatched"]), "numWithin": int(c["numWithin"]),
+                      "maxD2": float(c["maxD2"]), "Msamples_per_s": round(na / (ts[0][0] * 1e3), 1)}
+    out["count_only"] = {"ms": round(ts[1][0], 4), "ms_min": round(ts[1][1], 4)}
+    # each kernel's share: one call between the library's own events
+    for name, co in (("kernels_ms", False), ("kernels_ms_count_only", True)):
+        L.simlod_profile_enable(1)
+        call(co)
+        torch.cuda.synchronize()
+        import bench
+        prof = bench.collect_profile(L)
+        L.simlod_profile_enable(0)
+        out[name] = {k: round(ms, 4) for k, (n, ms) in prof.items() if k.startswith("k_c_")}
+    if "k_c_test" in out["kernels_ms"]:
+        t_test = out["kernels_ms"]["k_c_test"]
+        out["test_pass"] = {"candidate_bytes": ideal_test, "GBs": round(ideal_test / (t_test * 1e6), 1),
+                            "Gtests_per_s": round(int(c["numCandidates"]) / (t_test * 1e6), 2)}
+    if not whole and radius_arg is None:
+        # for scale: the same positions through simlod_query_neighbours at k = 1, in batches of 65 536 queries (each sized by its own
+        # count-only call); the sum of the batches' medians of three runs is the figure
+        centers = ex_a.samples
+        n_q = 1 << 16
+        nn, bound = int(st["numNodes"]), int(st["numPoints"]) + int(st["numVoxels"])
+        per_batch, candidates = [], 0
+        for lo in range(0, na, n_q):
+            q = Spheres.from_points(centers[lo:lo + n_q], radius)
+            nq = len(q)
+            d_q = torch.from_numpy(q.record().view(np.uint8).reshape(-1)).to(dev.device)
+            cn = dev.count_neighbours(u, q, 1)
+            n_need = int(L.simlod_neighbours_buffer_min_bytes(nn, bound, nq, 1, int(cn["numPairs"]), int(cn["numCandidates"])))
+            n_scratch = torch.empty(n_need, dtype=torch.uint8, device=dev.device)
+            n_out = torch.empty(nq * abi.neighbour_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+            n_within = torch.empty(nq, dtype=torch.int32, device=dev.device)
+            n_counts = torch.zeros(abi.neighbour_counts_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+
+            def nbq():
+                rc = L.simlod_query_neighbours(p(dev.nodes), p(dev.stats), up, p(d_q), nq, 1, 20, abi.EXPORT_CUT, p(n_scratch), ctypes.c_uint64(n_need), None, nn,
+                                               p(n_out), p(n_within), p(n_counts), stream)
+                assert rc == 0
+            per_batch.append(timed(nbq, 3, warmup=1)[0])
+            candidates += int(cn["numCandidates"])
+            del n_scratch, n_out, n_within, d_q
+        total = float(sum(per_batch))
+        out["find_neighbours_k1"] = {"queries": na, "batches": len(per_batch), "ms": round(total, 2), "ms_per_batch_min": round(min(per_batch), 3),
+                                     "ms_per_batch_max": round(max(per_batch), 3), "numCandidates": candidates, "candidates_per_query": round(candidates / na, 1),
+                                     "Msamples_per_s": round(na / (total * 1e3), 3), "ratio_to_compare": round((na / total) / (na / ts[0][0]), 5)}
+    print(json.dumps(out))
+
+
 def view_bench(dev, u, box, st, reps):
     from simlod_amd import fingerprint
     L, p, stream = dev.L, dev._p, dev._stream()
@@ -1008,6 +1114,10 @@ def main():
     ap.add_argument("--paint-only", default=None, metavar="REGION:MODE", help="--paint: this case alone, e.g. city_block:set (a per-kernel trace of one case)")
     ap.add_argument("--summary", action="store_true", help="time simlod_query_summary (whole box, half the terrain, a city block; the whole box in one colour) beside the ALL@20 region query and its count-only call instead")
     ap.add_argument("--summary-only", default=None, metavar="REGION", help="--summary: this case alone, e.g. whole_box or whole_box_one_colour (a per-kernel trace of one case)")
+    ap.add_argument("--compare", action="store_true", help="time simlod_compare_samples (a 1 M-sample CUT@20 selection against the full CUT@20 export at radius 2.167; count-only, with results, per kernel) beside simlod_query_neighbours k = 1 instead")
+    ap.add_argument("--compare-whole", action="store_true", help="--compare with A = B = the full CUT@20 export (skipped above 4 096 candidates per sample)")
+    ap.add_argument("--compare-workgroups", type=int, default=0, help="--compare / --compare-whole: SimlodCompareParams.maxWorkgroups (0: the library's choice)")
+    ap.add_argument("--compare-radius", type=float, default=None, help="--compare: another radius (heavier cells); the neighbour yardstick is then left out")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
     pts, box = synthetic.terrain(n_points, seed=7)
@@ -1040,6 +1150,8 @@ def main():
         return rays_bench(dev, u, box, st, args.reps, T, 1920, 1080)
     if args.neighbours:
         return neighbours_bench(dev, u, box, st, args.reps, pts)
+    if args.compare or args.compare_whole:
+        return compare_bench(dev, u, box, st, args.reps, pts, whole=args.compare_whole, workgroups=args.compare_workgroups, radius_arg=args.compare_radius)
     if args.view:
         return view_bench(dev, u, box, st, args.reps)
     if args.view_delta:
