@@ -35,6 +35,8 @@ def pixels(kind):
         return np.array([(96, 100), (96, 150), (160, 150), (160, 100)], np.float32)
     if kind == "tri":
         return np.array([(40, 60), (220, 90), (110, 230)], np.float32)
+    if kind == "half":                     # the left half of the screen (inverse_ref.half_screen; the builder states scale it onto the points' picture)
+        return np.array([(0, 0), (W / 2, 0), (W / 2, H), (0, H)], np.float32)
     if kind == "bowtie":                   # crossing order: two triangles that meet in the centre
         return np.array([(50, 50), (200, 200), (50, 200), (200, 50)], np.float32)
     if kind == "cover":                    # 64 screens wide: larger than the picture of a box that lies in front of the camera

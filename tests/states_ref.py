@@ -1,13 +1,17 @@
 """Shared by tests/test_gpu_builder_states.py and tests/test_builder_states_io.py: the inputs of the builder states, the query sets one
 battery asks of every state, the guards that keep a comparison from passing on nothing, the precondition helpers, and `collapse`, which
-turns a full export into the octree a builder without free node slots leaves behind (leaves of more than 50 chunks).  Everything here is
-numpy on host arrays: nothing depends on the code under test."""
+turns a full export into the octree a builder without free node slots leaves behind (leaves of more than 50 chunks).  The battery holds a
+region, a footprint, rays, spheres, a view with its budget and delta, a profile, two paints, pack / unpack, a lasso on the view's screen,
+summaries of the region, the lasso and the whole box, and the inverse of the region, the footprint and the lasso as a query, a summary and a
+paint each.  Everything here is numpy on host arrays: nothing depends on the code under test."""
 from collections import namedtuple
 
 import numpy as np
 
 import cases
 import footprint_ref as fr
+import inverse_ref as ir
+import lasso_ref as lr
 import neighbours_ref as nr
 import oracle
 import pack_ref as kr
@@ -15,10 +19,11 @@ import paint_ref as pf
 import profile_ref as pr
 import rays_ref as yr
 import region_ref as rr
+import summary_ref as zr
 import view_ref as vr
 from export_ref import export_host
 from simlod_amd import abi, synthetic
-from simlod_amd.octree_io import Footprint, OctreeExport, Paint, Profile, Rays, Region, Spheres
+from simlod_amd.octree_io import Footprint, Lasso, OctreeExport, Paint, Profile, Rays, Region, Spheres, _box_of, classify_footprint, classify_lasso, classify_nodes
 
 State = namedtuple("State", "dev u pts box")            # the device object, its uniforms, the points the octree holds NOW, the box
 ROW = 50                                                 # chunk addresses a row of the builder's chunk table holds (LEAF_ROW_SLOTS)
@@ -221,10 +226,35 @@ def assert_masked_rank(table, pts, mine, box, mask):
 
 
 # ---- the battery's queries and their guards ----------------------------------------------------------------------------------------------------
-Queries = namedtuple("Queries", "region footprint rays spheres radius profile")
+Queries = namedtuple("Queries", "region footprint rays spheres radius profile lasso foot_lasso z0 scale")
+W, H = cases.W, cases.H
 
 
-def queries(pts, box):
+def screen_lasso(transform, pts):
+    """lasso_ref's "half" — the left half of the screen — scaled onto the PICTURE of `pts` under the camera `transform` (row-major, as the
+    uniforms store it): its right edge stands at the median pixel column of the points in front of the eye, the other three edges one extent
+    of the picture (its 2 % .. 98 % quantiles) outside it.  So the lasso holds half the points in front of the eye wherever they lie in the
+    box (a launch that stopped short, the hotspot's one cell), the nodes left of the median column can be copied whole, the nodes it crosses
+    are filtered, and the nodes right of it are outside — where the octree has nodes small enough for either (Shape, below)."""
+    m = np.asarray(transform, np.float64).reshape(4, 4)
+    p = np.stack([pts[a].astype(np.float64) for a in "xyz"] + [np.ones(len(pts))], axis=1)
+    wc = p @ m[3]
+    front = wc > 0
+    assert front.any(), "no point in front of the eye"
+    u, v = (p[front] @ (0.5 * W * (m[0] + m[3]))) / wc[front], (p[front] @ (0.5 * H * (m[1] + m[3]))) / wc[front]
+    lo, hi = np.array([np.quantile(u, 0.02), np.quantile(v, 0.02)]), np.array([np.quantile(u, 0.98), np.quantile(v, 0.98)])
+    a, b = lo - (hi - lo), np.array([float(np.median(u)), hi[1] + (hi[1] - lo[1])])
+    half = lr.pixels("half").astype(np.float64)                # (0, 0) .. (W / 2, H)
+    return Lasso.from_pixels(m, W, H, a + half / np.array([W / 2, H]) * (b - a))
+
+
+def bins_of(lo, ext):
+    """test_gpu_inverse._bins for the heights the points span (z0 a tenth of the span above the lowest, 256 bins over 0.7 of it): samples
+    below bin 0 and above bin 255 exist and are clamped -> (z0, scale) as float32"""
+    return np.float32(float(lo) + 0.1 * float(ext)), np.float32(256.0 / (0.7 * float(ext)))
+
+
+def queries(pts, box, transform=None):
     """One query of each kind for an octree that holds `pts` in `box`, made from the points alone (a launch that stopped short holds
     points in a part of its box only, the hotspot in one level-3 cell: every query is placed by the points' bounding box, `the cube` below is
     its larger xy extent — for a filled box the octree's cube): region_ref's oblique half-space through the middle of that box; a
@@ -238,7 +268,9 @@ def queries(pts, box):
     the whole plan square of the lower-left quarter (x -0.1 .. 0.6, y -0.02 .. 0.52), so rule P3 copies the nodes over it as the star does, its rim
     and segment 1 filter their neighbours, and the two rectangles overlap over x 0.33 .. 0.6, y 0.25 .. 0.52, where the lower segment owns the
     samples.  The bend and the end go by the extent of EACH axis, so that on a strip of points (the first batches of a terrain, whose cube is the
-    long side) both segments and their overlap still hold points; only the half-width is the cube's."""
+    long side) both segments and their overlap still hold points; only the half-width is the cube's.  transform (the battery's view camera):
+    screen_lasso on the points' picture under it, the footprint once more as a lasso (Lasso.from_footprint: it must select what the footprint
+    selects), and the bins of the summaries over the heights the points span (bins_of)."""
     lo = np.array([float(pts[a].min()) for a in "xyz"])
     ext = np.array([float(pts[a].max()) for a in "xyz"]) - lo
     size = float(ext[:2].max())
@@ -254,7 +286,8 @@ def queries(pts, box):
     rays = Rays(c - d, d, 0.0, 2.0, 0.5 * radius, 0.0)
     bend = (lo[0] + 0.6 * ext[0], lo[1] + 0.25 * ext[1])
     corridor = Profile.from_xy([(lo[0] - 0.1 * size, bend[1]), bend, (bend[0], lo[1] + 0.9 * ext[1])], 0.27 * size)
-    return Queries(rr.region("oblique", ext, lo), star, rays, Spheres(c, radius), radius, corridor)
+    lasso = None if transform is None else screen_lasso(transform, pts)
+    return Queries(rr.region("oblique", ext, lo), star, rays, Spheres(c, radius), radius, corridor, lasso, Lasso.from_footprint(star), *bins_of(lo[2], ext[2]))
 
 
 def assert_crop_not_vacuous(cnt, what, copies=True):
@@ -307,10 +340,17 @@ def assert_delta_not_vacuous(delta, what, adds=True):
 # What the guards can ask of an octree, stated per state (a flag that is False asserts the OPPOSITE, so each is a fact about the octree and not
 # a check left out): `camera` of the view; whether the region / the footprint copies a node whole; whether the bias-0 cut adds nodes to the
 # bias-2 cut; whether the view's ladder has a coarser rung with samples (without one a budget of S(0) - 1 chooses the first EMPTY cut); whether
-# the profile copies a node whole.
-Shape = namedtuple("Shape", "camera region_copies footprint_copies delta_adds coarser profile_copies", defaults=("closer", True, True, True, True, True))
-NINE_NODES = Shape("inside", region_copies=False, delta_adds=False)     # a root and eight leaves: the plane through the middle cuts all eight
-ROOT_LEAF = Shape("closer", False, False, False, False, False)          # one node: filtered by everything, the only cut there is
+# the profile copies a node whole; whether the screen lasso copies a node whole (an octree of a root and eight octants seen from inside has none
+# in front of the eye whole, and under `closer` the octants of a small octree are wider than half the picture); whether the region / the
+# footprint / the lasso leaves a node WITH samples outside — the nodes its inverse copies whole, as the nodes a selection copies are the ones its
+# inverse lists at zero samples (rule I2); whether every leaf is longer than a chunk-table row — then every inverse result and every summary
+# must hold samples from behind the row.
+Shape = namedtuple("Shape", "camera region_copies footprint_copies delta_adds coarser profile_copies lasso_copies region_culls footprint_culls lasso_culls long_leaves",
+                   defaults=("closer", True, True, True, True, True, True, True, True, True, False))
+# a root and eight leaves of 75 chunks: the plane through the middle cuts all eight, the star leaves none outside, the eye is inside the box
+NINE_NODES = Shape("inside", region_copies=False, delta_adds=False, lasso_copies=False, region_culls=False, footprint_culls=False, long_leaves=True)
+ROOT_LEAF = Shape("closer", False, False, False, False, False, False, False, False, False)      # one node: filtered by everything, the only cut there is
+SUMMARY_SUBSET, SUMMARY_SEED = 4096, 53                                 # samples summary_ref's per-sample Python loop takes of a larger selection
 PAINT_SEED = 91                                                         # of the colours of the battery's ARRAY paint
 
 
@@ -318,11 +358,12 @@ def mirrors(full, pts, uv, what, shape=Shape(), pairs_all=False):
     """What the battery expects of an octree whose anchored full export is `full` and which holds `pts`, from the numpy mirrors alone: every
     answer guarded (above), the cuts equal to the brute-force filters of `pts`, the rays' t and the spheres' d2 bit-equal to the brute force
     over `pts`, the delta consistent in itself; the profile, the two paint calls and the packed export as profile_mirrors, paint_mirrors and
-    pack_mirror (below) hold them.  `uv`: the view's uniforms at bias 0.  pairs_all: rays and spheres with select "all" too."""
+    pack_mirror (below) hold them, the lasso, the summaries and the inverses as lasso_mirrors, summary_mirrors and inverse_mirrors.  `uv`: the
+    view's uniforms at bias 0, whose camera is the lasso's screen too.  pairs_all: rays and spheres with select "all" too."""
     import delta_ref
     mn, size = np.asarray(full.box_min, np.float64), np.asarray(full.box_max, np.float64) - np.asarray(full.box_min, np.float64)
     assert not mn.any()
-    q = queries(pts, tuple(size))
+    q = queries(pts, tuple(size), uv["transform"])
     m = {"q": q, "crop": {}, "rays": {}, "spheres": {}}
     for kind, region, foot in (("region", q.region, None), ("footprint", Region(), q.footprint)):
         for sel in ("cut", "all"):
@@ -358,7 +399,216 @@ def mirrors(full, pts, uv, what, shape=Shape(), pairs_all=False):
     m["profile"] = profile_mirrors(full, q.profile, pts, what, shape.profile_copies)
     m["paint"] = paint_mirrors(full, q, tuple(size), m["crop"], what)
     m["pack"] = pack_mirror(full, what)
+    # rule I1 over the points held and over every sample of the export (the voxels among them), once for all that follows
+    gone = {kind: ir.passes_inverse(*sel3, pts) for kind, sel3 in selections(q).items()}
+    gone_all = {kind: ir.passes_inverse(*sel3, full.samples) for kind, sel3 in selections(q).items()}
+    m["lasso"] = lasso_mirrors(full, q, pts, ~gone["lasso"], m["crop"], what, shape)
+    m["summary"] = summary_mirrors(full, q, pts, gone, gone_all, m["crop"], m["lasso"], what, shape)
+    m["inverse"] = inverse_mirrors(full, q, pts, gone, gone_all, m["crop"], m["lasso"], m["summary"], tuple(size), what, shape)
     return m
+
+
+def selections(q):
+    """The battery's three selections, one per family of the inverse, as (region, footprint, lasso)"""
+    return {"region": (q.region, None, None), "footprint": (Region(), q.footprint, None), "lasso": (Region(), None, q.lasso)}
+
+
+def selection_classes(full, sel3):
+    """The POSITIVE query's (outside, copied) per entry of the full export, the polygons' classes combined as rules F4 / L4 combine them."""
+    region, fp, lasso = sel3
+    outside, inside = classify_nodes(np.asarray(region.planes, np.float32).astype(np.float64), full.nodes, full.box_min, full.box_max)
+    if fp is not None:
+        near, corner = classify_footprint(fp, full.nodes, full.box_min, full.box_max)
+        outside, inside = outside | (~near & ~corner), inside & ~near & corner
+    if lasso is not None:
+        behind, covered = classify_lasso(lasso, full.nodes, full.box_min, full.box_max)
+        outside, inside = outside | behind, inside & covered
+    return outside, inside
+
+
+def behind_row(full, index):
+    """How many of the samples full.samples[index] lie in a LEAF at an ordinal of ROW chunks or more: in a chunk that no row of the builder's
+    chunk table names, which the read side reaches by `next` alone (from firstSample / numSamples and the chunk size)."""
+    t = full.nodes
+    first = t["firstSample"].astype(np.int64)
+    index = np.asarray(index, np.int64)
+    node = np.searchsorted(first, index, side="right") - 1             # (entries without samples share their successor's firstSample and come before it)
+    assert ((index >= first[node]) & (index < first[node] + t["numSamples"][node].astype(np.int64))).all()
+    leaf = (t["flags"] & abi.EXPORT_FLAG_LEAF) != 0
+    return int((leaf[node] & (index - first[node] >= ROW * abi.POINTS_PER_CHUNK)).sum())
+
+
+def lasso_mirrors(full, q, pts, inside, crops, what, shape=Shape()):
+    """OctreeExport.crop(lasso=) of the screen lasso at level 20 for "cut" and "all", and of the footprint's lasso for "cut"
+    -> {"cut" / "all" / "footprint": (export, counts)}.  The screen lasso's cut is guarded as the crops are and is rule L1 decided exactly over
+    `pts` (inside: lasso_ref.contains_exact's mask, through inverse_ref.passes_inverse); the footprint's lasso returns the footprint crop's samples (as a multiset: the two polygons' node rules need not copy the same nodes)."""
+    m = {sel: full.crop(Region(), 20, sel, return_counts=True, lasso=q.lasso) for sel in ("cut", "all")}
+    assert_crop_not_vacuous(m["cut"][1], f"{what} lasso", shape.lasso_copies)
+    rr.assert_same_multiset(m["cut"][0].samples, pts[inside], f"{what} lasso")
+    m["footprint"] = full.crop(Region(), 20, "cut", return_counts=True, lasso=q.foot_lasso)
+    rr.assert_same_multiset(m["footprint"][0].samples, crops["footprint", "cut"][0].samples, f"{what}: the footprint as a lasso")
+    return m
+
+
+def summarize_whole(samples, box_min, size, z0, scale):
+    """summary_ref's rules S1-S4 once more for FINITE samples, a whole selection at a time: the cells, the bins and their clamps in numpy
+    float64 as summary_ref words them (one subtraction, one multiplication, truncation), sums and counts in uint64.  Written from summary_ref,
+    sharing nothing with octree_io; assert_summary_is_exact holds it against the per-sample loop before it relies on it."""
+    mn, inv = [float(np.float32(v)) for v in box_min], zr.inv_of(float(np.float32(size)))
+    rec = np.zeros((), dtype=abi.summary_dtype)
+    rec["numSamples"] = len(samples)
+    c16 = []
+    for k, a in enumerate("xyz"):
+        v = samples[a]
+        assert np.isfinite(v).all()
+        rec["min"][k], rec["max"][k] = v.min(), v.max()
+        t = (v.astype(np.float64) - mn[k]) * inv
+        c = np.where(t >= 1048575.0, 1048575.0, np.where(t > 0.0, t, 0.0)).astype(np.uint64)
+        rec["sum"][k] = c.sum(dtype=np.uint64)
+        c16.append(c >> np.uint64(4))
+    for j, (a, b) in enumerate(zr.MOMENTS):
+        rec["sum2"][j] = (c16[a] * c16[b]).sum(dtype=np.uint64)
+    t = (samples["z"].astype(np.float64) - float(np.float32(z0))) * float(np.float32(scale))
+    rec["histZ"] = np.bincount(np.where(t >= 255.0, 255.0, np.where(t > 0.0, t, 0.0)).astype(np.int64), minlength=256)
+    for k in range(4):
+        rec["histC"][k] = np.bincount((samples["color"] >> np.uint32(8 * k)) & np.uint32(255), minlength=256)
+    return rec
+
+
+def _same_record(got, want, what):
+    for f in abi.summary_dtype.names:                           # (the extent by value: the two zeros compare equal)
+        same = np.array_equal(got[f], want[f]) if f in ("min", "max") else got[f].tobytes() == want[f].tobytes()
+        assert same, f"{what}: {f} differs: {got[f]} != {want[f]}"
+
+
+def assert_summary_is_exact(summary, selected, full, q, what):
+    """A mirror's Summary against summary_ref over `selected`, the brute-force selection: every field of the record.  Up to SUMMARY_SUBSET
+    samples summary_ref.summarize_exact (one sample at a time, in Python integers) gives the record itself.  More: the per-sample loop takes
+    a fixed seeded subset of SUMMARY_SUBSET of them and holds summarize_whole, the same rules vectorised, on exactly that subset; the record of
+    the WHOLE selection — count, extent, sums, moments, every bin of the five histograms — is then summarize_whole's."""
+    n = len(selected)
+    assert summary.num_samples == n > 0, f"{what}: the summary counts {summary.num_samples} samples, the brute force selects {n}"
+    size = _box_of(full.box_min, full.box_max)[1]
+    sub = selected if n <= SUMMARY_SUBSET else selected[np.sort(np.random.RandomState(SUMMARY_SEED).choice(n, SUMMARY_SUBSET, replace=False))]
+    want = zr.summarize_exact(sub, full.box_min, size, q.z0, q.scale)
+    _same_record(summarize_whole(sub, full.box_min, size, q.z0, q.scale), want, f"{what}: the vectorised rules against the per-sample loop on {len(sub)} samples")
+    if n <= SUMMARY_SUBSET:
+        assert summary.tobytes() == want.tobytes(), what
+    _same_record(summary, summarize_whole(selected, full.box_min, size, q.z0, q.scale), what)
+
+
+def summary_mirrors(full, q, pts, gone, gone_all, crops, lassos, what, shape=Shape()):
+    """OctreeExport.summarize with the bins of q -> {(kind, sel): (Summary, counts, the table of the crop it summarises)} for the region ("cut" and "all"), the screen lasso and the
+    whole box ("cut"; the box "all" too: the halves of rule I7 add up to it).  Each "cut" is held against summary_ref over the brute-force
+    selection of `pts` (assert_summary_is_exact), the region's "all" over the brute-force selection of the export's samples.  A condition on the
+    bins: the whole box fills more than half of them, and both end bins, where rule E3 clamps."""
+    nobody = np.ones(len(pts), bool)
+    m = {}
+    for kind, region, lasso, sel, selected in (("region", q.region, None, "cut", pts[~gone["region"]]),
+                                               ("region", q.region, None, "all", full.samples[~gone_all["region"]]),
+                                               ("lasso", Region(), q.lasso, "cut", pts[~gone["lasso"]]),
+                                               ("box", Region(), None, "cut", pts[nobody]), ("box", Region(), None, "all", full.samples)):
+        table = crops["region", sel][0].nodes if kind == "region" else lassos[sel][0].nodes if kind == "lasso" else full.crop(Region(), 20, sel).nodes
+        m[kind, sel] = full.summarize(region, 20, sel, z0=q.z0, scale=q.scale, return_counts=True, lasso=lasso) + (table,)
+        assert len(table) == int(m[kind, sel][1]["numNodes"])
+        assert_summary_is_exact(m[kind, sel][0], selected, full, q, f"{what} summary {kind} {sel}")
+    hz = m["box", "cut"][0]["histZ"].reshape(-1)
+    assert int((hz > 0).sum()) > 128 and hz[0] > 0 and hz[255] > 0, f"{what} summary: {int((hz > 0).sum())} bins filled, {int(hz[0])} / {int(hz[255])} samples in the end bins"
+    if shape.long_leaves:                                       # (what contributes to a cut's summary: the leaves' samples the exact rule selects)
+        in_leaf = np.repeat((full.nodes["flags"] & abi.EXPORT_FLAG_LEAF) != 0, full.nodes["numSamples"].astype(np.int64))
+        for kind, mask in (("region", ~gone_all["region"]), ("lasso", ~gone_all["lasso"]), ("box", True)):
+            assert int((in_leaf & mask).sum()) == m[kind, "cut"][0].num_samples
+            assert behind_row(full, np.nonzero(in_leaf & mask)[0]) > 0, f"{what} summary {kind}: no contributing sample lies behind a leaf's row"
+    return m
+
+
+InversePaint = namedtuple("InversePaint", "sel3 paint colors with_previous export counts previous")
+SET_COLOR = 0x11223344
+
+
+def inverse_mirrors(full, q, pts, gone, gone_all, crops, lassos, summaries, size, what, shape=Shape()):
+    """OctreeExport.crop / summarize / paint with invert=True for the battery's three selections -> {"query": {(kind, sel): (export, counts)},
+    "summary": {(kind, sel): (Summary, counts)}, "paint": [InversePaint x 3], "classes": {kind: (emptied, copied) nodes of the cut}}.
+    Each cut is rule I1 decided exactly over `pts` (inverse_ref.passes_inverse) and, with the positive cut, holds `pts` exactly once; each
+    "all" result is, sample for sample and in the export's order, what the same rule leaves of the export's samples (the voxels of filtered inner
+    nodes among them).  The summaries, cut and all, are summary_ref's of those selections and add up with the positive query's to the whole
+    box's (rules I6 / I7).  Guards, conditions on the
+    selections: every inverse returns at least one sample and not every candidate; the nodes the positive query copies are listed at zero
+    samples (Q_EMPTIED) and the nodes it leaves outside are copied whole — at least one of each among the cut's leaves, or none where the Shape
+    says so; with long leaves every "all" result holds samples from behind a row.  The paints, each on top of the one before: a SET by the
+    region's inverse WITHOUT `previous` (the path that stores without loading), a height ramp by the footprint's, an ARRAY of seeded colours by the
+    lasso's; `previous` written back in reverse order, each in its query's order, gives `full`."""
+    m = {"query": {}, "summary": {}, "paint": [], "classes": {}, "index": {}}
+    leaf = (full.nodes["flags"] & abi.EXPORT_FLAG_LEAF) != 0
+    ns = full.nodes["numSamples"].astype(np.int64)
+    in_leaf = np.repeat(leaf, ns)
+    positive = {"region": crops["region", "cut"], "footprint": crops["footprint", "cut"], "lasso": lassos["cut"]}
+    flags = {"region": (shape.region_copies, shape.region_culls), "footprint": (shape.footprint_copies, shape.footprint_culls), "lasso": (shape.lasso_copies, shape.lasso_culls)}
+    for kind, sel3 in selections(q).items():
+        region, fp, lasso = sel3
+        outside, inside = selection_classes(full, sel3)
+        cls = ir.class_map(outside, inside)
+        for sel in ("cut", "all"):
+            ex, cnt, index = full.crop(region, 20, sel, return_counts=True, footprint=fp, lasso=lasso, invert=True, return_index=True)
+            m["query"][kind, sel], m["index"][kind, sel] = (ex, cnt), index
+            assert 1 <= int(cnt["numSamples"]) <= int(cnt["numCandidates"]) - 1, f"{what} inverse {kind} {sel}: {int(cnt['numSamples'])} of {int(cnt['numCandidates'])} candidates"
+            # rule I3: every node is listed, in the export's order; rule I2 per node
+            chosen = (ns > 0) & (leaf if sel == "cut" else True)
+            got = ex.nodes["numSamples"].astype(np.int64)
+            assert len(got) == full.num_nodes and (got[chosen & (cls == ir.EMPTIED)] == 0).all() and (got[chosen & (cls == ir.COPIED)] == ns[chosen & (cls == ir.COPIED)]).all(), \
+                f"{what} inverse {kind} {sel}: an emptied node keeps samples or a copied one loses some"
+            assert int(cnt["numCopiedNodes"]) == int((chosen & (cls == ir.COPIED)).sum()) and int(cnt["numFilteredNodes"]) == int((chosen & (cls == ir.FILTERED)).sum())
+            # rule I1 on every sample of the selected nodes: the result is exactly the samples that fail, in the export's order
+            assert np.array_equal(index, np.nonzero(gone_all[kind] & (in_leaf if sel == "cut" else True))[0]), f"{what} inverse {kind} {sel}: not the samples the exact rule leaves"
+            m["summary"][kind, sel] = full.summarize(region, 20, sel, footprint=fp, lasso=lasso, z0=q.z0, scale=q.scale, return_counts=True, invert=True)
+            assert_summary_is_exact(m["summary"][kind, sel][0], full.samples[index] if sel == "all" else pts[gone[kind]], full, q, f"{what} inverse summary {kind} {sel}")
+            if (kind, sel) in summaries:                        # (the footprint's halves: tests/test_builder_states_io.py)
+                assert_halves_add_up(summaries[kind, sel][0], m["summary"][kind, sel][0], summaries["box", sel][0], f"{what} inverse summary {kind} {sel}")
+            if shape.long_leaves and sel == "all":
+                assert behind_row(full, index) > 0, f"{what} inverse {kind} all: no sample from behind a leaf's row"
+        emptied, copied = int((leaf & (ns > 0) & (cls == ir.EMPTIED)).sum()), int((leaf & (ns > 0) & (cls == ir.COPIED)).sum())
+        m["classes"][kind] = (emptied, copied)
+        assert emptied == int(positive[kind][1]["numCopiedNodes"]), f"{what} inverse {kind}: {emptied} emptied leaves, the positive cut copies {int(positive[kind][1]['numCopiedNodes'])}"
+        assert ((emptied > 0) == flags[kind][0]) and ((copied > 0) == flags[kind][1]), f"{what} inverse {kind}: {emptied} leaves emptied / {copied} copied whole, the shape says {flags[kind]}"
+        inv = m["query"][kind, "cut"][0]
+        rr.assert_same_multiset(inv.samples, pts[gone[kind]], f"{what} inverse {kind}")
+        # (the positive cut is pts[~gone] as a multiset — mirrors and lasso_mirrors hold it against the same exact rules —: the two cuts partition `pts`)
+        assert inv.num_samples + positive[kind][0].num_samples == len(pts), f"{what} inverse {kind}: the two halves do not hold the points once"
+    state = full
+    n = int(m["query"]["lasso", "all"][1]["numSamples"])
+    colors = np.random.RandomState(PAINT_SEED + 1).randint(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    for kind, paint, col, with_previous in (("region", Paint.set(SET_COLOR), None, False), ("footprint", pf.paints(size)["ramp"], None, True), ("lasso", Paint.array(), colors, True)):
+        region, fp, lasso = selections(q)[kind]
+        e, c, prev = state.paint(region, paint, footprint=fp, lasso=lasso, colors=col, return_previous=True, invert=True)
+        assert c.tobytes() == m["query"][kind, "all"][1].tobytes() and len(prev) == int(c["numSamples"]), f"{what} inverse paint {kind}: not the inverse query's counts"
+        assert (e.samples["color"] != state.samples["color"]).any(), f"{what} inverse paint {kind}: the call changes nothing"
+        assert np.array_equal(prev, state.samples["color"][m["index"][kind, "all"]]), f"{what} inverse paint {kind}: previous is not in the inverse query's order"
+        m["paint"].append(InversePaint(selections(q)[kind], paint, col, with_previous, e, c, prev))
+        state = e
+    back = state.samples["color"].copy()                        # the undo: an ARRAY paint writes previous[j] to sample j of the query's order (rule I8)
+    for kind, call in reversed(list(zip(selections(q), m["paint"]))):
+        back[m["index"][kind, "all"]] = call.previous
+    assert np.array_equal(back, full.samples["color"]) and state.nodes.tobytes() == full.nodes.tobytes(), f"{what} inverse paint: the undo is not the octree before"
+    return m
+
+
+def assert_forced_empty_listed(full, inverse, pts, mine, box):
+    """State H: at least one node the mask forces (assert_masked_rank) holds no sample before any query — the rank never put a point under it
+    —, and every inverse table lists it where the export does, at zero samples: a node that reaches the classes of rule I2 empty.  -> how many"""
+    t = full.nodes
+    empty = (points_in_nodes(t, mine, box) == 0) & (points_in_nodes(t, pts, box) > 0) & (t["numSamples"] == 0)
+    assert int(empty.sum()) >= 1, "every node the mask forces holds samples"
+    for key, (ex, cnt) in inverse["query"].items():
+        e = ex.nodes
+        assert len(e) == len(t) and all(np.array_equal(e[f][empty], t[f][empty]) for f in ("level", "X", "Y", "Z")) and not e["numSamples"][empty].any(), f"inverse {key}: a forced empty node"
+    return int(empty.sum())
+
+
+def assert_halves_add_up(pos, inv, whole, what):
+    """Rules I6 / I7 on summaries: a selection's and its inverse's count, sums and histograms add up to the whole box's, field by field."""
+    assert pos.num_samples + inv.num_samples == whole.num_samples, f"{what}: {pos.num_samples} + {inv.num_samples} samples of {whole.num_samples}"
+    for f in ("histC", "histZ", "sum", "sum2", "numNonFinite"):
+        assert np.array_equal(pos[f] + inv[f], whole[f]), f"{what}: {f} of the two halves does not add up to the whole box's"
 
 
 def words(a):
@@ -457,10 +707,14 @@ def held_table(view, counts):
 
 # ---- the states' shapes, and their oracle twins ----------------------------------------------------------------------------------------------------
 # (what the GPU tier passes to the battery; tests/test_builder_states_io.py holds every one of them against the oracle's octree of the same input)
-SHAPES = {"A": NINE_NODES, "C": Shape(), "D hotspot_150k": Shape(region_copies=False), "D dense_cube": Shape(), "E": Shape(), "E1": Shape(delta_adds=False, profile_copies=False), "F": Shape(), "H": Shape(),
-          "G 600000 poisoned": Shape(), "G 600000 continued": Shape(), "G 90000 poisoned": ROOT_LEAF,
-          "G 90000 continued": Shape("inside", delta_adds=False, coarser=False, profile_copies=False),
-          "I A": Shape("bird"), "I B": Shape("inside", delta_adds=False)}
+# (the inverse's facts: a half-space through the middle and a star around a quarter leave a node outside only where the octree is deep enough —
+# the star from four terrain batches on; seen from inside, or from `closer` on 17 nodes, no node lies in the lasso whole)
+_NO_CULL = dict(region_culls=False, footprint_culls=False)
+SHAPES = {"A": NINE_NODES, "B": NINE_NODES, "C": Shape(), "D hotspot_150k": Shape(region_copies=False, lasso_culls=False, **_NO_CULL), "D dense_cube": Shape(), "E": Shape(),
+          "E1": Shape(delta_adds=False, profile_copies=False, lasso_copies=False, **_NO_CULL), "E2": Shape(footprint_culls=False), "E3": Shape(footprint_culls=False),
+          "F": Shape(), "H": Shape(), "G 600000 poisoned": Shape(), "G 600000 continued": Shape(), "G 90000 poisoned": ROOT_LEAF,
+          "G 90000 continued": Shape("inside", delta_adds=False, coarser=False, profile_copies=False, lasso_copies=False, lasso_culls=False, **_NO_CULL),
+          "I A": Shape("bird", footprint_culls=False), "I B": Shape("inside", delta_adds=False, lasso_copies=False, **_NO_CULL)}
 G_CASES = [(600_000, 300_000, 100_000), (90_000, 30_000, 15_000)]
 
 

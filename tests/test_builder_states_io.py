@@ -1,7 +1,10 @@
 """CPU tier of tests/test_gpu_builder_states.py: what that module holds the device against must stand on its own first.  `collapse` (the
 mirrors' first leaves of more than 50 chunks) against brute force and against itself; the oracle twins of the states, each through the
 guards the GPU battery uses, with the Shape it uses; the oracle's continuous build that a resumed import of over-full leaves must reach; and
-the precondition helpers, each against a hand-made input that does not take the path.  Oracle, numpy mirrors and brute force only."""
+the precondition helpers, each against a hand-made input that does not take the path.  The lasso, the summaries and the inverses (query,
+summary, paint) run on the collapsed octree and on every twin with the rest of the battery's mirrors: their guards hold by the references
+alone, on the collapsed octree each of them reaches samples behind a leaf's row with the classes the node rules give, and on every twin the
+summaries of a selection and of its inverse add up to the whole box's.  Oracle, numpy mirrors and brute force only."""
 import numpy as np
 import pytest
 
@@ -15,7 +18,7 @@ import rays_ref as yr
 import region_ref as rr
 import states_ref as sr
 from simlod_amd import abi
-from simlod_amd.octree_io import Region, classify_footprint, classify_nodes, classify_profile, delta_between
+from simlod_amd.octree_io import Region, classify_footprint, classify_lasso, classify_nodes, classify_profile, delta_between
 from test_gpu_trunk import _partition
 
 _TWINS, _MIRRORS = {}, {}
@@ -108,8 +111,8 @@ def test_held_counts_around_the_row_end_send_exactly_the_tails(built_libs):
     assert delta_ref.states(w) == (4, 0, 4, 4) and w.num_samples == int(fresh.nodes["numSamples"][idx].astype(np.int64).sum())
 
 
-def _result_classes(full, result, region, footprint=None, profile=None):
-    """Per entry of a crop's table, by the node rules alone (region rule 2, footprint rules F3 / F4, profile rule P3):
+def _result_classes(full, result, region, footprint=None, profile=None, lasso=None):
+    """Per entry of a crop's table, by the node rules alone (region rule 2, footprint rules F3 / F4, profile rule P3, lasso rules L2-L4):
     -> (its entry in `full`, whether the node is copied whole, whether it is filtered sample by sample)"""
     key = lambda a: list(zip(a["level"].tolist(), a["X"].tolist(), a["Y"].tolist(), a["Z"].tolist()))
     at = {k: i for i, k in enumerate(key(full.nodes))}
@@ -121,7 +124,53 @@ def _result_classes(full, result, region, footprint=None, profile=None):
     if profile is not None:
         far, covered = classify_profile(profile, full.nodes, full.box_min, full.box_max)
         out, ins = out | far, ins & covered
+    if lasso is not None:
+        behind, covered = classify_lasso(lasso, full.nodes, full.box_min, full.box_max)
+        out, ins = out | behind, ins & covered
     return src, ins[src], ~out[src] & ~ins[src]
+
+
+def test_lasso_summary_and_inverse_on_the_collapsed_octree_reach_behind_the_row(built_libs):
+    """What makes state A worth running for the lasso, the summary and the inverse: the screen lasso filters seven leaves of 75 chunks, and
+    samples pass at ordinals of 50 000 and more; each summary's contributing samples (the crop's, rule S0) include such samples; each inverse
+    paint recolours such samples — in a leaf the inverse copies whole (the lasso leaves one outside: every chunk behind the row is stored, by
+    the SET without `previous` too where the selection has such a leaf) and in leaves it filters.  Per node the results' classes are the node
+    rules' (_result_classes): what the selection copies the inverse lists at zero samples, what it leaves outside the inverse copies whole."""
+    c, pts, box, shape, _ = _twin("A")
+    m = _mirrors("A")
+    q = m["q"]
+    row = sr.ROW * abi.POINTS_PER_CHUNK
+    ns = c.nodes["numSamples"].astype(np.int64)
+    ex, cnt = m["lasso"]["cut"]
+    again, index = c.crop(Region(), 20, "cut", lasso=q.lasso, return_index=True)
+    assert again.samples.tobytes() == ex.samples.tobytes() and again.nodes.tobytes() == ex.nodes.tobytes()
+    src, copied, filtered = _result_classes(c, ex, Region(), lasso=q.lasso)
+    leaf = (ex.nodes["flags"] & abi.EXPORT_FLAG_LEAF) != 0
+    assert (int((copied & leaf).sum()), int((filtered & leaf).sum())) == (int(cnt["numCopiedNodes"]), int(cnt["numFilteredNodes"])) == (0, 7)
+    n, first = ex.nodes["numSamples"].astype(np.int64), ex.nodes["firstSample"].astype(np.int64)
+    behind = [int((index[first[t]: first[t] + n[t]] - int(c.nodes["firstSample"][src[t]]) >= row).sum()) for t in np.nonzero(filtered & leaf)[0]]
+    assert sum(behind) == sr.behind_row(c, index) and max(behind) >= 1, "no leaf the lasso filters has a passing sample behind the row"
+    print(f"lasso on A: passing samples at ordinals >= 50 000 per filtered leaf {behind}")
+    for (kind, sel), region, lasso in ((("region", "cut"), q.region, None), (("region", "all"), q.region, None), (("lasso", "cut"), Region(), q.lasso), (("box", "cut"), Region(), None)):
+        index = c.crop(region, 20, sel, lasso=lasso, return_index=True)[1]
+        assert m["summary"][kind, sel][0].num_samples == len(index) and sr.behind_row(c, index) >= 1, f"summary {kind} {sel}: no contributing sample behind the row"
+    state, far = c, {"copied": 0, "filtered": 0}
+    for kind, call in zip(sr.selections(q), m["inverse"]["paint"]):
+        region, fp, lasso = call.sel3
+        res, index = state.crop(region, 20, "all", footprint=fp, lasso=lasso, invert=True, return_index=True)
+        assert np.array_equal(state.samples["color"][index], call.previous) and res.nodes.tobytes() == m["inverse"]["query"][kind, "all"][0].nodes.tobytes()
+        src, emptied, filtered = _result_classes(c, res, region, fp, lasso=lasso)
+        assert np.array_equal(src, np.arange(c.num_nodes))                              # rule I3: every node, in the export's order
+        whole = ~emptied & ~filtered
+        n = res.nodes["numSamples"].astype(np.int64)
+        assert not n[emptied].any() and np.array_equal(n[whole], ns[whole])
+        assert (int((whole & (ns > 0)).sum()), int((filtered & (ns > 0)).sum())) == (int(call.counts["numCopiedNodes"]), int(call.counts["numFilteredNodes"]))
+        assert sr.behind_row(c, index) >= 1, f"inverse paint {kind}: no recoloured sample behind the row"
+        far["copied"] += int((whole & (n > row)).sum())
+        far["filtered"] += int(sum(sr.behind_row(c, index[(index >= int(c.nodes["firstSample"][t])) & (index < int(c.nodes["firstSample"][t]) + ns[t])]) > 0 for t in np.nonzero(filtered & (ns > row))[0]))
+        state = call.export
+    print(f"inverse paint on A: leaves recoloured at a per-node offset >= 50 000: {far}")
+    assert far["copied"] >= 1 and far["filtered"] >= 1, far
 
 
 def test_profile_and_paint_on_the_collapsed_octree_reach_behind_the_row(built_libs):
@@ -217,11 +266,26 @@ def test_packed_tails_around_the_row_end_merge_within_the_bound(built_libs):
                                   "G 90000 poisoned", "G 90000 continued", "I A", "I B"])
 def test_oracle_twin_passes_the_guards_of_its_state(built_libs, name):
     """The battery's mirrors on the oracle's octree of the state's input, with the Shape the GPU tier passes: every guard holds, the cuts are
-    the brute-force filters, t and d2 are the brute force's.  (E1 .. E5: whatever number of batches a launch under the time budget takes.)"""
+    the brute-force filters, t and d2 are the brute force's; the lasso's and the inverses' cuts are the exact rules' over the points, the
+    summaries summary_ref's, and the summaries of a selection and of its inverse add up to the whole box's field by field (rules I6 / I7).
+    (E1 .. E5: whatever number of batches a launch under the time budget takes.)"""
     ex, pts, box, shape, ho = _twin(name)
     ex.validate(buildable=True)
     rr.assert_same_multiset(ex.truncated(20, "cut").samples, pts, name)
-    _mirrors(name)
+    m = _mirrors(name)
+    print(f"{name}: the lasso copies {int(m['lasso']['cut'][1]['numCopiedNodes'])} leaves and filters {int(m['lasso']['cut'][1]['numFilteredNodes'])}; "
+          f"leaves the inverses empty / copy whole: {m['inverse']['classes']}")
+    q = m["q"]
+    foot = ex.summarize(Region(), 20, "cut", footprint=q.footprint, z0=q.z0, scale=q.scale)
+    sr.assert_halves_add_up(foot, m["inverse"]["summary"]["footprint", "cut"][0], m["summary"]["box", "cut"][0], f"{name}: the footprint's halves")
+    if name == "H":
+        allpts, _, mask, mine, _ = sr.h_input(_partition)
+        assert sr.assert_forced_empty_listed(ex, m["inverse"], allpts, mine, box) >= 1
+    if name.startswith("E"):
+        # the inverse summary the GPU tier enqueues directly behind the launch is of the BOX's oblique half-space (the host does not know yet
+        # which batches the launch took): whatever it took, that inverse holds some of the samples and not all
+        cnt = ex.crop(rr.region("oblique", box), 20, "all", return_counts=True, invert=True)[1]
+        assert 0 < int(cnt["numSamples"]) < ex.num_samples, f"{name}: {int(cnt['numSamples'])} of {ex.num_samples} samples outside the box's oblique half-space"
 
 
 def test_twin_of_e_is_the_octree_of_two_of_six_batches(built_libs):
@@ -308,3 +372,16 @@ def test_precondition_helpers_reject_octrees_off_the_path(built_libs):
     cnt["numCopiedNodes"], cnt["numSamples"] = 1, 10
     with pytest.raises(AssertionError):
         sr.assert_crop_not_vacuous(cnt, "hand-made")
+    # behind the row: ordinal 49 999 of a leaf is in the row's last chunk, 50 000 in the first behind it; an inner node's voxels never count
+    a = int(c.nodes["firstSample"][1])
+    assert [sr.behind_row(c, [i]) for i in (0, a + 49_999, a + 50_000, a + int(c.nodes["numSamples"][1]) - 1)] == [0, 0, 1, 1]
+    # halves that do not add up, a summary that is not the selection's, a forced node that is not empty
+    m = _mirrors("A")
+    pos, inv, whole = m["summary"]["region", "cut"][0], m["inverse"]["summary"]["region", "cut"][0], m["summary"]["box", "cut"][0]
+    sr.assert_halves_add_up(pos, inv, whole, "hand-made")
+    with pytest.raises(AssertionError):
+        sr.assert_halves_add_up(pos, pos, whole, "hand-made")
+    with pytest.raises(AssertionError):
+        sr.assert_summary_is_exact(pos, pts[sr.rr.brute_mask(m["q"].region, pts)][1:], c, m["q"], "hand-made")
+    with pytest.raises(AssertionError, match="holds samples"):
+        sr.assert_forced_empty_listed(c, m["inverse"], pts, pts[:1], box)       # (every node of A holds samples)

@@ -4,9 +4,15 @@ coalesced mode, a launch that stopped short with no host wait before the export,
 under a trunk mask, two octrees in one context and a rebuild in the same buffers.  Every state first asserts its precondition from Stats and
 the downloaded image, then goes through ONE battery: the export anchored byte for byte to export_ref.export_host of the downloaded image,
 the chunk table's stamp through the rasteriser's counter, one query of each kind against the numpy mirrors on the anchored export (guarded
-and held against brute force over the points the octree holds, tests/states_ref.py) — a profile, pack / unpack of the export and two paint
-calls with their undo among them —, and all of it again with the table dropped.  Where the builder goes on after a state (B, C, E), the octree
-is painted whole first and must end as the oracle's octree of the recoloured input (paint rule E7)."""
+and held against brute force over the points the octree holds, tests/states_ref.py) — a profile, pack / unpack of the export, two paint
+calls with their undo, a lasso on the screen of the view's camera (and the footprint once more as a lasso), summaries of the region, the lasso
+and the whole box (each once more from one workgroup), and the inverse of the region, the footprint and the lasso as a query, a summary and
+three paints on top of each other with their undo, one of them a SET without `previous` —, and all of it again with the table dropped.
+State B goes through the same battery twice: the plain import of A, and the buildable import of A before its resume.
+Where the builder goes on after a state (B, C, E), the octree is painted whole first and must end as the oracle's octree of the recoloured
+input (paint rule E7).  erase_region ends in an import, which leaves an octree render-only: it runs on a copy of the state in a second device
+object (A, C deferred, G's root leaf, H, the larger octree of I) against the frames the state itself draws with SIMLOD_CLIP_OUTSIDE; and state E
+enqueues an inverse summary, like its export, directly behind the launch that stops short."""
 import ctypes
 
 import numpy as np
@@ -18,18 +24,21 @@ import oracle
 import region_ref as rr
 import states_ref as sr
 import test_gpu_footprint as on_footprints
+import test_gpu_inverse as on_inverse
+import test_gpu_lasso as on_lassos
 import test_gpu_neighbours as on_spheres
 import test_gpu_pack as on_pack
 import test_gpu_paint as on_paint
 import test_gpu_profile as on_profile
 import test_gpu_rays as on_rays
 import test_gpu_region as on_regions
+import test_gpu_summary as on_summary
 import test_gpu_view as on_view
 import test_gpu_view_delta as on_delta
 import view_ref as vr
 from export_ref import export_host
 from simlod_amd import abi, synthetic
-from simlod_amd.octree_io import OctreeExport, Paint, Region
+from simlod_amd.octree_io import Clip, OctreeExport, Paint, Region
 from states_ref import State
 from test_gpu_deep_octrees import _count_fields, _feed_one_by_one, _feed_one_group
 from test_gpu_export import _assert_export, _device, _frames_equal
@@ -160,17 +169,113 @@ def _paints(S, M, what):
     return painted
 
 
-def _battery(S, table, what, shape=sr.Shape(), pairs_all=False, between=None):
+def _lassos(S, M, what):
+    """simlod_query_lasso for the screen lasso, cut and all, and for the footprint's lasso: counts, table and samples byte for byte, poison
+    behind them; the count-only call has the same counts and table and writes no sample.  -> the mirror's counts of the cut"""
+    q = M["q"]
+    for key, (mirror, cnt) in M["lasso"].items():
+        lasso, sel = (q.foot_lasso, "cut") if key == "footprint" else (q.lasso, key)
+        on_lassos._assert_matches(on_lassos.Raw(S.dev, S.u, lasso, None, 20, sel), mirror, cnt, f"{what} lasso {key}")
+        only = on_lassos.Raw(S.dev, S.u, lasso, None, 20, sel, count_only=True)
+        assert only.rc == 0 and _count_fields(only.counts) == _count_fields(cnt) and only.table_bytes() == mirror.nodes.tobytes(), f"{what} lasso {key}: the count-only call"
+        assert only.poison_behind(mirror.num_nodes, 0), f"{what} lasso {key}: the count-only call wrote a sample"
+    return M["lasso"]["cut"][1]
+
+
+def _assert_summary(raw, want, cnt, table, what):
+    """One raw summary call of any of the three entry points: counts, table and record are the mirror's, poison behind table and record."""
+    assert raw.rc == 0 and _count_fields(raw.counts) == _count_fields(cnt), f"{what}: counts {raw.counts}, the mirror has {cnt}"
+    n = int(cnt["numNodes"])
+    assert raw.table[: n * 40].cpu().numpy().tobytes() == table.tobytes(), f"{what}: the table differs"
+    assert bool((raw.table[n * 40:] == 0xA5).all()) and bool((raw.out_t[on_summary.NBYTES:] == 0xA5).all()), f"{what}: written past the table or the record"
+    got = raw.out_t[: on_summary.NBYTES].cpu().numpy().view(abi.summary_dtype)[0]
+    for f in abi.summary_dtype.names:
+        assert got[f].tobytes() == want[f].tobytes(), f"{what}: {f} differs: {got[f]} != {want[f]}"
+    assert raw.summary_bytes() == want.tobytes(), what
+
+
+def _summaries(S, M, what):
+    """simlod_query_summary for the region (cut and all) and the whole box, simlod_query_summary_lasso for the screen lasso: the record byte
+    for byte the mirror's, and once more from ONE workgroup (rule S7: the bytes do not depend on the grid).  -> the mirror's Summary of the
+    region's cut"""
+    q = M["q"]
+    for (kind, sel), (want, cnt, table) in M["summary"].items():
+        for wg in (0, 1):
+            if kind == "lasso":
+                raw = on_lassos.RawSummary(S.dev, S.u, Region(), q.lasso, ml=20, sel=sel, z0=q.z0, scale=q.scale, max_wg=wg)
+            else:
+                raw = on_summary.Raw(S.dev, S.u, q.region if kind == "region" else Region(), None, ml=20, sel=sel, z0=q.z0, scale=q.scale, max_wg=wg)
+            _assert_summary(raw, want, cnt, table, f"{what} summary {kind} {sel}, maxWorkgroups {wg}")
+    return M["summary"]["region", "cut"][0]
+
+
+def _inverses(S, M, what):
+    """simlod_query_inverse (cut, all and count-only), simlod_query_summary_inverse and simlod_paint_inverse for the region, the footprint and
+    the screen lasso against the mirrors.  The three paints stand on top of each other — the first a SET without `previous`, the path that
+    stores without loading on the chunks the positive query culls —; after each the export is the mirror's and the Node array and Stats are
+    as before; ARRAY paints of `previous` in reverse order (for the SET: the colours the mirror remembers) give back the image taken before,
+    Node array, Stats and every allocated byte of the persistent buffer.  -> the mirror's counts of the three cuts"""
+    dev, u, q, I = S.dev, S.u, M["q"], M["inverse"]
+    sels = sr.selections(q)
+    for (kind, sel), (mirror, cnt) in I["query"].items():
+        on_inverse._assert_matches(on_inverse.Raw(dev, u, sels[kind], 20, sel), mirror, cnt, f"{what} inverse {kind} {sel}")
+        only = on_inverse.Raw(dev, u, sels[kind], 20, sel, count_only=True)
+        assert only.rc == 0 and _count_fields(only.counts) == _count_fields(cnt) and only.table_bytes() == mirror.nodes.tobytes(), f"{what} inverse {kind} {sel}: the count-only call"
+        assert only.poison_behind(mirror.num_nodes, 0), f"{what} inverse {kind} {sel}: the count-only call wrote a sample"
+    for (kind, sel), (want, cnt) in I["summary"].items():
+        raw = on_inverse.RawSummary(dev, u, sels[kind], ml=20, sel=sel, z0=q.z0, scale=q.scale)
+        _assert_summary(raw, want, cnt, I["query"][kind, sel][0].nodes, f"{what} inverse summary {kind} {sel}")
+    before = on_paint._image(dev)
+    for kind, call in zip(sels, I["paint"]):
+        tag = f"{what} inverse paint by the {kind}"
+        n = int(call.counts["numSamples"])
+        raw = on_inverse.RawPaint(dev, u, call.paint, call.sel3, colors=call.colors, previous=call.with_previous)
+        assert raw.rc == 0 and _count_fields(raw.counts) == _count_fields(call.counts), f"{tag}: counts {raw.counts}, the mirror has {call.counts}"
+        nn = int(call.counts["numNodes"])
+        assert raw.table[: nn * 40].cpu().numpy().tobytes() == I["query"][kind, "all"][0].nodes.tobytes(), f"{tag}: not the inverse query's table (rule I8)"
+        assert bool((raw.table[nn * 40:] == 0xA5).all()), f"{tag}: the table was written past numNodes"
+        got = raw.previous()
+        if call.with_previous:
+            assert np.array_equal(got[:n], call.previous), f"{tag}: {int((got[:n] != call.previous).sum())} words of previous differ, the first at {int(np.argmax(got[:n] != call.previous))}"
+            assert (got[n:] == on_inverse.POISON).all(), f"{tag}: previous was written past numSamples"
+        else:
+            assert (got == on_inverse.POISON).all(), f"{tag}: previous was written without being given"
+        ex = dev.export_octree(u)
+        assert ex.nodes.tobytes() == call.export.nodes.tobytes(), f"{tag}: the table of the export moved"
+        assert ex.samples.tobytes() == call.export.samples.tobytes(), f"{tag}: {int((ex.samples['color'] != call.export.samples['color']).sum())} colours differ from the mirror's"
+        # (the export above shows what was painted; the persistent buffer's bytes are compared once, after the undo)
+        assert dev.nodes[: len(before[0])].cpu().numpy().tobytes() == before[0] and dev.stats.cpu().numpy().tobytes() == before[1], f"{tag}: the Node array or Stats moved"
+    for call in reversed(I["paint"]):
+        raw = on_inverse.RawPaint(dev, u, Paint.array(), call.sel3, colors=call.previous, previous=False)
+        assert raw.rc == 0 and _count_fields(raw.counts) == _count_fields(call.counts), f"{what}: the counts of the inverse paints' undo"
+    after = on_paint._image(dev)
+    assert after[0] == before[0] and after[1] == before[1], f"{what}: the Node array or Stats differ after the inverse paints' undo"
+    assert after[2] == before[2], f"{what}: the persistent buffer differs after the inverse paints' undo"
+    return {kind: I["query"][kind, "cut"][1] for kind in sels}
+
+
+def _battery(S, table, what, shape=sr.Shape(), pairs_all=False, between=None, erase=None, check=None, cache=None):
     """Points 1-4 of the battery on one state.  table: whether the state claims a valid chunk table — True: a frame reads lists through it;
     False: it must not; "long": the stamp holds, but every list a frame can draw is longer than a row and the rasteriser, which takes whole
     rows only, reads none (the read side takes the row and follows `next` behind it: the fault table of DESIGN §7 shows that it does).
-    between(): called between the crops and the pair queries (a host whose launches keep coming).  -> the anchored full export"""
+    between(): called between the crops and the pair queries (a host whose launches keep coming).  erase ("frames" / "no frames"): after
+    everything else, _erase_on_a_copy.  check(full, M): a guard of the state's own on the anchored export and the mirrors, before the device
+    is asked.  cache (a dict): the mirrors of an anchored export are kept in it and taken from it for an export that is byte for byte the same (A and its
+    imports: the mirrors depend on the export, the points and the camera alone).  -> the anchored full export"""
     dev = S.dev
     full, used = _anchor(S, what)
     print(f"{what}: {full.num_nodes} nodes, {full.num_samples} samples, {used} lists read through the table")
     assert (used > 0) if table is True else (used == 0), f"{what}: {used} chunk lists read through the table"
     uv = on_view._uniforms(dev, S.u, vr.transform_of(shape.camera, S.box))
-    M = sr.mirrors(full, S.pts, uv, what, shape, pairs_all)
+    image = (full.nodes.tobytes(), full.samples.tobytes(), shape, pairs_all)
+    if cache is not None and cache.get("image") == image:
+        M = cache["mirrors"]
+    else:
+        M = sr.mirrors(full, S.pts, uv, what, shape, pairs_all)
+        if cache is not None:
+            cache.update(image=image, mirrors=M)
+    if check is not None:
+        check(full, M)
     for source in ("chunk table" if table else "no table", "walk"):
         _crops(S, M, f"{what} ({source})")
         if between is not None:
@@ -179,14 +284,83 @@ def _battery(S, table, what, shape=sr.Shape(), pairs_all=False, between=None):
         _views(S, uv, M, f"{what} ({source})")
         pc = _profiles(S, M, f"{what} ({source})")
         _packs(S, full, M, f"{what} ({source})")
-        painted = _paints(S, M, f"{what} ({source})")           # last: it writes the octree, and undoes it
+        lc = _lassos(S, M, f"{what} ({source})")
+        sm = _summaries(S, M, f"{what} ({source})")
+        painted = _paints(S, M, f"{what} ({source})")           # last, with the inverses: they write the octree, and undo it
+        ic = _inverses(S, M, f"{what} ({source})")
         print(f"{what} ({source}): the profile copies {int(pc['numCopiedNodes'])} nodes and filters {int(pc['numFilteredNodes'])} ({int(pc['numSamples'])} samples), "
               f"the paint calls recolour {painted[0]} and {painted[1]} samples")
+        print(f"{what} ({source}): the lasso copies {int(lc['numCopiedNodes'])} nodes and filters {int(lc['numFilteredNodes'])} ({int(lc['numSamples'])} samples), the region's summary holds "
+              f"{sm.num_samples} samples; the inverses (leaves copied / filtered / emptied, samples): "
+              + ", ".join(f"{kind} {int(c['numCopiedNodes'])} / {int(c['numFilteredNodes'])} / {M['inverse']['classes'][kind][0]}, {int(c['numSamples'])}" for kind, c in ic.items())
+              + f"; the inverse paints recolour {', '.join(str(int(p.counts['numSamples'])) for p in M['inverse']['paint'])} samples")
         if source != "walk":
             assert dev.L.simlod_octree_image_replaced(dev._p(dev.nodes)) == 0    # point 4, last: the builder's side tables go with it
     dev.render(S.u)
     assert dev.lists_read_through_table() == 0, f"{what}: the table is still read after simlod_octree_image_replaced"
+    if erase is not None:
+        _erase_on_a_copy(S, full, M, what, frames=erase == "frames")
     return full
+
+
+def _erase_on_a_copy(S, full, M, what, frames=True):
+    """erase_region on a state: the import it ends with leaves an octree render-only, so it runs on a COPY — the state's export imported into
+    a second device object whose node array was poisoned — and the state's builder can go on.  What test_erase_makes_clip_outside_permanent
+    asserts: the counts are the mirror's inverse (all@20) of the battery's region; Stats; the copy's frames, plain and HQS, are word for word
+    the frames the SOURCE draws with Clip(region, "outside"); the re-export is the mirror's inverse byte for byte.  Then the footprint erased
+    from what is left: the leaves the star holds whole are listed at zero samples.  frames=False: an octree whose root is a leaf — the export
+    carries the root's points and not its voxel list, which a render-only import does not give back (include/simlod_hip.h: only the
+    buildable import promises "a root that is still a leaf gets its voxels back"), so the header promises no equal frame there."""
+    src, u = S.dev, S.u
+    q = M["q"]
+    mirror, cnt = M["inverse"]["query"]["region", "all"]
+    dst = _device()
+    dst.nodes.fill_(0xA5)
+    dst.import_octree(src.export_octree(u))
+    assert int(dst.read_stats()["dbg"]) == 0
+    us = []
+    for hqs in (False, True):
+        us.append(np.array(u, copy=True))
+        us[-1]["useHighQualityShading"], us[-1]["showBoundingBox"] = hqs, False
+    clipped = []
+    if frames:
+        assert full.nodes["childMask"][0] != 0
+        src.set_clip(Clip(q.region, "outside"))
+        try:
+            for v in us:
+                src.render(v)
+                clipped.append(src.framebuffer(W, H).copy())
+        finally:
+            src.set_clip(None)
+        src.render(us[0])
+        assert not np.array_equal(src.framebuffer(W, H), clipped[0]), f"{what}: the clip must change the frame"
+    else:
+        assert full.num_nodes == 1
+    c = dst.erase_region(us[0], q.region)
+    assert _count_fields(c) == _count_fields(cnt), f"{what} erase: counts {c}, the mirror's inverse has {cnt}"
+    assert 0 < int(c["numSamples"]) < full.num_samples
+    st = dst.read_stats()
+    assert int(st["dbg"]) == 0 and int(st["numPoints"]) + int(st["numVoxels"]) == int(c["numSamples"]) and int(st["numNodes"]) == full.num_nodes
+    for v, want in zip(us, clipped):
+        dst.render(v)
+        got = dst.framebuffer(W, H)
+        assert int(dst.read_stats()["dbg"]) == 0
+        diff = np.nonzero(got != want)[0]
+        assert len(diff) == 0, f"{what} erase, hqs={int(v['useHighQualityShading'])}: {len(diff)} pixels differ from the clipped frame of the source, first {diff[:5]}"
+        assert int((got != abi.CLEAR_PIXEL).sum()) > 100
+    after = dst.export_octree(us[0]).to("cpu")
+    assert after.nodes.tobytes() == mirror.nodes.tobytes() and after.samples.tobytes() == mirror.samples.tobytes(), f"{what} erase: the re-export is not the mirror's inverse"
+    c2 = dst.erase_region(us[0], Region(), footprint=q.footprint)
+    mirror2, cnt2 = after.crop(Region(), 20, "all", return_counts=True, footprint=q.footprint, invert=True)
+    # (on G's root leaf, and only there, the star holds ALL the region's inverse left: the octree that is left is empty, and still the mirror's)
+    assert _count_fields(c2) == _count_fields(cnt2) and (0 if frames else -1) < int(c2["numSamples"]) < int(c["numSamples"]), f"{what} erase, the footprint: counts {c2}, the mirror has {cnt2}"
+    twice = dst.export_octree(us[0])
+    assert twice.nodes.tobytes() == mirror2.nodes.tobytes() and twice.samples.tobytes() == mirror2.samples.tobytes(), f"{what} erase, the footprint: the re-export"
+    emptied = int(((after.nodes["numSamples"] > 0) & (mirror2.nodes["numSamples"] == 0)).sum())
+    print(f"{what} erase: {int(c['numSamples'])} of {full.num_samples} samples left by the region, {int(c2['numSamples'])} by the footprint, which empties {emptied} nodes")
+    with pytest.raises(Exception):
+        dst.construct(us[0])                 # render-only until a reset
+    dst.close()
 
 
 PAINTED = 0xFF57C0DE                         # a colour no input point carries (each test asserts it)
@@ -229,7 +403,7 @@ def _oracle_export(box, batches, **kw):
 
 
 # ---- A. node array full: over-full leaves ----------------------------------------------------------------------------------------------------
-_A = {}
+_A, _A_MIRRORS = {}, {}
 
 
 def _state_a():
@@ -256,6 +430,7 @@ def _release(built_libs):
     from simlod_amd.runtime import lib
     yield
     _A.clear()
+    _A_MIRRORS.clear()
     lib().simlod_set_node_capacity(NODE_CAPACITY)
 
 
@@ -327,7 +502,7 @@ def test_a_leaves_hold_what_the_oracles_subtrees_hold(built_libs):
 
 def test_a_battery(built_libs):
     a = _state_a()
-    _battery(State(a["dev"], a["u"], a["pts"], a["box"]), "long", "A", sr.SHAPES["A"], pairs_all=True)
+    _battery(State(a["dev"], a["u"], a["pts"], a["box"]), "long", "A", sr.SHAPES["A"], pairs_all=True, erase="frames", cache=_A_MIRRORS)
 
 
 # ---- B. import of A ---------------------------------------------------------------------------------------------------------------------------
@@ -343,6 +518,9 @@ def test_b_plain_import_through_a_file(built_libs, tmp_path):
     re = dst.export_octree(u)
     assert re.nodes.tobytes() == full.nodes.tobytes() and re.samples.tobytes() == full.samples.tobytes(), "the re-export differs"
     _frames_equal(src, dst, u, "B plain import")
+    # the whole battery on the import: eight leaves of 75 chunks the IMPORT wrote, no chunk table (the import drops it), every list walked
+    # by `next` from the first chunk on — with A's Shape, long_leaves among it: every inverse result and every summary reaches behind slot 50
+    _battery(State(dst, u, a["pts"], a["box"]), False, "B plain import", sr.SHAPES["B"], pairs_all=True, cache=_A_MIRRORS)
 
 
 @pytest.mark.parametrize("mode", ["batch_by_batch", "one_group"])
@@ -357,6 +535,10 @@ def test_b_resume_splits_the_imported_overfull_leaves(built_libs, tmp_path, mode
     dst = _device()
     dst.tune("SIMLOD_EXACT_GROUP", 1 if mode == "batch_by_batch" else 2)
     uu = _import(dst, ld, a["u"])
+    if mode == "batch_by_batch":
+        # the battery on the buildable import BEFORE its resume (grids rebuilt, a builder state as after a reset, the over-full leaves pending):
+        # the builder goes on afterwards, from the tables it rebuilds behind the battery's simlod_octree_image_replaced
+        _battery(State(dst, uu, a["pts"], a["box"]), False, "B buildable import", sr.SHAPES["B"], pairs_all=True, cache=_A_MIRRORS)
     (_feed_one_by_one if mode == "batch_by_batch" else _feed_one_group)(dst, uu, more)
     st = dst.read_stats()
     assert int(st["dbg"]) == 0 and int(st["numPoints"]) == len(pts) and int(st["numPointsProcessed"]) == 200_000
@@ -435,7 +617,7 @@ def test_c_deferred_splits_and_the_catch_up(built_libs):
     assert int(st["numPoints"]) == C_POINTS == int(st["numPointsProcessed"])
     before = dev.export_octree(u)
     assert sr.assert_state_c(st["dbg"], before.nodes) == C_PENDING
-    _battery(State(dev, u, pts[:C_POINTS], box), True, "C deferred", sr.SHAPES["C"])
+    _battery(State(dev, u, pts[:C_POINTS], box), True, "C deferred", sr.SHAPES["C"], erase="frames")
     # rule E7 across the catch-up: everything painted while the splits are pending — the next batch moves those leaves' points
     st = dev.read_stats()
     pending = dev.export_octree(u)
@@ -492,12 +674,23 @@ def test_e_export_directly_behind_a_launch_that_stops_short(built_libs, stop):
     need = int(dev.L.simlod_export_buffer_min_bytes(nn, ns))
     scratch, table = torch.empty(need, dtype=torch.uint8, device=dev.device), torch.empty(nn * 40, dtype=torch.uint8, device=dev.device)
     samples, counts = torch.empty(ns * 16, dtype=torch.uint8, device=dev.device), torch.zeros(abi.export_counts_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+    # ... and an inverse summary behind the export, of a region and in bins the host can state before it knows what the launch took: the
+    # box's oblique half-space, the bins of test_gpu_inverse._bins
+    region, (z0, scale) = rr.region("oblique", box), on_inverse._bins(box)
+    sneed = int(dev.L.simlod_summary_buffer_min_bytes(nn, ns))
+    sscratch, stable = on_inverse._mk(dev, sneed), on_inverse._mk(dev, (nn + on_inverse.SLACK) * 40)
+    sout, scounts = on_inverse._mk(dev, on_summary.NBYTES + on_inverse.SLACK), on_inverse._mk(dev, abi.query_counts_dtype.itemsize)
+    rrec, prec = region.record(), np.zeros(1, dtype=abi.summary_params_dtype)
+    prec["z0"], prec["scale"] = z0, scale
+    uu, up = dev._u(u)
     torch.cuda.synchronize()
     dev.construct(u)                                                     # ... and, with nothing in between on the host, the export behind it
     rc = dev.L.simlod_export_octree(dev._p(dev.nodes), dev._p(dev.stats), abi.MAX_DEPTH, abi.EXPORT_ALL, dev._p(scratch), ctypes.c_uint64(need), dev._p(table), nn,
                                     dev._p(samples), ctypes.c_uint64(ns), dev._p(counts), dev._stream())
+    src = dev.L.simlod_query_summary_inverse(dev._p(dev.nodes), dev._p(dev.stats), up, on_inverse._ptr(rrec), None, None, on_inverse._ptr(prec), abi.MAX_DEPTH,
+                                             abi.EXPORT_ALL, dev._p(sscratch), ctypes.c_uint64(sneed), dev._p(stable), nn, dev._p(sout), dev._p(scounts), dev._stream())
     torch.cuda.synchronize()
-    assert rc == 0
+    assert rc == 0 and src == 0
     c = counts.cpu().numpy().view(abi.export_counts_dtype)[0]
     st = dev.read_stats()
     b = int(st["batchletIndex"])
@@ -507,6 +700,13 @@ def test_e_export_directly_behind_a_launch_that_stops_short(built_libs, stop):
     ex = OctreeExport(table[: int(c["numNodes"]) * 40], samples[: int(c["numSamples"]) * 16], u["boxMin"], u["boxMax"])
     nodes, pers, n = host_image_of(dev)
     _assert_export(ex, *export_host(nodes, n), f"E {stop}: the export behind the launch")
+    want, wc = ex.to("cpu").summarize(region, 20, "all", z0=z0, scale=scale, return_counts=True, invert=True)
+    sc = scounts.cpu().numpy()[:32].view(abi.query_counts_dtype)[0]
+    assert int(sc["error"]) == 0 and _count_fields(sc) == _count_fields(wc), f"E {stop}: the inverse summary behind the launch counts {sc}, the mirror of the export {wc}"
+    assert 0 < int(wc["numSamples"]) < ex.num_samples and int(wc["numNodes"]) == ex.num_nodes
+    assert sout[: on_summary.NBYTES].cpu().numpy().tobytes() == want.tobytes(), f"E {stop}: the inverse summary behind the launch is not the mirror's of the export behind it"
+    assert stable[: ex.num_nodes * 40].cpu().numpy().tobytes() == ex.to("cpu").crop(region, 20, "all", invert=True).nodes.tobytes(), f"E {stop}: the inverse summary's table"
+    assert bool((stable[ex.num_nodes * 40:] == 0xA5).all()) and bool((sout[on_summary.NBYTES:] == 0xA5).all()), f"E {stop}: the inverse summary wrote past its table or its record"
     want, _ = _oracle_export(box, batches[:b])
     sr.assert_same_per_node(ex, want, f"E {stop} against the oracle's octree of {b} batches")
     _battery(State(dev, u, np.concatenate(batches[:b]), box), True, f"E {stop}", sr.SHAPES.get(f"E{b}", sr.SHAPES["E"]))
@@ -574,7 +774,7 @@ def test_g_foreign_image_continued(built_libs, total, first, batch):
     dev.momentary[4096 + 8_000_000:].fill_(0xA5)
     dev.upload_image(nodes, pers, nn, stats=st)
     small = total < 100_000
-    _battery(State(dev, u, pts[:first], box), False, f"G {total} poisoned", sr.SHAPES[f"G {total} poisoned"])
+    _battery(State(dev, u, pts[:first], box), False, f"G {total} poisoned", sr.SHAPES[f"G {total} poisoned"], erase="no frames" if small else None)
     assert dev.uploaded_host == dev.processed_host == first // batch
     for i in range(first, total, batch):
         dev.upload(pts[i:i + batch])
@@ -597,7 +797,9 @@ def test_h_rank_octree_under_a_trunk_mask(built_libs):
     assert int(dev.read_stats()["dbg"]) == 0
     want, _ = _oracle_export(box, batches, mask=mask)
     sr.assert_masked_rank(want.nodes, pts, mine, box, mask)
-    full = _battery(State(dev, u, mine, box), True, "H", sr.SHAPES["H"])
+    # a node the mask forces is EMPTY before any query, and every inverse lists it at zero samples: the classes of rule I2 see a node without samples
+    forced_empty = lambda full, M: print(f"H: {sr.assert_forced_empty_listed(full, M['inverse'], pts, mine, box)} nodes the mask forces are empty")
+    full = _battery(State(dev, u, mine, box), True, "H", sr.SHAPES["H"], erase="frames", check=forced_empty)
     sr.assert_masked_rank(full.nodes, pts, mine, box, mask)
     sr.assert_same_per_node(full, want, "H against the oracle with the same mask")
 
@@ -635,7 +837,7 @@ def test_i_two_octrees_in_one_context_and_a_rebuild(built_libs):
             assert dev.lists_read_through_table() > 0
         # each battery paints its octree (and undoes it): the OTHER octree of the context — Node array, Stats, every allocated byte — stays
         other = on_paint._image(B)
-        fa = _battery(State(A, ua, pa, box_a), True, "I A", sr.SHAPES["I A"])
+        fa = _battery(State(A, ua, pa, box_a), True, "I A", sr.SHAPES["I A"], erase="frames")
         assert on_paint._image(B) == other, "I: the battery of A, its paint calls among it, changed B"
         other = on_paint._image(A)
         fb = _battery(State(B, ub, pb, box_b), True, "I B", sr.SHAPES["I B"])
