@@ -1459,6 +1459,129 @@ int simlod_compare_samples(const SimlodUniforms* uniforms /*host*/, const Simlod
                            SimlodCompareRecord* records /*or NULL: count only*/, uint32_t* colors /*or NULL*/,
                            SimlodCompareSummary* summary, void* stream);
 
+/* ---- surface queries: each sample's normal and roughness from its neighbours --------------------------------------------------------------------
+ * simlod_surface_samples fits a least-squares plane through the samples of `b` within a radius of every sample of `a` (b == a is the usual
+ * case): the plane's unnormalised normal, the two numbers whose quotient is the surface variation l1 / (l1 + l2 + l3) of the neighbourhood's
+ * covariance (eigenvalues l1 <= l2 <= l3; 0 on a plane, 1/3 for an isotropic blob), `within`, and a colour from a 256-entry table indexed by
+ * a hillshade (the Lambert term against a light direction) or by the variation.  It runs on the compare queries' hash grid over `b`, built
+ * by the same kernels in the same scratch layout; the arrays, the box and the grid's fields of the summary mean what they mean there.
+ *
+ * No division and no square root run on the device: every device operation is an fp64 add, subtract, multiply or compare, an integer
+ * operation, a conversion, or an exact scaling by a power of two, without fused multiply-add, every sum in the order written here.  fp64
+ * SUBNORMALS ARE NOT FLUSHED, on the device or in the host mirror: rule N4 multiplies small entries by a power of two that may leave them
+ * subnormal and relies on IEEE gradual underflow giving the same bits on both sides.  A symmetric 3x3 matrix is its six entries xx, xy, xz,
+ * yy, yz, zz.
+ *  N1. Neighbourhood.  Rules C1, C2 and C4 hold with this record's radius: the valid samples, the test d2 <= rr, and the grid — h, inv, the
+ *      up to 27 cells, numCells, maxCellPopulation, numCandidates and numInvalidB are the compare query's, and so are its refusals.
+ *  N2. Quantised offsets.  invq = 16384.0 / h, one IEEE division made by the launcher on the host.  For a sample s of `b` that passes for
+ *      the sample c of `a`, per axis q = (int32_t)(p * invq) with p = (double)s - (double)c as in rule C2, truncated towards zero.
+ *      |p| <= r * (1 + 2^-52) < h (rule C4's argument), so |q| <= 16384.
+ *  N3. Sums.  Per sample of `a` nine signed 64-bit sums over the passing samples: Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz of q and of the
+ *      products of two q (each <= 2^28: an int32; with fewer than 2^32 neighbours every sum stays below 2^60).  They are integers: they
+ *      depend neither on the order of visiting nor on where the hash table put a cell.  D(S) = (double)(int32_t)(S >> 32) * 4294967296.0 +
+ *      (double)(uint32_t)S — an arithmetic shift, an exact product and one rounded add —, n = (double)within, and for the six entries
+ *      M_uv = n * D(S_uv) - D(S_u) * D(S_v): n^2 times the covariance of the quantised offsets, with no division.
+ *  N4. The scaling P of a symmetric matrix.  m = the largest |x| of its six entries, e = the 11 exponent bits of m, f = the double whose
+ *      bits are (uint64_t)(2046 - e) << 52, i.e. 2^(1023 - e); every entry is multiplied by f — exact for the largest, which lands in
+ *      [1, 2) (in [2^-51, 2) when m itself is subnormal), IEEE-rounded for an entry that becomes subnormal.  m == 0 makes the sample
+ *      degenerate (rule N9).
+ *  N5. The normal.  M <- P(M); t = (Mxx + Myy) + Mzz; B = t*I - M (diagonal entries t - M_uu, the others -M_uv, a change of sign): the
+ *      eigenvector of M's smallest eigenvalue is B's dominant one.  Eight times B <- P(B*B), each entry (Bi0*B0j + Bi1*B1j) + Bi2*B2j for
+ *      i <= j, the matrix kept symmetric.  j* = the FIRST index of the largest diagonal entry of the result, v = its column j*.  Eight
+ *      squarings raise the eigenvalue ratio to the 256th power: with g = (l2 - l1) / (l2 + l3) >= 1/8 the other eigenvectors' share of v is
+ *      at most (7/8)^256 = 1.4e-15.
+ *  N6. Orientation.  orientMode SIMLOD_SURFACE_ORIENT_DIRECTION: o = `orient`, widened; SIMLOD_SURFACE_ORIENT_POSITION (a sensor's
+ *      position): o = (double)orient - (double)c per axis.  s = (vx*ox + vy*oy) + vz*oz; s < 0 negates v, s == 0 keeps it (so a zero
+ *      `orient` direction never flips).  normal[k] = (float)v[k], rounded to nearest.
+ *  N7. Variation.  w = M*v, w_i = (Mi0*v0 + Mi1*v1) + Mi2*v2 with the scaled M and the oriented v; lambdaNum = (v0*w0 + v1*w1) + v2*w2,
+ *      vv = (v0*v0 + v1*v1) + v2*v2, lambdaDen = vv * t.  Both go into the record; the host divides.
+ *  N8. Colour index.  colourBy SIMLOD_SURFACE_SHADE: a = (vx*Lx + vy*Ly) + vz*Lz with L = `light`, widened (finite, not all zero),
+ *      num = a * fabs(a), den = vv * ((Lx*Lx + Ly*Ly) + Lz*Lz): the thresholds are signed squared cosines in [-1, 1].
+ *      SIMLOD_SURFACE_VARIATION: num = lambdaNum, den = lambdaDen: the thresholds are variations in [0, 1].  The index (0 .. 255) is the
+ *      number of the 255 thresholds (finite, ascending: each >= the one before) with thresholds[i] * den <= num, found by binary search —
+ *      den >= 0 and IEEE rounding is monotone, so the products ascend with the thresholds.  colors[i] = table[index]; hist[index] counts it.
+ *  N9. Degenerate and invalid samples.  A valid sample of `a` is degenerate when within < 3 or rule N4 finds m == 0, for M or for any of
+ *      the eight B: normal 0, lambdaNum = lambdaDen = 0, its true `within`, missColor, hist[256], counted in numDegenerate.  An invalid
+ *      sample of `a` gets the same record with within = 0 and is counted in numInvalidA, not in numDegenerate.  Every other sample is
+ *      counted in numEstimated; numWithin is the sum of every record's `within`.
+ * N10. Budget, count only, determinism.  Rules C6 and C7 hold with SIMLOD_SURFACE_ERR_BUDGET (numEstimated = numDegenerate = numWithin = 0
+ *      and hist all zero where no sample is tested).  Rule C8 holds and is stronger here: no index of `b` enters a record, so a record does
+ *      not depend on the order of `b` at all.
+ * Nothing is written but `scratch`, `records`, `colors` and `summary`.  `a` and `b` may be the same array. */
+#define SIMLOD_SURFACE_ERR_BUDGET       0x1u
+#define SIMLOD_SURFACE_SHADE            0u
+#define SIMLOD_SURFACE_VARIATION        1u
+#define SIMLOD_SURFACE_ORIENT_DIRECTION 0u
+#define SIMLOD_SURFACE_ORIENT_POSITION  1u
+typedef struct SimlodSurfaceRecord {   /* DEVICE memory, one per sample of `a`, same index */
+	float    normal[3];                /* rules N5, N6: unnormalised; degenerate or invalid: 0                  */
+	uint32_t within;                   /* valid samples of `b` that pass rule C2                                */
+	double   lambdaNum;                /* rule N7                                                               */
+	double   lambdaDen;                /* rule N7; variation = lambdaNum / lambdaDen                            */
+} SimlodSurfaceRecord;
+typedef struct SimlodSurfaceParams {   /* host memory; read completely before the call returns */
+	float    radius;                   /* finite, >= 0                                                          */
+	uint32_t missColor;                /* rule N9                                                               */
+	uint64_t maxCandidates;            /* rule C6; 0: no limit                                                  */
+	double   thresholds[255];          /* rule N8: ascending, finite                                            */
+	uint32_t table[256];               /* rule N8                                                               */
+	float    light[3];                 /* rule N8: finite; not all zero with SIMLOD_SURFACE_SHADE               */
+	float    orient[3];                /* rule N6: finite                                                       */
+	uint32_t colourBy;                 /* SIMLOD_SURFACE_SHADE or SIMLOD_SURFACE_VARIATION                      */
+	uint32_t orientMode;               /* SIMLOD_SURFACE_ORIENT_DIRECTION or SIMLOD_SURFACE_ORIENT_POSITION     */
+	uint32_t maxWorkgroups;            /* 0: the library's choice; else no kernel launches more workgroups      */
+	uint32_t reserved;                 /* 0                                                                     */
+} SimlodSurfaceParams;
+typedef struct SimlodSurfaceSummary {  /* written by the device; SimlodCompareSummary's layout, field for field */
+	uint32_t error;                    /* SIMLOD_SURFACE_ERR_* bits                                             */
+	uint32_t numCells;                 /* rule C4                                                               */
+	uint32_t maxCellPopulation;        /* rule C4                                                               */
+	uint32_t numInvalidA;              /* rule C1                                                               */
+	uint32_t numInvalidB;              /* rule C1                                                               */
+	uint32_t numEstimated;             /* samples of `a` with a normal                                          */
+	uint64_t numWithin;                /* the sum of within                                                     */
+	uint64_t numCandidates;            /* rule C4                                                               */
+	uint64_t numDegenerate;            /* rule N9                                                               */
+	uint64_t hist[257];                /* rule N8; [256]: degenerate and invalid samples of `a`                 */
+} SimlodSurfaceSummary;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodSurfaceRecord) == 32, "SurfaceRecord");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceRecord, within) == 12, "SurfaceRecord.within");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceRecord, lambdaNum) == 16, "SurfaceRecord.lambdaNum");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceRecord, lambdaDen) == 24, "SurfaceRecord.lambdaDen");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodSurfaceParams) == 3120, "SurfaceParams");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceParams, missColor) == 4, "SurfaceParams.missColor");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceParams, maxCandidates) == 8, "SurfaceParams.maxCandidates");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceParams, thresholds) == 16, "SurfaceParams.thresholds");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceParams, table) == 2056, "SurfaceParams.table");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceParams, light) == 3080, "SurfaceParams.light");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceParams, orient) == 3092, "SurfaceParams.orient");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceParams, colourBy) == 3104, "SurfaceParams.colourBy");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceParams, orientMode) == 3108, "SurfaceParams.orientMode");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceParams, maxWorkgroups) == 3112, "SurfaceParams.maxWorkgroups");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceParams, reserved) == 3116, "SurfaceParams.reserved");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodSurfaceSummary) == sizeof(SimlodCompareSummary), "SurfaceSummary");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceSummary, numCells) == 4, "SurfaceSummary.numCells");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceSummary, maxCellPopulation) == 8, "SurfaceSummary.maxCellPopulation");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceSummary, numInvalidA) == 12, "SurfaceSummary.numInvalidA");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceSummary, numInvalidB) == 16, "SurfaceSummary.numInvalidB");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceSummary, numEstimated) == offsetof(SimlodCompareSummary, numMatched), "SurfaceSummary.numEstimated");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceSummary, numWithin) == 24, "SurfaceSummary.numWithin");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceSummary, numCandidates) == 32, "SurfaceSummary.numCandidates");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceSummary, numDegenerate) == offsetof(SimlodCompareSummary, maxD2), "SurfaceSummary.numDegenerate");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodSurfaceSummary, hist) == 48, "SurfaceSummary.hist");
+
+/* Bytes of the `scratch` buffer a surface call needs: simlod_compare_buffer_min_bytes(numA, numB), the layout is the compare call's. */
+uint64_t simlod_surface_buffer_min_bytes(uint64_t numA, uint64_t numB);
+
+/* The surface query (rules above).  Asynchronous on `stream` once `uniforms` and `params` have been read.  hipErrorInvalidValue with nothing
+ * enqueued and nothing touched: everything simlod_compare_samples refuses (null pointers, colors without records, the counts, the radius, the
+ * box, thresholds not ascending or not finite, `reserved`, scratchBytes one byte short, the alignments — `records` at 16 bytes); a colourBy
+ * or an orientMode out of range; a `light` or an `orient` that is not finite; a zero `light` with SIMLOD_SURFACE_SHADE. */
+int simlod_surface_samples(const SimlodUniforms* uniforms /*host*/, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB,
+                           const SimlodSurfaceParams* params /*host*/, void* scratch, uint64_t scratchBytes,
+                           SimlodSurfaceRecord* records /*or NULL: count only*/, uint32_t* colors /*or NULL*/,
+                           SimlodSurfaceSummary* summary, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

@@ -225,6 +225,26 @@ compare_summary_dtype = np.dtype({"names": ["error", "numCells", "maxCellPopulat
                                   "offsets": [0, 4, 8, 12, 16, 20, 24, 32, 40, 48], "itemsize": 2104})
 assert compare_record_dtype.itemsize == 16 and compare_params_dtype.itemsize == 3088 and compare_summary_dtype.itemsize == 2104
 
+# ---- surface queries (include/simlod_hip.h, "surface queries") ---------------------------------------------------------------------------
+SURFACE_ERR_BUDGET = 0x1
+SURFACE_SHADE, SURFACE_VARIATION = 0, 1                                     # colourBy
+SURFACE_ORIENT_DIRECTION, SURFACE_ORIENT_POSITION = 0, 1                    # orientMode
+SURFACE_ORIENT_MODES = {"direction": SURFACE_ORIENT_DIRECTION, "position": SURFACE_ORIENT_POSITION}
+SURFACE_MIN_WITHIN = 3                                                      # rule N9: fewer neighbours span no plane
+SURFACE_Q_SCALE = 16384.0                                                   # rule N2: invq = 16384 / h
+SURFACE_SQUARINGS = 8                                                       # rule N5
+surface_record_dtype = np.dtype({"names": ["normal", "within", "lambdaNum", "lambdaDen"], "formats": [("<f4", 3), "<u4", "<f8", "<f8"],
+                                 "offsets": [0, 12, 16, 24], "itemsize": 32})
+surface_params_dtype = np.dtype({"names": ["radius", "missColor", "maxCandidates", "thresholds", "table", "light", "orient", "colourBy", "orientMode",
+                                           "maxWorkgroups", "reserved"],
+                                 "formats": ["<f4", "<u4", "<u8", ("<f8", 255), ("<u4", 256), ("<f4", 3), ("<f4", 3), "<u4", "<u4", "<u4", "<u4"],
+                                 "offsets": [0, 4, 8, 16, 2056, 3080, 3092, 3104, 3108, 3112, 3116], "itemsize": 3120})
+surface_summary_dtype = np.dtype({"names": ["error", "numCells", "maxCellPopulation", "numInvalidA", "numInvalidB", "numEstimated", "numWithin",
+                                            "numCandidates", "numDegenerate", "hist"],
+                                  "formats": ["<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<u8", "<u8", "<u8", ("<u8", 257)],
+                                  "offsets": [0, 4, 8, 12, 16, 20, 24, 32, 40, 48], "itemsize": 2104})
+assert surface_record_dtype.itemsize == 32 and surface_params_dtype.itemsize == 3120 and surface_summary_dtype.itemsize == 2104
+
 # ---- lasso queries (include/simlod_hip.h, "lasso queries") -------------------------------------------------------------------------------
 LASSO_MAX_VERTICES = 256
 lasso_dtype = np.dtype({"names": ["numVertices", "reserved", "rowU", "rowV", "rowW", "vertices"],

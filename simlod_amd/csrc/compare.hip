@@ -23,6 +23,8 @@
 //                lookups, a loop over each cell's records with rule C2's test and rule C3's order (d2, index).  The lane writes its own
 //                record (one 16-byte store) and colour, counts its bin in the workgroup's LDS histogram and keeps the sums in registers.
 //   k_c_final    the test pass's partial records added up -> numMatched, numWithin, maxD2, hist.  Returns at once unless `run`.
+// The surface queries (compare_surface.inc, included below) run the first six launches as they are — launch_grid — and follow them with their
+// own test pass and final.
 // No atomic touches global memory for the summary: every kernel writes ONE partial record per workgroup (CmpPart, its own fields of it) with
 // plain stores, as export_summary.inc does, and integer sums and maxima do not depend on the order of adding (rule C8).  d2 is never negative,
 // so the maximum of its 64 bits as an unsigned integer is the maximum of the doubles.
@@ -36,6 +38,7 @@
 #include "simlod_hip.h"
 #include "simlod_internal.hpp"
 #include "compare_rules.hpp"
+#include "surface_rules.hpp"
 
 namespace simlod {
 namespace {
@@ -416,6 +419,53 @@ uint32_t compare_grid(uint64_t work, uint32_t limit) {
 
 inline bool aligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1u)) == 0u; }
 
+// what the compare call and the surface call share: the fields of their params records the grid needs
+struct CmpCall {
+	float    radius;
+	uint32_t missColor;
+	uint64_t maxCandidates;
+	uint32_t maxWorkgroups;
+};
+
+// the checks of everything but the params record (already accepted), and the arguments of the grid's kernels; false: refused.  Enqueues nothing.
+bool compare_prepare(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB, const CmpCall& call, void* scratch,
+                     uint64_t scratchBytes, const void* records, uint32_t* colors, SimlodCompareSummary* summary, CmpArgs& c) {
+	if (u == nullptr || a == nullptr || b == nullptr || scratch == nullptr || summary == nullptr) return false;
+	if (records == nullptr && colors != nullptr) return false;
+	if (!compare_count_acceptable(numA) || !compare_count_acceptable(numB)) return false;
+	if (!aligned(a, 16) || !aligned(b, 16) || !aligned(scratch, 16) || !aligned(records, 16) || !aligned(colors, 4) || !aligned(summary, 8)) return false;
+	float size, mn[3];
+	octree_box(u, size, mn[0], mn[1], mn[2]);
+	if (!compare_box_acceptable(mn, size)) return false;
+	const CmpLayout lay(numB);
+	if (scratchBytes < lay.bytes) return false;
+	c.a = reinterpret_cast<const u32x4*>(a); c.b = reinterpret_cast<const u32x4*>(b); c.numA = numA; c.numB = numB;
+	c.scratch = reinterpret_cast<uint8_t*>(scratch);
+	c.slots = lay.slots; c.table = lay.table; c.slotOf = lay.slotOf; c.rank = lay.rank; c.cells = lay.cells; c.parts = lay.parts;
+	c.log2Slots = compare_log2(lay.slots);
+	c.gridA = compare_grid(numA, call.maxWorkgroups); c.gridB = compare_grid(numB, call.maxWorkgroups);
+	c.gridS = compare_grid((lay.slots + CMP_RANGE_PER_LANE - 1u) / CMP_RANGE_PER_LANE, call.maxWorkgroups);
+	c.countOnly = records == nullptr ? 1u : 0u; c.missColor = call.missColor;
+	for (int k = 0; k < 3; k++) c.min[k] = (double)mn[k];
+	c.inv = compare_inv(call.radius, size);
+	c.rr = (double)call.radius * (double)call.radius;
+	c.maxCandidates = call.maxCandidates;
+	c.records = nullptr; c.colors = colors; c.summary = summary;
+	return true;
+}
+
+// the grid over `b` and rule C6's decision: k_c_init .. k_c_decide
+void launch_grid(const CmpArgs& c, hipStream_t stream) {
+	SIMLOD_LAUNCH(k_c_init, dim3(c.gridS), dim3(CMP_TPB), stream, c);
+	SIMLOD_LAUNCH(k_c_insert, dim3(c.gridB), dim3(CMP_TPB), stream, c);
+	SIMLOD_LAUNCH(k_c_ranges, dim3(c.gridS), dim3(CMP_TPB), stream, c);
+	if (c.countOnly == 0u) SIMLOD_LAUNCH(k_c_fill, dim3(c.gridB), dim3(CMP_TPB), stream, c);
+	SIMLOD_LAUNCH(k_c_count, dim3(c.gridA), dim3(CMP_TPB), stream, c);
+	SIMLOD_LAUNCH(k_c_decide, dim3(1), dim3(CMP_TPB), stream, c);
+}
+
+#include "compare_surface.inc"
+
 }  // namespace
 
 uint64_t compare_slots(uint64_t numB) { return compare_count_acceptable(numB) ? compare_table_slots(numB) : 0u; }
@@ -427,41 +477,45 @@ uint64_t compare_min_bytes(uint64_t numA, uint64_t numB) {
 // simlod_compare_samples: the checks (nothing is enqueued before the last of them), then the launches listed at the top.
 int launch_compare(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB, const SimlodCompareParams* params,
                    void* scratch, uint64_t scratchBytes, SimlodCompareRecord* records, uint32_t* colors, SimlodCompareSummary* summary, hipStream_t stream) {
-	if (u == nullptr || a == nullptr || b == nullptr || params == nullptr || scratch == nullptr || summary == nullptr) return (int)hipErrorInvalidValue;
-	if (records == nullptr && colors != nullptr) return (int)hipErrorInvalidValue;
-	if (!compare_count_acceptable(numA) || !compare_count_acceptable(numB) || !compare_acceptable(*params)) return (int)hipErrorInvalidValue;
-	if (!aligned(a, 16) || !aligned(b, 16) || !aligned(scratch, 16) || !aligned(records, 16) || !aligned(colors, 4) || !aligned(summary, 8))
-		return (int)hipErrorInvalidValue;
-	float size, mn[3];
-	octree_box(u, size, mn[0], mn[1], mn[2]);
-	if (!compare_box_acceptable(mn, size)) return (int)hipErrorInvalidValue;
-	const CmpLayout lay(numB);
-	if (scratchBytes < lay.bytes) return (int)hipErrorInvalidValue;
+	if (params == nullptr || !compare_acceptable(*params)) return (int)hipErrorInvalidValue;
 	CmpTestArgs t{};
 	CmpArgs& c = t.c;
-	c.a = reinterpret_cast<const u32x4*>(a); c.b = reinterpret_cast<const u32x4*>(b); c.numA = numA; c.numB = numB;
-	c.scratch = reinterpret_cast<uint8_t*>(scratch);
-	c.slots = lay.slots; c.table = lay.table; c.slotOf = lay.slotOf; c.rank = lay.rank; c.cells = lay.cells; c.parts = lay.parts;
-	c.log2Slots = compare_log2(lay.slots);
-	c.gridA = compare_grid(numA, params->maxWorkgroups); c.gridB = compare_grid(numB, params->maxWorkgroups);
-	c.gridS = compare_grid((lay.slots + CMP_RANGE_PER_LANE - 1u) / CMP_RANGE_PER_LANE, params->maxWorkgroups);
-	c.countOnly = records == nullptr ? 1u : 0u; c.missColor = params->missColor;
-	for (int k = 0; k < 3; k++) c.min[k] = (double)mn[k];
-	c.inv = compare_inv(params->radius, size);
-	c.rr = (double)params->radius * (double)params->radius;
-	c.maxCandidates = params->maxCandidates;
-	c.records = records; c.colors = colors; c.summary = summary;
+	const CmpCall call{params->radius, params->missColor, params->maxCandidates, params->maxWorkgroups};
+	if (!compare_prepare(u, a, numA, b, numB, call, scratch, scratchBytes, records, colors, summary, c)) return (int)hipErrorInvalidValue;
+	c.records = records;
 	for (uint32_t i = 0; i < COMPARE_THRESHOLDS; i++) t.t2[i] = params->thresholds2[i];
 	for (uint32_t i = 0; i < 256u; i++) t.table[i] = params->table[i];
-	SIMLOD_LAUNCH(k_c_init, dim3(c.gridS), dim3(CMP_TPB), stream, c);
-	SIMLOD_LAUNCH(k_c_insert, dim3(c.gridB), dim3(CMP_TPB), stream, c);
-	SIMLOD_LAUNCH(k_c_ranges, dim3(c.gridS), dim3(CMP_TPB), stream, c);
-	if (records != nullptr) SIMLOD_LAUNCH(k_c_fill, dim3(c.gridB), dim3(CMP_TPB), stream, c);
-	SIMLOD_LAUNCH(k_c_count, dim3(c.gridA), dim3(CMP_TPB), stream, c);
-	SIMLOD_LAUNCH(k_c_decide, dim3(1), dim3(CMP_TPB), stream, c);
+	launch_grid(c, stream);
 	if (records != nullptr) {
 		SIMLOD_LAUNCH(k_c_test, dim3(c.gridA), dim3(CMP_TPB), stream, t);
 		SIMLOD_LAUNCH(k_c_final, dim3(CMP_FINAL_HIST_WGS + 1u), dim3(CMP_TPB), stream, c);
+	}
+	if (profile_enabled()) profile_close(stream);
+	return (int)hipGetLastError();
+}
+
+// simlod_surface_samples: the same checks and the same six launches, then compare_surface.inc's two.
+int launch_surface(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB, const SimlodSurfaceParams* params,
+                   void* scratch, uint64_t scratchBytes, SimlodSurfaceRecord* records, uint32_t* colors, SimlodSurfaceSummary* summary, hipStream_t stream) {
+	if (params == nullptr || !surface_acceptable(*params)) return (int)hipErrorInvalidValue;
+	SurfTestArgs t{};
+	CmpArgs& c = t.c;
+	const CmpCall call{params->radius, params->missColor, params->maxCandidates, params->maxWorkgroups};
+	// (the summary has SimlodCompareSummary's layout: k_c_decide writes it as it is, numDegenerate = 0 being maxD2 = 0.0's bits)
+	if (!compare_prepare(u, a, numA, b, numB, call, scratch, scratchBytes, records, colors, reinterpret_cast<SimlodCompareSummary*>(summary), c))
+		return (int)hipErrorInvalidValue;
+	float size, mn[3];
+	octree_box(u, size, mn[0], mn[1], mn[2]);
+	t.records = records;
+	t.invq = surface_invq(params->radius, size);
+	t.colourBy = params->colourBy; t.orientMode = params->orientMode;
+	for (int k = 0; k < 3; k++) { t.light[k] = (double)params->light[k]; t.orient[k] = (double)params->orient[k]; }
+	for (uint32_t i = 0; i < SURFACE_THRESHOLDS; i++) t.thresholds[i] = params->thresholds[i];
+	for (uint32_t i = 0; i < 256u; i++) t.table[i] = params->table[i];
+	launch_grid(c, stream);
+	if (records != nullptr) {
+		SIMLOD_LAUNCH(k_s_test, dim3(c.gridA), dim3(CMP_TPB), stream, t);
+		SIMLOD_LAUNCH(k_s_final, dim3(CMP_FINAL_HIST_WGS + 1u), dim3(CMP_TPB), stream, c);
 	}
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();

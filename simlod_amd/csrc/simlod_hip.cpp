@@ -633,6 +633,14 @@ int simlod_compare_samples(const SimlodUniforms* uniforms, const SimlodPoint* a,
 	return launch_compare(uniforms, a, numA, b, numB, params, scratch, scratchBytes, records, colors, summary, (hipStream_t)stream);
 }
 
+uint64_t simlod_surface_buffer_min_bytes(uint64_t numA, uint64_t numB) { return compare_min_bytes(numA, numB); }
+
+int simlod_surface_samples(const SimlodUniforms* uniforms, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB,
+                           const SimlodSurfaceParams* params, void* scratch, uint64_t scratchBytes, SimlodSurfaceRecord* records, uint32_t* colors,
+                           SimlodSurfaceSummary* summary, void* stream) {
+	return launch_surface(uniforms, a, numA, b, numB, params, scratch, scratchBytes, records, colors, summary, (hipStream_t)stream);
+}
+
 uint64_t simlod_rays_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates) {
 	return rays_min_bytes(nodeCapacity, sampleBound, numRays, numPairs, numCandidates);
 }

@@ -230,6 +230,8 @@ int launch_compare(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA,
                    void* scratch, uint64_t scratchBytes, SimlodCompareRecord* records, uint32_t* colors, SimlodCompareSummary* summary, hipStream_t stream);
 uint64_t compare_min_bytes(uint64_t numA, uint64_t numB);
 uint64_t compare_slots(uint64_t numB);
+int launch_surface(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB, const SimlodSurfaceParams* params,
+                   void* scratch, uint64_t scratchBytes, SimlodSurfaceRecord* records, uint32_t* colors, SimlodSurfaceSummary* summary, hipStream_t stream);
 int launch_rays(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRay* rays, uint32_t numRays,
                 uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
                 SimlodRayHit* hits, SimlodRayCounts* counts, hipStream_t stream);

@@ -40,6 +40,10 @@ Compare queries (include/simlod_hip.h, "compare queries"): `Compare` holds the r
 C1-C5 in numpy float64 and integers —, `OctreeExport.compare` applies it to two exports and `CompareResult` is what
 DeviceOctree.compare_region returns.
 
+Surface queries (include/simlod_hip.h, "surface queries"): `Surface` holds the radius, the thresholds, the colour table, the light and the
+orientation, `surface_samples` is the host mirror of simlod_surface_samples — rules N1-N10 on compare_samples' pairs, the sums in int64, the
+rest in numpy float64 —, `OctreeExport.surface` applies it to an export and `SurfaceResult` is what DeviceOctree.surface_region returns.
+
 Profile queries (include/simlod_hip.h, "profile queries"): `Profile` holds the polyline, the half-width and the three affine maps,
 `OctreeExport.profile` is the host mirror of simlod_query_profile — samples and records — and `classify_profile` of its rule P3.
 
@@ -346,6 +350,13 @@ class OctreeExport:
         """The host mirror of simlod_compare_samples on this export's samples (A) and `other`'s (B; may be this export), in this export's box:
         compare_samples' (records, colours, summary)."""
         return compare_samples(self.samples, other.samples, (self.box_min, self.box_max), compare, count_only=count_only)
+
+    # -- surface queries (include/simlod_hip.h, "surface queries") -------------------------------------------------------------------------
+    def surface(self, surface, other=None, count_only=False):
+        """The host mirror of simlod_surface_samples on this export's samples (A) and `other`'s (B; None: this export), in this export's box:
+        surface_samples' (records, colours, summary)."""
+        other = self if other is None else other
+        return surface_samples(self.samples, other.samples, (self.box_min, self.box_max), surface, count_only=count_only)
 
     # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
     def profile(self, profile, region=None, max_level=None, select="all", return_counts=False, test_every_sample=False):
@@ -1475,23 +1486,22 @@ def compare_cells(points, box_min, inv):
     return valid, keys
 
 
-def compare_samples(a, b, uniforms_box, compare, count_only=False):
-    """The host mirror of simlod_compare_samples (include/simlod_hip.h, "compare queries"): a, b arrays of abi.point_dtype, uniforms_box the
-    (box_min, box_max) of the uniforms, compare a Compare -> (records as abi.compare_record_dtype, colours as uint32, the summary as one
-    abi.compare_summary_dtype record); count_only, or a budget exceeded (rule C6): records and colours are None.  The cells by the same cell20
-    the summary's mirror uses, grouped by np.unique over the keys; rules C2, C3 and C5 in numpy float64 and unsigned integers, in the order
-    the header gives.  Only the cells rule C4 names are searched, as on the device."""
+def _compare_pairs(a, b, uniforms_box, radius, max_candidates, count_only, summary_dtype):
+    """What compare_samples and surface_samples share (rules C1, C2, C4, C6, C7): the grid over b's valid samples, the grid's fields of a
+    summary record of `summary_dtype` (both summaries keep them, and the budget's error bit, in the same places), and every pair (i, j) of a
+    sample of a and a sample of b from its up to 27 cells that passes rule C2 -> (a, b, the record, (pi, pj, [px, py, pz], d2)); the pairs are
+    None for a count-only call and when the budget is exceeded."""
     a, b = np.asarray(a, dtype=abi.point_dtype).reshape(-1), np.asarray(b, dtype=abi.point_dtype).reshape(-1)
     if not (0 < len(a) <= abi.COMPARE_MAX_COUNT and 0 < len(b) <= abi.COMPARE_MAX_COUNT):
         raise ValueError("numA and numB are 1 .. 2^32 - 2")
     mn, size = _box_of(*uniforms_box)
     if not (np.isfinite(mn).all() and np.isfinite(size) and size > 0):
         raise ValueError("the box needs a finite corner and a finite extent > 0")
-    inv = np.float64(1.0) / compare_h(compare.radius, size)
-    rr = np.float64(compare.radius) * np.float64(compare.radius)
+    inv = np.float64(1.0) / compare_h(radius, size)
+    rr = np.float64(radius) * np.float64(radius)
     va, ka = compare_cells(a, mn, inv)
     vb, kb = compare_cells(b, mn, inv)
-    out = np.zeros((), dtype=abi.compare_summary_dtype)
+    out = np.zeros((), dtype=summary_dtype)
     out["numInvalidA"], out["numInvalidB"] = int((~va).sum()), int((~vb).sum())
     ib = np.flatnonzero(vb)
     ib = ib[np.argsort(kb[ib], kind="stable")]                             # the grid: b's valid samples by cell, ascending index within a cell
@@ -1515,18 +1525,30 @@ def compare_samples(a, b, uniforms_box, compare, count_only=False):
                 who.append(ia[ok][hit]); start.append(first[at[hit]]); count.append(pop[at[hit]])
     who, start, count = (np.concatenate(v).astype(np.int64) for v in (who, start, count))
     out["numCandidates"] = int(count.sum())
-    budget = compare.max_candidates or 0
+    budget = max_candidates or 0
     if budget != 0 and int(out["numCandidates"]) > budget:
         out["error"] = abi.COMPARE_ERR_BUDGET
     if count_only or int(out["error"]) != 0:
-        return None, None, out
+        return a, b, out, None
     # every candidate pair (i, j), then rule C2
     pi = np.repeat(who, count)
     pj = ib[np.repeat(start, count) + (np.arange(len(pi)) - np.repeat(np.cumsum(count) - count, count))]
     d = [b[name][pj].astype(np.float64) - a[name][pi].astype(np.float64) for name in ("x", "y", "z")]
     d2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
     ok = d2 <= rr
-    pi, pj, d2 = pi[ok], pj[ok], d2[ok]
+    return a, b, out, (pi[ok], pj[ok], [v[ok] for v in d], d2[ok])
+
+
+def compare_samples(a, b, uniforms_box, compare, count_only=False):
+    """The host mirror of simlod_compare_samples (include/simlod_hip.h, "compare queries"): a, b arrays of abi.point_dtype, uniforms_box the
+    (box_min, box_max) of the uniforms, compare a Compare -> (records as abi.compare_record_dtype, colours as uint32, the summary as one
+    abi.compare_summary_dtype record); count_only, or a budget exceeded (rule C6): records and colours are None.  The cells by the same cell20
+    the summary's mirror uses, grouped by np.unique over the keys; rules C2, C3 and C5 in numpy float64 and unsigned integers, in the order
+    the header gives.  Only the cells rule C4 names are searched, as on the device."""
+    a, b, out, pairs = _compare_pairs(a, b, uniforms_box, compare.radius, compare.max_candidates, count_only, abi.compare_summary_dtype)
+    if pairs is None:
+        return None, None, out
+    pi, pj, _, d2 = pairs
     rec = np.zeros(len(a), dtype=abi.compare_record_dtype)
     rec["d2"], rec["nearest"] = np.inf, abi.COMPARE_MISS
     rec["within"] = np.bincount(pi, minlength=len(a))
@@ -1575,6 +1597,234 @@ class CompareResult:
             raise ValueError("only a compare_region(max_level=20, select='all') result is in the order paint_region takes")
         return dev.paint_region(uniforms, s["region"], Paint.array(), footprint=s["footprint"], colors=self.colors, return_previous=return_previous,
                                 lasso=s["lasso"], invert=s["invert"])
+
+
+class Surface:
+    """The parameters of a surface query (include/simlod_hip.h, "surface queries"; abi.surface_params_dtype): the radius (float32), the 255
+    ascending thresholds and the 256 colour words of rule N8, what the colour is taken from (colour_by: abi.SURFACE_SHADE with the light
+    direction, or abi.SURFACE_VARIATION), rule N6's orientation (orient with orient_mode "direction" or "position"), the miss colour of rule
+    N9, and the candidate budget of rule C6 (max_candidates; None, 0 and a number as in Compare).  The refusals are the C call's."""
+
+    def __init__(self, radius, thresholds, table, colour_by=abi.SURFACE_SHADE, light=(0.0, 0.0, 1.0), orient=(0.0, 0.0, 1.0), orient_mode="direction",
+                 miss_color=0, max_candidates=None, max_workgroups=0):
+        with np.errstate(over="ignore"):
+            self.radius = np.float32(radius)
+            self.light = np.asarray(light, dtype=np.float32).reshape(-1).copy()
+            self.orient = np.asarray(orient, dtype=np.float32).reshape(-1).copy()
+        self.thresholds = np.asarray(thresholds, dtype=np.float64).reshape(-1).copy()
+        self.table = np.asarray(table, dtype=np.uint32).reshape(-1).copy()
+        self.miss_color, self.max_workgroups, self.colour_by = int(miss_color), int(max_workgroups), int(colour_by)
+        self.orient_mode = abi.SURFACE_ORIENT_MODES.get(orient_mode, -1) if isinstance(orient_mode, str) else int(orient_mode)
+        self.max_candidates = None if max_candidates is None else int(max_candidates)
+        if not (np.isfinite(self.radius) and self.radius >= 0):
+            raise ValueError("a surface query needs a finite radius >= 0 (as float32)")
+        if len(self.thresholds) != 255 or len(self.table) != 256:
+            raise ValueError(f"{len(self.thresholds)} thresholds and {len(self.table)} table entries: 255 and 256")
+        if not np.isfinite(self.thresholds).all() or (np.diff(self.thresholds) < 0).any():
+            raise ValueError("the thresholds are finite and ascending")
+        if self.colour_by not in (abi.SURFACE_SHADE, abi.SURFACE_VARIATION) or self.orient_mode not in (abi.SURFACE_ORIENT_DIRECTION, abi.SURFACE_ORIENT_POSITION):
+            raise ValueError("colour_by is SURFACE_SHADE or SURFACE_VARIATION, orient_mode 'direction' or 'position'")
+        if len(self.light) != 3 or len(self.orient) != 3 or not (np.isfinite(self.light).all() and np.isfinite(self.orient).all()):
+            raise ValueError("light and orient are three finite float32 values")
+        if self.colour_by == abi.SURFACE_SHADE and not self.light.any():
+            raise ValueError("a hillshade needs a light direction that is not zero")
+        if not 0 <= self.miss_color <= 0xFFFFFFFF or (self.max_candidates is not None and self.max_candidates < 0):
+            raise ValueError("a colour word is a 32-bit unsigned integer, a budget is not negative")
+
+    @classmethod
+    def hillshade(cls, radius, light, colours, orient=(0.0, 0.0, 1.0), orient_mode="direction", **kw):
+        """Bins of equal width in the COSINE between the normal and the light: thresholds[i] = c * |c| with c = -1 + (i + 1) / 128, the signed
+        squared cosine rule N8 compares.  colours: the palette, facing away first, any number of words, spread evenly over the 256 bins."""
+        c = np.float64(-1.0) + np.arange(1, 256).astype(np.float64) / np.float64(128.0)
+        return cls(radius, c * np.abs(c), Compare._spread(colours), abi.SURFACE_SHADE, light, orient, orient_mode, **kw)
+
+    @classmethod
+    def variation(cls, radius, vmax, colours, **kw):
+        """Bins of equal width in the surface variation up to vmax (at most 1/3 is typical): thresholds[i] = (i + 1) * vmax / 255, so a
+        neighbourhood at vmax or rougher gets table[255].  colours: the palette, flattest first."""
+        vmax = np.float64(vmax)
+        if not (np.isfinite(vmax) and vmax > 0):
+            raise ValueError("a variation ramp needs a finite vmax > 0")
+        return cls(radius, (np.arange(1, 256).astype(np.float64) * vmax) / np.float64(255.0), Compare._spread(colours), abi.SURFACE_VARIATION, **kw)
+
+    @classmethod
+    def from_record(cls, record):
+        r = np.asarray(record, dtype=abi.surface_params_dtype).reshape(-1)[0]
+        if int(r["reserved"]) != 0:
+            raise ValueError("the reserved word is 0")
+        return cls(r["radius"], r["thresholds"], r["table"], int(r["colourBy"]), r["light"], r["orient"], int(r["orientMode"]), int(r["missColor"]),
+                   int(r["maxCandidates"]), int(r["maxWorkgroups"]))
+
+    def __eq__(self, other):
+        return isinstance(other, Surface) and self.record().tobytes() == other.record().tobytes()
+
+    def record(self, max_candidates=None):
+        """The SimlodSurfaceParams the C ABI takes (abi.surface_params_dtype, one record); max_candidates overrides the object's."""
+        r = np.zeros(1, dtype=abi.surface_params_dtype)
+        budget = self.max_candidates if max_candidates is None else int(max_candidates)
+        r["radius"], r["missColor"], r["maxCandidates"], r["maxWorkgroups"] = self.radius, self.miss_color, budget or 0, self.max_workgroups
+        r["colourBy"], r["orientMode"] = self.colour_by, self.orient_mode
+        r["thresholds"][0], r["table"][0], r["light"][0], r["orient"][0] = self.thresholds, self.table, self.light, self.orient
+        return r
+
+    def index(self, num, den):
+        """Rule N8's table index: the number of thresholds with thresholds[i] * den <= num, by the device's binary search (eight steps)."""
+        num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+        lo, hi = np.zeros(num.shape, np.int64), np.full(num.shape, 255, np.int64)
+        for _ in range(8):                                                 # 255 -> 0 in eight halvings
+            mid = (lo + hi) >> 1
+            go = (lo < hi) & (self.thresholds[np.minimum(mid, 254)] * den <= num)
+            stay = (lo < hi) & ~go
+            lo, hi = np.where(go, mid + 1, lo), np.where(stay, mid, hi)
+        return lo
+
+
+def _surface_widen(s):
+    """Rule N3's D of an int64 array: the high word times 2^32 (exact) plus the low word, one rounded add."""
+    return (s >> np.int64(32)).astype(np.float64) * np.float64(4294967296.0) + (s & np.int64(0xFFFFFFFF)).astype(np.float64)
+
+
+def _surface_scale(m):
+    """Rule N4's P of six arrays (xx, xy, xz, yy, yz, zz) -> (the scaled arrays, m != 0)."""
+    big = np.abs(m[0])
+    for v in m[1:]:
+        big = np.maximum(big, np.abs(v))
+    e = (big.view(np.uint64) >> np.uint64(52)) & np.uint64(0x7FF)
+    f = ((np.uint64(2046) - e) << np.uint64(52)).view(np.float64)
+    return [v * f for v in m], big != 0.0
+
+
+def _surface_estimates(a, pairs, uniforms_box, surface):
+    """Rules N2-N7 for every sample of a at once, in float64 before anything is rounded into a record -> (within, valid, ok, v, lambdaNum,
+    lambdaDen, vv): ok marks the samples with an estimate, the others' numbers mean nothing."""
+    pi, _, d, _ = pairs
+    mn, size = _box_of(*uniforms_box)
+    invq = np.float64(abi.SURFACE_Q_SCALE) / compare_h(surface.radius, size)
+    n = len(a)
+    valid = np.isfinite(a["x"]) & np.isfinite(a["y"]) & np.isfinite(a["z"])
+    within = np.bincount(pi, minlength=n).astype(np.int64)
+    q = [(v * invq).astype(np.int64) for v in d]                           # rule N2: truncation towards zero
+    order = np.argsort(pi, kind="stable")
+    first = np.flatnonzero(np.r_[True, pi[order][1:] != pi[order][:-1]]) if len(order) else order
+    have = pi[order][first]
+
+    def total(v):                                                           # rule N3: exact integer sums per sample of a
+        s = np.zeros(n, np.int64)
+        if len(first):
+            s[have] = np.add.reduceat(v[order], first)
+        return s
+    with np.errstate(all="ignore"):
+        sx, sy, sz = (_surface_widen(total(v)) for v in q)
+        cnt = within.astype(np.float64)
+        M = [cnt * _surface_widen(total(q[0] * q[0])) - sx * sx, cnt * _surface_widen(total(q[0] * q[1])) - sx * sy,
+             cnt * _surface_widen(total(q[0] * q[2])) - sx * sz, cnt * _surface_widen(total(q[1] * q[1])) - sy * sy,
+             cnt * _surface_widen(total(q[1] * q[2])) - sy * sz, cnt * _surface_widen(total(q[2] * q[2])) - sz * sz]
+        M, ok = _surface_scale(M)                                           # rule N5
+        ok &= valid & (within >= abi.SURFACE_MIN_WITHIN)
+        t = (M[0] + M[3]) + M[5]
+        B = [t - M[0], -M[1], -M[2], t - M[3], -M[4], t - M[5]]
+        for _ in range(abi.SURFACE_SQUARINGS):
+            xx, xy, xz, yy, yz, zz = B
+            B, nz = _surface_scale([(xx * xx + xy * xy) + xz * xz, (xx * xy + xy * yy) + xz * yz, (xx * xz + xy * yz) + xz * zz,
+                                    (xy * xy + yy * yy) + yz * yz, (xy * xz + yy * yz) + yz * zz, (xz * xz + yz * yz) + zz * zz])
+            ok &= nz
+        xx, xy, xz, yy, yz, zz = B
+        j1 = yy > xx                                                        # the first index of the largest diagonal entry
+        j2 = zz > np.where(j1, yy, xx)
+        v = [np.where(j2, xz, np.where(j1, xy, xx)), np.where(j2, yz, np.where(j1, yy, xy)), np.where(j2, zz, np.where(j1, yz, xz))]
+        o = [np.float64(surface.orient[k]) for k in range(3)]               # rule N6
+        if surface.orient_mode == abi.SURFACE_ORIENT_POSITION:
+            o = [o[k] - a[name].astype(np.float64) for k, name in enumerate(("x", "y", "z"))]
+        flip = (v[0] * o[0] + v[1] * o[1]) + v[2] * o[2] < 0.0
+        v = [np.where(flip, -c, c) for c in v]
+        w = [(M[0] * v[0] + M[1] * v[1]) + M[2] * v[2], (M[1] * v[0] + M[3] * v[1]) + M[4] * v[2], (M[2] * v[0] + M[4] * v[1]) + M[5] * v[2]]   # rule N7
+        lnum = (v[0] * w[0] + v[1] * w[1]) + v[2] * w[2]
+        vv = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]
+        lden = vv * t
+    return within, valid, ok, v, lnum, lden, vv
+
+
+def surface_normals64(a, b, uniforms_box, surface):
+    """The mirror's oriented normals BEFORE the record rounds them to float32: (n, 3) float64, zero rows where there is no estimate.  What
+    an accuracy check against another eigen-solver compares; the records themselves carry float32."""
+    a, b, _, pairs = _compare_pairs(a, b, uniforms_box, surface.radius, 0, False, abi.surface_summary_dtype)
+    _, _, ok, v, _, _, _ = _surface_estimates(a, pairs, uniforms_box, surface)
+    return np.stack([np.where(ok, c, 0.0) for c in v], -1)
+
+
+def surface_samples(a, b, uniforms_box, surface, count_only=False):
+    """The host mirror of simlod_surface_samples (include/simlod_hip.h, "surface queries"): a, b arrays of abi.point_dtype, uniforms_box the
+    (box_min, box_max) of the uniforms, surface a Surface -> (records as abi.surface_record_dtype, colours as uint32, the summary as one
+    abi.surface_summary_dtype record); count_only, or a budget exceeded: records and colours are None.  The neighbourhood is compare_samples'
+    (the same cells, the same pairs); rules N2 and N3 in int64, rules N4-N8 in numpy float64 over all samples at once, each sum in the order
+    the header gives."""
+    a, b, out, pairs = _compare_pairs(a, b, uniforms_box, surface.radius, surface.max_candidates, count_only, abi.surface_summary_dtype)
+    if pairs is None:
+        return None, None, out
+    within, valid, ok, v, lnum, lden, vv = _surface_estimates(a, pairs, uniforms_box, surface)
+    n = len(a)
+    with np.errstate(all="ignore"):
+        if surface.colour_by == abi.SURFACE_SHADE:                          # rule N8
+            L = [np.float64(surface.light[k]) for k in range(3)]
+            al = (v[0] * L[0] + v[1] * L[1]) + v[2] * L[2]
+            num, den = al * np.abs(al), vv * ((L[0] * L[0] + L[1] * L[1]) + L[2] * L[2])
+        else:
+            num, den = lnum, lden
+        idx = np.where(ok, surface.index(np.where(ok, num, 0.0), np.where(ok, den, 0.0)), 256)
+        rec = np.zeros(n, dtype=abi.surface_record_dtype)
+        for k in range(3):
+            rec["normal"][:, k] = np.where(ok, v[k], 0.0).astype(np.float32)
+    rec["within"], rec["lambdaNum"], rec["lambdaDen"] = within, np.where(ok, lnum, 0.0), np.where(ok, lden, 0.0)
+    colours = np.where(ok, surface.table[np.minimum(idx, 255)], np.uint32(surface.miss_color)).astype(np.uint32)
+    out["numEstimated"], out["numDegenerate"] = int(ok.sum()), int((valid & ~ok).sum())
+    out["numWithin"] = int(within.sum())
+    out["hist"] = np.bincount(idx, minlength=257).astype(np.uint64)
+    return rec, colours, out
+
+
+class SurfaceResult:
+    """What DeviceOctree.surface_region returns: `a`, the selection as an OctreeExport (query_region's); `b`, the export it was estimated
+    from (a itself unless another octree was given); `records` (abi.surface_record_dtype, one per sample of a, as bytes) and `colors` (uint32
+    words) as tensors on the device, in a's order; `summary`, one abi.surface_summary_dtype record on the host; the Surface; and the
+    selection's arguments."""
+
+    def __init__(self, a, b, records, colors, summary, surface, selection):
+        self.a, self.b, self.records, self.colors, self.summary, self.surface, self.selection = a, b, records, colors, summary, surface, selection
+
+    def records_host(self):
+        """The records as a numpy array of abi.surface_record_dtype."""
+        return self.records.cpu().numpy().view(abi.surface_record_dtype)
+
+    def unit_normals(self):
+        """The normals at length 1 as float64 (n, 3), on the host — the square root and the division the device does not take; a degenerate
+        or invalid sample's zero row stays zero."""
+        return surface_unit_normals(self.records_host())
+
+    def variation(self):
+        """The surface variation lambdaNum / lambdaDen per sample as float64, 0 where the sample is degenerate or invalid."""
+        return surface_variation(self.records_host())
+
+    def paint(self, dev, uniforms, return_previous=False):
+        """Write the colours into the octree `dev` the selection was taken from — an ARRAY paint of the same selection, as CompareResult.paint.
+        Only a result of max_level=20, select="all" has the order that paint takes."""
+        s = self.selection
+        if s["max_level"] != abi.MAX_DEPTH or s["select"] != "all":
+            raise ValueError("only a surface_region(max_level=20, select='all') result is in the order paint_region takes")
+        return dev.paint_region(uniforms, s["region"], Paint.array(), footprint=s["footprint"], colors=self.colors, return_previous=return_previous,
+                                lasso=s["lasso"], invert=s["invert"])
+
+
+def surface_unit_normals(records):
+    """SurfaceResult.unit_normals for an array of abi.surface_record_dtype."""
+    v = np.asarray(records, dtype=abi.surface_record_dtype)["normal"].astype(np.float64).reshape(-1, 3)
+    length = np.sqrt((v * v).sum(axis=1))
+    return np.divide(v, length[:, None], out=np.zeros_like(v), where=length[:, None] > 0)
+
+
+def surface_variation(records):
+    """SurfaceResult.variation for an array of abi.surface_record_dtype."""
+    r = np.asarray(records, dtype=abi.surface_record_dtype).reshape(-1)
+    return np.divide(r["lambdaNum"], r["lambdaDen"], out=np.zeros(len(r), np.float64), where=r["lambdaDen"] != 0)
 
 
 class Footprint:

@@ -138,6 +138,9 @@ def lib():
         L.simlod_compare_table_slots.restype = u64
         L.simlod_compare_table_slots.argtypes = [u64]
         L.simlod_compare_samples.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp]
+        L.simlod_surface_buffer_min_bytes.restype = u64
+        L.simlod_surface_buffer_min_bytes.argtypes = [u64, u64]
+        L.simlod_surface_samples.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -165,6 +168,7 @@ EXPORTED_SYMBOLS = [
     "simlod_lasso_buffer_min_bytes", "simlod_query_lasso", "simlod_paint_lasso", "simlod_query_summary_lasso",
     "simlod_inverse_buffer_min_bytes", "simlod_query_inverse", "simlod_paint_inverse", "simlod_query_summary_inverse",
     "simlod_compare_buffer_min_bytes", "simlod_compare_table_slots", "simlod_compare_samples",
+    "simlod_surface_buffer_min_bytes", "simlod_surface_samples",
 ]
 
 
@@ -956,6 +960,77 @@ class DeviceOctree:
         if int(s["error"]) != 0:
             raise SimlodError(f"simlod_compare_samples reported error bits {int(s['error']):#x}; no record was written")
         return CompareResult(a, b, records, colors, s, compare, sel)
+
+    # -- surface queries (include/simlod_hip.h, "surface queries") -------------------------------------------------------------------------
+    def surface_samples(self, uniforms, a, b, surface, count_only=False, max_candidates=None):
+        """One simlod_surface_samples call on two sample arrays (as compare_samples takes them; b may be a): per sample of `a` the plane
+        through the samples of `b` within surface.radius.  -> (records: a uint8 tensor of abi.surface_record_dtype records, colors: an int32
+        tensor of colour words, both on this device and in a's order, and the abi.surface_summary_dtype record on the host); count_only:
+        (None, None, record).  The call ALWAYS carries a candidate budget, compare_samples' (rule C6): max_candidates if given, else
+        surface.max_candidates, else 64 candidates per sample of `a`; an explicit 0 is the opt-out.  A budget exceeded comes back as
+        (None, None, record) with SIMLOD_SURFACE_ERR_BUDGET in the record's error field."""
+        u, up = self._u(uniforms)
+        ta, tb = self._samples_tensor(a), self._samples_tensor(b)
+        na, nb = ta.numel() // abi.point_dtype.itemsize, tb.numel() // abi.point_dtype.itemsize
+        budget = max_candidates if max_candidates is not None else surface.max_candidates
+        pr = surface.record(self.COMPARE_BUDGET_PER_SAMPLE * na if budget is None else int(budget))
+        need = int(self.L.simlod_surface_buffer_min_bytes(na, nb))
+        if need == 0:
+            raise ValueError("numA and numB are 1 .. 2^32 - 2")
+        scratch = self._export_scratch(need)
+        out = torch.zeros(abi.surface_summary_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        records = colors = None
+        if not count_only:
+            records = torch.empty(na * abi.surface_record_dtype.itemsize, dtype=torch.uint8, device=self.device)
+            colors = torch.empty(na, dtype=torch.int32, device=self.device)
+        opt = lambda t: None if t is None else self._p(t)
+        _check(self.L.simlod_surface_samples(up, self._p(ta), ctypes.c_uint64(na), self._p(tb), ctypes.c_uint64(nb), ctypes.c_void_p(pr.ctypes.data),
+                                             self._p(scratch), ctypes.c_uint64(scratch.numel()), opt(records), opt(colors), self._p(out), self._stream()),
+               "simlod_surface_samples")
+        rec = out.cpu().numpy().view(abi.surface_summary_dtype)[0]
+        return (None, None, rec) if int(rec["error"]) != 0 else (records, colors, rec)
+
+    def _surface_inputs(self, uniforms, other, region, max_level, select, footprint, lasso, invert, other_max_level, other_select):
+        """compare_region's selection; other None: the selection against itself."""
+        if other is not None:
+            return self._compare_inputs(uniforms, other, region, max_level, select, footprint, lasso, invert, other_max_level, other_select)
+        from .octree_io import Region
+        region = Region() if region is None else region
+        a = self.query_region(uniforms, region, max_level, select, footprint=footprint, lasso=lasso, invert=invert)
+        if a.num_samples == 0:
+            raise SimlodError("nothing to estimate: the selection holds no sample")
+        sel = {"region": region, "max_level": abi.MAX_DEPTH if max_level is None else int(max_level), "select": select, "footprint": footprint,
+               "lasso": lasso, "invert": invert}
+        return a, a, sel
+
+    def count_surface(self, uniforms, region, surface, other=None, max_level=None, select="cut", footprint=None, lasso=None, invert=False,
+                      other_max_level=None, other_select="cut"):
+        """What surface_region would cost: the abi.surface_summary_dtype record of the count-only call (numCells, maxCellPopulation,
+        numCandidates, the invalid counts) for the same arguments; nothing is estimated and no budget applies."""
+        a, b, _ = self._surface_inputs(uniforms, other, region, max_level, select, footprint, lasso, invert, other_max_level, other_select)
+        return self.surface_samples(uniforms, a, b, surface, count_only=True, max_candidates=0)[2]
+
+    def surface_region(self, uniforms, region, surface, other=None, max_level=None, select="cut", footprint=None, lasso=None, invert=False,
+                       other_max_level=None, other_select="cut"):
+        """Normal, variation and colour of each sample of a selection of THIS octree from its neighbours within surface.radius:
+        A = query_region(region, max_level, select, footprint / lasso / invert); the neighbours come from A itself (other None) or from
+        other.export_octree(other_max_level, other_select), a DeviceOctree on this device.  A count-only simlod_surface_samples call, the
+        budget check, then the call with results -> an octree_io.SurfaceResult.  The budget is surface.max_candidates (None: 64 candidates
+        per sample of A; 0: none); a count above it raises SimlodError naming numCandidates and maxCellPopulation — pick a smaller radius.
+        With max_level=20, select="all" the colours are in the order paint_region's ARRAY paint takes: SurfaceResult.paint(dev, uniforms)
+        writes them into the octree."""
+        from .octree_io import SurfaceResult
+        a, b, sel = self._surface_inputs(uniforms, other, region, max_level, select, footprint, lasso, invert, other_max_level, other_select)
+        budget = self.COMPARE_BUDGET_PER_SAMPLE * a.num_samples if surface.max_candidates is None else surface.max_candidates
+        c = self.surface_samples(uniforms, a, b, surface, count_only=True, max_candidates=0)[2]
+        if budget != 0 and int(c["numCandidates"]) > budget:
+            raise SimlodError(f"the surface of {a.num_samples} samples from {b.num_samples} at radius {float(surface.radius)} would test numCandidates = "
+                              f"{int(c['numCandidates'])} pairs, above the budget of {budget} (maxCellPopulation = {int(c['maxCellPopulation'])} in "
+                              f"{int(c['numCells'])} cells): pick a smaller radius or a coarser cut")
+        records, colors, s = self.surface_samples(uniforms, a, b, surface, max_candidates=budget)
+        if int(s["error"]) != 0:
+            raise SimlodError(f"simlod_surface_samples reported error bits {int(s['error']):#x}; no record was written")
+        return SurfaceResult(a, b, records, colors, s, surface, sel)
 
     # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
     def _profile(self, uniforms, profile, region, ml, sel, table, samples, records, sample_capacity, bound):

@@ -48,7 +48,8 @@ full CUT@20 export, radius 2.167 as --neighbours' in DESIGN §11: the call with 
 kernel's time from one call between the library's own events, candidates per sample and the largest cell, the rate on the ideal bytes against
 the device-to-device copy — and, for scale, the same positions through simlod_query_neighbours at k = 1, in batches of 65 536.  --compare-radius R:
 another radius, for cells of hundreds or thousands of samples, without that yardstick.
---compare-whole: the same with A = B = the full export.  --compare-workgroups N: SimlodCompareParams.maxWorkgroups for either."""
+--compare-whole: the same with A = B = the full export.  --compare-workgroups N: SimlodCompareParams.maxWorkgroups for either.  --surface: with
+either, simlod_surface_samples on the same arrays at the same radius as well, alternating with the compare call, and its kernels."""
 import argparse
 import ctypes
 import json
@@ -722,7 +723,7 @@ def neighbours_bench(dev, u, box, st, reps, pts):
     print(json.dumps(out))
 
 
-def compare_bench(dev, u, box, st, reps, pts, whole=False, workgroups=0, radius_arg=None):
+def compare_bench(dev, u, box, st, reps, pts, whole=False, workgroups=0, radius_arg=None, surface=False):
     """simlod_compare_samples: A = the CUT@20 selection of a box of 1/36 of the plan area (about 1 M samples), B = the octree's full CUT@20
     export, at --neighbours' radius of DESIGN §11 (2.167)."""
     from simlod_amd import fingerprint
@@ -790,7 +791,34 @@ def compare_bench(dev, u, box, st, reps, pts, whole=False, workgroups=0, radius_
         t_test = out["kernels_ms"]["k_c_test"]
         out["test_pass"] = {"candidate_bytes": ideal_test, "GBs": round(ideal_test / (t_test * 1e6), 1),
                             "Gtests_per_s": round(int(c["numCandidates"]) / (t_test * 1e6), 2)}
-    if not whole and radius_arg is None:
+    if surface:
+        # simlod_surface_samples on the same two arrays at the same radius, alternating rep by rep with the compare call; its kernels from one
+        # call between the library's own events (the six grid kernels are the compare call's own)
+        from simlod_amd.octree_io import Surface
+        sp = Surface.hillshade(radius, (1.0, 1.0, 2.0), [0xFF202020, 0xFFFFFFFF], miss_color=0xFF808080, max_workgroups=workgroups).record(0)
+        s_records = torch.empty(na * abi.surface_record_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+        s_summary = torch.zeros(abi.surface_summary_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+
+        def scall():
+            rc = L.simlod_surface_samples(up, p(ta), ctypes.c_uint64(na), p(tb), ctypes.c_uint64(nb), ctypes.c_void_p(sp.ctypes.data), p(scratch),
+                                          ctypes.c_uint64(need), p(s_records), p(colors), p(s_summary), stream)
+            assert rc == 0
+        tss = timed_alternating([scall, lambda: call()], reps)
+        L.simlod_profile_enable(1)
+        scall()
+        torch.cuda.synchronize()
+        import bench
+        prof = bench.collect_profile(L)
+        L.simlod_profile_enable(0)
+        sc = s_summary.cpu().numpy().view(abi.surface_summary_dtype)[0]
+        assert int(sc["error"]) == 0 and int(sc["numCandidates"]) == int(c["numCandidates"])
+        kernels = {k: round(ms, 4) for k, (n, ms) in prof.items() if k.startswith("k_c_") or k.startswith("k_s_")}
+        out["surface"] = {"ms": round(tss[0][0], 4), "ms_min": round(tss[0][1], 4), "compare_ms_beside_it": round(tss[1][0], 4), "kernels_ms": kernels,
+                          "numEstimated": int(sc["numEstimated"]), "numDegenerate": int(sc["numDegenerate"]), "numWithin": int(sc["numWithin"]),
+                          "Msamples_per_s": round(na / (tss[0][0] * 1e3), 1)}
+        if "k_s_test" in kernels and "k_c_test" in out["kernels_ms"]:
+            out["surface"]["k_s_test_over_k_c_test"] = round(kernels["k_s_test"] / out["kernels_ms"]["k_c_test"], 3)
+    if not whole and radius_arg is None and not surface:
         # for scale: the same positions through simlod_query_neighbours at k = 1, in batches of 65 536 queries (each sized by its own
         # count-only call); the sum of the batches' medians of three runs is the figure
         centers = ex_a.samples
@@ -1117,6 +1145,7 @@ def main():
     ap.add_argument("--compare", action="store_true", help="time simlod_compare_samples (a 1 M-sample CUT@20 selection against the full CUT@20 export at radius 2.167; count-only, with results, per kernel) beside simlod_query_neighbours k = 1 instead")
     ap.add_argument("--compare-whole", action="store_true", help="--compare with A = B = the full CUT@20 export (skipped above 4 096 candidates per sample)")
     ap.add_argument("--compare-workgroups", type=int, default=0, help="--compare / --compare-whole: SimlodCompareParams.maxWorkgroups (0: the library's choice)")
+    ap.add_argument("--surface", action="store_true", help="--compare / --compare-whole: also time simlod_surface_samples on the same arrays at the same radius, alternating with the compare call, with its kernels (the neighbour yardstick is then left out)")
     ap.add_argument("--compare-radius", type=float, default=None, help="--compare: another radius (heavier cells); the neighbour yardstick is then left out")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
@@ -1151,7 +1180,8 @@ def main():
     if args.neighbours:
         return neighbours_bench(dev, u, box, st, args.reps, pts)
     if args.compare or args.compare_whole:
-        return compare_bench(dev, u, box, st, args.reps, pts, whole=args.compare_whole, workgroups=args.compare_workgroups, radius_arg=args.compare_radius)
+        return compare_bench(dev, u, box, st, args.reps, pts, whole=args.compare_whole, workgroups=args.compare_workgroups, radius_arg=args.compare_radius,
+                             surface=args.surface)
     if args.view:
         return view_bench(dev, u, box, st, args.reps)
     if args.view_delta:
