@@ -1582,6 +1582,118 @@ int simlod_surface_samples(const SimlodUniforms* uniforms /*host*/, const Simlod
                            SimlodSurfaceRecord* records /*or NULL: count only*/, uint32_t* colors /*or NULL*/,
                            SimlodSurfaceSummary* summary, void* stream);
 
+/* ---- cluster queries: each sample's connected component within a radius ------------------------------------------------------------------------
+ * simlod_cluster_samples relates ONE sample array to itself: the samples that can be reached from one another in steps of at most a radius
+ * form a cluster.  With minNeighbours > 1 only samples with that many samples around them carry a step (the density rule of DBSCAN), so a
+ * thin bridge of stray samples joins nothing.  Per sample it returns the cluster's number, its root (the lowest index of its cores), its size
+ * and `within`, a colour from a 256-entry table indexed by the cluster's number, and one summary record.  It runs on the compare queries' hash
+ * grid over `a`, built by the same kernels; the array, the box and the grid's fields of the summary mean what they mean there.  Every number
+ * returned is an integer.
+ *  K1. Valid samples, the test, the grid.  Rules C1, C2 and C4 hold with this record's radius and b = a: the valid samples, the test
+ *      d2 <= rr, and the grid — h, inv, the up to 27 cells, numCells, maxCellPopulation, numCandidates, and the compare query's refusals.
+ *  K2. Budget and count only.  Rules C6 and C7 hold with SIMLOD_CLUSTER_ERR_BUDGET: where no sample is tested every field of the summary
+ *      past numCandidates is zero and no record and no colour is written.
+ *  K3. Core.  within[i] is the number of valid samples j of `a`, i itself included, with d2 <= rr (rule C2).  A valid sample is a CORE iff
+ *      within[i] >= minNeighbours.  minNeighbours must be >= 1; 1 makes every valid sample a core, which is plain Euclidean clustering
+ *      (single linkage at the radius).  Rule C2's d2 is symmetric bit for bit: s - c and c - s are exact negations of each other, their
+ *      squares are equal and the sums are taken in the same order, so "i is within r of j" does not depend on which of the two asks.
+ *  K4. Components.  Two cores are linked iff their d2 <= rr.  A cluster is a connected component of the cores under these links; its
+ *      `root` is the lowest index in `a` of its cores.
+ *  K5. Border and noise.  A valid sample that is no core, with at least one core passing rule C2, is a BORDER sample of the cluster of the
+ *      first such core in the total order (d2, index) — rule C3's order.  It links nothing: two clusters that share a border sample stay
+ *      two.  With no core passing the sample is noise.  An invalid sample is noise with within = 0.
+ *  K6. Sizes.  A cluster's size is the number of its cores plus the number of its border samples.
+ *  K7. Small clusters.  A cluster whose size is below minClusterSize (>= 1; 1 keeps all) is DISSOLVED: its members keep `root` and `size`
+ *      and get cluster = SIMLOD_CLUSTER_NOISE, so root != SIMLOD_CLUSTER_MISS tells a dissolved sample from true noise.
+ *  K8. Numbers.  The kept clusters are numbered 0 .. numClusters - 1 in ascending order of `root`.
+ *  K9. Record, colour, summary.  A member of a cluster: {cluster, root, size, within}; true noise: {SIMLOD_CLUSTER_NOISE,
+ *      SIMLOD_CLUSTER_MISS, 0, within}.  colors[i] = table[cluster & 255] for a sample of a kept cluster, noiseColor for every other.
+ *      numClusters: the kept clusters; numDissolved: the dissolved ones; numCore and numBorder: the cores and the border samples of the
+ *      KEPT clusters; numNoise: every other sample — true noise, the members of dissolved clusters and the invalid samples —, so that
+ *      numCore + numBorder + numNoise = numA; numWithin: the sum of within; largestSize: the largest size of a kept cluster (0 with none),
+ *      largestCluster: the lowest number among the clusters of that size (0 with none); sizeHist[k]: the kept clusters with
+ *      floor(log2(size)) = k.  numInvalidB repeats numInvalidA: the grid is over `a` itself.
+ * K10. Determinism.  Rule C8 holds: every field is a sum of integers, a maximum, or the minimum of a total order — a root is the minimum of
+ *      a set of indices, a number the rank of a root —: a pure function of the array and the parameters, independent of the schedule, of
+ *      maxWorkgroups and of where the hash table puts a cell.  Two calls give the same bytes.  The union-find that finds the components
+ *      bounds every loop by a number known at launch; should a bound ever be reached the call stops there and sets
+ *      SIMLOD_CLUSTER_ERR_INTERNAL, with records that mean nothing.  No input is known that does it.
+ * Nothing is written but `scratch`, `records`, `colors` and `summary`. */
+#define SIMLOD_CLUSTER_ERR_BUDGET   0x1u
+#define SIMLOD_CLUSTER_ERR_INTERNAL 0x2u
+#define SIMLOD_CLUSTER_NOISE        0xffffffffu
+#define SIMLOD_CLUSTER_MISS         0xffffffffu
+#define SIMLOD_CLUSTER_SIZE_BINS    33
+typedef struct SimlodClusterRecord {   /* DEVICE memory, one per sample of `a`, same index */
+	uint32_t cluster;                  /* rule K8; SIMLOD_CLUSTER_NOISE: noise or dissolved                     */
+	uint32_t root;                     /* rule K4; SIMLOD_CLUSTER_MISS: true noise                              */
+	uint32_t size;                     /* rule K6; 0: true noise                                                */
+	uint32_t within;                   /* rule K3                                                               */
+} SimlodClusterRecord;
+typedef struct SimlodClusterParams {   /* host memory; read completely before the call returns */
+	float    radius;                   /* finite, >= 0                                                          */
+	uint32_t minNeighbours;            /* rule K3; >= 1                                                         */
+	uint32_t minClusterSize;           /* rule K7; >= 1                                                         */
+	uint32_t noiseColor;               /* rule K9                                                               */
+	uint64_t maxCandidates;            /* rule C6; 0: no limit                                                  */
+	uint32_t table[256];               /* rule K9                                                               */
+	uint32_t maxWorkgroups;            /* 0: the library's choice; else no kernel launches more workgroups      */
+	uint32_t reserved;                 /* 0                                                                     */
+} SimlodClusterParams;
+typedef struct SimlodClusterSummary {  /* written by the device; SimlodCompareSummary's size, its leading fields at their offsets */
+	uint32_t error;                    /* SIMLOD_CLUSTER_ERR_* bits                                             */
+	uint32_t numCells;                 /* rule C4                                                               */
+	uint32_t maxCellPopulation;        /* rule C4                                                               */
+	uint32_t numInvalidA;              /* rule C1                                                               */
+	uint32_t numInvalidB;              /* = numInvalidA                                                         */
+	uint32_t numClusters;              /* rule K8                                                               */
+	uint64_t numWithin;                /* the sum of within                                                     */
+	uint64_t numCandidates;            /* rule C4                                                               */
+	uint64_t numCore;                  /* rule K9                                                               */
+	uint64_t numBorder;                /* rule K9                                                               */
+	uint64_t numNoise;                 /* rule K9                                                               */
+	uint64_t numDissolved;             /* rule K7: clusters, not samples                                        */
+	uint32_t largestSize;              /* rule K9                                                               */
+	uint32_t largestCluster;           /* rule K9                                                               */
+	uint64_t sizeHist[SIMLOD_CLUSTER_SIZE_BINS];   /* rule K9                                                   */
+	uint64_t zero[220];                /* 0                                                                     */
+} SimlodClusterSummary;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodClusterRecord) == 16, "ClusterRecord");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterRecord, within) == 12, "ClusterRecord.within");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodClusterParams) == 1056, "ClusterParams");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterParams, maxCandidates) == 16, "ClusterParams.maxCandidates");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterParams, table) == 24, "ClusterParams.table");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterParams, maxWorkgroups) == 1048, "ClusterParams.maxWorkgroups");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterParams, reserved) == 1052, "ClusterParams.reserved");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodClusterSummary) == sizeof(SimlodCompareSummary), "ClusterSummary");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, error) == offsetof(SimlodCompareSummary, error), "ClusterSummary.error");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, numCells) == offsetof(SimlodCompareSummary, numCells), "ClusterSummary.numCells");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, maxCellPopulation) == offsetof(SimlodCompareSummary, maxCellPopulation), "ClusterSummary.maxCellPopulation");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, numInvalidA) == offsetof(SimlodCompareSummary, numInvalidA), "ClusterSummary.numInvalidA");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, numInvalidB) == offsetof(SimlodCompareSummary, numInvalidB), "ClusterSummary.numInvalidB");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, numClusters) == offsetof(SimlodCompareSummary, numMatched), "ClusterSummary.numClusters");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, numWithin) == offsetof(SimlodCompareSummary, numWithin), "ClusterSummary.numWithin");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, numCandidates) == offsetof(SimlodCompareSummary, numCandidates), "ClusterSummary.numCandidates");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, numCore) == offsetof(SimlodCompareSummary, maxD2), "ClusterSummary.numCore");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, numBorder) == offsetof(SimlodCompareSummary, hist), "ClusterSummary.numBorder");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, largestSize) == 72, "ClusterSummary.largestSize");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, sizeHist) == 80, "ClusterSummary.sizeHist");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodClusterSummary, zero) == 344, "ClusterSummary.zero");
+
+/* Bytes of the `scratch` buffer a cluster call needs, a pure function of numA: simlod_compare_buffer_min_bytes(numA, numA), five 32-bit words
+ * per sample (within, parent, attach / root, size, number; each array rounded up to 16 bytes) and the partial records of the largest grid.
+ * 0 for a count the call refuses. */
+uint64_t simlod_cluster_buffer_min_bytes(uint64_t numA);
+
+/* The cluster query (rules above).  Asynchronous on `stream` once `uniforms` and `params` have been read.  hipErrorInvalidValue with nothing
+ * enqueued and nothing touched: everything simlod_compare_samples refuses of its arguments with b = a (null pointers, colors without
+ * records, the count, the radius, the box, `reserved`, the alignments — `records` at 16 bytes); minNeighbours == 0; minClusterSize == 0;
+ * scratchBytes below simlod_cluster_buffer_min_bytes(numA) (one byte less is refused, the exact size is accepted). */
+int simlod_cluster_samples(const SimlodUniforms* uniforms /*host*/, const SimlodPoint* a, uint64_t numA,
+                           const SimlodClusterParams* params /*host*/, void* scratch, uint64_t scratchBytes,
+                           SimlodClusterRecord* records /*or NULL: count only*/, uint32_t* colors /*or NULL*/,
+                           SimlodClusterSummary* summary, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

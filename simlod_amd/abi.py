@@ -245,6 +245,24 @@ surface_summary_dtype = np.dtype({"names": ["error", "numCells", "maxCellPopulat
                                   "offsets": [0, 4, 8, 12, 16, 20, 24, 32, 40, 48], "itemsize": 2104})
 assert surface_record_dtype.itemsize == 32 and surface_params_dtype.itemsize == 3120 and surface_summary_dtype.itemsize == 2104
 
+# ---- cluster queries (include/simlod_hip.h, "cluster queries") ---------------------------------------------------------------------------
+CLUSTER_ERR_BUDGET, CLUSTER_ERR_INTERNAL = 0x1, 0x2
+CLUSTER_NOISE = 0xFFFFFFFF                                                  # `cluster` of noise and of dissolved samples
+CLUSTER_MISS = 0xFFFFFFFF                                                   # `root` of true noise
+CLUSTER_SIZE_BINS = 33                                                      # sizeHist: floor(log2(size))
+cluster_record_dtype = np.dtype({"names": ["cluster", "root", "size", "within"], "formats": ["<u4", "<u4", "<u4", "<u4"], "offsets": [0, 4, 8, 12],
+                                 "itemsize": 16})
+cluster_params_dtype = np.dtype({"names": ["radius", "minNeighbours", "minClusterSize", "noiseColor", "maxCandidates", "table", "maxWorkgroups", "reserved"],
+                                 "formats": ["<f4", "<u4", "<u4", "<u4", "<u8", ("<u4", 256), "<u4", "<u4"],
+                                 "offsets": [0, 4, 8, 12, 16, 24, 1048, 1052], "itemsize": 1056})
+cluster_summary_dtype = np.dtype({"names": ["error", "numCells", "maxCellPopulation", "numInvalidA", "numInvalidB", "numClusters", "numWithin",
+                                            "numCandidates", "numCore", "numBorder", "numNoise", "numDissolved", "largestSize", "largestCluster",
+                                            "sizeHist", "zero"],
+                                  "formats": ["<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<u8", "<u8", "<u8", "<u8", "<u8", "<u8", "<u4", "<u4",
+                                              ("<u8", CLUSTER_SIZE_BINS), ("<u8", 220)],
+                                  "offsets": [0, 4, 8, 12, 16, 20, 24, 32, 40, 48, 56, 64, 72, 76, 80, 344], "itemsize": 2104})
+assert cluster_record_dtype.itemsize == 16 and cluster_params_dtype.itemsize == 1056 and cluster_summary_dtype.itemsize == compare_summary_dtype.itemsize
+
 # ---- lasso queries (include/simlod_hip.h, "lasso queries") -------------------------------------------------------------------------------
 LASSO_MAX_VERTICES = 256
 lasso_dtype = np.dtype({"names": ["numVertices", "reserved", "rowU", "rowV", "rowW", "vertices"],

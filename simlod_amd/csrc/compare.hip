@@ -24,7 +24,7 @@
 //                record (one 16-byte store) and colour, counts its bin in the workgroup's LDS histogram and keeps the sums in registers.
 //   k_c_final    the test pass's partial records added up -> numMatched, numWithin, maxD2, hist.  Returns at once unless `run`.
 // The surface queries (compare_surface.inc, included below) run the first six launches as they are — launch_grid — and follow them with their
-// own test pass and final.
+// own test pass and final; the cluster queries (compare_cluster.inc) run them with b = a and follow them with seven kernels of their own.
 // No atomic touches global memory for the summary: every kernel writes ONE partial record per workgroup (CmpPart, its own fields of it) with
 // plain stores, as export_summary.inc does, and integer sums and maxima do not depend on the order of adding (rule C8).  d2 is never negative,
 // so the maximum of its 64 bits as an unsigned integer is the maximum of the doubles.
@@ -39,6 +39,7 @@
 #include "simlod_internal.hpp"
 #include "compare_rules.hpp"
 #include "surface_rules.hpp"
+#include "cluster_rules.hpp"
 
 namespace simlod {
 namespace {
@@ -465,6 +466,7 @@ void launch_grid(const CmpArgs& c, hipStream_t stream) {
 }
 
 #include "compare_surface.inc"
+#include "compare_cluster.inc"
 
 }  // namespace
 
@@ -519,6 +521,14 @@ int launch_surface(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA,
 	}
 	if (profile_enabled()) profile_close(stream);
 	return (int)hipGetLastError();
+}
+
+uint64_t cluster_min_bytes(uint64_t numA) { return cluster_bytes(numA); }
+
+// simlod_cluster_samples: compare_cluster.inc's launcher.
+int launch_cluster(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA, const SimlodClusterParams* params, void* scratch, uint64_t scratchBytes,
+                   SimlodClusterRecord* records, uint32_t* colors, SimlodClusterSummary* summary, hipStream_t stream) {
+	return launch_cluster_impl(u, a, numA, params, scratch, scratchBytes, records, colors, summary, stream);
 }
 
 }  // namespace simlod

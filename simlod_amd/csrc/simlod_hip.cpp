@@ -641,6 +641,13 @@ int simlod_surface_samples(const SimlodUniforms* uniforms, const SimlodPoint* a,
 	return launch_surface(uniforms, a, numA, b, numB, params, scratch, scratchBytes, records, colors, summary, (hipStream_t)stream);
 }
 
+uint64_t simlod_cluster_buffer_min_bytes(uint64_t numA) { return cluster_min_bytes(numA); }
+
+int simlod_cluster_samples(const SimlodUniforms* uniforms, const SimlodPoint* a, uint64_t numA, const SimlodClusterParams* params, void* scratch,
+                           uint64_t scratchBytes, SimlodClusterRecord* records, uint32_t* colors, SimlodClusterSummary* summary, void* stream) {
+	return launch_cluster(uniforms, a, numA, params, scratch, scratchBytes, records, colors, summary, (hipStream_t)stream);
+}
+
 uint64_t simlod_rays_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates) {
 	return rays_min_bytes(nodeCapacity, sampleBound, numRays, numPairs, numCandidates);
 }

@@ -40,6 +40,11 @@ Compare queries (include/simlod_hip.h, "compare queries"): `Compare` holds the r
 C1-C5 in numpy float64 and integers —, `OctreeExport.compare` applies it to two exports and `CompareResult` is what
 DeviceOctree.compare_region returns.
 
+Cluster queries (include/simlod_hip.h, "cluster queries"): `Cluster` holds the radius, minNeighbours, minClusterSize, the colour table and the
+budget, `cluster_samples` is the host mirror of simlod_cluster_samples — rules K1-K10 on compare_samples' pairs, the components by passing the
+minimum label along the core links with pointer jumping until nothing changes, numpy only —, `OctreeExport.cluster` applies it to an export
+and `ClusterResult` is what DeviceOctree.cluster_region returns.
+
 Surface queries (include/simlod_hip.h, "surface queries"): `Surface` holds the radius, the thresholds, the colour table, the light and the
 orientation, `surface_samples` is the host mirror of simlod_surface_samples — rules N1-N10 on compare_samples' pairs, the sums in int64, the
 rest in numpy float64 —, `OctreeExport.surface` applies it to an export and `SurfaceResult` is what DeviceOctree.surface_region returns.
@@ -350,6 +355,12 @@ class OctreeExport:
         """The host mirror of simlod_compare_samples on this export's samples (A) and `other`'s (B; may be this export), in this export's box:
         compare_samples' (records, colours, summary)."""
         return compare_samples(self.samples, other.samples, (self.box_min, self.box_max), compare, count_only=count_only)
+
+    # -- cluster queries (include/simlod_hip.h, "cluster queries") -------------------------------------------------------------------------
+    def cluster(self, cluster, count_only=False):
+        """The host mirror of simlod_cluster_samples on this export's samples, in this export's box: cluster_samples' (records, colours,
+        summary)."""
+        return cluster_samples(self.samples, (self.box_min, self.box_max), cluster, count_only=count_only)
 
     # -- surface queries (include/simlod_hip.h, "surface queries") -------------------------------------------------------------------------
     def surface(self, surface, other=None, count_only=False):
@@ -1825,6 +1836,156 @@ def surface_variation(records):
     """SurfaceResult.variation for an array of abi.surface_record_dtype."""
     r = np.asarray(records, dtype=abi.surface_record_dtype).reshape(-1)
     return np.divide(r["lambdaNum"], r["lambdaDen"], out=np.zeros(len(r), np.float64), where=r["lambdaDen"] != 0)
+
+
+class Cluster:
+    """The parameters of a cluster query (include/simlod_hip.h, "cluster queries"; abi.cluster_params_dtype): the radius (float32),
+    min_neighbours (rule K3; 1: plain Euclidean clustering), min_cluster_size (rule K7; 1 keeps every cluster), the 256 colour words of rule
+    K9 (None: Cluster.palette()), the noise colour, and the candidate budget of rule C6 (max_candidates; None, 0 and a number as in Compare).
+    The refusals are the C call's."""
+
+    def __init__(self, radius, min_neighbours=1, min_cluster_size=1, table=None, noise_color=0xFF404040, max_candidates=None, max_workgroups=0):
+        with np.errstate(over="ignore"):
+            self.radius = np.float32(radius)
+        self.min_neighbours, self.min_cluster_size = int(min_neighbours), int(min_cluster_size)
+        self.table = (Cluster.palette() if table is None else np.asarray(table, dtype=np.uint32).reshape(-1)).copy()
+        self.noise_color, self.max_workgroups = int(noise_color), int(max_workgroups)
+        self.max_candidates = None if max_candidates is None else int(max_candidates)
+        if not (np.isfinite(self.radius) and self.radius >= 0):
+            raise ValueError("a cluster query needs a finite radius >= 0 (as float32)")
+        if not (1 <= self.min_neighbours <= 0xFFFFFFFF and 1 <= self.min_cluster_size <= 0xFFFFFFFF):
+            raise ValueError("min_neighbours and min_cluster_size are 32-bit unsigned integers >= 1")
+        if len(self.table) != 256:
+            raise ValueError(f"{len(self.table)} table entries: 256")
+        if not 0 <= self.noise_color <= 0xFFFFFFFF or (self.max_candidates is not None and self.max_candidates < 0):
+            raise ValueError("a colour word is a 32-bit unsigned integer, a budget is not negative")
+
+    @staticmethod
+    def palette():
+        """256 distinct opaque colours: the index times an odd constant modulo 2^24 — a bijection, so no two agree — under full alpha."""
+        i = np.arange(256, dtype=np.uint64)
+        return (((i * np.uint64(0x9E3779B1) + np.uint64(0x7F4A7C)) & np.uint64(0xFFFFFF)) | np.uint64(0xFF000000)).astype(np.uint32)
+
+    @classmethod
+    def from_record(cls, record):
+        r = np.asarray(record, dtype=abi.cluster_params_dtype).reshape(-1)[0]
+        if int(r["reserved"]) != 0:
+            raise ValueError("the reserved word is 0")
+        return cls(r["radius"], int(r["minNeighbours"]), int(r["minClusterSize"]), r["table"], int(r["noiseColor"]), int(r["maxCandidates"]),
+                   int(r["maxWorkgroups"]))
+
+    def __eq__(self, other):
+        return isinstance(other, Cluster) and self.record().tobytes() == other.record().tobytes()
+
+    def record(self, max_candidates=None):
+        """The SimlodClusterParams the C ABI takes (abi.cluster_params_dtype, one record); max_candidates overrides the object's."""
+        r = np.zeros(1, dtype=abi.cluster_params_dtype)
+        budget = self.max_candidates if max_candidates is None else int(max_candidates)
+        r["radius"], r["minNeighbours"], r["minClusterSize"], r["noiseColor"] = self.radius, self.min_neighbours, self.min_cluster_size, self.noise_color
+        r["maxCandidates"], r["maxWorkgroups"] = budget or 0, self.max_workgroups
+        r["table"][0] = self.table
+        return r
+
+
+def cluster_samples(a, uniforms_box, cluster, count_only=False):
+    """The host mirror of simlod_cluster_samples (include/simlod_hip.h, "cluster queries"): a an array of abi.point_dtype, uniforms_box the
+    (box_min, box_max) of the uniforms, cluster a Cluster -> (records as abi.cluster_record_dtype, colours as uint32, the summary as one
+    abi.cluster_summary_dtype record); count_only, or a budget exceeded: records and colours are None.  The pairs are compare_samples' with
+    b = a (rules C1, C2, C4); rule K4's components by passing the minimum label along the core links — of the two labels a link joins the
+    higher one's own label becomes the lowest label offered to it — and then replacing every label by its label's label (pointer jumping),
+    both until nothing changes: a label only ever decreases and stays inside its component, so it ends at the component's lowest core."""
+    a, _, out, pairs = _compare_pairs(a, a, uniforms_box, cluster.radius, cluster.max_candidates, count_only, abi.cluster_summary_dtype)
+    if pairs is None:
+        return None, None, out
+    pi, pj, _, d2 = pairs
+    n = len(a)
+    valid = np.isfinite(a["x"]) & np.isfinite(a["y"]) & np.isfinite(a["z"])
+    within = np.bincount(pi, minlength=n).astype(np.int64)
+    core = valid & (within >= cluster.min_neighbours)                       # rule K3
+    label = np.arange(n, dtype=np.int64)
+    link = core[pi] & core[pj] & (pi > pj)                                  # rule K4 (the pairs hold every link from both its ends: one will do)
+    ei, ej = pi[link], pj[link]
+    while len(ei):
+        li, lj = label[ei], label[ej]                                       # (fully jumped: the labels of labels are themselves)
+        open_ = li != lj
+        if not open_.any():
+            break
+        ei, ej, li, lj = ei[open_], ej[open_], li[open_], lj[open_]
+        np.minimum.at(label, np.maximum(li, lj), np.minimum(li, lj))        # the higher label's label: the lowest label offered to it
+        while True:
+            new = label[label]
+            if (new == label).all():
+                break
+            label = new
+    root = np.full(n, abi.CLUSTER_MISS, dtype=np.int64)
+    root[core] = label[core]
+    cand = core[pj] & valid[pi] & ~core[pi]                                 # rule K5: the first core in (d2, index)
+    bi, bj, bd = pi[cand], pj[cand], d2[cand]
+    order = np.lexsort((bj, bd, bi))
+    lead = order[np.r_[True, bi[order][1:] != bi[order][:-1]]] if len(order) else order
+    root[bi[lead]] = label[bj[lead]]
+    member = root != abi.CLUSTER_MISS
+    size_of = np.bincount(root[member], minlength=n).astype(np.int64)       # rule K6, at the root's index
+    is_root = core & (label == np.arange(n))
+    kept_root = is_root & (size_of >= cluster.min_cluster_size)             # rule K7
+    number = np.cumsum(kept_root) - 1                                       # rule K8, at the root's index
+    rec = np.zeros(n, dtype=abi.cluster_record_dtype)
+    rec["within"] = within
+    rec["root"] = root
+    safe = np.where(member, root, 0)
+    rec["size"] = np.where(member, size_of[safe], 0)
+    kept = member & kept_root[safe]
+    rec["cluster"] = np.where(kept, number[safe], abi.CLUSTER_NOISE)
+    colours = np.where(kept, cluster.table[rec["cluster"] & 255], np.uint32(cluster.noise_color)).astype(np.uint32)   # rule K9
+    sizes = size_of[kept_root]
+    out["numClusters"], out["numDissolved"] = int(kept_root.sum()), int((is_root & ~kept_root).sum())
+    out["numCore"], out["numBorder"], out["numNoise"] = int((kept & core).sum()), int((kept & ~core).sum()), int((~kept).sum())
+    out["numWithin"] = int(within.sum())
+    if len(sizes):
+        out["largestSize"], out["largestCluster"] = int(sizes.max()), int(np.argmax(sizes))      # (argmax: the first, the lowest number)
+        out["sizeHist"] = np.bincount(np.floor(np.log2(sizes)).astype(np.int64), minlength=abi.CLUSTER_SIZE_BINS).astype(np.uint64)
+    return rec, colours, out
+
+
+class ClusterResult:
+    """What DeviceOctree.cluster_region returns: `a`, the selection as an OctreeExport (query_region's); `records`
+    (abi.cluster_record_dtype, one per sample of a, as bytes) and `colors` (uint32 words) as tensors on the device, in a's order; `summary`,
+    one abi.cluster_summary_dtype record on the host; the Cluster; and the selection's arguments."""
+
+    def __init__(self, a, records, colors, summary, cluster, selection):
+        self.a, self.records, self.colors, self.summary, self.cluster, self.selection = a, records, colors, summary, cluster, selection
+
+    def records_host(self):
+        """The records as a numpy array of abi.cluster_record_dtype."""
+        r = self.records
+        return (r.cpu().numpy() if hasattr(r, "cpu") else np.asarray(r)).view(abi.cluster_record_dtype).reshape(-1)
+
+    @property
+    def labels(self):
+        """Per sample its cluster's number as int64, -1 for noise and for the members of dissolved clusters."""
+        c = self.records_host()["cluster"].astype(np.int64)
+        return np.where(c == abi.CLUSTER_NOISE, -1, c)
+
+    def sizes(self):
+        """The sizes of the kept clusters, by number (int64, numClusters entries)."""
+        rec = self.records_host()
+        out = np.zeros(int(self.summary["numClusters"]), np.int64)
+        kept = rec["cluster"] != abi.CLUSTER_NOISE
+        out[rec["cluster"][kept]] = rec["size"][kept]
+        return out
+
+    def members(self, number):
+        """The indices in a of the samples of the kept cluster `number`, ascending."""
+        return np.flatnonzero(self.records_host()["cluster"] == np.uint32(number))
+
+    def paint(self, dev, uniforms, return_previous=False):
+        """Write the colours into the octree `dev` the selection was taken from — an ARRAY paint of the same selection, as CompareResult.paint.
+        Only a result of max_level=20, select="all" has that order."""
+        s = self.selection
+        if s["max_level"] != abi.MAX_DEPTH or s["select"] != "all":
+            raise ValueError("only a cluster_region(max_level=20, select='all') result is in the order paint_region takes")
+        return dev.paint_region(uniforms, s["region"], Paint.array(), footprint=s["footprint"], colors=self.colors, return_previous=return_previous,
+                                lasso=s["lasso"], invert=s["invert"])
 
 
 class Footprint:

@@ -141,6 +141,9 @@ def lib():
         L.simlod_surface_buffer_min_bytes.restype = u64
         L.simlod_surface_buffer_min_bytes.argtypes = [u64, u64]
         L.simlod_surface_samples.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp]
+        L.simlod_cluster_buffer_min_bytes.restype = u64
+        L.simlod_cluster_buffer_min_bytes.argtypes = [u64]
+        L.simlod_cluster_samples.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -169,6 +172,7 @@ EXPORTED_SYMBOLS = [
     "simlod_inverse_buffer_min_bytes", "simlod_query_inverse", "simlod_paint_inverse", "simlod_query_summary_inverse",
     "simlod_compare_buffer_min_bytes", "simlod_compare_table_slots", "simlod_compare_samples",
     "simlod_surface_buffer_min_bytes", "simlod_surface_samples",
+    "simlod_cluster_buffer_min_bytes", "simlod_cluster_samples",
 ]
 
 
@@ -1031,6 +1035,60 @@ class DeviceOctree:
         if int(s["error"]) != 0:
             raise SimlodError(f"simlod_surface_samples reported error bits {int(s['error']):#x}; no record was written")
         return SurfaceResult(a, b, records, colors, s, surface, sel)
+
+    # -- cluster queries (include/simlod_hip.h, "cluster queries") -------------------------------------------------------------------------
+    def cluster_samples(self, uniforms, a, cluster, count_only=False, max_candidates=None):
+        """One simlod_cluster_samples call on a sample array (as compare_samples takes them): per sample its connected component within
+        cluster.radius.  -> (records: a uint8 tensor of abi.cluster_record_dtype records, colors: an int32 tensor of colour words, both on
+        this device and in a's order, and the abi.cluster_summary_dtype record on the host); count_only: (None, None, record).  The call
+        ALWAYS carries a candidate budget, compare_samples' (rule C6): max_candidates if given, else cluster.max_candidates, else 64
+        candidates per sample; an explicit 0 is the opt-out.  A budget exceeded comes back as (None, None, record) with
+        SIMLOD_CLUSTER_ERR_BUDGET in the record's error field."""
+        u, up = self._u(uniforms)
+        ta = self._samples_tensor(a)
+        na = ta.numel() // abi.point_dtype.itemsize
+        budget = max_candidates if max_candidates is not None else cluster.max_candidates
+        pr = cluster.record(self.COMPARE_BUDGET_PER_SAMPLE * na if budget is None else int(budget))
+        need = int(self.L.simlod_cluster_buffer_min_bytes(na))
+        if need == 0:
+            raise ValueError("numA is 1 .. 2^32 - 2")
+        scratch = self._export_scratch(need)
+        out = torch.zeros(abi.cluster_summary_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        records = colors = None
+        if not count_only:
+            records = torch.empty(na * abi.cluster_record_dtype.itemsize, dtype=torch.uint8, device=self.device)
+            colors = torch.empty(na, dtype=torch.int32, device=self.device)
+        opt = lambda t: None if t is None else self._p(t)
+        _check(self.L.simlod_cluster_samples(up, self._p(ta), ctypes.c_uint64(na), ctypes.c_void_p(pr.ctypes.data), self._p(scratch),
+                                             ctypes.c_uint64(scratch.numel()), opt(records), opt(colors), self._p(out), self._stream()),
+               "simlod_cluster_samples")
+        rec = out.cpu().numpy().view(abi.cluster_summary_dtype)[0]
+        return (None, None, rec) if int(rec["error"]) != 0 else (records, colors, rec)
+
+    def count_cluster(self, uniforms, region, cluster, max_level=None, select="cut", footprint=None, lasso=None, invert=False):
+        """What cluster_region would cost: the abi.cluster_summary_dtype record of the count-only call (numCells, maxCellPopulation,
+        numCandidates, the invalid count) for the same arguments; nothing is clustered and no budget applies."""
+        a, _, _ = self._surface_inputs(uniforms, None, region, max_level, select, footprint, lasso, invert, None, "cut")
+        return self.cluster_samples(uniforms, a, cluster, count_only=True, max_candidates=0)[2]
+
+    def cluster_region(self, uniforms, region, cluster, max_level=None, select="cut", footprint=None, lasso=None, invert=False):
+        """The clusters of a selection of THIS octree: A = query_region(region, max_level, select, footprint / lasso / invert), a count-only
+        simlod_cluster_samples call, the budget check, then the call with results -> an octree_io.ClusterResult.  The budget is
+        cluster.max_candidates (None: 64 candidates per sample of A; 0: none); a count above it raises SimlodError naming numCandidates and
+        maxCellPopulation — pick a smaller radius or a coarser cut.  With max_level=20, select="all" the colours are in the order
+        paint_region's ARRAY paint takes: ClusterResult.paint(dev, uniforms) writes them into the octree."""
+        from .octree_io import ClusterResult
+        a, _, sel = self._surface_inputs(uniforms, None, region, max_level, select, footprint, lasso, invert, None, "cut")
+        budget = self.COMPARE_BUDGET_PER_SAMPLE * a.num_samples if cluster.max_candidates is None else cluster.max_candidates
+        c = self.cluster_samples(uniforms, a, cluster, count_only=True, max_candidates=0)[2]
+        if budget != 0 and int(c["numCandidates"]) > budget:
+            raise SimlodError(f"clustering {a.num_samples} samples at radius {float(cluster.radius)} would test numCandidates = "
+                              f"{int(c['numCandidates'])} pairs, above the budget of {budget} (maxCellPopulation = {int(c['maxCellPopulation'])} in "
+                              f"{int(c['numCells'])} cells): pick a smaller radius or a coarser cut")
+        records, colors, s = self.cluster_samples(uniforms, a, cluster, max_candidates=budget)
+        if int(s["error"]) != 0:
+            raise SimlodError(f"simlod_cluster_samples reported error bits {int(s['error']):#x}; no record is valid")
+        return ClusterResult(a, records, colors, s, cluster, sel)
 
     # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
     def _profile(self, uniforms, profile, region, ml, sel, table, samples, records, sample_capacity, bound):

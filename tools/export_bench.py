@@ -49,7 +49,8 @@ kernel's time from one call between the library's own events, candidates per sam
 the device-to-device copy — and, for scale, the same positions through simlod_query_neighbours at k = 1, in batches of 65 536.  --compare-radius R:
 another radius, for cells of hundreds or thousands of samples, without that yardstick.
 --compare-whole: the same with A = B = the full export.  --compare-workgroups N: SimlodCompareParams.maxWorkgroups for either.  --surface: with
-either, simlod_surface_samples on the same arrays at the same radius as well, alternating with the compare call, and its kernels."""
+either, simlod_surface_samples on the same arrays at the same radius as well, alternating with the compare call, and its kernels.  --cluster: with
+either, simlod_cluster_samples on A alone at the same radius with minNeighbours 1 and 8, beside simlod_compare_samples(A, A), and its kernels."""
 import argparse
 import ctypes
 import json
@@ -723,7 +724,7 @@ def neighbours_bench(dev, u, box, st, reps, pts):
     print(json.dumps(out))
 
 
-def compare_bench(dev, u, box, st, reps, pts, whole=False, workgroups=0, radius_arg=None, surface=False):
+def compare_bench(dev, u, box, st, reps, pts, whole=False, workgroups=0, radius_arg=None, surface=False, cluster=False):
     """simlod_compare_samples: A = the CUT@20 selection of a box of 1/36 of the plan area (about 1 M samples), B = the octree's full CUT@20
     export, at --neighbours' radius of DESIGN §11 (2.167)."""
     from simlod_amd import fingerprint
@@ -818,7 +819,55 @@ def compare_bench(dev, u, box, st, reps, pts, whole=False, workgroups=0, radius_
                           "Msamples_per_s": round(na / (tss[0][0] * 1e3), 1)}
         if "k_s_test" in kernels and "k_c_test" in out["kernels_ms"]:
             out["surface"]["k_s_test_over_k_c_test"] = round(kernels["k_s_test"] / out["kernels_ms"]["k_c_test"], 3)
-    if not whole and radius_arg is None and not surface:
+    if cluster:
+        # simlod_cluster_samples on A alone at the same radius, with minNeighbours 1 and 8, alternating rep by rep with simlod_compare_samples(A, A) —
+        # the yardstick on the same input —; each call's kernels from one call between the library's own events
+        from simlod_amd.octree_io import Cluster
+        k_need = int(L.simlod_cluster_buffer_min_bytes(na))
+        k_scratch = torch.empty(k_need, dtype=torch.uint8, device=dev.device)
+        k_records = torch.empty(na * abi.cluster_record_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+        k_summary = torch.zeros(abi.cluster_summary_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+        a_summary = torch.zeros(abi.compare_summary_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+        kp = {m: Cluster(radius, m, 1, max_workgroups=workgroups).record(0) for m in (1, 8)}
+
+        def kcall(m):
+            rc = L.simlod_cluster_samples(up, p(ta), ctypes.c_uint64(na), ctypes.c_void_p(kp[m].ctypes.data), p(k_scratch), ctypes.c_uint64(k_need),
+                                          p(k_records), p(colors), p(k_summary), stream)
+            assert rc == 0
+
+        def acall():
+            rc = L.simlod_compare_samples(up, p(ta), ctypes.c_uint64(na), p(ta), ctypes.c_uint64(na), ctypes.c_void_p(pr.ctypes.data), p(k_scratch),
+                                          ctypes.c_uint64(k_need), p(records), p(colors), p(a_summary), stream)
+            assert rc == 0
+        tks = timed_alternating([lambda: kcall(1), lambda: kcall(8), acall], reps)
+        import bench
+        out["cluster"] = {"scratch_bytes": k_need, "compare_a_a_ms": round(tks[2][0], 4), "compare_a_a_ms_min": round(tks[2][1], 4)}
+        L.simlod_profile_enable(1)
+        acall()
+        torch.cuda.synchronize()
+        prof = bench.collect_profile(L)
+        L.simlod_profile_enable(0)
+        out["cluster"]["compare_a_a_kernels_ms"] = {k: round(ms, 4) for k, (n, ms) in prof.items() if k.startswith("k_c_")}
+        t_test = out["cluster"]["compare_a_a_kernels_ms"].get("k_c_test")
+        for i, m in enumerate((1, 8)):
+            L.simlod_profile_enable(1)
+            kcall(m)
+            torch.cuda.synchronize()
+            prof = bench.collect_profile(L)
+            L.simlod_profile_enable(0)
+            kc = k_summary.cpu().numpy().view(abi.cluster_summary_dtype)[0]
+            assert int(kc["error"]) == 0
+            kernels = {k: round(ms, 4) for k, (n, ms) in prof.items() if k.startswith("k_c_") or k.startswith("k_k_")}
+            row = {"ms": round(tks[i][0], 4), "ms_min": round(tks[i][1], 4), "over_compare_a_a": round(tks[i][0] / tks[2][0], 3), "kernels_ms": kernels,
+                   "numClusters": int(kc["numClusters"]), "largestSize": int(kc["largestSize"]), "largestCluster": int(kc["largestCluster"]),
+                   "numCore": int(kc["numCore"]), "numBorder": int(kc["numBorder"]), "numNoise": int(kc["numNoise"]), "numWithin": int(kc["numWithin"]),
+                   "numCandidates": int(kc["numCandidates"]), "Msamples_per_s": round(na / (tks[i][0] * 1e3), 1)}
+            if t_test and "k_k_link" in kernels and "k_k_core" in kernels:
+                row["k_k_core_over_k_c_test"] = round(kernels["k_k_core"] / t_test, 3)
+                row["k_k_link_over_k_c_test"] = round(kernels["k_k_link"] / t_test, 3)
+            out["cluster"][f"minNeighbours_{m}"] = row
+        del k_scratch, k_records
+    if not whole and radius_arg is None and not surface and not cluster:
         # for scale: the same positions through simlod_query_neighbours at k = 1, in batches of 65 536 queries (each sized by its own
         # count-only call); the sum of the batches' medians of three runs is the figure
         centers = ex_a.samples
@@ -1146,6 +1195,7 @@ def main():
     ap.add_argument("--compare-whole", action="store_true", help="--compare with A = B = the full CUT@20 export (skipped above 4 096 candidates per sample)")
     ap.add_argument("--compare-workgroups", type=int, default=0, help="--compare / --compare-whole: SimlodCompareParams.maxWorkgroups (0: the library's choice)")
     ap.add_argument("--surface", action="store_true", help="--compare / --compare-whole: also time simlod_surface_samples on the same arrays at the same radius, alternating with the compare call, with its kernels (the neighbour yardstick is then left out)")
+    ap.add_argument("--cluster", action="store_true", help="--compare / --compare-whole: also time simlod_cluster_samples on A alone at the same radius with minNeighbours 1 and 8, alternating with simlod_compare_samples(A, A), with its kernels (the neighbour yardstick is then left out)")
     ap.add_argument("--compare-radius", type=float, default=None, help="--compare: another radius (heavier cells); the neighbour yardstick is then left out")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
@@ -1181,7 +1231,7 @@ def main():
         return neighbours_bench(dev, u, box, st, args.reps, pts)
     if args.compare or args.compare_whole:
         return compare_bench(dev, u, box, st, args.reps, pts, whole=args.compare_whole, workgroups=args.compare_workgroups, radius_arg=args.compare_radius,
-                             surface=args.surface)
+                             surface=args.surface, cluster=args.cluster)
     if args.view:
         return view_bench(dev, u, box, st, args.reps)
     if args.view_delta:
