@@ -1694,6 +1694,130 @@ int simlod_cluster_samples(const SimlodUniforms* uniforms /*host*/, const Simlod
                            SimlodClusterRecord* records /*or NULL: count only*/, uint32_t* colors /*or NULL*/,
                            SimlodClusterSummary* summary, void* stream);
 
+/* ---- align queries: the rigid motion that fits one cloud onto another -------------------------------------------------------------------------
+ * simlod_align_samples is one step of a registration by ICP (iterative closest point): every sample of `a` is moved by a pose, its nearest
+ * sample of `b` within a radius is found as the compare query finds it, and over the matched pairs the call returns the exact integer sums
+ * a least-squares rigid fit needs — the two centroids, the nine cross moments and the squared residual.  The host solves the 3x3 problem
+ * (simlod_amd/octree_io.py align_solve) and calls again with the updated pose.  `b` does not move between steps, so the hash grid over it
+ * is built by the first call and REUSED by the later ones (rule A7), which launch the test pass alone.  The arrays, the box, the scratch
+ * layout and the grid's fields of the summary mean what they mean for the compare query; the scratch buffer is that query's with one more
+ * array of partial records behind it.
+ *
+ * All fp64 arithmetic runs without fused multiply-add, every sum in the order written here.  Each field is defined by its rule alone,
+ * whatever work the kernels skip.
+ *  A1. Pose.  `pose` is a 3x4 matrix T, row-major; all 12 entries must be finite or the call is refused.  For a sample c of `a`, widened
+ *      to fp64: c'_k = ((T_k0*cx + T_k1*cy) + T_k2*cz) + T_k3.  A sample of `a` is valid iff its x, y and z are finite AND all three c'_k
+ *      are finite (a product can overflow); an invalid one gets the miss record and counts in numInvalidA.  Rule C1 holds unchanged for `b`.
+ *  A2. The grid.  Rule C4 holds with gridRadius in the place of the radius: h = max((double)gridRadius * (1 + 2^-10), (double)size * 2^-20),
+ *      inv = 1.0 / h.  gridRadius must be finite and >= radius, or the call is refused: one grid serves every smaller radius, so an ICP may
+ *      tighten its radius between steps without a new build.  The cell of c' is, per axis, C4's clamp applied to t = (c'_k - min_k) * inv:
+ *      1048575 if t >= 1048575.0, (uint32_t)t if t > 0.0, else 0.  The up to 27 cells around it are searched, and that never changes rule
+ *      A3: here p = s - c' is a ROUNDED subtraction, but d2 <= rr still bounds |p_k| by r * (1 + 2^-52) (C4's argument), the true
+ *      difference is p_k * (1 + e) with |e| <= 2^-53, so |s_k - c'_k| < r * (1 + 2^-51); with r <= gridRadius the two t differ by less than
+ *      (1 + 2^-51) / (1 + 2^-10) < 1 - 2^-11 plus the roundings of the two subtractions from min and of the two products, each at most
+ *      2^-31 inside the clamp range: less than 1, so truncation puts them into the same cell or into adjacent ones, and the clamp never
+ *      moves two cells further apart.  The factor 1 + 2^-10 covers it; with h at its floor the radius is smaller still.
+ *  A3. Test and result.  p = (double)s - c' per component, d2 = (px*px + py*py) + pz*pz; a sample of `b` passes iff
+ *      d2 <= (double)radius * (double)radius.  within, nearest and d2 follow rule C3 in the order (d2, index in `b`).  The record is
+ *      SimlodCompareRecord and the miss record is the compare query's.
+ *  A4. Quantisation.  invQ = 16777216.0 / (double)size, one IEEE division made by the launcher on the host.  For a double x on axis k:
+ *      t = (x - min_k) * invQ; x is INSIDE iff t >= 0.0 && t < 16777216.0, and then Q = (uint32_t)t (24 bits).  A matched pair
+ *      (c', s = b[nearest]) is SUMMED iff all six coordinates are inside; a matched pair that is not summed counts in numOutside.
+ *  A5. Sums over the summed pairs.  numSummed is their number; sumA[k] = sum of Q(c'_k), sumB[k] = sum of Q(s_k).  For the product
+ *      P = Q(c'_k) * Q(s_l) < 2^48: crossLo[3k+l] = sum of (P & 0xffffffff), crossHi[3k+l] = sum of (P >> 32).  With
+ *      e_k = (int64)Q(s_k) - (int64)Q(c'_k) and E = (e_x*e_x + e_y*e_y) + e_z*e_z < 2^50: sqLo = sum of (E & 0xffffffff),
+ *      sqHi = sum of (E >> 32).  With fewer than 2^32 pairs no word overflows: every term is below 2^32.  The host reads hi * 2^32 + lo
+ *      as an integer of any size.
+ *  A6. Budget, count only.  Rule C6 holds with SIMLOD_ALIGN_ERR_BUDGET: no sample is tested, no record is written, and every field after
+ *      numCandidates is zero.  SIMLOD_ALIGN_COUNT_ONLY gives the grid's fields only, as rule C7 does.  records == NULL WITHOUT that flag
+ *      is a full call that writes no records: the ICP's normal case.
+ *  A7. Grid reuse.  A call without SIMLOD_ALIGN_REUSE_GRID builds the grid with the compare query's kernels and then writes a STAMP into
+ *      the unused words of the scratch buffer's header: a magic number, the pointer `b`, numB, the bits of inv and of min[3], whether the
+ *      grid records were filled (a count-only build fills none), and the grid's totals numCells, maxCellPopulation and numInvalidB.  A
+ *      call WITH the flag builds nothing; every kernel it launches compares the stamp with its own arguments before its first read of the
+ *      table.  On a mismatch — another `b` or numB, another box or gridRadius, a scratch buffer no build call stamped, a full call on a
+ *      grid a count-only build left unfilled — nothing of the table or the grid records is read, no record is written,
+ *      error = SIMLOD_ALIGN_ERR_GRID and every other field of the summary is zero.  The grid's totals of a reuse call come from the
+ *      stamp, so maxWorkgroups may differ between the calls.  The caller must not have changed `b` or the scratch buffer between the
+ *      build call and the reuse call: the stamp names the array, it does not hash it.  Every other call of this header that takes a
+ *      scratch buffer neither writes a stamp nor honours one (the compare, surface and cluster calls clear it).
+ *  A8. Refusals: below, at the call.
+ *  A9. Determinism.  Rule C8 holds; a reuse call returns the bytes a build call with the same arguments returns.
+ * A10. Identity.  With the identity pose and gridRadius == radius the records and the summary's fields up to maxD2 are those of
+ *      simlod_compare_samples, byte for byte: ((1*x + 0*y) + 0*z) + 0 == x for finite x, y and z — the product by 1 is exact, a zero
+ *      product adds nothing — so c' is the widened sample and every later operation is the compare query's.
+ * Nothing is written but `scratch`, `records` and `summary`.  `a` and `b` may be the same array. */
+#define SIMLOD_ALIGN_ERR_BUDGET  0x1u
+#define SIMLOD_ALIGN_ERR_GRID    0x2u
+#define SIMLOD_ALIGN_COUNT_ONLY  0x1u      /* flags: rule A6 */
+#define SIMLOD_ALIGN_REUSE_GRID  0x2u      /* flags: rule A7 */
+typedef struct SimlodAlignParams {     /* host memory; read completely before the call returns */
+	float    radius;                   /* finite, >= 0                                                          */
+	float    gridRadius;               /* rule A2: finite, >= radius                                            */
+	uint64_t maxCandidates;            /* rule C6; 0: no limit                                                  */
+	double   pose[12];                 /* rule A1: 3x4, row-major, finite                                       */
+	uint32_t flags;                    /* SIMLOD_ALIGN_COUNT_ONLY | SIMLOD_ALIGN_REUSE_GRID                     */
+	uint32_t maxWorkgroups;            /* 0: the library's choice; else no kernel launches more workgroups      */
+	uint32_t reserved;                 /* 0                                                                     */
+} SimlodAlignParams;
+typedef struct SimlodAlignSummary {    /* written by the device; SimlodCompareSummary's leading fields at their offsets */
+	uint32_t error;                    /* SIMLOD_ALIGN_ERR_* bits                                               */
+	uint32_t numCells;                 /* rule C4                                                               */
+	uint32_t maxCellPopulation;        /* rule C4                                                               */
+	uint32_t numInvalidA;              /* rule A1                                                               */
+	uint32_t numInvalidB;              /* rule C1                                                               */
+	uint32_t numMatched;               /* samples of `a` with within > 0                                        */
+	uint64_t numWithin;                /* the sum of within                                                     */
+	uint64_t numCandidates;            /* rule C4                                                               */
+	double   maxD2;                    /* the largest matched d2; 0 when none matched                           */
+	uint64_t numSummed;                /* rule A5                                                               */
+	uint64_t numOutside;               /* rule A4                                                               */
+	uint64_t sumA[3];                  /* rule A5                                                               */
+	uint64_t sumB[3];                  /* rule A5                                                               */
+	uint64_t crossLo[9];               /* rule A5: [3k + l], k the axis of c', l the axis of s                  */
+	uint64_t crossHi[9];               /* rule A5                                                               */
+	uint64_t sqLo;                     /* rule A5                                                               */
+	uint64_t sqHi;                     /* rule A5                                                               */
+} SimlodAlignSummary;
+SIMLOD_STATIC_ASSERT(sizeof(SimlodAlignParams) == 128, "AlignParams");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignParams, gridRadius) == 4, "AlignParams.gridRadius");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignParams, maxCandidates) == 8, "AlignParams.maxCandidates");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignParams, pose) == 16, "AlignParams.pose");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignParams, flags) == 112, "AlignParams.flags");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignParams, maxWorkgroups) == 116, "AlignParams.maxWorkgroups");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignParams, reserved) == 120, "AlignParams.reserved");
+SIMLOD_STATIC_ASSERT(sizeof(SimlodAlignSummary) == 272, "AlignSummary");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, error) == offsetof(SimlodCompareSummary, error), "AlignSummary.error");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, numCells) == offsetof(SimlodCompareSummary, numCells), "AlignSummary.numCells");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, maxCellPopulation) == offsetof(SimlodCompareSummary, maxCellPopulation), "AlignSummary.maxCellPopulation");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, numInvalidA) == offsetof(SimlodCompareSummary, numInvalidA), "AlignSummary.numInvalidA");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, numInvalidB) == offsetof(SimlodCompareSummary, numInvalidB), "AlignSummary.numInvalidB");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, numMatched) == offsetof(SimlodCompareSummary, numMatched), "AlignSummary.numMatched");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, numWithin) == offsetof(SimlodCompareSummary, numWithin), "AlignSummary.numWithin");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, numCandidates) == offsetof(SimlodCompareSummary, numCandidates), "AlignSummary.numCandidates");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, maxD2) == offsetof(SimlodCompareSummary, maxD2), "AlignSummary.maxD2");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, numSummed) == 48, "AlignSummary.numSummed");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, numOutside) == 56, "AlignSummary.numOutside");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, sumA) == 64, "AlignSummary.sumA");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, sumB) == 88, "AlignSummary.sumB");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, crossLo) == 112, "AlignSummary.crossLo");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, crossHi) == 184, "AlignSummary.crossHi");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, sqLo) == 256, "AlignSummary.sqLo");
+SIMLOD_STATIC_ASSERT(offsetof(SimlodAlignSummary, sqHi) == 264, "AlignSummary.sqHi");
+
+/* Bytes of the `scratch` buffer an align call needs: simlod_compare_buffer_min_bytes(numA, numB) and, behind that layout, the test pass's
+ * partial records of the largest grid the library ever chooses.  0 for counts the call refuses. */
+uint64_t simlod_align_buffer_min_bytes(uint64_t numA, uint64_t numB);
+
+/* The align query (rules above).  Asynchronous on `stream` once `uniforms` and `params` have been read.  hipErrorInvalidValue with nothing
+ * enqueued and nothing touched (rule A8): everything simlod_compare_samples refuses of the arguments both calls have (null pointers other
+ * than `records`, the counts, the radius, the box, the alignments — `records` at 16 bytes, `summary` at 8); a `pose` with an entry that is
+ * not finite; a gridRadius that is not finite or < radius; unknown bits in `flags`; a nonzero `reserved`; scratchBytes below
+ * simlod_align_buffer_min_bytes(numA, numB) (one byte less is refused, the exact size is accepted). */
+int simlod_align_samples(const SimlodUniforms* uniforms /*host*/, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB,
+                         const SimlodAlignParams* params /*host*/, void* scratch, uint64_t scratchBytes,
+                         SimlodCompareRecord* records /*or NULL: sums only*/, SimlodAlignSummary* summary, void* stream);
+
 /* Version / build info string (static storage). */
 const char* simlod_build_info(void);
 

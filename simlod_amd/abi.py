@@ -263,6 +263,30 @@ cluster_summary_dtype = np.dtype({"names": ["error", "numCells", "maxCellPopulat
                                   "offsets": [0, 4, 8, 12, 16, 20, 24, 32, 40, 48, 56, 64, 72, 76, 80, 344], "itemsize": 2104})
 assert cluster_record_dtype.itemsize == 16 and cluster_params_dtype.itemsize == 1056 and cluster_summary_dtype.itemsize == compare_summary_dtype.itemsize
 
+# ---- align queries (include/simlod_hip.h, "align queries") -------------------------------------------------------------------------------
+ALIGN_ERR_BUDGET, ALIGN_ERR_GRID = 0x1, 0x2
+ALIGN_COUNT_ONLY, ALIGN_REUSE_GRID = 0x1, 0x2                               # flags
+ALIGN_Q_SCALE = 16777216.0                                                  # rule A4: invQ = 2^24 / size
+align_params_dtype = np.dtype({"names": ["radius", "gridRadius", "maxCandidates", "pose", "flags", "maxWorkgroups", "reserved"],
+                               "formats": ["<f4", "<f4", "<u8", ("<f8", 12), "<u4", "<u4", "<u4"],
+                               "offsets": [0, 4, 8, 16, 112, 116, 120], "itemsize": 128})
+align_summary_dtype = np.dtype({"names": ["error", "numCells", "maxCellPopulation", "numInvalidA", "numInvalidB", "numMatched", "numWithin",
+                                          "numCandidates", "maxD2", "numSummed", "numOutside", "sumA", "sumB", "crossLo", "crossHi", "sqLo", "sqHi"],
+                                "formats": ["<u4", "<u4", "<u4", "<u4", "<u4", "<u4", "<u8", "<u8", "<f8", "<u8", "<u8", ("<u8", 3), ("<u8", 3),
+                                            ("<u8", 9), ("<u8", 9), "<u8", "<u8"],
+                                "offsets": [0, 4, 8, 12, 16, 20, 24, 32, 40, 48, 56, 64, 88, 112, 184, 256, 264], "itemsize": 272})
+assert align_params_dtype.itemsize == 128 and align_summary_dtype.itemsize == 272
+
+
+def align_prototypes(L):
+    """The ctypes prototypes of the two align entry points on the loaded library L (runtime.lib() calls it)."""
+    import ctypes
+    u64, vp = ctypes.c_uint64, ctypes.c_void_p
+    L.simlod_align_buffer_min_bytes.restype = u64
+    L.simlod_align_buffer_min_bytes.argtypes = [u64, u64]
+    L.simlod_align_samples.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp]
+
+
 # ---- lasso queries (include/simlod_hip.h, "lasso queries") -------------------------------------------------------------------------------
 LASSO_MAX_VERTICES = 256
 lasso_dtype = np.dtype({"names": ["numVertices", "reserved", "rowU", "rowV", "rowW", "vertices"],

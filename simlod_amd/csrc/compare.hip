@@ -24,7 +24,8 @@
 //                record (one 16-byte store) and colour, counts its bin in the workgroup's LDS histogram and keeps the sums in registers.
 //   k_c_final    the test pass's partial records added up -> numMatched, numWithin, maxD2, hist.  Returns at once unless `run`.
 // The surface queries (compare_surface.inc, included below) run the first six launches as they are — launch_grid — and follow them with their
-// own test pass and final; the cluster queries (compare_cluster.inc) run them with b = a and follow them with seven kernels of their own.
+// own test pass and final; the cluster queries (compare_cluster.inc) run them with b = a and follow them with seven kernels of their own; the
+// align queries (compare_align.inc) run the first four, or on a grid they built earlier none, and follow them with four kernels of their own.
 // No atomic touches global memory for the summary: every kernel writes ONE partial record per workgroup (CmpPart, its own fields of it) with
 // plain stores, as export_summary.inc does, and integer sums and maxima do not depend on the order of adding (rule C8).  d2 is never negative,
 // so the maximum of its 64 bits as an unsigned integer is the maximum of the doubles.
@@ -40,6 +41,7 @@
 #include "compare_rules.hpp"
 #include "surface_rules.hpp"
 #include "cluster_rules.hpp"
+#include "align_rules.hpp"
 
 namespace simlod {
 namespace {
@@ -467,6 +469,7 @@ void launch_grid(const CmpArgs& c, hipStream_t stream) {
 
 #include "compare_surface.inc"
 #include "compare_cluster.inc"
+#include "compare_align.inc"
 
 }  // namespace
 
@@ -529,6 +532,16 @@ uint64_t cluster_min_bytes(uint64_t numA) { return cluster_bytes(numA); }
 int launch_cluster(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA, const SimlodClusterParams* params, void* scratch, uint64_t scratchBytes,
                    SimlodClusterRecord* records, uint32_t* colors, SimlodClusterSummary* summary, hipStream_t stream) {
 	return launch_cluster_impl(u, a, numA, params, scratch, scratchBytes, records, colors, summary, stream);
+}
+
+uint64_t align_min_bytes(uint64_t numA, uint64_t numB) {
+	return compare_count_acceptable(numA) && compare_count_acceptable(numB) ? align_bytes(numB) : 0u;
+}
+
+// simlod_align_samples: compare_align.inc's launcher.
+int launch_align(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB, const SimlodAlignParams* params,
+                 void* scratch, uint64_t scratchBytes, SimlodCompareRecord* records, SimlodAlignSummary* summary, hipStream_t stream) {
+	return launch_align_impl(u, a, numA, b, numB, params, scratch, scratchBytes, records, summary, stream);
 }
 
 }  // namespace simlod

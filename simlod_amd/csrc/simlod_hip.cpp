@@ -648,6 +648,14 @@ int simlod_cluster_samples(const SimlodUniforms* uniforms, const SimlodPoint* a,
 	return launch_cluster(uniforms, a, numA, params, scratch, scratchBytes, records, colors, summary, (hipStream_t)stream);
 }
 
+uint64_t simlod_align_buffer_min_bytes(uint64_t numA, uint64_t numB) { return align_min_bytes(numA, numB); }
+
+int simlod_align_samples(const SimlodUniforms* uniforms, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB,
+                         const SimlodAlignParams* params, void* scratch, uint64_t scratchBytes, SimlodCompareRecord* records,
+                         SimlodAlignSummary* summary, void* stream) {
+	return launch_align(uniforms, a, numA, b, numB, params, scratch, scratchBytes, records, summary, (hipStream_t)stream);
+}
+
 uint64_t simlod_rays_buffer_min_bytes(uint32_t nodeCapacity, uint64_t sampleBound, uint32_t numRays, uint64_t numPairs, uint64_t numCandidates) {
 	return rays_min_bytes(nodeCapacity, sampleBound, numRays, numPairs, numCandidates);
 }

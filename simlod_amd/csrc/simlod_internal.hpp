@@ -235,6 +235,9 @@ int launch_surface(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA,
 int launch_cluster(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA, const SimlodClusterParams* params, void* scratch, uint64_t scratchBytes,
                    SimlodClusterRecord* records, uint32_t* colors, SimlodClusterSummary* summary, hipStream_t stream);
 uint64_t cluster_min_bytes(uint64_t numA);
+int launch_align(const SimlodUniforms* u, const SimlodPoint* a, uint64_t numA, const SimlodPoint* b, uint64_t numB, const SimlodAlignParams* params,
+                 void* scratch, uint64_t scratchBytes, SimlodCompareRecord* records, SimlodAlignSummary* summary, hipStream_t stream);
+uint64_t align_min_bytes(uint64_t numA, uint64_t numB);
 int launch_rays(Context& ctx, const SimlodNode* nodes, const SimlodStats* stats, const SimlodUniforms* u, const SimlodRay* rays, uint32_t numRays,
                 uint32_t maxLevel, uint32_t select, void* scratch, uint64_t scratchBytes, SimlodExportNode* table, uint32_t tableCapacity,
                 SimlodRayHit* hits, SimlodRayCounts* counts, hipStream_t stream);

@@ -680,6 +680,14 @@ def cell20(x, box_min, inv):
         return np.where(t >= top, top, np.where(t > 0.0, t, 0.0)).astype(np.uint64)
 
 
+def cell20_f64(x, box_min, inv):
+    """cell20 for float64 coordinates (align_rules.hpp align_cell20, rule A2): the same clamp on t = (x - boxMin) * inv."""
+    top = np.float64(abi.SUMMARY_CELLS - 1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = (np.asarray(x, np.float64) - np.float64(box_min)) * np.float64(inv)
+        return np.where(t >= top, top, np.where(t > 0.0, t, 0.0)).astype(np.uint64)
+
+
 def _box_of(box_min, box_max):
     """(min as float64, size): the box as construct.hip derives it — the largest of the fp32 differences boxMax - boxMin."""
     mn32, mx32 = np.asarray(box_min, np.float32), np.asarray(box_max, np.float32)
@@ -1497,20 +1505,29 @@ def compare_cells(points, box_min, inv):
     return valid, keys
 
 
-def _compare_pairs(a, b, uniforms_box, radius, max_candidates, count_only, summary_dtype):
+def _compare_pairs(a, b, uniforms_box, radius, max_candidates, count_only, summary_dtype, centres=None, grid_radius=None):
     """What compare_samples and surface_samples share (rules C1, C2, C4, C6, C7): the grid over b's valid samples, the grid's fields of a
     summary record of `summary_dtype` (both summaries keep them, and the budget's error bit, in the same places), and every pair (i, j) of a
     sample of a and a sample of b from its up to 27 cells that passes rule C2 -> (a, b, the record, (pi, pj, [px, py, pz], d2)); the pairs are
-    None for a count-only call and when the budget is exceeded."""
+    None for a count-only call and when the budget is exceeded.  align_samples passes `centres` — (which samples of a are valid, their
+    three float64 coordinate arrays: rule A1's c', held against b in the place of a's own positions) — and `grid_radius` (rule A2: the cell
+    size comes from it, the test from `radius`)."""
     a, b = np.asarray(a, dtype=abi.point_dtype).reshape(-1), np.asarray(b, dtype=abi.point_dtype).reshape(-1)
     if not (0 < len(a) <= abi.COMPARE_MAX_COUNT and 0 < len(b) <= abi.COMPARE_MAX_COUNT):
         raise ValueError("numA and numB are 1 .. 2^32 - 2")
     mn, size = _box_of(*uniforms_box)
     if not (np.isfinite(mn).all() and np.isfinite(size) and size > 0):
         raise ValueError("the box needs a finite corner and a finite extent > 0")
-    inv = np.float64(1.0) / compare_h(radius, size)
+    inv = np.float64(1.0) / compare_h(radius if grid_radius is None else grid_radius, size)
     rr = np.float64(radius) * np.float64(radius)
-    va, ka = compare_cells(a, mn, inv)
+    if centres is None:
+        va, ka = compare_cells(a, mn, inv)
+        ctr = [a[name].astype(np.float64) for name in ("x", "y", "z")]
+    else:
+        va, ctr = centres
+        ka = np.zeros(len(a), np.uint64)
+        for k in range(3):
+            ka |= np.where(va, cell20_f64(ctr[k], mn[k], inv), np.uint64(0)) << np.uint64(20 * k)
     vb, kb = compare_cells(b, mn, inv)
     out = np.zeros((), dtype=summary_dtype)
     out["numInvalidA"], out["numInvalidB"] = int((~va).sum()), int((~vb).sum())
@@ -1544,7 +1561,7 @@ def _compare_pairs(a, b, uniforms_box, radius, max_candidates, count_only, summa
     # every candidate pair (i, j), then rule C2
     pi = np.repeat(who, count)
     pj = ib[np.repeat(start, count) + (np.arange(len(pi)) - np.repeat(np.cumsum(count) - count, count))]
-    d = [b[name][pj].astype(np.float64) - a[name][pi].astype(np.float64) for name in ("x", "y", "z")]
+    d = [b[name][pj].astype(np.float64) - ctr[k][pi] for k, name in enumerate(("x", "y", "z"))]
     d2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
     ok = d2 <= rr
     return a, b, out, (pi[ok], pj[ok], [v[ok] for v in d], d2[ok])
@@ -1986,6 +2003,245 @@ class ClusterResult:
             raise ValueError("only a cluster_region(max_level=20, select='all') result is in the order paint_region takes")
         return dev.paint_region(uniforms, s["region"], Paint.array(), footprint=s["footprint"], colors=self.colors, return_previous=return_previous,
                                 lasso=s["lasso"], invert=s["invert"])
+
+
+IDENTITY_POSE = np.hstack([np.eye(3), np.zeros((3, 1))])
+
+
+def _pose(pose):
+    """A pose as a 3x4 float64 matrix (None: the identity); its entries are finite."""
+    T = IDENTITY_POSE.copy() if pose is None else np.array(pose, dtype=np.float64).reshape(3, 4)
+    if not np.isfinite(T).all():
+        raise ValueError("a pose is a 3x4 matrix of finite entries")
+    return T
+
+
+class Align:
+    """The parameters of an align query (include/simlod_hip.h, "align queries"; abi.align_params_dtype) that stay the same over the steps of
+    a registration: the radius and the grid's radius (both float32; grid_radius None: the radius — rule A2: one grid serves every radius up
+    to grid_radius), the candidate budget of rule C6 (max_candidates as Compare's: None the device entry points' default of 64 per sample
+    of A, 0 no limit) and max_workgroups.  The pose and the flags change from call to call and go into record()."""
+
+    def __init__(self, radius, grid_radius=None, max_candidates=None, max_workgroups=0):
+        with np.errstate(over="ignore"):
+            self.radius = np.float32(radius)
+            self.grid_radius = self.radius if grid_radius is None else np.float32(grid_radius)
+        self.max_workgroups = int(max_workgroups)
+        self.max_candidates = None if max_candidates is None else int(max_candidates)
+        if not (np.isfinite(self.radius) and self.radius >= 0):
+            raise ValueError("an align query needs a finite radius >= 0 (as float32)")
+        if not (np.isfinite(self.grid_radius) and self.grid_radius >= self.radius):
+            raise ValueError("the grid's radius is finite and >= the radius (as float32)")
+        if self.max_candidates is not None and self.max_candidates < 0:
+            raise ValueError("a budget is not negative")
+
+    @classmethod
+    def from_record(cls, record):
+        r = np.asarray(record, dtype=abi.align_params_dtype).reshape(-1)[0]
+        return cls(r["radius"], r["gridRadius"], int(r["maxCandidates"]), int(r["maxWorkgroups"]))
+
+    def __eq__(self, other):
+        return isinstance(other, Align) and self.record(None).tobytes() == other.record(None).tobytes()
+
+    def with_radius(self, radius):
+        """The same grid with a smaller test radius: what an ICP that tightens its radius passes to its later, reusing steps."""
+        return Align(radius, self.grid_radius, self.max_candidates, self.max_workgroups)
+
+    def record(self, pose, flags=0, max_candidates=None):
+        """The SimlodAlignParams the C ABI takes (abi.align_params_dtype, one record) for one call: pose a 3x4 matrix (None: the identity),
+        flags of abi.ALIGN_COUNT_ONLY and abi.ALIGN_REUSE_GRID; max_candidates overrides the object's."""
+        r = np.zeros(1, dtype=abi.align_params_dtype)
+        budget = self.max_candidates if max_candidates is None else int(max_candidates)
+        r["radius"], r["gridRadius"], r["maxCandidates"], r["maxWorkgroups"] = self.radius, self.grid_radius, budget or 0, self.max_workgroups
+        r["pose"][0], r["flags"] = _pose(pose).reshape(-1), int(flags)
+        return r
+
+
+def align_pose_points(points, pose):
+    """Rule A1 for an array of abi.point_dtype: (valid, [c'x, c'y, c'z] as float64) — c'_k = ((T_k0*cx + T_k1*cy) + T_k2*cz) + T_k3; valid
+    iff x, y and z are finite and all three c'_k are."""
+    T = _pose(pose)
+    c = [points[name].astype(np.float64) for name in ("x", "y", "z")]
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = [((T[k, 0] * c[0] + T[k, 1] * c[1]) + T[k, 2] * c[2]) + T[k, 3] for k in range(3)]
+    valid = np.isfinite(c[0]) & np.isfinite(c[1]) & np.isfinite(c[2]) & np.isfinite(out[0]) & np.isfinite(out[1]) & np.isfinite(out[2])
+    return valid, out
+
+
+def align_q(x, box_min, invq):
+    """Rule A4 on one axis: (inside, Q as uint64; 0 where outside) of float64 coordinates."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = (np.asarray(x, np.float64) - np.float64(box_min)) * np.float64(invq)
+    inside = (t >= 0.0) & (t < abi.ALIGN_Q_SCALE)
+    return inside, np.where(inside, t, 0.0).astype(np.uint64)
+
+
+def align_samples(a, b, uniforms_box, align, pose, count_only=False):
+    """The host mirror of simlod_align_samples (include/simlod_hip.h, "align queries"): a, b arrays of abi.point_dtype, uniforms_box the
+    (box_min, box_max) of the uniforms, align an Align, pose a 3x4 matrix (None: the identity) -> (records as abi.compare_record_dtype, the
+    summary as one abi.align_summary_dtype record); count_only, or a budget exceeded (rule A6): the records are None.  The grid, the
+    candidates and the test are _compare_pairs', the compare mirror's, with the posed centres in the place of a's positions; rules A4 and
+    A5 in numpy float64 and unsigned 64-bit integers.  A grid is never reused here: a reuse call returns a build call's bytes (rule A9)."""
+    a = np.asarray(a, dtype=abi.point_dtype).reshape(-1)
+    va, ctr = align_pose_points(a, pose)
+    a, b, out, pairs = _compare_pairs(a, b, uniforms_box, align.radius, align.max_candidates, count_only, abi.align_summary_dtype,
+                                      centres=(va, ctr), grid_radius=align.grid_radius)
+    if pairs is None:
+        return None, out
+    pi, pj, _, d2 = pairs
+    rec = np.zeros(len(a), dtype=abi.compare_record_dtype)
+    rec["d2"], rec["nearest"] = np.inf, abi.COMPARE_MISS
+    rec["within"] = np.bincount(pi, minlength=len(a))
+    order = np.lexsort((pj, d2, pi))                                        # rule C3: per sample the first in (d2, index)
+    lead = order[np.r_[True, pi[order][1:] != pi[order][:-1]]] if len(order) else order
+    rec["d2"][pi[lead]], rec["nearest"][pi[lead]] = d2[lead], pj[lead]
+    matched = rec["within"] != 0
+    out["numMatched"], out["numWithin"] = int(matched.sum()), int(rec["within"].sum(dtype=np.uint64))
+    out["maxD2"] = rec["d2"][matched].max() if matched.any() else 0.0
+    # rules A4, A5 over the matched pairs (c', b[nearest])
+    mn, size = _box_of(*uniforms_box)
+    invq = np.float64(abi.ALIGN_Q_SCALE) / size
+    i, j = np.flatnonzero(matched), rec["nearest"][matched].astype(np.int64)
+    inside = np.ones(len(i), bool)
+    qa, qb = [], []
+    for k, name in enumerate(("x", "y", "z")):
+        ia, q = align_q(ctr[k][i], mn[k], invq)
+        ib, r = align_q(b[name][j].astype(np.float64), mn[k], invq)
+        inside &= ia & ib
+        qa.append(q); qb.append(r)
+    qa, qb = [q[inside] for q in qa], [q[inside] for q in qb]
+    out["numSummed"], out["numOutside"] = int(inside.sum()), int((~inside).sum())
+    lo, total = np.uint64(0xFFFFFFFF), lambda v: int(v.sum(dtype=np.uint64))
+    for k in range(3):
+        out["sumA"][k], out["sumB"][k] = total(qa[k]), total(qb[k])
+        for l in range(3):
+            P = qa[k] * qb[l]                                               # < 2^48
+            out["crossLo"][3 * k + l], out["crossHi"][3 * k + l] = total(P & lo), total(P >> np.uint64(32))
+    e = [qb[k].astype(np.int64) - qa[k].astype(np.int64) for k in range(3)]
+    E = ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]).astype(np.uint64)      # < 2^50
+    out["sqLo"], out["sqHi"] = total(E & lo), total(E >> np.uint64(32))
+    return rec, out
+
+
+def align_solve(summary, box_min, size):
+    """The host's half of an ICP step: the least-squares rigid motion that takes the summed pairs' posed samples of A onto their nearest
+    samples of B, from one abi.align_summary_dtype record -> (update: a 3x4 float64 matrix, rms: the pairs' root mean square distance
+    before the update, in the box's units), or None with fewer than 3 summed pairs or a second singular value of 0 (the pairs span no
+    plane: the rotation is not determined).  N[k][l] = n * cross[k][l] - sumA[k] * sumB[l] is formed in Python integers — exact: n^2 times
+    the cross-covariance of the quantised coordinates — and converted to float64 once; numpy.linalg.svd of it, the rotation
+    R = V diag(1, 1, det(V U^T)) U^T, the centroids min + (sum / n + 0.5) / invQ (the half step undoes the truncation's bias) and
+    t = mu_b - R mu_a."""
+    s = np.asarray(summary, dtype=abi.align_summary_dtype).reshape(-1)[0]
+    n = int(s["numSummed"])
+    if n < 3:
+        return None
+    sum_a, sum_b = [int(v) for v in s["sumA"]], [int(v) for v in s["sumB"]]
+    cross = [(int(h) << 32) + int(l) for l, h in zip(s["crossLo"], s["crossHi"])]
+    N = np.array([[float(n * cross[3 * k + l] - sum_a[k] * sum_b[l]) for l in range(3)] for k in range(3)], dtype=np.float64)
+    scale = np.abs(N).max()
+    if scale == 0.0:
+        return None
+    U, S, Vt = np.linalg.svd(N / scale)
+    if not S[1] > 0.0:
+        return None
+    D = np.diag([1.0, 1.0, 1.0 if np.linalg.det(Vt.T @ U.T) >= 0.0 else -1.0])
+    R = Vt.T @ D @ U.T
+    invq = np.float64(abi.ALIGN_Q_SCALE) / np.float64(np.float32(size))
+    mn = np.asarray(box_min, np.float32).astype(np.float64)
+    mu_a = mn + (np.array([v / n for v in sum_a]) + 0.5) / invq
+    mu_b = mn + (np.array([v / n for v in sum_b]) + 0.5) / invq
+    sq = (int(s["sqHi"]) << 32) + int(s["sqLo"])
+    return np.hstack([R, (mu_b - R @ mu_a).reshape(3, 1)]), float(np.sqrt(sq / n) / invq)
+
+
+def compose_pose(update, pose):
+    """The pose that applies `pose` first and `update` after it, in float64: [Ru Rp | Ru tp + tu]."""
+    u, p = _pose(update), _pose(pose)
+    return np.hstack([u[:, :3] @ p[:, :3], (u[:, :3] @ p[:, 3] + u[:, 3]).reshape(3, 1)])
+
+
+def _pose_corners(pose, corners):
+    return corners @ pose[:, :3].T + pose[:, 3]
+
+
+class AlignResult:
+    """What a registration returns: `pose`, the 3x4 float64 matrix that takes A onto B; `summaries`, the abi.align_summary_dtype record of
+    every step (host); `rms`, the summed pairs' root mean square distance at every solved step, measured BEFORE that step's update;
+    `converged`: the last update moved no corner of A's bounding box by more than the tolerance.  register_region adds `a`, `b` (the
+    OctreeExports) and `selection`."""
+
+    def __init__(self, pose, summaries, rms, converged):
+        self.pose, self.summaries, self.rms, self.converged = pose, summaries, rms, converged
+        self.a = self.b = self.selection = None
+
+    @property
+    def steps(self):
+        return len(self.summaries)
+
+    def transform(self, samples):
+        """The 16-byte samples with their positions moved by the pose — rule A1 in float64, rounded to float32 — and their colours kept: a
+        torch tensor of whole records (any dtype, any device) gives a uint8 tensor on its device, anything else a numpy array of
+        abi.point_dtype."""
+        T = self.pose
+        try:
+            import torch
+        except ImportError:
+            torch = None
+        if torch is not None and isinstance(samples, torch.Tensor):
+            raw = samples.reshape(-1).view(torch.uint8).contiguous().clone()
+            f = raw.view(torch.float32).reshape(-1, 4)
+            c = [f[:, k].double() for k in range(3)]
+            for k in range(3):
+                f[:, k] = (((T[k, 0] * c[0] + T[k, 1] * c[1]) + T[k, 2] * c[2]) + T[k, 3]).float()
+            return raw
+        out = np.array(np.asarray(samples, dtype=abi.point_dtype).reshape(-1), copy=True)
+        c = [out[name].astype(np.float64) for name in ("x", "y", "z")]
+        with np.errstate(invalid="ignore", over="ignore"):
+            for k, name in enumerate(("x", "y", "z")):
+                out[name] = (((T[k, 0] * c[0] + T[k, 1] * c[1]) + T[k, 2] * c[2]) + T[k, 3]).astype(np.float32)
+        return out
+
+
+def register_steps(step, box_min, size, corners, pose=None, iterations=30, tol=None):
+    """The ICP loop both register_samples (here, on the mirror) and DeviceOctree.register_samples (on the device) run: step(pose, first)
+    -> one abi.align_summary_dtype record; align_solve; compose_pose; until the update moves none of `corners` (the 8 corners of A's
+    bounding box, under the pose so far) by more than tol (None: size * 2^-22) or `iterations` steps are done.  A step that reports an
+    error bit or that align_solve cannot solve ends the loop unconverged.  -> an AlignResult."""
+    pose = _pose(pose)
+    tol = float(np.float32(size)) * 2.0 ** -22 if tol is None else float(tol)
+    corners = np.asarray(corners, np.float64).reshape(-1, 3)
+    summaries, rms, converged = [], [], False
+    for it in range(int(iterations)):
+        s = step(pose, it == 0)
+        summaries.append(s)
+        solved = None if int(s["error"]) != 0 else align_solve(s, box_min, size)
+        if solved is None:
+            break
+        rms.append(solved[1])
+        now = _pose_corners(pose, corners)
+        moved = np.abs(_pose_corners(solved[0], now) - now).max() if len(corners) else 0.0
+        pose = compose_pose(solved[0], pose)
+        if moved <= tol:
+            converged = True
+            break
+    return AlignResult(pose, summaries, rms, converged)
+
+
+def bounding_corners(points):
+    """The 8 corners of the bounding box of the finite samples of an abi.point_dtype array (none finite: no corner)."""
+    p = np.asarray(points, dtype=abi.point_dtype).reshape(-1)
+    ok = np.isfinite(p["x"]) & np.isfinite(p["y"]) & np.isfinite(p["z"])
+    if not ok.any():
+        return np.zeros((0, 3))
+    lo, hi = ([float(f(p[name][ok])) for name in ("x", "y", "z")] for f in (np.min, np.max))
+    return np.array([[(lo, hi)[i >> k & 1][k] for k in range(3)] for i in range(8)], dtype=np.float64)
+
+
+def register_samples(a, b, uniforms_box, align, pose=None, iterations=30, tol=None):
+    """The registration of a onto b on the host mirror: register_steps over align_samples.  -> an AlignResult."""
+    mn, size = _box_of(*uniforms_box)
+    step = lambda T, first: align_samples(a, b, uniforms_box, align, T)[1]
+    return register_steps(step, mn, size, bounding_corners(a), pose, iterations, tol)
 
 
 class Footprint:

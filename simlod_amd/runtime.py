@@ -144,6 +144,7 @@ def lib():
         L.simlod_cluster_buffer_min_bytes.restype = u64
         L.simlod_cluster_buffer_min_bytes.argtypes = [u64]
         L.simlod_cluster_samples.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]
+        abi.align_prototypes(L)
         _lib = L
     return _lib
 
@@ -173,6 +174,7 @@ EXPORTED_SYMBOLS = [
     "simlod_compare_buffer_min_bytes", "simlod_compare_table_slots", "simlod_compare_samples",
     "simlod_surface_buffer_min_bytes", "simlod_surface_samples",
     "simlod_cluster_buffer_min_bytes", "simlod_cluster_samples",
+    "simlod_align_buffer_min_bytes", "simlod_align_samples",
 ]
 
 
@@ -1089,6 +1091,93 @@ class DeviceOctree:
         if int(s["error"]) != 0:
             raise SimlodError(f"simlod_cluster_samples reported error bits {int(s['error']):#x}; no record is valid")
         return ClusterResult(a, records, colors, s, cluster, sel)
+
+    # -- align queries (include/simlod_hip.h, "align queries") -----------------------------------------------------------------------------
+    def align_scratch(self, a, b):
+        """A scratch buffer of its own for align calls on `a` and `b` (sample arrays as compare_samples takes them, or their counts): the
+        one a build call stamps and later reuse calls must be given unchanged (rule A7)."""
+        na, nb = (v if isinstance(v, int) else self._samples_tensor(v).numel() // abi.point_dtype.itemsize for v in (a, b))
+        need = int(self.L.simlod_align_buffer_min_bytes(na, nb))
+        if need == 0:
+            raise ValueError("numA and numB are 1 .. 2^32 - 2")
+        return torch.empty(need, dtype=torch.uint8, device=self.device)
+
+    def align_samples(self, uniforms, a, b, align, pose, scratch=None, reuse=False, records=False, count_only=False, max_candidates=None):
+        """One simlod_align_samples call on two sample arrays (as compare_samples takes them; pass the SAME device tensor for `b` to every
+        call that shares a grid): the samples of `a` moved by `pose` (3x4; None: the identity) against their nearest samples of `b` within
+        align.radius.  -> (records: a uint8 tensor of abi.compare_record_dtype records on this device, or None unless records=True, and the
+        abi.align_summary_dtype record on the host).  scratch: a buffer of align_scratch(a, b) (None: the octree's shared one, which the
+        next query overwrites); reuse=True: the grid an earlier call built in `scratch` is reused (rule A7) — a grid that does not serve
+        comes back as SIMLOD_ALIGN_ERR_GRID in the record's error field.  count_only: the grid's fields only.  The call ALWAYS carries a
+        candidate budget, compare_samples' (rule C6): max_candidates if given, else align.max_candidates, else 64 candidates per sample of
+        `a`; an explicit 0 is the opt-out.  With an error bit set no record was written: (None, record)."""
+        u, up = self._u(uniforms)
+        ta, tb = self._samples_tensor(a), self._samples_tensor(b)
+        na, nb = ta.numel() // abi.point_dtype.itemsize, tb.numel() // abi.point_dtype.itemsize
+        budget = max_candidates if max_candidates is not None else align.max_candidates
+        flags = (abi.ALIGN_COUNT_ONLY if count_only else 0) | (abi.ALIGN_REUSE_GRID if reuse else 0)
+        pr = align.record(pose, flags, self.COMPARE_BUDGET_PER_SAMPLE * na if budget is None else int(budget))
+        need = int(self.L.simlod_align_buffer_min_bytes(na, nb))
+        if need == 0:
+            raise ValueError("numA and numB are 1 .. 2^32 - 2")
+        if scratch is None:
+            if reuse:
+                raise ValueError("a reuse call needs the scratch buffer of the call that built the grid")
+            scratch = self._export_scratch(need)
+        out = torch.zeros(abi.align_summary_dtype.itemsize, dtype=torch.uint8, device=self.device)
+        rec_t = torch.empty(na * abi.compare_record_dtype.itemsize, dtype=torch.uint8, device=self.device) if records and not count_only else None
+        _check(self.L.simlod_align_samples(up, self._p(ta), ctypes.c_uint64(na), self._p(tb), ctypes.c_uint64(nb), ctypes.c_void_p(pr.ctypes.data),
+                                           self._p(scratch), ctypes.c_uint64(scratch.numel()), None if rec_t is None else self._p(rec_t), self._p(out),
+                                           self._stream()), "simlod_align_samples")
+        rec = out.cpu().numpy().view(abi.align_summary_dtype)[0]
+        return (None, rec) if int(rec["error"]) != 0 else (rec_t, rec)
+
+    def register_samples(self, uniforms, a, b, align, pose=None, iterations=30, tol=None):
+        """The registration of `a` onto `b` by ICP -> an octree_io.AlignResult: one scratch buffer (the octree's shared one, every
+        query's: a first call pays for its allocation, which for gigabytes costs more than the steps), the first simlod_align_samples call builds the grid over `b` and every
+        later one reuses it; each step reads its summary (one synchronisation), solves for the update on
+        the host (octree_io.align_solve) and composes it into the pose.  It stops when the update moves no corner of A's bounding box by
+        more than tol (None: size * 2^-22) or after `iterations` steps.  No record is written.  A step that reports an error bit raises
+        SimlodError naming it."""
+        from .octree_io import register_steps, _box_of
+        u, _ = self._u(uniforms)
+        ta, tb = self._samples_tensor(a), self._samples_tensor(b)
+        mn, size = _box_of(u["boxMin"][0], u["boxMax"][0])
+        xyz = ta.view(torch.float32).reshape(-1, 4)[:, :3]
+        ok = torch.isfinite(xyz).all(dim=1, keepdim=True)
+        inf = torch.tensor(float("inf"), device=self.device)
+        lo, hi = torch.where(ok, xyz, inf).amin(dim=0).cpu().numpy().astype(np.float64), torch.where(ok, xyz, -inf).amax(dim=0).cpu().numpy().astype(np.float64)
+        corners = np.array([[(lo, hi)[i >> k & 1][k] for k in range(3)] for i in range(8)]) if np.isfinite(lo).all() else np.zeros((0, 3))
+        need = int(self.L.simlod_align_buffer_min_bytes(ta.numel() // abi.point_dtype.itemsize, tb.numel() // abi.point_dtype.itemsize))
+        if need == 0:
+            raise ValueError("numA and numB are 1 .. 2^32 - 2")
+        scratch = self._export_scratch(need)                                    # (no other query runs on this octree between the steps)
+        step = lambda T, first: self.align_samples(uniforms, ta, tb, align, T, scratch=scratch, reuse=not first)[1]
+        res = register_steps(step, mn, size, corners, pose, iterations, tol)
+        err = int(res.summaries[-1]["error"]) if res.summaries else 0
+        if err != 0:
+            s = res.summaries[-1]
+            raise SimlodError(f"simlod_align_samples reported error bits {err:#x} at step {res.steps} (numCandidates = {int(s['numCandidates'])}, "
+                              f"maxCellPopulation = {int(s['maxCellPopulation'])}): pick a smaller radius or a coarser cut of the other cloud")
+        return res
+
+    def count_align(self, uniforms, other, region, align, pose=None, max_level=None, select="cut", footprint=None, lasso=None, invert=False,
+                    other_max_level=None, other_select="cut"):
+        """What a step of register_region would cost: the abi.align_summary_dtype record of the count-only call (numCells, maxCellPopulation,
+        numCandidates, the invalid counts) for the same arguments under `pose`; nothing is tested and no budget applies."""
+        a, b, _ = self._compare_inputs(uniforms, other, region, max_level, select, footprint, lasso, invert, other_max_level, other_select)
+        return self.align_samples(uniforms, a, b, align, pose, count_only=True, max_candidates=0)[1]
+
+    def register_region(self, uniforms, other, region, align, pose=None, iterations=30, tol=None, max_level=None, select="cut", footprint=None,
+                        lasso=None, invert=False, other_max_level=None, other_select="cut"):
+        """The registration of a selection of THIS octree onto `other` (a DeviceOctree on this device): A = query_region(region, max_level,
+        select, footprint / lasso / invert), B = other.export_octree(other_max_level, other_select), as compare_region selects them, then
+        register_samples -> its octree_io.AlignResult with `a`, `b` and `selection` filled in.  AlignResult.transform(result.a.samples_tensor)
+        gives the moved samples; neither octree is changed."""
+        a, b, sel = self._compare_inputs(uniforms, other, region, max_level, select, footprint, lasso, invert, other_max_level, other_select)
+        res = self.register_samples(uniforms, a, b, align, pose, iterations, tol)
+        res.a, res.b, res.selection = a, b, sel
+        return res
 
     # -- profile queries (include/simlod_hip.h, "profile queries") -------------------------------------------------------------------------
     def _profile(self, uniforms, profile, region, ml, sel, table, samples, records, sample_capacity, bound):

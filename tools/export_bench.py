@@ -50,7 +50,9 @@ the device-to-device copy — and, for scale, the same positions through simlod_
 another radius, for cells of hundreds or thousands of samples, without that yardstick.
 --compare-whole: the same with A = B = the full export.  --compare-workgroups N: SimlodCompareParams.maxWorkgroups for either.  --surface: with
 either, simlod_surface_samples on the same arrays at the same radius as well, alternating with the compare call, and its kernels.  --cluster: with
-either, simlod_cluster_samples on A alone at the same radius with minNeighbours 1 and 8, beside simlod_compare_samples(A, A), and its kernels."""
+either, simlod_cluster_samples on A alone at the same radius with minNeighbours 1 and 8, beside simlod_compare_samples(A, A), and its kernels.
+--align: with either, simlod_align_samples on the same arrays at the same radius under a small motion: a build call and a reuse call beside the
+compare call, their kernels, and a 20-step DeviceOctree.register_samples beside 20 compare calls."""
 import argparse
 import ctypes
 import json
@@ -724,7 +726,7 @@ def neighbours_bench(dev, u, box, st, reps, pts):
     print(json.dumps(out))
 
 
-def compare_bench(dev, u, box, st, reps, pts, whole=False, workgroups=0, radius_arg=None, surface=False, cluster=False):
+def compare_bench(dev, u, box, st, reps, pts, whole=False, workgroups=0, radius_arg=None, surface=False, cluster=False, align=False):
     """simlod_compare_samples: A = the CUT@20 selection of a box of 1/36 of the plan area (about 1 M samples), B = the octree's full CUT@20
     export, at --neighbours' radius of DESIGN §11 (2.167)."""
     from simlod_amd import fingerprint
@@ -819,6 +821,62 @@ def compare_bench(dev, u, box, st, reps, pts, whole=False, workgroups=0, radius_
                           "Msamples_per_s": round(na / (tss[0][0] * 1e3), 1)}
         if "k_s_test" in kernels and "k_c_test" in out["kernels_ms"]:
             out["surface"]["k_s_test_over_k_c_test"] = round(kernels["k_s_test"] / out["kernels_ms"]["k_c_test"], 3)
+    if align:
+        # simlod_align_samples on the same two arrays at the same radius under a small motion: a build call and a reuse call (no records: the ICP's
+        # calls), alternating rep by rep with the compare call; each call's kernels from one call between the library's own events; and a
+        # 20-step DeviceOctree.register_samples (its summaries read back, its updates solved on the host) beside 20 compare calls: ONE
+        # wall-clock sample each, the host's solves included, after a registration of one step that warms the scratch buffer
+        import time
+        import bench
+        from simlod_amd.octree_io import Align
+        al = Align(radius, max_candidates=0, max_workgroups=workgroups)
+        centre = (b[0] * 0.5, b[1] * 0.5, b[2] * 0.5)
+        ang = np.deg2rad(0.05)
+        R = np.array([[np.cos(ang), -np.sin(ang), 0.0], [np.sin(ang), np.cos(ang), 0.0], [0.0, 0.0, 1.0]])
+        pose = np.hstack([R, (np.asarray(centre) - R @ np.asarray(centre) + np.array([0.3, -0.2, 0.1]) * radius).reshape(3, 1)])
+        a_need = int(L.simlod_align_buffer_min_bytes(na, nb))
+        a_scratch = torch.empty(a_need, dtype=torch.uint8, device=dev.device)
+        a_summary = torch.zeros(abi.align_summary_dtype.itemsize, dtype=torch.uint8, device=dev.device)
+        recs = {False: al.record(pose, 0, 0), True: al.record(pose, abi.ALIGN_REUSE_GRID, 0)}
+
+        def acall(reuse):
+            rc = L.simlod_align_samples(up, p(ta), ctypes.c_uint64(na), p(tb), ctypes.c_uint64(nb), ctypes.c_void_p(recs[reuse].ctypes.data), p(a_scratch),
+                                        ctypes.c_uint64(a_need), None, p(a_summary), stream)
+            assert rc == 0
+        acall(False)
+        torch.cuda.synchronize()
+        built = a_summary.cpu().numpy().view(abi.align_summary_dtype)[0].copy()
+        tas = timed_alternating([lambda: acall(False), lambda: acall(True), lambda: call()], reps)
+        acall(True)
+        torch.cuda.synchronize()
+        reused = a_summary.cpu().numpy().view(abi.align_summary_dtype)[0].copy()
+        assert int(built["error"]) == 0 and reused.tobytes() == built.tobytes()
+        kernels = {}
+        for name, reuse in (("build", False), ("reuse", True)):
+            L.simlod_profile_enable(1)
+            acall(reuse)
+            torch.cuda.synchronize()
+            prof = bench.collect_profile(L)
+            L.simlod_profile_enable(0)
+            kernels[name] = {k: round(ms, 4) for k, (n, ms) in prof.items() if k.startswith("k_c_") or k.startswith("k_a_")}
+        out["align"] = {"scratch_bytes": a_need, "build_ms": round(tas[0][0], 4), "build_ms_min": round(tas[0][1], 4), "reuse_ms": round(tas[1][0], 4),
+                        "reuse_ms_min": round(tas[1][1], 4), "compare_ms_beside_it": round(tas[2][0], 4), "reuse_over_build": round(tas[1][0] / tas[0][0], 4),
+                        "kernels_ms": kernels, "numMatched": int(built["numMatched"]), "numSummed": int(built["numSummed"]), "numOutside": int(built["numOutside"])}
+        if "k_a_test" in kernels["reuse"] and "k_c_test" in out["kernels_ms"]:
+            out["align"]["k_a_test_over_k_c_test"] = round(kernels["reuse"]["k_a_test"] / out["kernels_ms"]["k_c_test"], 3)
+        dev.register_samples(u, ta, tb, al, pose=pose, iterations=1)           # (warm: the octree's shared scratch buffer grows to the size once)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = dev.register_samples(u, ta, tb, al, pose=pose, iterations=20, tol=0.0)
+        torch.cuda.synchronize()
+        t_reg = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        for _ in range(20):
+            call()
+        torch.cuda.synchronize()
+        t_cmp = (time.perf_counter() - t0) * 1e3
+        out["align"]["register_20"] = {"steps": res.steps, "ms": round(t_reg, 3), "compare_x20_ms": round(t_cmp, 3), "over_compare_x20": round(t_reg / t_cmp, 4),
+                                       "rms_first": res.rms[0] if res.rms else None, "rms_last": res.rms[-1] if res.rms else None}
     if cluster:
         # simlod_cluster_samples on A alone at the same radius, with minNeighbours 1 and 8, alternating rep by rep with simlod_compare_samples(A, A) —
         # the yardstick on the same input —; each call's kernels from one call between the library's own events
@@ -1196,6 +1254,7 @@ def main():
     ap.add_argument("--compare-workgroups", type=int, default=0, help="--compare / --compare-whole: SimlodCompareParams.maxWorkgroups (0: the library's choice)")
     ap.add_argument("--surface", action="store_true", help="--compare / --compare-whole: also time simlod_surface_samples on the same arrays at the same radius, alternating with the compare call, with its kernels (the neighbour yardstick is then left out)")
     ap.add_argument("--cluster", action="store_true", help="--compare / --compare-whole: also time simlod_cluster_samples on A alone at the same radius with minNeighbours 1 and 8, alternating with simlod_compare_samples(A, A), with its kernels (the neighbour yardstick is then left out)")
+    ap.add_argument("--align", action="store_true", help="--compare / --compare-whole: also time simlod_align_samples on the same arrays at the same radius under a small motion: a build call and a reuse call beside the compare call, k_a_test beside k_c_test, and a 20-step register_samples beside 20 compare calls")
     ap.add_argument("--compare-radius", type=float, default=None, help="--compare: another radius (heavier cells); the neighbour yardstick is then left out")
     args = ap.parse_args()
     n_points, batch = args.points, abi.MAX_BATCH_SIZE
@@ -1231,7 +1290,7 @@ def main():
         return neighbours_bench(dev, u, box, st, args.reps, pts)
     if args.compare or args.compare_whole:
         return compare_bench(dev, u, box, st, args.reps, pts, whole=args.compare_whole, workgroups=args.compare_workgroups, radius_arg=args.compare_radius,
-                             surface=args.surface, cluster=args.cluster)
+                             surface=args.surface, cluster=args.cluster, align=args.align)
     if args.view:
         return view_bench(dev, u, box, st, args.reps)
     if args.view_delta:
